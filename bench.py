@@ -35,6 +35,34 @@ import torch
 
 PEAK_F32 = 157.3            # TFLOP/s, dense f32 MFMA = f32 vector peak (MI355X_MICROARCH.md)
 PEAK_HBM = 8.0e12           # B/s
+DUMP_CAP_BYTES = 64 << 20   # --dump-outputs: total size of the written arrays
+
+
+def dump_outputs(out_dir, samples, theta, cap=DUMP_CAP_BYTES):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the policy parameters after the update and the
+    samples_data of process_samples (observations, actions, rewards, returns, advantages, agent_infos, valids) -- as float32 / float64 .npy
+    files.  Per-sample arrays share one row selection: all rows when they fit in `cap`, else a fixed (seed 0) sorted sample of rows."""
+    def host(t):
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        return a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+    arrays = {'theta': host(theta), 'log_std': host(samples['agent_infos']['log_std'])}
+    per_sample = {'observations': samples['observations'], 'actions': samples['actions'], 'rewards': samples['rewards'],
+                  'returns': samples['returns'], 'advantages': samples['advantages'], 'mean': samples['agent_infos']['mean'],
+                  'valids': samples['valids']}
+    n = int(per_sample['observations'].shape[0])
+    fixed = sum(a.nbytes for a in arrays.values())
+    row_bytes = sum(max(t.element_size(), 4) * (t.numel() // n) for t in per_sample.values())
+    rows = None
+    if fixed + n * row_bytes > cap:
+        keep = max(1, (cap - fixed) // (row_bytes + 8))      # + the float64 row index written as sample_rows
+        rows = torch.from_numpy(np.sort(np.random.RandomState(0).choice(n, size=keep, replace=False)))
+    for name, t in per_sample.items():
+        arrays[name] = host(t if rows is None else t.index_select(0, rows.to(t.device)))
+    if rows is not None:
+        arrays['sample_rows'] = rows.numpy().astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def flops_per_unit(ns, na, n_drop, dyn_hidden, pol_hidden):
@@ -126,6 +154,9 @@ def main():
     ap.add_argument('--no-strong', action='store_true', help='skip the second (strong-scaling) timed region of a --gpus N > 1 run')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-H', type=int, default=100, help='horizon of the bounded CPU-baseline sample')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed (updated policy parameters + the samples handed to the update) '
+                         'as DIR/<name>.npy (rank 0; at most %d MB, a fixed seeded row sample of larger batches)' % (DUMP_CAP_BYTES >> 20))
     args = ap.parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         self_launch(args)
@@ -226,6 +257,7 @@ def main():
             e1.record(); ev_upd.append((e0, e1))
         if timed:
             steps_run.append(paths.traj.T); n_valid.append(samples['n_valid_global'])
+        return samples
 
     # The host meets the device once per iteration (the line search reads its trial back), so a stop-the-world pass of Python's cyclic
     # collector lands 1:1 on an iteration: one 2.2-2.4 ms iteration in every 20-step run (per-iteration events).  The iteration allocates no
@@ -241,10 +273,13 @@ def main():
     comm.barrier(); torch.cuda.synchronize()
     t0 = time.perf_counter()
     for j in range(args.steps):
-        step(args.warmup + j, True)
+        last_samples = step(args.warmup + j, True)
     algo.optimizer.finish()                                   # the last update's line search is closed inside the timed region
     comm.barrier(); torch.cuda.synchronize()
     dt = comm.max_float(time.perf_counter() - t0, device='cuda' if backend == 'nccl' else 'cpu')
+    if args.dump_outputs and comm.rank == 0:                  # before the instrumented pass overwrites the reused trajectory buffers
+        dump_outputs(args.dump_outputs, last_samples, eng.get_policy())
+        torch.cuda.synchronize()
     # instrumented pass (untimed): the same iterations with HIP events around rollout / update / iteration.  Iterations of tens of ms and more
     # (C2 / C3 / C4) do not feel the events: a few of them are enough
     n_inst = args.steps if dt / args.steps < 0.05 else max(1, min(args.steps, 3))

@@ -59,7 +59,9 @@ def test_edge_vectors_through_fused_rollouts(env, variant):
     running = eng.set_rollout_variant(1 if variant == 'head_per_wave' else 0)
     want = dict(generic=None, head_per_wave=1, coop=2, gemm=3)[variant]
     if want is not None and running != want:
-        pytest.skip('no %s kernel for %s (running variant %d)' % (variant, env, running))
+        # no kernel of that family for this env (Humanoid has neither MFMA rollout form): the engine must fall back to the step-wise GEMM path
+        # or the generic kernel, and the edge rows must come out right through whichever of them runs
+        assert variant in ('coop', 'head_per_wave') and running in (0, 3), 'asked for %s on %s, engine runs variant %d' % (variant, env, running)
     rows = [load_golden('rewards_' + env)]
     xn, u, ref_rew = rows[0]['x_next'], rows[0]['u'], -rows[0]['cost']
     ref_done = np.zeros(len(xn), bool)

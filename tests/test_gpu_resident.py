@@ -32,10 +32,7 @@ def _fields(tr):
                                                ('ant', 5, 100, 10, 6, 'step_rand')])          # params-ant.json network: episodes also end on the state reached
 def test_resident_rollout_against_oracle(env, K, B, T, H, mode, hid):
     """hid = 1024: the 4-wave workgroups of resident_compute_wide (params-half-cheetah / -hopper / -snake.json networks)."""
-    if hid == 1024 and (env, B) in (('swimmer', 128), ('hopper', 1)):
-        pytest.skip('covered at 512')
-    if hid == 512 and env == 'ant':
-        pytest.skip('no 2 x 512 Ant in the kernel table (no params file has one)')
+    resident = not (hid == 512 and env == 'ant')                     # no 2 x 512 Ant in the kernel table (no params file has one)
     eng, dm, theta, pdims, pool = Hh.make_engine(env, K, (hid, hid), (32, 32), seed=61)
     if env == 'ant':                                                 # some envs start near the lower z bound: state-dependent dones inside the call
         pool[::3, 2] = 0.21; dm.diff_mean[2] = -0.02
@@ -45,7 +42,8 @@ def test_resident_rollout_against_oracle(env, K, B, T, H, mode, hid):
     dr = Hh.draws(np.random.RandomState(8), K, B, T, dm.ns, dm.na, len(pool))
     dr32 = {k: (v.astype(np.float32) if v.dtype == np.float64 else v) for k, v in dr.items()}
     traj = eng.rollout(B, T, H, mode, pool, **dr32)
-    assert eng.last_rollout_kernel() == 'resident'
+    # where the table has no resident kernel the engine must pick another one, and that one must pass the same checks
+    assert (eng.last_rollout_kernel() == 'resident') == resident, eng.last_rollout_kernel()
     drf = {k: (v.astype(np.float64) if v.dtype == np.float32 else v) for k, v in dr32.items()}
     ref = Hh.oracle_rollout(dm, th, pdims, env, pool32, drf, B, T, H, mode, teacher_obs=cpu(traj.obs))
     tol = TOL.WIDE                                                   # row 2: 512- / 1024-wide fp32 sums in a fixed, different order
