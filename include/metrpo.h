@@ -369,6 +369,14 @@ typedef struct {
 
 /* sess.run(dynamics_adam_init) (model_based_rl.py:912-918): zero the Adam moments and the step count. */
 int32_t metrpo_dyn_train_reset(metrpo_ctx* ctx, void* stream);
+/* The dynamics optimizer's state (the adam_<scope> slots of model_based_rl.py:154-183, saved by tf.train.Saver() :495):
+ * d_m, d_v [K][dyn_param_count] each, in metrpo_get_dynamics' layout; t = Adam steps taken (the next step uses t + 1).
+ * Before the first train step a get returns zeros and t = 0; a set allocates the state as that step would.  The copies are
+ * asynchronous on `stream` (no device-wide sync); the one exception is a set before the first step, whose one-time
+ * allocation and zero fill (hipMalloc + hipMemset, as in that first step) synchronise.  METRPO_EINVAL for a NULL ctx or
+ * pointer, or t < 0. */
+int32_t metrpo_get_dyn_adam(metrpo_ctx* ctx, float* d_m, float* d_v, int64_t* t_out, void* stream);
+int32_t metrpo_set_dyn_adam(metrpo_ctx* ctx, const float* d_m, const float* d_v, int64_t t, void* stream);
 /* One sess.run([dynamics_opt_op, dynamics_loss]) (model_based_rl.py:961-971; loss graph :39-71; optimizers :154-183).
  * d_x [batch_size*K][ns+na] = (state, action), d_y [batch_size*K][ns] = next state; the block is consumed as the
  * reference's np.reshape(x_batch, (batch_size, -1)) + utils.get_ith_tensor: model i trains on rows i, K+i, 2K+i, ...
@@ -399,6 +407,11 @@ int32_t metrpo_bptt_grad(metrpo_ctx* ctx, const float* d_init, int32_t B, int32_
                          double* d_grad, void* stream);
 /* sess.run(policy_adam_init) (model_based_rl.py:202-204): zero the policy optimizer's moments and step count. */
 int32_t metrpo_policy_adam_reset(metrpo_ctx* ctx, void* stream);
+/* The policy optimizer's state (adam_<policy scope> of get_policy_optimizer, model_based_rl.py:186-204): d_m, d_v [policy_param_count]
+ * each, in metrpo_get_policy's layout (log_std slots included); t as for metrpo_get_dyn_adam.  Same zero-before-first-step,
+ * allocation, stream and status rules as metrpo_get_dyn_adam / metrpo_set_dyn_adam; t must also fit an int32. */
+int32_t metrpo_get_policy_adam(metrpo_ctx* ctx, float* d_m, float* d_v, int64_t* t_out, void* stream);
+int32_t metrpo_set_policy_adam(metrpo_ctx* ctx, const float* d_m, const float* d_v, int64_t t, void* stream);
 /* policy_opt_op (get_policy_optimizer, model_based_rl.py:186-195): tf.clip_by_norm(grad, clip_val) per VARIABLE (W_l, b_l;
  * utils.py:262-276; clip_val <= 0: none) then tf.train.AdamOptimizer(lr).apply_gradients on the ctx policy parameters. */
 int32_t metrpo_policy_adam_step(metrpo_ctx* ctx, const double* d_grad, double lr, double beta1, double beta2, double eps,

@@ -19,6 +19,7 @@ from . import early_stop
 from . import dynamics_training
 from .bptt import BPTT
 from . import formats
+from . import tf_checkpoint
 from .params import from_params, shapes_from_params
 
 __all__ = ['Engine', 'Trajectory', 'xavier_policy_theta', 'Comm', 'NeuralNetEnv', 'VecSimpleEnv', 'InitStatePool',

@@ -115,6 +115,10 @@ SYMBOLS = {
     'metrpo_rollout_note': (C.c_char_p, [_P]),
     'metrpo_policy_adam_reset': (_I, [_P, _P]),
     'metrpo_policy_adam_step': (_I, [_P, _P, _D, _D, _D, _D, _D, _P]),
+    'metrpo_get_dyn_adam': (_I, [_P, _P, _P, C.POINTER(_L), _P]),
+    'metrpo_set_dyn_adam': (_I, [_P, _P, _P, _L, _P]),
+    'metrpo_get_policy_adam': (_I, [_P, _P, _P, C.POINTER(_L), _P]),
+    'metrpo_set_policy_adam': (_I, [_P, _P, _P, _L, _P]),
 }
 # diagnostics hooks exported besides the header's ABI (used by tests to cross-check the two rollout kernels)
 EXTRA_SYMBOLS = {

@@ -542,6 +542,42 @@ extern "C" int32_t metrpo_dyn_train_reset(metrpo_ctx* c, void* stream) {
     return METRPO_OK;
 }
 
+// optimizer state in / out (checkpoints, formats.py): the moments cross the ABI in metrpo_get_dynamics' dense layout, t as the step count
+// the next metrpo_dyn_train_step continues from.  Before the first step the state is zero; a set allocates it as that step would.
+extern "C" int32_t metrpo_get_dyn_adam(metrpo_ctx* c, float* m, float* v, int64_t* t_out, void* stream) {
+    if (!c) return METRPO_EINVAL;
+    if (!m || !v || !t_out) return set_err(c, METRPO_EINVAL, "get_dyn_adam: NULL pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (!c->d_adam) {
+        const size_t n = (size_t)c->pd.K * c->pd.dyn.api_n_params * sizeof(float);
+        HIP_TRY(c, hipMemsetAsync(m, 0, n, st));
+        HIP_TRY(c, hipMemsetAsync(v, 0, n, st));
+        *t_out = 0;
+        return METRPO_OK;
+    }
+    const float* am = (const float*)c->d_adam;
+    repack_dyn(c, am, m, c->pd.K, false, st);
+    repack_dyn(c, am + dyn_adam_floats(c), v, c->pd.K, false, st);
+    HIP_TRY(c, hipGetLastError());
+    *t_out = c->adam_t;
+    return METRPO_OK;
+}
+
+extern "C" int32_t metrpo_set_dyn_adam(metrpo_ctx* c, const float* m, const float* v, int64_t t, void* stream) {
+    if (!c) return METRPO_EINVAL;
+    if (!m || !v) return set_err(c, METRPO_EINVAL, "set_dyn_adam: NULL pointer");
+    if (t < 0) return set_err(c, METRPO_EINVAL, "set_dyn_adam: t < 0");
+    const int rc = ensure_dyn_adam(c);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    float* am = (float*)c->d_adam;
+    repack_dyn(c, m, am, c->pd.K, true, st);                          // the padding slots of the resident layout stay zero
+    repack_dyn(c, v, am + dyn_adam_floats(c), c->pd.K, true, st);
+    HIP_TRY(c, hipGetLastError());
+    c->adam_t = t;
+    return METRPO_OK;
+}
+
 extern "C" int32_t metrpo_dyn_train_step(metrpo_ctx* c, const float* x, const float* y, const metrpo_train_params* tp, double* loss_out,
                                          void* stream) {
     TraceRange trace_("metrpo:dyn_train_step");
@@ -889,6 +925,39 @@ extern "C" int32_t metrpo_bptt_grad(metrpo_ctx* c, const float* init, int32_t B,
 extern "C" int32_t metrpo_policy_adam_reset(metrpo_ctx* c, void* stream) {
     if (!c) return METRPO_ENULL;
     return launch_policy_adam(c, nullptr, 0.0, 0.9, 0.999, 1e-8, 0.0, true, (hipStream_t)stream);
+}
+
+extern "C" int32_t metrpo_get_policy_adam(metrpo_ctx* c, float* m, float* v, int64_t* t_out, void* stream) {
+    if (!c) return METRPO_EINVAL;
+    if (!m || !v || !t_out) return set_err(c, METRPO_EINVAL, "get_policy_adam: NULL pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = sizeof(float) * (size_t)c->pd.P;
+    if (!c->d_pol_adam) {
+        HIP_TRY(c, hipMemsetAsync(m, 0, n, st));
+        HIP_TRY(c, hipMemsetAsync(v, 0, n, st));
+        *t_out = 0;
+        return METRPO_OK;
+    }
+    const float* am = (const float*)c->d_pol_adam;
+    HIP_TRY(c, hipMemcpyAsync(m, am, n, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(v, am + c->pd.P, n, hipMemcpyDeviceToDevice, st));
+    *t_out = c->pol_adam_t;
+    return METRPO_OK;
+}
+
+extern "C" int32_t metrpo_set_policy_adam(metrpo_ctx* c, const float* m, const float* v, int64_t t, void* stream) {
+    if (!c) return METRPO_EINVAL;
+    if (!m || !v) return set_err(c, METRPO_EINVAL, "set_policy_adam: NULL pointer");
+    if (t < 0 || t > INT32_MAX) return set_err(c, METRPO_EINVAL, "set_policy_adam: t outside [0, 2^31)");
+    const int rc = ensure_policy_adam(c);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = sizeof(float) * (size_t)c->pd.P;
+    float* am = (float*)c->d_pol_adam;
+    HIP_TRY(c, hipMemcpyAsync(am, m, n, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(am + c->pd.P, v, n, hipMemcpyDeviceToDevice, st));
+    c->pol_adam_t = (int)t;
+    return METRPO_OK;
 }
 
 extern "C" int32_t metrpo_policy_adam_step(metrpo_ctx* c, const double* grad, double lr, double beta1, double beta2, double eps,

@@ -305,18 +305,25 @@ int launch_bptt_grad(metrpo_ctx* c, const float* init, int B, int T, double gamm
     return METRPO_OK;
 }
 
+// policy optimizer state: m [P] | v [P] | segment table (one clip_by_norm segment per variable) [2L+2] int
+int ensure_policy_adam(metrpo_ctx* c) {
+    if (c->d_pol_adam) return METRPO_OK;
+    const ProblemDesc& pd = c->pd;
+    const int P = pd.P, L = pd.pol.n_layers, nseg = 2 * L + 1;
+    HIP_TRY(c, ws_alloc(c, (void**)&c->d_pol_adam, sizeof(float) * 2 * (size_t)P + sizeof(int) * (nseg + 1)));
+    HIP_TRY(c, hipMemset(c->d_pol_adam, 0, sizeof(float) * 2 * (size_t)P));
+    int seg[2 * MAXL + 2];
+    for (int l = 0; l < L; ++l) { seg[2 * l] = pd.pol.w_off[l]; seg[2 * l + 1] = pd.pol.b_off[l]; }
+    seg[2 * L] = pd.pol.n_params; seg[2 * L + 1] = P;
+    HIP_TRY(c, hipMemcpy((char*)c->d_pol_adam + sizeof(float) * 2 * (size_t)P, seg, sizeof(int) * (nseg + 1), hipMemcpyHostToDevice));
+    c->pol_adam_t = 0;
+    return METRPO_OK;
+}
+
 int launch_policy_adam(metrpo_ctx* c, const double* grad, double lr, double b1, double b2, double eps, double clip_val, bool reset, hipStream_t st) {
     const ProblemDesc& pd = c->pd;
     const int P = pd.P, L = pd.pol.n_layers, nseg = 2 * L + 1;
-    if (!c->d_pol_adam) {
-        HIP_TRY(c, ws_alloc(c, (void**)&c->d_pol_adam, sizeof(float) * 2 * (size_t)P + sizeof(int) * (nseg + 1)));
-        HIP_TRY(c, hipMemset(c->d_pol_adam, 0, sizeof(float) * 2 * (size_t)P));
-        int seg[2 * MAXL + 2];
-        for (int l = 0; l < L; ++l) { seg[2 * l] = pd.pol.w_off[l]; seg[2 * l + 1] = pd.pol.b_off[l]; }
-        seg[2 * L] = pd.pol.n_params; seg[2 * L + 1] = P;
-        HIP_TRY(c, hipMemcpy((char*)c->d_pol_adam + sizeof(float) * 2 * (size_t)P, seg, sizeof(int) * (nseg + 1), hipMemcpyHostToDevice));
-        c->pol_adam_t = 0;
-    }
+    { const int rc = ensure_policy_adam(c); if (rc) return rc; }
     float* am = (float*)c->d_pol_adam; float* av = am + P;
     if (reset) {
         HIP_TRY(c, hipMemsetAsync(am, 0, sizeof(float) * 2 * (size_t)P, st));

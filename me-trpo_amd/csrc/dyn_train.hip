@@ -133,6 +133,17 @@ __global__ void k_adam_apply(int splits, int heads, long long stridePart, const 
     *pw = w - lr_t * m1 / (sqrtf(v1) + eps) - decay * w;
 }
 
+// Adam moments live in their own allocation (they persist across steps and batch sizes): m [K][Pd] | v [K][Pd] | 64 loss accumulators
+size_t dyn_adam_floats(const metrpo_ctx* c) { return (((size_t)c->pd.K * c->pd.dyn.n_params) + 3) & ~(size_t)3; }
+int ensure_dyn_adam(metrpo_ctx* c) {
+    if (c->d_adam) return METRPO_OK;
+    const size_t nP = dyn_adam_floats(c);
+    HIP_TRY(c, ws_alloc(c, (void**)&c->d_adam, 2 * nP * sizeof(float) + 64 * sizeof(double)));
+    HIP_TRY(c, hipMemset(c->d_adam, 0, 2 * nP * sizeof(float) + 64 * sizeof(double)));
+    c->adam_t = 0;
+    return METRPO_OK;
+}
+
 static int ensure_train_ws(metrpo_ctx* c, int rows, TrainWs* ws) {
     const ProblemDesc& pd = c->pd;
     const int K = pd.K, L = pd.dyn.n_layers;
@@ -141,13 +152,8 @@ static int ensure_train_ws(metrpo_ctx* c, int rows, TrainWs* ws) {
     size_t hsum = 0;
     for (int l = 1; l < L; ++l) { maxw = std::max(maxw, pd.dyn.dims[l]); hsum += up4((size_t)K * rows * pd.dyn.dims[l]); }
     const size_t nXn = up4((size_t)K * rows * pd.nin), nOut = up4((size_t)K * rows * pd.ns), nZ = up4((size_t)K * rows * maxw);
-    const size_t nP = up4((size_t)K * pd.dyn.n_params);
-    // Adam moments live in their own allocation (they persist across steps and batch sizes)
-    if (!c->d_adam) {
-        HIP_TRY(c, ws_alloc(c, (void**)&c->d_adam, 2 * nP * sizeof(float) + 64 * sizeof(double)));
-        HIP_TRY(c, hipMemset(c->d_adam, 0, 2 * nP * sizeof(float) + 64 * sizeof(double)));
-        c->adam_t = 0;
-    }
+    const size_t nP = dyn_adam_floats(c);
+    { const int rc = ensure_dyn_adam(c); if (rc) return rc; }
     size_t nPart = 0;
     for (int l = 0; l < L; ++l) {
         const SplitK sk = choose_split(pd.dyn.dims[l], pd.dyn.dims[l + 1], rows, K);

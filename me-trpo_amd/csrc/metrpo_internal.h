@@ -243,6 +243,9 @@ int launch_rollout_gemm(metrpo_ctx*, const metrpo_rollout_args*, hipStream_t);
 int launch_rollout_resident(metrpo_ctx*, const metrpo_rollout_args*, hipStream_t);   // METRPO_EUNSUPPORTED: not a shape / call of the resident kernel
 int launch_bptt_grad(metrpo_ctx*, const float* init, int B, int T, double gamma, double* costs, double* grad, hipStream_t);
 int launch_policy_adam(metrpo_ctx*, const double* grad, double lr, double b1, double b2, double eps, double clip_val, bool reset, hipStream_t);
+int ensure_policy_adam(metrpo_ctx*);                 // bptt.hip: allocate the zeroed policy optimizer state + segment table (first Adam step / reset / set)
+int ensure_dyn_adam(metrpo_ctx*);                    // dyn_train.hip: allocate the zeroed dynamics optimizer state (first train step / set)
+size_t dyn_adam_floats(const metrpo_ctx*);           // floats of ONE moment array in d_adam ([K][Pd] rounded up to 4)
 int det_mfma_select(const metrpo_ctx*);
 int launch_det_forward(metrpo_ctx*, int idx, const float* s0, int B, int T, double gamma, float* XS, float* WT, double* part, double* costs, hipStream_t);
 int launch_det_backward(metrpo_ctx*, int idx, int B, int T, const float* XS, const float* WT, float* GM, hipStream_t);

@@ -567,6 +567,22 @@ class Engine(object):
     def train_reset(self):
         self._chk(lib.metrpo_dyn_train_reset(self._ctx, self._stream()))
 
+    def get_train_adam(self):
+        """-> (m, v [K, dyn_param_count] float32 device tensors, t): the dynamics optimizer's moments in get_dynamics' layout and
+        its step count (zeros and 0 before the first train_step)."""
+        m = torch.empty(self.K, self.dyn_param_count, dtype=torch.float32, device=self.device)
+        v = torch.empty_like(m)
+        t = C.c_int64()
+        self._chk(lib.metrpo_get_dyn_adam(self._ctx, _ptr(m), _ptr(v), C.byref(t), self._stream()))
+        return m, v, int(t.value)
+
+    def set_train_adam(self, m, v, t):
+        """Restore get_train_adam's state: the next train_step continues as if never interrupted."""
+        shape = (self.K, self.dyn_param_count)
+        m = _f32(m, self.device, shape); v = _f32(v, self.device, shape)
+        self._chk(lib.metrpo_set_dyn_adam(self._ctx, _ptr(m), _ptr(v), int(t), self._stream()))
+        torch.cuda.current_stream(self.device).synchronize()     # inputs may be temporaries
+
     def train_step(self, x, y, batch_size, lr, reg_constant=0.0, beta1=0.9, beta2=0.999, eps=1e-8, want_loss=True):
         """x [batch_size*K, ns+na], y [batch_size*K, ns] device tensors; returns per-model losses (before the update)."""
         dev = self.device
@@ -606,6 +622,19 @@ class Engine(object):
 
     def policy_adam_reset(self):
         self._chk(lib.metrpo_policy_adam_reset(self._ctx, self._stream()))
+
+    def get_policy_adam(self):
+        """-> (m, v [P] float32 device tensors, t): the BPTT policy optimizer's moments in get_policy's layout and its step count."""
+        m = torch.empty(self.P, dtype=torch.float32, device=self.device)
+        v = torch.empty_like(m)
+        t = C.c_int64()
+        self._chk(lib.metrpo_get_policy_adam(self._ctx, _ptr(m), _ptr(v), C.byref(t), self._stream()))
+        return m, v, int(t.value)
+
+    def set_policy_adam(self, m, v, t):
+        m = _f32(m, self.device, (self.P,)); v = _f32(v, self.device, (self.P,))
+        self._chk(lib.metrpo_set_policy_adam(self._ctx, _ptr(m), _ptr(v), int(t), self._stream()))
+        torch.cuda.current_stream(self.device).synchronize()
 
     def policy_adam_step(self, grad, lr, clip_val=None, beta1=0.9, beta2=0.999, eps=1e-8):
         g = grad if isinstance(grad, torch.Tensor) else torch.as_tensor(grad)

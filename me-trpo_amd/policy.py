@@ -33,7 +33,11 @@ class GaussianMLPPolicy(object):
         return self.engine.get_policy().double().cpu().numpy()
 
     def set_param_values(self, flat, trainable=True):
-        self.engine.set_policy(np.asarray(flat, dtype=np.float32))
+        """flat: rllab get_param_values order (e.g. the `params` vector of an rllab pickle, formats.load_rllab_policy_pickle)."""
+        flat = np.asarray(flat, dtype=np.float32).reshape(-1)
+        if flat.size != self.engine.P:
+            raise ValueError("set_param_values: %d values for a policy of %d parameters (metrpo_policy_param_count)" % (flat.size, self.engine.P))
+        self.engine.set_policy(flat)
 
     def log_std(self):
         return torch.clamp(self.engine.get_policy()[-self.engine.na:], min=float(np.log(1e-6)))
