@@ -66,7 +66,7 @@ struct CgView { double *gout, *x, *r, *p, *z, *step, *scal, *lk, *ls; };
 static CgView cg_view(metrpo_ctx* c) {
     const int P = c->pd.P;
     CgView v;
-    v.gout = c->d_cg; v.x = v.gout + 1 + P; v.r = v.x + P; v.p = v.r + P; v.z = v.p + P; v.step = v.z + P;
+    v.gout = c->d_cg.p; v.x = v.gout + 1 + P; v.r = v.x + P; v.p = v.r + P; v.z = v.p + P; v.step = v.z + P;
     v.scal = v.step + P; v.lk = v.scal + 8;      // lk directly behind scal[8], ls behind lk: run_trpo_update reads scal | lk | ls back as ONE 14-double copy
     v.ls = v.lk + 2;                             // device-side line-search state (cg_device.h: CgTail::ls)
     return v;
@@ -109,7 +109,7 @@ extern "C" int32_t metrpo_debug_fvp_us(metrpo_ctx* c, double* mean_us, int32_t* 
 }
 
 
-// Diagnostics hook (tests/test_gpu_api.py): outgrown workspaces this context holds back instead of freeing them inside a launch entry point (metrpo_internal.h: ws_retire);
+// Diagnostics hook (tests/test_gpu_api.py): outgrown workspaces this context holds back instead of freeing them inside a launch entry point (metrpo_internal.h: ws_grow);
 // sweep != 0 frees them now (a synchronising call, like the sweep the library runs by itself past WS_RETIRED_MAX).  Returns the count in front of the sweep.
 extern "C" int32_t metrpo_debug_ws_retired(metrpo_ctx* c, unsigned long long* bytes, int32_t sweep) {
     if (!c) return METRPO_ENULL;
@@ -122,9 +122,9 @@ extern "C" int32_t metrpo_debug_ws_retired(metrpo_ctx* c, unsigned long long* by
 // (mlp_persist.h: SkpArgs::stats), 8 values per workgroup; returns the number of workgroups (0: none recorded).
 extern "C" int32_t metrpo_debug_persist_stats(metrpo_ctx* c, unsigned long long* out, int32_t cap_wgs, void* stream) {
     if (!c || !out) return METRPO_ENULL;
-    if (!c->d_skp_stats || c->skp_stats_n == 0) return 0;
+    if (!c->d_skp_stats.p || c->skp_stats_n == 0) return 0;
     const int n = std::min(cap_wgs, c->skp_stats_n);
-    HIP_TRY(c, hipMemcpyAsync(out, c->d_skp_stats, sizeof(unsigned long long) * 8 * n, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(c, hipMemcpyAsync(out, c->d_skp_stats.p, sizeof(unsigned long long) * 8 * n, hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIP_TRY(c, hipStreamSynchronize((hipStream_t)stream));
     return n;
 }
@@ -183,19 +183,12 @@ extern "C" int32_t metrpo_create(metrpo_ctx** out, int32_t device, const metrpo_
     metrpo_ctx* c = new (std::nothrow) metrpo_ctx();
     if (!c) return METRPO_EINVAL;
     c->device = device; c->dims = *d;
-    c->d_dyn = c->d_norm = c->d_theta = nullptr; c->have_dyn = c->have_pol = false;
-    c->d_dyn_img = c->d_pol_img = nullptr; c->pol_img_idx = -1; c->d_pol_imgval = nullptr; c->d_pol_vpos = nullptr; c->img_live = 0;
-    c->d_bptt = nullptr; c->bptt_cap = 0; c->det_cfg = -1; c->d_detpart = nullptr; c->detpart_cap = 0; c->det_gemm = 0; c->d_dg = nullptr; c->dg_cap = 0; c->vjp_gm = nullptr; c->ls_skip = nullptr; c->d_pol_adam = nullptr; c->pol_adam_t = 0; c->mfma_cfg = -1; c->pol_mfma = -1; c->coop_cfg = -1; c->rollout_variant = 0;
-    c->d_partials = nullptr; c->partials_cap = 0; c->d_cg = nullptr; c->d_vf = nullptr; c->d_theta_try = nullptr;
-    c->d_valbuf = nullptr; c->h_pinned = nullptr; c->n_sm = 256; c->n_cu_sched = 0; c->fallback_logged = 0; c->fvp_ev_n = 0; c->fvp_ev_made = 0; c->d_skp_tab = nullptr; c->d_skp_stats = nullptr; c->skp_stats_n = 0; c->skp_tab_cap = 0; c->persist_failed = 0; for (int i = 0; i < 8; ++i) c->skp_key[i] = -1;
     for (int i = 0; i < OPT_COUNT; ++i) {                     // the ONLY place the library reads the environment for kernel selection: defaults of the option table
         const std::string ev = std::string("METRPO_") + metrpo_opt_name(i);
         const char* e = getenv(ev.c_str());
         c->opt_set[i] = (e != nullptr); c->opt_val[i] = e ? e : "";
     }
-    c->exclusive = 1;                                         // until metrpo_set_exclusive(ctx, 0) says otherwise (option NO_RESIDENT is combined with it in ctx_exclusive())
     opt_apply(c, -1);
-    c->d_vbuf = nullptr; c->vbuf_cap = 0; c->d_gae_part = nullptr; c->gae_part_cap = 0; c->d_gram_part = nullptr; c->gram_cap = 0; c->d_big = nullptr; c->big_cap = 0; c->d_res = nullptr; c->res_cap = 0; c->res_seq = 0; c->res_failed = 0; c->last_rollout_kernel = -1; c->upd_pending = 0; c->upd_spec = 0; c->upd_changed_in_end = 0; c->h_upd = nullptr; c->upd_stamp = 0; c->side_ready = 0; c->d_ticket = nullptr; c->d_hcache = nullptr; c->hcache_cap = 0; c->hcache_on = 0; c->d_mig = nullptr; c->mig_cap = 0; c->mig_epoch = 0; c->nccl_comm = nullptr; c->comm_world = 0; c->comm_rank = 0; c->pol_path = 1; c->d_pg = nullptr; c->pg_cap = 0; c->pg_fwd_rows = -1; c->pg_fwd_obs = nullptr; c->pol_f3 = 0; c->d_f3 = nullptr; c->f3_cap = 0; c->f3_rows = -1; c->f3_obs = nullptr; c->f3_theta = nullptr; c->f3_img_ok = 0; c->d_adam = nullptr; c->adam_t = 0; c->d_train = nullptr; c->train_cap = 0; c->d_train_part = nullptr; c->train_part_cap = 0;
     ProblemDesc& pd = c->pd;
     pd.env = d->env; pd.ns = d->ns; pd.na = d->na; pd.K = d->n_models; pd.n_drop = d->n_drop;
     pd.nin = d->ns + d->na - d->n_drop;
@@ -210,26 +203,19 @@ extern "C" int32_t metrpo_create(metrpo_ctx** out, int32_t device, const metrpo_
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_sm = prop.multiProcessorCount;
     const size_t ncg = (size_t)(1 + pd.P) + 5 * (size_t)pd.P + 8 + 2 + 4 + 1;      // ... | scal[8] | lk[2] | ls[4] | validation time-out cell (val_err_cell)
-    if (hipMalloc(&c->d_dyn, sizeof(float) * (size_t)pd.K * pd.dyn.n_params) != hipSuccess ||
-        hipMalloc(&c->d_norm, sizeof(float) * (2 * (pd.ns + pd.na) + 2 * pd.ns)) != hipSuccess ||
-        hipMalloc(&c->d_theta, sizeof(float) * pd.P) != hipSuccess ||
-        hipMalloc(&c->d_vf, sizeof(float) * pd.P) != hipSuccess ||
-        hipMalloc(&c->d_theta_try, sizeof(float) * pd.P) != hipSuccess ||
-        hipMalloc(&c->d_cg, sizeof(double) * ncg) != hipSuccess ||
-        hipMalloc(&c->d_valbuf, sizeof(double) * pd.K) != hipSuccess ||
-        hipMalloc(&c->d_ticket, sizeof(unsigned int)) != hipSuccess ||
-        hipHostMalloc(&c->h_pinned, sizeof(double) * 16) != hipSuccess) {
-        c->err = "device allocation failed";
-        return METRPO_EHIP;
-    }
-    if (hipMemset(c->d_dyn, 0, sizeof(float) * (size_t)pd.K * pd.dyn.n_params) != hipSuccess) { c->err = "hipMemset failed"; return METRPO_EHIP; }
-    if (hipMemset(c->d_cg, 0, sizeof(double) * ncg) != hipSuccess) { c->err = "hipMemset failed"; return METRPO_EHIP; }   // scal[S_COMMERR] starts clear
-    if (hipMemset(c->d_ticket, 0, sizeof(unsigned int)) != hipSuccess) { c->err = "hipMemset failed"; return METRPO_EHIP; }   // the reductions' arrival counter resets itself
+    int rc;
+    if ((rc = ws_grow(c, c->d_dyn, sizeof(float) * (size_t)pd.K * pd.dyn.n_params)) || (rc = ws_grow(c, c->d_norm, sizeof(float) * (2 * (pd.ns + pd.na) + 2 * pd.ns))) ||
+        (rc = ws_grow(c, c->d_theta, sizeof(float) * pd.P)) || (rc = ws_grow(c, c->d_vf, sizeof(float) * pd.P)) || (rc = ws_grow(c, c->d_theta_try, sizeof(float) * pd.P)) ||
+        (rc = ws_grow(c, c->d_cg, sizeof(double) * ncg)) || (rc = ws_grow(c, c->d_valbuf, sizeof(double) * pd.K)) || (rc = ws_grow(c, c->d_ticket, sizeof(unsigned int))))
+        return rc;
+    if (hipHostMalloc(&c->h_pinned, sizeof(double) * 16) != hipSuccess) { c->err = "pinned host allocation failed"; return METRPO_EHIP; }
+    if (hipMemset(c->d_dyn.p, 0, sizeof(float) * (size_t)pd.K * pd.dyn.n_params) != hipSuccess) { c->err = "hipMemset failed"; return METRPO_EHIP; }
+    if (hipMemset(c->d_cg.p, 0, sizeof(double) * ncg) != hipSuccess) { c->err = "hipMemset failed"; return METRPO_EHIP; }   // scal[S_COMMERR] starts clear
+    if (hipMemset(c->d_ticket.p, 0, sizeof(unsigned int)) != hipSuccess) { c->err = "hipMemset failed"; return METRPO_EHIP; }   // the reductions' arrival counter resets itself
     c->mfma_cfg = mfma_select_config(c);
     c->pol_mfma = policy_mfma_select(pd);
     c->pol_f3 = policy_f3_select(pd);
     c->coop_cfg = coop_select_config(c);
-    c->coop_pad_cfg = -1; c->d_dyn_pad = nullptr;
     if (c->coop_cfg < 0 && pd.dyn.n_layers == 3 && pd.dyn.dims[1] <= 64 && pd.dyn.dims[2] <= 64) {      // narrow nets (either width below 64): zero-padded to the fused kernel's 64 x 64
         const int32_t hid64[2] = {64, 64}, acts[2] = {pd.dyn.act[0], pd.dyn.act[1]};
         if (build_net(&c->dyn_pad, pd.nin, hid64, acts, 2, pd.ns, METRPO_ACT_RELU, true)) {
@@ -239,7 +225,7 @@ extern "C" int32_t metrpo_create(metrpo_ctx** out, int32_t device, const metrpo_
             pd.dyn = real;
             if (cfg >= 0) {
                 const size_t bytes = sizeof(float) * (size_t)pd.K * c->dyn_pad.n_params;
-                if (hipMalloc(&c->d_dyn_pad, bytes) != hipSuccess || hipMemset(c->d_dyn_pad, 0, bytes) != hipSuccess) { c->err = "hipMalloc failed (padded dynamics)"; return METRPO_EHIP; }
+                if (ws_grow(c, c->d_dyn_pad, bytes) != METRPO_OK || hipMemset(c->d_dyn_pad.p, 0, bytes) != hipSuccess) { c->err = "hipMalloc failed (padded dynamics)"; return METRPO_EHIP; }
                 c->coop_pad_cfg = cfg;
             }
         }
@@ -247,7 +233,6 @@ extern "C" int32_t metrpo_create(metrpo_ctx** out, int32_t device, const metrpo_
     c->det_cfg = det_mfma_select(c);
     c->det_padded = (c->coop_cfg < 0 && c->coop_pad_cfg >= 0) ? 1 : 0;
     c->det_gemm = det_gemm_applicable(c) ? 1 : 0;
-    c->rollout_variant = 0;
     (void)sched_cus(c, nullptr);                              // CU census here, not inside the first resident / cooperative launch (probe.hip)
     return METRPO_OK;
 }
@@ -257,21 +242,15 @@ extern "C" int32_t metrpo_destroy(metrpo_ctx* c) {
     if (c->nccl_comm) (void)metrpo_comm_destroy(c);
     (void)metrpo_comm_ipc_detach(c);
     if (c->xg_region) (void)hipFree(c->xg_region);
-    void* bufs[] = {c->d_dyn, c->d_norm, c->d_theta, c->d_vf, c->d_theta_try, c->d_cg, c->d_valbuf, c->d_partials,
-                    c->d_dyn_img, c->d_pol_img, c->d_pol_imgval, c->d_pol_vpos, c->d_vbuf, c->d_gae_part, c->d_train_part, c->d_gram_part, c->d_big, c->d_res, c->d_ticket, c->d_hcache, c->d_mig, c->d_pg, c->d_f3, c->d_adam, c->d_train, c->d_bptt, c->d_pol_adam, c->d_detpart, c->d_dg};
-    for (void* p : bufs) if (p) (void)hipFree(p);
     if (c->side_ready) {
         for (int i = 0; i < METRPO_MAX_PAR_ROUNDS - 1; ++i) { (void)hipStreamDestroy(c->side_stream[i]); (void)hipEventDestroy(c->ev_join[i]); }
         (void)hipEventDestroy(c->ev_fork);
     }
     for (int i = 0; i < c->fvp_ev_made; ++i) (void)hipEventDestroy(c->fvp_ev[i]);
     ws_sweep(c);
-    if (c->d_dyn_pad) (void)hipFree(c->d_dyn_pad);
-    if (c->d_skp_tab) (void)hipFree(c->d_skp_tab);
-    if (c->d_skp_stats) (void)hipFree(c->d_skp_stats);
     if (c->h_pinned) (void)hipHostFree(c->h_pinned);
     if (c->h_upd) (void)hipHostFree(c->h_upd);
-    delete c;
+    delete c;                                                 // frees the context's device buffers (DevBuf)
     return METRPO_OK;
 }
 
@@ -286,11 +265,11 @@ extern "C" int32_t metrpo_set_dynamics(metrpo_ctx* c, const float* p, const floa
     hipStream_t st = (hipStream_t)stream;
     const ProblemDesc& pd = c->pd;
     const int nx = pd.ns + pd.na;
-    repack_dyn(c, p, c->d_dyn, pd.K, true, st);
-    HIP_TRY(c, hipMemcpyAsync(c->d_norm, in_mean, sizeof(float) * nx, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->d_norm + nx, in_std, sizeof(float) * nx, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->d_norm + 2 * nx, diff_mean, sizeof(float) * pd.ns, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->d_norm + 2 * nx + pd.ns, diff_std, sizeof(float) * pd.ns, hipMemcpyDeviceToDevice, st));
+    repack_dyn(c, p, c->d_dyn.p, pd.K, true, st);
+    HIP_TRY(c, hipMemcpyAsync(c->d_norm.p, in_mean, sizeof(float) * nx, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_norm.p + nx, in_std, sizeof(float) * nx, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_norm.p + 2 * nx, diff_mean, sizeof(float) * pd.ns, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_norm.p + 2 * nx + pd.ns, diff_std, sizeof(float) * pd.ns, hipMemcpyDeviceToDevice, st));
     c->have_dyn = true;
     if (c->mfma_cfg >= 0) return mfma_prepare_dynamics(c, st);
     return METRPO_OK;
@@ -301,7 +280,7 @@ extern "C" int32_t metrpo_set_policy(metrpo_ctx* c, const float* theta, void* st
     if (!theta) return set_err(c, METRPO_ENULL, "set_policy: NULL pointer");
     if (c->upd_pending) return set_err(c, METRPO_ESTATE, "set_policy: an update begun with metrpo_trpo_update_begin is still open (metrpo_trpo_update_end decides which theta stands)");
     hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(c, hipMemcpyAsync(c->d_theta, theta, sizeof(float) * c->pd.P, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_theta.p, theta, sizeof(float) * c->pd.P, hipMemcpyDeviceToDevice, st));
     c->have_pol = true;
     if (c->mfma_cfg >= 0) return mfma_prepare_policy(c, st);
     return METRPO_OK;
@@ -311,7 +290,7 @@ extern "C" int32_t metrpo_get_policy(metrpo_ctx* c, float* out, void* stream) {
     if (!c) return METRPO_ENULL;
     if (!out) return set_err(c, METRPO_ENULL, "get_policy: NULL pointer");
     if (!c->have_pol) return set_err(c, METRPO_ESTATE, "policy not set");
-    HIP_TRY(c, hipMemcpyAsync(out, c->d_theta, sizeof(float) * c->pd.P, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIP_TRY(c, hipMemcpyAsync(out, c->d_theta.p, sizeof(float) * c->pd.P, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return METRPO_OK;
 }
 
@@ -535,9 +514,9 @@ extern "C" int32_t metrpo_loss_kl(metrpo_ctx* c, const metrpo_batch* b, const fl
 extern "C" int32_t metrpo_dyn_train_reset(metrpo_ctx* c, void* stream) {
     if (!c) return METRPO_ENULL;
     c->adam_t = 0;
-    if (c->d_adam) {
+    if (c->d_adam.p) {
         const size_t nP = (((size_t)c->pd.K * c->pd.dyn.n_params) + 3) & ~(size_t)3;
-        HIP_TRY(c, hipMemsetAsync(c->d_adam, 0, 2 * nP * sizeof(float), (hipStream_t)stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_adam.p, 0, 2 * nP * sizeof(float), (hipStream_t)stream));
     }
     return METRPO_OK;
 }
@@ -548,14 +527,14 @@ extern "C" int32_t metrpo_get_dyn_adam(metrpo_ctx* c, float* m, float* v, int64_
     if (!c) return METRPO_EINVAL;
     if (!m || !v || !t_out) return set_err(c, METRPO_EINVAL, "get_dyn_adam: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
-    if (!c->d_adam) {
+    if (!c->d_adam.p) {
         const size_t n = (size_t)c->pd.K * c->pd.dyn.api_n_params * sizeof(float);
         HIP_TRY(c, hipMemsetAsync(m, 0, n, st));
         HIP_TRY(c, hipMemsetAsync(v, 0, n, st));
         *t_out = 0;
         return METRPO_OK;
     }
-    const float* am = (const float*)c->d_adam;
+    const float* am = (const float*)c->d_adam.p;
     repack_dyn(c, am, m, c->pd.K, false, st);
     repack_dyn(c, am + dyn_adam_floats(c), v, c->pd.K, false, st);
     HIP_TRY(c, hipGetLastError());
@@ -570,7 +549,7 @@ extern "C" int32_t metrpo_set_dyn_adam(metrpo_ctx* c, const float* m, const floa
     const int rc = ensure_dyn_adam(c);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    float* am = (float*)c->d_adam;
+    float* am = (float*)c->d_adam.p;
     repack_dyn(c, m, am, c->pd.K, true, st);                          // the padding slots of the resident layout stay zero
     repack_dyn(c, v, am + dyn_adam_floats(c), c->pd.K, true, st);
     HIP_TRY(c, hipGetLastError());
@@ -601,7 +580,7 @@ extern "C" int32_t metrpo_get_dynamics(metrpo_ctx* c, float* out, void* stream) 
     if (!c) return METRPO_ENULL;
     NEED_DYN(c);
     if (!out) return set_err(c, METRPO_ENULL, "get_dynamics: NULL pointer");
-    repack_dyn(c, c->d_dyn, out, c->pd.K, false, (hipStream_t)stream);
+    repack_dyn(c, c->d_dyn.p, out, c->pd.K, false, (hipStream_t)stream);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
 }
@@ -611,7 +590,7 @@ extern "C" int32_t metrpo_set_dynamics_model(metrpo_ctx* c, int32_t model, const
     NEED_DYN(c);
     if (!p) return set_err(c, METRPO_ENULL, "set_dynamics_model: NULL pointer");
     if (model < 0 || model >= c->pd.K) return set_err(c, METRPO_EINVAL, "set_dynamics_model: model index out of range");
-    repack_dyn(c, p, c->d_dyn + (size_t)model * c->pd.dyn.n_params, 1, true, (hipStream_t)stream);
+    repack_dyn(c, p, c->d_dyn.p + (size_t)model * c->pd.dyn.n_params, 1, true, (hipStream_t)stream);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
 }
@@ -622,10 +601,10 @@ extern "C" int32_t metrpo_set_normalizers(metrpo_ctx* c, const float* in_mean, c
     if (!in_mean || !in_std || !diff_mean || !diff_std) return set_err(c, METRPO_ENULL, "set_normalizers: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
     const int nx = c->pd.ns + c->pd.na, ns = c->pd.ns;
-    HIP_TRY(c, hipMemcpyAsync(c->d_norm, in_mean, sizeof(float) * nx, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->d_norm + nx, in_std, sizeof(float) * nx, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->d_norm + 2 * nx, diff_mean, sizeof(float) * ns, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->d_norm + 2 * nx + ns, diff_std, sizeof(float) * ns, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_norm.p, in_mean, sizeof(float) * nx, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_norm.p + nx, in_std, sizeof(float) * nx, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_norm.p + 2 * nx, diff_mean, sizeof(float) * ns, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_norm.p + 2 * nx + ns, diff_std, sizeof(float) * ns, hipMemcpyDeviceToDevice, st));
     return METRPO_OK;
 }
 
@@ -690,7 +669,7 @@ int run_trpo_update(metrpo_ctx* c, const metrpo_batch* b, const metrpo_trpo_para
                     double* g_out, double* dir_out, hipStream_t st, int phase, int spec) {
     const int rc = run_trpo_update_impl(c, b, pr, diag, g_out, dir_out, st, phase, spec);
     if (rc != METRPO_OK) {
-        (void)hipGetLastError(); (void)hipMemsetAsync(c->d_ticket, 0, sizeof(unsigned int), st); c->upd_pending = 0;
+        (void)hipGetLastError(); (void)hipMemsetAsync(c->d_ticket.p, 0, sizeof(unsigned int), st); c->upd_pending = 0;
     }
     return rc;
 }
@@ -725,7 +704,7 @@ static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metr
     struct FuseOff { metrpo_ctx* c; ~FuseOff() { c->xg_fuse = 0; } } fuse_off{c};
     const int implicit_hd = pr->explicit_final_hvp ? 0 : 1;
     CgTail tl; tl.pub_dst = nullptr; tl.pub_stamp = 0; tl.P = P; tl.last = 0; tl.implicit_hd = implicit_hd; tl.reg = pr->reg_coeff; tl.tol = pr->residual_tol; tl.max_kl = pr->max_kl;
-    tl.x = v.x; tl.r = v.r; tl.p = v.p; tl.z = v.z; tl.step = v.step; tl.scal = v.scal; tl.gout = v.gout; tl.pf = c->d_vf; tl.ticket = c->d_ticket;
+    tl.x = v.x; tl.r = v.r; tl.p = v.p; tl.z = v.z; tl.step = v.step; tl.scal = v.scal; tl.gout = v.gout; tl.pf = c->d_vf.p; tl.ticket = c->d_ticket.p;
     tl.vpos = nullptr; tl.imgval = nullptr; tl.ls = nullptr; tl.lk = nullptr; tl.th = nullptr; tl.th_try = nullptr; tl.trial = 0; tl.accept_violation = 0;
     const int nspec = std::min(spec, (int)pr->max_backtracks);
     // Device-decided line search (phase 1): theta of trial 0 is built by the tail that finishes the step size, theta of trial n + 1 by trial n's accept test
@@ -740,33 +719,33 @@ static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metr
     struct CacheOff { metrpo_ctx* c; ~CacheOff() { c->hcache_on = 0; c->img_live = 0; } } cache_off{c};
     if (c->img_live) {
         if ((rc = policy_mfma_image_buffers(c))) return rc;
-        tl.vpos = c->d_pol_vpos; tl.imgval = c->d_pol_imgval;
+        tl.vpos = c->d_pol_vpos.p; tl.imgval = c->d_pol_imgval.p;
     }
     if ((rc = launch_loss_grad(c, b, v.gout, st, fused ? &tl : nullptr))) return rc;
     if (!fused) {
         AR(v.gout, 1 + P);
-        hipLaunchKernelGGL(k_cg_init, dim3(1), dim3(1024), 0, st, P, v.gout, v.x, v.r, v.p, c->d_vf, v.scal);   // same block shape as the fused tail: identical summation order
+        hipLaunchKernelGGL(k_cg_init, dim3(1), dim3(1024), 0, st, P, v.gout, v.x, v.r, v.p, c->d_vf.p, v.scal);   // same block shape as the fused tail: identical summation order
     }
     if (pr->cg_iters == 0) {
-        hipLaunchKernelGGL(k_zero_f, dim3((P + 255) / 256), dim3(256), 0, st, c->d_vf, P);
+        hipLaunchKernelGGL(k_zero_f, dim3((P + 255) / 256), dim3(256), 0, st, c->d_vf.p, P);
         hipLaunchKernelGGL(k_cg_finish_implicit, dim3(1), dim3(1024), 0, st, P, pr->max_kl, v.x, v.r, v.gout, v.step, v.scal);
     }
     const bool fold_try = (phase == 1 && nspec >= 1);
-    auto arm_try0 = [&]() { tl.nx_try = c->d_theta_try; tl.nx_prev = c->d_theta; tl.nx_ratio = 1.0; tl.nx_ls = v.ls; try0_built = true; };      // backtrack_ratio ^ 0
+    auto arm_try0 = [&]() { tl.nx_try = c->d_theta_try.p; tl.nx_prev = c->d_theta.p; tl.nx_ratio = 1.0; tl.nx_ls = v.ls; try0_built = true; };      // backtrack_ratio ^ 0
     for (int i = 0; i < pr->cg_iters; ++i) {
         tl.op = 1; tl.last = (i == pr->cg_iters - 1) ? 1 : 0;
         if (fold_try && tl.last && implicit_hd) arm_try0();
-        if (fused) { if ((rc = launch_fvp_tail(c, b, c->d_vf, v.p, v.z, &tl, st))) return rc; continue; }
-        if ((rc = launch_fvp_f32(c, b, c->d_vf, v.p, v.z, st))) return rc;
+        if (fused) { if ((rc = launch_fvp_tail(c, b, c->d_vf.p, v.p, v.z, &tl, st))) return rc; continue; }
+        if ((rc = launch_fvp_f32(c, b, c->d_vf.p, v.p, v.z, st))) return rc;
         AR(v.z, P);
         hipLaunchKernelGGL(k_cg_step, dim3(1), dim3(1024), 0, st, tl, pr->cg_iters);
     }
     if (!implicit_hd && pr->cg_iters > 0) {                      // rllab's literal route: one more f_Hx on the descent direction
         tl.op = 2; tl.last = 0;
         if (fused && fold_try) arm_try0();
-        if (fused) { if ((rc = launch_fvp_tail(c, b, c->d_vf, v.x, v.z, &tl, st))) return rc; }
+        if (fused) { if ((rc = launch_fvp_tail(c, b, c->d_vf.p, v.x, v.z, &tl, st))) return rc; }
         else {
-            if ((rc = launch_fvp_f32(c, b, c->d_vf, v.x, v.z, st))) return rc;
+            if ((rc = launch_fvp_f32(c, b, c->d_vf.p, v.x, v.z, st))) return rc;
             AR(v.z, P);
             hipLaunchKernelGGL(k_cg_finish, dim3(1), dim3(1024), 0, st, P, pr->reg_coeff, pr->max_kl, v.x, v.z, v.step, v.scal);
         }
@@ -785,12 +764,12 @@ static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metr
             const double ratio = std::pow(pr->backtrack_ratio, (double)n);
             // trial 0 opens the search (ls reset rides in its k_try_theta), the last trial's reduction publishes the outcome: no launches of their own
             if (n == 0 && !try0_built)
-                hipLaunchKernelGGL(k_try_theta, dim3((P + 255) / 256), dim3(256), 0, st, P, ratio, c->d_theta, v.step, c->d_theta_try, (const double*)nullptr, v.ls);
+                hipLaunchKernelGGL(k_try_theta, dim3((P + 255) / 256), dim3(256), 0, st, P, ratio, c->d_theta.p, v.step, c->d_theta_try.p, (const double*)nullptr, v.ls);
             CgTail dt = tl;
-            if (n + 1 < nspec) { dt.nx_try = c->d_theta_try; dt.nx_prev = c->d_theta; dt.nx_ratio = std::pow(pr->backtrack_ratio, (double)(n + 1)); dt.nx_ls = nullptr; }
-            dt.op = 4; dt.ls = v.ls; dt.lk = v.lk; dt.th = c->d_theta; dt.th_try = c->d_theta_try; dt.trial = n; dt.accept_violation = pr->accept_violation;
+            if (n + 1 < nspec) { dt.nx_try = c->d_theta_try.p; dt.nx_prev = c->d_theta.p; dt.nx_ratio = std::pow(pr->backtrack_ratio, (double)(n + 1)); dt.nx_ls = nullptr; }
+            dt.op = 4; dt.ls = v.ls; dt.lk = v.lk; dt.th = c->d_theta.p; dt.th_try = c->d_theta_try.p; dt.trial = n; dt.accept_violation = pr->accept_violation;
             if (n == nspec - 1) { dt.pub_dst = c->h_upd; dt.pub_stamp = c->upd_stamp; }
-            if ((rc = launch_loss_kl(c, b, c->d_theta_try, v.lk, st, &dt))) return rc;
+            if ((rc = launch_loss_kl(c, b, c->d_theta_try.p, v.lk, st, &dt))) return rc;
         }
         if (c->mfma_cfg >= 0 && (rc = mfma_prepare_policy(c, st))) return rc;      // of whatever theta the trials left in place
         if (nspec == 0) hipLaunchKernelGGL(k_ls_publish, dim3(1), dim3(64), 0, st, (const double*)v.scal, c->h_upd, c->upd_stamp);
@@ -826,8 +805,8 @@ static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metr
     for (int n = n_start; n < pr->max_backtracks && !stopped; ++n) {
         n_iter = n;
         const double ratio = std::pow(pr->backtrack_ratio, (double)n);
-        hipLaunchKernelGGL(k_try_theta, dim3((P + 255) / 256), dim3(256), 0, st, P, ratio, c->d_theta, v.step, c->d_theta_try, (const double*)nullptr, (double*)nullptr);
-        if ((rc = launch_loss_kl(c, b, c->d_theta_try, v.lk, st))) return rc;
+        hipLaunchKernelGGL(k_try_theta, dim3((P + 255) / 256), dim3(256), 0, st, P, ratio, c->d_theta.p, v.step, c->d_theta_try.p, (const double*)nullptr, (double*)nullptr);
+        if ((rc = launch_loss_kl(c, b, c->d_theta_try.p, v.lk, st))) return rc;
         AR(v.lk, 2);
         HIP_TRY(c, hipMemcpyAsync(c->h_pinned, v.scal, sizeof(double) * 10, hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipStreamSynchronize(st));
@@ -845,7 +824,7 @@ static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metr
     if ((std::isnan(loss) || std::isnan(kl) || loss >= loss_before || kl >= pr->max_kl) && !pr->accept_violation) accepted = false;
     if (stopped) accepted = taken;                               // decided on the device: an accepted trial's theta is already the policy
     else if (accepted) {
-        std::swap(c->d_theta, c->d_theta_try);               // both ctx-owned, every launch takes c->d_theta afresh: no copy
+        std::swap(c->d_theta.p, c->d_theta_try.p);               // both ctx-owned and of one size, every launch takes c->d_theta afresh: no copy
         if (c->mfma_cfg >= 0 && (rc = mfma_prepare_policy(c, st))) return rc;
         c->upd_changed_in_end = (phase == 2) ? 1 : 0;        // theta changed on the HOST side of a two-half update: work enqueued after _begin used theta_prev
     }
@@ -932,13 +911,13 @@ extern "C" int32_t metrpo_get_policy_adam(metrpo_ctx* c, float* m, float* v, int
     if (!m || !v || !t_out) return set_err(c, METRPO_EINVAL, "get_policy_adam: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
     const size_t n = sizeof(float) * (size_t)c->pd.P;
-    if (!c->d_pol_adam) {
+    if (!c->d_pol_adam.p) {
         HIP_TRY(c, hipMemsetAsync(m, 0, n, st));
         HIP_TRY(c, hipMemsetAsync(v, 0, n, st));
         *t_out = 0;
         return METRPO_OK;
     }
-    const float* am = (const float*)c->d_pol_adam;
+    const float* am = (const float*)c->d_pol_adam.p;
     HIP_TRY(c, hipMemcpyAsync(m, am, n, hipMemcpyDeviceToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(v, am + c->pd.P, n, hipMemcpyDeviceToDevice, st));
     *t_out = c->pol_adam_t;
@@ -953,7 +932,7 @@ extern "C" int32_t metrpo_set_policy_adam(metrpo_ctx* c, const float* m, const f
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t n = sizeof(float) * (size_t)c->pd.P;
-    float* am = (float*)c->d_pol_adam;
+    float* am = (float*)c->d_pol_adam.p;
     HIP_TRY(c, hipMemcpyAsync(am, m, n, hipMemcpyDeviceToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(am + c->pd.P, v, n, hipMemcpyDeviceToDevice, st));
     c->pol_adam_t = (int)t;

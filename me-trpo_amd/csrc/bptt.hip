@@ -252,17 +252,12 @@ int launch_bptt_grad(metrpo_ctx* c, const float* init, int B, int T, double gamm
                  nGM = (((size_t)K * (T + 1) * B * na) + 3) & ~(size_t)3;
     const size_t need = (nXS + nWT + nGM) * sizeof(float) + sizeof(double) * (size_t)(pd.P + 1 + K);
     if (c->det_cfg >= 0) { const int rc0 = ensure_detpart(c, B); if (rc0) return rc0; }
-    if (need > c->bptt_cap) {
-        ws_retire(c, c->d_bptt);
-        c->d_bptt = nullptr; c->bptt_cap = 0;
-        HIP_TRY(c, ws_alloc(c, (void**)&c->d_bptt, need));
-        c->bptt_cap = need;
-    }
-    float* XS = (float*)c->d_bptt; float* WT = XS + nXS; float* GM = WT + nWT;
+    { const int rc = ws_grow(c, c->d_bptt, need); if (rc) return rc; }
+    float* XS = (float*)c->d_bptt.p; float* WT = XS + nXS; float* GM = WT + nWT;
     double* gout = (double*)(GM + nGM); double* cst = gout + pd.P + 1;
     HIP_TRY(c, hipMemsetAsync(GM, 0, sizeof(float) * nGM, st));
     if (c->det_cfg >= 0) {                                   // MFMA sweeps (bptt_mfma.hip)
-        int rc1 = launch_det_forward(c, c->det_cfg, init, B, T, gamma, XS, WT, c->d_detpart, cst, st);
+        int rc1 = launch_det_forward(c, c->det_cfg, init, B, T, gamma, XS, WT, c->d_detpart.p, cst, st);
         if (rc1) return rc1;
         if ((rc1 = launch_det_backward(c, c->det_cfg, B, T, XS, WT, GM, st))) return rc1;
         const int rc2 = launch_policy_vjp(c, XS, GM, (long long)K * (T + 1) * B, gout, st);
@@ -293,9 +288,9 @@ int launch_bptt_grad(metrpo_ctx* c, const float* init, int B, int T, double gamm
     }
     const dim3 grid((B + bs - 1) / bs, K);
     { const int rcp = ensure_detpart_n(c, (size_t)K * grid.x); if (rcp) return rcp; }
-    hipLaunchKernelGGL(k_bptt_forward, grid, dim3(bs), sh, st, pd, c->d_dyn, c->d_theta, c->d_norm, init, B, T, gamma, XS, WT, c->d_detpart);
-    { const int rcp = launch_det_cost_reduce(c, (int)grid.x, c->d_detpart, cst, st); if (rcp) return rcp; }
-    hipLaunchKernelGGL(k_bptt_backward, grid, dim3(bs), sh, st, pd, c->d_dyn, c->d_theta, c->d_norm, B, T, XS, WT, GM);
+    hipLaunchKernelGGL(k_bptt_forward, grid, dim3(bs), sh, st, pd, c->d_dyn.p, c->d_theta.p, c->d_norm.p, init, B, T, gamma, XS, WT, c->d_detpart.p);
+    { const int rcp = launch_det_cost_reduce(c, (int)grid.x, c->d_detpart.p, cst, st); if (rcp) return rcp; }
+    hipLaunchKernelGGL(k_bptt_backward, grid, dim3(bs), sh, st, pd, c->d_dyn.p, c->d_theta.p, c->d_norm.p, B, T, XS, WT, GM);
     HIP_TRY(c, hipGetLastError());
     // policy-parameter gradient: sum over the K (T+1) B samples of J(x)^T gm  (gradient kernels of the TRPO update, mean-adjoint supplied)
     const int rc = launch_policy_vjp(c, XS, GM, (long long)K * (T + 1) * B, gout, st);
@@ -307,15 +302,15 @@ int launch_bptt_grad(metrpo_ctx* c, const float* init, int B, int T, double gamm
 
 // policy optimizer state: m [P] | v [P] | segment table (one clip_by_norm segment per variable) [2L+2] int
 int ensure_policy_adam(metrpo_ctx* c) {
-    if (c->d_pol_adam) return METRPO_OK;
     const ProblemDesc& pd = c->pd;
     const int P = pd.P, L = pd.pol.n_layers, nseg = 2 * L + 1;
-    HIP_TRY(c, ws_alloc(c, (void**)&c->d_pol_adam, sizeof(float) * 2 * (size_t)P + sizeof(int) * (nseg + 1)));
-    HIP_TRY(c, hipMemset(c->d_pol_adam, 0, sizeof(float) * 2 * (size_t)P));
+    bool grew = false;
+    { const int rc = ws_grow(c, c->d_pol_adam, sizeof(float) * 2 * (size_t)P + sizeof(int) * (nseg + 1), &grew); if (rc || !grew) return rc; }
+    HIP_TRY(c, hipMemset(c->d_pol_adam.p, 0, sizeof(float) * 2 * (size_t)P));
     int seg[2 * MAXL + 2];
     for (int l = 0; l < L; ++l) { seg[2 * l] = pd.pol.w_off[l]; seg[2 * l + 1] = pd.pol.b_off[l]; }
     seg[2 * L] = pd.pol.n_params; seg[2 * L + 1] = P;
-    HIP_TRY(c, hipMemcpy((char*)c->d_pol_adam + sizeof(float) * 2 * (size_t)P, seg, sizeof(int) * (nseg + 1), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy((char*)c->d_pol_adam.p + sizeof(float) * 2 * (size_t)P, seg, sizeof(int) * (nseg + 1), hipMemcpyHostToDevice));
     c->pol_adam_t = 0;
     return METRPO_OK;
 }
@@ -324,7 +319,7 @@ int launch_policy_adam(metrpo_ctx* c, const double* grad, double lr, double b1, 
     const ProblemDesc& pd = c->pd;
     const int P = pd.P, L = pd.pol.n_layers, nseg = 2 * L + 1;
     { const int rc = ensure_policy_adam(c); if (rc) return rc; }
-    float* am = (float*)c->d_pol_adam; float* av = am + P;
+    float* am = (float*)c->d_pol_adam.p; float* av = am + P;
     if (reset) {
         HIP_TRY(c, hipMemsetAsync(am, 0, sizeof(float) * 2 * (size_t)P, st));
         c->pol_adam_t = 0;
@@ -332,7 +327,7 @@ int launch_policy_adam(metrpo_ctx* c, const double* grad, double lr, double b1, 
     }
     c->pol_adam_t += 1;
     const double lr_t = lr * std::sqrt(1.0 - std::pow(b2, (double)c->pol_adam_t)) / (1.0 - std::pow(b1, (double)c->pol_adam_t));
-    hipLaunchKernelGGL(k_policy_adam, dim3(nseg), dim3(256), 0, st, nseg, (const int*)(av + P), grad, c->d_theta, am, av, (float)lr_t, (float)b1,
+    hipLaunchKernelGGL(k_policy_adam, dim3(nseg), dim3(256), 0, st, nseg, (const int*)(av + P), grad, c->d_theta.p, am, av, (float)lr_t, (float)b1,
                        (float)b2, (float)eps, clip_val);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
@@ -341,11 +336,5 @@ int launch_policy_adam(metrpo_ctx* c, const double* grad, double lr, double b1, 
 int ensure_detpart(metrpo_ctx* c, int B) { return ensure_detpart_n(c, (size_t)c->pd.K * (size_t)(4 * ((B + 63) / 64))); }
 int ensure_detpart_n(metrpo_ctx* c, size_t n_doubles) {
     const size_t need = sizeof(double) * n_doubles;
-    if (need > c->detpart_cap) {
-        ws_retire(c, c->d_detpart);
-        c->d_detpart = nullptr; c->detpart_cap = 0;
-        HIP_TRY(c, ws_alloc(c, (void**)&c->d_detpart, need));
-        c->detpart_cap = need;
-    }
-    return METRPO_OK;
+    return ws_grow(c, c->d_detpart, need);
 }

@@ -424,9 +424,9 @@ int launch_det_forward(metrpo_ctx* c, int idx, const float* s0, int B, int T, do
     const size_t sh = sizeof(float) * (size_t)en.lds_floats;
     if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)en.fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
     const int gx = (B + 63) / 64;
-    const float* dyn = c->d_dyn;
-    if (c->det_padded) { const int rc = launch_pad_dyn(c, st); if (rc) return rc; dyn = c->d_dyn_pad; }
-    hipLaunchKernelGGL(en.fwd, dim3(gx, c->pd.K), dim3(256), sh, st, c->pd.K, B, T, gamma, dyn, c->d_theta, c->d_norm, s0, XS, WT,
+    const float* dyn = c->d_dyn.p;
+    if (c->det_padded) { const int rc = launch_pad_dyn(c, st); if (rc) return rc; dyn = c->d_dyn_pad.p; }
+    hipLaunchKernelGGL(en.fwd, dim3(gx, c->pd.K), dim3(256), sh, st, c->pd.K, B, T, gamma, dyn, c->d_theta.p, c->d_norm.p, s0, XS, WT,
                        (float*)nullptr, part);
     hipLaunchKernelGGL(k_det_cost_reduce, dim3(c->pd.K), dim3(64), 0, st, gx * 4, part, costs, (const double*)nullptr);
     HIP_TRY(c, hipGetLastError());
@@ -437,9 +437,9 @@ int launch_det_backward(metrpo_ctx* c, int idx, int B, int T, const float* XS, c
     const DetEntry& en = kDet[idx];
     const size_t sh = sizeof(float) * (size_t)en.lds_floats;
     if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)en.bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-    const float* dyn = c->d_dyn;
-    if (c->det_padded) { const int rc = launch_pad_dyn(c, st); if (rc) return rc; dyn = c->d_dyn_pad; }
-    hipLaunchKernelGGL(en.bwd, dim3((B + 63) / 64, c->pd.K), dim3(256), sh, st, c->pd.K, B, T, 1.0, dyn, c->d_theta, c->d_norm,
+    const float* dyn = c->d_dyn.p;
+    if (c->det_padded) { const int rc = launch_pad_dyn(c, st); if (rc) return rc; dyn = c->d_dyn_pad.p; }
+    hipLaunchKernelGGL(en.bwd, dim3((B + 63) / 64, c->pd.K), dim3(256), sh, st, c->pd.K, B, T, 1.0, dyn, c->d_theta.p, c->d_norm.p,
                        (const float*)nullptr, const_cast<float*>(XS), const_cast<float*>(WT), GM, (double*)nullptr);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;

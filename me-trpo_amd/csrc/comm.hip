@@ -195,7 +195,7 @@ extern "C" int32_t metrpo_comm_ipc_detach(metrpo_ctx* c) {
     c->xg_world = 0; c->xg_rank = 0; c->xg_fuse = 0;
     // The time-out cell of the exchanges is sticky by design; it must not outlive the transport that raised it: 'auto' mode detaches after a
     // timed-out test exchange and goes on over RCCL or the caller's callback, and every later update of this context would report that old time-out.
-    if (c->d_cg) {
+    if (c->d_cg.p) {
         (void)hipSetDevice(c->device);
         (void)hipMemset(comm_err_cell(c), 0, sizeof(double));
         (void)hipDeviceSynchronize();

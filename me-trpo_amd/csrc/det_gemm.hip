@@ -409,13 +409,8 @@ static int dg_workspace(metrpo_ctx* c, int B, DgState* s) {
     if (const int ft = dg_fuse_tile(c, B)) nP = std::max(nP, up4(gemm_fused_out_part_floats(B, pd.dyn.dims[L - 1], K, pd.ns, ft)));
     const size_t nPimg = up4((size_t)pre_mfma3_image_floats<55, 21, 100, 50, 25>());     // the one three-hidden-layer policy with an MFMA pre-step (dg_pre_mfma_select): 67 KB
     const size_t need = (4 * nS + nX + 2 * nU + nH + 2 * nZ + nD + nP + nPimg) * sizeof(float) + R * sizeof(double) + 64;
-    if (need > c->dg_cap) {
-        ws_retire(c, c->d_dg);
-        c->d_dg = nullptr; c->dg_cap = 0;
-        HIP_TRY(c, ws_alloc(c, (void**)&c->d_dg, need));
-        c->dg_cap = need;
-    }
-    float* p = (float*)c->d_dg;
+    { const int rc = ws_grow(c, c->d_dg, need); if (rc) return rc; }
+    float* p = (float*)c->d_dg.p;
     s->S = p; p += nS; s->OUT = p; p += nS; s->G = p; p += nS; s->LAM = p; p += nS; s->X = p; p += nX; s->U = p; p += nU; s->MU = p; p += nU;
     for (int l = 1; l < L; ++l) { s->H[l - 1] = p; p += up4(R * pd.dyn.dims[l]); }
     s->DZa = p; p += nZ; s->DZb = p; p += nZ; s->DONES = p; p += nD; s->PART = nP ? p : nullptr; p += nP; s->PIMG = p; p += nPimg;
@@ -427,16 +422,16 @@ static void dg_forward_layers(metrpo_ctx* c, DgState& s, int B, int n_layers_to_
     const ProblemDesc& pd = c->pd;
     const int K = pd.K, L = pd.dyn.n_layers;
     const float* in = s.X; int ldin = pd.nin;
-    s.out_splits = 0; s.out_stride = 0; s.out_bias = c->d_dyn + pd.dyn.b_off[L - 1]; s.out_bias_stride = pd.dyn.n_params;
+    s.out_splits = 0; s.out_stride = 0; s.out_bias = c->d_dyn.p + pd.dyn.b_off[L - 1]; s.out_bias_stride = pd.dyn.n_params;
     const int fuse_tile = (defer_out && n_layers_to_run == L) ? dg_fuse_tile(c, B) : 0;
     for (int l = 0; l < n_layers_to_run; ++l) {
         const int Kd = pd.dyn.dims[l], N = pd.dyn.dims[l + 1];
         float* out = (l == L - 1) ? s.OUT : s.H[l];
         GemmEpi ep = {};
-        ep.bias = c->d_dyn + pd.dyn.b_off[l]; ep.strideBias = pd.dyn.n_params;
-        const float* Wl = c->d_dyn + pd.dyn.w_off[l];
+        ep.bias = c->d_dyn.p + pd.dyn.b_off[l]; ep.strideBias = pd.dyn.n_params;
+        const float* Wl = c->d_dyn.p + pd.dyn.w_off[l];
         if (fuse_tile && l == L - 2) {
-            gemm_relu_fused_out(fuse_tile, in, (long long)B * Kd, ldin, Wl, pd.dyn.n_params, N, ep.bias, ep.strideBias, c->d_dyn + pd.dyn.w_off[L - 1],
+            gemm_relu_fused_out(fuse_tile, in, (long long)B * Kd, ldin, Wl, pd.dyn.n_params, N, ep.bias, ep.strideBias, c->d_dyn.p + pd.dyn.w_off[L - 1],
                                 pd.dyn.n_params, pd.ns, B, N, Kd, K, s.PART, st, &s.out_splits, &s.out_stride);
             break;
         }
@@ -469,14 +464,14 @@ int launch_dg_forward(metrpo_ctx* c, const float* s0, int B, int T, double gamma
     size_t pre_lds = 0;
     const dg_pre_mfma_t pre_mfma = dg_pre_mfma_select(c, &pre_lds);
     if (pre_lds) {
-        hipLaunchKernelGGL((k_pre_mfma3_image<55, 21, 100, 50, 25>), dim3((unsigned)((P3<55, 21, 100, 50, 25>::IMG + 255) / 256)), dim3(256), 0, st, c->d_theta, s.PIMG);
+        hipLaunchKernelGGL((k_pre_mfma3_image<55, 21, 100, 50, 25>), dim3((unsigned)((P3<55, 21, 100, 50, 25>::IMG + 255) / 256)), dim3(256), 0, st, c->d_theta.p, s.PIMG);
         if (pre_lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)pre_mfma, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pre_lds));
     }
     for (int t = 0; t < T; ++t) {
-        if (pre_mfma) hipLaunchKernelGGL(pre_mfma, dim3((B + 63) / 64, K), dim3(256), pre_lds, st, pd, B, c->d_theta, c->d_norm, (const float*)nullptr, 0LL, s);
-        else hipLaunchKernelGGL(k_dg_pre, dim3((B + pbs - 1) / pbs, K), dim3(pbs), psh, st, pd, B, c->d_theta, c->d_norm, (const float*)nullptr, 0LL, s);
+        if (pre_mfma) hipLaunchKernelGGL(pre_mfma, dim3((B + 63) / 64, K), dim3(256), pre_lds, st, pd, B, c->d_theta.p, c->d_norm.p, (const float*)nullptr, 0LL, s);
+        else hipLaunchKernelGGL(k_dg_pre, dim3((B + pbs - 1) / pbs, K), dim3(pbs), psh, st, pd, B, c->d_theta.p, c->d_norm.p, (const float*)nullptr, 0LL, s);
         dg_forward_layers(c, s, B, L, true, st);
-        hipLaunchKernelGGL(k_dg_post, dim3((B + DG_POST_ROWS - 1) / DG_POST_ROWS, K), dim3(DG_POST_THREADS), 0, st, pd, B, T, t, g, c->d_norm, s, XS, WT);
+        hipLaunchKernelGGL(k_dg_post, dim3((B + DG_POST_ROWS - 1) / DG_POST_ROWS, K), dim3(DG_POST_THREADS), 0, st, pd, B, T, t, g, c->d_norm.p, s, XS, WT);
         g *= gamma;
     }
     hipLaunchKernelGGL(k_dg_costs, dim3(K), dim3(256), 0, st, B, s.ACC, costs);
@@ -503,19 +498,19 @@ int launch_dg_backward(metrpo_ctx* c, int B, int T, const float* XS, const float
     size_t pre_lds = 0;
     const dg_pre_mfma_t pre_mfma = dg_pre_mfma_select(c, &pre_lds);
     if (pre_lds) {
-        hipLaunchKernelGGL((k_pre_mfma3_image<55, 21, 100, 50, 25>), dim3((unsigned)((P3<55, 21, 100, 50, 25>::IMG + 255) / 256)), dim3(256), 0, st, c->d_theta, s.PIMG);
+        hipLaunchKernelGGL((k_pre_mfma3_image<55, 21, 100, 50, 25>), dim3((unsigned)((P3<55, 21, 100, 50, 25>::IMG + 255) / 256)), dim3(256), 0, st, c->d_theta.p, s.PIMG);
         if (pre_lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)pre_mfma, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pre_lds));
     }
     for (int t = T - 1; t >= 0; --t) {
-        if (pre_mfma) hipLaunchKernelGGL(pre_mfma, dim3((B + 63) / 64, K), dim3(256), pre_lds, st, pd, B, c->d_theta, c->d_norm, XS + (size_t)t * B * pd.ns, xs_model, s);
-        else hipLaunchKernelGGL(k_dg_pre, dim3((B + pbs - 1) / pbs, K), dim3(pbs), psh, st, pd, B, c->d_theta, c->d_norm,
+        if (pre_mfma) hipLaunchKernelGGL(pre_mfma, dim3((B + 63) / 64, K), dim3(256), pre_lds, st, pd, B, c->d_theta.p, c->d_norm.p, XS + (size_t)t * B * pd.ns, xs_model, s);
+        else hipLaunchKernelGGL(k_dg_pre, dim3((B + pbs - 1) / pbs, K), dim3(pbs), psh, st, pd, B, c->d_theta.p, c->d_norm.p,
                                 XS + (size_t)t * B * pd.ns, xs_model, s);
         dg_forward_layers(c, s, B, L - 1, false, st);                             // hidden activations only
-        hipLaunchKernelGGL(k_dg_mid, dim3((B + 127) / 128, K), dim3(128), 0, st, pd, B, T, t, c->d_norm, XS, WT, s);
+        hipLaunchKernelGGL(k_dg_mid, dim3((B + 127) / 128, K), dim3(128), 0, st, pd, B, T, t, c->d_norm.p, XS, WT, s);
         float* dz = s.DZa; float* dzn = s.DZb;
         for (int l = L - 1; l >= 0; --l) {
             const int n_in = pd.dyn.dims[l], n_out = pd.dyn.dims[l + 1];
-            const float* Wl = c->d_dyn + pd.dyn.w_off[l];
+            const float* Wl = c->d_dyn.p + pd.dyn.w_off[l];
             GemmEpi ep = {};
             if (l > 0) {
                 ep.mask = s.H[l - 1]; ep.strideMask = (long long)B * n_in; ep.ldm = n_in;
@@ -527,7 +522,7 @@ int launch_dg_backward(metrpo_ctx* c, int B, int T, const float* XS, const float
             }
             float* tmp = dz; dz = dzn; dzn = tmp;
         }
-        hipLaunchKernelGGL(k_dg_back, dim3((B + pbs - 1) / pbs, K), dim3(pbs), bsh, st, pd, B, T, t, c->d_theta, c->d_norm, XS, WT, dz, s, GM);
+        hipLaunchKernelGGL(k_dg_back, dim3((B + pbs - 1) / pbs, K), dim3(pbs), bsh, st, pd, B, T, t, c->d_theta.p, c->d_norm.p, XS, WT, dz, s, GM);
     }
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;

@@ -136,10 +136,10 @@ __global__ void k_adam_apply(int splits, int heads, long long stridePart, const 
 // Adam moments live in their own allocation (they persist across steps and batch sizes): m [K][Pd] | v [K][Pd] | 64 loss accumulators
 size_t dyn_adam_floats(const metrpo_ctx* c) { return (((size_t)c->pd.K * c->pd.dyn.n_params) + 3) & ~(size_t)3; }
 int ensure_dyn_adam(metrpo_ctx* c) {
-    if (c->d_adam) return METRPO_OK;
     const size_t nP = dyn_adam_floats(c);
-    HIP_TRY(c, ws_alloc(c, (void**)&c->d_adam, 2 * nP * sizeof(float) + 64 * sizeof(double)));
-    HIP_TRY(c, hipMemset(c->d_adam, 0, 2 * nP * sizeof(float) + 64 * sizeof(double)));
+    bool grew = false;
+    { const int rc = ws_grow(c, c->d_adam, 2 * nP * sizeof(float) + 64 * sizeof(double), &grew); if (rc || !grew) return rc; }
+    HIP_TRY(c, hipMemset(c->d_adam.p, 0, 2 * nP * sizeof(float) + 64 * sizeof(double)));
     c->adam_t = 0;
     return METRPO_OK;
 }
@@ -161,28 +161,18 @@ static int ensure_train_ws(metrpo_ctx* c, int rows, TrainWs* ws) {
     }
     nPart = std::max(nPart, skinny_part_floats(rows, pd.ns, pd.dyn.dims[L - 1], K));      // forward output layer (train_forward)
     const size_t need = (nXn + hsum + nOut + 2 * nZ + nPart) * sizeof(float);
-    if (need > c->train_cap) {
-        ws_retire(c, c->d_train);
-        c->d_train = nullptr; c->train_cap = 0;
-        HIP_TRY(c, ws_alloc(c, (void**)&c->d_train, need));
-        c->train_cap = need;
-    }
+    { const int rc = ws_grow(c, c->d_train, need); if (rc) return rc; }
     const size_t nLp = (size_t)K * (1 + (size_t)(rows + 127) / 128);
-    if (nLp > c->train_part_cap) {
-        ws_retire(c, c->d_train_part);
-        c->d_train_part = nullptr; c->train_part_cap = 0;
-        const size_t cap = std::max<size_t>(nLp, 2048);
-        HIP_TRY(c, ws_alloc(c, (void**)&c->d_train_part, cap * sizeof(double)));
-        HIP_TRY(c, hipMemset(c->d_train_part, 0, cap * sizeof(double)));          // tickets start at zero; every launch leaves them there
-        c->train_part_cap = cap;
-    }
-    ws->lpart = c->d_train_part;
-    float* p = (float*)c->d_train;
+    bool grew = false;
+    { const int rc = ws_grow(c, c->d_train_part, std::max<size_t>(nLp, 2048) * sizeof(double), &grew); if (rc) return rc; }
+    if (grew) HIP_TRY(c, hipMemset(c->d_train_part.p, 0, c->d_train_part.bytes));          // tickets start at zero; every launch leaves them there
+    ws->lpart = c->d_train_part.p;
+    float* p = (float*)c->d_train.p;
     ws->Xn = p; p += nXn;
     for (int l = 1; l < L; ++l) { ws->H[l] = p; p += up4((size_t)K * rows * pd.dyn.dims[l]); }
     ws->H[0] = ws->Xn;
     ws->OUT = p; p += nOut; ws->dZa = p; p += nZ; ws->dZb = p; p += nZ; ws->part = p;
-    ws->am = (float*)c->d_adam; ws->av = ws->am + nP; ws->loss = (double*)(ws->av + nP);
+    ws->am = (float*)c->d_adam.p; ws->av = ws->am + nP; ws->loss = (double*)(ws->av + nP);
     ws->rows = rows;
     return METRPO_OK;
 }
@@ -195,8 +185,8 @@ static void train_forward(metrpo_ctx* c, const TrainWs& ws, int rows, hipStream_
         const int Kd = pd.dyn.dims[l], N = pd.dyn.dims[l + 1];
         float* out = (l == L - 1) ? ws.OUT : ws.H[l + 1];
         GemmEpi ep = {};
-        ep.bias = c->d_dyn + pd.dyn.b_off[l]; ep.strideBias = pd.dyn.n_params;
-        const float* Wl = c->d_dyn + pd.dyn.w_off[l];
+        ep.bias = c->d_dyn.p + pd.dyn.b_off[l]; ep.strideBias = pd.dyn.n_params;
+        const float* Wl = c->d_dyn.p + pd.dyn.w_off[l];
         // output layer (ns <= 64 columns, contraction over the hidden width): split-K partials + ordered reduce where that pays (gemm_skinny_bias; one
         // 64-column tile per 64 rows walks the whole K axis on a fifth of the CUs: 25.8 us of a 210 us step at 2 x 512, batch 1000)
         if (l == L - 1) gemm_skinny_bias(ws.H[l], (long long)rows * Kd, Kd, Wl, pd.dyn.n_params, N, ep.bias, ep.strideBias, out, (long long)rows * N, rows, N, Kd, K, ws.part, st);
@@ -217,12 +207,12 @@ int launch_dyn_train_step(metrpo_ctx* c, const float* x, const float* y, const m
     HIP_TRY(c, hipMemsetAsync(ws.loss, 0, sizeof(double) * (K + 1), st));
     {
         const long long total = (long long)K * rows * pd.nin;
-        hipLaunchKernelGGL(k_train_prep, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, pd, c->d_norm, x, n_rows, rows, 0, ws.Xn);
+        hipLaunchKernelGGL(k_train_prep, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, pd, c->d_norm.p, x, n_rows, rows, 0, ws.Xn);
     }
     train_forward(c, ws, rows, st);
-    hipLaunchKernelGGL(k_train_out, dim3((rows + 127) / 128, K), dim3(128), 0, st, pd, c->d_norm, x, y, n_rows, rows, 0, 1.0 / (double)rows,
+    hipLaunchKernelGGL(k_train_out, dim3((rows + 127) / 128, K), dim3(128), 0, st, pd, c->d_norm.p, x, y, n_rows, rows, 0, 1.0 / (double)rows,
                        ws.OUT, ws.dZa, ws.loss, ws.lpart);
-    if (tp->reg_constant != 0.0) hipLaunchKernelGGL(k_reg_loss, dim3(K), dim3(256), 0, st, pd.dyn.n_params, c->d_dyn, tp->reg_constant, ws.loss);
+    if (tp->reg_constant != 0.0) hipLaunchKernelGGL(k_reg_loss, dim3(K), dim3(256), 0, st, pd.dyn.n_params, c->d_dyn.p, tp->reg_constant, ws.loss);
     // Adam step (tf.train.AdamOptimizer: lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t), epsilon outside the correction)
     c->adam_t += 1;
     const double lr_t = tp->lr * std::sqrt(1.0 - std::pow(tp->beta2, (double)c->adam_t)) / (1.0 - std::pow(tp->beta1, (double)c->adam_t));
@@ -230,7 +220,7 @@ int launch_dyn_train_step(metrpo_ctx* c, const float* x, const float* y, const m
     float* dz = ws.dZa; float* dz_next = ws.dZb;
     for (int l = L - 1; l >= 0; --l) {
         const int n_in = pd.dyn.dims[l], n_out = pd.dyn.dims[l + 1];
-        float* Wl = c->d_dyn + pd.dyn.w_off[l];
+        float* Wl = c->d_dyn.p + pd.dyn.w_off[l];
         if (l > 0) {            // dH_{l-1} = dZ_l . W_l^T, masked by relu'(H_{l-1})  -- uses W_l BEFORE its update
             GemmEpi ep = {};
             ep.mask = ws.H[l]; ep.strideMask = (long long)rows * n_in; ep.ldm = n_in;
@@ -240,7 +230,7 @@ int launch_dyn_train_step(metrpo_ctx* c, const float* x, const float* y, const m
         {                       // dW_l = H_{l-1}^T . dZ_l with the Adam update as epilogue (W_l updated in place)
             GemmEpi ep = {};
             ep.am = ws.am + pd.dyn.w_off[l]; ep.av = ws.av + pd.dyn.w_off[l]; ep.strideAdam = pd.dyn.n_params;
-            ep.bvec = c->d_dyn + pd.dyn.b_off[l]; ep.bam = ws.am + pd.dyn.b_off[l]; ep.bav = ws.av + pd.dyn.b_off[l];   // b_l: column sums of dZ_l
+            ep.bvec = c->d_dyn.p + pd.dyn.b_off[l]; ep.bam = ws.am + pd.dyn.b_off[l]; ep.bav = ws.av + pd.dyn.b_off[l];   // b_l: column sums of dZ_l
             ep.lr_t = (float)lr_t; ep.beta1 = (float)tp->beta1; ep.beta2 = (float)tp->beta2; ep.eps = (float)tp->eps; ep.decay = decay;
             const SplitK sk = choose_split(n_in, n_out, rows, K);
             if (sk.splits > 1) {
@@ -273,13 +263,13 @@ int launch_dyn_eval_losses(metrpo_ctx* c, const float* x, const float* y, long l
     for (long long r0 = 0; r0 < n; r0 += CH) {
         const int rows = (int)std::min<long long>(CH, n - r0);
         const long long total = (long long)K * rows * pd.nin;
-        hipLaunchKernelGGL(k_train_prep, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, pd, c->d_norm, x + r0 * (pd.ns + pd.na), n - r0,
+        hipLaunchKernelGGL(k_train_prep, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, pd, c->d_norm.p, x + r0 * (pd.ns + pd.na), n - r0,
                            rows, 1, ws.Xn);
         train_forward(c, ws, rows, st);
-        hipLaunchKernelGGL(k_train_out, dim3((rows + 127) / 128, K), dim3(128), 0, st, pd, c->d_norm, x + r0 * (pd.ns + pd.na), y + r0 * pd.ns,
+        hipLaunchKernelGGL(k_train_out, dim3((rows + 127) / 128, K), dim3(128), 0, st, pd, c->d_norm.p, x + r0 * (pd.ns + pd.na), y + r0 * pd.ns,
                            n - r0, rows, 1, 1.0 / (double)n, ws.OUT, (float*)nullptr, ws.loss, ws.lpart);
     }
-    if (reg_constant != 0.0) hipLaunchKernelGGL(k_reg_loss, dim3(K), dim3(256), 0, st, pd.dyn.n_params, c->d_dyn, reg_constant, ws.loss);
+    if (reg_constant != 0.0) hipLaunchKernelGGL(k_reg_loss, dim3(K), dim3(256), 0, st, pd.dyn.n_params, c->d_dyn.p, reg_constant, ws.loss);
     HIP_TRY(c, hipMemcpyAsync(losses, ws.loss, sizeof(double) * K, hipMemcpyDeviceToDevice, st));
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;

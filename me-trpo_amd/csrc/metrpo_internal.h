@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <string>
 #include <atomic>
+#include <utility>
 #include <vector>
 #include "metrpo.h"
 #include "xchg_device.h"
@@ -44,93 +45,100 @@ enum MetrpoOpt {
     OPT_COUNT
 };
 
+// One device allocation owned by a context: freed (hipFree) when the context is deleted, bytes = its size (0: none).  Not copyable -- a copy
+// would be a second owner, and a kernel argument taken by value would be the wrapper rather than the pointer -- and deliberately without
+// a conversion to T*: every use names .p.  Grown only by ws_grow below.
+template <class T> struct DevBuf {
+    T* p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
 struct metrpo_ctx {
-    int device;
-    metrpo_dims dims;
-    ProblemDesc pd;
-    float* d_dyn;        // [K][dyn.n_params]
-    float* d_norm;       // 2*(ns+na) + 2*ns
-    float* d_theta;      // [P]
-    bool have_dyn, have_pol;
-    // --- MFMA fast path (rollout_mfma.hip): pre-permuted weight images, built by set_* ---
-    float* d_dyn_img;    // per-model register image, see rollout_mfma.hip
-    float* d_pol_img;    // (int32 payload) gather map of the policy weight-fragment image, see policy_mfma.hip
-    int pol_img_idx;     // table index the map was built for (-1: none)
+    int device = 0;
+    metrpo_dims dims = {};
+    ProblemDesc pd = {};
+    DevBuf<float> d_dyn;     // [K][dyn.n_params]
+    DevBuf<float> d_norm;    // 2*(ns+na) + 2*ns
+    DevBuf<float> d_theta;   // [P]
+    bool have_dyn = false, have_pol = false;
+    // --- MFMA fast path: pre-permuted weight images, built by set_* ---
+    DevBuf<float> d_pol_img; // (int32 payload) gather map of the policy weight-fragment image, see policy_mfma.hip
+    int pol_img_idx = -1;    // table index the map was built for (-1: none)
     // image VALUES of one CG solve (policy_mfma.hip): [weight entries of theta, written by the gradient kernel's block 0 | tangent entries of the
     // current CG vector, written by the fused CG tails through d_pol_vpos (theta index -> image position, -1: none)].  img_live is raised by
     // run_trpo_update while both writers are on the launch sequence; the cached-activation FVP then copies the image instead of gathering it.
-    float* d_pol_imgval; int* d_pol_vpos; int img_live;
+    DevBuf<float> d_pol_imgval; DevBuf<int> d_pol_vpos; int img_live = 0;
     // --- BPTT (bptt.hip) ---
-    void* d_bptt; size_t bptt_cap;      // XS | WT | GM | gout | costs
-    const float* vjp_gm;                // set around the VJP launch of the gradient kernels
-    const double* ls_skip;              // set around a speculative line-search evaluation (PolK::skip of the fused MFMA kernels)
-    void* d_pol_adam; int pol_adam_t;   // Adam moments of the policy parameters + segment table
-    int det_cfg;                        // bptt_mfma.hip table index (-1: generic sweeps / generic validation kernel)
-    double* d_detpart; size_t detpart_cap;   // per-tile cost partials of the MFMA forward sweep
-    int det_gemm;                       // 1: GEMM-path sweeps (det_gemm.hip) for large dynamics nets
-    void* d_dg; size_t dg_cap;          // workspace of the GEMM-path sweeps
-    int mfma_cfg;        // index into the instantiation table, -1 = generic path only
-    int pol_mfma;        // index into policy_mfma.hip's table, -1 = generic update kernels
-    int coop_cfg;        // index into rollout_coop.hip's table, -1 = head-per-wave kernel (rollout_mfma.hip)
+    DevBuf<void> d_bptt;                      // XS | WT | GM | gout | costs
+    const float* vjp_gm = nullptr;            // set around the VJP launch of the gradient kernels
+    const double* ls_skip = nullptr;          // set around a speculative line-search evaluation (PolK::skip of the fused MFMA kernels)
+    DevBuf<void> d_pol_adam; int pol_adam_t = 0;   // Adam moments of the policy parameters + segment table
+    int det_cfg = -1;                         // bptt_mfma.hip table index (-1: generic sweeps / generic validation kernel)
+    DevBuf<double> d_detpart;                 // per-tile cost partials of the MFMA forward sweep
+    int det_gemm = 0;                         // 1: GEMM-path sweeps (det_gemm.hip) for large dynamics nets
+    DevBuf<void> d_dg;                        // workspace of the GEMM-path sweeps
+    int mfma_cfg = -1;       // index into the instantiation table, -1 = generic path only
+    int pol_mfma = -1;       // index into policy_mfma.hip's table, -1 = generic update kernels
+    int coop_cfg = -1;       // index into rollout_coop.hip's table, -1 = head-per-wave kernel (rollout_mfma.hip)
     // two hidden layers of at most 64 units each, not both 64 (round 6): the cooperative kernel on a zero-padded copy of the weights in the 64 x 64 layout (padded units: zero weights and
     // bias -> relu(0) = 0 -> they add exact zeros); the copy is rebuilt from d_dyn in front of every rollout launch (one small kernel: no tracking of who wrote d_dyn)
-    int coop_pad_cfg; float* d_dyn_pad; NetDesc dyn_pad;
-    int det_padded;      // the validation-cost / BPTT sweeps of bptt_mfma.hip run on the same padded copy
-    int rollout_variant; // test hook: 0 = fastest available, 1 = head-per-wave MFMA kernel
+    int coop_pad_cfg = -1; DevBuf<float> d_dyn_pad; NetDesc dyn_pad = {};
+    int det_padded = 0;      // the validation-cost / BPTT sweeps of bptt_mfma.hip run on the same padded copy
+    int rollout_variant = 0; // test hook: 0 = fastest available, 1 = head-per-wave MFMA kernel
     // --- workspaces for the update path (lazily sized) ---
-    float* d_partials;   // [n_blocks][P+2] per-block partial sums
-    size_t partials_cap;
-    double* d_cg;        // CG vectors + scalars, see trpo_update.hip
-    float* d_vf;         // [P] float copy of the FVP input
-    float* d_theta_try;  // [P] line-search candidate
-    double* d_valbuf;    // validation-cost accumulators
-    double* d_vbuf;      // [N] baseline predictions for the GAE scan
-    double* d_gae_part; size_t gae_part_cap;   // k_gae: arrival ticket + one (sum adv, sum adv^2, count) triple per workgroup, added in workgroup order
-    size_t vbuf_cap;
-    double* d_gram_part; // per-block Gram partials (process.hip)
-    size_t gram_cap;
-    unsigned int* d_ticket; // arrival counter of k_finalize's fused CG tail
-    float* d_hcache; size_t hcache_cap; int hcache_on;   // activation cache of one CG solve (policy_mfma.hip MODE_FVPC)
-    void* d_mig; int mig_cap, mig_epoch;            // rollout_coop.hip: hand-over slots of migrating tiles (flag | ts | model | obs per tile)
-    void* nccl_comm; int comm_world, comm_rank;   // comm.hip: RCCL communicator attached by metrpo_comm_init (NULL: single rank)
+    DevBuf<float> d_partials;      // [n_blocks][P+2] per-block partial sums
+    DevBuf<double> d_cg;           // CG vectors + scalars, see trpo_update.hip
+    DevBuf<float> d_vf;            // [P] float copy of the FVP input
+    DevBuf<float> d_theta_try;     // [P] line-search candidate
+    DevBuf<double> d_valbuf;       // validation-cost accumulators
+    DevBuf<double> d_vbuf;         // [N] baseline predictions for the GAE scan
+    DevBuf<double> d_gae_part;     // k_gae: arrival ticket + one (sum adv, sum adv^2, count) triple per workgroup, added in workgroup order
+    DevBuf<double> d_gram_part;    // per-block Gram partials (process.hip)
+    DevBuf<unsigned int> d_ticket; // arrival counter of k_finalize's fused CG tail
+    DevBuf<float> d_hcache; int hcache_on = 0;    // activation cache of one CG solve (policy_mfma.hip MODE_FVPC)
+    DevBuf<void> d_mig; int mig_epoch = 0;        // rollout_coop.hip: hand-over slots of migrating tiles (flag | ts | model | obs per tile)
+    void* nccl_comm = nullptr; int comm_world = 0, comm_rank = 0;   // comm.hip: RCCL communicator attached by metrpo_comm_init (NULL: single rank)
     // comm.hip: one-shot direct all-reduce (xchg_device.h).  xg_region = this rank's receive region (IPC-exported), xg_peer[q] = rank q's
     // region as mapped here; xg_seq counts the exchanges issued so far (identical on every rank: SPMD); xg_fuse is raised by
     // run_trpo_update while the reductions of the update kernels carry the exchange in their own tail
-    void* xg_region; void* xg_peer[XCHG_MAX_WORLD]; int xg_world, xg_rank, xg_cap, xg_fuse; unsigned int xg_seq; unsigned long long xg_timeout;
-    int pol_path;        // 1 auto (fused MFMA kernels where the shape has them, GEMM path for large N otherwise), 0 generic forced, 2 GEMM path forced
-    void* d_pg; size_t pg_cap; long long pg_fwd_rows; const float* pg_fwd_obs;   // policy_gemm.hip workspace + validity of its cached forward pass
-    int pol_f3;          // 1: fused MFMA update kernels for three-hidden-layer policies (policy_fused3.hip) serve this shape
-    void* d_f3; size_t f3_cap; long long f3_rows; const float* f3_obs; const float* f3_theta; int f3_img_ok;   // policy_fused3.hip: activation cache + mean-adjoint of one (theta, batch) and its validity
-    void* d_adam;        // Adam moments [2][K][Pd] + loss accumulators (dyn_train.hip)
-    long long adam_t;    // Adam step count
-    void* d_train;       // training activation workspace
-    double* d_train_part; size_t train_part_cap;   // k_train_out: per-model arrival tickets + per-workgroup loss sums (added in workgroup order)
-    size_t train_cap;
-    void* d_big;         // workspace of the GEMM step-wise rollout (rollout_gemm.hip)
-    size_t big_cap;
-    void* d_res; size_t res_cap; unsigned int res_seq;   // rollout_resident.hip: uncached exchange region (abort cell | X packets | P packets) and the step stamps issued so far
-    unsigned long long* d_skp_stats; int skp_stats_n;   // option PERSIST_STATS: per-workgroup statistics of the last persistent launch (metrpo_debug_persist_stats)
+    void* xg_region = nullptr; void* xg_peer[XCHG_MAX_WORLD] = {}; int xg_world = 0, xg_rank = 0, xg_cap = 0, xg_fuse = 0; unsigned int xg_seq = 0; unsigned long long xg_timeout = 0;
+    int pol_path = 1;        // 1 auto (fused MFMA kernels where the shape has them, GEMM path for large N otherwise), 0 generic forced, 2 GEMM path forced
+    DevBuf<void> d_pg; long long pg_fwd_rows = -1; const float* pg_fwd_obs = nullptr;   // policy_gemm.hip workspace + validity of its cached forward pass
+    int pol_f3 = 0;          // 1: fused MFMA update kernels for three-hidden-layer policies (policy_fused3.hip) serve this shape
+    DevBuf<void> d_f3; long long f3_rows = -1; const float* f3_obs = nullptr; const float* f3_theta = nullptr; int f3_img_ok = 0;   // policy_fused3.hip: activation cache + mean-adjoint of one (theta, batch) and its validity
+    DevBuf<void> d_adam;     // Adam moments [2][K][Pd] + loss accumulators (dyn_train.hip)
+    long long adam_t = 0;    // Adam step count
+    DevBuf<void> d_train;    // training activation workspace
+    DevBuf<double> d_train_part;   // k_train_out: per-model arrival tickets + per-workgroup loss sums (added in workgroup order)
+    DevBuf<void> d_big;      // workspace of the GEMM step-wise rollout (rollout_gemm.hip)
+    DevBuf<void> d_res; unsigned int res_seq = 0;   // rollout_resident.hip: uncached exchange region (abort cell | X packets | P packets) and the step stamps issued so far
+    DevBuf<unsigned long long> d_skp_stats; int skp_stats_n = 0;   // option PERSIST_STATS: per-workgroup statistics of the last persistent launch (metrpo_debug_persist_stats) | its workgroup count
     std::vector<int> skp_tab_host;                    // host copy of the table below, as raw 32-bit words (source of its asynchronous upload; SkRec: mlp_streamk.h)
-    void* d_skp_tab; size_t skp_tab_cap; long long skp_key[8]; int skp_Jx[8], skp_Jmax, skp_L, skp_NSL; int persist_failed;   // mlp_persist.h: cached chunk-record table of the persistent stream-K rollout (key: the launch's shape) | a persistent launch timed out
-    int res_failed;                                       // a resident launch gave up (its grid was not co-resident): this context stays on the step-wise path from then on
-    int last_rollout_kernel;
+    DevBuf<void> d_skp_tab; long long skp_key[8] = {-1, -1, -1, -1, -1, -1, -1, -1}; int skp_Jx[8] = {}, skp_Jmax = 0, skp_L = 0, skp_NSL = 0; int persist_failed = 0;   // mlp_persist.h: cached chunk-record table of the persistent stream-K rollout (key: the launch's shape) | a persistent launch timed out
+    int res_failed = 0;                                   // a resident launch gave up (its grid was not co-resident): this context stays on the step-wise path from then on
+    int last_rollout_kernel = -1;                         // which kernel family the last metrpo_rollout ran on: 0 generic, 1 head-per-wave MFMA, 2 cooperative MFMA, 3 step-wise GEMM, 4 resident
     // metrpo_trpo_update_begin / _end: an update whose line search is still undecided on the host
     // metrpo_trpo_update_begin's outcome lands in pinned host memory straight from its last kernel (k_ls_publish: scal | lk | ls, then a
     // stamp); _end polls the stamp (no copy engine, no event, no blocking wait to wake up from).  Publishing from a side stream behind a device-scope
     // event was measured too: the second queue costs the update 35 us, more than the 15 us gap in front of the next rollout it removes.
-    double* h_upd; unsigned long long upd_stamp;
-    int upd_pending, upd_spec, upd_changed_in_end; metrpo_batch upd_batch; metrpo_trpo_params upd_params; metrpo_trpo_diag upd_diag;                              // which kernel family the last metrpo_rollout ran on: 0 generic, 1 head-per-wave MFMA, 2 cooperative MFMA, 3 step-wise GEMM, 4 resident
-    hipStream_t side_stream[METRPO_MAX_PAR_ROUNDS - 1]; hipEvent_t ev_fork, ev_join[METRPO_MAX_PAR_ROUNDS - 1]; int side_ready;   // rollout_gemm.hip: independent rounds of a small-batch rollout run concurrently
-    double* h_pinned;    // pinned host scratch for the per-trial read-back
-    int n_sm;            // CU count (device property)
-    int upd_tiles_per_wave;   // MFMA update kernels: at least this many 16-sample tiles per wave before another block is added (1; the option that set it was retired in round 6: experiments/upd_small.py)
-    int n_cu_sched;      // CUs that actually ran this process's waves (probe.hip: census; 0 = not measured yet)
-    int exclusive;       // the caller's metrpo_set_exclusive value (1 at metrpo_create); 0: the GPU is shared with other compute processes.  Read through ctx_exclusive(), which also honours option NO_RESIDENT
-    std::string opt_val[OPT_COUNT]; bool opt_set[OPT_COUNT];   // METRPO_OPT_LIST: set by metrpo_create from the environment, then only by metrpo_set_option
-    hipEvent_t fvp_ev[32]; int fvp_ev_n, fvp_ev_made;   // option TIME_FVP: events around the Fisher-vector-product kernel of launch_fvp_tail (metrpo_debug_fvp_us)
+    double* h_upd = nullptr; unsigned long long upd_stamp = 0;
+    int upd_pending = 0, upd_spec = 0, upd_changed_in_end = 0; metrpo_batch upd_batch = {}; metrpo_trpo_params upd_params = {}; metrpo_trpo_diag upd_diag = {};
+    hipStream_t side_stream[METRPO_MAX_PAR_ROUNDS - 1] = {}; hipEvent_t ev_fork = nullptr, ev_join[METRPO_MAX_PAR_ROUNDS - 1] = {}; int side_ready = 0;   // rollout_gemm.hip: independent rounds of a small-batch rollout run concurrently
+    double* h_pinned = nullptr;    // pinned host scratch for the per-trial read-back
+    int n_sm = 256;          // CU count (device property)
+    int upd_tiles_per_wave = 1;   // MFMA update kernels: at least this many 16-sample tiles per wave before another block is added (1; the option that set it was retired in round 6: experiments/upd_small.py)
+    int n_cu_sched = 0;      // CUs that actually ran this process's waves (probe.hip: census; 0 = not measured yet)
+    int exclusive = 1;       // the caller's metrpo_set_exclusive value (1 at metrpo_create); 0: the GPU is shared with other compute processes.  Read through ctx_exclusive(), which also honours option NO_RESIDENT
+    std::string opt_val[OPT_COUNT]; bool opt_set[OPT_COUNT] = {};   // METRPO_OPT_LIST: set by metrpo_create from the environment, then only by metrpo_set_option
+    hipEvent_t fvp_ev[32] = {}; int fvp_ev_n = 0, fvp_ev_made = 0;   // option TIME_FVP: events around the Fisher-vector-product kernel of launch_fvp_tail (metrpo_debug_fvp_us)
     std::string rollout_note;   // why the last metrpo_rollout left the fast dispatch table ("" when it did not): metrpo_rollout_note
-    int fallback_logged;  // a rollout shape that fell off the fast dispatch table has been reported once (METRPO_VERBOSE)
-    std::vector<void*> ws_retired; size_t ws_retired_bytes = 0;   // outgrown workspaces (ws_retire below): freed by metrpo_destroy, or by one sweep once they pass WS_RETIRED_MAX
+    int fallback_logged = 0;  // a rollout shape that fell off the fast dispatch table has been reported once (METRPO_VERBOSE)
+    std::vector<std::pair<void*, size_t>> ws_retired; size_t ws_retired_bytes = 0;   // outgrown workspaces and their sizes (ws_grow below): freed by metrpo_destroy, or by one sweep once they pass WS_RETIRED_MAX
     std::string err;
 };
 
@@ -141,20 +149,28 @@ struct metrpo_ctx {
 // running work (tests/test_gpu_api.py::test_rollout_at_a_larger_batch_does_not_wait_for_other_streams).
 constexpr size_t WS_RETIRED_MAX = (size_t)4 << 30;
 static inline void ws_sweep(metrpo_ctx* c) {
-    for (void* p : c->ws_retired) (void)hipFree(p);           // (the first hipFree waits for the device)
+    for (const auto& r : c->ws_retired) (void)hipFree(r.first);   // (the first hipFree waits for the device)
     c->ws_retired.clear(); c->ws_retired_bytes = 0;
 }
-static inline void ws_retire(metrpo_ctx* c, void* p) {
-    if (!p) return;
-    size_t sz = 0;
-    if (hipMemPtrGetInfo(p, &sz) != hipSuccess) { (void)hipGetLastError(); sz = 0; }
-    c->ws_retired.push_back(p); c->ws_retired_bytes += sz;
-    if (c->ws_retired_bytes > WS_RETIRED_MAX) ws_sweep(c);
-}
-static inline hipError_t ws_alloc(metrpo_ctx* c, void** p, size_t bytes) {
-    hipError_t e = hipMalloc(p, bytes);
-    if (e == hipErrorOutOfMemory && !c->ws_retired.empty()) { (void)hipGetLastError(); ws_sweep(c); e = hipMalloc(p, bytes); }
-    return e;
+int set_err(metrpo_ctx* c, int code, const std::string& msg);
+// The one way a context-owned buffer gets memory: afterwards it holds at least `bytes`.  When it has to grow, the old buffer is retired with its size
+// and a new one of exactly `bytes` is allocated (a failure for lack of memory sweeps the retired buffers and tries once more); *grew then reports
+// that the contents are new and uninitialised.  On failure the buffer is left empty.
+template <class T> static inline int ws_grow(metrpo_ctx* c, DevBuf<T>& b, size_t bytes, bool* grew = nullptr) {
+    if (grew) *grew = false;
+    if (bytes <= b.bytes) return METRPO_OK;
+    if (b.p) {
+        c->ws_retired.emplace_back((void*)b.p, b.bytes); c->ws_retired_bytes += b.bytes;
+        b.p = nullptr; b.bytes = 0;
+        if (c->ws_retired_bytes > WS_RETIRED_MAX) ws_sweep(c);
+    }
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, bytes);
+    if (e == hipErrorOutOfMemory && !c->ws_retired.empty()) { (void)hipGetLastError(); ws_sweep(c); e = hipMalloc(&p, bytes); }
+    if (e != hipSuccess) return set_err(c, METRPO_EHIP, "hipMalloc(" + std::to_string(bytes) + " bytes): " + hipGetErrorString(e));
+    b.p = (T*)p; b.bytes = bytes;
+    if (grew) *grew = true;
+    return METRPO_OK;
 }
 
 // value of a switch, NULL when unset -- the same contract as the getenv() calls these replaced
@@ -223,7 +239,6 @@ struct CgTail;
 int policy_mfma_launch(metrpo_ctx*, int idx, int mode, const metrpo_batch*, const float* theta, const float* v,
                        float* partials, int nblocks, hipStream_t);
 
-int set_err(metrpo_ctx* c, int code, const std::string& msg);
 #define HIP_TRY(c, expr)                                                                      \
     do {                                                                                      \
         hipError_t _e = (expr);                                                               \
@@ -283,7 +298,7 @@ int comm_allreduce_f64(metrpo_ctx*, double* buf, long long count, hipStream_t);
 XchgK xchg_next(metrpo_ctx*);
 static inline XchgK xchg_none() { XchgK x = {}; return x; }
 // scal[S_COMMERR] of the CG workspace (gout[1+P] | x r p z step [5P] | scal[8] | lk[2]): sticky error cell of the exchanges
-static inline double* comm_err_cell(metrpo_ctx* c) { return c->d_cg + (size_t)(1 + c->pd.P) + 5 * (size_t)c->pd.P + 6; }
+static inline double* comm_err_cell(metrpo_ctx* c) { return c->d_cg.p + (size_t)(1 + c->pd.P) + 5 * (size_t)c->pd.P + 6; }
 // time-out cell of the resident VALIDATION launches (behind scal | lk | ls): cleared in front of every such launch, so an earlier rollout's sticky S_ROLLERR
 // cannot poison validation costs and a validation time-out cannot be mistaken for a rollout's
 static inline double* val_err_cell(metrpo_ctx* c) { return comm_err_cell(c) + 8; }

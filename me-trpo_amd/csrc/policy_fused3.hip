@@ -645,13 +645,10 @@ static int f3_ensure(metrpo_ctx* c, long long N) {
     typedef ShHumanoid S;
     const size_t tiles = (size_t)((N + 15) / 16);
     const size_t need = tiles * (S::NHB + S::CB4) * 64 * sizeof(float) * 4 + (size_t)S::IMG_FLOATS * sizeof(float);
-    if (need > c->f3_cap) {
-        if (c->d_f3) { ws_retire(c, c->d_f3); c->d_f3 = nullptr; c->f3_cap = 0; }
-        HIP_TRY(c, ws_alloc(c, (void**)&c->d_f3, need));
-        c->f3_cap = need;
-        c->f3_rows = -1;
-    }
-    return METRPO_OK;
+    bool grew = false;
+    const int rc = ws_grow(c, c->d_f3, need, &grew);
+    if (grew) c->f3_rows = -1;
+    return rc;
 }
 
 template <class K> static int f3_attr(metrpo_ctx* c, K kern, size_t sh) {
@@ -669,7 +666,7 @@ int policy_f3_launch(metrpo_ctx* c, int mode, const metrpo_batch* b, const float
     F3K k = {};
     k.obs = b->d_obs; k.act = b->d_act; k.adv = b->d_adv; k.old_mean = b->d_old_mean; k.old_ls = b->d_old_log_std; k.ls_stride = b->old_log_std_stride;
     k.valid = b->d_valid; k.N = N; k.inv_n = (float)b->inv_n_global; k.skip = c->ls_skip; k.theta = theta; k.v = vf;
-    k.hc = (f32x4*)c->d_f3; k.u = k.hc + tiles * S::NHB * 64;
+    k.hc = (f32x4*)c->d_f3.p; k.u = k.hc + tiles * S::NHB * 64;
     float* img = (float*)(k.u + tiles * S::CB4 * 64);
     k.img = img;
     auto build_image = [&](int what) { hipLaunchKernelGGL((k_f3_image<S>), dim3(64), dim3(256), 0, st, k, img, what); };

@@ -762,14 +762,14 @@ int policy_mfma_image_buffers(metrpo_ctx* c) {
             if (j >= c->pd.P || vpos[j] != -1) return set_err(c, METRPO_EINVAL, "policy image map: tangent entry out of range or stored twice");
             vpos[j] = (int)i;
         }
-    for (void** q : {(void**)&c->d_pol_img, (void**)&c->d_pol_vpos, (void**)&c->d_pol_imgval}) if (*q) { ws_retire(c, *q); *q = nullptr; }
     c->pol_img_idx = -1;
-    HIP_TRY(c, ws_alloc(c, (void**)&c->d_pol_img, sizeof(int) * map.size()));
-    HIP_TRY(c, hipMemcpy(c->d_pol_img, map.data(), sizeof(int) * map.size(), hipMemcpyHostToDevice));
-    HIP_TRY(c, ws_alloc(c, (void**)&c->d_pol_vpos, sizeof(int) * vpos.size()));
-    HIP_TRY(c, hipMemcpy(c->d_pol_vpos, vpos.data(), sizeof(int) * vpos.size(), hipMemcpyHostToDevice));
-    HIP_TRY(c, ws_alloc(c, (void**)&c->d_pol_imgval, sizeof(float) * map.size()));
-    HIP_TRY(c, hipMemset(c->d_pol_imgval, 0, sizeof(float) * map.size()));
+    int rc;
+    if ((rc = ws_grow(c, c->d_pol_img, sizeof(int) * map.size())) || (rc = ws_grow(c, c->d_pol_vpos, sizeof(int) * vpos.size())) ||
+        (rc = ws_grow(c, c->d_pol_imgval, sizeof(float) * map.size())))
+        return rc;
+    HIP_TRY(c, hipMemcpy(c->d_pol_img.p, map.data(), sizeof(int) * map.size(), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_pol_vpos.p, vpos.data(), sizeof(int) * vpos.size(), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemset(c->d_pol_imgval.p, 0, sizeof(float) * map.size()));
     c->pol_img_idx = idx;
     return METRPO_OK;
 }
@@ -782,19 +782,15 @@ int policy_mfma_launch(metrpo_ctx* c, int idx, int mode, const metrpo_batch* b, 
     k.obs = b->d_obs; k.act = b->d_act; k.adv = b->d_adv; k.old_mean = b->d_old_mean; k.old_ls = b->d_old_log_std;
     k.ls_stride = b->old_log_std_stride; k.valid = b->d_valid; k.N = b->N; k.inv_n = (float)b->inv_n_global;
     { const int rc = policy_mfma_image_buffers(c); if (rc) return rc; }
-    k.img_map = (const int*)c->d_pol_img;
+    k.img_map = (const int*)c->d_pol_img.p;
     k.gm = c->vjp_gm;
     k.skip = c->ls_skip;
     k.hcache = nullptr;
-    k.imgval = (c->img_live && c->hcache_on && k.gm == nullptr && (mode == MODE_GRAD || mode == MODE_FVP)) ? c->d_pol_imgval : nullptr;
+    k.imgval = (c->img_live && c->hcache_on && k.gm == nullptr && (mode == MODE_GRAD || mode == MODE_FVP)) ? c->d_pol_imgval.p : nullptr;
     if (c->hcache_on && (mode == MODE_GRAD || mode == MODE_FVP) && k.gm == nullptr) {      // set by run_trpo_update around one CG solve
         const size_t need = (size_t)((b->N + 15) / 16) * 2 * (size_t)cdiv_(en.ph, 16) * 64 * 4;
-        if (need > c->hcache_cap) {
-            if (c->d_hcache) { ws_retire(c, c->d_hcache); c->d_hcache = nullptr; c->hcache_cap = 0; }
-            HIP_TRY(c, ws_alloc(c, (void**)&c->d_hcache, need * sizeof(float)));
-            c->hcache_cap = need;
-        }
-        k.hcache = c->d_hcache;
+        { const int rc = ws_grow(c, c->d_hcache, need * sizeof(float)); if (rc) return rc; }
+        k.hcache = c->d_hcache.p;
         if (mode == MODE_FVP) mode = MODE_FVPC;
     }
     // loss + KL evaluation (line search): no transpose tiles, 128 VGPRs -> two blocks fit a CU (run_mode launches 2 x n_sm of them)

@@ -381,13 +381,7 @@ __global__ void k_d2f(const double* __restrict__ in, float* __restrict__ out, in
 // ---------------------------------------------------------------------------------------------
 static int ensure_partials(metrpo_ctx* c, int nrows) {
     const size_t need = (size_t)nrows * (c->pd.P + PART_EXTRA);
-    if (need > c->partials_cap) {
-        ws_retire(c, c->d_partials);
-        c->d_partials = nullptr; c->partials_cap = 0;
-        HIP_TRY(c, ws_alloc(c, (void**)&c->d_partials, need * sizeof(float)));
-        c->partials_cap = need;
-    }
-    return METRPO_OK;
+    return ws_grow(c, c->d_partials, need * sizeof(float));
 }
 
 static int fill_polk(metrpo_ctx* c, const metrpo_batch* b, PolK* k, bool need_targets) {
@@ -405,11 +399,11 @@ static int fill_polk(metrpo_ctx* c, const metrpo_batch* b, PolK* k, bool need_ta
 static void finalize(metrpo_ctx* c, int mode, int nrows, int stride, int lk_col, const double* v, double* out, hipStream_t st,
                      const CgTail* tail = nullptr) {
     const int nout = (mode == 0) ? c->pd.P + 1 : (mode == 1) ? c->pd.P : 2;
-    CgTail none; none.op = 0; none.ticket = c->d_ticket; none.vpos = nullptr; none.imgval = nullptr; none.ls = nullptr; none.pub_dst = nullptr;
+    CgTail none; none.op = 0; none.ticket = c->d_ticket.p; none.vpos = nullptr; none.imgval = nullptr; none.ls = nullptr; none.pub_dst = nullptr;
     // inside a fused update of a sharded run (run_trpo_update raises xg_fuse) the reduction carries the cross-rank sum in its tail
     const XchgK xc = (c->xg_fuse && c->xg_world > 1) ? xchg_next(c) : xchg_none();
     hipLaunchKernelGGL(k_finalize, dim3((nout + FIN_C - 1) / FIN_C), dim3(1024), 0, st, c->pd, mode, nrows, stride, lk_col,
-                       c->d_partials, c->d_theta, v, out, tail ? *tail : none, xc);
+                       c->d_partials.p, c->d_theta.p, v, out, tail ? *tail : none, xc);
 }
 
 // generic kernels: pick the largest sample tile (threads per block) whose LDS columns fit
@@ -427,13 +421,13 @@ static int launch_generic(metrpo_ctx* c, int mode, const PolK& k, const float* t
     *nrows = g;
     if (mode == 0) {
         if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_loss_grad<PT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        hipLaunchKernelGGL(k_loss_grad<PT>, dim3(g), dim3(PT), sh, st, c->pd, k, theta, c->d_partials);
+        hipLaunchKernelGGL(k_loss_grad<PT>, dim3(g), dim3(PT), sh, st, c->pd, k, theta, c->d_partials.p);
     } else if (mode == 1) {
         if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_fvp<PT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        hipLaunchKernelGGL(k_fvp<PT>, dim3(g), dim3(PT), sh, st, c->pd, k, theta, vf, c->d_partials);
+        hipLaunchKernelGGL(k_fvp<PT>, dim3(g), dim3(PT), sh, st, c->pd, k, theta, vf, c->d_partials.p);
     } else {
         if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_loss_kl<PT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        hipLaunchKernelGGL(k_loss_kl<PT>, dim3(g), dim3(PT), sh, st, c->pd, k, theta, c->d_partials);
+        hipLaunchKernelGGL(k_loss_kl<PT>, dim3(g), dim3(PT), sh, st, c->pd, k, theta, c->d_partials.p);
     }
     return METRPO_OK;
 }
@@ -454,7 +448,7 @@ static int run_mode(metrpo_ctx* c, int mode, const metrpo_batch* b, const PolK& 
         int rc = ensure_partials(c, g); if (rc) return rc;
         *nrows = g; *stride = P + PART_EXTRA; *lk_col = P;
         c->ls_skip = k.skip;
-        rc = policy_mfma_launch(c, c->pol_mfma, mode, b, theta, vf, c->d_partials, g, st);
+        rc = policy_mfma_launch(c, c->pol_mfma, mode, b, theta, vf, c->d_partials.p, g, st);
         c->ls_skip = nullptr;
         return rc;
     }
@@ -467,7 +461,7 @@ static int run_mode(metrpo_ctx* c, int mode, const metrpo_batch* b, const PolK& 
         int rc = ensure_partials(c, g); if (rc) return rc;
         *nrows = g; *stride = P + PART_EXTRA; *lk_col = P;
         c->ls_skip = k.skip;
-        rc = policy_f3_launch(c, mode, b, theta, vf, c->d_partials, g, st);
+        rc = policy_f3_launch(c, mode, b, theta, vf, c->d_partials.p, g, st);
         c->ls_skip = nullptr;
         return rc;
     }
@@ -481,9 +475,9 @@ static int run_mode(metrpo_ctx* c, int mode, const metrpo_batch* b, const PolK& 
 
 int launch_loss_grad(metrpo_ctx* c, const metrpo_batch* b, double* out, hipStream_t st, const CgTail* tail) {
     PolK k; int rc = fill_polk(c, b, &k, true); if (rc) return rc;
-    if (policy_gemm_applicable(c, b->N)) return policy_gemm_run(c, 0, b, k, c->d_theta, nullptr, nullptr, out, tail, st);
+    if (policy_gemm_applicable(c, b->N)) return policy_gemm_run(c, 0, b, k, c->d_theta.p, nullptr, nullptr, out, tail, st);
     int nrows, stride, lk;
-    if ((rc = run_mode(c, 0, b, k, c->d_theta, nullptr, &nrows, &stride, &lk, st))) return rc;
+    if ((rc = run_mode(c, 0, b, k, c->d_theta.p, nullptr, &nrows, &stride, &lk, st))) return rc;
     finalize(c, 0, nrows, stride, lk, nullptr, out, st, tail);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
@@ -500,11 +494,11 @@ int launch_policy_vjp(metrpo_ctx* c, const float* obs, const float* gm, long lon
     int nrows, stride, lk;
     c->vjp_gm = gm;
     if (policy_gemm_applicable(c, N)) {
-        const int rcg = policy_gemm_run(c, 0, &b, k, c->d_theta, nullptr, nullptr, out, nullptr, st);
+        const int rcg = policy_gemm_run(c, 0, &b, k, c->d_theta.p, nullptr, nullptr, out, nullptr, st);
         c->vjp_gm = nullptr;
         return rcg;
     }
-    const int rc = run_mode(c, 0, &b, k, c->d_theta, nullptr, &nrows, &stride, &lk, st);
+    const int rc = run_mode(c, 0, &b, k, c->d_theta.p, nullptr, &nrows, &stride, &lk, st);
     c->vjp_gm = nullptr;
     if (rc) return rc;
     finalize(c, 0, nrows, stride, lk, nullptr, out, st);
@@ -515,8 +509,8 @@ int launch_policy_vjp(metrpo_ctx* c, const float* obs, const float* gm, long lon
 int launch_fvp(metrpo_ctx* c, const metrpo_batch* b, const double* v, double* hv, hipStream_t st) {
     if (!v || !hv) return set_err(c, METRPO_ENULL, "v/hv is NULL");
     const int P = c->pd.P;
-    hipLaunchKernelGGL(k_d2f, dim3((P + 127) / 128), dim3(128), 0, st, v, c->d_vf, P);
-    return launch_fvp_f32(c, b, c->d_vf, v, hv, st);
+    hipLaunchKernelGGL(k_d2f, dim3((P + 127) / 128), dim3(128), 0, st, v, c->d_vf.p, P);
+    return launch_fvp_f32(c, b, c->d_vf.p, v, hv, st);
 }
 
 int launch_fvp_f32(metrpo_ctx* c, const metrpo_batch* b, const float* vf, const double* v, double* hv, hipStream_t st) {
@@ -525,14 +519,14 @@ int launch_fvp_f32(metrpo_ctx* c, const metrpo_batch* b, const float* vf, const 
 
 int launch_fvp_tail(metrpo_ctx* c, const metrpo_batch* b, const float* vf, const double* v, double* hv, const CgTail* tail, hipStream_t st) {
     PolK k; int rc = fill_polk(c, b, &k, false); if (rc) return rc;
-    if (policy_gemm_applicable(c, b->N)) return policy_gemm_run(c, 1, b, k, c->d_theta, vf, v, hv, tail, st);
+    if (policy_gemm_applicable(c, b->N)) return policy_gemm_run(c, 1, b, k, c->d_theta.p, vf, v, hv, tail, st);
     int nrows, stride, lk;
     const bool timed = ctx_opt(c, OPT_TIME_FVP) != nullptr && c->fvp_ev_n + 2 <= 32;      // diagnostics: metrpo_debug_fvp_us
     if (timed) {
         for (; c->fvp_ev_made < 32; ++c->fvp_ev_made) HIP_TRY(c, hipEventCreate(&c->fvp_ev[c->fvp_ev_made]));
         HIP_TRY(c, hipEventRecord(c->fvp_ev[c->fvp_ev_n], st));
     }
-    if ((rc = run_mode(c, 1, b, k, c->d_theta, vf, &nrows, &stride, &lk, st))) return rc;
+    if ((rc = run_mode(c, 1, b, k, c->d_theta.p, vf, &nrows, &stride, &lk, st))) return rc;
     if (timed) { HIP_TRY(c, hipEventRecord(c->fvp_ev[c->fvp_ev_n + 1], st)); c->fvp_ev_n += 2; }
     finalize(c, 1, nrows, stride, lk, v, hv, st, tail);
     HIP_TRY(c, hipGetLastError());
@@ -543,11 +537,11 @@ int launch_loss_kl(metrpo_ctx* c, const metrpo_batch* b, const float* theta, dou
     PolK k; int rc = fill_polk(c, b, &k, true); if (rc) return rc;
     if (policy_gemm_applicable(c, b->N)) {
         if (decide) return set_err(c, METRPO_EUNSUPPORTED, "device-side line search: not on the GEMM update path");
-        return policy_gemm_run(c, 2, b, k, theta ? theta : c->d_theta, nullptr, nullptr, out, nullptr, st);
+        return policy_gemm_run(c, 2, b, k, theta ? theta : c->d_theta.p, nullptr, nullptr, out, nullptr, st);
     }
     if (decide) k.skip = decide->ls;
     int nrows, stride, lk;
-    if ((rc = run_mode(c, 2, b, k, theta ? theta : c->d_theta, nullptr, &nrows, &stride, &lk, st))) return rc;
+    if ((rc = run_mode(c, 2, b, k, theta ? theta : c->d_theta.p, nullptr, &nrows, &stride, &lk, st))) return rc;
     finalize(c, 2, nrows, stride, lk, nullptr, out, st, decide);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;

@@ -517,17 +517,12 @@ static int launch_gram_mfma_wide(metrpo_ctx* c, const float* obs, const float* r
     const long long tiles = (N + 15) / 16;
     const int g = (int)std::max<long long>(1, std::min<long long>(tiles, (long long)c->n_sm * 2));
     const size_t need = (size_t)g * (F * F + F);
-    if (need > c->gram_cap) {
-        ws_retire(c, c->d_gram_part);
-        c->d_gram_part = nullptr; c->gram_cap = 0;
-        HIP_TRY(c, ws_alloc(c, (void**)&c->d_gram_part, need * sizeof(double)));
-        c->gram_cap = need;
-    }
+    { const int rc = ws_grow(c, c->d_gram_part, need * sizeof(double)); if (rc) return rc; }
     const size_t sh = sizeof(double) * M * M;                         // >= the 2 x 16 x M floats of the main loop
     if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_gram_mfma_wide<NFB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-    hipLaunchKernelGGL(k_gram_mfma_wide<NFB>, dim3(g), dim3(256), sh, st, obs, ret, tpath, valid, (long long)N, c->pd.ns, c->d_gram_part);
+    hipLaunchKernelGGL(k_gram_mfma_wide<NFB>, dim3(g), dim3(256), sh, st, obs, ret, tpath, valid, (long long)N, c->pd.ns, c->d_gram_part.p);
     const int nout = F * F + F;
-    hipLaunchKernelGGL(k_gram_final, dim3((nout + 15) / 16), dim3(1024), 0, st, c->d_gram_part, g, M, F, AtA, Aty);
+    hipLaunchKernelGGL(k_gram_final, dim3((nout + 15) / 16), dim3(1024), 0, st, c->d_gram_part.p, g, M, F, AtA, Aty);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
 }
@@ -540,17 +535,12 @@ static int launch_gram_mfma(metrpo_ctx* c, const float* obs, const float* ret, c
     const long long tiles = (N + 15) / 16;
     const int g = (int)std::max<long long>(1, std::min<long long>((tiles + 3) / 4, (long long)c->n_sm * 2));   // inputs are prefetched one tile ahead: few blocks, few partial matrices
     const size_t need = (size_t)g * (F * F + F);
-    if (need > c->gram_cap) {
-        ws_retire(c, c->d_gram_part);
-        c->d_gram_part = nullptr; c->gram_cap = 0;
-        HIP_TRY(c, ws_alloc(c, (void**)&c->d_gram_part, need * sizeof(double)));
-        c->gram_cap = need;
-    }
+    { const int rc = ws_grow(c, c->d_gram_part, need * sizeof(double)); if (rc) return rc; }
     const size_t sh = sizeof(double) * 4 * M * M;
     if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_gram_mfma<NFB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-    hipLaunchKernelGGL(k_gram_mfma<NFB>, dim3(g), dim3(256), sh, st, obs, ret, tpath, valid, (long long)N, c->pd.ns, c->d_gram_part);
+    hipLaunchKernelGGL(k_gram_mfma<NFB>, dim3(g), dim3(256), sh, st, obs, ret, tpath, valid, (long long)N, c->pd.ns, c->d_gram_part.p);
     const int nout = F * F + F;
-    hipLaunchKernelGGL(k_gram_final, dim3((nout + 15) / 16), dim3(1024), 0, st, c->d_gram_part, g, M, F, AtA, Aty);
+    hipLaunchKernelGGL(k_gram_final, dim3((nout + 15) / 16), dim3(1024), 0, st, c->d_gram_part.p, g, M, F, AtA, Aty);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
 }
@@ -561,23 +551,13 @@ int launch_gae(metrpo_ctx* c, const float* obs, const float* rew, const uint8_t*
     const long long N = (long long)T * B;
     double* V = nullptr;
     if (coeffs != nullptr) {
-        if ((size_t)N > c->vbuf_cap) {
-            ws_retire(c, c->d_vbuf);
-            c->d_vbuf = nullptr; c->vbuf_cap = 0;
-            HIP_TRY(c, ws_alloc(c, (void**)&c->d_vbuf, sizeof(double) * (size_t)N));
-            c->vbuf_cap = (size_t)N;
-        }
-        V = c->d_vbuf;
+        { const int rc = ws_grow(c, c->d_vbuf, sizeof(double) * (size_t)N); if (rc) return rc; }
+        V = c->d_vbuf.p;
     }
     const int nblk = (B + 63) / 64;
-    if ((size_t)nblk * 3 + 2 > c->gae_part_cap) {
-        ws_retire(c, c->d_gae_part);
-        c->d_gae_part = nullptr; c->gae_part_cap = 0;
-        const size_t cap = std::max<size_t>((size_t)nblk * 3 + 2, 1024);
-        HIP_TRY(c, ws_alloc(c, (void**)&c->d_gae_part, sizeof(double) * cap));
-        HIP_TRY(c, hipMemsetAsync(c->d_gae_part, 0, sizeof(double) * cap, st));       // the ticket (first word) starts at zero; every launch leaves it there
-        c->gae_part_cap = cap;
-    }
+    bool grew = false;
+    { const int rc = ws_grow(c, c->d_gae_part, sizeof(double) * std::max<size_t>((size_t)nblk * 3 + 2, 1024), &grew); if (rc) return rc; }
+    if (grew) HIP_TRY(c, hipMemsetAsync(c->d_gae_part.p, 0, c->d_gae_part.bytes, st));       // the ticket (first word) starts at zero; every launch leaves it there
     const int ns = c->pd.ns;
     // few env columns and a long horizon (the params-file batches: B = 100, T = 600): the grid is 2 workgroups and the kernel is the
     // dependent chain of one wave's steps -- 16 time chunks instead of 8 shorten it (84 -> 67 us at C0-params-file); at C1 (79 workgroups) 8 is faster
@@ -595,7 +575,7 @@ int launch_gae(metrpo_ctx* c, const float* obs, const float* rew, const uint8_t*
     const size_t sh = (coeffs != nullptr && !pre_v) ? sizeof(float) * nw * 64 * (size_t)ns : 0;
 #define GAE_LAUNCH_NW(NSV, NWV) do { \
         if (sh > 48 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_gae<NSV, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh)); \
-        hipLaunchKernelGGL((k_gae<NSV, NWV>), dim3((B + 63) / 64), dim3(64 * NWV), sh, st, obs, tpath, coeffs, ns, pre_v, V, rew, done, T, B, gamma, lam, adv, ret, valid, stats, c->d_gae_part); } while (0)
+        hipLaunchKernelGGL((k_gae<NSV, NWV>), dim3((B + 63) / 64), dim3(64 * NWV), sh, st, obs, tpath, coeffs, ns, pre_v, V, rew, done, T, B, gamma, lam, adv, ret, valid, stats, c->d_gae_part.p); } while (0)
 #define GAE_LAUNCH(NSV) do { if (wide) GAE_LAUNCH_NW(NSV, 16); else GAE_LAUNCH_NW(NSV, GAE_NW); } while (0)
 #define GAE_LAUNCH8(NSV) GAE_LAUNCH_NW(NSV, GAE_NW)
     if (sh + 48 * 1024 > 160 * 1024) return set_err(c, METRPO_EUNSUPPORTED, "gae: observation too wide for the staging buffer");
@@ -621,7 +601,7 @@ __global__ void k_process_begin(const float* __restrict__ theta, int P, int na, 
 }
 int launch_process_begin(metrpo_ctx* c, float* ls_out, double* acc, int64_t n_acc, hipStream_t st) {
     const int64_t n = std::max<int64_t>(n_acc, (int64_t)c->pd.na);
-    hipLaunchKernelGGL(k_process_begin, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)c->d_theta, c->pd.P, c->pd.na, ls_out, acc, n_acc);
+    hipLaunchKernelGGL(k_process_begin, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)c->d_theta.p, c->pd.P, c->pd.na, ls_out, acc, n_acc);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
 }
@@ -769,15 +749,10 @@ int launch_gram(metrpo_ctx* c, const float* obs, const float* ret, const int32_t
     const int grid = (int)std::min<int64_t>((N + GRAM_TILE - 1) / GRAM_TILE, (int64_t)c->n_sm * 4);
     const int nout = F * F + F;
     const size_t need = (size_t)grid * nout;
-    if (need > c->gram_cap) {
-        ws_retire(c, c->d_gram_part);
-        c->d_gram_part = nullptr; c->gram_cap = 0;
-        HIP_TRY(c, ws_alloc(c, (void**)&c->d_gram_part, sizeof(double) * need));
-        c->gram_cap = need;
-    }
+    { const int rc = ws_grow(c, c->d_gram_part, sizeof(double) * need); if (rc) return rc; }
     if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_gram, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-    hipLaunchKernelGGL(k_gram, dim3(grid), dim3(bs), sh, st, obs, ret, tpath, valid, N, c->pd.ns, c->d_gram_part);
-    hipLaunchKernelGGL(k_gram_final, dim3((nout + 15) / 16), dim3(1024), 0, st, c->d_gram_part, grid, 0, F, AtA, Aty);
+    hipLaunchKernelGGL(k_gram, dim3(grid), dim3(bs), sh, st, obs, ret, tpath, valid, N, c->pd.ns, c->d_gram_part.p);
+    hipLaunchKernelGGL(k_gram_final, dim3((nout + 15) / 16), dim3(1024), 0, st, c->d_gram_part.p, grid, 0, F, AtA, Aty);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
 }

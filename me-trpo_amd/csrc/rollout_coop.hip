@@ -62,7 +62,7 @@ __global__ void __launch_bounds__(256) k_pad_dyn(NetDesc src, NetDesc dst, int K
 
 int launch_pad_dyn(metrpo_ctx* c, hipStream_t st) {
     const long long n = (long long)c->pd.K * c->dyn_pad.n_params;
-    hipLaunchKernelGGL(k_pad_dyn, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c->pd.dyn, c->dyn_pad, c->pd.K, c->d_dyn, c->d_dyn_pad);
+    hipLaunchKernelGGL(k_pad_dyn, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c->pd.dyn, c->dyn_pad, c->pd.K, c->d_dyn.p, c->d_dyn_pad.p);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
 }
@@ -90,25 +90,23 @@ int launch_rollout_coop(metrpo_ctx* c, int idx, const RolloutK& r_in, hipStream_
     const int grid = one ? (tiles < n_cu ? tiles : n_cu) : tiles;
     if (one && tiles > grid) {                                           // hand-over slots: flag[tiles] | ts[16 tiles] | model[16 tiles] | obs[16 tiles][ns]
         const int ns = c->pd.ns;
-        if (c->mig_cap < tiles) {
-            if (c->d_mig) { ws_retire(c, c->d_mig); c->d_mig = nullptr; c->mig_cap = 0; }
-            const size_t bytes = sizeof(int32_t) * (size_t)tiles * (1 + 32 + 16 * ns);
-            HIP_TRY(c, ws_alloc(c, (void**)&c->d_mig, bytes));
-            HIP_TRY(c, hipMemsetAsync(c->d_mig, 0, bytes, st));
-            c->mig_cap = tiles; c->mig_epoch = 0;
-        }
-        int32_t* base = (int32_t*)c->d_mig;
-        r.mig_flag = base; r.mig_ts = base + c->mig_cap; r.mig_model = base + 17 * (size_t)c->mig_cap;
-        r.mig_obs = (float*)(base + 33 * (size_t)c->mig_cap);
+        const size_t tile_bytes = sizeof(int32_t) * (1 + 32 + 16 * (size_t)ns);
+        bool grew = false;
+        { const int rc = ws_grow(c, c->d_mig, tile_bytes * (size_t)tiles, &grew); if (rc) return rc; }
+        if (grew) { HIP_TRY(c, hipMemsetAsync(c->d_mig.p, 0, c->d_mig.bytes, st)); c->mig_epoch = 0; }
+        const size_t cap = c->d_mig.bytes / tile_bytes;                     // slots laid out for the capacity (the flags outlive the launch)
+        int32_t* base = (int32_t*)c->d_mig.p;
+        r.mig_flag = base; r.mig_ts = base + cap; r.mig_model = base + 17 * cap;
+        r.mig_obs = (float*)(base + 33 * cap);
         r.mig_epoch = ++c->mig_epoch;
         r.mig_err = comm_err_cell(c) + 1;                                // scal[S_ROLLERR]
     }
     const bool draws = r.eps || r.model_idx || r.sel_noise || r.reset_idx || r.reset_model;
     const coop_kernel_t kern = en.kern[one ? 1 : 0][draws ? 1 : 0];
     if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-    const float* dyn = c->d_dyn;
-    if (padded) { const int rc = launch_pad_dyn(c, st); if (rc) return rc; dyn = c->d_dyn_pad; }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), sh, st, r, dyn, c->d_theta, c->d_norm);
+    const float* dyn = c->d_dyn.p;
+    if (padded) { const int rc = launch_pad_dyn(c, st); if (rc) return rc; dyn = c->d_dyn_pad.p; }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), sh, st, r, dyn, c->d_theta.p, c->d_norm.p);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
 }

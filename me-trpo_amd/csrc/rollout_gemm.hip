@@ -742,7 +742,7 @@ static bool skp_select(const metrpo_ctx* c, int S0, int OT, int CB, int B, SkpVt
 // chunk-record table of this launch shape in device memory (cached in the context: the shape repeats every iteration)
 static int skp_table(metrpo_ctx* c, const SkpVt& v, const SkArgs& a, SkpArgs* p, hipStream_t st) {
     const long long key[8] = {a.M, a.heads, a.K1, a.N, (long long)a.strideW1, (long long)a.strideW0, (long long)a.stridePart, (long long)c->pd.env * 2 + (v.wide ? 1 : 0)};
-    bool same = c->d_skp_tab != nullptr;
+    bool same = c->d_skp_tab.p != nullptr;
     for (int i = 0; i < 8; ++i) same = same && c->skp_key[i] == key[i];
     if (!same) {
         // first use of a shape only.  The records live in the context (the copy below is ordered on the caller's stream behind the launches that still read the old
@@ -751,16 +751,11 @@ static int skp_table(metrpo_ctx* c, const SkpVt& v, const SkArgs& a, SkpArgs* p,
         v.tab(a, v.wide, tab, c->skp_Jx, c->skp_Jmax, c->skp_L, c->skp_NSL);
         const size_t bytes = tab.size() * sizeof(SkRec);
         c->skp_tab_host.assign((const int*)tab.data(), (const int*)tab.data() + bytes / sizeof(int));
-        if (bytes > c->skp_tab_cap) {
-            ws_retire(c, c->d_skp_tab);          // (launches already enqueued may still read the old table: retired, not freed)
-            c->d_skp_tab = nullptr; c->skp_tab_cap = 0;
-            HIP_TRY(c, ws_alloc(c, (void**)&c->d_skp_tab, bytes));
-            c->skp_tab_cap = bytes;
-        }
-        HIP_TRY(c, hipMemcpyAsync(c->d_skp_tab, c->skp_tab_host.data(), bytes, hipMemcpyHostToDevice, st));
+        { const int rc = ws_grow(c, c->d_skp_tab, bytes); if (rc) return rc; }     // (launches already enqueued may still read the old table: retired, not freed)
+        HIP_TRY(c, hipMemcpyAsync(c->d_skp_tab.p, c->skp_tab_host.data(), bytes, hipMemcpyHostToDevice, st));
         for (int i = 0; i < 8; ++i) c->skp_key[i] = key[i];
     }
-    p->tab = (const SkRec*)c->d_skp_tab;
+    p->tab = (const SkRec*)c->d_skp_tab.p;
     for (int x = 0; x < 8; ++x) p->Jx[x] = c->skp_Jx[x];
     p->Jmax = c->skp_Jmax; p->L = c->skp_L; p->NSL = c->skp_NSL;
     return METRPO_OK;
@@ -878,19 +873,19 @@ static int rollout_gemm_chunk(metrpo_ctx* c, const metrpo_rollout_args* a, hipSt
     if (sk.mode) {
         const int Lo = L - 1;                                // output layer
         HIP_TRY(c, hipMemsetAsync(sk_flag, 0, nSkFlag * sizeof(float), st));
-        sk_epi_image(sk.OT, c->d_dyn + pd.dyn.b_off[Lo - 1], pd.dyn.n_params, c->d_dyn + pd.dyn.w_off[Lo], pd.dyn.n_params, pd.ns, ska.N, K, sk_img, st);
+        sk_epi_image(sk.OT, c->d_dyn.p + pd.dyn.b_off[Lo - 1], pd.dyn.n_params, c->d_dyn.p + pd.dyn.w_off[Lo], pd.dyn.n_params, pd.ns, ska.N, K, sk_img, st);
         SkArgs& o = (sk.mode == 2) ? sk.a2 : sk.a1;
-        o.W1 = c->d_dyn + pd.dyn.w_off[Lo - 1]; o.strideW1 = pd.dyn.n_params;
+        o.W1 = c->d_dyn.p + pd.dyn.w_off[Lo - 1]; o.strideW1 = pd.dyn.n_params;
         o.epi = sk_img; o.part = bs.PART;
         if (sk.mode == 1) {
             o.A = bs.X; o.strideA = 0;
-            o.W0 = c->d_dyn + pd.dyn.w_off[0]; o.strideW0 = pd.dyn.n_params;      // row nin of the resident layout = b0 (X[nin] = 1), the rows behind it meet X's zero pad
+            o.W0 = c->d_dyn.p + pd.dyn.w_off[0]; o.strideW0 = pd.dyn.n_params;      // row nin of the resident layout = b0 (X[nin] = 1), the rows behind it meet X's zero pad
         } else if (sk.mode == 3) {
             o.A = bs.HA; o.strideA = (long long)B * o.K1; o.lda = o.K1;
         } else {
             SkArgs& h = sk.a1;                               // layer 1: relu(HA W1 + b1) -> HB
             h.A = bs.HA; h.strideA = (long long)B * h.K1; h.lda = h.K1;
-            h.W1 = c->d_dyn + pd.dyn.w_off[1]; h.strideW1 = pd.dyn.n_params; h.b1 = c->d_dyn + pd.dyn.b_off[1]; h.strideB1 = pd.dyn.n_params;
+            h.W1 = c->d_dyn.p + pd.dyn.w_off[1]; h.strideW1 = pd.dyn.n_params; h.b1 = c->d_dyn.p + pd.dyn.b_off[1]; h.strideB1 = pd.dyn.n_params;
             h.C = bs.HB; h.strideC = (long long)B * h.N; h.ldc = h.N;
             o.A = bs.HB; o.strideA = (long long)B * o.K1; o.lda = o.K1;
         }
@@ -901,9 +896,9 @@ static int rollout_gemm_chunk(metrpo_ctx* c, const metrpo_rollout_args* a, hipSt
             HIP_TRY(c, sk.v2.sched(sk.a2, sk.p2, sk_sched + ((sk.p1.sched_bytes + 255) & ~(size_t)255), st));
         }
         bs.out_splits = ska.N / 256; bs.out_stride = ska.stridePart; bs.out_ld = ska.ldp;
-        bs.out_bias = c->d_dyn + pd.dyn.b_off[Lo]; bs.out_bias_stride = pd.dyn.n_params;
+        bs.out_bias = c->d_dyn.p + pd.dyn.b_off[Lo]; bs.out_bias_stride = pd.dyn.n_params;
     }
-    if (nPimg) hipLaunchKernelGGL((k_pre_mfma3_image<55, 21, 100, 50, 25>), dim3((unsigned)((nPimg + 255) / 256)), dim3(256), 0, st, c->d_theta, bs.PIMG);
+    if (nPimg) hipLaunchKernelGGL((k_pre_mfma3_image<55, 21, 100, 50, 25>), dim3((unsigned)((nPimg + 255) / 256)), dim3(256), 0, st, c->d_theta.p, bs.PIMG);
     bs.ldx = ldx;
     RolloutK r = make_rollout_k(a);
     r.vB = vB; r.vR = vR;                                    // merged rounds: a->B = vR * vB rows, a->T = H steps (launch_rollout_gemm)
@@ -925,10 +920,10 @@ static int rollout_gemm_chunk(metrpo_ctx* c, const metrpo_rollout_args* a, hipSt
         pa.xflag = skp_flags; pa.arrive = (unsigned*)(skp_flags + (B + 127) / 128); pa.stop = r.stop; pa.post = skp_post;
         HIP_TRY(c, hipMemsetAsync(skp_flags, 0, nSkpFlag * sizeof(float), st));
         if (ctx_opt(c, OPT_PERSIST_STATS) != nullptr) {           // developer statistics of this launch (metrpo_debug_persist_stats)
-            if (c->skp_stats_n < skp_grid) { ws_retire(c, c->d_skp_stats); c->d_skp_stats = nullptr; HIP_TRY(c, ws_alloc(c, (void**)&c->d_skp_stats, sizeof(unsigned long long) * 8 * skp_grid)); }
+            { const int rc = ws_grow(c, c->d_skp_stats, sizeof(unsigned long long) * 8 * skp_grid); if (rc) return rc; }
             c->skp_stats_n = skp_grid;
-            HIP_TRY(c, hipMemsetAsync(c->d_skp_stats, 0, sizeof(unsigned long long) * 8 * skp_grid, st));
-            pa.stats = c->d_skp_stats;
+            HIP_TRY(c, hipMemsetAsync(c->d_skp_stats.p, 0, sizeof(unsigned long long) * 8 * skp_grid, st));
+            pa.stats = c->d_skp_stats.p;
             pa.nowait = ctx_opt(c, OPT_PERSIST_STATS)[0] == '2' ? 1 : ctx_opt(c, OPT_PERSIST_STATS)[0] == '3' ? 3 : 0;      // 2: no flag waits; 3: no flag waits and no chunk barrier (timing only)
         }
         if (skp_stop) {                                          // the sampler's stop rule inside the launch (mlp_persist.h)
@@ -938,13 +933,13 @@ static int rollout_gemm_chunk(metrpo_ctx* c, const metrpo_rollout_args* a, hipSt
             HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)(pa.misc + 2), (int)SKP_NOHALT, 1, st));
             pa.stop_batch = a->stop_batch; pa.stop_cum0 = a->d_stop_cum;
         }
-        SkpPost po; po.pd = pd; po.r = r; po.st = bs; po.theta = c->d_theta; po.norm = c->d_norm;
+        SkpPost po; po.pd = pd; po.r = r; po.st = bs; po.theta = c->d_theta.p; po.norm = c->d_norm.p;
         hipLaunchKernelGGL(k_skp_post_args, dim3(1), dim3(64), 0, st, po, skp_post);
-        hipLaunchKernelGGL(pre_mfma, dim3((B + 63) / 64), dim3(256), pre_lds, st, pd, r, 0, c->d_theta, c->d_norm, bs);
+        hipLaunchKernelGGL(pre_mfma, dim3((B + 63) / 64), dim3(256), pre_lds, st, pd, r, 0, c->d_theta.p, c->d_norm.p, bs);
         skp.launch(pa, skp_grid, skp.lds, st);
         const int tl = a->T - 1;
-        if (pd.ns <= 32) hipLaunchKernelGGL(k_big_post<32>, dim3((B + 7) / 8), dim3(256), 0, st, pd, r, tl, c->d_norm, bs);
-        else hipLaunchKernelGGL(k_big_post<64>, dim3((B + 3) / 4), dim3(256), 0, st, pd, r, tl, c->d_norm, bs);
+        if (pd.ns <= 32) hipLaunchKernelGGL(k_big_post<32>, dim3((B + 7) / 8), dim3(256), 0, st, pd, r, tl, c->d_norm.p, bs);
+        else hipLaunchKernelGGL(k_big_post<64>, dim3((B + 3) / 4), dim3(256), 0, st, pd, r, tl, c->d_norm.p, bs);
         HIP_TRY(c, hipGetLastError());
         c->last_rollout_kernel = 6;
         return METRPO_OK;
@@ -952,23 +947,23 @@ static int rollout_gemm_chunk(metrpo_ctx* c, const metrpo_rollout_args* a, hipSt
     // Humanoid's 100-50-25 pre-step at small batches: a tile per workgroup, column blocks over its waves (k_big_pre_mfma3_split)
     const bool pre_split = pre_mfma != nullptr && pre_lds != 0 && B <= 16 * c->n_sm && ctx_opt(c, OPT_NO_PRE_SPLIT) == nullptr;
     for (int t = 0; t < a->T; ++t) {
-        if (pre_split && !(pre_post && t > 0)) hipLaunchKernelGGL((k_big_pre_mfma3_split<55, 21, 0, 100, 50, 25>), dim3((B + 15) / 16), dim3(256), 0, st, pd, r, t, c->d_theta, c->d_norm, bs);
-        else if (pre_post && t > 0) hipLaunchKernelGGL(pre_post, dim3((B + 63) / 64), dim3(256), pre_lds_post, st, pd, r, t, c->d_theta, c->d_norm, bs);
-        else if (pre_mfma) hipLaunchKernelGGL(pre_mfma, dim3((B + 63) / 64), dim3(256), pre_lds, st, pd, r, t, c->d_theta, c->d_norm, bs);
+        if (pre_split && !(pre_post && t > 0)) hipLaunchKernelGGL((k_big_pre_mfma3_split<55, 21, 0, 100, 50, 25>), dim3((B + 15) / 16), dim3(256), 0, st, pd, r, t, c->d_theta.p, c->d_norm.p, bs);
+        else if (pre_post && t > 0) hipLaunchKernelGGL(pre_post, dim3((B + 63) / 64), dim3(256), pre_lds_post, st, pd, r, t, c->d_theta.p, c->d_norm.p, bs);
+        else if (pre_mfma) hipLaunchKernelGGL(pre_mfma, dim3((B + 63) / 64), dim3(256), pre_lds, st, pd, r, t, c->d_theta.p, c->d_norm.p, bs);
         else if (pre_gemm) {
-            hipLaunchKernelGGL(k_big_pre_gather, dim3((unsigned)(((long long)B * pd.ns + 255) / 256)), dim3(256), 0, st, pd, r, t, c->d_norm, bs);
+            hipLaunchKernelGGL(k_big_pre_gather, dim3((unsigned)(((long long)B * pd.ns + 255) / 256)), dim3(256), 0, st, pd, r, t, c->d_norm.p, bs);
             const float* pin = bs.S; int ldp = pd.ns;
             float* pbuf[2] = {bs.PA, bs.PB};
             for (int l = 0; l < pd.pol.n_layers; ++l) {
                 const int Kp = pd.pol.dims[l], Np = pd.pol.dims[l + 1];
                 float* pout = pbuf[l & 1];
-                gemm_launch(pd.pol.act[l], pin, 0, ldp, c->d_theta + pd.pol.w_off[l], 0, Np, c->d_theta + pd.pol.b_off[l], 0, pout, 0, Np, B, Np, Kp, 1, st);
+                gemm_launch(pd.pol.act[l], pin, 0, ldp, c->d_theta.p + pd.pol.w_off[l], 0, Np, c->d_theta.p + pd.pol.b_off[l], 0, pout, 0, Np, B, Np, Kp, 1, st);
                 pin = pout; ldp = Np;
             }
             const int npair = (pd.na + 1) / 2;
-            hipLaunchKernelGGL(k_big_pre_action, dim3((unsigned)(((long long)B * npair + 255) / 256)), dim3(256), 0, st, pd, r, t, c->d_theta, c->d_norm, pin, bs);
+            hipLaunchKernelGGL(k_big_pre_action, dim3((unsigned)(((long long)B * npair + 255) / 256)), dim3(256), 0, st, pd, r, t, c->d_theta.p, c->d_norm.p, pin, bs);
         }
-        else hipLaunchKernelGGL(k_big_pre, dim3((B + 63) / 64), dim3(pbs), psh, st, pd, r, t, c->d_theta, c->d_norm, bs);
+        else hipLaunchKernelGGL(k_big_pre, dim3((B + 63) / 64), dim3(pbs), psh, st, pd, r, t, c->d_theta.p, c->d_norm.p, bs);
         const float* in = bs.X; long long sIn = 0; int ldin = bs.ldx;
         float* bufs[2] = {bs.HA, bs.HB};
         if (sk.mode == 1) {                                  // the whole dynamics ensemble of this step in one launch
@@ -977,13 +972,13 @@ static int rollout_gemm_chunk(metrpo_ctx* c, const metrpo_rollout_args* a, hipSt
         } else if (sk.mode >= 2) {
             if (l0r) {
                 L0Args la = {};
-                la.M = B; la.heads = K; la.N = pd.dyn.dims[1]; la.ldx = bs.ldx; la.x = bs.X; la.W0 = c->d_dyn + pd.dyn.w_off[0]; la.strideW0 = pd.dyn.n_params;
+                la.M = B; la.heads = K; la.N = pd.dyn.dims[1]; la.ldx = bs.ldx; la.x = bs.X; la.W0 = c->d_dyn.p + pd.dyn.w_off[0]; la.strideW0 = pd.dyn.n_params;
                 la.C = bs.HA; la.strideC = (long long)B * pd.dyn.dims[1];
                 hipError_t e = hipSuccess;
                 (void)l0_rows(S0all, la, c->n_sm, st, &e);
                 HIP_TRY(c, e);
             } else
-            gemm_launch(METRPO_ACT_RELU, bs.X, 0, bs.ldx, c->d_dyn + pd.dyn.w_off[0], pd.dyn.n_params, pd.dyn.dims[1], c->d_dyn + pd.dyn.b_off[0], pd.dyn.n_params,
+            gemm_launch(METRPO_ACT_RELU, bs.X, 0, bs.ldx, c->d_dyn.p + pd.dyn.w_off[0], pd.dyn.n_params, pd.dyn.dims[1], c->d_dyn.p + pd.dyn.b_off[0], pd.dyn.n_params,
                         bs.HA, (long long)B * pd.dyn.dims[1], pd.dyn.dims[1], B, pd.dyn.dims[1], bs.ldx, K, st);
             sk.a1.epoch = ++sk_epoch;
             HIP_TRY(c, sk.v1.launch(sk.a1, sk.p1, st));
@@ -999,13 +994,13 @@ static int rollout_gemm_chunk(metrpo_ctx* c, const metrpo_rollout_args* a, hipSt
             const bool lastl = (l == L - 1);
             float* out = lastl ? bs.OUT : bufs[l & 1];
             const long long sOut = (long long)B * N;
-            const float* Wl = c->d_dyn + pd.dyn.w_off[l];
-            const float* bl = c->d_dyn + pd.dyn.b_off[l];
+            const float* Wl = c->d_dyn.p + pd.dyn.w_off[l];
+            const float* bl = c->d_dyn.p + pd.dyn.b_off[l];
             if (fuse_out && l == L - 2) {
-                const float* W2 = c->d_dyn + pd.dyn.w_off[L - 1];
+                const float* W2 = c->d_dyn.p + pd.dyn.w_off[L - 1];
                 gemm_relu_fused_out(fuse_tile, in, sIn, ldin, Wl, pd.dyn.n_params, N, bl, pd.dyn.n_params, W2, pd.dyn.n_params, pd.ns, B, N, Kd, K, bs.PART, st,
                                     &bs.out_splits, &bs.out_stride);
-                bs.out_bias = c->d_dyn + pd.dyn.b_off[L - 1]; bs.out_bias_stride = pd.dyn.n_params;
+                bs.out_bias = c->d_dyn.p + pd.dyn.b_off[L - 1]; bs.out_bias_stride = pd.dyn.n_params;
                 break;
             }
             SkinnyDefer df = {0, 0};
@@ -1014,8 +1009,8 @@ static int rollout_gemm_chunk(metrpo_ctx* c, const metrpo_rollout_args* a, hipSt
             in = out; sIn = sOut; ldin = N;
         }
         if (pre_post && t + 1 < a->T) continue;             // closed by the next step's launch
-        if (pd.ns <= 32) hipLaunchKernelGGL(k_big_post<32>, dim3((B + 7) / 8), dim3(256), 0, st, pd, r, t, c->d_norm, bs);
-        else hipLaunchKernelGGL(k_big_post<64>, dim3((B + 3) / 4), dim3(256), 0, st, pd, r, t, c->d_norm, bs);
+        if (pd.ns <= 32) hipLaunchKernelGGL(k_big_post<32>, dim3((B + 7) / 8), dim3(256), 0, st, pd, r, t, c->d_norm.p, bs);
+        else hipLaunchKernelGGL(k_big_post<64>, dim3((B + 3) / 4), dim3(256), 0, st, pd, r, t, c->d_norm.p, bs);
     }
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
@@ -1083,14 +1078,9 @@ int launch_rollout_gemm(metrpo_ctx* c, const metrpo_rollout_args* a, hipStream_t
     const size_t init_rows = merged ? (size_t)R * B : (par ? (size_t)(R - 1) * B : 0);
     const size_t init_bytes = (init_rows * (pd.ns * sizeof(float) + 2 * sizeof(int32_t)) + 255) & ~(size_t)255;
     const size_t need = ((par && !merged) ? (size_t)R * need1 : need1) + init_bytes;
-    if (need > c->big_cap) {
-        ws_retire(c, c->d_big);
-        c->d_big = nullptr; c->big_cap = 0;
-        HIP_TRY(c, ws_alloc(c, (void**)&c->d_big, need));
-        c->big_cap = need;
-    }
+    { const int rc = ws_grow(c, c->d_big, need); if (rc) return rc; }
     if (merged) {
-        char* base = (char*)c->d_big;
+        char* base = (char*)c->d_big.p;
         float* init_obs = (float*)(base + need1);
         int32_t* init_ts = (int32_t*)(init_obs + (size_t)R * B * pd.ns);
         int32_t* init_model = init_ts + (size_t)R * B;
@@ -1102,7 +1092,7 @@ int launch_rollout_gemm(metrpo_ctx* c, const metrpo_rollout_args* a, hipStream_t
         am.d_init_obs = init_obs; am.d_init_ts = init_ts; am.d_init_model = init_model;
         return rollout_gemm_chunk(c, &am, st, base, nullptr, B, R);
     }
-    if (!par) return rollout_gemm_chunk(c, a, st, (char*)c->d_big, nullptr);
+    if (!par) return rollout_gemm_chunk(c, a, st, (char*)c->d_big.p, nullptr);
     if (!c->side_ready) {
         for (int i = 0; i < METRPO_MAX_PAR_ROUNDS - 1; ++i) {
             HIP_TRY(c, hipStreamCreateWithFlags(&c->side_stream[i], hipStreamNonBlocking));
@@ -1111,7 +1101,7 @@ int launch_rollout_gemm(metrpo_ctx* c, const metrpo_rollout_args* a, hipStream_t
         HIP_TRY(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
         c->side_ready = 1;
     }
-    char* base = (char*)c->d_big;
+    char* base = (char*)c->d_big.p;
     float* init_obs = (float*)(base + (size_t)R * need1);
     int32_t* init_ts = (int32_t*)(init_obs + (size_t)(R - 1) * B * pd.ns);
     int32_t* init_model = init_ts + (size_t)(R - 1) * B;

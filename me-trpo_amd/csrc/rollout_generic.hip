@@ -312,7 +312,7 @@ int launch_policy_actions(metrpo_ctx* c, const float* obs, const float* eps, int
     int rc = pick_block(c, (size_t)pd.ns + 2 * pd.pol.max_width, B, &bs, &sh);
     if (rc) return rc;
     if ((rc = allow_lds(c, k_policy_actions, sh))) return rc;
-    hipLaunchKernelGGL(k_policy_actions, dim3((B + bs - 1) / bs), dim3(bs), sh, st, pd, c->d_theta, obs, eps, B,
+    hipLaunchKernelGGL(k_policy_actions, dim3((B + bs - 1) / bs), dim3(bs), sh, st, pd, c->d_theta.p, obs, eps, B,
                        actions, mean);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
@@ -325,7 +325,7 @@ int launch_step(metrpo_ctx* c, const float* s, const float* a, int B, int sam_mo
     int rc = pick_block(c, envbufs_floats(pd, sam_mode, 1), B, &bs, &sh);
     if (rc) return rc;
     if ((rc = allow_lds(c, k_step, sh))) return rc;
-    hipLaunchKernelGGL(k_step, dim3((B + bs - 1) / bs), dim3(bs), sh, st, pd, c->d_dyn, c->d_norm, s, a, B, sam_mode,
+    hipLaunchKernelGGL(k_step, dim3((B + bs - 1) / bs), dim3(bs), sh, st, pd, c->d_dyn.p, c->d_norm.p, s, a, B, sam_mode,
                        model_idx, noise, s_next, reward, done, next_all);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
@@ -338,8 +338,8 @@ int launch_rollout_generic(metrpo_ctx* c, const metrpo_rollout_args* a, hipStrea
     if (rc) return rc;
     if ((rc = allow_lds(c, k_rollout_generic, sh))) return rc;
     RolloutK r = make_rollout_k(a);
-    hipLaunchKernelGGL(k_rollout_generic, dim3((a->B + bs - 1) / bs), dim3(bs), sh, st, pd, r, c->d_dyn, c->d_theta,
-                       c->d_norm);
+    hipLaunchKernelGGL(k_rollout_generic, dim3((a->B + bs - 1) / bs), dim3(bs), sh, st, pd, r, c->d_dyn.p, c->d_theta.p,
+                       c->d_norm.p);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
 }
@@ -348,7 +348,7 @@ int launch_validation_cost(metrpo_ctx* c, const float* s0, int Bv, int T, double
     const ProblemDesc& pd = c->pd;
     if (c->det_cfg >= 0) {                                   // MFMA forward sweep (bptt_mfma.hip), costs only
         const int rc0 = ensure_detpart(c, Bv); if (rc0) return rc0;
-        return launch_det_forward(c, c->det_cfg, s0, Bv, T, gamma, nullptr, nullptr, c->d_detpart, costs, st);
+        return launch_det_forward(c, c->det_cfg, s0, Bv, T, gamma, nullptr, nullptr, c->d_detpart.p, costs, st);
     }
     if (c->det_gemm) {                                       // large nets: the resident kernel's validation mode where its table has the shape, else the GEMM-path sweep (det_gemm.hip)
         if (ctx_opt(c, OPT_NO_RESIDENT_VALIDATION) == nullptr) {
@@ -363,7 +363,7 @@ int launch_validation_cost(metrpo_ctx* c, const float* s0, int Bv, int T, double
     if ((rc = allow_lds(c, k_validation, sh))) return rc;
     const int gx = (Bv + bs - 1) / bs;
     if ((rc = ensure_detpart_n(c, (size_t)pd.K * gx))) return rc;
-    hipLaunchKernelGGL(k_validation, dim3(gx, pd.K), dim3(bs), sh, st, pd, c->d_dyn, c->d_theta,
-                       c->d_norm, s0, Bv, T, gamma, c->d_detpart);
-    return launch_det_cost_reduce(c, gx, c->d_detpart, costs, st);
+    hipLaunchKernelGGL(k_validation, dim3(gx, pd.K), dim3(bs), sh, st, pd, c->d_dyn.p, c->d_theta.p,
+                       c->d_norm.p, s0, Bv, T, gamma, c->d_detpart.p);
+    return launch_det_cost_reduce(c, gx, c->d_detpart.p, costs, st);
 }

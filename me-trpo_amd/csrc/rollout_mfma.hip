@@ -419,7 +419,7 @@ int launch_rollout_mfma(metrpo_ctx* c, const metrpo_rollout_args* a, hipStream_t
     const int K = c->pd.K;
     size_t sh = sizeof(float) * ((size_t)K * en.w_total + 2 * (size_t)K * 16 * en.nsp);
     const int grid = (a->B + 15) / 16;
-    hipLaunchKernelGGL(en.kern, dim3(grid), dim3(K * 64), sh, st, r, K, c->d_dyn, c->d_theta, c->d_norm);
+    hipLaunchKernelGGL(en.kern, dim3(grid), dim3(K * 64), sh, st, r, K, c->d_dyn.p, c->d_theta.p, c->d_norm.p);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
 }

@@ -1086,20 +1086,16 @@ int launch_rollout_resident(metrpo_ctx* c, const metrpo_rollout_args* a, hipStre
     const int max_cols = std::max(1, n_cu / (K * (DH / pick->ws)));
     const size_t nX = (size_t)Rg * NT * 4 * NIN_KS * 16, nP = (size_t)Rg * NT * K * NSL * 16 * OUT_CB * 16 * (may_rot ? max_cols : 1);
     const size_t need = (nX + nP + 32) * sizeof(unsigned long long);
-    if (need > c->res_cap) {
-        ws_retire(c, c->d_res);
-        c->d_res = nullptr; c->res_cap = 0;
-        // ORDINARY device memory.  The packets only ever move through agent-scope atomics (L2-served, never L1), so the memory type buys nothing:
-        // uncached, fine-grained and ordinary memory all measure 2.73 ms at the params-file shape.  It is ordinary memory because a region that was
-        // allocated hipDeviceMallocUncached and later hipFree'd can come back from hipMalloc as somebody's ordinary buffer with lines of its old
-        // life still sitting in one XCD's L2: seen as a step-wise rollout (rollout_gemm.hip) of a LATER engine reading two stale cache lines of
-        // its fresh workspace, gone after evicting the L2s (tests/test_gpu_resident.py::test_stepwise_workspace_after_freed_resident_regions).
-        HIP_TRY(c, ws_alloc(c, (void**)&c->d_res, need));
-        HIP_TRY(c, hipMemsetAsync(c->d_res, 0, need, st));
-        c->res_cap = need; c->res_seq = 0;
-    }
+    // ORDINARY device memory.  The packets only ever move through agent-scope atomics (L2-served, never L1), so the memory type buys nothing:
+    // uncached, fine-grained and ordinary memory all measure 2.73 ms at the params-file shape.  It is ordinary memory because a region that was
+    // allocated hipDeviceMallocUncached and later hipFree'd can come back from hipMalloc as somebody's ordinary buffer with lines of its old
+    // life still sitting in one XCD's L2: seen as a step-wise rollout (rollout_gemm.hip) of a LATER engine reading two stale cache lines of
+    // its fresh workspace, gone after evicting the L2s (tests/test_gpu_resident.py::test_stepwise_workspace_after_freed_resident_regions).
+    bool grew = false;
+    { const int rc = ws_grow(c, c->d_res, need, &grew); if (rc) return rc; }
+    if (grew) { HIP_TRY(c, hipMemsetAsync(c->d_res.p, 0, need, st)); c->res_seq = 0; }
     if ((unsigned long long)c->res_seq + (unsigned long long)((R + Rg - 1) / Rg) * (steps + 1) >= 0xfffffff0ull) {   // stamps would wrap: start over on a clean region
-        HIP_TRY(c, hipMemsetAsync(c->d_res, 0, c->res_cap, st));
+        HIP_TRY(c, hipMemsetAsync(c->d_res.p, 0, c->d_res.bytes, st));
         c->res_seq = 0;
     }
     if (pick->lds > 64 * 1024) {
@@ -1126,12 +1122,12 @@ int launch_rollout_resident(metrpo_ctx* c, const metrpo_rollout_args* a, hipStre
         // column the partial sums are there before the post wave looks, and the extra round trip of the sentinel read costs 2 - 4 % (half-cheetah, 5 rounds)
         z.sentinel = (pick->threads == 256 && z.NTC <= 4 && !resident_plan_has(c, "nosentinel")) ? 1 : 0;
         if (const char* sk = ctx_opt(c, OPT_RESIDENT_TEST_SKIP)) z.skip_block = atoi(sk);
-        z.abort_cell = (unsigned int*)c->d_res;
-        z.X = (unsigned long long*)c->d_res + 32; z.P = z.X + nX;
+        z.abort_cell = (unsigned int*)c->d_res.p;
+        z.X = (unsigned long long*)c->d_res.p + 32; z.P = z.X + nX;
         z.err = comm_err_cell(c) + 1;                               // scal[S_ROLLERR]
         const int grid = z.U + (rg * NT + PW - 1) / PW;
         if (grid > n_cu) return set_err(c, METRPO_EHIP, "resident rollout: grid larger than the schedulable CUs (launch rule out of step with the census)");
-        hipLaunchKernelGGL(z.rot ? pick->fn_rot : pick->fn, dim3(grid), dim3(pick->threads), pick->lds, st, pd, rk, z, c->d_dyn, c->d_theta, c->d_norm);
+        hipLaunchKernelGGL(z.rot ? pick->fn_rot : pick->fn, dim3(grid), dim3(pick->threads), pick->lds, st, pd, rk, z, c->d_dyn.p, c->d_theta.p, c->d_norm.p);
     }
     HIP_TRY(c, hipGetLastError());
     c->last_rollout_kernel = 4;
@@ -1198,15 +1194,11 @@ int launch_validation_resident(metrpo_ctx* c, const float* s0, int Bv, int T, do
     const int OUT_CB = (pd.ns + 15) / 16, NIN_KS = (pd.nin + 1 + 3) / 4;
     const size_t nX = (size_t)G * 4 * NIN_KS * 16, nP = (size_t)G * K * NSL * 16 * OUT_CB * 16;
     const size_t need = (nX + nP + 32) * sizeof(unsigned long long);
-    if (need > c->res_cap) {
-        ws_retire(c, c->d_res);
-        c->d_res = nullptr; c->res_cap = 0;
-        HIP_TRY(c, ws_alloc(c, (void**)&c->d_res, need));                      // ordinary device memory: see launch_rollout_resident
-        HIP_TRY(c, hipMemsetAsync(c->d_res, 0, need, st));
-        c->res_cap = need; c->res_seq = 0;
-    }
+    bool grew = false;
+    { const int rc = ws_grow(c, c->d_res, need, &grew); if (rc) return rc; }      // ordinary device memory: see launch_rollout_resident
+    if (grew) { HIP_TRY(c, hipMemsetAsync(c->d_res.p, 0, need, st)); c->res_seq = 0; }
     if ((unsigned long long)c->res_seq + (unsigned long long)nb * (T + 1) >= 0xfffffff0ull) {
-        HIP_TRY(c, hipMemsetAsync(c->d_res, 0, c->res_cap, st));
+        HIP_TRY(c, hipMemsetAsync(c->d_res.p, 0, c->d_res.bytes, st));
         c->res_seq = 0;
     }
     { const int rc = ensure_detpart_n(c, (size_t)K * nb * NTM); if (rc) return rc; }
@@ -1217,15 +1209,15 @@ int launch_validation_resident(metrpo_ctx* c, const float* s0, int Bv, int T, do
         const int b_lo = ch * Bc, bn = std::min(Bc, Bv - b_lo);
         ResidentK z;
         z.R = 1; z.round0 = 0; z.rounds_total = 1; z.NT = NTM; z.NSL = NSL; z.U = cols * K * NSL; z.PW = PW; z.steps = T; z.NTC = NTC; z.rot = 0;
-        z.det = 1; z.NTM = NTM; z.gamma = (float)gamma; z.s0 = s0 + (size_t)b_lo * pd.ns; z.det_part = c->d_detpart;
+        z.det = 1; z.NTM = NTM; z.gamma = (float)gamma; z.s0 = s0 + (size_t)b_lo * pd.ns; z.det_part = c->d_detpart.p;
         z.part_stride = nb * NTM; z.part_off = ch * NTM; z.Btot = Bv;
         z.seq0 = c->res_seq; c->res_seq += (unsigned int)T + 1u;
         z.skip_block = -1; z.sentinel = 0;
-        z.abort_cell = (unsigned int*)c->d_res;
-        z.X = (unsigned long long*)c->d_res + 32; z.P = z.X + nX;
+        z.abort_cell = (unsigned int*)c->d_res.p;
+        z.X = (unsigned long long*)c->d_res.p + 32; z.P = z.X + nX;
         z.err = val_err_cell(c);
-        hipLaunchKernelGGL(e->fn[ntw_i], dim3(z.U + post_blocks), dim3(256), e->lds, st, pd, std::max(bn, 0), z, c->d_dyn, c->d_theta, c->d_norm);
+        hipLaunchKernelGGL(e->fn[ntw_i], dim3(z.U + post_blocks), dim3(256), e->lds, st, pd, std::max(bn, 0), z, c->d_dyn.p, c->d_theta.p, c->d_norm.p);
     }
     HIP_TRY(c, hipGetLastError());
-    return launch_det_cost_reduce(c, nb * NTM, c->d_detpart, costs, st, val_err_cell(c));
+    return launch_det_cost_reduce(c, nb * NTM, c->d_detpart.p, costs, st, val_err_cell(c));
 }
