@@ -405,6 +405,16 @@ int32_t metrpo_rms_accumulate(metrpo_ctx* ctx, const float* d_x, int64_t n, int3
  * d_costs [K] float64 (optional) = policy_costs[i] (same values as metrpo_validation_cost); d_grad [P] float64, log_std slots 0. */
 int32_t metrpo_bptt_grad(metrpo_ctx* ctx, const float* d_init, int32_t B, int32_t T, double gamma, double* d_costs,
                          double* d_grad, void* stream);
+/* 'bptt-stochastic' branch (model_based_rl.py:1188-1196): metrpo_bptt_grad with u = clip(mean + eps*exp(log_std)) (training.py:115-116,
+ * model_based_rl.py:128), eps ~ N(0, 1) independently for every (model i, step t, env b, action d); exp acts on the raw log_std parameter.
+ * d_noise [K][T][B][na] float32 (parity mode) or NULL: Philox4x32-10 with key = seed, counter (b, i, t, 4<<16 | d/4), Box-Muller of the
+ * block = eps of action dims 4(d/4) .. 4(d/4)+3 (csrc/device_common.h, RNG_BPTT).  Both sweeps see the same eps.
+ * d_costs [K] f64 (optional) = the stochastic rollout's policy_costs; d_grad [P] f64 incl. the log_std slots
+ * (sum over i, t, b of dcost/du_pre * eps * exp(log_std), float64 in a fixed order);
+ * d_n_saturates [B][na] int32 (optional) = sum over models and steps of |u| == 1 (model_based_rl.py:129). */
+int32_t metrpo_bptt_grad_stochastic(metrpo_ctx* ctx, const float* d_init, int32_t B, int32_t T, double gamma,
+                                    const float* d_noise, uint64_t seed, double* d_costs, double* d_grad,
+                                    int32_t* d_n_saturates, void* stream);
 /* sess.run(policy_adam_init) (model_based_rl.py:202-204): zero the policy optimizer's moments and step count. */
 int32_t metrpo_policy_adam_reset(metrpo_ctx* ctx, void* stream);
 /* The policy optimizer's state (adam_<policy scope> of get_policy_optimizer, model_based_rl.py:186-204): d_m, d_v [policy_param_count]

@@ -107,6 +107,7 @@ SYMBOLS = {
     'metrpo_set_normalizers': (_I, [_P, _P, _P, _P, _P, _P]),
     'metrpo_rms_accumulate': (_I, [_P, _P, _L, _I, _P, _P, _P]),
     'metrpo_bptt_grad': (_I, [_P, _P, _I, _I, _D, _P, _P, _P]),
+    'metrpo_bptt_grad_stochastic': (_I, [_P, _P, _I, _I, _D, _P, C.c_uint64, _P, _P, _P, _P]),
     'metrpo_set_exclusive': (_I, [_P, _I]),
     'metrpo_set_option': (_I, [_P, C.c_char_p, C.c_char_p]),
     'metrpo_get_option': (_I, [_P, C.c_char_p, C.c_char_p, _I]),

@@ -901,6 +901,18 @@ extern "C" int32_t metrpo_bptt_grad(metrpo_ctx* c, const float* init, int32_t B,
     return launch_bptt_grad(c, init, B, T, gamma, costs, grad, (hipStream_t)stream);
 }
 
+extern "C" int32_t metrpo_bptt_grad_stochastic(metrpo_ctx* c, const float* init, int32_t B, int32_t T, double gamma, const float* noise,
+                                               uint64_t seed, double* costs, double* grad, int32_t* n_saturates, void* stream) {
+    TraceRange trace_("metrpo:bptt_grad_stochastic");
+    if (!c) return METRPO_ENULL;
+    NEED_DYN(c); NEED_POL(c);
+    if (B <= 0 || T <= 0) return set_err(c, METRPO_EINVAL, "bptt_grad_stochastic: B and T must be positive");
+    if (!init) return set_err(c, METRPO_ENULL, "bptt_grad_stochastic: NULL pointer");
+    BpttNoise nz;
+    nz.eps = noise; nz.log_std = c->d_theta.p + c->pd.pol.n_params; nz.n_sat = n_saturates; nz.seed = seed; nz.T = T;
+    return launch_bptt_grad(c, init, B, T, gamma, costs, grad, (hipStream_t)stream, &nz);
+}
+
 extern "C" int32_t metrpo_policy_adam_reset(metrpo_ctx* c, void* stream) {
     if (!c) return METRPO_ENULL;
     return launch_policy_adam(c, nullptr, 0.0, 0.9, 0.999, 1e-8, 0.0, true, (hipStream_t)stream);

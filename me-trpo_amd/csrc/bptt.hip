@@ -89,10 +89,24 @@ __device__ __forceinline__ void cost_adjoint(int env, int ns, int na, const floa
     for (int d = 0; d < na; ++d) gU[d * LD + tid] = cu * u[d * LD + tid];
 }
 
+// STOCH ('bptt-stochastic'): the policy mean gets the noise of nz before the clip, u = clip(mean + eps exp(log_std)) (training.py:115-116);
+// the deterministic instantiations never read nz.
+// eps of action dim d of (model, t, env b): e4[d & 3] after bptt_eps4 for chunk d >> 2 (drawn when d % 4 == 0); u_pre returned
+template <bool STOCH>
+__device__ __forceinline__ float bptt_noisy_mean(const BpttNoise& nz, int model, int t, int B, int b, bool active, int na, int d, float m, float e4[4]) {
+    if (!STOCH) return m;
+    if ((d & 3) == 0) {
+        if (active) bptt_eps4(nz, model, t, B, b, na, d >> 2, e4);
+        else e4[0] = e4[1] = e4[2] = e4[3] = 0.0f;
+    }
+    return fmaf(e4[d & 3], expf(nz.log_std[d]), m);
+}
+
 // XS [K][T+1][B][ns], WT [K][T][B], costs [K] (+=)
+template <bool STOCH>
 __global__ void k_bptt_forward(ProblemDesc pd, const float* __restrict__ dynp, const float* __restrict__ theta, const float* __restrict__ norm,
                                const float* __restrict__ s0, int B, int T, double gamma, float* __restrict__ XS, float* __restrict__ WT,
-                               double* __restrict__ costs) {
+                               double* __restrict__ costs, BpttNoise nz) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ double red[16];
     const int LD = blockDim.x, tid = threadIdx.x;
@@ -109,7 +123,12 @@ __global__ void k_bptt_forward(ProblemDesc pd, const float* __restrict__ dynp, c
     float dones = 0.0f;
     for (int t = 0; t < T; ++t) {
         float* m = mlp_col(pd.pol, theta, e.S, e.GA, e.GB, LD, tid);
-        for (int d = 0; d < na; ++d) e.U[d * LD + tid] = fminf(fmaxf(m[d * LD + tid], -1.0f), 1.0f);        // :128
+        float e4[4];
+        for (int d = 0; d < na; ++d) {
+            const float u = fminf(fmaxf(bptt_noisy_mean<STOCH>(nz, model, t, B, b, active, na, d, m[d * LD + tid], e4), -1.0f), 1.0f);   // :128
+            e.U[d * LD + tid] = u;
+            if (STOCH && nz.n_sat != nullptr && active && fabsf(u) == 1.0f) atomicAdd(&nz.n_sat[(size_t)b * na + d], 1);       // :129
+        }
         for (int i = 0; i < ns; ++i) e.X[i * LD + tid] = (e.S[i * LD + tid] - in_mean[i]) / in_std[i];
         for (int d = 0; d < na; ++d) e.X[(ns + d) * LD + tid] = (e.U[d * LD + tid] - in_mean[ns + d]) / in_std[ns + d];
         float* out = mlp_col(pd.dyn, pk, e.X + pd.n_drop * LD, e.GA, e.GB, LD, tid);
@@ -129,9 +148,11 @@ __global__ void k_bptt_forward(ProblemDesc pd, const float* __restrict__ dynp, c
     if (tid == 0) costs[(size_t)model * gridDim.x + blockIdx.x] = tot / (double)B;      // one partial per block; added in block order by k_det_cost_reduce
 }
 
-// GM [K][T+1][B][na]: adjoint of the (pre-clip) policy mean for every sample; slice t = T stays zero
+// GM [K][T+1][B][na]: adjoint of the (pre-clip) policy mean for every sample; slice t = T stays zero.  STOCH: the clip gate is taken on
+// mean + eps exp(log_std), eps recomputed (d u_pre / d mean = 1, so GM keeps its meaning)
+template <bool STOCH>
 __global__ void k_bptt_backward(ProblemDesc pd, const float* __restrict__ dynp, const float* __restrict__ theta, const float* __restrict__ norm,
-                                int B, int T, const float* __restrict__ XS, const float* __restrict__ WT, float* __restrict__ GM) {
+                                int B, int T, const float* __restrict__ XS, const float* __restrict__ WT, float* __restrict__ GM, BpttNoise nz) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int LD = blockDim.x, tid = threadIdx.x;
     const int b = blockIdx.x * blockDim.x + tid, model = blockIdx.y;
@@ -151,8 +172,12 @@ __global__ void k_bptt_backward(ProblemDesc pd, const float* __restrict__ dynp, 
         }
         const float w = active ? WT[((size_t)model * T + t) * B + b] : 0.0f;
         // ---- recompute the step: policy (all layer outputs kept), clip, normalise, dynamics hidden layers ----
-        float* mu = mlp_col_store(pn, theta, e.S, e.PH, nullptr, LD, tid);
-        for (int d = 0; d < na; ++d) e.U[d * LD + tid] = fminf(fmaxf(mu[d * LD + tid], -1.0f), 1.0f);
+        float* mu = mlp_col_store(pn, theta, e.S, e.PH, nullptr, LD, tid);         // output rows: not read by the policy VJP below
+        float e4[4];
+        for (int d = 0; d < na; ++d) {
+            if (STOCH) mu[d * LD + tid] = bptt_noisy_mean<STOCH>(nz, model, t, B, b, active, na, d, mu[d * LD + tid], e4);
+            e.U[d * LD + tid] = fminf(fmaxf(mu[d * LD + tid], -1.0f), 1.0f);
+        }
         for (int i = 0; i < ns; ++i) e.X[i * LD + tid] = (e.S[i * LD + tid] - in_mean[i]) / in_std[i];
         for (int d = 0; d < na; ++d) e.X[(ns + d) * LD + tid] = (e.U[d * LD + tid] - in_mean[ns + d]) / in_std[ns + d];
         {
@@ -224,7 +249,8 @@ __global__ void k_bptt_backward(ProblemDesc pd, const float* __restrict__ dynp, 
     }
 }
 
-// tf.clip_by_norm per variable + tf.train.AdamOptimizer on theta (one block per variable: W_l, b_l; log_std has zero gradient here)
+// tf.clip_by_norm per variable + tf.train.AdamOptimizer on theta (one block per variable: W_l, b_l, log_std; the log_std gradient is 0 in
+// the 'bptt' branch and k_bptt_logstd_* in 'bptt-stochastic')
 __global__ void k_policy_adam(int n_seg, const int* __restrict__ seg_off, const double* __restrict__ grad, float* __restrict__ theta,
                               float* __restrict__ am, float* __restrict__ av, float lr_t, float b1, float b2, float eps, double clip_val) {
     __shared__ double red[16];
@@ -244,57 +270,99 @@ __global__ void k_policy_adam(int n_seg, const int* __restrict__ seg_off, const 
     }
 }
 
+// 'bptt-stochastic' log_std gradient (bptt.hip header; the mean-adjoint GM is the adjoint of u_pre = mean + eps exp(log_std)):
+//   g[log_std_d] = exp(p_d) * sum_{i,t,b} GM[i][t][b][d] eps[i][t][b][d]
+// float64 in a fixed order: thread (block x, lane l) of action chunk blockIdx.y sums the samples s = (i T + t) B + b with s = 256 x + l mod
+// (gridDim.x 256), in increasing s; the block's tree (block_sum) gives one partial per (chunk, block, dim); k_bptt_logstd_final adds a dim's
+// partials in block order.  eps is recomputed exactly as the sweeps drew it (bptt_eps4), so nothing of [K][T][B][na] size is stored.
+constexpr int LOGSTD_BLOCKS = 128;
+__global__ void __launch_bounds__(256) k_bptt_logstd_part(int K, int T, int B, int na, const float* __restrict__ GM, BpttNoise nz,
+                                                          double* __restrict__ part) {
+    __shared__ double red[16];
+    const int ch = blockIdx.y;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    const long long n = (long long)K * T * B;
+    for (long long s = (long long)blockIdx.x * 256 + threadIdx.x; s < n; s += (long long)gridDim.x * 256) {
+        const int b = (int)(s % B);
+        const long long it = s / B;
+        const int t = (int)(it % T), i = (int)(it / T);
+        float e[4];
+        bptt_eps4(nz, i, t, B, b, na, ch, e);
+        const float* gm = GM + (((size_t)i * (T + 1) + t) * B + b) * na;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (4 * ch + j < na) acc[j] += (double)gm[4 * ch + j] * (double)e[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const double v = block_sum(acc[j], red);
+        if (threadIdx.x == 0) part[((size_t)ch * gridDim.x + blockIdx.x) * 4 + j] = v;
+    }
+}
+
+// out[d] (the log_std slots of the gradient) = exp(p_d) * the nblk partials of dim d added in block order
+__global__ void k_bptt_logstd_final(int na, int nblk, const double* __restrict__ part, const float* __restrict__ log_std, double* __restrict__ out) {
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= na) return;
+    double s = 0.0;
+    for (int x = 0; x < nblk; ++x) s += part[((size_t)(d >> 2) * nblk + x) * 4 + (d & 3)];
+    out[d] = s * exp((double)log_std[d]);
+}
+
 // -------------------------------------------------------------------------------------------------
-int launch_bptt_grad(metrpo_ctx* c, const float* init, int B, int T, double gamma, double* costs, double* grad, hipStream_t st) {
+// nz == NULL: the 'bptt' gradient; otherwise 'bptt-stochastic' with the noise of *nz (nz->n_sat zeroed here when set)
+int launch_bptt_grad(metrpo_ctx* c, const float* init, int B, int T, double gamma, double* costs, double* grad, hipStream_t st, const BpttNoise* nz) {
     const ProblemDesc& pd = c->pd;
     const int K = pd.K, ns = pd.ns, na = pd.na;
+    const int nchunk = (na + 3) / 4;
     const size_t nXS = (((size_t)K * (T + 1) * B * ns) + 3) & ~(size_t)3, nWT = (((size_t)K * T * B) + 3) & ~(size_t)3,
                  nGM = (((size_t)K * (T + 1) * B * na) + 3) & ~(size_t)3;
-    const size_t need = (nXS + nWT + nGM) * sizeof(float) + sizeof(double) * (size_t)(pd.P + 1 + K);
+    const size_t nLS = nz ? (size_t)nchunk * LOGSTD_BLOCKS * 4 : 0;
+    const size_t need = (nXS + nWT + nGM) * sizeof(float) + sizeof(double) * (size_t)(pd.P + 1 + K + nLS);
     if (c->det_cfg >= 0) { const int rc0 = ensure_detpart(c, B); if (rc0) return rc0; }
     { const int rc = ws_grow(c, c->d_bptt, need); if (rc) return rc; }
     float* XS = (float*)c->d_bptt.p; float* WT = XS + nXS; float* GM = WT + nWT;
-    double* gout = (double*)(GM + nGM); double* cst = gout + pd.P + 1;
+    double* gout = (double*)(GM + nGM); double* cst = gout + pd.P + 1; double* lpart = cst + K;
     HIP_TRY(c, hipMemsetAsync(GM, 0, sizeof(float) * nGM, st));
+    if (nz && nz->n_sat) HIP_TRY(c, hipMemsetAsync(nz->n_sat, 0, sizeof(int) * (size_t)B * na, st));
     if (c->det_cfg >= 0) {                                   // MFMA sweeps (bptt_mfma.hip)
-        int rc1 = launch_det_forward(c, c->det_cfg, init, B, T, gamma, XS, WT, c->d_detpart.p, cst, st);
+        int rc1 = launch_det_forward(c, c->det_cfg, init, B, T, gamma, XS, WT, c->d_detpart.p, cst, st, nz);
         if (rc1) return rc1;
-        if ((rc1 = launch_det_backward(c, c->det_cfg, B, T, XS, WT, GM, st))) return rc1;
-        const int rc2 = launch_policy_vjp(c, XS, GM, (long long)K * (T + 1) * B, gout, st);
-        if (rc2) return rc2;
-        if (grad) HIP_TRY(c, hipMemcpyAsync(grad, gout + 1, sizeof(double) * pd.P, hipMemcpyDeviceToDevice, st));
-        if (costs) HIP_TRY(c, hipMemcpyAsync(costs, cst, sizeof(double) * K, hipMemcpyDeviceToDevice, st));
-        return METRPO_OK;
-    }
-    if (c->det_gemm) {                                       // GEMM-path sweeps for large dynamics nets (det_gemm.hip)
-        int rc1 = launch_dg_forward(c, init, B, T, gamma, XS, WT, cst, st);
+        if ((rc1 = launch_det_backward(c, c->det_cfg, B, T, XS, WT, GM, st, nz))) return rc1;
+    } else if (c->det_gemm) {                                // GEMM-path sweeps for large dynamics nets (det_gemm.hip)
+        int rc1 = launch_dg_forward(c, init, B, T, gamma, XS, WT, cst, st, nz);
         if (rc1) return rc1;
-        if ((rc1 = launch_dg_backward(c, B, T, XS, WT, GM, st))) return rc1;
-        const int rc2 = launch_policy_vjp(c, XS, GM, (long long)K * (T + 1) * B, gout, st);
-        if (rc2) return rc2;
-        if (grad) HIP_TRY(c, hipMemcpyAsync(grad, gout + 1, sizeof(double) * pd.P, hipMemcpyDeviceToDevice, st));
-        if (costs) HIP_TRY(c, hipMemcpyAsync(costs, cst, sizeof(double) * K, hipMemcpyDeviceToDevice, st));
-        return METRPO_OK;
+        if ((rc1 = launch_dg_backward(c, B, T, XS, WT, GM, st, nz))) return rc1;
+    } else {
+        const size_t fpt = bptt_floats(pd);
+        const size_t LDS_MAX = 160 * 1024;
+        int bs = 64;
+        while (bs > 1 && fpt * bs * sizeof(float) > LDS_MAX) bs >>= 1;
+        if (fpt * bs * sizeof(float) > LDS_MAX) return set_err(c, METRPO_EUNSUPPORTED, "bptt: layer widths exceed the LDS budget of the generic kernel");
+        const size_t sh = fpt * bs * sizeof(float);
+        const void* fwd = nz ? (const void*)k_bptt_forward<true> : (const void*)k_bptt_forward<false>;
+        const void* bwd = nz ? (const void*)k_bptt_backward<true> : (const void*)k_bptt_backward<false>;
+        if (sh > 64 * 1024) {
+            HIP_TRY(c, hipFuncSetAttribute(fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+            HIP_TRY(c, hipFuncSetAttribute(bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+        }
+        const dim3 grid((B + bs - 1) / bs, K);
+        const BpttNoise nz0 = nz ? *nz : BpttNoise{};
+        { const int rcp = ensure_detpart_n(c, (size_t)K * grid.x); if (rcp) return rcp; }
+        if (nz) hipLaunchKernelGGL(k_bptt_forward<true>, grid, dim3(bs), sh, st, pd, c->d_dyn.p, c->d_theta.p, c->d_norm.p, init, B, T, gamma, XS, WT, c->d_detpart.p, nz0);
+        else hipLaunchKernelGGL(k_bptt_forward<false>, grid, dim3(bs), sh, st, pd, c->d_dyn.p, c->d_theta.p, c->d_norm.p, init, B, T, gamma, XS, WT, c->d_detpart.p, nz0);
+        { const int rcp = launch_det_cost_reduce(c, (int)grid.x, c->d_detpart.p, cst, st); if (rcp) return rcp; }
+        if (nz) hipLaunchKernelGGL(k_bptt_backward<true>, grid, dim3(bs), sh, st, pd, c->d_dyn.p, c->d_theta.p, c->d_norm.p, B, T, XS, WT, GM, nz0);
+        else hipLaunchKernelGGL(k_bptt_backward<false>, grid, dim3(bs), sh, st, pd, c->d_dyn.p, c->d_theta.p, c->d_norm.p, B, T, XS, WT, GM, nz0);
+        HIP_TRY(c, hipGetLastError());
     }
-    const size_t fpt = bptt_floats(pd);
-    const size_t LDS_MAX = 160 * 1024;
-    int bs = 64;
-    while (bs > 1 && fpt * bs * sizeof(float) > LDS_MAX) bs >>= 1;
-    if (fpt * bs * sizeof(float) > LDS_MAX) return set_err(c, METRPO_EUNSUPPORTED, "bptt: layer widths exceed the LDS budget of the generic kernel");
-    const size_t sh = fpt * bs * sizeof(float);
-    if (sh > 64 * 1024) {
-        HIP_TRY(c, hipFuncSetAttribute((const void*)k_bptt_forward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        HIP_TRY(c, hipFuncSetAttribute((const void*)k_bptt_backward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-    }
-    const dim3 grid((B + bs - 1) / bs, K);
-    { const int rcp = ensure_detpart_n(c, (size_t)K * grid.x); if (rcp) return rcp; }
-    hipLaunchKernelGGL(k_bptt_forward, grid, dim3(bs), sh, st, pd, c->d_dyn.p, c->d_theta.p, c->d_norm.p, init, B, T, gamma, XS, WT, c->d_detpart.p);
-    { const int rcp = launch_det_cost_reduce(c, (int)grid.x, c->d_detpart.p, cst, st); if (rcp) return rcp; }
-    hipLaunchKernelGGL(k_bptt_backward, grid, dim3(bs), sh, st, pd, c->d_dyn.p, c->d_theta.p, c->d_norm.p, B, T, XS, WT, GM);
-    HIP_TRY(c, hipGetLastError());
     // policy-parameter gradient: sum over the K (T+1) B samples of J(x)^T gm  (gradient kernels of the TRPO update, mean-adjoint supplied)
     const int rc = launch_policy_vjp(c, XS, GM, (long long)K * (T + 1) * B, gout, st);
     if (rc) return rc;
+    if (nz) {                                                // the log_std slots (0 from the VJP: the mean does not depend on log_std)
+        hipLaunchKernelGGL(k_bptt_logstd_part, dim3(LOGSTD_BLOCKS, nchunk), dim3(256), 0, st, K, T, B, na, (const float*)GM, *nz, lpart);
+        hipLaunchKernelGGL(k_bptt_logstd_final, dim3((na + 63) / 64), dim3(64), 0, st, na, LOGSTD_BLOCKS, (const double*)lpart, nz->log_std, gout + 1 + pd.pol.n_params);
+        HIP_TRY(c, hipGetLastError());
+    }
     if (grad) HIP_TRY(c, hipMemcpyAsync(grad, gout + 1, sizeof(double) * pd.P, hipMemcpyDeviceToDevice, st));
     if (costs) HIP_TRY(c, hipMemcpyAsync(costs, cst, sizeof(double) * K, hipMemcpyDeviceToDevice, st));
     return METRPO_OK;

@@ -48,11 +48,13 @@ __device__ __forceinline__ float cost_row(const float* xn, const float* u, int N
     return 0.0f;
 }
 
-template <int ENV, int MODE>
+// STOCH ('bptt-stochastic', bptt.hip): mu becomes mean + eps exp(log_std) before the clip in both sweeps (lane (c, q) draws chunk q of env c,
+// bptt_eps4), so the reverse sweep's clip gate sees the forward sweep's pre-clip action; the deterministic instantiations never read nz.
+template <int ENV, int MODE, bool STOCH>
 __global__ void __launch_bounds__(256, 2) k_det_mfma(int K, int B, int T, double gamma, const float* __restrict__ dynp,
                                                     const float* __restrict__ theta, const float* __restrict__ norm,
                                                     const float* __restrict__ s0, float* __restrict__ XS, float* __restrict__ WT,
-                                                    float* __restrict__ GM, double* __restrict__ cost_part) {
+                                                    float* __restrict__ GM, double* __restrict__ cost_part, BpttNoise nz) {
     using L = DetL<ENV>;
     using C = typename L::C;
     constexpr int NS = C::NS, NA = C::NA, NDROP = C::NDROP, NIN = C::NIN, DH = 64, PH = 32, OUT_CB = C::OUT_CB, NS_KS = C::NS_KS,
@@ -136,11 +138,15 @@ __global__ void __launch_bounds__(256, 2) k_det_mfma(int K, int B, int T, double
             dstd[cb][r] = (dim < NS) ? norm[2 * (NS + NA) + NS + dim] : 0.0f;
         }
     const size_t xs_model = (size_t)model * (T + 1) * B * NS;
+    float sd[4];                                                             // exp(log_std) of the action dims 4q .. 4q+3 (STOCH)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) sd[r] = (STOCH && 4 * q + r < NA) ? expf(nz.log_std[4 * q + r]) : 0.0f;
     __syncthreads();
 
     // one step of the forward computations shared by both modes: policy chain -> clip -> ACT; dynamics layers 0, 1
     f32x4 p0[2], p1[2], mu, h0[4], h1[4];
-    auto step_forward = [&]() {
+    int nsat[4] = {0, 0, 0, 0};                                              // STOCH forward: |u| == 1 count of (env c, dim 4q + r) over t
+    auto step_forward = [&](int t) {
         p0[0] = *(const f32x4*)&IMG[L::O_BP0 + 4 * q]; p0[1] = *(const f32x4*)&IMG[L::O_BP0 + 16 + 4 * q];
 #pragma unroll
         for (int s = 0; s < NS_KS; ++s) {
@@ -170,8 +176,21 @@ __global__ void __launch_bounds__(256, 2) k_det_mfma(int K, int B, int T, double
             m1 = MFMA16(IMG[L::O_PF2 + (kk + 1) * 64 + lane], p1[(kk + 1) >> 2][(kk + 1) & 3], m1);
         }
         mu = m0 + m1;
+        if (STOCH && 4 * q < NA) {
+            float e[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (active) bptt_eps4(nz, model, t, B, b, NA, q, e);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { const int d = 4 * q + r; if (d < NA) ACT[c * NA + d] = fminf(fmaxf(mu[r], -1.0f), 1.0f); }      // :128
+            for (int r = 0; r < 4; ++r) mu[r] = fmaf(e[r], sd[r], mu[r]);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int d = 4 * q + r;
+            if (d < NA) {
+                const float u = fminf(fmaxf(mu[r], -1.0f), 1.0f);                                       // :128
+                ACT[c * NA + d] = u;
+                if (STOCH && MODE == DET_FWD && fabsf(u) == 1.0f) ++nsat[r];                                 // :129
+            }
+        }
         wave_lds_sync();
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb) h0[cb] = *(const f32x4*)&IMG[L::O_BD0 + 16 * cb + 4 * q];
@@ -209,7 +228,7 @@ __global__ void __launch_bounds__(256, 2) k_det_mfma(int K, int B, int T, double
         float dones = 0.0f;
         for (int t = 0; t < T; ++t) {
             if (XS != nullptr) for (int i = lane; i < lim; i += 64) XS[xs_model + ((size_t)t * B + b0) * NS + i] = ST[i];
-            step_forward();
+            step_forward(t);
             f32x4 oa[OUT_CB], ob[OUT_CB];
 #pragma unroll
             for (int cb = 0; cb < OUT_CB; ++cb) { oa[cb] = *(const f32x4*)&IMG[L::O_BD2 + 16 * cb + 4 * q]; ob[cb] = f32x4{0.f, 0.f, 0.f, 0.f}; }
@@ -247,6 +266,9 @@ __global__ void __launch_bounds__(256, 2) k_det_mfma(int K, int B, int T, double
             wave_lds_sync();
         }
         if (XS != nullptr) for (int i = lane; i < lim; i += 64) XS[xs_model + ((size_t)T * B + b0) * NS + i] = ST[i];
+        if (STOCH && nz.n_sat != nullptr && active)                          // one add per (model, env, dim): the models share a cell
+#pragma unroll
+            for (int r = 0; r < 4; ++r) if (4 * q + r < NA && nsat[r] != 0) atomicAdd(&nz.n_sat[(size_t)b * NA + 4 * q + r], nsat[r]);
         // deterministic cost reduction: lanes -> wave (shuffles) -> one slot per (model, tile)
         for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
         if (lane == 0) cost_part[(size_t)model * (gridDim.x * 4) + blockIdx.x * 4 + wave] = acc / (double)B;
@@ -262,7 +284,7 @@ __global__ void __launch_bounds__(256, 2) k_det_mfma(int K, int B, int T, double
             }
             const float w = active ? WT[((size_t)model * T + t) * B + b] : 0.0f;
             wave_lds_sync();
-            step_forward();
+            step_forward(t);
             // ---- cost adjoint in D layout: G = lambda_{t+1} + w dc/dx_next (state dims), gU = w dc/du (action dims) ----
             f32x4 G[OUT_CB], gU = {0.f, 0.f, 0.f, 0.f};
             float cu = 0.0f;
@@ -399,9 +421,9 @@ int launch_det_cost_reduce(metrpo_ctx* c, int n_part, const double* part, double
 }
 
 // -------------------------------------------------------------------------------------------------
-typedef void (*det_kernel_t)(int, int, int, double, const float*, const float*, const float*, const float*, float*, float*, float*, double*);
-struct DetEntry { int env; det_kernel_t fwd, bwd; int lds_floats; };
-#define DENTRY(E) {E, k_det_mfma<E, DET_FWD>, k_det_mfma<E, DET_BWD>, DetL<E>::TOTAL}
+typedef void (*det_kernel_t)(int, int, int, double, const float*, const float*, const float*, const float*, float*, float*, float*, double*, BpttNoise);
+struct DetEntry { int env; det_kernel_t fwd, bwd, fwd_s, bwd_s; int lds_floats; };       // _s: the 'bptt-stochastic' sweeps
+#define DENTRY(E) {E, k_det_mfma<E, DET_FWD, false>, k_det_mfma<E, DET_BWD, false>, k_det_mfma<E, DET_FWD, true>, k_det_mfma<E, DET_BWD, true>, DetL<E>::TOTAL}
 static const DetEntry kDet[] = {DENTRY(METRPO_ENV_SWIMMER), DENTRY(METRPO_ENV_HALF_CHEETAH), DENTRY(METRPO_ENV_HOPPER), DENTRY(METRPO_ENV_SNAKE),
                                 DENTRY(METRPO_ENV_ANT)};
 
@@ -418,29 +440,32 @@ int det_mfma_select(const metrpo_ctx* c) {
 }
 
 // part: >= K * tiles4 doubles of scratch (tiles4 = 4 * ceil(B/64)).  XS / WT may be NULL (validation cost only).
+// nz: the 'bptt-stochastic' noise (NULL: deterministic)
 int launch_det_forward(metrpo_ctx* c, int idx, const float* s0, int B, int T, double gamma, float* XS, float* WT, double* part, double* costs,
-                       hipStream_t st) {
+                       hipStream_t st, const BpttNoise* nz) {
     const DetEntry& en = kDet[idx];
+    const det_kernel_t fwd = nz ? en.fwd_s : en.fwd;
     const size_t sh = sizeof(float) * (size_t)en.lds_floats;
-    if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)en.fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+    if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
     const int gx = (B + 63) / 64;
     const float* dyn = c->d_dyn.p;
     if (c->det_padded) { const int rc = launch_pad_dyn(c, st); if (rc) return rc; dyn = c->d_dyn_pad.p; }
-    hipLaunchKernelGGL(en.fwd, dim3(gx, c->pd.K), dim3(256), sh, st, c->pd.K, B, T, gamma, dyn, c->d_theta.p, c->d_norm.p, s0, XS, WT,
-                       (float*)nullptr, part);
+    hipLaunchKernelGGL(fwd, dim3(gx, c->pd.K), dim3(256), sh, st, c->pd.K, B, T, gamma, dyn, c->d_theta.p, c->d_norm.p, s0, XS, WT,
+                       (float*)nullptr, part, nz ? *nz : BpttNoise{});
     hipLaunchKernelGGL(k_det_cost_reduce, dim3(c->pd.K), dim3(64), 0, st, gx * 4, part, costs, (const double*)nullptr);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
 }
 
-int launch_det_backward(metrpo_ctx* c, int idx, int B, int T, const float* XS, const float* WT, float* GM, hipStream_t st) {
+int launch_det_backward(metrpo_ctx* c, int idx, int B, int T, const float* XS, const float* WT, float* GM, hipStream_t st, const BpttNoise* nz) {
     const DetEntry& en = kDet[idx];
+    const det_kernel_t bwd = nz ? en.bwd_s : en.bwd;
     const size_t sh = sizeof(float) * (size_t)en.lds_floats;
-    if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)en.bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+    if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
     const float* dyn = c->d_dyn.p;
     if (c->det_padded) { const int rc = launch_pad_dyn(c, st); if (rc) return rc; dyn = c->d_dyn_pad.p; }
-    hipLaunchKernelGGL(en.bwd, dim3((B + 63) / 64, c->pd.K), dim3(256), sh, st, c->pd.K, B, T, 1.0, dyn, c->d_theta.p, c->d_norm.p,
-                       (const float*)nullptr, const_cast<float*>(XS), const_cast<float*>(WT), GM, (double*)nullptr);
+    hipLaunchKernelGGL(bwd, dim3((B + 63) / 64, c->pd.K), dim3(256), sh, st, c->pd.K, B, T, 1.0, dyn, c->d_theta.p, c->d_norm.p,
+                       (const float*)nullptr, const_cast<float*>(XS), const_cast<float*>(WT), GM, (double*)nullptr, nz ? *nz : BpttNoise{});
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
 }

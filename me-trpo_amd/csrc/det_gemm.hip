@@ -21,9 +21,14 @@ struct DgState {
     int out_splits; long long out_stride; const float* out_bias; long long out_bias_stride;
 };
 
+// The three pre-step kernels serve both sweeps of step t.  STOCH ('bptt-stochastic', bptt.hip): MU is the pre-clip action mean + eps exp(log_std)
+// (bptt_eps4 of (k, t, b)), so k_dg_back's clip gate needs no change; the forward sweep (xs_t == NULL) also counts |u| == 1 into nz.n_sat.
+// The deterministic instantiations never read nz.
+
 // thread = row (k, b): policy forward of the current state, clipped action, pre-clip mean, normalised + dropped dynamics input
+template <bool STOCH>
 __global__ void k_dg_pre(ProblemDesc pd, int B, const float* __restrict__ theta, const float* __restrict__ norm, const float* __restrict__ xs_t,
-                         long long xs_model_stride, DgState st) {
+                         long long xs_model_stride, DgState st, BpttNoise nz, int t) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int LD = blockDim.x, tid = threadIdx.x;
     const int b = blockIdx.x * blockDim.x + tid, k = blockIdx.y;
@@ -41,19 +46,25 @@ __global__ void k_dg_pre(ProblemDesc pd, int B, const float* __restrict__ theta,
         if (xs_t != nullptr) st.S[row * ns + i] = s;
         if (i >= pd.n_drop) st.X[row * pd.nin + i - pd.n_drop] = (s - in_mean[i]) / in_std[i];
     }
+    float e[4];
     for (int d = 0; d < na; ++d) {
-        const float mu = m[d * LD + tid];
+        float mu = m[d * LD + tid];
+        if (STOCH) {
+            if ((d & 3) == 0) bptt_eps4(nz, k, t, B, b, na, d >> 2, e);
+            mu = fmaf(e[d & 3], expf(nz.log_std[d]), mu);
+        }
         const float ac = fminf(fmaxf(mu, -1.0f), 1.0f);                                   // model_based_rl.py:128
         st.MU[row * na + d] = mu; st.U[row * na + d] = ac;
         st.X[row * pd.nin + (ns - pd.n_drop) + d] = (ac - in_mean[ns + d]) / in_std[ns + d];
+        if (STOCH && xs_t == nullptr && nz.n_sat != nullptr && fabsf(ac) == 1.0f) atomicAdd(&nz.n_sat[(size_t)b * na + d], 1);   // :129
     }
 }
 
 // MFMA variant of k_dg_pre for the 2x32 tanh policies: a wave evaluates the policy of a 16-row tile of one model as the transposed MFMA
 // chain of the fused kernels (30 MFMAs) instead of 64 threads walking three dense layers each.  grid = (ceil(B/64), K) blocks of 4 waves.
-template <int ENV>
+template <int ENV, bool STOCH>
 __global__ void __launch_bounds__(256) k_dg_pre_mfma(ProblemDesc pd, int B, const float* __restrict__ theta, const float* __restrict__ norm,
-                                                     const float* __restrict__ xs_t, long long xs_model_stride, DgState st) {
+                                                     const float* __restrict__ xs_t, long long xs_model_stride, DgState st, BpttNoise nz, int t) {
     using C = Cfg<ENV, 64, 32>;
     constexpr int NS = C::NS, NA = C::NA, NDROP = C::NDROP, NIN = C::NIN, PH = 32, NS_KS = C::NS_KS;
     constexpr int O_PF1 = NS_KS * 2 * 64, O_PF2 = O_PF1 + 16 * 64, O_B0 = O_PF2 + 8 * 64, O_B1 = O_B0 + 32, O_B2 = O_B1 + 32, IMG = O_B2 + 16;
@@ -113,8 +124,14 @@ __global__ void __launch_bounds__(256) k_dg_pre_mfma(ProblemDesc pd, int B, cons
         m0 = MFMA16(lds[O_PF2 + kk * 64 + lane], p1[kk >> 2][kk & 3], m0);
         m1 = MFMA16(lds[O_PF2 + (kk + 1) * 64 + lane], p1[(kk + 1) >> 2][(kk + 1) & 3], m1);
     }
-    const f32x4 mu = m0 + m1;
+    f32x4 mu = m0 + m1;
     if (!active) return;
+    if (STOCH && 4 * q < NA) {
+        float e[4];
+        bptt_eps4(nz, k, t, B, b, NA, q, e);
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) if (4 * q + rr < NA) mu[rr] = fmaf(e[rr], expf(nz.log_std[4 * q + rr]), mu[rr]);
+    }
     const size_t row = (size_t)k * B + b;
     const float* in_mean = norm; const float* in_std = norm + (NS + NA);
     for (int i = q; i < NS; i += 4) if (i >= NDROP) st.X[row * NIN + i - NDROP] = (ST[c * NS + i] - in_mean[i]) / in_std[i];
@@ -125,6 +142,7 @@ __global__ void __launch_bounds__(256) k_dg_pre_mfma(ProblemDesc pd, int B, cons
             const float ac = fminf(fmaxf(mu[rr], -1.0f), 1.0f);                           // model_based_rl.py:128
             st.MU[row * NA + d] = mu[rr]; st.U[row * NA + d] = ac;
             st.X[row * NIN + (NS - NDROP) + d] = (ac - in_mean[NS + d]) / in_std[NS + d];
+            if (STOCH && xs_t == nullptr && nz.n_sat != nullptr && fabsf(ac) == 1.0f) atomicAdd(&nz.n_sat[(size_t)b * NA + d], 1);   // :129
         }
     }
 }
@@ -132,9 +150,9 @@ __global__ void __launch_bounds__(256) k_dg_pre_mfma(ProblemDesc pd, int B, cons
 // MFMA variant of k_dg_pre for three-hidden-layer tanh policies (Humanoid's 100-50-25; policy_chain3.h): the thread-per-row k_dg_pre walks that
 // policy's 12 275 weights through scalar loads, 253 us per step whatever the batch -- 70 % of a validation-cost evaluation at the
 // params-humanoid.json shape.  grid = (ceil(B/64), K) blocks of 4 waves, dynamic LDS = image + state tiles.
-template <int NS, int NA, int NDROP, int W1, int W2, int W3>
+template <int NS, int NA, int NDROP, int W1, int W2, int W3, bool STOCH>
 __global__ void __launch_bounds__(256) k_dg_pre_mfma3(ProblemDesc pd, int B, const float* __restrict__ theta, const float* __restrict__ norm,
-                                                      const float* __restrict__ xs_t, long long xs_model_stride, DgState st) {
+                                                      const float* __restrict__ xs_t, long long xs_model_stride, DgState st, BpttNoise nz, int t) {
     using PC = P3<NS, NA, W1, W2, W3>;
     constexpr int CO = PC::CO, IMG = PC::IMG, NIN = NS - NDROP + NA;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -161,34 +179,43 @@ __global__ void __launch_bounds__(256) k_dg_pre_mfma3(ProblemDesc pd, int B, con
     const float* in_mean = norm; const float* in_std = norm + (NS + NA);
     for (int i = q; i < NS; i += 4) if (i >= NDROP) st.X[row * NIN + i - NDROP] = (ST[c * NS + i] - in_mean[i]) / in_std[i];
 #pragma unroll
-    for (int cb = 0; cb < CO; ++cb)
+    for (int cb = 0; cb < CO; ++cb) {
+        // STOCH: chunk 4 cb + q = action dims 16 cb + 4 q .. +3.  The noisy mean is formed in a scalar and mu is left untouched: built from an
+        // in-place update of the f32x4 elements mu[cb][rr], this instantiation stored wrong normalised actions for dims 18 and 19 with every
+        // draw exactly 0 (mu itself and the draws checked equal by printf), caught by the zero-noise identity test.
+        float e[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (STOCH && 16 * cb + 4 * q < NA) bptt_eps4(nz, k, t, B, b, NA, 4 * cb + q, e);
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
             const int d = 16 * cb + 4 * q + rr;
             if (d < NA) {
-                const float ac = fminf(fmaxf(mu[cb][rr], -1.0f), 1.0f);                       // model_based_rl.py:128
-                st.MU[row * NA + d] = mu[cb][rr]; st.U[row * NA + d] = ac;
+                const float m = STOCH ? fmaf(e[rr], expf(nz.log_std[d]), mu[cb][rr]) : mu[cb][rr];
+                const float ac = fminf(fmaxf(m, -1.0f), 1.0f);                                // model_based_rl.py:128
+                st.MU[row * NA + d] = m; st.U[row * NA + d] = ac;
                 st.X[row * NIN + (NS - NDROP) + d] = (ac - in_mean[NS + d]) / in_std[NS + d];
+                if (STOCH && xs_t == nullptr && nz.n_sat != nullptr && fabsf(ac) == 1.0f) atomicAdd(&nz.n_sat[(size_t)b * NA + d], 1);   // :129
             }
         }
+    }
 }
 
-typedef void (*dg_pre_mfma_t)(ProblemDesc, int, const float*, const float*, const float*, long long, DgState);
+typedef void (*dg_pre_mfma_t)(ProblemDesc, int, const float*, const float*, const float*, long long, DgState, BpttNoise, int);
+template <bool STOCH>
 static dg_pre_mfma_t dg_pre_mfma_select(const metrpo_ctx* c, size_t* dyn_lds = nullptr) {
     const ProblemDesc& pd = c->pd;
     if (dyn_lds) *dyn_lds = 0;
     if (dyn_lds && pd.env == METRPO_ENV_HUMANOID && pd.ns == 55 && pd.na == 21 && pd.n_drop == 0 && pd.pol.n_layers == 4 && pd.pol.dims[1] == 100 &&
         pd.pol.dims[2] == 50 && pd.pol.dims[3] == 25 && pd.pol.act[0] == METRPO_ACT_TANH && pd.pol.act[1] == METRPO_ACT_TANH && pd.pol.act[2] == METRPO_ACT_TANH) {
         *dyn_lds = sizeof(float) * (size_t)(P3<55, 21, 100, 50, 25>::IMG + 4 * 16 * 55);
-        return k_dg_pre_mfma3<55, 21, 0, 100, 50, 25>;
+        return k_dg_pre_mfma3<55, 21, 0, 100, 50, 25, STOCH>;
     }
     if (pd.pol.n_layers != 3 || pd.pol.dims[1] != 32 || pd.pol.dims[2] != 32 || pd.pol.act[0] != METRPO_ACT_TANH) return nullptr;
     switch (pd.env) {
-    case METRPO_ENV_SWIMMER: return (pd.ns == 10 && pd.na == 2 && pd.n_drop == 2) ? k_dg_pre_mfma<METRPO_ENV_SWIMMER> : nullptr;
-    case METRPO_ENV_HALF_CHEETAH: return (pd.ns == 18 && pd.na == 6 && pd.n_drop == 1) ? k_dg_pre_mfma<METRPO_ENV_HALF_CHEETAH> : nullptr;
-    case METRPO_ENV_ANT: return (pd.ns == 29 && pd.na == 8 && pd.n_drop == 2) ? k_dg_pre_mfma<METRPO_ENV_ANT> : nullptr;
-    case METRPO_ENV_HOPPER: return (pd.ns == 11 && pd.na == 3 && pd.n_drop == 0) ? k_dg_pre_mfma<METRPO_ENV_HOPPER> : nullptr;
-    case METRPO_ENV_SNAKE: return (pd.ns == 14 && pd.na == 4 && pd.n_drop == 2) ? k_dg_pre_mfma<METRPO_ENV_SNAKE> : nullptr;
+    case METRPO_ENV_SWIMMER: return (pd.ns == 10 && pd.na == 2 && pd.n_drop == 2) ? k_dg_pre_mfma<METRPO_ENV_SWIMMER, STOCH> : nullptr;
+    case METRPO_ENV_HALF_CHEETAH: return (pd.ns == 18 && pd.na == 6 && pd.n_drop == 1) ? k_dg_pre_mfma<METRPO_ENV_HALF_CHEETAH, STOCH> : nullptr;
+    case METRPO_ENV_ANT: return (pd.ns == 29 && pd.na == 8 && pd.n_drop == 2) ? k_dg_pre_mfma<METRPO_ENV_ANT, STOCH> : nullptr;
+    case METRPO_ENV_HOPPER: return (pd.ns == 11 && pd.na == 3 && pd.n_drop == 0) ? k_dg_pre_mfma<METRPO_ENV_HOPPER, STOCH> : nullptr;
+    case METRPO_ENV_SNAKE: return (pd.ns == 14 && pd.na == 4 && pd.n_drop == 2) ? k_dg_pre_mfma<METRPO_ENV_SNAKE, STOCH> : nullptr;
     }
     return nullptr;
 }
@@ -443,8 +470,8 @@ static void dg_forward_layers(metrpo_ctx* c, DgState& s, int B, int n_layers_to_
     }
 }
 
-// forward sweep; XS / WT may be NULL (validation cost only)
-int launch_dg_forward(metrpo_ctx* c, const float* s0, int B, int T, double gamma, float* XS, float* WT, double* costs, hipStream_t st) {
+// forward sweep; XS / WT may be NULL (validation cost only); nz: the 'bptt-stochastic' noise (NULL: deterministic)
+int launch_dg_forward(metrpo_ctx* c, const float* s0, int B, int T, double gamma, float* XS, float* WT, double* costs, hipStream_t st, const BpttNoise* nz) {
     const ProblemDesc& pd = c->pd;
     const int K = pd.K, L = pd.dyn.n_layers;
     DgState s;
@@ -459,17 +486,20 @@ int launch_dg_forward(metrpo_ctx* c, const float* s0, int B, int T, double gamma
     const int pbs = 64;
     const size_t psh = (size_t)(pd.ns + 2 * pd.pol.max_width) * pbs * sizeof(float);
     if (psh > 160 * 1024) return set_err(c, METRPO_EUNSUPPORTED, "policy too wide for k_dg_pre");
-    if (psh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_dg_pre, hipFuncAttributeMaxDynamicSharedMemorySize, (int)psh));
+    const BpttNoise nz0 = nz ? *nz : BpttNoise{};
+    const void* pre_col = nz ? (const void*)k_dg_pre<true> : (const void*)k_dg_pre<false>;
+    if (psh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute(pre_col, hipFuncAttributeMaxDynamicSharedMemorySize, (int)psh));
     double g = 1.0;
     size_t pre_lds = 0;
-    const dg_pre_mfma_t pre_mfma = dg_pre_mfma_select(c, &pre_lds);
+    const dg_pre_mfma_t pre_mfma = nz ? dg_pre_mfma_select<true>(c, &pre_lds) : dg_pre_mfma_select<false>(c, &pre_lds);
     if (pre_lds) {
         hipLaunchKernelGGL((k_pre_mfma3_image<55, 21, 100, 50, 25>), dim3((unsigned)((P3<55, 21, 100, 50, 25>::IMG + 255) / 256)), dim3(256), 0, st, c->d_theta.p, s.PIMG);
         if (pre_lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)pre_mfma, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pre_lds));
     }
     for (int t = 0; t < T; ++t) {
-        if (pre_mfma) hipLaunchKernelGGL(pre_mfma, dim3((B + 63) / 64, K), dim3(256), pre_lds, st, pd, B, c->d_theta.p, c->d_norm.p, (const float*)nullptr, 0LL, s);
-        else hipLaunchKernelGGL(k_dg_pre, dim3((B + pbs - 1) / pbs, K), dim3(pbs), psh, st, pd, B, c->d_theta.p, c->d_norm.p, (const float*)nullptr, 0LL, s);
+        if (pre_mfma) hipLaunchKernelGGL(pre_mfma, dim3((B + 63) / 64, K), dim3(256), pre_lds, st, pd, B, c->d_theta.p, c->d_norm.p, (const float*)nullptr, 0LL, s, nz0, t);
+        else if (nz) hipLaunchKernelGGL(k_dg_pre<true>, dim3((B + pbs - 1) / pbs, K), dim3(pbs), psh, st, pd, B, c->d_theta.p, c->d_norm.p, (const float*)nullptr, 0LL, s, nz0, t);
+        else hipLaunchKernelGGL(k_dg_pre<false>, dim3((B + pbs - 1) / pbs, K), dim3(pbs), psh, st, pd, B, c->d_theta.p, c->d_norm.p, (const float*)nullptr, 0LL, s, nz0, t);
         dg_forward_layers(c, s, B, L, true, st);
         hipLaunchKernelGGL(k_dg_post, dim3((B + DG_POST_ROWS - 1) / DG_POST_ROWS, K), dim3(DG_POST_THREADS), 0, st, pd, B, T, t, g, c->d_norm.p, s, XS, WT);
         g *= gamma;
@@ -479,7 +509,7 @@ int launch_dg_forward(metrpo_ctx* c, const float* s0, int B, int T, double gamma
     return METRPO_OK;
 }
 
-int launch_dg_backward(metrpo_ctx* c, int B, int T, const float* XS, const float* WT, float* GM, hipStream_t st) {
+int launch_dg_backward(metrpo_ctx* c, int B, int T, const float* XS, const float* WT, float* GM, hipStream_t st, const BpttNoise* nz) {
     const ProblemDesc& pd = c->pd;
     const int K = pd.K, L = pd.dyn.n_layers;
     DgState s;
@@ -492,19 +522,24 @@ int launch_dg_backward(metrpo_ctx* c, int B, int T, const float* XS, const float
     for (int l = 1; l <= pd.pol.n_layers; ++l) prow += pd.pol.dims[l];
     const size_t bsh = (size_t)(pd.ns + prow + 2 * pd.pol.max_width) * pbs * sizeof(float);
     if (psh > 160 * 1024 || bsh > 160 * 1024) return set_err(c, METRPO_EUNSUPPORTED, "policy too wide for the GEMM-path sweeps");
-    if (psh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_dg_pre, hipFuncAttributeMaxDynamicSharedMemorySize, (int)psh));
+    const BpttNoise nz0 = nz ? *nz : BpttNoise{};
+    const void* pre_col = nz ? (const void*)k_dg_pre<true> : (const void*)k_dg_pre<false>;
+    if (psh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute(pre_col, hipFuncAttributeMaxDynamicSharedMemorySize, (int)psh));
     if (bsh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_dg_back, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bsh));
     const long long xs_model = (long long)(T + 1) * B * pd.ns;
     size_t pre_lds = 0;
-    const dg_pre_mfma_t pre_mfma = dg_pre_mfma_select(c, &pre_lds);
+    const dg_pre_mfma_t pre_mfma = nz ? dg_pre_mfma_select<true>(c, &pre_lds) : dg_pre_mfma_select<false>(c, &pre_lds);
     if (pre_lds) {
         hipLaunchKernelGGL((k_pre_mfma3_image<55, 21, 100, 50, 25>), dim3((unsigned)((P3<55, 21, 100, 50, 25>::IMG + 255) / 256)), dim3(256), 0, st, c->d_theta.p, s.PIMG);
         if (pre_lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)pre_mfma, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pre_lds));
     }
     for (int t = T - 1; t >= 0; --t) {
-        if (pre_mfma) hipLaunchKernelGGL(pre_mfma, dim3((B + 63) / 64, K), dim3(256), pre_lds, st, pd, B, c->d_theta.p, c->d_norm.p, XS + (size_t)t * B * pd.ns, xs_model, s);
-        else hipLaunchKernelGGL(k_dg_pre, dim3((B + pbs - 1) / pbs, K), dim3(pbs), psh, st, pd, B, c->d_theta.p, c->d_norm.p,
-                                XS + (size_t)t * B * pd.ns, xs_model, s);
+        if (pre_mfma) hipLaunchKernelGGL(pre_mfma, dim3((B + 63) / 64, K), dim3(256), pre_lds, st, pd, B, c->d_theta.p, c->d_norm.p, XS + (size_t)t * B * pd.ns, xs_model, s,
+                                         nz0, t);
+        else if (nz) hipLaunchKernelGGL(k_dg_pre<true>, dim3((B + pbs - 1) / pbs, K), dim3(pbs), psh, st, pd, B, c->d_theta.p, c->d_norm.p,
+                                        XS + (size_t)t * B * pd.ns, xs_model, s, nz0, t);
+        else hipLaunchKernelGGL(k_dg_pre<false>, dim3((B + pbs - 1) / pbs, K), dim3(pbs), psh, st, pd, B, c->d_theta.p, c->d_norm.p,
+                                XS + (size_t)t * B * pd.ns, xs_model, s, nz0, t);
         dg_forward_layers(c, s, B, L - 1, false, st);                             // hidden activations only
         hipLaunchKernelGGL(k_dg_mid, dim3((B + 127) / 128, K), dim3(128), 0, st, pd, B, T, t, c->d_norm.p, XS, WT, s);
         float* dz = s.DZa; float* dzn = s.DZb;

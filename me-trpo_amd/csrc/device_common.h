@@ -26,7 +26,9 @@ __device__ __forceinline__ float act_apply(int act, float x) {
 //   .z -> step_rand model index of step t (high bits) and cur_model_idx of the reset following step t (low 16 bits),
 //   .w -> pool row of that reset.   => the common case (na <= 2) costs ONE Philox block per env-step.
 // RNG_SELNOISE, chunk c: 4 normals = model_mean_std noise of state dims 4c..4c+3.  RNG_RESET: initial reset (.x row, .y model).
-enum { RNG_STEP = 1, RNG_SELNOISE = 2, RNG_RESET = 3 };
+// RNG_BPTT ('bptt-stochastic' gradient, bptt.hip): counter (env b, model i, t, RNG_BPTT<<16 | chunk c) -> normal4 = eps of action dims
+//   4c .. 4c+3 of (model i, step t, env b)  => one Philox block per (i, t, b) for na <= 4.  Both sweeps of every family recompute it.
+enum { RNG_STEP = 1, RNG_SELNOISE = 2, RNG_RESET = 3, RNG_BPTT = 4 };
 
 __device__ __forceinline__ uint4 philox4x32(uint4 ctr, uint2 key) {
     const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
@@ -65,6 +67,17 @@ __device__ __forceinline__ void normal2(uint32_t a, uint32_t b, float& n0, float
     float sn, cs;
     __sincosf(6.283185307179586f * u1, &sn, &cs);
     n0 = rad * cs; n1 = rad * sn;
+}
+
+// eps of action dims 4 chunk .. 4 chunk + 3 of (model i, step t, env b < B); dims >= na read as 0 in parity mode
+__device__ __forceinline__ void bptt_eps4(const BpttNoise& nz, int i, int t, int B, int b, int na, int chunk, float e[4]) {
+    if (nz.eps != nullptr) {
+        const float* p = nz.eps + (((size_t)i * nz.T + t) * B + b) * na;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) e[j] = (4 * chunk + j < na) ? p[4 * chunk + j] : 0.0f;
+    } else {
+        normal4(rng_draw(nz.seed, ((uint64_t)(uint32_t)i << 32) | (uint32_t)b, (uint32_t)t, RNG_BPTT, (uint32_t)chunk), e);
+    }
 }
 
 __device__ __forceinline__ int rng_index(uint32_t r, int n) { return (int)(((uint64_t)r * (uint64_t)n) >> 32); }

@@ -256,21 +256,32 @@ int sched_cus(metrpo_ctx*, hipStream_t);
 bool grid_is_coresident(metrpo_ctx*, const void* kernel, int threads, size_t lds, long long grid, hipStream_t);
 int launch_rollout_gemm(metrpo_ctx*, const metrpo_rollout_args*, hipStream_t);
 int launch_rollout_resident(metrpo_ctx*, const metrpo_rollout_args*, hipStream_t);   // METRPO_EUNSUPPORTED: not a shape / call of the resident kernel
-int launch_bptt_grad(metrpo_ctx*, const float* init, int B, int T, double gamma, double* costs, double* grad, hipStream_t);
+// 'bptt-stochastic' policy noise of one BPTT gradient (bptt.hip): u = clip(mean + eps * exp(log_std)).  Drawn by device_common.h bptt_eps4.
+struct BpttNoise {
+    const float* eps;               // parity mode: [K][T][B][na] draws; NULL: Philox4x32-10, purpose RNG_BPTT, key = seed
+    const float* log_std;           // [na] raw parameter (d_theta + pol.n_params)
+    int* n_sat;                     // [B][na] int32 count of |u| == 1 over models and steps (forward sweep), or NULL
+    unsigned long long seed;
+    int T;
+};
+// nz == NULL: the deterministic 'bptt' gradient
+int launch_bptt_grad(metrpo_ctx*, const float* init, int B, int T, double gamma, double* costs, double* grad, hipStream_t, const BpttNoise* nz = nullptr);
 int launch_policy_adam(metrpo_ctx*, const double* grad, double lr, double b1, double b2, double eps, double clip_val, bool reset, hipStream_t);
 int ensure_policy_adam(metrpo_ctx*);                 // bptt.hip: allocate the zeroed policy optimizer state + segment table (first Adam step / reset / set)
 int ensure_dyn_adam(metrpo_ctx*);                    // dyn_train.hip: allocate the zeroed dynamics optimizer state (first train step / set)
 size_t dyn_adam_floats(const metrpo_ctx*);           // floats of ONE moment array in d_adam ([K][Pd] rounded up to 4)
 int det_mfma_select(const metrpo_ctx*);
-int launch_det_forward(metrpo_ctx*, int idx, const float* s0, int B, int T, double gamma, float* XS, float* WT, double* part, double* costs, hipStream_t);
-int launch_det_backward(metrpo_ctx*, int idx, int B, int T, const float* XS, const float* WT, float* GM, hipStream_t);
+int launch_det_forward(metrpo_ctx*, int idx, const float* s0, int B, int T, double gamma, float* XS, float* WT, double* part, double* costs, hipStream_t,
+                       const BpttNoise* nz = nullptr);
+int launch_det_backward(metrpo_ctx*, int idx, int B, int T, const float* XS, const float* WT, float* GM, hipStream_t, const BpttNoise* nz = nullptr);
 int ensure_detpart(metrpo_ctx*, int B);
 int ensure_detpart_n(metrpo_ctx*, size_t n_doubles);
 int launch_det_cost_reduce(metrpo_ctx*, int n_part, const double* part, double* costs, hipStream_t, const double* err = nullptr);   // err: time-out cell of the launch that wrote the partials (NaN costs when set)
 int launch_validation_resident(metrpo_ctx*, const float* s0, int Bv, int T, double gamma, double* costs, hipStream_t);   // rollout_resident.hip; METRPO_EUNSUPPORTED: not this shape
 bool det_gemm_applicable(const metrpo_ctx*);
-int launch_dg_forward(metrpo_ctx*, const float* s0, int B, int T, double gamma, float* XS, float* WT, double* costs, hipStream_t);
-int launch_dg_backward(metrpo_ctx*, int B, int T, const float* XS, const float* WT, float* GM, hipStream_t);
+int launch_dg_forward(metrpo_ctx*, const float* s0, int B, int T, double gamma, float* XS, float* WT, double* costs, hipStream_t,
+                      const BpttNoise* nz = nullptr);
+int launch_dg_backward(metrpo_ctx*, int B, int T, const float* XS, const float* WT, float* GM, hipStream_t, const BpttNoise* nz = nullptr);
 int launch_policy_vjp(metrpo_ctx*, const float* obs, const float* gm, long long N, double* out, hipStream_t);
 int launch_dyn_train_step(metrpo_ctx*, const float*, const float*, const metrpo_train_params*, double*, hipStream_t);
 int launch_dyn_eval_losses(metrpo_ctx*, const float*, const float*, long long, double, double*, hipStream_t);

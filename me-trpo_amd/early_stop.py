@@ -63,9 +63,15 @@ def update_stats(min_validation_costs, candidates, whole=False):
 
 def optimize_policy(algo, validation_init, T, gamma, mode='estimated', whole=True, log_every=5,
                     num_iters_threshold=25, max_iters=400, stop_fn=None, reset_log_std=True, real_cost_fn=None,
-                    logger=None):
-    """TRPO branch of model_based_rl.py:optimize_policy.  `real_cost_fn()` stands in for
+                    logger=None, init_pool=None):
+    """TRPO branch of model_based_rl.py:optimize_policy; a BPTT object as `algo` runs its 'bptt' / 'bptt-stochastic' branch instead
+    (optimize_policy_bptt; `init_pool` is then its source of reset states).  `real_cost_fn()` stands in for
     evaluate_fixed_init_trajectories on the real simulator (out of scope; None -> 0.0)."""
+    from .bptt import BPTT
+    if isinstance(algo, BPTT):
+        return optimize_policy_bptt(algo, validation_init, T, gamma, init_pool, mode=mode, whole=whole, log_every=log_every,
+                                    num_iters_threshold=num_iters_threshold, max_iters=max_iters, stop_fn=stop_fn, real_cost_fn=real_cost_fn,
+                                    logger=logger)
     eng = algo.engine
     stop_fn = stop_fn or stop_critereon(0.10, 1e-5, 0.30)
     if reset_log_std:
@@ -108,3 +114,40 @@ def optimize_policy(algo, validation_init, T, gamma, mode='estimated', whole=Tru
                 break
     eng.set_policy(snapshot)                                               # log_and_restore, :1301/:1400
     return dict(best_index=best_index, last_index=j, min_validation_costs=min_costs, history=history)
+
+
+def optimize_policy_bptt(bptt, validation_init, T, gamma, init_pool, mode='estimated', whole=True, log_every=5, num_iters_threshold=25,
+                         max_iters=400, stop_fn=None, real_cost_fn=None, logger=None):
+    """'bptt' / 'bptt-stochastic' branches of model_based_rl.py:optimize_policy (:1181-1196, 1209-1215, 1286-1298): every iteration
+    `batch_size` reset states from `init_pool` (an InitStatePool or an env with reset()) and one BPTT step (stochastic as `bptt` is set:
+    every 'bptt-stochastic' step sees the noise); every `log_every` iterations the K validation costs, deterministic as in the reference
+    (which sets stochastic back to 0 first, :1211-1215); the stop rule and the snapshot / restore of the TRPO branch.  No reset_opt: the
+    reference builds it for trpo / vpg only.  `mode` 'trpo_mean' has no TRPO sampler here and compares 0.0, as for the other branches."""
+    if init_pool is None or not (hasattr(init_pool, 'sample') or hasattr(init_pool, 'reset')):
+        raise ValueError("the bptt branches draw their batch from init_pool: an InitStatePool or an env with reset() (from_params: "
+                         "Setup.bptt_optimize_policy_kwargs carries it)")
+    eng = bptt.engine
+    stop_fn = stop_fn or stop_critereon(0.10, 1e-5, 0.30)
+    snapshot = eng.get_policy().clone()
+    real = (lambda: float(real_cost_fn())) if real_cost_fn else (lambda: 0.0)
+    est = lambda: eng.validation_cost(validation_init, T, gamma).cpu().numpy()
+    min_costs = {'real': real(), 'trpo_mean': np.inf, 'estimated': est()}
+    best_index, candidates, history, training_costs = 0, {}, [], []
+    j = 0
+    for j in range(1, max_iters + 1):
+        training_costs.append(float(bptt.optimize_policy_iteration(init_pool)))        # :1183-1196, np.squeeze(training_cost)
+        if j % log_every == 0:                                             # :1209
+            candidates['trpo_mean'] = 0.0
+            candidates['estimated'] = est()
+            candidates['real'] = real()
+            history.append((j, float(np.mean(candidates['estimated']))))
+            if logger:
+                logger('iter %d training_cost=%.6g est=%s' % (j, training_costs[-1], np.array_str(candidates['estimated'], precision=3)))
+            if not is_done(mode, stop_fn, min_costs, candidates):          # :1286-1295
+                best_index = j
+                snapshot = eng.get_policy().clone()
+                update_stats(min_costs, candidates, whole)
+            if j - best_index >= num_iters_threshold:                      # :1298
+                break
+    eng.set_policy(snapshot)
+    return dict(best_index=best_index, last_index=j, min_validation_costs=min_costs, history=history, training_costs=training_costs)

@@ -620,6 +620,26 @@ class Engine(object):
         self._keep_bptt = x0
         return costs, grad
 
+    def bptt_grad_stochastic(self, init_states, T, gamma=1.0, noise=None, seed=None, n_saturates=False):
+        """'bptt-stochastic' gradient (model_based_rl.py:1188-1196): bptt_grad with u = clip(mean + eps * exp(log_std)), log_std slots
+        included.  `noise` [K, T, B, na]: the draws (parity mode); None: Philox draws keyed by `seed` (an int; required then).
+        -> (costs, grad), plus n_saturates [B, na] int32 device tensor (model_based_rl.py:129) when asked for."""
+        x0 = _f32(init_states, self.device)
+        B = x0.shape[0]
+        if noise is None:
+            if seed is None:
+                raise ValueError("bptt_grad_stochastic: give the draws (noise) or a Philox seed")
+            eps = None
+        else:
+            eps = _f32(noise, self.device, (self.K, int(T), B, self.na))
+        costs = torch.empty(self.K, dtype=torch.float64, device=self.device)
+        grad = torch.empty(self.P, dtype=torch.float64, device=self.device)
+        nsat = torch.empty((B, self.na), dtype=torch.int32, device=self.device) if n_saturates else None
+        self._chk(lib.metrpo_bptt_grad_stochastic(self._ctx, _ptr(x0), B, int(T), float(gamma), _ptr(eps), int(seed or 0) & 0xFFFFFFFFFFFFFFFF,
+                                                  _ptr(costs), _ptr(grad), _ptr(nsat), self._stream()))
+        self._keep_bptt = (x0, eps)
+        return (costs, grad, nsat) if n_saturates else (costs, grad)
+
     def policy_adam_reset(self):
         self._chk(lib.metrpo_policy_adam_reset(self._ctx, self._stream()))
 

@@ -84,7 +84,9 @@ class Setup(object):
     """What `from_params` hands back: the objects of the inner loop plus the keyword sets of the two loop drivers.
         s = metrpo_amd.from_params('params/params-swimmer.json', init_states=real_env_reset_states)
         s.engine.set_dynamics_layers(...)                       # or train them: dynamics_training.optimize_models(s.engine, ..., **s.dynamics_opt)
-        out = metrpo_amd.early_stop.optimize_policy(s.algo, validation_init, **s.optimize_policy_kwargs)"""
+        out = metrpo_amd.early_stop.optimize_policy(s.algo, validation_init, **s.optimize_policy_kwargs)
+    'bptt' / 'bptt-stochastic' runs also carry `bptt` (a BPTT object; stochastic for the latter) and the keywords of the BPTT branch:
+        out = metrpo_amd.early_stop.optimize_policy(s.bptt, validation_init, **s.bptt_optimize_policy_kwargs)"""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -103,8 +105,9 @@ def from_params(path_or_dict, device=0, init_states=None, comm=None, seed=0, n_e
     from .bptt import BPTT
     p = _load(path_or_dict)
     sh = shapes_from_params(p)
-    if sh['algo'] not in ('trpo', 'bptt'):
-        raise ValueError("params 'algo' = %r: this path builds 'trpo' (and the 'bptt' update of section 8f); vpg / svg / l-bfgs are out of scope" % sh['algo'])
+    if sh['algo'] not in ('trpo', 'bptt', 'bptt-stochastic'):
+        raise ValueError("params 'algo' = %r: this path builds 'trpo' (and the 'bptt' / 'bptt-stochastic' updates of section 8f); vpg / svg / l-bfgs "
+                         "are out of scope" % sh['algo'])
     eng = Engine(sh['env'], sh['K'], sh['dyn_hidden'], sh['pol_hidden'], n_drop=sh['n_drop'], dyn_act=sh['dyn_act'], device=device)
     policy = GaussianMLPPolicy(eng, init_std=sh['trpo']['init_std'], seed=seed)
     baseline = LinearFeatureBaseline()
@@ -114,9 +117,12 @@ def from_params(path_or_dict, device=0, init_states=None, comm=None, seed=0, n_e
                 step_size=sh['trpo']['step_size'], sampler_args=(dict(n_envs=n_envs) if n_envs else None), comm=comm, seed=seed)
     stop_fn = early_stop.stop_critereon(sh['stop_critereon']['threshold'], sh['stop_critereon']['offset'], sh['stop_critereon']['percent_models_threshold'])
     okw = dict(sh['optimize_policy'], stop_fn=stop_fn, reset_log_std=sh['trpo']['reset'])
-    bptt = None
-    if sh['algo'] == 'bptt':
+    bptt, bkw = None, None
+    if sh['algo'] in ('bptt', 'bptt-stochastic'):
         bptt = BPTT(eng, sh['T'], gamma=sh['optimize_policy']['gamma'], learning_rate=sh['bptt']['learning_rate'],
-                    grad_norm_clipping=sh['bptt']['grad_norm_clipping'], batch_size=sh['bptt']['batch_size'])
+                    grad_norm_clipping=sh['bptt']['grad_norm_clipping'], batch_size=sh['bptt']['batch_size'],
+                    stochastic=(sh['algo'] == 'bptt-stochastic'), seed=seed)
+        # no reset_opt for these branches: the reference builds it for trpo / vpg only (training.py:350-352, 368-370)
+        bkw = dict(sh['optimize_policy'], stop_fn=stop_fn, init_pool=pool)
     return Setup(params=p, shapes=sh, engine=eng, policy=policy, baseline=baseline, env=env, algo=algo, bptt=bptt, optimize_policy_kwargs=okw,
-                 dynamics_opt=sh['dynamics_opt'])
+                 bptt_optimize_policy_kwargs=bkw, dynamics_opt=sh['dynamics_opt'])
