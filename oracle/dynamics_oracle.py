@@ -242,6 +242,20 @@ def train_step(dm, adam, x_batch, y_batch, batch_size, lr, reg_constant=0.0, b1=
     return loss
 
 
+def adam_lr_t(lr, t, b1=0.9, b2=0.999):
+    """tf.train.AdamOptimizer's step size at step t (1-based): the bias corrections folded into lr, epsilon left outside."""
+    return lr * np.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
+
+
+def adam_expect(w, m, v, g, lr_t, decay, b1=0.9, b2=0.999, eps=1e-8):
+    """One element-wise update of train_step in float64: Adam with step size lr_t (adam_lr_t) on the gradient g, plus SGD on
+    the regulariser (decay = lr * reg_constant).  -> (m1, v1, w1).  Taking lr_t and the betas separately lets a caller state
+    both exactly as a device computes them (fp32 betas in the moments, lr_t formed from the float64 betas)."""
+    m1 = b1 * m + (1 - b1) * g
+    v1 = b2 * v + (1 - b2) * g * g
+    return m1, v1, w - lr_t * m1 / (np.sqrt(v1) + eps) - decay * w
+
+
 def validation_losses(dm, x_val, y_val, reg_constant=0.0):
     """dynamics_losses on np.tile(val, n_models): every model sees the whole validation set (:933-945)."""
     xs, ys = [x_val] * dm.K, [y_val] * dm.K

@@ -96,7 +96,7 @@ def test_single_step_gradient_direction():
 def test_eval_losses_chunking_and_model_restore():
     eng, dm, theta, pdims, pool = Hh.make_engine('swimmer', 3, (64, 64), (32, 32), seed=73)
     xv, yv = data(dm, 20000, 11)                       # > one 8192-row pass
-    np.testing.assert_allclose(cpu(eng.eval_losses(xv, yv)), D.validation_losses(dm, xv, yv), rtol=TOL.DYN_EVAL_LOSS['rtol'])
+    np.testing.assert_allclose(cpu(eng.eval_losses(xv, yv)), D.validation_losses(dm, xv, yv), **TOL.DYN_LOSS)   # untrained: no drift
     snap = eng.get_dynamics().clone()
     eng.train_reset()
     for _ in range(3):
@@ -105,6 +105,34 @@ def test_eval_losses_chunking_and_model_restore():
     eng.set_dynamics_model(1, snap[1])
     cur = eng.get_dynamics()
     assert torch.equal(cur[1], snap[1]) and not torch.equal(cur[0], snap[0])
+
+
+@pytest.mark.parametrize('n', [1, 8193])
+def test_eval_losses_params_file_shape(n):
+    """eval_losses at the params files' 2 x 1024, K = 5: a single row, and 8193 rows (the second 8192-row pass holds one row)."""
+    eng, dm, theta, pdims, pool = Hh.make_engine('half_cheetah', 5, (1024, 1024), (32, 32), seed=76)
+    for l in range(len(dm.Ws)):
+        dm.Ws[l] = dm.Ws[l].astype(np.float32).astype(np.float64); dm.bs[l] = dm.bs[l].astype(np.float32).astype(np.float64)
+    for a in ('in_mean', 'in_std', 'diff_mean', 'diff_std'):
+        setattr(dm, a, getattr(dm, a).astype(np.float32).astype(np.float64))
+    xv, yv = data(dm, n, 12)
+    for reg in (0.0, 1e-3):
+        np.testing.assert_allclose(cpu(eng.eval_losses(xv, yv, reg)), D.validation_losses(dm, xv, yv, reg), **TOL.DYN_LOSS)
+
+
+@pytest.mark.parametrize('dim', [76, 111])
+@pytest.mark.parametrize('n', [1, 3, 1001])
+def test_rms_accumulate_two_column_blocks(dim, n):
+    """k_rms_accumulate with two 64-column blocks (the second one partial), two calls into the same sums: float64 sums of the fp32 rows"""
+    eng, dm, theta, pdims, pool = Hh.make_engine('swimmer', 2, (64, 64), (32, 32), seed=78)
+    rng = np.random.RandomState(dim + n)
+    chunks = [(rng.randn(n, dim) * 1.0 + 2.0).astype(np.float32), (rng.randn(n, dim) * 3.0 + 1.0).astype(np.float32)]
+    rsum = torch.full((dim,), 0.25, dtype=torch.float64, device='cuda'); rsumsq = torch.full((dim,), 0.5, dtype=torch.float64, device='cuda')
+    for c in chunks:
+        eng.rms_accumulate(c, rsum, rsumsq)
+    z = np.concatenate(chunks).astype(np.float64)
+    np.testing.assert_allclose(cpu(rsum), 0.25 + np.sum(z, axis=0), rtol=1e-12, atol=1e-12 * np.abs(z).sum(0).max())
+    np.testing.assert_allclose(cpu(rsumsq), 0.5 + np.sum(z * z, axis=0), rtol=1e-12)
 
 
 def test_replay_buffer_and_normalizers_match_reference_semantics():

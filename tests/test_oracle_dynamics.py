@@ -97,6 +97,32 @@ def test_train_steps_match_tf_style_adam_on_autograd(reg):
         np.testing.assert_allclose(dm.bs[l], bs[l].detach().numpy(), rtol=1e-9, atol=1e-12)
 
 
+@pytest.mark.parametrize('reg', [0.0, 1e-3])
+def test_adam_expect_reproduces_train_step(reg):
+    """adam_expect / adam_lr_t (the element-wise expectation of tests/test_gpu_dyn_train_grad.py) restate train_step's update:
+    three steps from non-zero moments, every weight, bias and moment to 1e-12."""
+    dm, x, y, n = _problem(seed=3)
+    adam = D.AdamState(dm)
+    rng = np.random.RandomState(4)
+    lr = 1e-3
+    for it in range(3):
+        idx = rng.randint(len(x), size=n * dm.K)
+        xb, yb = x[idx], y[idx]
+        xs, ys = D.split_batch(xb, yb, n, dm.K)
+        grads = [D.model_gradients(dm, k, xs[k], ys[k]) for k in range(dm.K)]
+        before = [[p.copy() for p in ps] for ps in (dm.Ws, adam.mW, adam.vW, dm.bs, adam.mb, adam.vb)]
+        lr_t = D.adam_lr_t(lr, adam.t + 1)
+        D.train_step(dm, adam, xb, yb, n, lr, reg_constant=reg)
+        for gi, (P, M, V) in enumerate(((dm.Ws, adam.mW, adam.vW), (dm.bs, adam.mb, adam.vb))):
+            P0, M0, V0 = before[3 * gi:3 * gi + 3]
+            for l in range(len(P)):
+                g = np.stack([grads[k][gi][l] for k in range(dm.K)])
+                m1, v1, w1 = D.adam_expect(P0[l], M0[l], V0[l], g, lr_t, lr * reg)
+                for got, want in ((M[l], m1), (V[l], v1), (P[l], w1)):
+                    np.testing.assert_allclose(got, want, rtol=1e-12, atol=1e-15)
+    assert adam.t == 3
+
+
 def run_reference_buffer_tests(make, combine, to_np=np.asarray):
     """The bodies of the reference's OWN tests utils.test_data_collection / test_combine_data_collection (utils.py:145-176),
     replayed on `make(max_size)` collections; every get_next_batch result and the combined collections are compared with what the
