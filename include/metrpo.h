@@ -274,6 +274,22 @@ int32_t metrpo_fvp(metrpo_ctx* ctx, const metrpo_batch* batch, const double* d_v
 int32_t metrpo_loss_kl(metrpo_ctx* ctx, const metrpo_batch* batch, const float* d_theta, double* d_out,
                        void* stream);
 
+/* ---- VPG update (algos/vpg.py:88 surr_obj = -mean(logli * adv), :26-33 FirstOrderOptimizer(batch_size=None, max_epochs=1);
+ * training.py:337-352).  logli = DiagonalGaussian.log_likelihood_sym of the unclipped stored action under the ctx policy (log_std
+ * clamped at log(1e-6) as in the TRPO kernels); no likelihood ratio: d_old_mean / d_old_log_std of the batch may be NULL. */
+/* f_loss + gradient of surr_obj: d_out[0] = loss partial, d_out[1..P] = gradient partial (log_std slots included), float64, this
+ * rank's share -- the layout of metrpo_loss_grad, for a host-driven all-reduce (metrpo_allreduce_fn, gloo) and metrpo_policy_adam_step. */
+int32_t metrpo_vpg_loss_grad(metrpo_ctx* ctx, const metrpo_batch* batch, double* d_out, void* stream);
+typedef struct {
+    double lr, beta1, beta2, eps;    /* tf.train.AdamOptimizer(learning_rate=1e-3): 1e-3, 0.9, 0.999, 1e-8 (FirstOrderOptimizer, vpg.py:26-33) */
+} metrpo_vpg_params;
+/* One optimize_policy of VPG (vpg.py:100-118): ONE Adam step on the whole batch's gradient, every policy parameter incl. log_std, no
+ * clipping.  The optimizer state is the ctx policy Adam state (metrpo_get_policy_adam / metrpo_set_policy_adam; not reset here,
+ * model_based_rl.py:398-405).  Two launches on the stream, no synchronisation: the gradient kernel, then the reduction whose blocks
+ * apply the step to the columns they reduced (with the ranks' sum when a one-shot transport is attached; with an RCCL communicator
+ * the all-reduce and a stand-alone step follow the reduction).  d_loss (optional, 1 double) = the loss at the entry theta. */
+int32_t metrpo_vpg_update(metrpo_ctx* ctx, const metrpo_batch* batch, const metrpo_vpg_params* params, double* d_loss, void* stream);
+
 /* ---- multi-GPU: one process and one ctx per GPU, the env batch B sharded over the ranks.  The only exchanges on
  * the path are sum all-reduces of small float64 vectors.  Attach an RCCL communicator to the ctx and metrpo_trpo_update issues
  * its all-reduces itself (ncclAllReduce on the caller's stream, in-place, float64); the reference has no counterpart (it is a

@@ -60,6 +60,10 @@ class TrpoDiag(C.Structure):
                 ('n_backtrack', C.c_int32), ('accepted', C.c_int32), ('cg_iters_run', C.c_int32)]
 
 
+class VpgParams(C.Structure):
+    _fields_ = [('lr', C.c_double), ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double)]
+
+
 # every symbol include/metrpo.h declares: name -> (restype, argtypes)
 _P, _I, _L, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 SYMBOLS = {
@@ -96,6 +100,8 @@ SYMBOLS = {
     'metrpo_loss_grad': (_I, [_P, C.POINTER(Batch), _P, _P]),
     'metrpo_fvp': (_I, [_P, C.POINTER(Batch), _P, _P, _P]),
     'metrpo_loss_kl': (_I, [_P, C.POINTER(Batch), _P, _P, _P]),
+    'metrpo_vpg_loss_grad': (_I, [_P, C.POINTER(Batch), _P, _P]),
+    'metrpo_vpg_update': (_I, [_P, C.POINTER(Batch), C.POINTER(VpgParams), _P, _P]),
     'metrpo_trpo_update': (_I, [_P, C.POINTER(Batch), C.POINTER(TrpoParams), C.POINTER(TrpoDiag), _P, _P, _P]),
     'metrpo_trpo_update_begin': (_I, [_P, C.POINTER(Batch), C.POINTER(TrpoParams), _I, _P, _P, _P]),
     'metrpo_trpo_update_end': (_I, [_P, C.POINTER(TrpoDiag), C.POINTER(C.c_int32), _P]),

@@ -1,4 +1,4 @@
-"""algos/batch_polopt.py, algos/npo.py, algos/trpo.py of the reference with the same constructor
+"""algos/batch_polopt.py, algos/npo.py, algos/trpo.py, algos/vpg.py of the reference with the same constructor
 arguments, attributes and methods (start_worker / obtain_samples / process_samples /
 optimize_policy), so that the reference's outer loop (model_based_rl.py:1171-1180) drives them
 unchanged:
@@ -114,3 +114,74 @@ class TRPO(NPO):
                 optimizer_args = dict()
             optimizer = ConjugateGradientOptimizer(**optimizer_args)
         super(TRPO, self).__init__(optimizer=optimizer, **kwargs)
+
+
+class FirstOrderOptimizer(object):
+    """[rllab] sandbox.rocky.tf.optimizers.first_order_optimizer.FirstOrderOptimizer as VPG builds it (vpg.py:26-33): tf_optimizer_cls =
+    tf.train.AdamOptimizer(learning_rate=1e-3) with TF's defaults (beta1 0.9, beta2 0.999, epsilon 1e-8), no gradient clipping.
+    batch_size=None and max_epochs=1 make every optimize() ONE step on the gradient of the whole batch; the loss before / after the
+    epoch feeds only a tolerance break that cannot fire with one epoch (and VPG's LossBefore / LossAfter logging is commented out,
+    vpg.py:119-124), so only the loss at the entry theta -- free from the gradient pass -- is kept (`last_loss`, a device tensor).
+    The Adam state is the engine's policy optimizer state (Engine.get_policy_adam / set_policy_adam); it is never reset here."""
+
+    def __init__(self, tf_optimizer_cls=None, tf_optimizer_args=None, max_epochs=1, tolerance=1e-6, batch_size=None, callback=None,
+                 verbose=False, learning_rate=1e-3, beta1=0.9, beta2=0.999, epsilon=1e-8, **kwargs):
+        if tf_optimizer_cls is not None:
+            raise NotImplementedError("FirstOrderOptimizer: only the AdamOptimizer VPG builds runs on this path")
+        if max_epochs != 1 or batch_size is not None:
+            raise NotImplementedError("FirstOrderOptimizer: VPG's setting (batch_size=None, max_epochs=1) is the one built")
+        args = dict(learning_rate=learning_rate, beta1=beta1, beta2=beta2, epsilon=epsilon)
+        args.update(tf_optimizer_args or {})
+        self.learning_rate, self.beta1, self.beta2, self.epsilon = (float(args['learning_rate']), float(args['beta1']), float(args['beta2']),
+                                                                    float(args['epsilon']))
+        self.max_epochs, self.tolerance, self.batch_size = max_epochs, tolerance, batch_size
+        self.last_loss = None
+
+    def update_opt(self, loss, target, inputs, extra_inputs=None, **kwargs):
+        self._target = target            # the surrogate graph itself (vpg.py:88) is what the HIP kernels compute
+
+    def optimize(self, engine, batch, comm=None):
+        """One Adam step.  With a communicator attached to the engine (Comm.attach_engine) or at world size 1 the whole step is
+        Engine.vpg_update (gradient kernel + reduction carrying the step); otherwise the gradient share is all-reduced on the host
+        (Comm, e.g. gloo) and the step follows as Engine.policy_adam_step with no clipping."""
+        comm = comm or Comm()
+        need = comm.world > 1 or comm.always_reduce
+        if need and not getattr(engine, 'comm_world', 0):
+            lg = comm.allreduce_sum_(engine.vpg_loss_grad(batch))
+            engine.policy_adam_step(lg[1:], self.learning_rate, clip_val=None, beta1=self.beta1, beta2=self.beta2, eps=self.epsilon)
+            self.last_loss = lg[:1]
+        else:
+            self.last_loss = engine.vpg_update(batch, lr=self.learning_rate, beta1=self.beta1, beta2=self.beta2, eps=self.epsilon)
+        return self.last_loss
+
+
+class VPG(BatchPolopt):
+    """Vanilla Policy Gradient (algos/vpg.py): surr_obj = -mean(logli * adv) (vpg.py:88), minimised by a FirstOrderOptimizer with
+    batch_size=None, max_epochs=1 -- one Adam step per optimize_policy.  process_samples is BatchPolopt's (linear baseline, gae_lambda 1,
+    center_adv), as for TRPO."""
+
+    def __init__(self, env, policy, baseline, optimizer=None, optimizer_args=None, **kwargs):
+        if optimizer is None:
+            default_args = dict(batch_size=None, max_epochs=1)
+            optimizer_args = default_args if optimizer_args is None else dict(default_args, **optimizer_args)
+            optimizer = FirstOrderOptimizer(**optimizer_args)
+        self.optimizer = optimizer
+        self.opt_info = None
+        super(VPG, self).__init__(env=env, policy=policy, baseline=baseline, **kwargs)
+
+    def init_opt(self):
+        self.optimizer.update_opt(loss=None, target=self.policy, inputs=None)
+        self.opt_info = dict()
+
+    def optimize_policy(self, itr, samples_data):
+        """vpg.py:100-118: inputs = (observations, actions, advantages); the old distribution is not an input."""
+        batch = self.engine.make_batch(samples_data["observations"], samples_data["actions"], samples_data["advantages"], None, None,
+                                       valid=samples_data.get("valids"), n_global=samples_data.get("n_valid_global"))
+        with self.timers.phase('policy_opt'):
+            self.optimizer.optimize(self.engine, batch, comm=self.comm)
+        if hasattr(self.sampler, 'finish_baseline_fit') and not getattr(self, 'defer_baseline_fit', False):
+            self.sampler.finish_baseline_fit()
+        return dict()
+
+    def get_itr_snapshot(self, itr, samples_data):
+        return dict(itr=itr, policy=self.policy, baseline=self.baseline, env=self.env)

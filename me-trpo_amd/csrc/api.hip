@@ -498,6 +498,20 @@ extern "C" int32_t metrpo_loss_grad(metrpo_ctx* c, const metrpo_batch* b, double
     if (!out) return set_err(c, METRPO_ENULL, "loss_grad: out NULL");
     return launch_loss_grad(c, b, out, (hipStream_t)stream);
 }
+// algos/vpg.py:88 (surr_obj) and :100-118 (optimize_policy: FirstOrderOptimizer, one Adam step), policy_update.hip
+extern "C" int32_t metrpo_vpg_loss_grad(metrpo_ctx* c, const metrpo_batch* b, double* out, void* stream) {
+    if (!c) return METRPO_ENULL;
+    if (!out) return set_err(c, METRPO_ENULL, "vpg_loss_grad: out NULL");
+    NEED_POL(c);
+    return launch_vpg_loss_grad(c, b, out, (hipStream_t)stream);
+}
+extern "C" int32_t metrpo_vpg_update(metrpo_ctx* c, const metrpo_batch* b, const metrpo_vpg_params* pr, double* d_loss, void* stream) {
+    if (!c) return METRPO_ENULL;
+    if (!pr) return set_err(c, METRPO_ENULL, "vpg_update: params NULL");
+    NEED_POL(c);
+    if (c->upd_pending) return set_err(c, METRPO_ESTATE, "vpg_update: a TRPO update is still open (metrpo_trpo_update_end first)");
+    return run_vpg_update(c, b, pr, d_loss, (hipStream_t)stream);
+}
 extern "C" int32_t metrpo_fvp(metrpo_ctx* c, const metrpo_batch* b, const double* v, double* hv, void* stream) {
     if (!c) return METRPO_ENULL;
     NEED_POL(c);

@@ -263,10 +263,7 @@ __global__ void k_policy_adam(int n_seg, const int* __restrict__ seg_off, const 
     __syncthreads();
     const double sc = s_scale;
     for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        const float g = (float)(grad[i] * sc);
-        const float m1 = b1 * am[i] + (1.0f - b1) * g, v1 = b2 * av[i] + (1.0f - b2) * g * g;
-        am[i] = m1; av[i] = v1;
-        theta[i] = theta[i] - lr_t * m1 / (sqrtf(v1) + eps);
+        tf_adam_elem((float)(grad[i] * sc), theta, am, av, i, lr_t, b1, b2, eps);
     }
 }
 

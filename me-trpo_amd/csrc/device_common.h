@@ -4,6 +4,18 @@
 
 #define LOG_MIN_STD (-13.815510557964274f)   // log(1e-6): [rllab] GaussianMLPPolicy(min_std=1e-6)
 #define KL_EPS 1e-8f                         // [rllab] DiagonalGaussian.kl_sym denominator constant
+#define HALF_LOG_2PI 0.9189385332046727f     // 0.5 log(2 pi): DiagonalGaussian.log_likelihood_sym's constant term
+
+// One element of tf.train.AdamOptimizer.apply_gradients with the bias correction folded into lr_t (launch_policy_adam, bptt.hip):
+// k_policy_adam and the 'vpg' step in k_finalize's tail (policy_update.hip) share it, so the two forms agree bit for bit.  Contraction is
+// spelt out: left to the compiler, which products fuse depends on the surrounding kernel.  The one fma (m1) is the form k_policy_adam
+// always compiled to.
+__device__ __forceinline__ void tf_adam_elem(float g, float* theta, float* am, float* av, int i, float lr_t, float b1, float b2, float eps) {
+#pragma clang fp contract(off)
+    const float m1 = fmaf(b1, am[i], (1.0f - b1) * g), v1 = b2 * av[i] + (1.0f - b2) * g * g;
+    am[i] = m1; av[i] = v1;
+    theta[i] = theta[i] - lr_t * m1 / (sqrtf(v1) + eps);
+}
 
 // tanh(x) = 1 - 2 / (1 + exp(2x)) in 5 VALU ops (v_mul, v_exp_f32, v_add, v_rcp_f32, v_fma): absolute error
 // <= ~2e-7 everywhere (exact saturation to +-1); libm's tanhf costs ~40 ops and sat on every kernel's critical path.

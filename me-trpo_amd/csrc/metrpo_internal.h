@@ -304,6 +304,11 @@ int launch_baseline_solve(metrpo_ctx*, const double* AtA, const double* Aty, dou
 int launch_gram(metrpo_ctx*, const float*, const float*, const int32_t*, const uint8_t*, int64_t, double*, double*,
                 hipStream_t);
 int launch_loss_grad(metrpo_ctx*, const metrpo_batch*, double*, hipStream_t, const CgTail* tail = nullptr);
+// 'vpg' policy update (algos/vpg.py): the gradient kernels of every update family in their UPD_VPG instantiation (ratio 1: loss = -mean(logli * adv)).
+// The mode number is shared by run_mode (policy_update.hip), policy_mfma_launch, policy_f3_launch and policy_gemm_run; 3 is policy_mfma.hip's MODE_FVPC.
+#define UPD_VPG 4
+int launch_vpg_loss_grad(metrpo_ctx*, const metrpo_batch*, double* out, hipStream_t);
+int run_vpg_update(metrpo_ctx*, const metrpo_batch*, const metrpo_vpg_params*, double* d_loss, hipStream_t);
 int comm_allreduce_f64(metrpo_ctx*, double* buf, long long count, hipStream_t);
 // descriptor of the NEXT one-shot exchange (advances the sequence number); world = 0 when no peer-mapped transport is attached
 XchgK xchg_next(metrpo_ctx*);

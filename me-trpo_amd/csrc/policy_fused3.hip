@@ -165,7 +165,7 @@ template <class S> __device__ __forceinline__ void fix_xb(float (&xb)[S::KS0], i
     for (int s = 0; s < S::KS0; ++s) if (4 * s + 3 >= S::D0) { const int f = 4 * s + q; if (f == S::D0) xb[s] = 1.0f; else if (f > S::D0) xb[s] = 0.f; }
 }
 
-enum { F3_GRAD = 0, F3_LOSSKL = 2, F3_CACHE = 3 };
+enum { F3_GRAD = 0, F3_LOSSKL = 2, F3_CACHE = 3, F3_VPG = UPD_VPG };     // F3_VPG: F3_GRAD with the VPG head (vpg.py:88; policy_mfma.hip MODE_VPG)
 enum { IMG_WHAT_F = 1, IMG_WHAT_V = 2, IMG_WHAT_B = 4 };
 // fragment tables of theta (F: forward, B: back-prop) and of the tangent vector v (V) -> the global image
 template <class S>
@@ -201,8 +201,10 @@ __global__ void __launch_bounds__(256) k_f3_image(F3K k, float* __restrict__ img
 
 // =========================================================================================================================================
 // forward + head
-template <class S, int MODE, int NW>
+template <class S, int MODE_, int NW>
 __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
+    constexpr bool VPG = (MODE_ == F3_VPG);
+    constexpr int MODE = VPG ? F3_GRAD : MODE_;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), c = lane & 15, q = lane >> 4;
     if (MODE == F3_LOSSKL && k.skip != nullptr && k.skip[0] >= 0.0) return;        // speculative line-search trial after the search stopped
@@ -232,6 +234,7 @@ __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int d = 16 * cb + 4 * q + r, dc = (d < S::D4) ? d : S::D4 - 1;
+                    if (VPG) { in.act[cb][r] = k.act[nl * S::D4 + dc]; continue; }
                     in.omu[cb][r] = k.old_mean[nl * S::D4 + dc]; in.act[cb][r] = k.act[nl * S::D4 + dc];
                     in.ols[cb][r] = k.old_ls[(size_t)nl * k.ls_stride + dc];
                 }
@@ -287,7 +290,11 @@ __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
             for (int r = 0; r < 4; ++r) {
                 const int d = 16 * cb + 4 * q + r;
                 zz[cb][r] = 0.f;
-                if (d < S::D4 && ok) {
+                if (VPG && d < S::D4 && ok) {              // DiagonalGaussian.log_likelihood_sym, less its constant (added per sample below)
+                    const float z = (in.act[cb][r] - mu[cb][r]) * inv_std[cb][r];
+                    llr -= ls[cb][r] + 0.5f * z * z;
+                    zz[cb][r] = z;
+                } else if (d < S::D4 && ok) {
                     const float omu = in.omu[cb][r], a = in.act[cb][r], ols = in.ols[cb][r];
                     const float eo = expf(-ols);
                     const float z = (a - mu[cb][r]) * inv_std[cb][r], zo = (a - omu) * eo;
@@ -300,8 +307,8 @@ __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
                 }
             }
         llr = xsum_q3(llr);                                 // the four q-lanes of sample c hold its action dims between them
-        const float la = ok ? expf(llr) * in.adv : 0.f;     // lr * adv
-        if (q == 0) acc0 -= la * k.inv_n;                   // surr_loss = -mean(lr * adv), once per sample
+        const float la = ok ? (VPG ? in.adv : expf(llr) * in.adv) : 0.f;     // lr * adv (VPG: ratio 1)
+        if (q == 0) acc0 -= (VPG ? (llr - S::D4 * HALF_LOG_2PI) * la : la) * k.inv_n;   // surr_loss = -mean(lr * adv) | -mean(logli * adv), once per sample
         if (MODE == F3_LOSSKL) { acc1 += kl * k.inv_n; continue; }
         const float w = -la * k.inv_n;
         f32x4* __restrict__ uw = k.u + (size_t)tile * S::CB4 * 64 + lane;
@@ -656,7 +663,7 @@ template <class K> static int f3_attr(metrpo_ctx* c, K kern, size_t sh) {
     return METRPO_OK;
 }
 
-// mode 0 gradient, 1 Fisher-vector product, 2 loss + KL; per-block rows of P + 3 floats land in `partials` (the layout k_finalize reads)
+// mode 0 gradient, 1 Fisher-vector product, 2 loss + KL, UPD_VPG the VPG gradient; per-block rows of P + 3 floats land in `partials` (the layout k_finalize reads)
 int policy_f3_launch(metrpo_ctx* c, int mode, const metrpo_batch* b, const float* theta, const float* vf, float* partials, int nblocks,
                      hipStream_t st) {
     typedef ShHumanoid S;
@@ -681,7 +688,12 @@ int policy_f3_launch(metrpo_ctx* c, int mode, const metrpo_batch* b, const float
         HIP_TRY(c, hipGetLastError());
         return METRPO_OK;
     }
-    if (mode == 0) {
+    if (mode == UPD_VPG) {
+        build_image(IMG_WHAT_F | IMG_WHAT_B); c->f3_img_ok = 1;
+        if ((rc = f3_attr(c, k_f3_fwd<S, F3_VPG, FWD_NW>, sh_fwd))) return rc;
+        hipLaunchKernelGGL((k_f3_fwd<S, F3_VPG, FWD_NW>), g, dim3(FWD_NW * 64), sh_fwd, st, k);
+        c->f3_rows = -1;                                    // (no CG solve follows)
+    } else if (mode == 0) {
         build_image(IMG_WHAT_F | IMG_WHAT_B); c->f3_img_ok = 1;
         if ((rc = f3_attr(c, k_f3_fwd<S, F3_GRAD, FWD_NW>, sh_fwd))) return rc;
         hipLaunchKernelGGL((k_f3_fwd<S, F3_GRAD, FWD_NW>), g, dim3(FWD_NW * 64), sh_fwd, st, k);

@@ -109,7 +109,8 @@ __global__ void k_pg_pad_obs(const float* __restrict__ obs, long long N, int ns,
 }
 
 // per-sample head, gradient mode (npo.py:69,75): U = d loss / d mean, per-block partial sums of loss and d loss / d log_std
-// part row (doubles): [0] loss, [1] kl, [2] valid weight, [3 .. 3+na) dls
+// part row (doubles): [0] loss, [1] kl, [2] valid weight, [3 .. 3+na) dls.  VPG (mode 0 only): the VPG surrogate (vpg.py:88), la = adv, loss = -mean(logli * adv)
+template <bool VPG>
 __global__ void __launch_bounds__(256) k_pg_head(int mode, PolK k, int na, int nap, const float* __restrict__ MU, const float* __restrict__ log_std,
                                                  float* __restrict__ U, double* __restrict__ parts) {
     __shared__ double sh[16];
@@ -134,6 +135,13 @@ __global__ void __launch_bounds__(256) k_pg_head(int mode, PolK k, int na, int n
         for (int d = 0; d < na; ++d) {
             zz[d] = 0.0f;
             if (!ok) continue;
+            if (VPG) {                                       // DiagonalGaussian.log_likelihood_sym, less its constant (added below)
+                const float ls = fmaxf(log_std[d], LOG_MIN_STD);
+                const float z = (k.act[n * na + d] - MU[n * nap + d]) * expf(-ls);
+                llr -= ls + 0.5f * z * z;
+                zz[d] = z;
+                continue;
+            }
             const float ls = fmaxf(log_std[d], LOG_MIN_STD), mu = MU[n * nap + d];
             const float ols = k.old_ls[(size_t)n * k.ls_stride + d], omu = k.old_mean[n * na + d], a = k.act[n * na + d];
             const float z = (a - mu) * expf(-ls), zo = (a - omu) * expf(-ols);
@@ -141,8 +149,8 @@ __global__ void __launch_bounds__(256) k_pg_head(int mode, PolK k, int na, int n
             zz[d] = z;
             if (mode == 2) { const float s2 = expf(2.0f * ls), os2 = expf(2.0f * ols), dm = omu - mu; kl += (dm * dm + os2 - s2) / (2.0f * s2 + KL_EPS) + ls - ols; }
         }
-        const float la = ok ? expf(llr) * k.adv[n] : 0.0f;   // lr * adv
-        acc[0] -= (double)(la * k.inv_n);                    // surr_loss = -mean(lr * adv)
+        const float la = ok ? (VPG ? k.adv[n] : expf(llr) * k.adv[n]) : 0.0f;   // lr * adv (VPG: ratio 1)
+        acc[0] -= VPG ? (double)((llr - na * HALF_LOG_2PI) * la * k.inv_n) : (double)(la * k.inv_n);   // surr_loss = -mean(lr * adv) | -mean(logli * adv)
         if (mode == 2) { acc[1] += (double)(kl * k.inv_n); continue; }
         const float w = -la * k.inv_n;
         for (int d = 0; d < nap; ++d) {
@@ -263,12 +271,14 @@ static int pg_ensure(metrpo_ctx* c, const PgLay& g, long long N, PgBufs* B) {
     return METRPO_OK;
 }
 
-// mode 0 grad (+ VJP when c->vjp_gm), 1 fvp, 2 loss/kl.  Writes `out` like k_finalize and then runs `tail` (may be NULL).
+// mode 0 grad (+ VJP when c->vjp_gm), 1 fvp, 2 loss/kl, UPD_VPG the VPG gradient (out as mode 0).  Writes `out` like k_finalize and then runs `tail` (may be NULL).
 int policy_gemm_run(metrpo_ctx* c, int mode, const metrpo_batch* b, const PolK& k0, const float* theta, const float* vf, const double* v64,
                     double* out, const CgTail* tail, hipStream_t st) {
     const ProblemDesc& pd = c->pd;
     const long long N = b->N;
     if (N > 2000000000LL) return set_err(c, METRPO_EUNSUPPORTED, "policy_gemm: N too large");
+    const bool vpg = (mode == UPD_VPG);                      // the gradient mode with the VPG head
+    if (vpg) mode = 0;
     const PgLay g = pg_layout(pd, N);
     PgBufs B;
     int rc = pg_ensure(c, g, N, &B); if (rc) return rc;
@@ -325,7 +335,8 @@ int policy_gemm_run(metrpo_ctx* c, int mode, const metrpo_batch* b, const PolK& 
     const bool head_elem = (mode == 1 && k.gm == nullptr);
     const int nblk = head_elem ? (int)std::min<long long>(1024, (N * nap + 2047) / 2048) : (int)std::min<long long>(1024, (N + 255) / 256);
     if (head_elem) hipLaunchKernelGGL(k_pg_head_fvp, dim3(nblk), dim3(256), 0, st, k, na, nap, MU, theta + pd.pol.n_params, U, B.hparts);
-    else hipLaunchKernelGGL(k_pg_head, dim3(nblk), dim3(256), 0, st, mode, k, na, nap, MU, theta + pd.pol.n_params, U, B.hparts);
+    else if (vpg) hipLaunchKernelGGL(k_pg_head<true>, dim3(nblk), dim3(256), 0, st, mode, k, na, nap, MU, theta + pd.pol.n_params, U, B.hparts);
+    else hipLaunchKernelGGL(k_pg_head<false>, dim3(nblk), dim3(256), 0, st, mode, k, na, nap, MU, theta + pd.pol.n_params, U, B.hparts);
     if (mode != 2) {
         // back-prop D_l = (D_{l+1} W_l^T) * (1 - H_l^2), l = L-1 .. 1
         for (long long r0 = 0; r0 < N; r0 += CH) {

@@ -81,7 +81,9 @@ __device__ __forceinline__ float xsum_c(float v) {
     return v;
 }
 
-enum { MODE_GRAD = 0, MODE_FVP = 1, MODE_LOSSKL = 2, MODE_FVPC = 3 };
+enum { MODE_GRAD = 0, MODE_FVP = 1, MODE_LOSSKL = 2, MODE_FVPC = 3, MODE_VPG = UPD_VPG };
+// MODE_VPG: the gradient kernel with the VPG surrogate's head (algos/vpg.py:88): la = adv (ratio 1), loss = -mean(logli * adv); the old
+// distribution is not read.  Everything else is MODE_GRAD's code.
 // (Measured and parked, tools/experiments/policy_mfma_with_cgp.hip + profiles/r05_update_levers.txt: issue priorities per SIMD wave pair (POL_PRIO), h0 recomputed instead of
 // cached (POL_H0R, +4.8 us per product), weight-gradient products deferred into the next tile's vector stretch (POL_DEFER_S7, 60.5 vs 59.8 us), the CG solve as one launch.)
 // MODE_FVPC: Fisher-vector product with the hidden activations h0, h1 = tanh(.) read from the cache the gradient kernel of the
@@ -105,8 +107,8 @@ struct PolImg {
 template <int NS, int NA, int PH, int MODE_>
 __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict__ theta, const float* __restrict__ v, float* __restrict__ partials) {
     using I = PolImg<NS, NA, PH>;
-    constexpr bool CACHED = (MODE_ == MODE_FVPC);
-    constexpr int MODE = CACHED ? MODE_FVP : MODE_;
+    constexpr bool CACHED = (MODE_ == MODE_FVPC), VPG = (MODE_ == MODE_VPG);
+    constexpr int MODE = CACHED ? MODE_FVP : VPG ? MODE_GRAD : MODE_;
     constexpr int NS_KS = I::NS_KS, NSI = cdiv_(NS, 16), HB = I::HB, KK = I::KK;
     constexpr int pW0 = 0, pb0 = NS * PH, pW1 = pb0 + PH, pb1 = pW1 + PH * PH, pW2 = pb1 + PH, pb2 = pW2 + PH * NA,
                   pLS = pb2 + NA, P = pLS + NA, ROW = P + PART_EXTRA;
@@ -127,7 +129,7 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
     const f32x4* __restrict__ hc = (const f32x4*)k.hcache;
     // a state-independent old log_std (stride 0: the reference's GaussianMLPPolicy) is one value per action dim for the whole batch: its loads
     // and its two exponentials per sample leave the tile loop (the loss / KL kernel is VALU-bound: 340 instructions per tile, 39 transcendental)
-    const bool ols_const = (MODE != MODE_FVP) && k.ls_stride == 0 && k.old_ls != nullptr;
+    const bool ols_const = !VPG && (MODE != MODE_FVP) && k.ls_stride == 0 && k.old_ls != nullptr;
     // Everything a tile reads from HBM (observations in both layouts, valid flag, cached activations, and for the loss modes the old
     // distribution / action / advantage) is fetched ONE TILE AHEAD into registers: consumed in the iteration that issued them, the
     // valid flag and the observation loads each put a full HBM round trip (~2000 cycles) on the wave's critical path, per tile.
@@ -165,6 +167,7 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int d = 4 * q + r, dc = (d < NA) ? d : NA - 1;
+                    if (VPG) { in.act[r] = k.act[nl * NA + dc]; continue; }
                     in.ols[r] = ols_const ? 0.f : k.old_ls[(size_t)nl * k.ls_stride + dc]; in.omu[r] = k.old_mean[nl * NA + dc]; in.act[r] = k.act[nl * NA + dc];
                 }
                 in.adv = k.adv[nl];
@@ -253,7 +256,7 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
     // k.img_map[i] = source index of image element i in theta (bit 30 clear) or in v (bit 30 set), -1 = zero; built once on the
     // host (pol_image_map).  Map loads, gathers and LDS stores are issued in independent batches of IMG_U per thread: the
     // prologue costs ~2 L2 round trips instead of one dependent global load per element.
-    constexpr int SPL = POL_SPLIT_R ? ((MODE_ == MODE_GRAD || MODE_ == MODE_FVP) ? POL_SPLIT_R : POL_SPLIT_R_FVP) : 0;      // rounds of the uneven tile deal (0: equal shares)
+    constexpr int SPL = POL_SPLIT_R ? ((MODE == MODE_GRAD || MODE_ == MODE_FVP) ? POL_SPLIT_R : POL_SPLIT_R_FVP) : 0;      // rounds of the uneven tile deal (0: equal shares)
     const long long first_tile = SPL ? (long long)blockIdx.x * 4 + (wave & 3) + ((wave < 4) ? 0 : 1) * (long long)gridDim.x * 4 : (long long)blockIdx.x * NWAVES + wave;
     if (CACHED && k.imgval != nullptr) {
         // inside a fused CG solve the image already exists in global memory, element for element (weight entries: published by block 0 of the
@@ -437,7 +440,11 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int d = 4 * q + r;
-                if (d < NA && ok) {
+                if (VPG && d < NA && ok) {                  // DiagonalGaussian.log_likelihood_sym, less its constant (added per sample below)
+                    const float z = (in.act[r] - mu[r]) * inv_std[r];
+                    llr -= ls[r] + 0.5f * z * z;
+                    zz[r] = z;
+                } else if (d < NA && ok) {
                     const float omu = in.omu[r], a = in.act[r];
                     float ols, eo, os2 = 0.f;
                     if (ols_const) { ols = ols_c[r]; eo = eo_c[r]; os2 = os2_c[r]; }          // wave-uniform branch
@@ -457,8 +464,8 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
                 }
             }
             llr = xsum_q(llr);                              // sum over action dims held by the 4 q-lanes of sample c
-            const float la = ok ? expf(llr) * in.adv : 0.f;         // lr * adv
-            if (q == 0) acc0 -= la * k.inv_n;               // surr_loss = -mean(lr*adv) (npo.py:75), once per sample
+            const float la = ok ? (VPG ? in.adv : expf(llr) * in.adv) : 0.f;         // lr * adv (VPG: ratio 1)
+            if (q == 0) acc0 -= (VPG ? (llr - NA * HALF_LOG_2PI) * la : la) * k.inv_n;   // surr_loss = -mean(lr*adv) (npo.py:75) | -mean(logli*adv) (vpg.py:88)
             if (MODE == MODE_LOSSKL) { acc1 += kl * k.inv_n; continue; }
             const float w = -la * k.inv_n;
 #pragma unroll
@@ -716,7 +723,7 @@ static void pol_image_map(std::vector<int>& map) {
 
 // -------------------------------------------------------------------------------------------------
 typedef void (*pol_kernel_t)(PolK, const float*, const float*, float*);
-struct PolEntry { int ns, na, ph; pol_kernel_t kern[4]; int lds_floats, lds_floats_eval; void (*build_map)(std::vector<int>&); };
+struct PolEntry { int ns, na, ph; pol_kernel_t kern[5]; int lds_floats, lds_floats_eval; void (*build_map)(std::vector<int>&); };
 template <int NS, int NA, int PH> constexpr int pol_lds() {
     constexpr int HB = cdiv_(PH, 16);
     constexpr int a = PolImg<NS, NA, PH>::TOTAL + NWAVES * (3 * HB + (NA <= 2 ? 0 : 1)) * 16 * 20;      // 20 = TS of the kernel's transpose tiles
@@ -729,7 +736,7 @@ template <int NS, int NA, int PH> constexpr int pol_lds_eval() {       // MODE_L
     constexpr int a = PolImg<NS, NA, PH>::TOTAL, b = NWAVES * (P + PART_EXTRA);
     return a > b ? a : b;
 }
-#define PENTRY(NS, NA, PH) {NS, NA, PH, {k_policy_mfma<NS, NA, PH, 0>, k_policy_mfma<NS, NA, PH, 1>, k_policy_mfma<NS, NA, PH, 2>, k_policy_mfma<NS, NA, PH, 3>}, pol_lds<NS, NA, PH>(), pol_lds_eval<NS, NA, PH>(), pol_image_map<NS, NA, PH>}
+#define PENTRY(NS, NA, PH) {NS, NA, PH, {k_policy_mfma<NS, NA, PH, 0>, k_policy_mfma<NS, NA, PH, 1>, k_policy_mfma<NS, NA, PH, 2>, k_policy_mfma<NS, NA, PH, 3>, k_policy_mfma<NS, NA, PH, MODE_VPG>}, pol_lds<NS, NA, PH>(), pol_lds_eval<NS, NA, PH>(), pol_image_map<NS, NA, PH>}
 static const PolEntry kPol[] = {
     PENTRY(10, 2, 32),    // swimmer
     PENTRY(18, 6, 32),    // half-cheetah

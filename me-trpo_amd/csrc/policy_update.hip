@@ -4,6 +4,8 @@
 //   k_fvp        -- Hessian(mean_kl) . v  (Gauss-Newton form, exact at theta_old; derivation in DESIGN.md)
 //   k_loss_kl    -- surrogate loss + mean KL at a trial theta (f_loss_constraint)
 //   k_finalize   -- fixed-order (deterministic) float64 reduction of the per-block partial rows
+// and of the VPG update (algos/vpg.py:88): k_loss_grad<PT, true> (surr_obj = -mean(logli * adv), no likelihood ratio) and k_finalize<true>,
+// whose blocks apply one TF-Adam step to the columns they reduced (run_vpg_update).
 //
 // Generic VALU formulation: a block of PT threads owns tiles of PT samples.  Phase A is thread-per-
 // sample (forward / tangent / back-prop in LDS columns, weights via scalar loads); phase B is
@@ -102,7 +104,9 @@ __device__ __forceinline__ void backward_accumulate(const NetDesc& net, const fl
 //   [P] = loss (or kl-side scalar), [P+1] = second scalar, [P+2] = valid-sample weight (count*inv_n)
 #define PART_EXTRA 3
 
-template <int PT>
+// VPG: the VPG surrogate (vpg.py:88) instead of NPO's: loss = -mean(logli * adv) with logli = DiagonalGaussian.log_likelihood_sym(act; mean,
+// log_std) = -sum(ls) - 0.5 sum(z^2) - 0.5 na log(2 pi); its gradient is NPO's at ratio 1 (la = adv).  old_mean / old_log_std are not read.
+template <int PT, bool VPG>
 __global__ void __launch_bounds__(PT) k_loss_grad(ProblemDesc pd, PolK k, const float* __restrict__ theta, float* __restrict__ partials) {
     constexpr int PLD = PT + 1;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -131,7 +135,17 @@ __global__ void __launch_bounds__(PT) k_loss_grad(ProblemDesc pd, PolK k, const 
             continue;
         }
         float w = 0.0f;
-        if (ok) {
+        if (ok && VPG) {
+            float logli = -(float)na * HALF_LOG_2PI;             // DiagonalGaussian.log_likelihood_sym
+            for (int d = 0; d < na; ++d) {
+                const float ls = fmaxf(raw_ls[d], LOG_MIN_STD);
+                const float z = (k.act[n * na + d] - DM[d * PLD + tid]) * expf(-ls);
+                logli -= ls + 0.5f * z * z;
+            }
+            const float la = k.adv[n];                           // ratio 1: d(logli * adv) = adv * d logli
+            loss_acc -= (double)logli * (double)la * (double)k.inv_n;      // surr_obj = -mean(logli * adv) (vpg.py:88)
+            w = -la * k.inv_n;
+        } else if (ok) {
             float llr = 0.0f;                                   // logli_new - logli_old
             for (int d = 0; d < na; ++d) {
                 const float ls = fmaxf(raw_ls[d], LOG_MIN_STD), ols = k.old_ls[(size_t)n * k.ls_stride + d];
@@ -287,9 +301,18 @@ extern "C" int32_t metrpo_debug_fin_phases(unsigned long long* out) { return hip
 #else
 #define FT_MARK(i)
 #endif
+// k_finalize<true> (run_vpg_update, mode 0): every block applies TF-Adam (tf_adam_elem) to the theta elements of the columns it has just reduced --
+// after adding the ranks' shares in a sharded run (each block pulls exactly the columns it pushed; no other workgroup reads them, so no arrival ticket).
+// A template variant, so that the TRPO reductions (k_finalize<false>) compile to the code they had before.
+struct AdamTail {
+    float* theta; float* m; float* v;           // the ctx policy and its Adam moments (metrpo_ctx::d_pol_adam)
+    float lr_t, b1, b2, eps;                    // lr_t: the bias-corrected step size of this step (launch_policy_adam's)
+    double* loss;                               // non-NULL: the reduced loss (column 0) is also stored here
+};
+template <bool ADAM>
 __global__ void __launch_bounds__(1024) k_finalize(ProblemDesc pd, int mode, int nrows, int stride, int lk_col,
                                                    const float* __restrict__ partials, const float* __restrict__ theta,
-                                                   const double* __restrict__ v, double* __restrict__ out, CgTail tail, XchgK xc) {
+                                                   const double* __restrict__ v, double* __restrict__ out, CgTail tail, XchgK xc, AdamTail ad) {
     // block = FIN_C output columns x (1024 / FIN_C) row slices (latency-bound sum: many small blocks); slice s adds rows
     // s, s+NSL, ... and the slice sums are added in slice order: deterministic.  32 columns = one 128-byte line per row read.
     constexpr int NSL = 1024 / FIN_C;
@@ -335,6 +358,13 @@ __global__ void __launch_bounds__(1024) k_finalize(ProblemDesc pd, int mode, int
             const double c = 4.0 * s2 * (2.0 * s2 - 1e-8) / ((2.0 * s2 + 1e-8) * (2.0 * s2 + 1e-8));
             t = (raw > (double)LOG_MIN_STD) ? c * v[p] * t : 0.0;
         }
+        if (ADAM) {
+            if (xc.world > 1) { xchg_push(xc, p, t); t = xchg_pull_sum(xc, p); }
+            out[p] = t;
+            if (p == 0) { if (ad.loss != nullptr) *ad.loss = t; }
+            else tf_adam_elem((float)t, ad.theta, ad.m, ad.v, p - 1, ad.lr_t, ad.b1, ad.b2, ad.eps);
+            return;
+        }
         // a fused tail reads `out` in ANOTHER workgroup (the last to arrive): write-through (sc1) stores, drained before the arrival ticket, instead of a
         // cache-wide release per workgroup (buffer_wbl2 x 45 workgroups at C1, x 391 for the 100-50-25 policy: 25-49 us of that reduction).
         // This relies on gfx942 / gfx950 lowering a relaxed agent-scope atomic store to an sc1 write-through store (visible beyond this XCD's L2 once vmcnt
@@ -348,7 +378,7 @@ __global__ void __launch_bounds__(1024) k_finalize(ProblemDesc pd, int mode, int
         else out[p] = t;
         if (xc.world > 1) xchg_push(xc, p, t);                // sharded run: this rank's share goes straight into every rank's receive slot
     }
-    if (tail.op == 0 && xc.world <= 1) return;
+    if (ADAM || (tail.op == 0 && xc.world <= 1)) return;
     // ---- fused tail: the last block to arrive owns the complete `out` vector: it adds the ranks' shares (one-shot exchange,
     //      xchg_device.h; the packets of the other blocks have been under way since they were produced) and runs the CG vector step ----
     __shared__ unsigned int s_last;
@@ -384,12 +414,14 @@ static int ensure_partials(metrpo_ctx* c, int nrows) {
     return ws_grow(c, c->d_partials, need * sizeof(float));
 }
 
-static int fill_polk(metrpo_ctx* c, const metrpo_batch* b, PolK* k, bool need_targets) {
+// vpg: the VPG surrogate reads no old distribution -- d_old_mean / d_old_log_std may be NULL
+static int fill_polk(metrpo_ctx* c, const metrpo_batch* b, PolK* k, bool need_targets, bool vpg = false) {
     if (!b || !b->d_obs) return set_err(c, METRPO_ENULL, "batch/d_obs is NULL");
     if (b->N <= 0) return set_err(c, METRPO_EINVAL, "batch N must be positive");
     if (c->pd.na > 32) return set_err(c, METRPO_EUNSUPPORTED, "na > 32");
-    if (need_targets && (!b->d_act || !b->d_adv || !b->d_old_mean || !b->d_old_log_std))
+    if (need_targets && (!b->d_act || !b->d_adv || (!vpg && (!b->d_old_mean || !b->d_old_log_std))))
         return set_err(c, METRPO_ENULL, "batch pointer is NULL");
+    if (vpg && !(b->inv_n_global > 0.0)) return set_err(c, METRPO_EINVAL, "batch inv_n_global must be positive");
     k->obs = b->d_obs; k->act = b->d_act; k->adv = b->d_adv; k->old_mean = b->d_old_mean; k->old_ls = b->d_old_log_std;
     k->ls_stride = b->old_log_std_stride; k->valid = b->d_valid; k->N = b->N; k->inv_n = (float)b->inv_n_global;
     k->gm = nullptr; k->img_map = nullptr; k->hcache = nullptr; k->imgval = nullptr; k->skip = nullptr;
@@ -397,13 +429,17 @@ static int fill_polk(metrpo_ctx* c, const metrpo_batch* b, PolK* k, bool need_ta
 }
 
 static void finalize(metrpo_ctx* c, int mode, int nrows, int stride, int lk_col, const double* v, double* out, hipStream_t st,
-                     const CgTail* tail = nullptr) {
+                     const CgTail* tail = nullptr, const AdamTail* adam = nullptr) {
     const int nout = (mode == 0) ? c->pd.P + 1 : (mode == 1) ? c->pd.P : 2;
     CgTail none; none.op = 0; none.ticket = c->d_ticket.p; none.vpos = nullptr; none.imgval = nullptr; none.ls = nullptr; none.pub_dst = nullptr;
     // inside a fused update of a sharded run (run_trpo_update raises xg_fuse) the reduction carries the cross-rank sum in its tail
     const XchgK xc = (c->xg_fuse && c->xg_world > 1) ? xchg_next(c) : xchg_none();
-    hipLaunchKernelGGL(k_finalize, dim3((nout + FIN_C - 1) / FIN_C), dim3(1024), 0, st, c->pd, mode, nrows, stride, lk_col,
-                       c->d_partials.p, c->d_theta.p, v, out, tail ? *tail : none, xc);
+    if (adam)
+        hipLaunchKernelGGL(k_finalize<true>, dim3((nout + FIN_C - 1) / FIN_C), dim3(1024), 0, st, c->pd, mode, nrows, stride, lk_col,
+                           c->d_partials.p, c->d_theta.p, v, out, none, xc, *adam);
+    else
+        hipLaunchKernelGGL(k_finalize<false>, dim3((nout + FIN_C - 1) / FIN_C), dim3(1024), 0, st, c->pd, mode, nrows, stride, lk_col,
+                           c->d_partials.p, c->d_theta.p, v, out, tail ? *tail : none, xc, AdamTail{});
 }
 
 // generic kernels: pick the largest sample tile (threads per block) whose LDS columns fit
@@ -411,7 +447,7 @@ template <int PT>
 static int launch_generic(metrpo_ctx* c, int mode, const PolK& k, const float* theta, const float* vf, int* nrows, hipStream_t st) {
     const NetDesc& net = c->pd.pol;
     int hrows = 0; for (int l = 0; l < net.n_layers; ++l) hrows += net.dims[l];
-    size_t rows = (mode == 0) ? hrows + c->pd.na : (mode == 1) ? hrows + c->pd.na + (hrows - net.dims[0])
+    size_t rows = (mode == 0 || mode == UPD_VPG) ? hrows + c->pd.na : (mode == 1) ? hrows + c->pd.na + (hrows - net.dims[0])
                                                               : (size_t)c->pd.ns + 2 * net.max_width;
     const size_t sh = rows * (PT + 1) * sizeof(float);
     if (sh > 160 * 1024) return METRPO_EUNSUPPORTED;
@@ -420,8 +456,11 @@ static int launch_generic(metrpo_ctx* c, int mode, const PolK& k, const float* t
     int rc = ensure_partials(c, g); if (rc) return rc;
     *nrows = g;
     if (mode == 0) {
-        if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_loss_grad<PT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        hipLaunchKernelGGL(k_loss_grad<PT>, dim3(g), dim3(PT), sh, st, c->pd, k, theta, c->d_partials.p);
+        if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_loss_grad<PT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+        hipLaunchKernelGGL((k_loss_grad<PT, false>), dim3(g), dim3(PT), sh, st, c->pd, k, theta, c->d_partials.p);
+    } else if (mode == UPD_VPG) {
+        if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_loss_grad<PT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+        hipLaunchKernelGGL((k_loss_grad<PT, true>), dim3(g), dim3(PT), sh, st, c->pd, k, theta, c->d_partials.p);
     } else if (mode == 1) {
         if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_fvp<PT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
         hipLaunchKernelGGL(k_fvp<PT>, dim3(g), dim3(PT), sh, st, c->pd, k, theta, vf, c->d_partials.p);
@@ -544,5 +583,59 @@ int launch_loss_kl(metrpo_ctx* c, const metrpo_batch* b, const float* theta, dou
     if ((rc = run_mode(c, 2, b, k, theta ? theta : c->d_theta.p, nullptr, &nrows, &stride, &lk, st))) return rc;
     finalize(c, 2, nrows, stride, lk, nullptr, out, st, decide);
     HIP_TRY(c, hipGetLastError());
+    return METRPO_OK;
+}
+
+// ---- 'vpg' (algos/vpg.py; FirstOrderOptimizer with batch_size=None, max_epochs=1: one Adam step on the whole batch's gradient) ----
+int launch_vpg_loss_grad(metrpo_ctx* c, const metrpo_batch* b, double* out, hipStream_t st) {
+    PolK k; int rc = fill_polk(c, b, &k, true, true); if (rc) return rc;
+    if (policy_gemm_applicable(c, b->N)) return policy_gemm_run(c, UPD_VPG, b, k, c->d_theta.p, nullptr, nullptr, out, nullptr, st);
+    int nrows, stride, lk;
+    if ((rc = run_mode(c, UPD_VPG, b, k, c->d_theta.p, nullptr, &nrows, &stride, &lk, st))) return rc;
+    finalize(c, 0, nrows, stride, lk, nullptr, out, st);
+    HIP_TRY(c, hipGetLastError());
+    return METRPO_OK;
+}
+
+// k_finalize<true>'s step as a launch of its own: behind an all-reduce that k_finalize cannot carry (RCCL, a gradient longer than an exchange slot)
+// and behind the GEMM path's own reduction.  gout = [loss | gradient], summed over the ranks.
+__global__ void k_vpg_adam(const double* __restrict__ gout, int P, AdamTail ad) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0 && ad.loss != nullptr) *ad.loss = gout[0];
+    if (i < P) tf_adam_elem((float)gout[1 + i], ad.theta, ad.m, ad.v, i, ad.lr_t, ad.b1, ad.b2, ad.eps);
+}
+
+int run_vpg_update(metrpo_ctx* c, const metrpo_batch* b, const metrpo_vpg_params* pr, double* d_loss, hipStream_t st) {
+    const int P = c->pd.P;
+    if (!pr) return set_err(c, METRPO_ENULL, "vpg_update: params NULL");
+    if (!(pr->lr >= 0.0) || !(pr->beta1 >= 0.0 && pr->beta1 < 1.0) || !(pr->beta2 >= 0.0 && pr->beta2 < 1.0) || !(pr->eps >= 0.0))
+        return set_err(c, METRPO_EINVAL, "vpg_update: need lr >= 0, 0 <= beta1, beta2 < 1, eps >= 0");
+    PolK k; int rc = fill_polk(c, b, &k, true, true); if (rc) return rc;
+    if ((rc = ensure_policy_adam(c))) return rc;
+    // TF's bias correction folded into the step size, exactly as launch_policy_adam (bptt.hip) computes it
+    const int t1 = c->pol_adam_t + 1;
+    const double lr_t = pr->lr * std::sqrt(1.0 - std::pow(pr->beta2, (double)t1)) / (1.0 - std::pow(pr->beta1, (double)t1));
+    float* am = (float*)c->d_pol_adam.p;
+    const AdamTail ad = {c->d_theta.p, am, am + P, (float)lr_t, (float)pr->beta1, (float)pr->beta2, (float)pr->eps, d_loss};
+    double* gout = c->d_cg.p;                               // [1 + P] of the CG workspace (no update is open across this call)
+    const bool gemm = policy_gemm_applicable(c, b->N);
+    const bool xg = c->xg_world > 1;
+    // the step rides in the reduction's tail unless an all-reduce the reduction cannot carry has to sit between them
+    const bool fused = !gemm && (xg ? (P + 1 <= c->xg_cap) : (c->nccl_comm == nullptr));
+    if (gemm) {
+        if ((rc = policy_gemm_run(c, UPD_VPG, b, k, c->d_theta.p, nullptr, nullptr, gout, nullptr, st))) return rc;
+    } else {
+        int nrows, stride, lk;
+        if ((rc = run_mode(c, UPD_VPG, b, k, c->d_theta.p, nullptr, &nrows, &stride, &lk, st))) return rc;
+        c->xg_fuse = (fused && xg) ? 1 : 0;
+        finalize(c, 0, nrows, stride, lk, nullptr, gout, st, nullptr, fused ? &ad : nullptr);
+        c->xg_fuse = 0;
+    }
+    if (!fused) {
+        if ((xg || c->nccl_comm) && (rc = comm_allreduce_f64(c, gout, P + 1, st))) return rc;
+        hipLaunchKernelGGL(k_vpg_adam, dim3((P + 255) / 256), dim3(256), 0, st, (const double*)gout, P, ad);
+    }
+    HIP_TRY(c, hipGetLastError());
+    c->pol_adam_t = t1;
     return METRPO_OK;
 }

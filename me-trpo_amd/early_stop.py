@@ -64,10 +64,15 @@ def update_stats(min_validation_costs, candidates, whole=False):
 def optimize_policy(algo, validation_init, T, gamma, mode='estimated', whole=True, log_every=5,
                     num_iters_threshold=25, max_iters=400, stop_fn=None, reset_log_std=True, real_cost_fn=None,
                     logger=None, init_pool=None):
-    """TRPO branch of model_based_rl.py:optimize_policy; a BPTT object as `algo` runs its 'bptt' / 'bptt-stochastic' branch instead
+    """TRPO branch of model_based_rl.py:optimize_policy (a VPG object runs the same branch: optimize_policy_vpg); a BPTT object as `algo` runs its
+    'bptt' / 'bptt-stochastic' branch instead
     (optimize_policy_bptt; `init_pool` is then its source of reset states).  `real_cost_fn()` stands in for
     evaluate_fixed_init_trajectories on the real simulator (out of scope; None -> 0.0)."""
     from .bptt import BPTT
+    from .algos import VPG
+    if isinstance(algo, VPG):
+        return optimize_policy_vpg(algo, validation_init, T, gamma, mode=mode, whole=whole, log_every=log_every, num_iters_threshold=num_iters_threshold,
+                                   max_iters=max_iters, stop_fn=stop_fn, reset_log_std=reset_log_std, real_cost_fn=real_cost_fn, logger=logger)
     if isinstance(algo, BPTT):
         return optimize_policy_bptt(algo, validation_init, T, gamma, init_pool, mode=mode, whole=whole, log_every=log_every,
                                     num_iters_threshold=num_iters_threshold, max_iters=max_iters, stop_fn=stop_fn, real_cost_fn=real_cost_fn,
@@ -113,6 +118,53 @@ def optimize_policy(algo, validation_init, T, gamma, mode='estimated', whole=Tru
             if j - best_index >= num_iters_threshold:                      # :1298
                 break
     eng.set_policy(snapshot)                                               # log_and_restore, :1301/:1400
+    return dict(best_index=best_index, last_index=j, min_validation_costs=min_costs, history=history)
+
+
+def optimize_policy_vpg(vpg, validation_init, T, gamma, mode='estimated', whole=True, log_every=5, num_iters_threshold=25, max_iters=400,
+                        stop_fn=None, reset_log_std=True, real_cost_fn=None, logger=None):
+    """'vpg' branch of model_based_rl.py:optimize_policy (:1171-1180 with the rllab VPG): the TRPO branch's loop with three differences of the
+    reference's wiring.  The Saver (:495) covers every global variable, so the snapshot (:1127 / :1291) and the restore (:1400) carry theta AND
+    VPG's Adam state (m, v, t) together.  policy_adam_init is empty for non-BPTT algorithms (:398-405): the Adam state is not reset at entry and
+    carries over between calls.  trpo_mean is computed for algo == 'trpo' only (:1219-1231): its candidate is 0.0 here."""
+    eng = vpg.engine
+    stop_fn = stop_fn or stop_critereon(0.10, 1e-5, 0.30)
+    if reset_log_std:
+        vpg.policy.reset_log_std()                                         # kwargs['reset_opt'] (training.py:350-352), :1119-1121
+
+    def save():
+        m, v, t = eng.get_policy_adam()
+        return eng.get_policy().clone(), m.clone(), v.clone(), t
+
+    def restore(snap):
+        theta, m, v, t = snap
+        eng.set_policy(theta)
+        eng.set_policy_adam(m, v, t)
+    snapshot = save()                                                      # saver.save, :1127-1129
+    real = (lambda: float(real_cost_fn())) if real_cost_fn else (lambda: 0.0)
+    est = lambda: eng.validation_cost(validation_init, T, gamma).cpu().numpy()
+    min_costs = {'real': real(), 'trpo_mean': np.inf, 'estimated': est()}  # :1153-1163
+    best_index, candidates, history = 0, {}, []
+    j = 0
+    for j in range(1, max_iters + 1):
+        vpg.start_worker()                                                 # :1175
+        paths = vpg.obtain_samples(j)
+        samples_data = vpg.process_samples(j, paths)
+        vpg.optimize_policy(j, samples_data)
+        if j % log_every == 0:                                             # :1209
+            candidates['trpo_mean'] = 0.0
+            candidates['estimated'] = est()                                # :1239-1241
+            candidates['real'] = real()
+            history.append((j, float(np.mean(candidates['estimated']))))
+            if logger:
+                logger('iter %d est=%s' % (j, np.array_str(candidates['estimated'], precision=3)))
+            if not is_done(mode, stop_fn, min_costs, candidates):          # :1286-1295
+                best_index = j
+                snapshot = save()
+                update_stats(min_costs, candidates, whole)
+            if j - best_index >= num_iters_threshold:                      # :1298
+                break
+    restore(snapshot)                                                      # log_and_restore, :1301/:1400
     return dict(best_index=best_index, last_index=j, min_validation_costs=min_costs, history=history)
 
 

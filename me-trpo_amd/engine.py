@@ -442,18 +442,22 @@ class Engine(object):
         dev = self.device
         obs = _f32(obs, dev).reshape(-1, self.ns); N = obs.shape[0]
         act = _f32(act, dev).reshape(N, self.na); adv = _f32(adv, dev).reshape(N)
-        old_mean = _f32(old_mean, dev).reshape(N, self.na)
-        old_log_std = _f32(old_log_std, dev)
-        stride = 0 if old_log_std.numel() == self.na else self.na
-        if stride:
-            old_log_std = old_log_std.reshape(N, self.na)
+        stride = 0
+        if old_mean is not None:             # (None: a batch for the VPG update only, which reads no old distribution)
+            old_mean = _f32(old_mean, dev).reshape(N, self.na)
+        if old_log_std is not None:
+            old_log_std = _f32(old_log_std, dev)
+            stride = 0 if old_log_std.numel() == self.na else self.na
+            if stride:
+                old_log_std = old_log_std.reshape(N, self.na)
         if valid is not None:
             valid = torch.as_tensor(valid, device=dev).to(torch.uint8).contiguous().reshape(N)
         if n_global is None:
             n_global = int(valid.sum().item()) if valid is not None else N
         b = _lib.Batch()
-        b.d_obs, b.d_act, b.d_adv, b.d_old_mean = obs.data_ptr(), act.data_ptr(), adv.data_ptr(), old_mean.data_ptr()
-        b.d_old_log_std, b.old_log_std_stride = old_log_std.data_ptr(), stride
+        b.d_obs, b.d_act, b.d_adv = obs.data_ptr(), act.data_ptr(), adv.data_ptr()
+        b.d_old_mean = old_mean.data_ptr() if old_mean is not None else None
+        b.d_old_log_std, b.old_log_std_stride = (old_log_std.data_ptr() if old_log_std is not None else None), stride
         b.d_valid = valid.data_ptr() if valid is not None else None
         b.N, b.inv_n_global = N, 1.0 / float(n_global)
         b._keep = (obs, act, adv, old_mean, old_log_std, valid)
@@ -463,6 +467,23 @@ class Engine(object):
         out = torch.empty(self.P + 1, dtype=torch.float64, device=self.device)
         self._chk(lib.metrpo_loss_grad(self._ctx, C.byref(batch), _ptr(out), self._stream()))
         return out
+
+    def vpg_loss_grad(self, batch):
+        """VPG surrogate (algos/vpg.py:88) -mean(logli * adv) and its gradient: tensor [1 + P] float64, loss_grad's layout (this rank's share)."""
+        out = torch.empty(self.P + 1, dtype=torch.float64, device=self.device)
+        self._chk(lib.metrpo_vpg_loss_grad(self._ctx, C.byref(batch), _ptr(out), self._stream()))
+        return out
+
+    def vpg_update(self, batch, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, want_loss=True):
+        """One VPG optimize_policy (vpg.py:100-118): one TF-Adam step on the whole batch's gradient, the state of get_policy_adam /
+        set_policy_adam, summed over the ranks by the communicator attached to this engine (if any).  Stream-ordered, no synchronisation;
+        returns the loss at the entry theta as a 1-element float64 device tensor (None with want_loss=False)."""
+        self._close_open_update()
+        p = _lib.VpgParams()
+        p.lr, p.beta1, p.beta2, p.eps = float(lr), float(beta1), float(beta2), float(eps)
+        loss = torch.empty(1, dtype=torch.float64, device=self.device) if want_loss else None
+        self._chk(lib.metrpo_vpg_update(self._ctx, C.byref(batch), C.byref(p), _ptr(loss), self._stream()))
+        return loss
 
     def fvp(self, batch, v):
         v = torch.as_tensor(v, device=self.device).to(torch.float64).contiguous()

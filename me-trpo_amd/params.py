@@ -1,5 +1,5 @@
 """The reference's run configuration (`params/params-*.json`, read by main.py:40-60 and unpacked in training.py:100-130 / :330-372) mapped onto
-this package: `from_params(path_or_dict)` builds the Engine, policy, baseline, imagined env and TRPO object the way training.py:297-372 and
+this package: `from_params(path_or_dict)` builds the Engine, policy, baseline, imagined env and TRPO (or VPG) object the way training.py:297-372 and
 model_based_rl.py:373-380 wire them, and returns the keyword arguments of `early_stop.optimize_policy` (policy_opt_params.{T, gamma, mode, whole,
 log_every, num_iters_threshold, max_iters, stop_critereon}) and of `dynamics_training` (dynamics_opt_params).  `shapes_from_params` is the GPU-free
 half: it only reads the keys and says which shapes the run has -- what tests/test_params.py checks against DESIGN.md section 4 for the six env files.
@@ -9,10 +9,12 @@ Keys read (params-swimmer.json:5-86):
     dynamics_model.{hidden_layers, nonlinearity, ignore_xy_input | ignore_x_input, prediction_type, use_logit_weights, regularization.constant}
     policy.hidden_layers
     policy_opt_params.{T, gamma, mode, whole, log_every, num_iters_threshold, max_iters, batch_size, sam_mode, learning_rate, grad_norm_clipping,
-                       stop_critereon.{threshold, offset, percent_models_threshold}, trpo.{init_std, step_size, discount, batch_size, reset}}
+                       stop_critereon.{threshold, offset, percent_models_threshold}, trpo.{init_std, step_size, discount, batch_size, reset},
+                       vpg.{init_std, discount, batch_size, reset}}
     dynamics_opt_params.{learning_rate.{scratch, refine}, batch_size, max_passes, log_every, num_passes_threshold, sample_mode, reinitialize,
                          stop_critereon.{threshold, offset}}
-Everything else in the files (rollout_params, sweep_iters, sample_size, *_path, vpg) steers the reference's real-simulator data collection and outer
+'algo' builds 'trpo', 'vpg' (training.py:337-352: VPG with the vpg block's batch size, discount and log_std reset), 'bptt' and 'bptt-stochastic';
+svg and l-bfgs raise.  Everything else in the files (rollout_params, sweep_iters, sample_size, *_path) steers the reference's real-simulator data collection and outer
 sweeps, which are out of scope here; those keys are passed through untouched in `Setup.params`."""
 import json
 
@@ -49,22 +51,26 @@ def shapes_from_params(path_or_dict):
     if None in acts or len(acts) != len(dm['hidden_layers']):                    # training.py:156 asserts the lengths agree
         raise ValueError("dynamics_model.nonlinearity = %r: one of %s per hidden layer" % (dm.get('nonlinearity'), sorted(_ACTS)))
     n_drop = 2 if dm.get('ignore_xy_input') else (1 if dm.get('ignore_x_input') else 0)      # training.py:146-154
-    trpo = po.get('trpo', {})
+    trpo, vpg = po.get('trpo', {}), po.get('vpg', {})
+    algo = p.get('algo', 'trpo')
     T = int(po['T'])
-    batch_size = int(trpo.get('batch_size', 5000))
+    # the sampler's batch comes from the block of the algorithm that runs (training.py:345 for vpg, :360 for trpo)
+    batch_size = int((vpg if algo == 'vpg' else trpo).get('batch_size', 5000))
     n_envs = max(1, min(int(batch_size / T), 100))                                # vectorized_sampler.py:24-27
     sc = po.get('stop_critereon', {})
     dop = p.get('dynamics_opt_params', {})
     lr = dop.get('learning_rate', {'scratch': 1e-3, 'refine': 1e-3})
     lr = dict(lr) if isinstance(lr, dict) else {'scratch': float(lr), 'refine': float(lr)}
     return dict(
-        env=env, algo=p.get('algo', 'trpo'), K=int(p['n_models']), ns=ns, na=na, n_drop=n_drop, nin=ns + na - n_drop,
+        env=env, algo=algo, K=int(p['n_models']), ns=ns, na=na, n_drop=n_drop, nin=ns + na - n_drop,
         dyn_hidden=tuple(int(h) for h in dm['hidden_layers']), dyn_act=acts, pol_hidden=tuple(int(h) for h in pol['hidden_layers']),
         dyn_reg_constant=float(dm.get('regularization', {}).get('constant', 0.0)),
         T=T, n_envs=n_envs, batch_size=batch_size, rounds=max(1, -(-batch_size // (n_envs * T))),
         sam_mode=po.get('sam_mode', 'step_rand'),
         trpo=dict(step_size=float(trpo.get('step_size', 0.01)), discount=float(trpo.get('discount', 1.0)), init_std=float(trpo.get('init_std', 1.0)),
                   reset=bool(trpo.get('reset', True))),
+        vpg=dict(discount=float(vpg.get('discount', 1.0)), init_std=float(vpg.get('init_std', 1.0)), batch_size=int(vpg.get('batch_size', 5000)),
+                 reset=bool(vpg.get('reset', True))),
         optimize_policy=dict(T=T, gamma=float(po.get('gamma', 1.0)), mode=po.get('mode', 'estimated'), whole=bool(po.get('whole', True)),
                              log_every=int(po.get('log_every', 5)), num_iters_threshold=int(po.get('num_iters_threshold', 25)),
                              max_iters=int(po.get('max_iters', 400))),
@@ -101,22 +107,28 @@ def from_params(path_or_dict, device=0, init_states=None, comm=None, seed=0, n_e
     from .policy import GaussianMLPPolicy
     from .baseline import LinearFeatureBaseline
     from .imagined_env import NeuralNetEnv, InitStatePool
-    from .algos import TRPO
+    from .algos import TRPO, VPG
     from .bptt import BPTT
     p = _load(path_or_dict)
     sh = shapes_from_params(p)
-    if sh['algo'] not in ('trpo', 'bptt', 'bptt-stochastic'):
-        raise ValueError("params 'algo' = %r: this path builds 'trpo' (and the 'bptt' / 'bptt-stochastic' updates of section 8f); vpg / svg / l-bfgs "
+    if sh['algo'] not in ('trpo', 'vpg', 'bptt', 'bptt-stochastic'):
+        raise ValueError("params 'algo' = %r: this path builds 'trpo', 'vpg' (and the 'bptt' / 'bptt-stochastic' updates of section 8f); svg / l-bfgs "
                          "are out of scope" % sh['algo'])
+    blk = sh['vpg'] if sh['algo'] == 'vpg' else sh['trpo']     # init_std / reset of the rllab algorithm that runs (training.py:350-352, 368-370)
     eng = Engine(sh['env'], sh['K'], sh['dyn_hidden'], sh['pol_hidden'], n_drop=sh['n_drop'], dyn_act=sh['dyn_act'], device=device)
-    policy = GaussianMLPPolicy(eng, init_std=sh['trpo']['init_std'], seed=seed)
+    policy = GaussianMLPPolicy(eng, init_std=blk['init_std'], seed=seed)
     baseline = LinearFeatureBaseline()
     pool = InitStatePool(synthetic.make_pool(sh['env']) if init_states is None else init_states, sh['na'])
     env = NeuralNetEnv(env=pool, inner_env=None, cost_np=sh['env'], dynamics_in=None, dynamics_outs=eng, sam_mode=sh['sam_mode'])
-    algo = TRPO(env=env, policy=policy, baseline=baseline, batch_size=sh['batch_size'], max_path_length=sh['T'], discount=sh['trpo']['discount'],
-                step_size=sh['trpo']['step_size'], sampler_args=(dict(n_envs=n_envs) if n_envs else None), comm=comm, seed=seed)
+    sargs = dict(n_envs=n_envs) if n_envs else None
+    if sh['algo'] == 'vpg':
+        algo = VPG(env=env, policy=policy, baseline=baseline, batch_size=sh['batch_size'], max_path_length=sh['T'], discount=sh['vpg']['discount'],
+                   sampler_args=sargs, comm=comm, seed=seed)
+    else:
+        algo = TRPO(env=env, policy=policy, baseline=baseline, batch_size=sh['batch_size'], max_path_length=sh['T'], discount=sh['trpo']['discount'],
+                    step_size=sh['trpo']['step_size'], sampler_args=sargs, comm=comm, seed=seed)
     stop_fn = early_stop.stop_critereon(sh['stop_critereon']['threshold'], sh['stop_critereon']['offset'], sh['stop_critereon']['percent_models_threshold'])
-    okw = dict(sh['optimize_policy'], stop_fn=stop_fn, reset_log_std=sh['trpo']['reset'])
+    okw = dict(sh['optimize_policy'], stop_fn=stop_fn, reset_log_std=blk['reset'])
     bptt, bkw = None, None
     if sh['algo'] in ('bptt', 'bptt-stochastic'):
         bptt = BPTT(eng, sh['T'], gamma=sh['optimize_policy']['gamma'], learning_rate=sh['bptt']['learning_rate'],
