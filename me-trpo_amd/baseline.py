@@ -43,7 +43,7 @@ class LinearFeatureBaseline(object):
         AtA, Aty = np.asarray(AtA, dtype=np.float64), np.asarray(Aty, dtype=np.float64)
         reg = self._reg_coeff
         for _ in range(5):
-            self._coeffs = np.linalg.lstsq(AtA + reg * np.identity(AtA.shape[0]), Aty, rcond=None)[0]
+            self._coeffs = np.linalg.lstsq(AtA + reg * np.identity(AtA.shape[0]), Aty, rcond=-1)[0]
             if not np.any(np.isnan(self._coeffs)):
                 break
             reg *= 10

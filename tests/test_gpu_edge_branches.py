@@ -203,7 +203,7 @@ def test_baseline_solve_regulariser_retry(env):
     # a regular system: one attempt, the oracle's lstsq solution of (A + reg I) x = b
     A2 = M.T @ M / (4 * F)
     gram2 = torch.tensor(np.concatenate([A2.reshape(-1), b]), dtype=torch.float64, device=eng.device)
-    want2 = np.linalg.lstsq(A2 + reg * np.eye(F), b, rcond=None)[0]
+    want2 = np.linalg.lstsq(A2 + reg * np.eye(F), b, rcond=-1)[0]
     np.testing.assert_allclose(cpu(eng.baseline_solve(gram2, reg_coeff=reg)), want2, rtol=1e-7, atol=1e-9 * np.abs(want2).max())
     # non-finite normal equations: five attempts, still non-finite -- the oracle's fit ends the same way
     A3 = A2.copy(); A3[1, 1] = np.nan
@@ -230,7 +230,7 @@ def test_baseline_solve_rank_deficient_features_match_lstsq(env):
     A, b, reg = Fm.T @ Fm, Fm.T @ y, 1e-5
     gram = torch.tensor(np.concatenate([A.reshape(-1), b]), dtype=torch.float64, device=eng.device)
     got = cpu(eng.baseline_solve(gram, reg_coeff=reg))
-    want = np.linalg.lstsq(A + reg * np.eye(Fm.shape[1]), b, rcond=None)[0]
+    want = np.linalg.lstsq(A + reg * np.eye(Fm.shape[1]), b, rcond=-1)[0]
     assert np.isfinite(got).all()
     assert np.abs(got).max() <= 10.0 * max(1.0, np.abs(want).max())                 # bounded like the minimum-norm solution
     np.testing.assert_allclose(Fm @ got, Fm @ want, rtol=0, atol=1e-6 * np.abs(y).max())      # the same fit

@@ -44,6 +44,14 @@ RETURNS = dict(rtol=1e-5, atol=1e-5)
 # ((a - mean) / (std + 1e-8), statistics summed in float64).  SURVEY 8d: atol 1e-4 after centring; observed 1.2e-6
 ADVANTAGE = dict(rtol=1e-5, atol=5e-5)
 ADVANTAGE_CENTRED = dict(rtol=1e-4, atol=1e-4)
+# k_gae itself, against the float64 restatement tests/process_ref.py (tests/test_gpu_process_kernels.py): the kernel forms the baseline values, deltas,
+# advantages and returns in float64 and rounds ONCE, when it stores adv / ret as fp32.  Its float64 value differs from the sequential float64 scan only
+# by the rounding of the composed chunk carry (a few float64 ulps of the largest term, <= 1e-13 of scale at T = 1000), so the stored value is within
+# half an fp32 ulp of the reference plus that: 1 ulp = spacing(fp32(|ref|)).  Where |ref| is tiny (cancelling terms) the float64 error of the
+# terms dominates: GAE_FLOOR x max |ref| of the case.  A carry factor in fp32, a float t/100, a V read from the wrong step miss it by orders.
+# Observed 0.50 of the bound over 37 shapes (T up to 1000, rewards up to 1e3): exactly the store's half ulp (profiles/r07_process_coverage.txt).
+GAE_ULP = 1
+GAE_FLOOR = 1e-12
 # the refitted linear baseline: normal equations from fp32 products summed in float64, solved in float64; the fit's conditioning (kappa ~ 1e3 on the
 # fixtures) multiplies the 2e-6 relative error of the moments.  Bound on predictions, relative to max |prediction|.  Observed 6.7e-5.
 BASELINE_FIT = 1e-3
