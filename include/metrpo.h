@@ -443,6 +443,41 @@ int32_t metrpo_set_policy_adam(metrpo_ctx* ctx, const float* d_m, const float* d
 int32_t metrpo_policy_adam_step(metrpo_ctx* ctx, const double* d_grad, double lr, double beta1, double beta2, double eps,
                                 double clip_val, void* stream);
 
+/* ---- 'l-bfgs' policy update (model_based_rl.py:391-398, :1197-1202): ScipyOptimizerInterface(training_policy_cost, method='L-BFGS-B')
+ * with scipy's defaults, run on the device.  L-BFGS-B 3.0 on an unbounded problem (nbd = 0) as scipy's minimize drives it, by reverse
+ * communication: each call consumes f and g at the last requested point and writes the next point to evaluate plus a task code in scipy's
+ * (task[0], task[1]) numbering (_lbfgsb_py.py status_messages / task_messages): (3, 0) FG = evaluate d_x_eval next; (4, 401) / (4, 402)
+ * CONVERGENCE; (5, 504) / (5, 502) STOP at maxiter / maxfun (checked at each new iterate, as scipy's wrapper does); (8, 0) ABNORMAL (line
+ * search failed with no stored pair).  Once the task is not FG the state is frozen and d_x_eval holds the last accepted iterate.
+ * State (float64 x, g, d, the start of the search, the S / Y ring of m pairs, the line search's scalars) is ctx-owned device memory; one
+ * single-workgroup launch per call, stream-ordered, no synchronisation. */
+typedef struct {
+    int32_t m, maxls, maxiter, maxfun;   /* scipy: maxcor 10, maxls 20, maxiter 15000, maxfun 15000 */
+    double ftol, gtol;                   /* scipy: 2.220446049250313e-09 (factr = ftol / eps = 1e7), 1e-5 */
+    int32_t lookahead;                   /* metrpo_lbfgs_policy: evaluations kept in flight ahead of the host's read of a task (1..16; 2) */
+    int32_t round_f32;                   /* metrpo_lbfgs_policy: f and g rounded to float32 before the step (TF's float32 loss; 1) */
+} metrpo_lbfgs_opts;
+typedef struct {
+    double fun;                          /* f of the last evaluation (scipy's OptimizeResult.fun) */
+    int32_t nit, nfev;                   /* iterations, evaluations (a point equal to the last one evaluated is not evaluated again) */
+    int32_t status;                      /* 0 converged, 1 maxiter / maxfun reached, 2 abnormal (scipy's warnflag) */
+    int32_t task, task_code;             /* scipy's task[0], task[1] */
+    int32_t pad_;
+} metrpo_lbfgs_result;
+/* Open a minimisation of n variables at d_x0 [n] float64; d_x_eval [n] <- x0 (the first point to evaluate).  m, maxls > 0, n > 0. */
+int32_t metrpo_lbfgs_begin(metrpo_ctx* ctx, int32_t n, const double* d_x0, const metrpo_lbfgs_opts* opts, double* d_x_eval, void* stream);
+/* One step on f = *d_f and g = d_g [n] at the last requested point: d_x_eval [n] <- the next point, d_task [2] <- the task. */
+int32_t metrpo_lbfgs_iterate(metrpo_ctx* ctx, const double* d_f, const double* d_g, double* d_x_eval, int32_t* d_task, void* stream);
+/* The state of the open minimisation as a result (fun = f of the last evaluation, nit, nfev, status, task); synchronises `stream`. */
+int32_t metrpo_lbfgs_get_result(metrpo_ctx* ctx, metrpo_lbfgs_result* out, void* stream);
+/* The 'l-bfgs' branch: x0 = float64(policy theta); each evaluation is metrpo_bptt_grad's cost and gradient at float32(x) on d_init
+ * [B][ns], f = mean over the K models (rounded to float32 with round_f32, as is g), then one step whose float32(x) goes straight into
+ * the ctx policy.  The host reads only the published task word of each step, `lookahead` evaluations behind the device.  On exit the
+ * policy is float32(last accepted iterate); the policy Adam state is untouched.  Synchronises `stream` (a bounded wait that surfaces a
+ * device fault); METRPO_ESTATE while a TRPO update is open; n must be the policy's parameter count (log_std slots have gradient 0). */
+int32_t metrpo_lbfgs_policy(metrpo_ctx* ctx, const float* d_init, int32_t B, int32_t T, double gamma, const metrpo_lbfgs_opts* opts,
+                            metrpo_lbfgs_result* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,10 +18,11 @@ from .algos import BatchPolopt, NPO, TRPO, VPG, FirstOrderOptimizer
 from . import early_stop
 from . import dynamics_training
 from .bptt import BPTT
+from .lbfgs import LBFGS
 from . import formats
 from . import tf_checkpoint
 from .params import from_params, shapes_from_params
 
 __all__ = ['Engine', 'Trajectory', 'xavier_policy_theta', 'Comm', 'NeuralNetEnv', 'VecSimpleEnv', 'InitStatePool',
            'Box', 'EnvSpec', 'GaussianMLPPolicy', 'LinearFeatureBaseline', 'VectorizedSampler', 'BaseSampler',
-           'DevicePaths', 'ConjugateGradientOptimizer', 'BatchPolopt', 'NPO', 'TRPO', 'VPG', 'FirstOrderOptimizer', 'early_stop', 'dynamics_training', 'from_params', 'shapes_from_params']
+           'DevicePaths', 'ConjugateGradientOptimizer', 'BatchPolopt', 'NPO', 'TRPO', 'VPG', 'FirstOrderOptimizer', 'LBFGS', 'early_stop', 'dynamics_training', 'from_params', 'shapes_from_params']

@@ -64,6 +64,16 @@ class VpgParams(C.Structure):
     _fields_ = [('lr', C.c_double), ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double)]
 
 
+class LbfgsOpts(C.Structure):
+    _fields_ = [('m', C.c_int32), ('maxls', C.c_int32), ('maxiter', C.c_int32), ('maxfun', C.c_int32), ('ftol', C.c_double),
+                ('gtol', C.c_double), ('lookahead', C.c_int32), ('round_f32', C.c_int32)]
+
+
+class LbfgsResult(C.Structure):
+    _fields_ = [('fun', C.c_double), ('nit', C.c_int32), ('nfev', C.c_int32), ('status', C.c_int32), ('task', C.c_int32),
+                ('task_code', C.c_int32), ('pad_', C.c_int32)]
+
+
 # every symbol include/metrpo.h declares: name -> (restype, argtypes)
 _P, _I, _L, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 SYMBOLS = {
@@ -122,6 +132,10 @@ SYMBOLS = {
     'metrpo_rollout_note': (C.c_char_p, [_P]),
     'metrpo_policy_adam_reset': (_I, [_P, _P]),
     'metrpo_policy_adam_step': (_I, [_P, _P, _D, _D, _D, _D, _D, _P]),
+    'metrpo_lbfgs_begin': (_I, [_P, _I, _P, C.POINTER(LbfgsOpts), _P, _P]),
+    'metrpo_lbfgs_iterate': (_I, [_P, _P, _P, _P, _P, _P]),
+    'metrpo_lbfgs_get_result': (_I, [_P, C.POINTER(LbfgsResult), _P]),
+    'metrpo_lbfgs_policy': (_I, [_P, _P, _I, _I, _D, C.POINTER(LbfgsOpts), C.POINTER(LbfgsResult), _P]),
     'metrpo_get_dyn_adam': (_I, [_P, _P, _P, C.POINTER(_L), _P]),
     'metrpo_set_dyn_adam': (_I, [_P, _P, _P, _L, _P]),
     'metrpo_get_policy_adam': (_I, [_P, _P, _P, C.POINTER(_L), _P]),

@@ -250,6 +250,7 @@ extern "C" int32_t metrpo_destroy(metrpo_ctx* c) {
     ws_sweep(c);
     if (c->h_pinned) (void)hipHostFree(c->h_pinned);
     if (c->h_upd) (void)hipHostFree(c->h_upd);
+    if (c->h_lb) (void)hipHostFree(c->h_lb);
     delete c;                                                 // frees the context's device buffers (DevBuf)
     return METRPO_OK;
 }
@@ -511,6 +512,46 @@ extern "C" int32_t metrpo_vpg_update(metrpo_ctx* c, const metrpo_batch* b, const
     NEED_POL(c);
     if (c->upd_pending) return set_err(c, METRPO_ESTATE, "vpg_update: a TRPO update is still open (metrpo_trpo_update_end first)");
     return run_vpg_update(c, b, pr, d_loss, (hipStream_t)stream);
+}
+// model_based_rl.py:391-398 (ScipyOptimizerInterface, method='L-BFGS-B') and :1197-1202 (the 'l-bfgs' branch), lbfgs.hip
+static int lbfgs_opts_check(metrpo_ctx* c, const metrpo_lbfgs_opts* o, const char* who) {
+    if (!o) return set_err(c, METRPO_ENULL, std::string(who) + ": opts NULL");
+    if (o->m <= 0 || o->maxls <= 0) return set_err(c, METRPO_EINVAL, std::string(who) + ": m and maxls must be positive");
+    if (!(o->ftol >= 0.0) || !(o->gtol >= 0.0)) return set_err(c, METRPO_EINVAL, std::string(who) + ": ftol and gtol must be >= 0");
+    return METRPO_OK;
+}
+extern "C" int32_t metrpo_lbfgs_begin(metrpo_ctx* c, int32_t n, const double* x0, const metrpo_lbfgs_opts* o, double* x_eval, void* stream) {
+    if (!c) return METRPO_ENULL;
+    if (!x0 || !x_eval) return set_err(c, METRPO_ENULL, "lbfgs_begin: NULL pointer");
+    if (n <= 0) return set_err(c, METRPO_EINVAL, "lbfgs_begin: n must be positive");
+    int rc;
+    if ((rc = lbfgs_opts_check(c, o, "lbfgs_begin"))) return rc;
+    return lbfgs_begin(c, n, x0, nullptr, o, x_eval, (hipStream_t)stream);
+}
+extern "C" int32_t metrpo_lbfgs_iterate(metrpo_ctx* c, const double* f, const double* g, double* x_eval, int32_t* task, void* stream) {
+    if (!c) return METRPO_ENULL;
+    if (!f || !g || !x_eval || !task) return set_err(c, METRPO_ENULL, "lbfgs_iterate: NULL pointer");
+    if (!c->lb_open) return set_err(c, METRPO_ESTATE, "lbfgs_iterate: no minimisation open (metrpo_lbfgs_begin first)");
+    return lbfgs_iterate(c, f, g, x_eval, task, (hipStream_t)stream);
+}
+extern "C" int32_t metrpo_lbfgs_get_result(metrpo_ctx* c, metrpo_lbfgs_result* out, void* stream) {
+    if (!c) return METRPO_ENULL;
+    if (!out) return set_err(c, METRPO_ENULL, "lbfgs_get_result: out NULL");
+    if (!c->lb_open) return set_err(c, METRPO_ESTATE, "lbfgs_get_result: no minimisation open (metrpo_lbfgs_begin first)");
+    return lbfgs_get_result(c, out, (hipStream_t)stream);
+}
+extern "C" int32_t metrpo_lbfgs_policy(metrpo_ctx* c, const float* init, int32_t B, int32_t T, double gamma, const metrpo_lbfgs_opts* o,
+                                       metrpo_lbfgs_result* out, void* stream) {
+    TraceRange trace_("metrpo:lbfgs_policy");
+    if (!c) return METRPO_ENULL;
+    if (!init || !out) return set_err(c, METRPO_ENULL, "lbfgs_policy: NULL pointer");
+    int rc;
+    if ((rc = lbfgs_opts_check(c, o, "lbfgs_policy"))) return rc;
+    if (o->lookahead < 1 || o->lookahead > 16) return set_err(c, METRPO_EINVAL, "lbfgs_policy: lookahead must be in 1..16");
+    NEED_DYN(c); NEED_POL(c);
+    if (B <= 0 || T <= 0) return set_err(c, METRPO_EINVAL, "lbfgs_policy: B and T must be positive");
+    if (c->upd_pending) return set_err(c, METRPO_ESTATE, "lbfgs_policy: an update begun with metrpo_trpo_update_begin is still open (metrpo_trpo_update_end first)");
+    return run_lbfgs_policy(c, init, B, T, gamma, o, out, (hipStream_t)stream);
 }
 extern "C" int32_t metrpo_fvp(metrpo_ctx* c, const metrpo_batch* b, const double* v, double* hv, void* stream) {
     if (!c) return METRPO_ENULL;

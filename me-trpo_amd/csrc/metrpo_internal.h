@@ -127,6 +127,9 @@ struct metrpo_ctx {
     // stamp); _end polls the stamp (no copy engine, no event, no blocking wait to wake up from).  Publishing from a side stream behind a device-scope
     // event was measured too: the second queue costs the update 35 us, more than the 15 us gap in front of the next rollout it removes.
     double* h_upd = nullptr; unsigned long long upd_stamp = 0;
+    // lbfgs.hip: the L-BFGS state (float64 vectors, S / Y ring, scalars) of the open minimisation, its shape, and the pinned slots its step kernels
+    // publish their task word into (one per evaluation in flight, stamped)
+    DevBuf<double> d_lb; int lb_n = 0, lb_m = 0, lb_open = 0; double* h_lb = nullptr; unsigned long long lb_stamp = 0;
     int upd_pending = 0, upd_spec = 0, upd_changed_in_end = 0; metrpo_batch upd_batch = {}; metrpo_trpo_params upd_params = {}; metrpo_trpo_diag upd_diag = {};
     hipStream_t side_stream[METRPO_MAX_PAR_ROUNDS - 1] = {}; hipEvent_t ev_fork = nullptr, ev_join[METRPO_MAX_PAR_ROUNDS - 1] = {}; int side_ready = 0;   // rollout_gemm.hip: independent rounds of a small-batch rollout run concurrently
     double* h_pinned = nullptr;    // pinned host scratch for the per-trial read-back
@@ -309,6 +312,11 @@ int launch_loss_grad(metrpo_ctx*, const metrpo_batch*, double*, hipStream_t, con
 #define UPD_VPG 4
 int launch_vpg_loss_grad(metrpo_ctx*, const metrpo_batch*, double* out, hipStream_t);
 int run_vpg_update(metrpo_ctx*, const metrpo_batch*, const metrpo_vpg_params*, double* d_loss, hipStream_t);
+// 'l-bfgs' policy update (lbfgs.hip): the reverse-communication L-BFGS-B core and the BPTT-driven minimisation
+int lbfgs_begin(metrpo_ctx*, int n, const double* x0, const float* x0_f32, const metrpo_lbfgs_opts*, double* x_eval, hipStream_t);
+int lbfgs_iterate(metrpo_ctx*, const double* f, const double* g, double* x_eval, int32_t* task, hipStream_t);
+int lbfgs_get_result(metrpo_ctx*, metrpo_lbfgs_result*, hipStream_t);
+int run_lbfgs_policy(metrpo_ctx*, const float* init, int B, int T, double gamma, const metrpo_lbfgs_opts*, metrpo_lbfgs_result*, hipStream_t);
 int comm_allreduce_f64(metrpo_ctx*, double* buf, long long count, hipStream_t);
 // descriptor of the NEXT one-shot exchange (advances the sequence number); world = 0 when no peer-mapped transport is attached
 XchgK xchg_next(metrpo_ctx*);

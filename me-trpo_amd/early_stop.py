@@ -65,11 +65,18 @@ def optimize_policy(algo, validation_init, T, gamma, mode='estimated', whole=Tru
                     num_iters_threshold=25, max_iters=400, stop_fn=None, reset_log_std=True, real_cost_fn=None,
                     logger=None, init_pool=None):
     """TRPO branch of model_based_rl.py:optimize_policy (a VPG object runs the same branch: optimize_policy_vpg); a BPTT object as `algo` runs its
-    'bptt' / 'bptt-stochastic' branch instead
+    'bptt' / 'bptt-stochastic' branch instead, and an LBFGS object the 'l-bfgs' branch: that loop with log_every = 1 and max_iters = 1
     (optimize_policy_bptt; `init_pool` is then its source of reset states).  `real_cost_fn()` stands in for
     evaluate_fixed_init_trajectories on the real simulator (out of scope; None -> 0.0)."""
     from .bptt import BPTT
     from .algos import VPG
+    from .lbfgs import LBFGS
+    if isinstance(algo, LBFGS):
+        # run_model_based_rl.py:114-117 (l_bfgs_exception, applied on every launch path): log_every = 1, max_iters = 1 -- one whole
+        # minimisation, one validation round, one keep-or-restore decision of the 'bptt' branch's loop (which carries theta only)
+        return optimize_policy_bptt(algo, validation_init, T, gamma, init_pool, mode=mode, whole=whole, log_every=1,
+                                    num_iters_threshold=num_iters_threshold, max_iters=1, stop_fn=stop_fn, real_cost_fn=real_cost_fn,
+                                    logger=logger)
     if isinstance(algo, VPG):
         return optimize_policy_vpg(algo, validation_init, T, gamma, mode=mode, whole=whole, log_every=log_every, num_iters_threshold=num_iters_threshold,
                                    max_iters=max_iters, stop_fn=stop_fn, reset_log_std=reset_log_std, real_cost_fn=real_cost_fn, logger=logger)

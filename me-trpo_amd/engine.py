@@ -661,6 +661,50 @@ class Engine(object):
         self._keep_bptt = (x0, eps)
         return (costs, grad, nsat) if n_saturates else (costs, grad)
 
+    # ------------------------------------------------------------------ 'l-bfgs' policy update (csrc/lbfgs.hip)
+    @staticmethod
+    def lbfgs_opts(m=10, maxls=20, maxiter=15000, maxfun=15000, ftol=2.220446049250313e-09, gtol=1e-5, lookahead=2, round_f32=True):
+        """metrpo_lbfgs_opts; the defaults are scipy's L-BFGS-B defaults (minimize(method='L-BFGS-B') with no options)."""
+        o = _lib.LbfgsOpts()
+        o.m, o.maxls, o.maxiter, o.maxfun = int(m), int(maxls), int(maxiter), int(maxfun)
+        o.ftol, o.gtol, o.lookahead, o.round_f32 = float(ftol), float(gtol), int(lookahead), int(bool(round_f32))
+        return o
+
+    def lbfgs_begin(self, x0, opts=None):
+        """Open a reverse-communication L-BFGS-B minimisation at x0 ([n] float64): -> the first point to evaluate ([n] float64 device tensor)."""
+        x0 = torch.as_tensor(x0, device=self.device).to(torch.float64).contiguous()
+        self._lb_x = torch.empty_like(x0)
+        self._lb_task = torch.empty(2, dtype=torch.int32, device=self.device)
+        o = opts if opts is not None else self.lbfgs_opts()
+        self._chk(lib.metrpo_lbfgs_begin(self._ctx, x0.numel(), _ptr(x0), C.byref(o), _ptr(self._lb_x), self._stream()))
+        self._lb_keep = x0
+        return self._lb_x
+
+    def lbfgs_iterate(self, f, g):
+        """One step on f (1-element float64 device tensor) and g ([n] float64) at the point asked for last: -> (x_next [n], task [2] int32),
+        both device tensors (stream-ordered, no synchronisation); task is scipy's (task[0], task[1]), (3, 0) = evaluate x_next."""
+        f = torch.as_tensor(f, device=self.device).to(torch.float64).reshape(1).contiguous()
+        g = torch.as_tensor(g, device=self.device).to(torch.float64).contiguous()
+        self._chk(lib.metrpo_lbfgs_iterate(self._ctx, _ptr(f), _ptr(g), _ptr(self._lb_x), _ptr(self._lb_task), self._stream()))
+        self._lb_keep = (f, g)
+        return self._lb_x, self._lb_task
+
+    def lbfgs_result(self):
+        """The open minimisation's state (metrpo_lbfgs_get_result; synchronises): dict(fun, nit, nfev, status, task)."""
+        r = _lib.LbfgsResult()
+        self._chk(lib.metrpo_lbfgs_get_result(self._ctx, C.byref(r), self._stream()))
+        return dict(fun=r.fun, nit=r.nit, nfev=r.nfev, status=r.status, task=(r.task, r.task_code))
+
+    def lbfgs_policy(self, init_states, T, gamma=1.0, opts=None):
+        """The 'l-bfgs' branch's minimize on the BPTT cost of init_states (metrpo_lbfgs_policy): the policy ends at float32 of the last
+        accepted iterate.  Synchronises.  -> dict(fun, nit, nfev, status, task=(task[0], task[1]))."""
+        self._close_open_update()
+        x0 = _f32(init_states, self.device)
+        o = opts if opts is not None else self.lbfgs_opts()
+        r = _lib.LbfgsResult()
+        self._chk(lib.metrpo_lbfgs_policy(self._ctx, _ptr(x0), x0.shape[0], int(T), float(gamma), C.byref(o), C.byref(r), self._stream()))
+        return dict(fun=r.fun, nit=r.nit, nfev=r.nfev, status=r.status, task=(r.task, r.task_code))
+
     def policy_adam_reset(self):
         self._chk(lib.metrpo_policy_adam_reset(self._ctx, self._stream()))
 

@@ -113,7 +113,7 @@ def from_params(path_or_dict, device=0, init_states=None, comm=None, seed=0, n_e
     sh = shapes_from_params(p)
     if sh['algo'] not in ('trpo', 'vpg', 'bptt', 'bptt-stochastic'):
         raise ValueError("params 'algo' = %r: this path builds 'trpo', 'vpg' (and the 'bptt' / 'bptt-stochastic' updates of section 8f); svg / l-bfgs "
-                         "are out of scope" % sh['algo'])
+                         "are not built from a params file (the 'l-bfgs' update runs as metrpo_amd.LBFGS)" % sh['algo'])
     blk = sh['vpg'] if sh['algo'] == 'vpg' else sh['trpo']     # init_std / reset of the rllab algorithm that runs (training.py:350-352, 368-370)
     eng = Engine(sh['env'], sh['K'], sh['dyn_hidden'], sh['pol_hidden'], n_drop=sh['n_drop'], dyn_act=sh['dyn_act'], device=device)
     policy = GaussianMLPPolicy(eng, init_std=blk['init_std'], seed=seed)
