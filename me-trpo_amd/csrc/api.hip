@@ -425,7 +425,7 @@ extern "C" int32_t metrpo_set_rollout_variant(metrpo_ctx* c, int32_t v) {
 // which policy-update kernels a batch of N samples would run on: 1 fused MFMA (policy_mfma.hip), 2 GEMM path (policy_gemm.hip), 0 generic
 extern "C" int32_t metrpo_update_path(const metrpo_ctx* c, int64_t N) {
     if (!c) return METRPO_ENULL;
-    return policy_gemm_applicable(c, N) ? 2 : ((c->pol_mfma >= 0 || f3_active(c)) ? 1 : 0);
+    return policy_gemm_applicable(c, N, false) ? 2 : ((c->pol_mfma >= 0 || f3_active(c, false)) ? 1 : 0);
 }
 // test hook: 0 forces the generic (VALU) update kernels, 1 restores the MFMA ones when available
 extern "C" int32_t metrpo_set_update_path(metrpo_ctx* c, int32_t use_mfma) {
@@ -435,7 +435,7 @@ extern "C" int32_t metrpo_set_update_path(metrpo_ctx* c, int32_t use_mfma) {
     c->pol_mfma = (use_mfma == 1) ? policy_mfma_select(c->pd) : -1;
     c->pol_f3 = (use_mfma == 1) ? policy_f3_select(c->pd) : 0;
     c->pg_fwd_rows = -1; c->f3_rows = -1;
-    return (c->pol_mfma >= 0 || f3_active(c)) ? 1 : (c->pol_path == 2 ? 2 : 0);
+    return (c->pol_mfma >= 0 || f3_active(c, false)) ? 1 : (c->pol_path == 2 ? 2 : 0);
 }
 
 extern "C" int32_t metrpo_validation_cost(metrpo_ctx* c, const float* s0, int32_t Bv, int32_t T, double gamma,
@@ -731,9 +731,7 @@ int run_trpo_update(metrpo_ctx* c, const metrpo_batch* b, const metrpo_trpo_para
 // Can this update's line search be decided on the device?  Needs the single-launch-sequence update (no host callback / stand-alone
 // all-reduce between a reduction and its consumer) on the fused MFMA or generic kernels; the GEMM path has its own reductions.
 static bool device_line_search_ok(const metrpo_ctx* c, const metrpo_batch* b, const metrpo_trpo_params* pr) {
-    const bool xg = (pr->allreduce == nullptr && c->xg_world > 1);
-    const bool fused = (pr->allreduce == nullptr && ((c->nccl_comm == nullptr && !xg) || (xg && !policy_gemm_applicable(c, b->N) && c->pd.P + 1 <= c->xg_cap)));
-    return fused && !policy_gemm_applicable(c, b->N);
+    return update_fusion(c, b->N, pr->allreduce != nullptr).carries_next_step();
 }
 static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metrpo_trpo_params* pr, metrpo_trpo_diag* diag,
                                 double* g_out, double* dir_out, hipStream_t st, int phase, int spec) {
@@ -743,20 +741,19 @@ static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metr
     // sum over ranks: the caller's callback if given, else the RCCL communicator attached to the ctx (comm.hip), else single rank
 #define AR(buf, n) do { if (pr->allreduce) { if ((rc = pr->allreduce(pr->allreduce_user, (buf), (n), (void*)st)) != 0) \
                                                  return set_err(c, METRPO_EINVAL, "allreduce callback failed"); } \
-                        else if (xg_fused) { /* summed in the tail of the reduction that produced buf */ } \
+                        else if (fusion.exchange_in_tail) { /* summed in the tail of the reduction that produced buf */ } \
                         else if (c->nccl_comm || xg) { if ((rc = comm_allreduce_f64(c, (buf), (n), st)) != 0) return rc; } } while (0)
     // krylov.cg with every vector step fused into the tail of the kernel that produced its input (no all-reduce in between) or
     // as stand-alone one-block kernels after the caller's all-reduce.  The step scale needs d.(H d): by default it is taken
     // from the CG recurrence (cg_device.h: A x = g - r), explicit_final_hvp = 1 spends the extra FVP rllab spends.
     // Sharded over a peer-mapped transport (comm.hip, one-shot exchange): the reductions of the update kernels add the ranks' shares in
-    // their own tail (xg_fuse), so the update keeps its single-rank launch sequence -- CG vector steps included.  The GEMM path
+    // their own tail (SolveScope::exchange_in_tail), so the update keeps its single-rank launch sequence -- CG vector steps included.  The GEMM path
     // (policy_gemm.hip) has its own reduction kernels: there the exchange is the stand-alone one-shot kernel between them and the CG step.
     const bool xg = (pr->allreduce == nullptr && c->xg_world > 1);
-    // in-tail exchange: per-element packets into ONE slot per source (k_finalize does not split); longer vectors take the stand-alone, chunked exchange
-    const bool xg_fused = xg && !policy_gemm_applicable(c, b->N) && P + 1 <= c->xg_cap;
-    const bool fused = (pr->allreduce == nullptr && ((c->nccl_comm == nullptr && !xg) || xg_fused));
-    c->xg_fuse = xg_fused ? 1 : 0;
-    struct FuseOff { metrpo_ctx* c; ~FuseOff() { c->xg_fuse = 0; } } fuse_off{c};
+    const UpdFusion fusion = update_fusion(c, b->N, pr->allreduce != nullptr);
+    const bool fused = fusion.fused;
+    SolveScope search;                   // what the line search's evaluations may rely on; the solve below adds its caches
+    search.exchange_in_tail = fusion.exchange_in_tail;
     const int implicit_hd = pr->explicit_final_hvp ? 0 : 1;
     CgTail tl; tl.pub_dst = nullptr; tl.pub_stamp = 0; tl.P = P; tl.last = 0; tl.implicit_hd = implicit_hd; tl.reg = pr->reg_coeff; tl.tol = pr->residual_tol; tl.max_kl = pr->max_kl;
     tl.x = v.x; tl.r = v.r; tl.p = v.p; tl.z = v.z; tl.step = v.step; tl.scal = v.scal; tl.gout = v.gout; tl.pf = c->d_vf.p; tl.ticket = c->d_ticket.p;
@@ -768,15 +765,15 @@ static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metr
     bool try0_built = false;
     if (phase != 2) {
     tl.op = 3;
-    c->hcache_on = 1;                    // the gradient kernel publishes tanh activations, the CG products of this solve reuse them
+    SolveScope solve = search;
+    solve.cache_activations = true;      // the gradient kernel publishes tanh activations, the CG products of this solve reuse them
     // ... and, when every CG vector comes out of a fused tail, its weight-fragment image; the tails add the tangent entries (policy_mfma.hip)
-    c->img_live = (fused && c->pol_mfma >= 0 && !policy_gemm_applicable(c, b->N)) ? 1 : 0;
-    struct CacheOff { metrpo_ctx* c; ~CacheOff() { c->hcache_on = 0; c->img_live = 0; } } cache_off{c};
-    if (c->img_live) {
+    solve.publish_image = fused && c->pol_mfma >= 0 && fusion.finalize_reduces;
+    if (solve.publish_image) {
         if ((rc = policy_mfma_image_buffers(c))) return rc;
         tl.vpos = c->d_pol_vpos.p; tl.imgval = c->d_pol_imgval.p;
     }
-    if ((rc = launch_loss_grad(c, b, v.gout, st, fused ? &tl : nullptr))) return rc;
+    if ((rc = launch_loss_grad(c, b, v.gout, st, fused ? &tl : nullptr, solve))) return rc;
     if (!fused) {
         AR(v.gout, 1 + P);
         hipLaunchKernelGGL(k_cg_init, dim3(1), dim3(1024), 0, st, P, v.gout, v.x, v.r, v.p, c->d_vf.p, v.scal);   // same block shape as the fused tail: identical summation order
@@ -790,17 +787,16 @@ static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metr
     for (int i = 0; i < pr->cg_iters; ++i) {
         tl.op = 1; tl.last = (i == pr->cg_iters - 1) ? 1 : 0;
         if (fold_try && tl.last && implicit_hd) arm_try0();
-        if (fused) { if ((rc = launch_fvp_tail(c, b, c->d_vf.p, v.p, v.z, &tl, st))) return rc; continue; }
-        if ((rc = launch_fvp_f32(c, b, c->d_vf.p, v.p, v.z, st))) return rc;
+        if ((rc = launch_fvp_tail(c, b, c->d_vf.p, v.p, v.z, fused ? &tl : nullptr, st, solve))) return rc;
+        if (fused) continue;
         AR(v.z, P);
         hipLaunchKernelGGL(k_cg_step, dim3(1), dim3(1024), 0, st, tl, pr->cg_iters);
     }
     if (!implicit_hd && pr->cg_iters > 0) {                      // rllab's literal route: one more f_Hx on the descent direction
         tl.op = 2; tl.last = 0;
         if (fused && fold_try) arm_try0();
-        if (fused) { if ((rc = launch_fvp_tail(c, b, c->d_vf.p, v.x, v.z, &tl, st))) return rc; }
-        else {
-            if ((rc = launch_fvp_f32(c, b, c->d_vf.p, v.x, v.z, st))) return rc;
+        if ((rc = launch_fvp_tail(c, b, c->d_vf.p, v.x, v.z, fused ? &tl : nullptr, st, solve))) return rc;
+        if (!fused) {
             AR(v.z, P);
             hipLaunchKernelGGL(k_cg_finish, dim3(1), dim3(1024), 0, st, P, pr->reg_coeff, pr->max_kl, v.x, v.z, v.step, v.scal);
         }
@@ -824,7 +820,7 @@ static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metr
             if (n + 1 < nspec) { dt.nx_try = c->d_theta_try.p; dt.nx_prev = c->d_theta.p; dt.nx_ratio = std::pow(pr->backtrack_ratio, (double)(n + 1)); dt.nx_ls = nullptr; }
             dt.op = 4; dt.ls = v.ls; dt.lk = v.lk; dt.th = c->d_theta.p; dt.th_try = c->d_theta_try.p; dt.trial = n; dt.accept_violation = pr->accept_violation;
             if (n == nspec - 1) { dt.pub_dst = c->h_upd; dt.pub_stamp = c->upd_stamp; }
-            if ((rc = launch_loss_kl(c, b, c->d_theta_try.p, v.lk, st, &dt))) return rc;
+            if ((rc = launch_loss_kl(c, b, c->d_theta_try.p, v.lk, st, &dt, search))) return rc;
         }
         if (c->mfma_cfg >= 0 && (rc = mfma_prepare_policy(c, st))) return rc;      // of whatever theta the trials left in place
         if (nspec == 0) hipLaunchKernelGGL(k_ls_publish, dim3(1), dim3(64), 0, st, (const double*)v.scal, c->h_upd, c->upd_stamp);
@@ -861,7 +857,7 @@ static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metr
         n_iter = n;
         const double ratio = std::pow(pr->backtrack_ratio, (double)n);
         hipLaunchKernelGGL(k_try_theta, dim3((P + 255) / 256), dim3(256), 0, st, P, ratio, c->d_theta.p, v.step, c->d_theta_try.p, (const double*)nullptr, (double*)nullptr);
-        if ((rc = launch_loss_kl(c, b, c->d_theta_try.p, v.lk, st))) return rc;
+        if ((rc = launch_loss_kl(c, b, c->d_theta_try.p, v.lk, st, nullptr, search))) return rc;
         AR(v.lk, 2);
         HIP_TRY(c, hipMemcpyAsync(c->h_pinned, v.scal, sizeof(double) * 10, hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipStreamSynchronize(st));

@@ -177,7 +177,7 @@ extern "C" int32_t metrpo_comm_ipc_attach(metrpo_ctx* c, const void* blobs, int3
         }
         c->xg_peer[q] = p;
     }
-    c->xg_world = world; c->xg_rank = rank; c->xg_seq = 0; c->xg_fuse = 0;
+    c->xg_world = world; c->xg_rank = rank; c->xg_seq = 0;
     long long ms = 20000;
     if (const char* t = ctx_opt(c, OPT_XCHG_TIMEOUT_MS)) { const long long v = atoll(t); if (v > 0) ms = v; }
     c->xg_timeout = (unsigned long long)ms * 100000ull;       // wall_clock64: 100 MHz
@@ -192,7 +192,7 @@ extern "C" int32_t metrpo_comm_ipc_detach(metrpo_ctx* c) {
         for (int q = 0; q < c->xg_world; ++q) if (q != c->xg_rank && c->xg_peer[q]) (void)hipIpcCloseMemHandle(c->xg_peer[q]);
     }
     for (int q = 0; q < XCHG_MAX_WORLD; ++q) c->xg_peer[q] = nullptr;
-    c->xg_world = 0; c->xg_rank = 0; c->xg_fuse = 0;
+    c->xg_world = 0; c->xg_rank = 0;
     // The time-out cell of the exchanges is sticky by design; it must not outlive the transport that raised it: 'auto' mode detaches after a
     // timed-out test exchange and goes on over RCCL or the caller's callback, and every later update of this context would report that old time-out.
     if (c->d_cg.p) {

@@ -70,13 +70,11 @@ struct metrpo_ctx {
     DevBuf<float> d_pol_img; // (int32 payload) gather map of the policy weight-fragment image, see policy_mfma.hip
     int pol_img_idx = -1;    // table index the map was built for (-1: none)
     // image VALUES of one CG solve (policy_mfma.hip): [weight entries of theta, written by the gradient kernel's block 0 | tangent entries of the
-    // current CG vector, written by the fused CG tails through d_pol_vpos (theta index -> image position, -1: none)].  img_live is raised by
-    // run_trpo_update while both writers are on the launch sequence; the cached-activation FVP then copies the image instead of gathering it.
-    DevBuf<float> d_pol_imgval; DevBuf<int> d_pol_vpos; int img_live = 0;
+    // current CG vector, written by the fused CG tails through d_pol_vpos (theta index -> image position, -1: none)].  SolveScope::publish_image is
+    // raised by run_trpo_update while both writers are on the launch sequence; the cached-activation FVP then copies the image instead of gathering it.
+    DevBuf<float> d_pol_imgval; DevBuf<int> d_pol_vpos;
     // --- BPTT (bptt.hip) ---
     DevBuf<void> d_bptt;                      // XS | WT | GM | gout | costs
-    const float* vjp_gm = nullptr;            // set around the VJP launch of the gradient kernels
-    const double* ls_skip = nullptr;          // set around a speculative line-search evaluation (PolK::skip of the fused MFMA kernels)
     DevBuf<void> d_pol_adam; int pol_adam_t = 0;   // Adam moments of the policy parameters + segment table
     int det_cfg = -1;                         // bptt_mfma.hip table index (-1: generic sweeps / generic validation kernel)
     DevBuf<double> d_detpart;                 // per-tile cost partials of the MFMA forward sweep
@@ -100,13 +98,12 @@ struct metrpo_ctx {
     DevBuf<double> d_gae_part;     // k_gae: arrival ticket + one (sum adv, sum adv^2, count) triple per workgroup, added in workgroup order
     DevBuf<double> d_gram_part;    // per-block Gram partials (process.hip)
     DevBuf<unsigned int> d_ticket; // arrival counter of k_finalize's fused CG tail
-    DevBuf<float> d_hcache; int hcache_on = 0;    // activation cache of one CG solve (policy_mfma.hip MODE_FVPC)
+    DevBuf<float> d_hcache;        // activation cache of one CG solve (policy_mfma.hip OP_FVPC)
     DevBuf<void> d_mig; int mig_epoch = 0;        // rollout_coop.hip: hand-over slots of migrating tiles (flag | ts | model | obs per tile)
     void* nccl_comm = nullptr; int comm_world = 0, comm_rank = 0;   // comm.hip: RCCL communicator attached by metrpo_comm_init (NULL: single rank)
     // comm.hip: one-shot direct all-reduce (xchg_device.h).  xg_region = this rank's receive region (IPC-exported), xg_peer[q] = rank q's
-    // region as mapped here; xg_seq counts the exchanges issued so far (identical on every rank: SPMD); xg_fuse is raised by
-    // run_trpo_update while the reductions of the update kernels carry the exchange in their own tail
-    void* xg_region = nullptr; void* xg_peer[XCHG_MAX_WORLD] = {}; int xg_world = 0, xg_rank = 0, xg_cap = 0, xg_fuse = 0; unsigned int xg_seq = 0; unsigned long long xg_timeout = 0;
+    // region as mapped here; xg_seq counts the exchanges issued so far (identical on every rank: SPMD)
+    void* xg_region = nullptr; void* xg_peer[XCHG_MAX_WORLD] = {}; int xg_world = 0, xg_rank = 0, xg_cap = 0; unsigned int xg_seq = 0; unsigned long long xg_timeout = 0;
     int pol_path = 1;        // 1 auto (fused MFMA kernels where the shape has them, GEMM path for large N otherwise), 0 generic forced, 2 GEMM path forced
     DevBuf<void> d_pg; long long pg_fwd_rows = -1; const float* pg_fwd_obs = nullptr;   // policy_gemm.hip workspace + validity of its cached forward pass
     int pol_f3 = 0;          // 1: fused MFMA update kernels for three-hidden-layer policies (policy_fused3.hip) serve this shape
@@ -180,8 +177,9 @@ template <class T> static inline int ws_grow(metrpo_ctx* c, DevBuf<T>& b, size_t
 static inline const char* ctx_opt(const metrpo_ctx* c, int id) { return c->opt_set[id] ? c->opt_val[id].c_str() : nullptr; }
 // kernels that wait on other workgroups of their own launch may be selected: the caller said the device is its own (metrpo_set_exclusive) AND option NO_RESIDENT is unset
 static inline bool ctx_exclusive(const metrpo_ctx* c) { return c->exclusive != 0 && ctx_opt(c, OPT_NO_RESIDENT) == nullptr; }
-// the three-hidden-layer fused update kernels (policy_fused3.hip) serve this context's next update launch (not the VJP mode of the gradient kernels: GEMM path)
-static inline bool f3_active(const metrpo_ctx* c) { return c->pol_f3 != 0 && c->pol_path == 1 && c->vjp_gm == nullptr && ctx_opt(c, OPT_NO_POL_FUSED3) == nullptr; }
+// the three-hidden-layer fused update kernels (policy_fused3.hip) serve an update launch of this context; vjp: the launch is the VJP mode of the gradient
+// kernels (PolK::gm supplied), which they do not have (GEMM path)
+static inline bool f3_active(const metrpo_ctx* c, bool vjp) { return c->pol_f3 != 0 && c->pol_path == 1 && !vjp && ctx_opt(c, OPT_NO_POL_FUSED3) == nullptr; }
 const char* metrpo_opt_name(int id);
 int metrpo_opt_id(const char* key);       // -1: unknown
 
@@ -232,15 +230,43 @@ struct PolK {
     const float* gm;         // non-NULL: VJP mode of the gradient kernels (bptt.hip): d objective / d mean [N][na] supplied, no loss terms
     const int* img_map;      // policy_mfma.hip: gather map of the LDS weight-fragment image (built once per ctx on the host)
     const double* skip;      // non-NULL: a line-search trial that leaves at once when skip[0] >= 0 (the search already stopped: CgTail::ls)
-    float* imgval;           // policy_mfma.hip: non-NULL while metrpo_ctx::img_live -- gradient kernel: block 0 publishes its image here; MODE_FVPC: the image to copy
-    float* hcache;           // policy_mfma.hip: hidden activations of (theta, batch): written by the gradient kernel, read by MODE_FVPC
+    float* imgval;           // policy_mfma.hip: non-NULL under SolveScope::publish_image -- gradient kernel: block 0 publishes its image here; OP_FVPC: the image to copy
+    float* hcache;           // policy_mfma.hip: hidden activations of (theta, batch): written by the gradient kernel, read by OP_FVPC
+};
+
+// ---- one policy-update launch (policy_update.hip run_update) ------------------------------------------------------------------------------------
+// The operation, shared by the four kernel families (generic, fused MFMA, fused 100-50-25, GEMM path).  The values are template arguments of the
+// kernels (as int: an unscoped enum converts) and the index into policy_mfma.hip's kern[] table.
+enum UpdOp {
+    OP_GRAD = 0,      // surrogate loss + gradient (with PolK::gm: the VJP of bptt.hip)
+    OP_FVP = 1,       // Fisher-vector product
+    OP_LOSSKL = 2,    // loss + KL at a trial theta (line search)
+    OP_FVPC = 3,      // policy_mfma.hip only, chosen by its launcher: OP_FVP on the activations the gradient kernel cached
+    OP_VPG = 4,       // OP_GRAD with the VPG surrogate's head (algos/vpg.py: ratio 1, loss = -mean(logli * adv))
+};
+// What the enclosing solve lets a launch rely on; run_trpo_update / run_vpg_update build one on their stack, every launch outside a solve passes the all-off default.
+struct SolveScope {
+    bool cache_activations = false;   // the gradient launch keeps its forward pass, the Fisher-vector products of the same (theta, batch) reuse it
+    bool publish_image = false;       // policy_mfma.hip: gradient kernel and fused CG tails maintain d_pol_imgval (needs cache_activations)
+    bool exchange_in_tail = false;    // sharded run: k_finalize adds the ranks' shares in its own tail (one-shot exchange, xchg_device.h)
+};
+struct CgTail;
+struct AdamTail;
+struct UpdCall {
+    UpdOp op;
+    PolK k;                  // batch; gm / skip set by the caller, img_map / imgval / hcache by policy_mfma_launch
+    const float* theta;
+    const float* vf;         // OP_FVP: float copy of the tangent vector
+    const double* v64;       // OP_FVP: the tangent vector (log_std rows)
+    double* out;
+    const CgTail* tail;      // step fused into the reduction's tail, or NULL
+    const AdamTail* adam;    // k_finalize only: Adam step on the reduced gradient, or NULL
+    SolveScope scope;
 };
 
 int policy_mfma_select(const ProblemDesc& pd);
 int policy_mfma_image_buffers(metrpo_ctx*);   // gather map, its inverse for the tangent entries and the image-value buffer of ctx->pol_mfma (idempotent)
-struct CgTail;
-int policy_mfma_launch(metrpo_ctx*, int idx, int mode, const metrpo_batch*, const float* theta, const float* v,
-                       float* partials, int nblocks, hipStream_t);
+int policy_mfma_launch(metrpo_ctx*, const UpdCall&, float* partials, int nblocks, hipStream_t);
 
 #define HIP_TRY(c, expr)                                                                      \
     do {                                                                                      \
@@ -306,10 +332,8 @@ int launch_sampler_progress(metrpo_ctx*, const uint8_t*, const int32_t*, int, in
 int launch_baseline_solve(metrpo_ctx*, const double* AtA, const double* Aty, double reg, double* coeffs, hipStream_t);
 int launch_gram(metrpo_ctx*, const float*, const float*, const int32_t*, const uint8_t*, int64_t, double*, double*,
                 hipStream_t);
-int launch_loss_grad(metrpo_ctx*, const metrpo_batch*, double*, hipStream_t, const CgTail* tail = nullptr);
-// 'vpg' policy update (algos/vpg.py): the gradient kernels of every update family in their UPD_VPG instantiation (ratio 1: loss = -mean(logli * adv)).
-// The mode number is shared by run_mode (policy_update.hip), policy_mfma_launch, policy_f3_launch and policy_gemm_run; 3 is policy_mfma.hip's MODE_FVPC.
-#define UPD_VPG 4
+int launch_loss_grad(metrpo_ctx*, const metrpo_batch*, double*, hipStream_t, const CgTail* tail = nullptr, SolveScope = {});
+// 'vpg' policy update (algos/vpg.py): the gradient kernels of every update family in their OP_VPG instantiation
 int launch_vpg_loss_grad(metrpo_ctx*, const metrpo_batch*, double* out, hipStream_t);
 int run_vpg_update(metrpo_ctx*, const metrpo_batch*, const metrpo_vpg_params*, double* d_loss, hipStream_t);
 // 'l-bfgs' policy update (lbfgs.hip): the reverse-communication L-BFGS-B core and the BPTT-driven minimisation
@@ -341,16 +365,32 @@ static inline int rollout_error_seen(metrpo_ctx* c, hipStream_t st) {
                                                   "the trajectories of that launch are invalid, later rollouts of this context use the step-wise path"
                                                 : "rollout: a migrating tile's hand-over timed out (producer workgroup never ran); trajectories are invalid");
 }
-bool policy_gemm_applicable(const metrpo_ctx*, long long N);
+bool policy_gemm_applicable(const metrpo_ctx*, long long N, bool vjp);   // vjp: as f3_active
+// Can the reductions of an update on N samples carry what follows them?  One answer for run_trpo_update, its device-side line search and run_vpg_update:
+// the ranks of a sharded run must agree on it, or they issue different numbers of exchanges.  has_callback: the caller brought its own all-reduce
+// (metrpo_trpo_params::allreduce).  Asked with no VJP open: an update never is one.
+struct UpdFusion {
+    bool fused;              // no stand-alone all-reduce (callback, RCCL, chunked exchange) sits between a reduction and its consumer
+    bool exchange_in_tail;   // sharded over the one-shot transport, and the reductions add the ranks' shares in their own tail (SolveScope)
+    bool finalize_reduces;   // the reduction is k_finalize, not the GEMM path's own kernels: it can carry an accept test or an Adam step
+    bool carries_next_step() const { return fused && finalize_reduces; }
+};
+static inline UpdFusion update_fusion(const metrpo_ctx* c, long long N, bool has_callback) {
+    const bool xg = !has_callback && c->xg_world > 1;
+    UpdFusion f;
+    f.finalize_reduces = !policy_gemm_applicable(c, N, false);
+    // in-tail exchange: per-element packets into ONE slot per source (k_finalize does not split); longer vectors take the stand-alone, chunked exchange
+    f.exchange_in_tail = xg && f.finalize_reduces && c->pd.P + 1 <= c->xg_cap;
+    f.fused = !has_callback && ((c->nccl_comm == nullptr && !xg) || f.exchange_in_tail);
+    return f;
+}
 int policy_f3_select(const ProblemDesc& pd);      // policy_fused3.hip: 1 when the three-hidden-layer kernels cover this policy shape
-int policy_f3_launch(metrpo_ctx*, int mode, const metrpo_batch*, const float* theta, const float* vf, float* partials, int nblocks, hipStream_t);
-int policy_gemm_run(metrpo_ctx*, int mode, const metrpo_batch*, const PolK&, const float* theta, const float* vf, const double* v64, double* out,
-                    const CgTail* tail, hipStream_t);
+int policy_f3_launch(metrpo_ctx*, const UpdCall&, float* partials, int nblocks, hipStream_t);
+int policy_gemm_run(metrpo_ctx*, const UpdCall&, hipStream_t);
 int launch_fvp(metrpo_ctx*, const metrpo_batch*, const double*, double*, hipStream_t);
+// FVP + reduction + (in the reduction kernel's last block) the CG vector step described by `tail` (may be NULL)
 // vf = float copy of v already on the device (skips the conversion launch); v is still needed for the log_std rows
-int launch_fvp_f32(metrpo_ctx*, const metrpo_batch*, const float* vf, const double* v, double* hv, hipStream_t);
-// FVP + reduction + (in the reduction kernel's last block) the CG vector step described by `tail`
-int launch_fvp_tail(metrpo_ctx*, const metrpo_batch*, const float* vf, const double* v, double* hv, const CgTail* tail, hipStream_t);
-int launch_loss_kl(metrpo_ctx*, const metrpo_batch*, const float*, double*, hipStream_t, const CgTail* decide = nullptr);   // decide: op 4 tail (device-side accept test)
+int launch_fvp_tail(metrpo_ctx*, const metrpo_batch*, const float* vf, const double* v, double* hv, const CgTail* tail, hipStream_t, SolveScope = {});
+int launch_loss_kl(metrpo_ctx*, const metrpo_batch*, const float*, double*, hipStream_t, const CgTail* decide = nullptr, SolveScope = {});   // decide: op 4 tail (device-side accept test)
 int run_trpo_update(metrpo_ctx*, const metrpo_batch*, const metrpo_trpo_params*, metrpo_trpo_diag*, double*,
                     double*, hipStream_t, int phase = 0, int spec = 0);

@@ -165,7 +165,9 @@ template <class S> __device__ __forceinline__ void fix_xb(float (&xb)[S::KS0], i
     for (int s = 0; s < S::KS0; ++s) if (4 * s + 3 >= S::D0) { const int f = 4 * s + q; if (f == S::D0) xb[s] = 1.0f; else if (f > S::D0) xb[s] = 0.f; }
 }
 
-enum { F3_GRAD = 0, F3_LOSSKL = 2, F3_CACHE = 3, F3_VPG = UPD_VPG };     // F3_VPG: F3_GRAD with the VPG head (vpg.py:88; policy_mfma.hip MODE_VPG)
+// MODE of k_f3_fwd: OP_GRAD, OP_LOSSKL, OP_VPG of UpdOp (metrpo_internal.h), and the forward pass that only fills the activation cache for a Fisher-vector product
+// whose gradient launch was not kept.  That one is no UpdOp: a file-local constant, whose value 3 is part of the kernel's mangled name.
+constexpr int F3_FILL_CACHE = 3;
 enum { IMG_WHAT_F = 1, IMG_WHAT_V = 2, IMG_WHAT_B = 4 };
 // fragment tables of theta (F: forward, B: back-prop) and of the tangent vector v (V) -> the global image
 template <class S>
@@ -203,11 +205,11 @@ __global__ void __launch_bounds__(256) k_f3_image(F3K k, float* __restrict__ img
 // forward + head
 template <class S, int MODE_, int NW>
 __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
-    constexpr bool VPG = (MODE_ == F3_VPG);
-    constexpr int MODE = VPG ? F3_GRAD : MODE_;
+    constexpr bool VPG = (MODE_ == OP_VPG);
+    constexpr int MODE = VPG ? OP_GRAD : MODE_;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), c = lane & 15, q = lane >> 4;
-    if (MODE == F3_LOSSKL && k.skip != nullptr && k.skip[0] >= 0.0) return;        // speculative line-search trial after the search stopped
+    if (MODE == OP_LOSSKL && k.skip != nullptr && k.skip[0] >= 0.0) return;        // speculative line-search trial after the search stopped
     float* T0 = lds; float* T1 = T0 + S::F0; float* T2 = T1 + S::F1; float* T3 = T2 + S::F2;
     const float* __restrict__ th = k.theta;
     copy_tab<S::LDS_FWD, NW * 64>(lds, k.img + S::IMG_F, tid);
@@ -218,7 +220,7 @@ __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int d = 16 * cb + 4 * q + r;
-            ls[cb][r] = (MODE != F3_CACHE && d < S::D4) ? fmaxf(th[k.ls_off + d], LOG_MIN_STD) : 0.f;
+            ls[cb][r] = (MODE != F3_FILL_CACHE && d < S::D4) ? fmaxf(th[k.ls_off + d], LOG_MIN_STD) : 0.f;
             inv_std[cb][r] = expf(-ls[cb][r]);
         }
     const long long ntiles = (k.N + 15) / 16;
@@ -228,7 +230,7 @@ __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
         fetch_xb<S>(k, tile, c, q, in.xb, in.nrem);
         const long long nl = tile * 16 + ((c < in.nrem) ? c : in.nrem - 1);
         in.vld = (k.valid == nullptr) ? 1 : (int)k.valid[nl];
-        if (MODE != F3_CACHE) {
+        if (MODE != F3_FILL_CACHE) {
 #pragma unroll
             for (int cb = 0; cb < S::CB4; ++cb)
 #pragma unroll
@@ -269,7 +271,7 @@ __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
         zero_acc(h3);
         chain<S::KS2, S::CB3, false>(T2, lane, [&](int kk) { return h2[kk >> 2][kk & 3]; }, h3);
         tanh_acc(h3); set_const_unit<S::D3>(h3, q);
-        if (MODE != F3_LOSSKL) {
+        if (MODE != OP_LOSSKL) {
             f32x4* __restrict__ hw = k.hc + (size_t)tile * S::NHB * 64 + lane;
 #pragma unroll
             for (int cb = 0; cb < S::CB1; ++cb) hw[cb * 64] = h1[cb];
@@ -278,7 +280,7 @@ __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
 #pragma unroll
             for (int cb = 0; cb < S::CB3; ++cb) hw[(S::CB1 + S::CB2 + cb) * 64] = h3[cb];
         }
-        if (MODE == F3_CACHE) continue;
+        if (MODE == F3_FILL_CACHE) continue;
         f32x4 mu[S::CB4];
         zero_acc(mu);
         chain<S::KS3, S::CB4, false>(T3, lane, [&](int kk) { return h3[kk >> 2][kk & 3]; }, mu);
@@ -300,7 +302,7 @@ __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
                     const float z = (a - mu[cb][r]) * inv_std[cb][r], zo = (a - omu) * eo;
                     llr += (ols - ls[cb][r]) + 0.5f * (zo * zo - z * z);
                     zz[cb][r] = z;
-                    if (MODE == F3_LOSSKL) {
+                    if (MODE == OP_LOSSKL) {
                         const float s2 = expf(2.f * ls[cb][r]), os2 = expf(2.f * ols), dm = omu - mu[cb][r];
                         kl += (dm * dm + os2 - s2) / (2.f * s2 + KL_EPS) + ls[cb][r] - ols;
                     }
@@ -309,7 +311,7 @@ __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
         llr = xsum_q3(llr);                                 // the four q-lanes of sample c hold its action dims between them
         const float la = ok ? (VPG ? in.adv : expf(llr) * in.adv) : 0.f;     // lr * adv (VPG: ratio 1)
         if (q == 0) acc0 -= (VPG ? (llr - S::D4 * HALF_LOG_2PI) * la : la) * k.inv_n;   // surr_loss = -mean(lr * adv) | -mean(logli * adv), once per sample
-        if (MODE == F3_LOSSKL) { acc1 += kl * k.inv_n; continue; }
+        if (MODE == OP_LOSSKL) { acc1 += kl * k.inv_n; continue; }
         const float w = -la * k.inv_n;
         f32x4* __restrict__ uw = k.u + (size_t)tile * S::CB4 * 64 + lane;
 #pragma unroll
@@ -323,7 +325,7 @@ __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
             uw[cb * 64] = um;
         }
     }
-    if (MODE == F3_CACHE) return;
+    if (MODE == F3_FILL_CACHE) return;
     // ---- per-block sums -> columns [ls_off, ls_off + D4) and P, P+1, P+2 of this block's partial row (fixed order over the waves)
     __syncthreads();
     float* red = lds;                                       // [NW][3 + P4]
@@ -343,7 +345,7 @@ __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
         for (int w = 0; w < NW; ++w) a += red[w * RW + tid];
         float* row = k.partials + (size_t)blockIdx.x * k.row_stride;
         if (tid < 3) row[k.P + tid] = a;
-        else if (MODE == F3_GRAD) row[k.ls_off + tid - 3] = (th[k.ls_off + tid - 3] > LOG_MIN_STD) ? a : 0.f;
+        else if (MODE == OP_GRAD) row[k.ls_off + tid - 3] = (th[k.ls_off + tid - 3] > LOG_MIN_STD) ? a : 0.f;
     }
 }
 
@@ -663,16 +665,16 @@ template <class K> static int f3_attr(metrpo_ctx* c, K kern, size_t sh) {
     return METRPO_OK;
 }
 
-// mode 0 gradient, 1 Fisher-vector product, 2 loss + KL, UPD_VPG the VPG gradient; per-block rows of P + 3 floats land in `partials` (the layout k_finalize reads)
-int policy_f3_launch(metrpo_ctx* c, int mode, const metrpo_batch* b, const float* theta, const float* vf, float* partials, int nblocks,
-                     hipStream_t st) {
+// u.op on the batch u.k; per-block rows of P + 3 floats land in `partials` (the layout k_finalize reads)
+int policy_f3_launch(metrpo_ctx* c, const UpdCall& u, float* partials, int nblocks, hipStream_t st) {
     typedef ShHumanoid S;
-    const long long N = b->N;
+    const PolK& b = u.k;
+    const long long N = b.N;
     int rc = f3_ensure(c, N); if (rc) return rc;
     const size_t tiles = (size_t)((N + 15) / 16);
     F3K k = {};
-    k.obs = b->d_obs; k.act = b->d_act; k.adv = b->d_adv; k.old_mean = b->d_old_mean; k.old_ls = b->d_old_log_std; k.ls_stride = b->old_log_std_stride;
-    k.valid = b->d_valid; k.N = N; k.inv_n = (float)b->inv_n_global; k.skip = c->ls_skip; k.theta = theta; k.v = vf;
+    k.obs = b.obs; k.act = b.act; k.adv = b.adv; k.old_mean = b.old_mean; k.old_ls = b.old_ls; k.ls_stride = b.ls_stride;
+    k.valid = b.valid; k.N = N; k.inv_n = b.inv_n; k.skip = b.skip; k.theta = u.theta; k.v = u.vf;
     k.hc = (f32x4*)c->d_f3.p; k.u = k.hc + tiles * S::NHB * 64;
     float* img = (float*)(k.u + tiles * S::CB4 * 64);
     k.img = img;
@@ -681,31 +683,31 @@ int policy_f3_launch(metrpo_ctx* c, int mode, const metrpo_batch* b, const float
     for (int l = 0; l < 4; ++l) { k.w_off[l] = c->pd.pol.w_off[l]; k.b_off[l] = c->pd.pol.b_off[l]; }
     const size_t sh_fwd = sizeof(float) * S::LDS_FWD, sh_jvp = sizeof(float) * S::LDS_JVP, sh_bwd = sizeof(float) * S::LDS_BWD;
     const dim3 g(nblocks);
-    if (mode == 2) {
+    if (u.op == OP_LOSSKL) {
         build_image(IMG_WHAT_F); c->f3_img_ok = 0;          // (the trial theta's tables: the image no longer belongs to the cached activations)
-        if ((rc = f3_attr(c, k_f3_fwd<S, F3_LOSSKL, FWD_NW>, sh_fwd))) return rc;
-        hipLaunchKernelGGL((k_f3_fwd<S, F3_LOSSKL, FWD_NW>), g, dim3(FWD_NW * 64), sh_fwd, st, k);
+        if ((rc = f3_attr(c, k_f3_fwd<S, OP_LOSSKL, FWD_NW>, sh_fwd))) return rc;
+        hipLaunchKernelGGL((k_f3_fwd<S, OP_LOSSKL, FWD_NW>), g, dim3(FWD_NW * 64), sh_fwd, st, k);
         HIP_TRY(c, hipGetLastError());
         return METRPO_OK;
     }
-    if (mode == UPD_VPG) {
+    if (u.op == OP_VPG) {
         build_image(IMG_WHAT_F | IMG_WHAT_B); c->f3_img_ok = 1;
-        if ((rc = f3_attr(c, k_f3_fwd<S, F3_VPG, FWD_NW>, sh_fwd))) return rc;
-        hipLaunchKernelGGL((k_f3_fwd<S, F3_VPG, FWD_NW>), g, dim3(FWD_NW * 64), sh_fwd, st, k);
+        if ((rc = f3_attr(c, k_f3_fwd<S, OP_VPG, FWD_NW>, sh_fwd))) return rc;
+        hipLaunchKernelGGL((k_f3_fwd<S, OP_VPG, FWD_NW>), g, dim3(FWD_NW * 64), sh_fwd, st, k);
         c->f3_rows = -1;                                    // (no CG solve follows)
-    } else if (mode == 0) {
+    } else if (u.op == OP_GRAD) {
         build_image(IMG_WHAT_F | IMG_WHAT_B); c->f3_img_ok = 1;
-        if ((rc = f3_attr(c, k_f3_fwd<S, F3_GRAD, FWD_NW>, sh_fwd))) return rc;
-        hipLaunchKernelGGL((k_f3_fwd<S, F3_GRAD, FWD_NW>), g, dim3(FWD_NW * 64), sh_fwd, st, k);
-        // the activations stay valid for the Fisher-vector products of this CG solve (run_trpo_update raises hcache_on around it)
-        c->f3_rows = c->hcache_on ? N : -1; c->f3_obs = b->d_obs; c->f3_theta = theta;
+        if ((rc = f3_attr(c, k_f3_fwd<S, OP_GRAD, FWD_NW>, sh_fwd))) return rc;
+        hipLaunchKernelGGL((k_f3_fwd<S, OP_GRAD, FWD_NW>), g, dim3(FWD_NW * 64), sh_fwd, st, k);
+        // the activations stay valid for the Fisher-vector products of this CG solve (SolveScope::cache_activations of run_trpo_update)
+        c->f3_rows = u.scope.cache_activations ? N : -1; c->f3_obs = b.obs; c->f3_theta = u.theta;
     } else {
-        const bool have = c->hcache_on && c->f3_img_ok && c->f3_rows == N && c->f3_obs == b->d_obs && c->f3_theta == theta;
+        const bool have = u.scope.cache_activations && c->f3_img_ok && c->f3_rows == N && c->f3_obs == b.obs && c->f3_theta == u.theta;
         build_image(IMG_WHAT_V | (have ? 0 : (IMG_WHAT_F | IMG_WHAT_B)));
         if (!have) {
             c->f3_img_ok = 0;
-            if ((rc = f3_attr(c, k_f3_fwd<S, F3_CACHE, FWD_NW>, sh_fwd))) return rc;
-            hipLaunchKernelGGL((k_f3_fwd<S, F3_CACHE, FWD_NW>), g, dim3(FWD_NW * 64), sh_fwd, st, k);
+            if ((rc = f3_attr(c, k_f3_fwd<S, F3_FILL_CACHE, FWD_NW>, sh_fwd))) return rc;
+            hipLaunchKernelGGL((k_f3_fwd<S, F3_FILL_CACHE, FWD_NW>), g, dim3(FWD_NW * 64), sh_fwd, st, k);
             c->f3_rows = -1;
         }
         if ((rc = f3_attr(c, k_f3_jvp<S, JVP_NW>, sh_jvp))) return rc;

@@ -109,7 +109,7 @@ __global__ void k_pg_pad_obs(const float* __restrict__ obs, long long N, int ns,
 }
 
 // per-sample head, gradient mode (npo.py:69,75): U = d loss / d mean, per-block partial sums of loss and d loss / d log_std
-// part row (doubles): [0] loss, [1] kl, [2] valid weight, [3 .. 3+na) dls.  VPG (mode 0 only): the VPG surrogate (vpg.py:88), la = adv, loss = -mean(logli * adv)
+// part row (doubles): [0] loss, [1] kl, [2] valid weight, [3 .. 3+na) dls.  VPG (OP_GRAD only): the VPG surrogate (vpg.py:88), la = adv, loss = -mean(logli * adv)
 template <bool VPG>
 __global__ void __launch_bounds__(256) k_pg_head(int mode, PolK k, int na, int nap, const float* __restrict__ MU, const float* __restrict__ log_std,
                                                  float* __restrict__ U, double* __restrict__ parts) {
@@ -118,7 +118,7 @@ __global__ void __launch_bounds__(256) k_pg_head(int mode, PolK k, int na, int n
     for (int i = 0; i < 3 + na; ++i) acc[i] = 0.0;
     for (long long n = (long long)blockIdx.x * 256 + threadIdx.x; n < k.N; n += (long long)gridDim.x * 256) {
         const bool ok = (k.valid == nullptr || k.valid[n]);
-        if (mode == 1) {                                     // FVP: U = tangent(mean) / (s^2 + eps/2) / N
+        if (mode == OP_FVP) {                                // FVP: U = tangent(mean) / (s^2 + eps/2) / N
             for (int d = 0; d < nap; ++d) {
                 float u = 0.0f;
                 if (ok && d < na) { const float ls = fmaxf(log_std[d], LOG_MIN_STD); u = MU[n * nap + d] / (expf(2.0f * ls) + 0.5f * KL_EPS) * k.inv_n; }
@@ -147,11 +147,11 @@ __global__ void __launch_bounds__(256) k_pg_head(int mode, PolK k, int na, int n
             const float z = (a - mu) * expf(-ls), zo = (a - omu) * expf(-ols);
             llr += (ols - ls) + 0.5f * (zo * zo - z * z);
             zz[d] = z;
-            if (mode == 2) { const float s2 = expf(2.0f * ls), os2 = expf(2.0f * ols), dm = omu - mu; kl += (dm * dm + os2 - s2) / (2.0f * s2 + KL_EPS) + ls - ols; }
+            if (mode == OP_LOSSKL) { const float s2 = expf(2.0f * ls), os2 = expf(2.0f * ols), dm = omu - mu; kl += (dm * dm + os2 - s2) / (2.0f * s2 + KL_EPS) + ls - ols; }
         }
         const float la = ok ? (VPG ? k.adv[n] : expf(llr) * k.adv[n]) : 0.0f;   // lr * adv (VPG: ratio 1)
         acc[0] -= VPG ? (double)((llr - na * HALF_LOG_2PI) * la * k.inv_n) : (double)(la * k.inv_n);   // surr_loss = -mean(lr * adv) | -mean(logli * adv)
-        if (mode == 2) { acc[1] += (double)(kl * k.inv_n); continue; }
+        if (mode == OP_LOSSKL) { acc[1] += (double)(kl * k.inv_n); continue; }
         const float w = -la * k.inv_n;
         for (int d = 0; d < nap; ++d) {
             float u = 0.0f;
@@ -190,7 +190,7 @@ __global__ void __launch_bounds__(256) k_pg_head_fvp(PolK k, int na, int nap, co
 }
 
 // ordered (deterministic) assembly of the result vector in float64:
-//   mode 0: out[0] = loss, out[1 + p] = g[p];   mode 1: out[p] = (H v)[p];   mode 2: out[0] = loss, out[1] = kl
+//   OP_GRAD: out[0] = loss, out[1 + p] = g[p];   OP_FVP: out[p] = (H v)[p];   OP_LOSSKL: out[0] = loss, out[1] = kl
 __global__ void __launch_bounds__(256) k_pg_assemble(int mode, PgLay g, int P, int n_params, int nblk_head, const float* __restrict__ part,
                                                      const double* __restrict__ hparts, const float* __restrict__ theta, const double* __restrict__ v,
                                                      double* __restrict__ out) {
@@ -207,14 +207,14 @@ __global__ void __launch_bounds__(256) k_pg_assemble(int mode, PgLay g, int P, i
         for (; b < nblk_head; ++b) t += hparts[(size_t)b * 40 + col];
         return t;
     };
-    if (mode == 2) { if (p < 2) out[p] = head_sum(p); return; }
-    if (p == 0 && mode == 0) out[0] = head_sum(0);
+    if (mode == OP_LOSSKL) { if (p < 2) out[p] = head_sum(p); return; }
+    if (p == 0 && mode == OP_GRAD) out[0] = head_sum(0);
     if (p >= P) return;
     double val = 0.0;
     if (p >= n_params) {                                     // log_std rows
         const int d = p - n_params;
         const double raw = (double)theta[p];
-        if (mode == 0) val = (raw > (double)LOG_MIN_STD) ? head_sum(3 + d) : 0.0;
+        if (mode == OP_GRAD) val = (raw > (double)LOG_MIN_STD) ? head_sum(3 + d) : 0.0;
         else {
             const double s2 = exp(2.0 * fmax(raw, (double)LOG_MIN_STD));
             const double c = 4.0 * s2 * (2.0 * s2 - 1e-8) / ((2.0 * s2 + 1e-8) * (2.0 * s2 + 1e-8));
@@ -238,7 +238,7 @@ __global__ void __launch_bounds__(256) k_pg_assemble(int mode, PgLay g, int P, i
         }
         for (; s < g.splits; ++s) val += (double)pl[(size_t)s * g.part_stride[l]];
     }
-    out[(mode == 0 ? 1 : 0) + p] = val;
+    out[(mode == OP_GRAD ? 1 : 0) + p] = val;
 }
 
 __global__ void k_pg_tail(CgTail t) {
@@ -249,10 +249,10 @@ __global__ void k_pg_tail(CgTail t) {
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------
-bool policy_gemm_applicable(const metrpo_ctx* c, long long N) {
+bool policy_gemm_applicable(const metrpo_ctx* c, long long N, bool vjp) {
     if (c->pol_path == 2) return true;                       // forced (test hook)
     if (c->pol_path == 0) return false;                      // generic forced
-    if (f3_active(c)) return false;                          // fused three-hidden-layer kernels (policy_fused3.hip)
+    if (f3_active(c, vjp)) return false;                          // fused three-hidden-layer kernels (policy_fused3.hip)
     // no fused kernel for this shape, and either enough rows to fill GEMM tiles or a policy large enough that the generic kernels' per-launch cost
     // (thread-per-parameter phases: 1.2 ms per launch for Humanoid's 12 275 weights, whatever N) exceeds the whole GEMM-path update (1.4 ms at N = 64)
     return c->pol_mfma < 0 && (N >= 8192 || c->pd.pol.n_params >= 4096);
@@ -271,30 +271,31 @@ static int pg_ensure(metrpo_ctx* c, const PgLay& g, long long N, PgBufs* B) {
     return METRPO_OK;
 }
 
-// mode 0 grad (+ VJP when c->vjp_gm), 1 fvp, 2 loss/kl, UPD_VPG the VPG gradient (out as mode 0).  Writes `out` like k_finalize and then runs `tail` (may be NULL).
-int policy_gemm_run(metrpo_ctx* c, int mode, const metrpo_batch* b, const PolK& k0, const float* theta, const float* vf, const double* v64,
-                    double* out, const CgTail* tail, hipStream_t st) {
+// OP_GRAD (+ VJP when u.k.gm), OP_FVP, OP_LOSSKL, OP_VPG (out as OP_GRAD).  Writes u.out like k_finalize and then runs u.tail (may be NULL).
+int policy_gemm_run(metrpo_ctx* c, const UpdCall& u, hipStream_t st) {
     const ProblemDesc& pd = c->pd;
-    const long long N = b->N;
+    const PolK& k = u.k;
+    const long long N = k.N;
     if (N > 2000000000LL) return set_err(c, METRPO_EUNSUPPORTED, "policy_gemm: N too large");
-    const bool vpg = (mode == UPD_VPG);                      // the gradient mode with the VPG head
-    if (vpg) mode = 0;
+    const bool vpg = (u.op == OP_VPG);                       // the gradient mode with the VPG head
+    const int mode = vpg ? OP_GRAD : u.op;
+    const float* theta = u.theta;
+    const bool cache = u.scope.cache_activations;
     const PgLay g = pg_layout(pd, N);
     PgBufs B;
     int rc = pg_ensure(c, g, N, &B); if (rc) return rc;
     const int L = g.L, na = pd.na, nap = g.dp[L];
-    PolK k = k0; k.gm = c->vjp_gm;
     auto RB = [&](size_t o) { return B.rows + o * (size_t)N; };
     float* X = RB(g.oX); float* MU = RB(g.oMU); float* U = RB(g.oU);
     const long long CH = 4000000;                            // rows per GEMM launch (grid.y <= 65535 even with 64-row tiles)
 
-    hipLaunchKernelGGL(k_pg_pack, dim3(8, L), dim3(256), 0, st, g, theta, (mode == 1) ? vf : (const float*)nullptr, B.wts);
+    hipLaunchKernelGGL(k_pg_pack, dim3(8, L), dim3(256), 0, st, g, theta, (mode == OP_FVP) ? u.vf : (const float*)nullptr, B.wts);
     // forward (cached across the Fisher-vector products of one CG solve: same theta, same observations)
-    const bool have_fwd = (mode == 1) && c->hcache_on && c->pg_fwd_rows == N && c->pg_fwd_obs == b->d_obs;
+    const bool have_fwd = (mode == OP_FVP) && cache && c->pg_fwd_rows == N && c->pg_fwd_obs == k.obs;
     if (!have_fwd) {
         {
             const long long tot = N * g.dp[0];
-            hipLaunchKernelGGL(k_pg_pad_obs, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, b->d_obs, N, g.d[0], g.dp[0], X);
+            hipLaunchKernelGGL(k_pg_pad_obs, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, k.obs, N, g.d[0], g.dp[0], X);
         }
         for (long long r0 = 0; r0 < N; r0 += CH) {
             const int rows = (int)std::min<long long>(CH, N - r0);
@@ -306,11 +307,11 @@ int policy_gemm_run(metrpo_ctx* c, int mode, const metrpo_batch* b, const PolK& 
                                                       2 * g.dp[l + 1], rows, g.dp[l + 1], g.dp[l], 1, ep, st);
             }
         }
-        c->pg_fwd_rows = (mode == 0 && c->hcache_on) ? N : -1; c->pg_fwd_obs = b->d_obs;
+        c->pg_fwd_rows = (mode == OP_GRAD && cache) ? N : -1; c->pg_fwd_obs = k.obs;
     }
     for (long long r0 = 0; r0 < N; r0 += CH) {
         const int rows = (int)std::min<long long>(CH, N - r0);
-        if (mode != 1) {                                     // mean = H_{L-1} W_{L-1} + b
+        if (mode != OP_FVP) {                                // mean = H_{L-1} W_{L-1} + b
             GemmEpi ep = {}; ep.bias = B.wts + g.oB[L - 1];
             const float* A = (L == 1) ? X + (size_t)r0 * g.dp[0] : RB(g.oHT[L - 1]) + (size_t)r0 * 2 * g.dp[L - 1];
             gemm_auto<EPI_BIAS_ID, false, false>(A, 0, (L == 1) ? g.dp[0] : 2 * g.dp[L - 1], B.wts + g.oW[L - 1], 0, nap, MU + (size_t)r0 * nap, 0, nap,
@@ -332,12 +333,12 @@ int policy_gemm_run(metrpo_ctx* c, int mode, const metrpo_batch* b, const PolK& 
         }
     }
     // per-sample head
-    const bool head_elem = (mode == 1 && k.gm == nullptr);
+    const bool head_elem = (mode == OP_FVP && k.gm == nullptr);
     const int nblk = head_elem ? (int)std::min<long long>(1024, (N * nap + 2047) / 2048) : (int)std::min<long long>(1024, (N + 255) / 256);
     if (head_elem) hipLaunchKernelGGL(k_pg_head_fvp, dim3(nblk), dim3(256), 0, st, k, na, nap, MU, theta + pd.pol.n_params, U, B.hparts);
     else if (vpg) hipLaunchKernelGGL(k_pg_head<true>, dim3(nblk), dim3(256), 0, st, mode, k, na, nap, MU, theta + pd.pol.n_params, U, B.hparts);
     else hipLaunchKernelGGL(k_pg_head<false>, dim3(nblk), dim3(256), 0, st, mode, k, na, nap, MU, theta + pd.pol.n_params, U, B.hparts);
-    if (mode != 2) {
+    if (mode != OP_LOSSKL) {
         // back-prop D_l = (D_{l+1} W_l^T) * (1 - H_l^2), l = L-1 .. 1
         for (long long r0 = 0; r0 < N; r0 += CH) {
             const int rows = (int)std::min<long long>(CH, N - r0);
@@ -359,8 +360,8 @@ int policy_gemm_run(metrpo_ctx* c, int mode, const metrpo_batch* b, const PolK& 
             gemm_mfma_launch<1, 1, EPI_PARTIAL, true, false>(A, 0, lda, Dn, 0, g.dp[l + 1], nullptr, 0, g.dp[l + 1], g.dp[l], g.dp[l + 1], (int)N, 1, ep, st);
         }
     }
-    hipLaunchKernelGGL(k_pg_assemble, dim3((pd.P + 1 + 255) / 256), dim3(256), 0, st, mode, g, pd.P, pd.pol.n_params, nblk, B.part, B.hparts, theta, v64, out);
-    if (tail && tail->op != 0) hipLaunchKernelGGL(k_pg_tail, dim3(1), dim3(1024), 0, st, *tail);
+    hipLaunchKernelGGL(k_pg_assemble, dim3((pd.P + 1 + 255) / 256), dim3(256), 0, st, mode, g, pd.P, pd.pol.n_params, nblk, B.part, B.hparts, theta, u.v64, u.out);
+    if (u.tail && u.tail->op != 0) hipLaunchKernelGGL(k_pg_tail, dim3(1), dim3(1024), 0, st, *u.tail);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
 }

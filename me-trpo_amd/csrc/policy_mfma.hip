@@ -48,7 +48,7 @@ static_assert(POL_SPLIT_R == 0 || (NWAVES == 8 && (POL_SPLIT_R & 1) == 1 && POL_
 // cached-activation FVP kernel, waves of workgroup 0, read back with metrpo_debug_pol_phases (tools/pol_phases.py).  Not in the shipped library.
 #ifdef POL_TIMING
 __device__ unsigned long long g_pol_phase[16][8];
-#define PT_MARK(i) { if (MODE_ == MODE_FVPC && blockIdx.x == 0 && lane == 0) g_pol_phase[wave][i] = __builtin_readcyclecounter(); }
+#define PT_MARK(i) { if (MODE_ == OP_FVPC && blockIdx.x == 0 && lane == 0) g_pol_phase[wave][i] = __builtin_readcyclecounter(); }
 extern "C" int32_t metrpo_debug_pol_phases(unsigned long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pol_phase), sizeof(unsigned long long) * 128) == hipSuccess ? 0 : -1; }
 #else
 #define PT_MARK(i)
@@ -81,12 +81,12 @@ __device__ __forceinline__ float xsum_c(float v) {
     return v;
 }
 
-enum { MODE_GRAD = 0, MODE_FVP = 1, MODE_LOSSKL = 2, MODE_FVPC = 3, MODE_VPG = UPD_VPG };
-// MODE_VPG: the gradient kernel with the VPG surrogate's head (algos/vpg.py:88): la = adv (ratio 1), loss = -mean(logli * adv); the old
-// distribution is not read.  Everything else is MODE_GRAD's code.
+// MODE template arguments: UpdOp (metrpo_internal.h)
+// OP_VPG: the gradient kernel with the VPG surrogate's head (algos/vpg.py:88): la = adv (ratio 1), loss = -mean(logli * adv); the old
+// distribution is not read.  Everything else is OP_GRAD's code.
 // (Measured and parked, tools/experiments/policy_mfma_with_cgp.hip + profiles/r05_update_levers.txt: issue priorities per SIMD wave pair (POL_PRIO), h0 recomputed instead of
 // cached (POL_H0R, +4.8 us per product), weight-gradient products deferred into the next tile's vector stretch (POL_DEFER_S7, 60.5 vs 59.8 us), the CG solve as one launch.)
-// MODE_FVPC: Fisher-vector product with the hidden activations h0, h1 = tanh(.) read from the cache the gradient kernel of the
+// OP_FVPC: Fisher-vector product with the hidden activations h0, h1 = tanh(.) read from the cache the gradient kernel of the
 // same (theta, batch) wrote (PolK::hcache) instead of being recomputed: all 10 products of a CG solve share theta and the
 // observations, so the forward pass (22 of the 100 MFMAs of a tile and all 16 tanh per lane) is done once per update, not 11 times.
 // Cache layout per 16-sample tile: [h0 cb0 | h0 cb1 | .. | h1 cb0 | ..][64 lanes] float4 in the MFMA D layout -- each wave
@@ -107,8 +107,8 @@ struct PolImg {
 template <int NS, int NA, int PH, int MODE_>
 __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict__ theta, const float* __restrict__ v, float* __restrict__ partials) {
     using I = PolImg<NS, NA, PH>;
-    constexpr bool CACHED = (MODE_ == MODE_FVPC), VPG = (MODE_ == MODE_VPG);
-    constexpr int MODE = CACHED ? MODE_FVP : VPG ? MODE_GRAD : MODE_;
+    constexpr bool CACHED = (MODE_ == OP_FVPC), VPG = (MODE_ == OP_VPG);
+    constexpr int MODE = CACHED ? OP_FVP : VPG ? OP_GRAD : MODE_;
     constexpr int NS_KS = I::NS_KS, NSI = cdiv_(NS, 16), HB = I::HB, KK = I::KK;
     constexpr int pW0 = 0, pb0 = NS * PH, pW1 = pb0 + PH, pb1 = pW1 + PH * PH, pW2 = pb1 + PH, pb2 = pW2 + PH * NA,
                   pLS = pb2 + NA, P = pLS + NA, ROW = P + PART_EXTRA;
@@ -121,7 +121,7 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave index in an SGPR: tile indices and base pointers stay scalar
     const int c = lane & 15, q = lane >> 4;
-    if (MODE_ == MODE_LOSSKL && k.skip != nullptr && k.skip[0] >= 0.0) return;      // speculative line-search trial after the search stopped
+    if (MODE_ == OP_LOSSKL && k.skip != nullptr && k.skip[0] >= 0.0) return;      // speculative line-search trial after the search stopped
     float* IMG = lds;
     float* TL = lds + I::TOTAL + wave * WTL;
     PT_MARK(0)
@@ -129,7 +129,7 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
     const f32x4* __restrict__ hc = (const f32x4*)k.hcache;
     // a state-independent old log_std (stride 0: the reference's GaussianMLPPolicy) is one value per action dim for the whole batch: its loads
     // and its two exponentials per sample leave the tile loop (the loss / KL kernel is VALU-bound: 340 instructions per tile, 39 transcendental)
-    const bool ols_const = !VPG && (MODE != MODE_FVP) && k.ls_stride == 0 && k.old_ls != nullptr;
+    const bool ols_const = !VPG && (MODE != OP_FVP) && k.ls_stride == 0 && k.old_ls != nullptr;
     // Everything a tile reads from HBM (observations in both layouts, valid flag, cached activations, and for the loss modes the old
     // distribution / action / advantage) is fetched ONE TILE AHEAD into registers: consumed in the iteration that issued them, the
     // valid flag and the observation loads each put a full HBM round trip (~2000 cycles) on the wave's critical path, per tile.
@@ -149,7 +149,7 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
         const float* __restrict__ ob = k.obs + n0 * NS;
 #pragma unroll
         for (int s = 0; s < NS_KS; ++s) { const int f = 4 * s + q; in.xB[s] = ob[cl * NS + ((f < NS) ? f : NS - 1)]; }
-        if (MODE != MODE_LOSSKL) {
+        if (MODE != OP_LOSSKL) {
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 const int sl = 4 * q + s, slc = (sl < nrem) ? sl : nrem - 1;     // lane q holds samples 4q .. 4q+3 (k-step s of S7 covers samples 4q+s)
@@ -158,9 +158,9 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
             }
         }
         in.vld = (k.valid == nullptr) ? 1 : (int)k.valid[n0 + cl];
-        if (MODE != MODE_FVP) {
+        if (MODE != OP_FVP) {
             const long long nl = n0 + cl;
-            if (MODE == MODE_GRAD && k.gm != nullptr) {
+            if (MODE == OP_GRAD && k.gm != nullptr) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { const int d = 4 * q + r; in.gmv[r] = k.gm[nl * NA + ((d < NA) ? d : NA - 1)]; }
             } else {
@@ -221,7 +221,7 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
             if (4 * q + r < NA) { ols_c[r] = k.old_ls[4 * q + r]; eo_c[r] = expf(-ols_c[r]); os2_c[r] = expf(2.f * ols_c[r]); }
     }
     f32x4 vb0f[HB], vb1f[HB], vb2f;
-    if (MODE == MODE_FVP) {
+    if (MODE == OP_FVP) {
 #pragma unroll
         for (int cb = 0; cb < HB; ++cb)
 #pragma unroll
@@ -243,12 +243,12 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
                 for (int d = 0; d < NAV; ++d) {
                     const int u = 16 * cb + 4 * q + r;
                     w2l[cb][r][d] = (u < PH) ? theta[pW2 + u * NA + d] : 0.f;
-                    v2l[cb][r][d] = (MODE == MODE_FVP && u < PH) ? v[pW2 + u * NA + d] : 0.f;
+                    v2l[cb][r][d] = (MODE == OP_FVP && u < PH) ? v[pW2 + u * NA + d] : 0.f;
                     gw2l[cb][r][d] = 0.f;
                 }
 #pragma unroll
         for (int d = 0; d < NAV; ++d) {
-            b2l[d] = theta[pb2 + d]; vb2l[d] = (MODE == MODE_FVP) ? v[pb2 + d] : 0.f;
+            b2l[d] = theta[pb2 + d]; vb2l[d] = (MODE == OP_FVP) ? v[pb2 + d] : 0.f;
             fisher_d[d] = 1.0f / (expf(2.f * fmaxf(theta[pLS + d], LOG_MIN_STD)) + 0.5f * KL_EPS);
         }
     }
@@ -256,7 +256,7 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
     // k.img_map[i] = source index of image element i in theta (bit 30 clear) or in v (bit 30 set), -1 = zero; built once on the
     // host (pol_image_map).  Map loads, gathers and LDS stores are issued in independent batches of IMG_U per thread: the
     // prologue costs ~2 L2 round trips instead of one dependent global load per element.
-    constexpr int SPL = POL_SPLIT_R ? ((MODE == MODE_GRAD || MODE_ == MODE_FVP) ? POL_SPLIT_R : POL_SPLIT_R_FVP) : 0;      // rounds of the uneven tile deal (0: equal shares)
+    constexpr int SPL = POL_SPLIT_R ? ((MODE == OP_GRAD || MODE_ == OP_FVP) ? POL_SPLIT_R : POL_SPLIT_R_FVP) : 0;      // rounds of the uneven tile deal (0: equal shares)
     const long long first_tile = SPL ? (long long)blockIdx.x * 4 + (wave & 3) + ((wave < 4) ? 0 : 1) * (long long)gridDim.x * 4 : (long long)blockIdx.x * NWAVES + wave;
     if (CACHED && k.imgval != nullptr) {
         // inside a fused CG solve the image already exists in global memory, element for element (weight entries: published by block 0 of the
@@ -282,8 +282,8 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
             for (int u = 0; u < IMG_U; ++u) {
                 const int i = i0 + u * NWAVES * 64 + tid;
                 bool use = m[u] >= 0;
-                if (MODE != MODE_FVP && (m[u] & 0x40000000)) use = false;                       // tangent tables: FVP only
-                if (MODE == MODE_LOSSKL && i >= I::O_W2B && i < I::O_W2F) use = false;          // back-prop tables unused
+                if (MODE != OP_FVP && (m[u] & 0x40000000)) use = false;                       // tangent tables: FVP only
+                if (MODE == OP_LOSSKL && i >= I::O_W2B && i < I::O_W2F) use = false;          // back-prop tables unused
                 if (CACHED && i < I::O_W1F) use = false;                            // W0 forward table unused
                 w[u] = 0.f;
                 if (use) w[u] = (m[u] & 0x40000000) ? v[m[u] & 0x3FFFFFFF] : theta[m[u]];
@@ -296,7 +296,7 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
         }
     }
     __syncthreads();
-    if (MODE_ == MODE_GRAD && k.imgval != nullptr && blockIdx.x == 0) {      // publish the image of this theta for the CG products that follow (tangent entries: zero here, the CG tails fill them)
+    if (MODE_ == OP_GRAD && k.imgval != nullptr && blockIdx.x == 0) {      // publish the image of this theta for the CG products that follow (tangent entries: zero here, the CG tails fill them)
         for (int i = tid; i < I::TOTAL; i += NWAVES * 64) k.imgval[i] = IMG[i];
     }
     PT_MARK(1)
@@ -347,18 +347,18 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
             for (int cb = 0; cb < HB; ++cb) { if (H0C) h0[cb] = in.h[cb]; h1[cb] = in.h[HB + cb]; }
         }
 #pragma unroll
-        for (int cb = 0; cb < HB; ++cb) { if (!H0C) h0[cb] = b0f[cb]; if (MODE == MODE_FVP) t0[cb] = vb0f[cb]; }
+        for (int cb = 0; cb < HB; ++cb) { if (!H0C) h0[cb] = b0f[cb]; if (MODE == OP_FVP) t0[cb] = vb0f[cb]; }
 #pragma unroll
         for (int s = 0; s < NS_KS; ++s)
 #pragma unroll
             for (int cb = 0; cb < HB; ++cb) {
                 if (!H0C) h0[cb] = MFMA16(FRAG2(I::O_W0F, s, cb), xB[s], h0[cb]);
-                if (MODE == MODE_FVP) t0[cb] = MFMA16(FRAG2(I::O_V0F, s, cb), xB[s], t0[cb]);
+                if (MODE == OP_FVP) t0[cb] = MFMA16(FRAG2(I::O_V0F, s, cb), xB[s], t0[cb]);
             }
 #pragma unroll
         for (int cb = 0; cb < HB; ++cb) {
             if (!CACHED) h1[cb] = b1f[cb];
-            if (MODE == MODE_FVP) t1[cb] = vb1f[cb];
+            if (MODE == OP_FVP) t1[cb] = vb1f[cb];
             if (!H0C) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) h0[cb][r] = tanh_fast(h0[cb][r]);
@@ -370,15 +370,15 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
 #pragma unroll
             for (int cb = 0; cb < HB; ++cb) {
                 if (!CACHED) h1[cb] = MFMA16(FRAG2(I::O_W1F, kk, cb), h0[kk >> 2][kk & 3], h1[cb]);
-                if (MODE == MODE_FVP) { if (POL_SKIP & 4) t1[cb][0] += h0[kk >> 2][kk & 3]; else t1[cb] = MFMA16(FRAG2(I::O_V1F, kk, cb), h0[kk >> 2][kk & 3], t1[cb]); }
+                if (MODE == OP_FVP) { if (POL_SKIP & 4) t1[cb][0] += h0[kk >> 2][kk & 3]; else t1[cb] = MFMA16(FRAG2(I::O_V1F, kk, cb), h0[kk >> 2][kk & 3], t1[cb]); }
             }
-        if (MODE != MODE_LOSSKL) {
+        if (MODE != OP_LOSSKL) {
 #pragma unroll
             for (int cb = 0; cb < HB; ++cb)
 #pragma unroll
                 for (int r = 0; r < ((POL_SKIP & 8) ? 0 : 4); ++r) T_H0[cb * TILE + (4 * q + r) * TS + wpos] = h0[cb][r];
         }
-        if (MODE == MODE_FVP) {
+        if (MODE == OP_FVP) {
 #pragma unroll
             for (int cb = 0; cb < HB; ++cb)
 #pragma unroll
@@ -395,13 +395,13 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
 #pragma unroll
                 for (int r = 0; r < 4; ++r) h1[cb][r] = tanh_fast(h1[cb][r]);
         }
-        if (MODE != MODE_LOSSKL) {
+        if (MODE != OP_LOSSKL) {
 #pragma unroll
             for (int cb = 0; cb < HB; ++cb)
 #pragma unroll
                 for (int r = 0; r < (((POL_SKIP & 8) || NA <= 2) ? 0 : 4); ++r) T_H1[cb * TILE + (4 * q + r) * TS + wpos] = h1[cb][r];     // only the MFMA output layer (na > 2) reads it back
         }
-        if (MODE == MODE_GRAD && k.hcache != nullptr) {     // publish the activations for the FVPs of this update
+        if (MODE == OP_GRAD && k.hcache != nullptr) {     // publish the activations for the FVPs of this update
             f32x4* hw = (f32x4*)k.hcache + (size_t)tile * (2 * HB) * 64 + lane;
 #pragma unroll
             for (int cb = 0; cb < HB; ++cb) { hw[cb * 64] = h0[cb]; hw[(HB + cb) * 64] = h1[cb]; }
@@ -411,10 +411,10 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
         float ual[NAV];                                     // FVP with the VALU output layer: the sample's mean-adjoint, already in all of its lanes
 #pragma unroll
         for (int d = 0; d < NAV; ++d) ual[d] = 0.f;
-        if (MODE == MODE_GRAD && k.gm != nullptr) {         // VJP mode (bptt.hip): the mean-adjoint is an input
+        if (MODE == OP_GRAD && k.gm != nullptr) {         // VJP mode (bptt.hip): the mean-adjoint is an input
 #pragma unroll
             for (int r = 0; r < 4; ++r) um[r] = (ok && 4 * q + r < NA) ? in.gmv[r] : 0.f;
-        } else if (MODE != MODE_FVP) {
+        } else if (MODE != OP_FVP) {
             f32x4 mu = Z4;
             if (L2V) {
 #pragma unroll
@@ -452,12 +452,12 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
                         ols = in.ols[r];
                         asm volatile("" : "+v"(ols));                                          // keeps the exponentials on this side of the branch
                         eo = expf(-ols);
-                        if (MODE == MODE_LOSSKL) os2 = expf(2.f * ols);
+                        if (MODE == OP_LOSSKL) os2 = expf(2.f * ols);
                     }
                     const float z = (a - mu[r]) * inv_std[r], zo = (a - omu) * eo;
                     llr += (ols - ls[r]) + 0.5f * (zo * zo - z * z);
                     zz[r] = z;
-                    if (MODE == MODE_LOSSKL) {
+                    if (MODE == OP_LOSSKL) {
                         const float s2 = expf(2.f * ls[r]), dm = omu - mu[r];
                         kl += (dm * dm + os2 - s2) / (2.f * s2 + KL_EPS) + ls[r] - ols;
                     }
@@ -466,7 +466,7 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
             llr = xsum_q(llr);                              // sum over action dims held by the 4 q-lanes of sample c
             const float la = ok ? (VPG ? in.adv : expf(llr) * in.adv) : 0.f;         // lr * adv (VPG: ratio 1)
             if (q == 0) acc0 -= (VPG ? (llr - NA * HALF_LOG_2PI) * la : la) * k.inv_n;   // surr_loss = -mean(lr*adv) (npo.py:75) | -mean(logli*adv) (vpg.py:88)
-            if (MODE == MODE_LOSSKL) { acc1 += kl * k.inv_n; continue; }
+            if (MODE == OP_LOSSKL) { acc1 += kl * k.inv_n; continue; }
             const float w = -la * k.inv_n;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -528,7 +528,7 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
         if (L2V) {
             float ua[NAV];                                  // the sample's mean-adjoint, broadcast from its q = 0 lane to all 4 lanes
 #pragma unroll
-            for (int d = 0; d < NAV; ++d) ua[d] = (MODE == MODE_FVP) ? ual[d] : __shfl(um[d], c, 64);
+            for (int d = 0; d < NAV; ++d) ua[d] = (MODE == OP_FVP) ? ual[d] : __shfl(um[d], c, 64);
 #pragma unroll
             for (int cb = 0; cb < HB; ++cb)
 #pragma unroll
@@ -621,9 +621,9 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
     float* row = RB + wave * ROW;
     // every column of the row is written exactly once below, except the log_std columns outside the gradient mode (zero there); the
     // loss / KL mode only produces the three scalar columns (and only those are summed and stored)
-    if (MODE != MODE_GRAD && lane < NA) row[pLS + lane] = 0.f;
+    if (MODE != OP_GRAD && lane < NA) row[pLS + lane] = 0.f;
     wave_sync_lds();
-    if (MODE != MODE_LOSSKL) {
+    if (MODE != OP_LOSSKL) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
 #pragma unroll
@@ -663,7 +663,7 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
             const float s2 = xsum_c(gb2[r]), sl = xsum_c(dls[r]);
             if (c == 0 && 4 * q + r < NA) {
                 row[pb2 + 4 * q + r] = s2;
-                if (MODE == MODE_GRAD) row[pLS + 4 * q + r] = (theta[pLS + 4 * q + r] > LOG_MIN_STD) ? sl : 0.f;
+                if (MODE == OP_GRAD) row[pLS + 4 * q + r] = (theta[pLS + 4 * q + r] > LOG_MIN_STD) ? sl : 0.f;
             }
         }
     }
@@ -674,7 +674,7 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
     __syncthreads();
     PT_MARK(5)
     float* out = partials + (size_t)blockIdx.x * ROW;
-    for (int i = (MODE == MODE_LOSSKL ? P : 0) + tid; i < ROW; i += NWAVES * 64) {            // fixed pairwise order over the waves
+    for (int i = (MODE == OP_LOSSKL ? P : 0) + tid; i < ROW; i += NWAVES * 64) {            // fixed pairwise order over the waves
         float a = 0.f;
 #pragma unroll
         for (int w = 0; w < NWAVES; w += 4) a += (RB[w * ROW + i] + RB[(w + 1) * ROW + i]) + (RB[(w + 2) * ROW + i] + RB[(w + 3) * ROW + i]);
@@ -723,7 +723,7 @@ static void pol_image_map(std::vector<int>& map) {
 
 // -------------------------------------------------------------------------------------------------
 typedef void (*pol_kernel_t)(PolK, const float*, const float*, float*);
-struct PolEntry { int ns, na, ph; pol_kernel_t kern[5]; int lds_floats, lds_floats_eval; void (*build_map)(std::vector<int>&); };
+struct PolEntry { int ns, na, ph; pol_kernel_t kern[5] /* indexed by UpdOp */; int lds_floats, lds_floats_eval; void (*build_map)(std::vector<int>&); };
 template <int NS, int NA, int PH> constexpr int pol_lds() {
     constexpr int HB = cdiv_(PH, 16);
     constexpr int a = PolImg<NS, NA, PH>::TOTAL + NWAVES * (3 * HB + (NA <= 2 ? 0 : 1)) * 16 * 20;      // 20 = TS of the kernel's transpose tiles
@@ -731,12 +731,12 @@ template <int NS, int NA, int PH> constexpr int pol_lds() {
     constexpr int b = NWAVES * (P + PART_EXTRA);
     return a > b ? a : b;
 }
-template <int NS, int NA, int PH> constexpr int pol_lds_eval() {       // MODE_LOSSKL: weight image, then the epilogue's [NWAVES][ROW] rows
+template <int NS, int NA, int PH> constexpr int pol_lds_eval() {       // OP_LOSSKL: weight image, then the epilogue's [NWAVES][ROW] rows
     constexpr int P = NS * PH + PH + PH * PH + PH + PH * NA + NA + NA;
     constexpr int a = PolImg<NS, NA, PH>::TOTAL, b = NWAVES * (P + PART_EXTRA);
     return a > b ? a : b;
 }
-#define PENTRY(NS, NA, PH) {NS, NA, PH, {k_policy_mfma<NS, NA, PH, 0>, k_policy_mfma<NS, NA, PH, 1>, k_policy_mfma<NS, NA, PH, 2>, k_policy_mfma<NS, NA, PH, 3>, k_policy_mfma<NS, NA, PH, MODE_VPG>}, pol_lds<NS, NA, PH>(), pol_lds_eval<NS, NA, PH>(), pol_image_map<NS, NA, PH>}
+#define PENTRY(NS, NA, PH) {NS, NA, PH, {k_policy_mfma<NS, NA, PH, OP_GRAD>, k_policy_mfma<NS, NA, PH, OP_FVP>, k_policy_mfma<NS, NA, PH, OP_LOSSKL>, k_policy_mfma<NS, NA, PH, OP_FVPC>, k_policy_mfma<NS, NA, PH, OP_VPG>}, pol_lds<NS, NA, PH>(), pol_lds_eval<NS, NA, PH>(), pol_image_map<NS, NA, PH>}
 static const PolEntry kPol[] = {
     PENTRY(10, 2, 32),    // swimmer
     PENTRY(18, 6, 32),    // half-cheetah
@@ -781,31 +781,27 @@ int policy_mfma_image_buffers(metrpo_ctx* c) {
     return METRPO_OK;
 }
 
-// launches mode `mode`; per-block rows of P+3 floats land in `partials`; returns the block count via *nblocks
-int policy_mfma_launch(metrpo_ctx* c, int idx, int mode, const metrpo_batch* b, const float* theta, const float* v,
-                       float* partials, int nblocks, hipStream_t st) {
-    const PolEntry& en = kPol[idx];
-    PolK k;
-    k.obs = b->d_obs; k.act = b->d_act; k.adv = b->d_adv; k.old_mean = b->d_old_mean; k.old_ls = b->d_old_log_std;
-    k.ls_stride = b->old_log_std_stride; k.valid = b->d_valid; k.N = b->N; k.inv_n = (float)b->inv_n_global;
+// launches u.op of ctx->pol_mfma (OP_FVP as OP_FVPC where the scope lets it read the gradient kernel's activations); per-block rows of P+3 floats land in `partials`
+int policy_mfma_launch(metrpo_ctx* c, const UpdCall& u, float* partials, int nblocks, hipStream_t st) {
+    const PolEntry& en = kPol[c->pol_mfma];
     { const int rc = policy_mfma_image_buffers(c); if (rc) return rc; }
+    PolK k = u.k;
+    int mode = u.op;
     k.img_map = (const int*)c->d_pol_img.p;
-    k.gm = c->vjp_gm;
-    k.skip = c->ls_skip;
     k.hcache = nullptr;
-    k.imgval = (c->img_live && c->hcache_on && k.gm == nullptr && (mode == MODE_GRAD || mode == MODE_FVP)) ? c->d_pol_imgval.p : nullptr;
-    if (c->hcache_on && (mode == MODE_GRAD || mode == MODE_FVP) && k.gm == nullptr) {      // set by run_trpo_update around one CG solve
-        const size_t need = (size_t)((b->N + 15) / 16) * 2 * (size_t)cdiv_(en.ph, 16) * 64 * 4;
+    const bool cached = u.scope.cache_activations && (mode == OP_GRAD || mode == OP_FVP) && k.gm == nullptr;      // one CG solve of run_trpo_update
+    k.imgval = (u.scope.publish_image && cached) ? c->d_pol_imgval.p : nullptr;
+    if (cached) {
+        const size_t need = (size_t)((k.N + 15) / 16) * 2 * (size_t)cdiv_(en.ph, 16) * 64 * 4;
         { const int rc = ws_grow(c, c->d_hcache, need * sizeof(float)); if (rc) return rc; }
         k.hcache = c->d_hcache.p;
-        if (mode == MODE_FVP) mode = MODE_FVPC;
+        if (mode == OP_FVP) mode = OP_FVPC;
     }
     // loss + KL evaluation (line search): no transpose tiles, 128 VGPRs -> two blocks fit a CU (run_mode launches 2 x n_sm of them)
     size_t sh = sizeof(float) * (size_t)en.lds_floats;
-    if (mode == MODE_LOSSKL) sh = sizeof(float) * (size_t)en.lds_floats_eval;
+    if (mode == OP_LOSSKL) sh = sizeof(float) * (size_t)en.lds_floats_eval;
     if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)en.kern[mode], hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-    hipLaunchKernelGGL(en.kern[mode], dim3(nblocks), dim3(NWAVES * 64), sh, st, k, theta, v, partials);
+    hipLaunchKernelGGL(en.kern[mode], dim3(nblocks), dim3(NWAVES * 64), sh, st, k, u.theta, u.vf, partials);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
 }
-

@@ -414,187 +414,162 @@ static int ensure_partials(metrpo_ctx* c, int nrows) {
     return ws_grow(c, c->d_partials, need * sizeof(float));
 }
 
-// vpg: the VPG surrogate reads no old distribution -- d_old_mean / d_old_log_std may be NULL
-static int fill_polk(metrpo_ctx* c, const metrpo_batch* b, PolK* k, bool need_targets, bool vpg = false) {
+// the descriptor of `op` on batch b at the context's theta, everything else off; validates what the operation reads
+// (OP_FVP: no targets; OP_VPG: the VPG surrogate reads no old distribution -- d_old_mean / d_old_log_std may be NULL)
+static int make_call(metrpo_ctx* c, UpdOp op, const metrpo_batch* b, UpdCall* u) {
+    const bool vpg = (op == OP_VPG);
     if (!b || !b->d_obs) return set_err(c, METRPO_ENULL, "batch/d_obs is NULL");
     if (b->N <= 0) return set_err(c, METRPO_EINVAL, "batch N must be positive");
     if (c->pd.na > 32) return set_err(c, METRPO_EUNSUPPORTED, "na > 32");
-    if (need_targets && (!b->d_act || !b->d_adv || (!vpg && (!b->d_old_mean || !b->d_old_log_std))))
+    if (op != OP_FVP && (!b->d_act || !b->d_adv || (!vpg && (!b->d_old_mean || !b->d_old_log_std))))
         return set_err(c, METRPO_ENULL, "batch pointer is NULL");
     if (vpg && !(b->inv_n_global > 0.0)) return set_err(c, METRPO_EINVAL, "batch inv_n_global must be positive");
-    k->obs = b->d_obs; k->act = b->d_act; k->adv = b->d_adv; k->old_mean = b->d_old_mean; k->old_ls = b->d_old_log_std;
-    k->ls_stride = b->old_log_std_stride; k->valid = b->d_valid; k->N = b->N; k->inv_n = (float)b->inv_n_global;
-    k->gm = nullptr; k->img_map = nullptr; k->hcache = nullptr; k->imgval = nullptr; k->skip = nullptr;
+    *u = UpdCall{};
+    u->op = op; u->theta = c->d_theta.p;
+    PolK& k = u->k;
+    k.obs = b->d_obs; k.act = b->d_act; k.adv = b->d_adv; k.old_mean = b->d_old_mean; k.old_ls = b->d_old_log_std;
+    k.ls_stride = b->old_log_std_stride; k.valid = b->d_valid; k.N = b->N; k.inv_n = (float)b->inv_n_global;
     return METRPO_OK;
 }
 
-static void finalize(metrpo_ctx* c, int mode, int nrows, int stride, int lk_col, const double* v, double* out, hipStream_t st,
-                     const CgTail* tail = nullptr, const AdamTail* adam = nullptr) {
+// partial rows of one launch in c->d_partials, as k_finalize reads them
+struct PartRows { int rc, nrows, stride, lk_col; };
+
+static void finalize(metrpo_ctx* c, const UpdCall& u, const PartRows& r, hipStream_t st) {
+    const int mode = (u.op == OP_LOSSKL) ? 2 : (u.op == OP_FVP) ? 1 : 0;        // output layout: [loss | gradient], H v, [loss, kl]
     const int nout = (mode == 0) ? c->pd.P + 1 : (mode == 1) ? c->pd.P : 2;
     CgTail none; none.op = 0; none.ticket = c->d_ticket.p; none.vpos = nullptr; none.imgval = nullptr; none.ls = nullptr; none.pub_dst = nullptr;
-    // inside a fused update of a sharded run (run_trpo_update raises xg_fuse) the reduction carries the cross-rank sum in its tail
-    const XchgK xc = (c->xg_fuse && c->xg_world > 1) ? xchg_next(c) : xchg_none();
-    if (adam)
-        hipLaunchKernelGGL(k_finalize<true>, dim3((nout + FIN_C - 1) / FIN_C), dim3(1024), 0, st, c->pd, mode, nrows, stride, lk_col,
-                           c->d_partials.p, c->d_theta.p, v, out, none, xc, *adam);
+    // inside a fused update of a sharded run the reduction carries the cross-rank sum in its tail
+    const XchgK xc = (u.scope.exchange_in_tail && c->xg_world > 1) ? xchg_next(c) : xchg_none();
+    if (u.adam)
+        hipLaunchKernelGGL(k_finalize<true>, dim3((nout + FIN_C - 1) / FIN_C), dim3(1024), 0, st, c->pd, mode, r.nrows, r.stride, r.lk_col,
+                           c->d_partials.p, c->d_theta.p, u.v64, u.out, none, xc, *u.adam);
     else
-        hipLaunchKernelGGL(k_finalize<false>, dim3((nout + FIN_C - 1) / FIN_C), dim3(1024), 0, st, c->pd, mode, nrows, stride, lk_col,
-                           c->d_partials.p, c->d_theta.p, v, out, tail ? *tail : none, xc, AdamTail{});
+        hipLaunchKernelGGL(k_finalize<false>, dim3((nout + FIN_C - 1) / FIN_C), dim3(1024), 0, st, c->pd, mode, r.nrows, r.stride, r.lk_col,
+                           c->d_partials.p, c->d_theta.p, u.v64, u.out, u.tail ? *u.tail : none, xc, AdamTail{});
 }
 
 // generic kernels: pick the largest sample tile (threads per block) whose LDS columns fit
 template <int PT>
-static int launch_generic(metrpo_ctx* c, int mode, const PolK& k, const float* theta, const float* vf, int* nrows, hipStream_t st) {
+static int launch_generic(metrpo_ctx* c, const UpdCall& u, int* nrows, hipStream_t st) {
     const NetDesc& net = c->pd.pol;
+    const PolK& k = u.k;
     int hrows = 0; for (int l = 0; l < net.n_layers; ++l) hrows += net.dims[l];
-    size_t rows = (mode == 0 || mode == UPD_VPG) ? hrows + c->pd.na : (mode == 1) ? hrows + c->pd.na + (hrows - net.dims[0])
-                                                              : (size_t)c->pd.ns + 2 * net.max_width;
+    size_t rows = (u.op == OP_GRAD || u.op == OP_VPG) ? hrows + c->pd.na : (u.op == OP_FVP) ? hrows + c->pd.na + (hrows - net.dims[0])
+                                                                         : (size_t)c->pd.ns + 2 * net.max_width;
     const size_t sh = rows * (PT + 1) * sizeof(float);
     if (sh > 160 * 1024) return METRPO_EUNSUPPORTED;
     const long long tiles = (k.N + PT - 1) / PT;
     const int g = (int)std::max<long long>(1, std::min<long long>(tiles, (long long)c->n_sm * 2));
     int rc = ensure_partials(c, g); if (rc) return rc;
     *nrows = g;
-    if (mode == 0) {
+    if (u.op == OP_GRAD) {
         if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_loss_grad<PT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        hipLaunchKernelGGL((k_loss_grad<PT, false>), dim3(g), dim3(PT), sh, st, c->pd, k, theta, c->d_partials.p);
-    } else if (mode == UPD_VPG) {
+        hipLaunchKernelGGL((k_loss_grad<PT, false>), dim3(g), dim3(PT), sh, st, c->pd, k, u.theta, c->d_partials.p);
+    } else if (u.op == OP_VPG) {
         if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_loss_grad<PT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        hipLaunchKernelGGL((k_loss_grad<PT, true>), dim3(g), dim3(PT), sh, st, c->pd, k, theta, c->d_partials.p);
-    } else if (mode == 1) {
+        hipLaunchKernelGGL((k_loss_grad<PT, true>), dim3(g), dim3(PT), sh, st, c->pd, k, u.theta, c->d_partials.p);
+    } else if (u.op == OP_FVP) {
         if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_fvp<PT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        hipLaunchKernelGGL(k_fvp<PT>, dim3(g), dim3(PT), sh, st, c->pd, k, theta, vf, c->d_partials.p);
+        hipLaunchKernelGGL(k_fvp<PT>, dim3(g), dim3(PT), sh, st, c->pd, k, u.theta, u.vf, c->d_partials.p);
     } else {
         if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_loss_kl<PT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        hipLaunchKernelGGL(k_loss_kl<PT>, dim3(g), dim3(PT), sh, st, c->pd, k, theta, c->d_partials.p);
+        hipLaunchKernelGGL(k_loss_kl<PT>, dim3(g), dim3(PT), sh, st, c->pd, k, u.theta, c->d_partials.p);
     }
     return METRPO_OK;
 }
 
-// runs mode on the fastest available path; on return the partial rows are in c->d_partials
-static int run_mode(metrpo_ctx* c, int mode, const metrpo_batch* b, const PolK& k, const float* theta, const float* vf,
-                    int* nrows, int* stride, int* lk_col, hipStream_t st) {
+// runs u on the fastest fused or generic family; on return the partial rows are in c->d_partials
+static PartRows run_mode(metrpo_ctx* c, const UpdCall& u, hipStream_t st) {
     const int P = c->pd.P;
-    if (c->pol_mfma >= 0) {
-        const long long tiles = (b->N + 15) / 16;
-        // one 8-wave block per CU = 2 waves per SIMD (measured in round 1: 2 and 3 waves per SIMD run at the same speed, 1 and 4
+    const long long tiles = (u.k.N + 15) / 16;
+    PartRows r = {METRPO_OK, 0, P + PART_EXTRA, P};
+    const bool mfma = c->pol_mfma >= 0;
+    if (mfma || f3_active(c, u.k.gm != nullptr)) {
+        // policy_mfma.hip: one 8-wave block per CU = 2 waves per SIMD (measured in round 1: 2 and 3 waves per SIMD run at the same speed, 1 and 4
         // are slower) and only n_sm partial rows for k_finalize
         // (the loss + KL evaluation of the line search needs no transpose tiles and half the registers: two blocks per CU)
         // small batches (the params files' N = 50 000 - 60 000: 1.5 tiles per wave on a full grid): fewer, fuller blocks -- a launch's fixed cost does not
         // shrink with the tile count, but k_finalize reads one partial row per block (upd_tiles_per_wave, api.hip)
-        const long long per_block = 8ll * std::max(1, c->upd_tiles_per_wave);
-        const int g = (int)std::max<long long>(1, std::min<long long>((tiles + per_block - 1) / per_block, (long long)c->n_sm * (mode == 2 ? 2 : 1)));
-        int rc = ensure_partials(c, g); if (rc) return rc;
-        *nrows = g; *stride = P + PART_EXTRA; *lk_col = P;
-        c->ls_skip = k.skip;
-        rc = policy_mfma_launch(c, c->pol_mfma, mode, b, theta, vf, c->d_partials.p, g, st);
-        c->ls_skip = nullptr;
-        return rc;
-    }
-    if (f3_active(c)) {
         // policy_fused3.hip: one block per CU; the back-prop kernel runs 4 waves per block (one per SIMD, 272 accumulator registers each), the
-        // forward / tangent kernels 8; all write the same `g` partial rows
-        const long long tiles = (b->N + 15) / 16;
-        const long long per_block = 4ll * std::max(1, c->upd_tiles_per_wave);
-        const int g = (int)std::max<long long>(1, std::min<long long>((tiles + per_block - 1) / per_block, (long long)c->n_sm));
-        int rc = ensure_partials(c, g); if (rc) return rc;
-        *nrows = g; *stride = P + PART_EXTRA; *lk_col = P;
-        c->ls_skip = k.skip;
-        rc = policy_f3_launch(c, mode, b, theta, vf, c->d_partials.p, g, st);
-        c->ls_skip = nullptr;
-        return rc;
+        // forward / tangent kernels 8; all write the same `nrows` partial rows
+        const long long per_block = (mfma ? 8ll : 4ll) * std::max(1, c->upd_tiles_per_wave);
+        const long long max_blocks = (long long)c->n_sm * ((mfma && u.op == OP_LOSSKL) ? 2 : 1);
+        r.nrows = (int)std::max<long long>(1, std::min<long long>((tiles + per_block - 1) / per_block, max_blocks));
+        if (!(r.rc = ensure_partials(c, r.nrows)))
+            r.rc = mfma ? policy_mfma_launch(c, u, c->d_partials.p, r.nrows, st) : policy_f3_launch(c, u, c->d_partials.p, r.nrows, st);
+        return r;
     }
-    *stride = (mode == 2) ? 2 : P + PART_EXTRA; *lk_col = 0;
-    int rc = launch_generic<128>(c, mode, k, theta, vf, nrows, st);
-    if (rc == METRPO_EUNSUPPORTED) rc = launch_generic<64>(c, mode, k, theta, vf, nrows, st);
-    if (rc == METRPO_EUNSUPPORTED) rc = launch_generic<32>(c, mode, k, theta, vf, nrows, st);
-    if (rc == METRPO_EUNSUPPORTED) return set_err(c, rc, "policy too wide for the update kernels' LDS tile");
-    return rc;
+    r.stride = (u.op == OP_LOSSKL) ? 2 : P + PART_EXTRA; r.lk_col = 0;
+    r.rc = launch_generic<128>(c, u, &r.nrows, st);
+    if (r.rc == METRPO_EUNSUPPORTED) r.rc = launch_generic<64>(c, u, &r.nrows, st);
+    if (r.rc == METRPO_EUNSUPPORTED) r.rc = launch_generic<32>(c, u, &r.nrows, st);
+    if (r.rc == METRPO_EUNSUPPORTED) r.rc = set_err(c, r.rc, "policy too wide for the update kernels' LDS tile");
+    return r;
 }
 
-int launch_loss_grad(metrpo_ctx* c, const metrpo_batch* b, double* out, hipStream_t st, const CgTail* tail) {
-    PolK k; int rc = fill_polk(c, b, &k, true); if (rc) return rc;
-    if (policy_gemm_applicable(c, b->N)) return policy_gemm_run(c, 0, b, k, c->d_theta.p, nullptr, nullptr, out, tail, st);
-    int nrows, stride, lk;
-    if ((rc = run_mode(c, 0, b, k, c->d_theta.p, nullptr, &nrows, &stride, &lk, st))) return rc;
-    finalize(c, 0, nrows, stride, lk, nullptr, out, st, tail);
+// One update launch: pick the family, launch, reduce into u.out (+ the step u.tail / u.adam describes, in the reduction's tail).
+// The GEMM path (policy_gemm.hip) has its own reduction: it runs u.tail as a kernel of its own and cannot carry an accept test or an Adam step.
+static int run_update(metrpo_ctx* c, const UpdCall& u, hipStream_t st) {
+    if (policy_gemm_applicable(c, u.k.N, u.k.gm != nullptr)) {
+        if (u.op == OP_LOSSKL && u.tail) return set_err(c, METRPO_EUNSUPPORTED, "device-side line search: not on the GEMM update path");
+        return policy_gemm_run(c, u, st);
+    }
+    const bool timed = u.op == OP_FVP && ctx_opt(c, OPT_TIME_FVP) != nullptr && c->fvp_ev_n + 2 <= 32;      // diagnostics: metrpo_debug_fvp_us
+    if (timed) {
+        for (; c->fvp_ev_made < 32; ++c->fvp_ev_made) HIP_TRY(c, hipEventCreate(&c->fvp_ev[c->fvp_ev_made]));
+        HIP_TRY(c, hipEventRecord(c->fvp_ev[c->fvp_ev_n], st));
+    }
+    const PartRows r = run_mode(c, u, st);
+    if (r.rc) return r.rc;
+    if (timed) { HIP_TRY(c, hipEventRecord(c->fvp_ev[c->fvp_ev_n + 1], st)); c->fvp_ev_n += 2; }
+    finalize(c, u, r, st);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
+}
+
+int launch_loss_grad(metrpo_ctx* c, const metrpo_batch* b, double* out, hipStream_t st, const CgTail* tail, SolveScope scope) {
+    UpdCall u; int rc = make_call(c, OP_GRAD, b, &u); if (rc) return rc;
+    u.out = out; u.tail = tail; u.scope = scope;
+    return run_update(c, u, st);
 }
 
 // sum_n J_policy(obs_n)^T gm_n -> out[1 .. P] (out[0] = 0): the gradient kernels with the mean-adjoint supplied (bptt.hip)
 int launch_policy_vjp(metrpo_ctx* c, const float* obs, const float* gm, long long N, double* out, hipStream_t st) {
     if (!obs || !gm || !out) return set_err(c, METRPO_ENULL, "policy_vjp: NULL pointer");
     if (c->pd.na > 32) return set_err(c, METRPO_EUNSUPPORTED, "na > 32");
-    metrpo_batch b = {};
-    b.d_obs = obs; b.N = N; b.inv_n_global = 1.0;
-    PolK k = {};
-    k.obs = obs; k.N = N; k.inv_n = 1.0f; k.gm = gm;
-    int nrows, stride, lk;
-    c->vjp_gm = gm;
-    if (policy_gemm_applicable(c, N)) {
-        const int rcg = policy_gemm_run(c, 0, &b, k, c->d_theta.p, nullptr, nullptr, out, nullptr, st);
-        c->vjp_gm = nullptr;
-        return rcg;
-    }
-    const int rc = run_mode(c, 0, &b, k, c->d_theta.p, nullptr, &nrows, &stride, &lk, st);
-    c->vjp_gm = nullptr;
-    if (rc) return rc;
-    finalize(c, 0, nrows, stride, lk, nullptr, out, st);
-    HIP_TRY(c, hipGetLastError());
-    return METRPO_OK;
+    UpdCall u = {};
+    u.op = OP_GRAD; u.theta = c->d_theta.p; u.out = out;
+    u.k.obs = obs; u.k.N = N; u.k.inv_n = 1.0f; u.k.gm = gm;
+    return run_update(c, u, st);
 }
 
 int launch_fvp(metrpo_ctx* c, const metrpo_batch* b, const double* v, double* hv, hipStream_t st) {
     if (!v || !hv) return set_err(c, METRPO_ENULL, "v/hv is NULL");
     const int P = c->pd.P;
     hipLaunchKernelGGL(k_d2f, dim3((P + 127) / 128), dim3(128), 0, st, v, c->d_vf.p, P);
-    return launch_fvp_f32(c, b, c->d_vf.p, v, hv, st);
+    return launch_fvp_tail(c, b, c->d_vf.p, v, hv, nullptr, st);
 }
 
-int launch_fvp_f32(metrpo_ctx* c, const metrpo_batch* b, const float* vf, const double* v, double* hv, hipStream_t st) {
-    return launch_fvp_tail(c, b, vf, v, hv, nullptr, st);
+int launch_fvp_tail(metrpo_ctx* c, const metrpo_batch* b, const float* vf, const double* v, double* hv, const CgTail* tail, hipStream_t st, SolveScope scope) {
+    UpdCall u; int rc = make_call(c, OP_FVP, b, &u); if (rc) return rc;
+    u.vf = vf; u.v64 = v; u.out = hv; u.tail = tail; u.scope = scope;
+    return run_update(c, u, st);
 }
 
-int launch_fvp_tail(metrpo_ctx* c, const metrpo_batch* b, const float* vf, const double* v, double* hv, const CgTail* tail, hipStream_t st) {
-    PolK k; int rc = fill_polk(c, b, &k, false); if (rc) return rc;
-    if (policy_gemm_applicable(c, b->N)) return policy_gemm_run(c, 1, b, k, c->d_theta.p, vf, v, hv, tail, st);
-    int nrows, stride, lk;
-    const bool timed = ctx_opt(c, OPT_TIME_FVP) != nullptr && c->fvp_ev_n + 2 <= 32;      // diagnostics: metrpo_debug_fvp_us
-    if (timed) {
-        for (; c->fvp_ev_made < 32; ++c->fvp_ev_made) HIP_TRY(c, hipEventCreate(&c->fvp_ev[c->fvp_ev_made]));
-        HIP_TRY(c, hipEventRecord(c->fvp_ev[c->fvp_ev_n], st));
-    }
-    if ((rc = run_mode(c, 1, b, k, c->d_theta.p, vf, &nrows, &stride, &lk, st))) return rc;
-    if (timed) { HIP_TRY(c, hipEventRecord(c->fvp_ev[c->fvp_ev_n + 1], st)); c->fvp_ev_n += 2; }
-    finalize(c, 1, nrows, stride, lk, v, hv, st, tail);
-    HIP_TRY(c, hipGetLastError());
-    return METRPO_OK;
-}
-
-int launch_loss_kl(metrpo_ctx* c, const metrpo_batch* b, const float* theta, double* out, hipStream_t st, const CgTail* decide) {
-    PolK k; int rc = fill_polk(c, b, &k, true); if (rc) return rc;
-    if (policy_gemm_applicable(c, b->N)) {
-        if (decide) return set_err(c, METRPO_EUNSUPPORTED, "device-side line search: not on the GEMM update path");
-        return policy_gemm_run(c, 2, b, k, theta ? theta : c->d_theta.p, nullptr, nullptr, out, nullptr, st);
-    }
-    if (decide) k.skip = decide->ls;
-    int nrows, stride, lk;
-    if ((rc = run_mode(c, 2, b, k, theta ? theta : c->d_theta.p, nullptr, &nrows, &stride, &lk, st))) return rc;
-    finalize(c, 2, nrows, stride, lk, nullptr, out, st, decide);
-    HIP_TRY(c, hipGetLastError());
-    return METRPO_OK;
+int launch_loss_kl(metrpo_ctx* c, const metrpo_batch* b, const float* theta, double* out, hipStream_t st, const CgTail* decide, SolveScope scope) {
+    UpdCall u; int rc = make_call(c, OP_LOSSKL, b, &u); if (rc) return rc;
+    if (theta) u.theta = theta;
+    if (decide) u.k.skip = decide->ls;
+    u.out = out; u.tail = decide; u.scope = scope;
+    return run_update(c, u, st);
 }
 
 // ---- 'vpg' (algos/vpg.py; FirstOrderOptimizer with batch_size=None, max_epochs=1: one Adam step on the whole batch's gradient) ----
 int launch_vpg_loss_grad(metrpo_ctx* c, const metrpo_batch* b, double* out, hipStream_t st) {
-    PolK k; int rc = fill_polk(c, b, &k, true, true); if (rc) return rc;
-    if (policy_gemm_applicable(c, b->N)) return policy_gemm_run(c, UPD_VPG, b, k, c->d_theta.p, nullptr, nullptr, out, nullptr, st);
-    int nrows, stride, lk;
-    if ((rc = run_mode(c, UPD_VPG, b, k, c->d_theta.p, nullptr, &nrows, &stride, &lk, st))) return rc;
-    finalize(c, 0, nrows, stride, lk, nullptr, out, st);
-    HIP_TRY(c, hipGetLastError());
-    return METRPO_OK;
+    UpdCall u; int rc = make_call(c, OP_VPG, b, &u); if (rc) return rc;
+    u.out = out;
+    return run_update(c, u, st);
 }
 
 // k_finalize<true>'s step as a launch of its own: behind an all-reduce that k_finalize cannot carry (RCCL, a gradient longer than an exchange slot)
@@ -610,7 +585,7 @@ int run_vpg_update(metrpo_ctx* c, const metrpo_batch* b, const metrpo_vpg_params
     if (!pr) return set_err(c, METRPO_ENULL, "vpg_update: params NULL");
     if (!(pr->lr >= 0.0) || !(pr->beta1 >= 0.0 && pr->beta1 < 1.0) || !(pr->beta2 >= 0.0 && pr->beta2 < 1.0) || !(pr->eps >= 0.0))
         return set_err(c, METRPO_EINVAL, "vpg_update: need lr >= 0, 0 <= beta1, beta2 < 1, eps >= 0");
-    PolK k; int rc = fill_polk(c, b, &k, true, true); if (rc) return rc;
+    UpdCall u; int rc = make_call(c, OP_VPG, b, &u); if (rc) return rc;
     if ((rc = ensure_policy_adam(c))) return rc;
     // TF's bias correction folded into the step size, exactly as launch_policy_adam (bptt.hip) computes it
     const int t1 = c->pol_adam_t + 1;
@@ -618,21 +593,13 @@ int run_vpg_update(metrpo_ctx* c, const metrpo_batch* b, const metrpo_vpg_params
     float* am = (float*)c->d_pol_adam.p;
     const AdamTail ad = {c->d_theta.p, am, am + P, (float)lr_t, (float)pr->beta1, (float)pr->beta2, (float)pr->eps, d_loss};
     double* gout = c->d_cg.p;                               // [1 + P] of the CG workspace (no update is open across this call)
-    const bool gemm = policy_gemm_applicable(c, b->N);
-    const bool xg = c->xg_world > 1;
     // the step rides in the reduction's tail unless an all-reduce the reduction cannot carry has to sit between them
-    const bool fused = !gemm && (xg ? (P + 1 <= c->xg_cap) : (c->nccl_comm == nullptr));
-    if (gemm) {
-        if ((rc = policy_gemm_run(c, UPD_VPG, b, k, c->d_theta.p, nullptr, nullptr, gout, nullptr, st))) return rc;
-    } else {
-        int nrows, stride, lk;
-        if ((rc = run_mode(c, UPD_VPG, b, k, c->d_theta.p, nullptr, &nrows, &stride, &lk, st))) return rc;
-        c->xg_fuse = (fused && xg) ? 1 : 0;
-        finalize(c, 0, nrows, stride, lk, nullptr, gout, st, nullptr, fused ? &ad : nullptr);
-        c->xg_fuse = 0;
-    }
+    const UpdFusion f = update_fusion(c, b->N, false);
+    const bool fused = f.carries_next_step();
+    u.out = gout; u.adam = fused ? &ad : nullptr; u.scope.exchange_in_tail = f.exchange_in_tail;
+    if ((rc = run_update(c, u, st))) return rc;
     if (!fused) {
-        if ((xg || c->nccl_comm) && (rc = comm_allreduce_f64(c, gout, P + 1, st))) return rc;
+        if ((c->xg_world > 1 || c->nccl_comm) && (rc = comm_allreduce_f64(c, gout, P + 1, st))) return rc;
         hipLaunchKernelGGL(k_vpg_adam, dim3((P + 255) / 256), dim3(256), 0, st, (const double*)gout, P, ad);
     }
     HIP_TRY(c, hipGetLastError());
