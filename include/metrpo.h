@@ -290,6 +290,29 @@ typedef struct {
  * the all-reduce and a stand-alone step follow the reduction).  d_loss (optional, 1 double) = the loss at the entry theta. */
 int32_t metrpo_vpg_update(metrpo_ctx* ctx, const metrpo_batch* batch, const metrpo_vpg_params* params, double* d_loss, void* stream);
 
+/* ---- PPO update (algos/ppo.py:107-119).  With lr_i = exp(logli_theta(a_i | o_i) - logli_old(a_i | o_i)) (ppo.py:107; logli as for VPG, the old
+ * distribution is the batch's d_old_mean / d_old_log_std, which must be there: NULL is METRPO_EINVAL):
+ *     loss = -mean_i min(lr_i A_i, clip(lr_i, 1 - clip_lr, 1 + clip_lr) A_i) - entropy_bonus_coeff * mean_i H_i        (ppo.py:112-119)
+ * H = sum_j log_std_j + na / 2 (1 + log 2 pi) of the clamped log_std (ppo.py:109), means over the valid samples (inv_n_global).  The gradient is
+ * tf.minimum's / tf.clip_by_value's: a sample contributes -A_i lr_i grad(logli_i) / N when lr_i A_i <= clip(lr_i) A_i (ties: the unclipped
+ * branch) and nothing otherwise; the entropy term adds -entropy_bonus_coeff on every unclamped log_std slot.  use_kl_penalty (ppo.py:120-121)
+ * is not built.  The optimiser ppo.py:61-62 names (an AdamOptimizer the file never imports or defines) is stated here: n_epochs full-batch
+ * tf.train.AdamOptimizer steps, no clipping, every policy parameter incl. log_std. */
+typedef struct {
+    double clip_lr, entropy_bonus_coeff;   /* ppo.py:19, :24: 0.3, 0 */
+    double lr, beta1, beta2, eps;          /* the Adam epochs of metrpo_ppo_update (1e-3, 0.9, 0.999, 1e-8); not read by metrpo_ppo_loss_grad */
+} metrpo_ppo_params;
+/* Loss and gradient of ppo.py:119's clipped_surr_pen_loss at the ctx policy: d_out [1 + P] float64 in metrpo_loss_grad's layout.  The surrogate part
+ * is this rank's share; the entropy term is per parameter and is added whole by every call -- a host-driven all-reduce over W ranks passes
+ * entropy_bonus_coeff / W. */
+int32_t metrpo_ppo_loss_grad(metrpo_ctx* ctx, const metrpo_batch* batch, const metrpo_ppo_params* params, double* d_out, void* stream);
+/* One optimize_policy of PPO (ppo.py:157-177, the optimizer.optimize call): n_epochs x (gradient kernel + reduction whose blocks add the entropy term
+ * and apply the Adam step to the columns they reduced), the old distribution fixed while theta moves.  No synchronisation and no host read between
+ * the epochs.  The optimizer state is the ctx policy Adam state, not reset here (as metrpo_vpg_update).  Sharded: each epoch's reduction carries the
+ * one-shot exchange in its tail; with an RCCL communicator (and on the GEMM path) the all-reduce and a stand-alone step follow the reduction.
+ * d_losses (optional, n_epochs doubles): d_losses[e] = the loss at the theta entering epoch e. */
+int32_t metrpo_ppo_update(metrpo_ctx* ctx, const metrpo_batch* batch, const metrpo_ppo_params* params, int32_t n_epochs, double* d_losses, void* stream);
+
 /* ---- multi-GPU: one process and one ctx per GPU, the env batch B sharded over the ranks.  The only exchanges on
  * the path are sum all-reduces of small float64 vectors.  Attach an RCCL communicator to the ctx and metrpo_trpo_update issues
  * its all-reduces itself (ncclAllReduce on the caller's stream, in-place, float64); the reference has no counterpart (it is a

@@ -64,6 +64,11 @@ class VpgParams(C.Structure):
     _fields_ = [('lr', C.c_double), ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double)]
 
 
+class PpoParams(C.Structure):
+    _fields_ = [('clip_lr', C.c_double), ('entropy_bonus_coeff', C.c_double), ('lr', C.c_double), ('beta1', C.c_double), ('beta2', C.c_double),
+                ('eps', C.c_double)]
+
+
 class LbfgsOpts(C.Structure):
     _fields_ = [('m', C.c_int32), ('maxls', C.c_int32), ('maxiter', C.c_int32), ('maxfun', C.c_int32), ('ftol', C.c_double),
                 ('gtol', C.c_double), ('lookahead', C.c_int32), ('round_f32', C.c_int32)]
@@ -112,6 +117,8 @@ SYMBOLS = {
     'metrpo_loss_kl': (_I, [_P, C.POINTER(Batch), _P, _P, _P]),
     'metrpo_vpg_loss_grad': (_I, [_P, C.POINTER(Batch), _P, _P]),
     'metrpo_vpg_update': (_I, [_P, C.POINTER(Batch), C.POINTER(VpgParams), _P, _P]),
+    'metrpo_ppo_loss_grad': (_I, [_P, C.POINTER(Batch), C.POINTER(PpoParams), _P, _P]),
+    'metrpo_ppo_update': (_I, [_P, C.POINTER(Batch), C.POINTER(PpoParams), C.c_int32, _P, _P]),
     'metrpo_trpo_update': (_I, [_P, C.POINTER(Batch), C.POINTER(TrpoParams), C.POINTER(TrpoDiag), _P, _P, _P]),
     'metrpo_trpo_update_begin': (_I, [_P, C.POINTER(Batch), C.POINTER(TrpoParams), _I, _P, _P, _P]),
     'metrpo_trpo_update_end': (_I, [_P, C.POINTER(TrpoDiag), C.POINTER(C.c_int32), _P]),

@@ -1,4 +1,4 @@
-"""algos/batch_polopt.py, algos/npo.py, algos/trpo.py, algos/vpg.py of the reference with the same constructor
+"""algos/batch_polopt.py, algos/npo.py, algos/trpo.py, algos/vpg.py, algos/ppo.py of the reference with the same constructor
 arguments, attributes and methods (start_worker / obtain_samples / process_samples /
 optimize_policy), so that the reference's outer loop (model_based_rl.py:1171-1180) drives them
 unchanged:
@@ -6,7 +6,7 @@ unchanged:
     algo.start_worker(); paths = algo.obtain_samples(j); samples_data = algo.process_samples(j, paths)
     algo.optimize_policy(j, samples_data)
 """
-from .optimizer import ConjugateGradientOptimizer
+from .optimizer import ConjugateGradientOptimizer, AdamOptimizer
 from .parallel import Comm
 from .sampler import VectorizedSampler
 from .tracing import PhaseTimers
@@ -182,6 +182,66 @@ class VPG(BatchPolopt):
         if hasattr(self.sampler, 'finish_baseline_fit') and not getattr(self, 'defer_baseline_fit', False):
             self.sampler.finish_baseline_fit()
         return dict()
+
+    def get_itr_snapshot(self, itr, samples_data):
+        return dict(itr=itr, policy=self.policy, baseline=self.baseline, env=self.env)
+
+
+class PPO(BatchPolopt):
+    """Proximal Policy Optimization (algos/ppo.py) with the reference's constructor signature.  The loss is ppo.py:107-119's clipped
+    likelihood-ratio surrogate with the entropy bonus; the optimiser ppo.py:61-62 names is never defined there and is optimizer.AdamOptimizer
+    here.  use_kl_penalty=True (ppo.py:120-121; the reference never calls its f_increase_penalty / f_decrease_penalty) is not built.  The other
+    arguments the reference's constructor stores and never reads (use_line_search, max_backtracks, backtrack_ratio, step_size, min_n_epochs,
+    adaptive_learning_rate, max / min_learning_rate, gradient_clipping, the penalty factors and bounds, log_loss_kl_before / _after) are stored
+    and not acted on, as there.  Recurrent policies are out of scope (ppo.py:103)."""
+
+    def __init__(self, clip_lr=0.3, increase_penalty_factor=2, decrease_penalty_factor=0.5, min_penalty=1e-3, max_penalty=1e6,
+                 entropy_bonus_coeff=0., gradient_clipping=40., log_loss_kl_before=True, log_loss_kl_after=True, use_kl_penalty=False,
+                 initial_kl_penalty=1., use_line_search=True, max_backtracks=10, backtrack_ratio=0.5, optimizer=None, step_size=0.01,
+                 min_n_epochs=2, adaptive_learning_rate=False, max_learning_rate=1e-3, min_learning_rate=1e-5, **kwargs):
+        if use_kl_penalty:
+            raise NotImplementedError("PPO: use_kl_penalty (ppo.py:120-121) is not built: its gate needs the batch-mean KL in front of the gradient")
+        self.clip_lr, self.entropy_bonus_coeff = clip_lr, entropy_bonus_coeff
+        self.increase_penalty_factor, self.decrease_penalty_factor = increase_penalty_factor, decrease_penalty_factor
+        self.min_penalty, self.max_penalty, self.initial_kl_penalty = min_penalty, max_penalty, initial_kl_penalty
+        self.gradient_clipping = gradient_clipping
+        self.log_loss_kl_before, self.log_loss_kl_after = log_loss_kl_before, log_loss_kl_after
+        self.use_kl_penalty, self.use_line_search = use_kl_penalty, use_line_search
+        self.max_backtracks, self.backtrack_ratio, self.step_size = max_backtracks, backtrack_ratio, step_size
+        self.min_n_epochs, self.adaptive_learning_rate = min_n_epochs, adaptive_learning_rate
+        self.max_learning_rate, self.min_learning_rate = max_learning_rate, min_learning_rate
+        if kwargs.get('policy') is not None and getattr(kwargs['policy'], 'recurrent', False):
+            raise NotImplementedError("PPO: recurrent policies are out of scope (ppo.py:103 asserts the same)")
+        if optimizer is None:
+            optimizer = AdamOptimizer()
+        self.optimizer = optimizer
+        self.opt_info = None
+        super(PPO, self).__init__(**kwargs)
+
+    def init_opt(self):
+        self.optimizer.update_opt(loss=None, target=self.policy, inputs=None)
+        self.opt_info = dict()
+        return dict()
+
+    def optimize_policy(self, itr, samples_data):
+        """ppo.py:157-183: inputs = (observations, actions, advantages, agent_infos[mean], agent_infos[log_std]); loss and mean KL before,
+        optimizer.optimize, mean KL and loss after.  The reference computes the five diagnostics and returns an empty dict (its record_tabular
+        lines are commented out); they are returned here, as 1-element device tensors (no synchronisation)."""
+        agent_infos = samples_data["agent_infos"]
+        batch = self.engine.make_batch(samples_data["observations"], samples_data["actions"], samples_data["advantages"],
+                                       agent_infos["mean"], agent_infos["log_std"], valid=samples_data.get("valids"),
+                                       n_global=samples_data.get("n_valid_global"))
+        eng, comm = self.engine, self.comm
+        reduce_ = (lambda t: comm.allreduce_sum_(t)) if (comm.world > 1 or comm.always_reduce) else (lambda t: t)
+        with self.timers.phase('policy_opt'):
+            lk_before = reduce_(eng.loss_kl(batch))                              # [unclipped surrogate, mean KL] at the entry theta
+            losses = self.optimizer.optimize(eng, batch, self.clip_lr, self.entropy_bonus_coeff, comm=comm)
+            lk_after = reduce_(eng.loss_kl(batch))
+            loss_after = self.optimizer.loss(eng, batch, self.clip_lr, self.entropy_bonus_coeff, comm=comm)
+        if hasattr(self.sampler, 'finish_baseline_fit') and not getattr(self, 'defer_baseline_fit', False):
+            self.sampler.finish_baseline_fit()
+        loss_before = losses[:1] if len(losses) else loss_after
+        return dict(LossBefore=loss_before, LossAfter=loss_after, MeanKLBefore=lk_before[1:2], MeanKL=lk_after[1:2], UnclippedSurrLoss=lk_after[:1])
 
     def get_itr_snapshot(self, itr, samples_data):
         return dict(itr=itr, policy=self.policy, baseline=self.baseline, env=self.env)

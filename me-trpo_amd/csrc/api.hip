@@ -513,6 +513,22 @@ extern "C" int32_t metrpo_vpg_update(metrpo_ctx* c, const metrpo_batch* b, const
     if (c->upd_pending) return set_err(c, METRPO_ESTATE, "vpg_update: a TRPO update is still open (metrpo_trpo_update_end first)");
     return run_vpg_update(c, b, pr, d_loss, (hipStream_t)stream);
 }
+// algos/ppo.py:107-119 (lr, ent, clipped_lr, clipped_surr_loss, clipped_surr_pen_loss), policy_update.hip
+extern "C" int32_t metrpo_ppo_loss_grad(metrpo_ctx* c, const metrpo_batch* b, const metrpo_ppo_params* pr, double* out, void* stream) {
+    if (!c) return METRPO_ENULL;
+    if (!pr) return set_err(c, METRPO_ENULL, "ppo_loss_grad: params NULL");
+    if (!out) return set_err(c, METRPO_ENULL, "ppo_loss_grad: out NULL");
+    NEED_POL(c);
+    return launch_ppo_loss_grad(c, b, pr, out, (hipStream_t)stream);
+}
+// algos/ppo.py:157-177 (optimize_policy: optimizer.optimize on the inputs of :158-165); the optimiser of ppo.py:61-62 as include/metrpo.h states it
+extern "C" int32_t metrpo_ppo_update(metrpo_ctx* c, const metrpo_batch* b, const metrpo_ppo_params* pr, int32_t n_epochs, double* d_losses, void* stream) {
+    if (!c) return METRPO_ENULL;
+    if (!pr) return set_err(c, METRPO_ENULL, "ppo_update: params NULL");
+    NEED_POL(c);
+    if (c->upd_pending) return set_err(c, METRPO_ESTATE, "ppo_update: a TRPO update is still open (metrpo_trpo_update_end first)");
+    return run_ppo_update(c, b, pr, n_epochs, d_losses, (hipStream_t)stream);
+}
 // model_based_rl.py:391-398 (ScipyOptimizerInterface, method='L-BFGS-B') and :1197-1202 (the 'l-bfgs' branch), lbfgs.hip
 static int lbfgs_opts_check(metrpo_ctx* c, const metrpo_lbfgs_opts* o, const char* who) {
     if (!o) return set_err(c, METRPO_ENULL, std::string(who) + ": opts NULL");

@@ -17,6 +17,17 @@ __device__ __forceinline__ void tf_adam_elem(float g, float* theta, float* am, f
     theta[i] = theta[i] - lr_t * m1 / (sqrtf(v1) + eps);
 }
 
+// PPO's head (ppo.py:112-117) for one sample with likelihood ratio lr and advantage adv: min(lr adv, clip(lr, lo, hi) adv) -> *surr, and the
+// sample's weight d surr / d logli: lr adv on the unclipped branch (tf.minimum: a tie goes to its first argument), 0 on the clipped one
+// (tf.clip_by_value passes no gradient outside the bounds).
+__device__ __forceinline__ float ppo_gate(float lr, float adv, float lo, float hi, float* surr) {
+    const float un = lr * adv, cl = fminf(fmaxf(lr, lo), hi) * adv;
+    const bool pass = un <= cl;
+    *surr = pass ? un : cl;
+    return pass ? un : 0.0f;
+}
+#define ENTROPY_CONST 1.4189385332046727f    // 0.5 (1 + log(2 pi)): DiagonalGaussian.entropy_sym's constant per action dim
+
 // tanh(x) = 1 - 2 / (1 + exp(2x)) in 5 VALU ops (v_mul, v_exp_f32, v_add, v_rcp_f32, v_fma): absolute error
 // <= ~2e-7 everywhere (exact saturation to +-1); libm's tanhf costs ~40 ops and sat on every kernel's critical path.
 __device__ __forceinline__ float tanh_fast(float x) {

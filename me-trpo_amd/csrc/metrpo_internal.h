@@ -226,7 +226,10 @@ static inline RolloutK make_rollout_k(const metrpo_rollout_args* a) {
 
 struct PolK {
     const float* obs; const float* act; const float* adv; const float* old_mean; const float* old_ls;
-    int ls_stride; const uint8_t* valid; long long N; float inv_n;
+    int ls_stride;
+    float clip_lo;           // OP_PPO: the clip bounds 1 - c and 1 + c (ppo.py:112).  The two floats sit where the struct had alignment padding, so every
+    const uint8_t* valid; long long N; float inv_n;
+    float clip_hi;           // other member keeps its offset and the other instantiations their argument layout
     const float* gm;         // non-NULL: VJP mode of the gradient kernels (bptt.hip): d objective / d mean [N][na] supplied, no loss terms
     const int* img_map;      // policy_mfma.hip: gather map of the LDS weight-fragment image (built once per ctx on the host)
     const double* skip;      // non-NULL: a line-search trial that leaves at once when skip[0] >= 0 (the search already stopped: CgTail::ls)
@@ -243,6 +246,8 @@ enum UpdOp {
     OP_LOSSKL = 2,    // loss + KL at a trial theta (line search)
     OP_FVPC = 3,      // policy_mfma.hip only, chosen by its launcher: OP_FVP on the activations the gradient kernel cached
     OP_VPG = 4,       // OP_GRAD with the VPG surrogate's head (algos/vpg.py: ratio 1, loss = -mean(logli * adv))
+    OP_PPO = 5,       // OP_GRAD with PPO's clipped head (algos/ppo.py:107-117): loss = -mean(min(lr adv, clip(lr) adv)), a clipped sample carries no gradient;
+                      // block 0 also leaves the entropy sum(ls) + na/2 (1 + log 2 pi) of the entry theta in column P+1 of its partial row (ppo_entropy_term)
 };
 // What the enclosing solve lets a launch rely on; run_trpo_update / run_vpg_update build one on their stack, every launch outside a solve passes the all-off default.
 struct SolveScope {
@@ -261,6 +266,8 @@ struct UpdCall {
     double* out;
     const CgTail* tail;      // step fused into the reduction's tail, or NULL
     const AdamTail* adam;    // k_finalize only: Adam step on the reduced gradient, or NULL
+    double ent_coeff;        // OP_PPO: entropy_bonus_coeff (ppo.py:119), applied where the gradient is reduced
+    bool ent_in_reduction;   // OP_PPO: k_finalize adds the entropy term (false: a stand-alone k_ppo_step does, behind the ranks' sum)
     SolveScope scope;
 };
 
@@ -336,6 +343,9 @@ int launch_loss_grad(metrpo_ctx*, const metrpo_batch*, double*, hipStream_t, con
 // 'vpg' policy update (algos/vpg.py): the gradient kernels of every update family in their OP_VPG instantiation
 int launch_vpg_loss_grad(metrpo_ctx*, const metrpo_batch*, double* out, hipStream_t);
 int run_vpg_update(metrpo_ctx*, const metrpo_batch*, const metrpo_vpg_params*, double* d_loss, hipStream_t);
+// 'ppo' policy update (algos/ppo.py): the OP_PPO instantiations, the entropy term in the reduction, n_epochs Adam steps with the old distribution fixed
+int launch_ppo_loss_grad(metrpo_ctx*, const metrpo_batch*, const metrpo_ppo_params*, double* out, hipStream_t);
+int run_ppo_update(metrpo_ctx*, const metrpo_batch*, const metrpo_ppo_params*, int n_epochs, double* d_losses, hipStream_t);
 // 'l-bfgs' policy update (lbfgs.hip): the reverse-communication L-BFGS-B core and the BPTT-driven minimisation
 int lbfgs_begin(metrpo_ctx*, int n, const double* x0, const float* x0_f32, const metrpo_lbfgs_opts*, double* x_eval, hipStream_t);
 int lbfgs_iterate(metrpo_ctx*, const double* f, const double* g, double* x_eval, int32_t* task, hipStream_t);

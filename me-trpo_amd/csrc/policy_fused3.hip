@@ -27,7 +27,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 struct F3K {                    // kernel arguments
     const float* obs; const float* act; const float* adv; const float* old_mean; const float* old_ls; int ls_stride;
-    const uint8_t* valid; long long N; float inv_n; const double* skip;
+    float clip_lo;              // OP_PPO: 1 - c and 1 + c (ppo.py:112); the two floats sit where the struct had alignment padding: no other member moves
+    const uint8_t* valid; long long N; float inv_n;
+    float clip_hi;
+    const double* skip;
     const float* theta; const float* v;
     const float* img;           // fragment tables (k_f3_image)
     f32x4* hc; f32x4* u;        // activation cache / mean-adjoint: [tile][block][64 lanes] 16-byte words in the MFMA D layout
@@ -165,7 +168,8 @@ template <class S> __device__ __forceinline__ void fix_xb(float (&xb)[S::KS0], i
     for (int s = 0; s < S::KS0; ++s) if (4 * s + 3 >= S::D0) { const int f = 4 * s + q; if (f == S::D0) xb[s] = 1.0f; else if (f > S::D0) xb[s] = 0.f; }
 }
 
-// MODE of k_f3_fwd: OP_GRAD, OP_LOSSKL, OP_VPG of UpdOp (metrpo_internal.h), and the forward pass that only fills the activation cache for a Fisher-vector product
+// MODE of k_f3_fwd: OP_GRAD, OP_LOSSKL, OP_VPG, OP_PPO (the gradient mode with ppo.py:112-117's clipped head, ppo_gate; block 0 leaves the entropy of theta in
+// column P+1) of UpdOp (metrpo_internal.h), and the forward pass that only fills the activation cache for a Fisher-vector product
 // whose gradient launch was not kept.  That one is no UpdOp: a file-local constant, whose value 3 is part of the kernel's mangled name.
 constexpr int F3_FILL_CACHE = 3;
 enum { IMG_WHAT_F = 1, IMG_WHAT_V = 2, IMG_WHAT_B = 4 };
@@ -205,8 +209,8 @@ __global__ void __launch_bounds__(256) k_f3_image(F3K k, float* __restrict__ img
 // forward + head
 template <class S, int MODE_, int NW>
 __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
-    constexpr bool VPG = (MODE_ == OP_VPG);
-    constexpr int MODE = VPG ? OP_GRAD : MODE_;
+    constexpr bool VPG = (MODE_ == OP_VPG), PPO = (MODE_ == OP_PPO);
+    constexpr int MODE = (VPG || PPO) ? OP_GRAD : MODE_;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), c = lane & 15, q = lane >> 4;
     if (MODE == OP_LOSSKL && k.skip != nullptr && k.skip[0] >= 0.0) return;        // speculative line-search trial after the search stopped
@@ -309,8 +313,10 @@ __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
                 }
             }
         llr = xsum_q3(llr);                                 // the four q-lanes of sample c hold its action dims between them
-        const float la = ok ? (VPG ? in.adv : expf(llr) * in.adv) : 0.f;     // lr * adv (VPG: ratio 1)
-        if (q == 0) acc0 -= (VPG ? (llr - S::D4 * HALF_LOG_2PI) * la : la) * k.inv_n;   // surr_loss = -mean(lr * adv) | -mean(logli * adv), once per sample
+        float la, surr;                                     // lr * adv (VPG: ratio 1; PPO: 0 on the clipped branch) | the sample's loss term
+        if constexpr (PPO) { la = ppo_gate(expf(llr), in.adv, k.clip_lo, k.clip_hi, &surr); if (!ok) { la = 0.f; surr = 0.f; } }
+        else { la = ok ? (VPG ? in.adv : expf(llr) * in.adv) : 0.f; surr = VPG ? (llr - S::D4 * HALF_LOG_2PI) * la : la; }
+        if (q == 0) acc0 -= surr * k.inv_n;                 // surr_loss = -mean(lr * adv) | -mean(logli * adv) | clipped_surr_loss (ppo.py:115), once per sample
         if (MODE == OP_LOSSKL) { acc1 += kl * k.inv_n; continue; }
         const float w = -la * k.inv_n;
         f32x4* __restrict__ uw = k.u + (size_t)tile * S::CB4 * 64 + lane;
@@ -326,6 +332,16 @@ __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
         }
     }
     if (MODE == F3_FILL_CACHE) return;
+    if (PPO) {                                              // entropy_sym of the entry theta (ppo.py:109): the four c = 0 lanes hold every action dim's log_std once
+        acc1 = 0.f;
+        if (blockIdx.x == 0 && wave == 0 && c == 0) {
+            acc1 = (q == 0) ? S::D4 * ENTROPY_CONST : 0.f;
+#pragma unroll
+            for (int cb = 0; cb < S::CB4; ++cb)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) if (16 * cb + 4 * q + r < S::D4) acc1 += ls[cb][r];
+        }
+    }
     // ---- per-block sums -> columns [ls_off, ls_off + D4) and P, P+1, P+2 of this block's partial row (fixed order over the waves)
     __syncthreads();
     float* red = lds;                                       // [NW][3 + P4]
@@ -690,7 +706,13 @@ int policy_f3_launch(metrpo_ctx* c, const UpdCall& u, float* partials, int nbloc
         HIP_TRY(c, hipGetLastError());
         return METRPO_OK;
     }
-    if (u.op == OP_VPG) {
+    if (u.op == OP_PPO) {
+        k.clip_lo = b.clip_lo; k.clip_hi = b.clip_hi;
+        build_image(IMG_WHAT_F | IMG_WHAT_B); c->f3_img_ok = 1;
+        if ((rc = f3_attr(c, k_f3_fwd<S, OP_PPO, FWD_NW>, sh_fwd))) return rc;
+        hipLaunchKernelGGL((k_f3_fwd<S, OP_PPO, FWD_NW>), g, dim3(FWD_NW * 64), sh_fwd, st, k);
+        c->f3_rows = -1;                                    // (theta moves between the epochs: nothing to keep)
+    } else if (u.op == OP_VPG) {
         build_image(IMG_WHAT_F | IMG_WHAT_B); c->f3_img_ok = 1;
         if ((rc = f3_attr(c, k_f3_fwd<S, OP_VPG, FWD_NW>, sh_fwd))) return rc;
         hipLaunchKernelGGL((k_f3_fwd<S, OP_VPG, FWD_NW>), g, dim3(FWD_NW * 64), sh_fwd, st, k);

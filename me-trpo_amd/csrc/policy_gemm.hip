@@ -110,9 +110,12 @@ __global__ void k_pg_pad_obs(const float* __restrict__ obs, long long N, int ns,
 
 // per-sample head, gradient mode (npo.py:69,75): U = d loss / d mean, per-block partial sums of loss and d loss / d log_std
 // part row (doubles): [0] loss, [1] kl, [2] valid weight, [3 .. 3+na) dls.  VPG (OP_GRAD only): the VPG surrogate (vpg.py:88), la = adv, loss = -mean(logli * adv)
-template <bool VPG>
+// HEAD: OP_GRAD / OP_VPG / OP_PPO (the gradient mode with ppo.py:112-117's clipped head, ppo_gate; the entropy term follows the reduction: k_ppo_step).
+// HEAD = OP_GRAD and OP_VPG compile to the code k_pg_head<false> and <true> had.
+template <int HEAD>
 __global__ void __launch_bounds__(256) k_pg_head(int mode, PolK k, int na, int nap, const float* __restrict__ MU, const float* __restrict__ log_std,
                                                  float* __restrict__ U, double* __restrict__ parts) {
+    constexpr bool VPG = (HEAD == OP_VPG), PPO = (HEAD == OP_PPO);
     __shared__ double sh[16];
     double acc[35];
     for (int i = 0; i < 3 + na; ++i) acc[i] = 0.0;
@@ -149,8 +152,15 @@ __global__ void __launch_bounds__(256) k_pg_head(int mode, PolK k, int na, int n
             zz[d] = z;
             if (mode == OP_LOSSKL) { const float s2 = expf(2.0f * ls), os2 = expf(2.0f * ols), dm = omu - mu; kl += (dm * dm + os2 - s2) / (2.0f * s2 + KL_EPS) + ls - ols; }
         }
-        const float la = ok ? (VPG ? k.adv[n] : expf(llr) * k.adv[n]) : 0.0f;   // lr * adv (VPG: ratio 1)
-        acc[0] -= VPG ? (double)((llr - na * HALF_LOG_2PI) * la * k.inv_n) : (double)(la * k.inv_n);   // surr_loss = -mean(lr * adv) | -mean(logli * adv)
+        float la;                                            // lr * adv (VPG: ratio 1; PPO: 0 on the clipped branch)
+        if constexpr (PPO) {
+            float surr = 0.0f;
+            la = ok ? ppo_gate(expf(llr), k.adv[n], k.clip_lo, k.clip_hi, &surr) : 0.0f;
+            acc[0] -= (double)(surr * k.inv_n);              // clipped_surr_loss (ppo.py:115-117)
+        } else {
+            la = ok ? (VPG ? k.adv[n] : expf(llr) * k.adv[n]) : 0.0f;
+            acc[0] -= VPG ? (double)((llr - na * HALF_LOG_2PI) * la * k.inv_n) : (double)(la * k.inv_n);   // surr_loss = -mean(lr * adv) | -mean(logli * adv)
+        }
         if (mode == OP_LOSSKL) { acc[1] += (double)(kl * k.inv_n); continue; }
         const float w = -la * k.inv_n;
         for (int d = 0; d < nap; ++d) {
@@ -271,14 +281,15 @@ static int pg_ensure(metrpo_ctx* c, const PgLay& g, long long N, PgBufs* B) {
     return METRPO_OK;
 }
 
-// OP_GRAD (+ VJP when u.k.gm), OP_FVP, OP_LOSSKL, OP_VPG (out as OP_GRAD).  Writes u.out like k_finalize and then runs u.tail (may be NULL).
+// OP_GRAD (+ VJP when u.k.gm), OP_FVP, OP_LOSSKL, OP_VPG and OP_PPO (out as OP_GRAD; OP_PPO without the entropy term: k_ppo_step, policy_update.hip).  Writes u.out like k_finalize and then runs u.tail (may be NULL).
 int policy_gemm_run(metrpo_ctx* c, const UpdCall& u, hipStream_t st) {
     const ProblemDesc& pd = c->pd;
     const PolK& k = u.k;
     const long long N = k.N;
     if (N > 2000000000LL) return set_err(c, METRPO_EUNSUPPORTED, "policy_gemm: N too large");
     const bool vpg = (u.op == OP_VPG);                       // the gradient mode with the VPG head
-    const int mode = vpg ? OP_GRAD : u.op;
+    const bool ppo = (u.op == OP_PPO);                       // ... with PPO's clipped head
+    const int mode = (vpg || ppo) ? OP_GRAD : u.op;
     const float* theta = u.theta;
     const bool cache = u.scope.cache_activations;
     const PgLay g = pg_layout(pd, N);
@@ -336,8 +347,9 @@ int policy_gemm_run(metrpo_ctx* c, const UpdCall& u, hipStream_t st) {
     const bool head_elem = (mode == OP_FVP && k.gm == nullptr);
     const int nblk = head_elem ? (int)std::min<long long>(1024, (N * nap + 2047) / 2048) : (int)std::min<long long>(1024, (N + 255) / 256);
     if (head_elem) hipLaunchKernelGGL(k_pg_head_fvp, dim3(nblk), dim3(256), 0, st, k, na, nap, MU, theta + pd.pol.n_params, U, B.hparts);
-    else if (vpg) hipLaunchKernelGGL(k_pg_head<true>, dim3(nblk), dim3(256), 0, st, mode, k, na, nap, MU, theta + pd.pol.n_params, U, B.hparts);
-    else hipLaunchKernelGGL(k_pg_head<false>, dim3(nblk), dim3(256), 0, st, mode, k, na, nap, MU, theta + pd.pol.n_params, U, B.hparts);
+    else if (ppo) hipLaunchKernelGGL(k_pg_head<OP_PPO>, dim3(nblk), dim3(256), 0, st, mode, k, na, nap, MU, theta + pd.pol.n_params, U, B.hparts);
+    else if (vpg) hipLaunchKernelGGL(k_pg_head<OP_VPG>, dim3(nblk), dim3(256), 0, st, mode, k, na, nap, MU, theta + pd.pol.n_params, U, B.hparts);
+    else hipLaunchKernelGGL(k_pg_head<OP_GRAD>, dim3(nblk), dim3(256), 0, st, mode, k, na, nap, MU, theta + pd.pol.n_params, U, B.hparts);
     if (mode != OP_LOSSKL) {
         // back-prop D_l = (D_{l+1} W_l^T) * (1 - H_l^2), l = L-1 .. 1
         for (long long r0 = 0; r0 < N; r0 += CH) {

@@ -84,6 +84,8 @@ __device__ __forceinline__ float xsum_c(float v) {
 // MODE template arguments: UpdOp (metrpo_internal.h)
 // OP_VPG: the gradient kernel with the VPG surrogate's head (algos/vpg.py:88): la = adv (ratio 1), loss = -mean(logli * adv); the old
 // distribution is not read.  Everything else is OP_GRAD's code.
+// OP_PPO: the gradient kernel with PPO's clipped head (algos/ppo.py:112-117, ppo_gate): a sample on the clipped branch carries no gradient; the clip
+// bounds are PolK::clip_lo / clip_hi.  Block 0 leaves the entropy of the theta it read in column P+1 of its partial row (ppo_entropy_term).
 // (Measured and parked, tools/experiments/policy_mfma_with_cgp.hip + profiles/r05_update_levers.txt: issue priorities per SIMD wave pair (POL_PRIO), h0 recomputed instead of
 // cached (POL_H0R, +4.8 us per product), weight-gradient products deferred into the next tile's vector stretch (POL_DEFER_S7, 60.5 vs 59.8 us), the CG solve as one launch.)
 // OP_FVPC: Fisher-vector product with the hidden activations h0, h1 = tanh(.) read from the cache the gradient kernel of the
@@ -107,8 +109,8 @@ struct PolImg {
 template <int NS, int NA, int PH, int MODE_>
 __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict__ theta, const float* __restrict__ v, float* __restrict__ partials) {
     using I = PolImg<NS, NA, PH>;
-    constexpr bool CACHED = (MODE_ == OP_FVPC), VPG = (MODE_ == OP_VPG);
-    constexpr int MODE = CACHED ? OP_FVP : VPG ? OP_GRAD : MODE_;
+    constexpr bool CACHED = (MODE_ == OP_FVPC), VPG = (MODE_ == OP_VPG), PPO = (MODE_ == OP_PPO);
+    constexpr int MODE = CACHED ? OP_FVP : (VPG || PPO) ? OP_GRAD : MODE_;
     constexpr int NS_KS = I::NS_KS, NSI = cdiv_(NS, 16), HB = I::HB, KK = I::KK;
     constexpr int pW0 = 0, pb0 = NS * PH, pW1 = pb0 + PH, pb1 = pW1 + PH * PH, pW2 = pb1 + PH, pb2 = pW2 + PH * NA,
                   pLS = pb2 + NA, P = pLS + NA, ROW = P + PART_EXTRA;
@@ -464,8 +466,10 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
                 }
             }
             llr = xsum_q(llr);                              // sum over action dims held by the 4 q-lanes of sample c
-            const float la = ok ? (VPG ? in.adv : expf(llr) * in.adv) : 0.f;         // lr * adv (VPG: ratio 1)
-            if (q == 0) acc0 -= (VPG ? (llr - NA * HALF_LOG_2PI) * la : la) * k.inv_n;   // surr_loss = -mean(lr*adv) (npo.py:75) | -mean(logli*adv) (vpg.py:88)
+            float la, surr;                                 // lr * adv (VPG: ratio 1; PPO: 0 on the clipped branch) | the sample's loss term
+            if constexpr (PPO) { la = ppo_gate(expf(llr), in.adv, k.clip_lo, k.clip_hi, &surr); if (!ok) { la = 0.f; surr = 0.f; } }
+            else { la = ok ? (VPG ? in.adv : expf(llr) * in.adv) : 0.f; surr = VPG ? (llr - NA * HALF_LOG_2PI) * la : la; }
+            if (q == 0) acc0 -= surr * k.inv_n;             // surr_loss = -mean(lr*adv) (npo.py:75) | -mean(logli*adv) (vpg.py:88) | clipped_surr_loss (ppo.py:115)
             if (MODE == OP_LOSSKL) { acc1 += kl * k.inv_n; continue; }
             const float w = -la * k.inv_n;
 #pragma unroll
@@ -667,6 +671,14 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
             }
         }
     }
+    if (PPO) {                                              // entropy_sym of the entry theta (ppo.py:109): one lane per q holds its four action dims' log_std
+        acc1 = 0.f;
+        if (blockIdx.x == 0 && wave == 0 && c == 0) {
+            acc1 = (q == 0) ? NA * ENTROPY_CONST : 0.f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) if (4 * q + r < NA) acc1 += ls[r];
+        }
+    }
     {
         const float a0 = xsum_c(xsum_q(acc0)), a1 = xsum_c(xsum_q(acc1)), aw = xsum_c(xsum_q(accw));
         if (lane == 0) { row[P] = a0; row[P + 1] = a1; row[P + 2] = aw; }
@@ -723,7 +735,7 @@ static void pol_image_map(std::vector<int>& map) {
 
 // -------------------------------------------------------------------------------------------------
 typedef void (*pol_kernel_t)(PolK, const float*, const float*, float*);
-struct PolEntry { int ns, na, ph; pol_kernel_t kern[5] /* indexed by UpdOp */; int lds_floats, lds_floats_eval; void (*build_map)(std::vector<int>&); };
+struct PolEntry { int ns, na, ph; pol_kernel_t kern[6] /* indexed by UpdOp */; int lds_floats, lds_floats_eval; void (*build_map)(std::vector<int>&); };
 template <int NS, int NA, int PH> constexpr int pol_lds() {
     constexpr int HB = cdiv_(PH, 16);
     constexpr int a = PolImg<NS, NA, PH>::TOTAL + NWAVES * (3 * HB + (NA <= 2 ? 0 : 1)) * 16 * 20;      // 20 = TS of the kernel's transpose tiles
@@ -736,7 +748,7 @@ template <int NS, int NA, int PH> constexpr int pol_lds_eval() {       // OP_LOS
     constexpr int a = PolImg<NS, NA, PH>::TOTAL, b = NWAVES * (P + PART_EXTRA);
     return a > b ? a : b;
 }
-#define PENTRY(NS, NA, PH) {NS, NA, PH, {k_policy_mfma<NS, NA, PH, OP_GRAD>, k_policy_mfma<NS, NA, PH, OP_FVP>, k_policy_mfma<NS, NA, PH, OP_LOSSKL>, k_policy_mfma<NS, NA, PH, OP_FVPC>, k_policy_mfma<NS, NA, PH, OP_VPG>}, pol_lds<NS, NA, PH>(), pol_lds_eval<NS, NA, PH>(), pol_image_map<NS, NA, PH>}
+#define PENTRY(NS, NA, PH) {NS, NA, PH, {k_policy_mfma<NS, NA, PH, OP_GRAD>, k_policy_mfma<NS, NA, PH, OP_FVP>, k_policy_mfma<NS, NA, PH, OP_LOSSKL>, k_policy_mfma<NS, NA, PH, OP_FVPC>, k_policy_mfma<NS, NA, PH, OP_VPG>, k_policy_mfma<NS, NA, PH, OP_PPO>}, pol_lds<NS, NA, PH>(), pol_lds_eval<NS, NA, PH>(), pol_image_map<NS, NA, PH>}
 static const PolEntry kPol[] = {
     PENTRY(10, 2, 32),    // swimmer
     PENTRY(18, 6, 32),    // half-cheetah

@@ -4,8 +4,9 @@
 //   k_fvp        -- Hessian(mean_kl) . v  (Gauss-Newton form, exact at theta_old; derivation in DESIGN.md)
 //   k_loss_kl    -- surrogate loss + mean KL at a trial theta (f_loss_constraint)
 //   k_finalize   -- fixed-order (deterministic) float64 reduction of the per-block partial rows
-// and of the VPG update (algos/vpg.py:88): k_loss_grad<PT, true> (surr_obj = -mean(logli * adv), no likelihood ratio) and k_finalize<true>,
-// whose blocks apply one TF-Adam step to the columns they reduced (run_vpg_update).
+// and of the VPG update (algos/vpg.py:88): k_loss_grad<PT, OP_VPG> (surr_obj = -mean(logli * adv), no likelihood ratio) and k_finalize<true, false>,
+// whose blocks apply one TF-Adam step to the columns they reduced (run_vpg_update); and of the PPO update (algos/ppo.py:107-119):
+// k_loss_grad<PT, OP_PPO> (the clipped head) and k_finalize<.., true> (the entropy bonus on the reduced vector, then the same step), n_epochs times (run_ppo_update).
 //
 // Generic VALU formulation: a block of PT threads owns tiles of PT samples.  Phase A is thread-per-
 // sample (forward / tangent / back-prop in LDS columns, weights via scalar loads); phase B is
@@ -106,8 +107,11 @@ __device__ __forceinline__ void backward_accumulate(const NetDesc& net, const fl
 
 // VPG: the VPG surrogate (vpg.py:88) instead of NPO's: loss = -mean(logli * adv) with logli = DiagonalGaussian.log_likelihood_sym(act; mean,
 // log_std) = -sum(ls) - 0.5 sum(z^2) - 0.5 na log(2 pi); its gradient is NPO's at ratio 1 (la = adv).  old_mean / old_log_std are not read.
-template <int PT, bool VPG>
+// PPO (HEAD = OP_PPO): NPO's ratio through ppo_gate (ppo.py:112-117); block 0 leaves the entropy of the entry theta in column P+1 (ppo_entropy_term).
+// HEAD = OP_GRAD and OP_VPG compile to the code k_loss_grad<PT, OP_GRAD> and <PT, true> had (only the template argument's type changed with the third head).
+template <int PT, int HEAD>
 __global__ void __launch_bounds__(PT) k_loss_grad(ProblemDesc pd, PolK k, const float* __restrict__ theta, float* __restrict__ partials) {
+    constexpr bool VPG = (HEAD == OP_VPG), PPO = (HEAD == OP_PPO);
     constexpr int PLD = PT + 1;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ double red[16];
@@ -155,9 +159,16 @@ __global__ void __launch_bounds__(PT) k_loss_grad(ProblemDesc pd, PolK k, const 
                 llr += (ols - ls) + 0.5f * (zo * zo - z * z);
             }
             const float lr = expf(llr);                          // likelihood_ratio_sym (npo.py:69)
-            const float la = lr * k.adv[n];
-            loss_acc -= (double)la * (double)k.inv_n;            // surr_loss = -mean(lr*adv) (npo.py:75)
-            w = -la * k.inv_n;
+            if constexpr (PPO) {
+                float surr;
+                const float la = ppo_gate(lr, k.adv[n], k.clip_lo, k.clip_hi, &surr);
+                loss_acc -= (double)surr * (double)k.inv_n;      // clipped_surr_loss (ppo.py:115-117)
+                w = -la * k.inv_n;
+            } else {
+                const float la = lr * k.adv[n];
+                loss_acc -= (double)la * (double)k.inv_n;        // surr_loss = -mean(lr*adv) (npo.py:75)
+                w = -la * k.inv_n;
+            }
         }
 #pragma unroll
         for (int d = 0; d < 32; ++d) {
@@ -177,6 +188,11 @@ __global__ void __launch_bounds__(PT) k_loss_grad(ProblemDesc pd, PolK k, const 
     for (int d = 0; d < na; ++d) {
         const double s = block_sum((double)dls_acc[d], red);
         if (tid == 0) part[net.n_params + d] = (raw_ls[d] > LOG_MIN_STD) ? (float)s : 0.0f;
+    }
+    if (PPO && blockIdx.x == 0 && tid == 0) {
+        float h = (float)na * ENTROPY_CONST;                     // DiagonalGaussian.entropy_sym (ppo.py:109) of the theta this launch read
+        for (int d = 0; d < na; ++d) h += fmaxf(raw_ls[d], LOG_MIN_STD);
+        part[P + 1] = h;
     }
 }
 
@@ -301,15 +317,26 @@ extern "C" int32_t metrpo_debug_fin_phases(unsigned long long* out) { return hip
 #else
 #define FT_MARK(i)
 #endif
-// k_finalize<true> (run_vpg_update, mode 0): every block applies TF-Adam (tf_adam_elem) to the theta elements of the columns it has just reduced --
+// k_finalize<true, ..> (run_vpg_update, run_ppo_update; mode 0): every block applies TF-Adam (tf_adam_elem) to the theta elements of the columns it has just reduced --
 // after adding the ranks' shares in a sharded run (each block pulls exactly the columns it pushed; no other workgroup reads them, so no arrival ticket).
-// A template variant, so that the TRPO reductions (k_finalize<false>) compile to the code they had before.
+// A template variant, so that the TRPO reductions (k_finalize<false, false>) compile to the code they had before.
 struct AdamTail {
     float* theta; float* m; float* v;           // the ctx policy and its Adam moments (metrpo_ctx::d_pol_adam)
     float lr_t, b1, b2, eps;                    // lr_t: the bias-corrected step size of this step (launch_policy_adam's)
     double* loss;                               // non-NULL: the reduced loss (column 0) is also stored here
+    double ent_coeff;                           // k_finalize<.., true> / k_ppo_step: PPO's entropy_bonus_coeff (last: the other members keep their offsets)
 };
-template <bool ADAM>
+// PPO's entropy bonus on the reduced [loss | gradient] vector (ppo.py:109, 119: - entropy_bonus_coeff * mean(entropy_sym)).  The entropy of a
+// state-independent log_std is the same for every sample, so the term is per parameter: -coeff on every unclamped log_std slot, and -coeff * H on
+// the loss, H as the gradient kernel's block 0 left it in column P+1 of partial row 0.  (Not recomputed from theta here: under ADAM other
+// workgroups of this launch are stepping the log_std slots.)  Added once, AFTER the ranks' shares are summed.
+__device__ __forceinline__ double ppo_entropy_term(const ProblemDesc& pd, int p, const float* __restrict__ partials, const float* __restrict__ theta, double coeff) {
+    if (p == 0) return -coeff * (double)partials[pd.P + 1];
+    return (p - 1 >= pd.pol.n_params && theta[p - 1] > LOG_MIN_STD) ? -coeff : 0.0;
+}
+// ENT (mode 0 only): ppo_entropy_term with AdamTail::ent_coeff is added to each reduced element before it is stored / stepped.  k_finalize<false, false>
+// and <true, false> compile to the code k_finalize<false> and <true> had.
+template <bool ADAM, bool ENT>
 __global__ void __launch_bounds__(1024) k_finalize(ProblemDesc pd, int mode, int nrows, int stride, int lk_col,
                                                    const float* __restrict__ partials, const float* __restrict__ theta,
                                                    const double* __restrict__ v, double* __restrict__ out, CgTail tail, XchgK xc, AdamTail ad) {
@@ -360,6 +387,7 @@ __global__ void __launch_bounds__(1024) k_finalize(ProblemDesc pd, int mode, int
         }
         if (ADAM) {
             if (xc.world > 1) { xchg_push(xc, p, t); t = xchg_pull_sum(xc, p); }
+            if (ENT) t += ppo_entropy_term(pd, p, partials, ad.theta, ad.ent_coeff);   // (ad.theta[p - 1] is this thread's own element, stepped below)
             out[p] = t;
             if (p == 0) { if (ad.loss != nullptr) *ad.loss = t; }
             else tf_adam_elem((float)t, ad.theta, ad.m, ad.v, p - 1, ad.lr_t, ad.b1, ad.b2, ad.eps);
@@ -374,6 +402,7 @@ __global__ void __launch_bounds__(1024) k_finalize(ProblemDesc pd, int mode, int
 #if !defined(__gfx942__) && !defined(__gfx950__) && defined(__HIP_DEVICE_COMPILE__)
 #error "k_finalize's fence-free hand-over is written for gfx942 / gfx950 (sc1 write-through stores); other targets need fence(release, agent) before the ticket"
 #endif
+        if (ENT) t += ppo_entropy_term(pd, p, partials, theta, ad.ent_coeff);       // (launched without a tail and outside an exchange: launch_ppo_loss_grad)
         if (tail.op != 0 || xc.world > 1) __hip_atomic_store(out + p, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else out[p] = t;
         if (xc.world > 1) xchg_push(xc, p, t);                // sharded run: this rank's share goes straight into every rank's receive slot
@@ -415,20 +444,28 @@ static int ensure_partials(metrpo_ctx* c, int nrows) {
 }
 
 // the descriptor of `op` on batch b at the context's theta, everything else off; validates what the operation reads
-// (OP_FVP: no targets; OP_VPG: the VPG surrogate reads no old distribution -- d_old_mean / d_old_log_std may be NULL)
-static int make_call(metrpo_ctx* c, UpdOp op, const metrpo_batch* b, UpdCall* u) {
+// (OP_FVP: no targets; OP_VPG: the VPG surrogate reads no old distribution -- d_old_mean / d_old_log_std may be NULL; OP_PPO: pr carries the clip)
+static int make_call(metrpo_ctx* c, UpdOp op, const metrpo_batch* b, UpdCall* u, const metrpo_ppo_params* pr = nullptr) {
     const bool vpg = (op == OP_VPG);
     if (!b || !b->d_obs) return set_err(c, METRPO_ENULL, "batch/d_obs is NULL");
     if (b->N <= 0) return set_err(c, METRPO_EINVAL, "batch N must be positive");
     if (c->pd.na > 32) return set_err(c, METRPO_EUNSUPPORTED, "na > 32");
+    if (op == OP_PPO) {
+        if (!pr) return set_err(c, METRPO_ENULL, "ppo: params NULL");
+        if (!b->d_old_mean || !b->d_old_log_std)
+            return set_err(c, METRPO_EINVAL, "ppo: the PPO surrogate needs the old distribution (batch d_old_mean / d_old_log_std is NULL)");
+        if (!(pr->clip_lr >= 0.0) || !std::isfinite(pr->entropy_bonus_coeff))
+            return set_err(c, METRPO_EINVAL, "ppo: need clip_lr >= 0 and a finite entropy_bonus_coeff");
+    }
     if (op != OP_FVP && (!b->d_act || !b->d_adv || (!vpg && (!b->d_old_mean || !b->d_old_log_std))))
         return set_err(c, METRPO_ENULL, "batch pointer is NULL");
-    if (vpg && !(b->inv_n_global > 0.0)) return set_err(c, METRPO_EINVAL, "batch inv_n_global must be positive");
+    if ((vpg || op == OP_PPO) && !(b->inv_n_global > 0.0)) return set_err(c, METRPO_EINVAL, "batch inv_n_global must be positive");
     *u = UpdCall{};
     u->op = op; u->theta = c->d_theta.p;
     PolK& k = u->k;
     k.obs = b->d_obs; k.act = b->d_act; k.adv = b->d_adv; k.old_mean = b->d_old_mean; k.old_ls = b->d_old_log_std;
     k.ls_stride = b->old_log_std_stride; k.valid = b->d_valid; k.N = b->N; k.inv_n = (float)b->inv_n_global;
+    if (op == OP_PPO) { k.clip_lo = (float)(1.0 - pr->clip_lr); k.clip_hi = (float)(1.0 + pr->clip_lr); u->ent_coeff = pr->entropy_bonus_coeff; u->ent_in_reduction = true; }
     return METRPO_OK;
 }
 
@@ -441,11 +478,20 @@ static void finalize(metrpo_ctx* c, const UpdCall& u, const PartRows& r, hipStre
     CgTail none; none.op = 0; none.ticket = c->d_ticket.p; none.vpos = nullptr; none.imgval = nullptr; none.ls = nullptr; none.pub_dst = nullptr;
     // inside a fused update of a sharded run the reduction carries the cross-rank sum in its tail
     const XchgK xc = (u.scope.exchange_in_tail && c->xg_world > 1) ? xchg_next(c) : xchg_none();
-    if (u.adam)
-        hipLaunchKernelGGL(k_finalize<true>, dim3((nout + FIN_C - 1) / FIN_C), dim3(1024), 0, st, c->pd, mode, r.nrows, r.stride, r.lk_col,
+    const dim3 grid((nout + FIN_C - 1) / FIN_C);
+    if (u.op == OP_PPO && u.adam)
+        hipLaunchKernelGGL((k_finalize<true, true>), grid, dim3(1024), 0, st, c->pd, mode, r.nrows, r.stride, r.lk_col,
+                           c->d_partials.p, c->d_theta.p, u.v64, u.out, none, xc, *u.adam);
+    else if (u.op == OP_PPO && u.ent_in_reduction) {
+        AdamTail ent = {}; ent.ent_coeff = u.ent_coeff;
+        hipLaunchKernelGGL((k_finalize<false, true>), grid, dim3(1024), 0, st, c->pd, mode, r.nrows, r.stride, r.lk_col,
+                           c->d_partials.p, c->d_theta.p, u.v64, u.out, none, xc, ent);
+    }
+    else if (u.adam)
+        hipLaunchKernelGGL((k_finalize<true, false>), dim3((nout + FIN_C - 1) / FIN_C), dim3(1024), 0, st, c->pd, mode, r.nrows, r.stride, r.lk_col,
                            c->d_partials.p, c->d_theta.p, u.v64, u.out, none, xc, *u.adam);
     else
-        hipLaunchKernelGGL(k_finalize<false>, dim3((nout + FIN_C - 1) / FIN_C), dim3(1024), 0, st, c->pd, mode, r.nrows, r.stride, r.lk_col,
+        hipLaunchKernelGGL((k_finalize<false, false>), dim3((nout + FIN_C - 1) / FIN_C), dim3(1024), 0, st, c->pd, mode, r.nrows, r.stride, r.lk_col,
                            c->d_partials.p, c->d_theta.p, u.v64, u.out, u.tail ? *u.tail : none, xc, AdamTail{});
 }
 
@@ -455,7 +501,7 @@ static int launch_generic(metrpo_ctx* c, const UpdCall& u, int* nrows, hipStream
     const NetDesc& net = c->pd.pol;
     const PolK& k = u.k;
     int hrows = 0; for (int l = 0; l < net.n_layers; ++l) hrows += net.dims[l];
-    size_t rows = (u.op == OP_GRAD || u.op == OP_VPG) ? hrows + c->pd.na : (u.op == OP_FVP) ? hrows + c->pd.na + (hrows - net.dims[0])
+    size_t rows = (u.op == OP_GRAD || u.op == OP_VPG || u.op == OP_PPO) ? hrows + c->pd.na : (u.op == OP_FVP) ? hrows + c->pd.na + (hrows - net.dims[0])
                                                                          : (size_t)c->pd.ns + 2 * net.max_width;
     const size_t sh = rows * (PT + 1) * sizeof(float);
     if (sh > 160 * 1024) return METRPO_EUNSUPPORTED;
@@ -464,11 +510,14 @@ static int launch_generic(metrpo_ctx* c, const UpdCall& u, int* nrows, hipStream
     int rc = ensure_partials(c, g); if (rc) return rc;
     *nrows = g;
     if (u.op == OP_GRAD) {
-        if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_loss_grad<PT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        hipLaunchKernelGGL((k_loss_grad<PT, false>), dim3(g), dim3(PT), sh, st, c->pd, k, u.theta, c->d_partials.p);
+        if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_loss_grad<PT, OP_GRAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+        hipLaunchKernelGGL((k_loss_grad<PT, OP_GRAD>), dim3(g), dim3(PT), sh, st, c->pd, k, u.theta, c->d_partials.p);
     } else if (u.op == OP_VPG) {
-        if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_loss_grad<PT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        hipLaunchKernelGGL((k_loss_grad<PT, true>), dim3(g), dim3(PT), sh, st, c->pd, k, u.theta, c->d_partials.p);
+        if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_loss_grad<PT, OP_VPG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+        hipLaunchKernelGGL((k_loss_grad<PT, OP_VPG>), dim3(g), dim3(PT), sh, st, c->pd, k, u.theta, c->d_partials.p);
+    } else if (u.op == OP_PPO) {
+        if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_loss_grad<PT, OP_PPO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+        hipLaunchKernelGGL((k_loss_grad<PT, OP_PPO>), dim3(g), dim3(PT), sh, st, c->pd, k, u.theta, c->d_partials.p);
     } else if (u.op == OP_FVP) {
         if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_fvp<PT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
         hipLaunchKernelGGL(k_fvp<PT>, dim3(g), dim3(PT), sh, st, c->pd, k, u.theta, u.vf, c->d_partials.p);
@@ -572,7 +621,7 @@ int launch_vpg_loss_grad(metrpo_ctx* c, const metrpo_batch* b, double* out, hipS
     return run_update(c, u, st);
 }
 
-// k_finalize<true>'s step as a launch of its own: behind an all-reduce that k_finalize cannot carry (RCCL, a gradient longer than an exchange slot)
+// k_finalize<true, false>'s step as a launch of its own: behind an all-reduce that k_finalize cannot carry (RCCL, a gradient longer than an exchange slot)
 // and behind the GEMM path's own reduction.  gout = [loss | gradient], summed over the ranks.
 __global__ void k_vpg_adam(const double* __restrict__ gout, int P, AdamTail ad) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -604,5 +653,71 @@ int run_vpg_update(metrpo_ctx* c, const metrpo_batch* b, const metrpo_vpg_params
     }
     HIP_TRY(c, hipGetLastError());
     c->pol_adam_t = t1;
+    return METRPO_OK;
+}
+
+// ---- 'ppo' (algos/ppo.py:107-119; the optimiser ppo.py:61-62 names but never defines is stated in include/metrpo.h: full-batch TF-Adam epochs) ----
+// The entropy term and (step) the Adam step on a reduced, rank-summed [loss | gradient] as ONE workgroup: behind the GEMM path's own reduction and behind an
+// all-reduce k_finalize cannot carry.  One workgroup so that the entropy of the entry theta is read before any log_std slot is stepped.
+__global__ void __launch_bounds__(1024) k_ppo_step(double* __restrict__ gout, int P, int n_params, int na, int step, AdamTail ad) {
+    const double coeff = ad.ent_coeff;
+    __shared__ float s_h;
+    if (threadIdx.x == 0) {
+        float h = (float)na * ENTROPY_CONST;                   // the gradient kernels' expression (OP_PPO, column P+1)
+        for (int d = 0; d < na; ++d) h += fmaxf(ad.theta[n_params + d], LOG_MIN_STD);
+        s_h = h;
+    }
+    __syncthreads();
+    for (int p = threadIdx.x; p < P + 1; p += blockDim.x) {
+        double t = gout[p];
+        if (p == 0) t += -coeff * (double)s_h;
+        else if (p - 1 >= n_params && ad.theta[p - 1] > LOG_MIN_STD) t += -coeff;
+        gout[p] = t;
+        if (p == 0) { if (ad.loss != nullptr) *ad.loss = t; }
+        else if (step) tf_adam_elem((float)t, ad.theta, ad.m, ad.v, p - 1, ad.lr_t, ad.b1, ad.b2, ad.eps);
+    }
+}
+
+int launch_ppo_loss_grad(metrpo_ctx* c, const metrpo_batch* b, const metrpo_ppo_params* pr, double* out, hipStream_t st) {
+    UpdCall u; int rc = make_call(c, OP_PPO, b, &u, pr); if (rc) return rc;
+    u.out = out;
+    if ((rc = run_update(c, u, st))) return rc;
+    if (policy_gemm_applicable(c, b->N, false)) {            // (its own reduction: the entropy term follows as a launch)
+        AdamTail ad = {}; ad.theta = c->d_theta.p; ad.ent_coeff = u.ent_coeff;
+        hipLaunchKernelGGL(k_ppo_step, dim3(1), dim3(1024), 0, st, out, c->pd.P, c->pd.pol.n_params, c->pd.na, 0, ad);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return METRPO_OK;
+}
+
+// n_epochs x (gradient kernel + reduction with the entropy term and the Adam step in its tail); the old distribution is the batch's throughout, theta moves.
+// Nothing here reads the device: the bias-corrected step sizes of all epochs are host arithmetic on the step count.
+int run_ppo_update(metrpo_ctx* c, const metrpo_batch* b, const metrpo_ppo_params* pr, int n_epochs, double* d_losses, hipStream_t st) {
+    const int P = c->pd.P;
+    if (!pr) return set_err(c, METRPO_ENULL, "ppo_update: params NULL");
+    if (n_epochs < 0) return set_err(c, METRPO_EINVAL, "ppo_update: n_epochs must be >= 0");
+    if (!(pr->lr >= 0.0) || !(pr->beta1 >= 0.0 && pr->beta1 < 1.0) || !(pr->beta2 >= 0.0 && pr->beta2 < 1.0) || !(pr->eps >= 0.0))
+        return set_err(c, METRPO_EINVAL, "ppo_update: need lr >= 0, 0 <= beta1, beta2 < 1, eps >= 0");
+    UpdCall u; int rc = make_call(c, OP_PPO, b, &u, pr); if (rc) return rc;
+    if ((rc = ensure_policy_adam(c))) return rc;
+    float* am = (float*)c->d_pol_adam.p;
+    double* gout = c->d_cg.p;                               // [1 + P] of the CG workspace (no update is open across this call)
+    const UpdFusion f = update_fusion(c, b->N, false);      // as run_vpg_update: the ranks must agree on it
+    const bool fused = f.carries_next_step();
+    u.out = gout; u.scope.exchange_in_tail = f.exchange_in_tail;
+    if (!fused) u.ent_in_reduction = false;                 // (the plain reduction k_finalize<false, false>: the stand-alone step adds the term, behind the ranks' sum)
+    for (int e = 0; e < n_epochs; ++e) {
+        const int t1 = c->pol_adam_t + 1;                   // launch_policy_adam's bias correction (bptt.hip)
+        const double lr_t = pr->lr * std::sqrt(1.0 - std::pow(pr->beta2, (double)t1)) / (1.0 - std::pow(pr->beta1, (double)t1));
+        const AdamTail ad = {c->d_theta.p, am, am + P, (float)lr_t, (float)pr->beta1, (float)pr->beta2, (float)pr->eps, d_losses ? d_losses + e : nullptr, u.ent_coeff};
+        u.adam = fused ? &ad : nullptr;
+        if ((rc = run_update(c, u, st))) return rc;
+        if (!fused) {
+            if ((c->xg_world > 1 || c->nccl_comm) && (rc = comm_allreduce_f64(c, gout, P + 1, st))) return rc;
+            hipLaunchKernelGGL(k_ppo_step, dim3(1), dim3(1024), 0, st, gout, P, c->pd.pol.n_params, c->pd.na, 1, ad);
+        }
+        HIP_TRY(c, hipGetLastError());
+        c->pol_adam_t = t1;
+    }
     return METRPO_OK;
 }

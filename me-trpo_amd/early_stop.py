@@ -69,7 +69,7 @@ def optimize_policy(algo, validation_init, T, gamma, mode='estimated', whole=Tru
     (optimize_policy_bptt; `init_pool` is then its source of reset states).  `real_cost_fn()` stands in for
     evaluate_fixed_init_trajectories on the real simulator (out of scope; None -> 0.0)."""
     from .bptt import BPTT
-    from .algos import VPG
+    from .algos import VPG, PPO
     from .lbfgs import LBFGS
     if isinstance(algo, LBFGS):
         # run_model_based_rl.py:114-117 (l_bfgs_exception, applied on every launch path): log_every = 1, max_iters = 1 -- one whole
@@ -77,7 +77,7 @@ def optimize_policy(algo, validation_init, T, gamma, mode='estimated', whole=Tru
         return optimize_policy_bptt(algo, validation_init, T, gamma, init_pool, mode=mode, whole=whole, log_every=1,
                                     num_iters_threshold=num_iters_threshold, max_iters=1, stop_fn=stop_fn, real_cost_fn=real_cost_fn,
                                     logger=logger)
-    if isinstance(algo, VPG):
+    if isinstance(algo, (VPG, PPO)):      # PPO: the same wiring (Adam state snapshotted and restored with theta, not reset at entry)
         return optimize_policy_vpg(algo, validation_init, T, gamma, mode=mode, whole=whole, log_every=log_every, num_iters_threshold=num_iters_threshold,
                                    max_iters=max_iters, stop_fn=stop_fn, reset_log_std=reset_log_std, real_cost_fn=real_cost_fn, logger=logger)
     if isinstance(algo, BPTT):
@@ -133,7 +133,9 @@ def optimize_policy_vpg(vpg, validation_init, T, gamma, mode='estimated', whole=
     """'vpg' branch of model_based_rl.py:optimize_policy (:1171-1180 with the rllab VPG): the TRPO branch's loop with three differences of the
     reference's wiring.  The Saver (:495) covers every global variable, so the snapshot (:1127 / :1291) and the restore (:1400) carry theta AND
     VPG's Adam state (m, v, t) together.  policy_adam_init is empty for non-BPTT algorithms (:398-405): the Adam state is not reset at entry and
-    carries over between calls.  trpo_mean is computed for algo == 'trpo' only (:1219-1231): its candidate is 0.0 here."""
+    carries over between calls.  trpo_mean is computed for algo == 'trpo' only (:1219-1231): its candidate is 0.0 here.
+    A PPO object (params 'algo': 'ppo', an extension: the reference's training.py has no such branch) runs this loop unchanged: its n_epochs Adam
+    steps per optimize_policy move the same state."""
     eng = vpg.engine
     stop_fn = stop_fn or stop_critereon(0.10, 1e-5, 0.30)
     if reset_log_std:

@@ -485,6 +485,33 @@ class Engine(object):
         self._chk(lib.metrpo_vpg_update(self._ctx, C.byref(batch), C.byref(p), _ptr(loss), self._stream()))
         return loss
 
+    @staticmethod
+    def _ppo_params(clip_lr, entropy_bonus_coeff, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8):
+        p = _lib.PpoParams()
+        p.clip_lr, p.entropy_bonus_coeff = float(clip_lr), float(entropy_bonus_coeff)
+        p.lr, p.beta1, p.beta2, p.eps = float(lr), float(beta1), float(beta2), float(eps)
+        return p
+
+    def ppo_loss_grad(self, batch, clip_lr=0.3, entropy_bonus_coeff=0.0):
+        """PPO's clipped surrogate with the entropy bonus (algos/ppo.py:107-119) and its gradient at the ctx policy: tensor [1 + P] float64,
+        loss_grad's layout.  The surrogate part is this rank's share; the entropy term is added whole (a host-driven all-reduce over W ranks
+        passes entropy_bonus_coeff / W)."""
+        out = torch.empty(self.P + 1, dtype=torch.float64, device=self.device)
+        p = self._ppo_params(clip_lr, entropy_bonus_coeff)
+        self._chk(lib.metrpo_ppo_loss_grad(self._ctx, C.byref(batch), C.byref(p), _ptr(out), self._stream()))
+        return out
+
+    def ppo_update(self, batch, n_epochs=10, clip_lr=0.3, entropy_bonus_coeff=0.0, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, want_losses=True):
+        """One PPO optimize_policy (ppo.py:157-177): n_epochs full-batch TF-Adam steps on ppo_loss_grad's loss, the batch's old distribution fixed
+        while theta moves; the state of get_policy_adam / set_policy_adam, not reset; summed over the ranks by the communicator attached to this
+        engine (if any).  Stream-ordered, no synchronisation and no host read between the epochs; returns the n_epochs losses at the thetas
+        entering each epoch as a float64 device tensor (None with want_losses=False)."""
+        self._close_open_update()
+        p = self._ppo_params(clip_lr, entropy_bonus_coeff, lr, beta1, beta2, eps)
+        losses = torch.empty(int(n_epochs), dtype=torch.float64, device=self.device) if want_losses else None
+        self._chk(lib.metrpo_ppo_update(self._ctx, C.byref(batch), C.byref(p), int(n_epochs), _ptr(losses), self._stream()))
+        return losses
+
     def fvp(self, batch, v):
         v = torch.as_tensor(v, device=self.device).to(torch.float64).contiguous()
         hv = torch.empty(self.P, dtype=torch.float64, device=self.device)

@@ -176,3 +176,45 @@ class ConjugateGradientOptimizer(object):
             ev.set_params(cur_param)
         return dict(loss_before=loss_before, loss=loss, kl=constraint_val, beta=float(initial_step_size),
                     n_backtrack=int(n_iter), accepted=accepted, g=flat_g, d=descent_direction)
+
+
+class AdamOptimizer(object):
+    """The optimiser algos/ppo.py:61-62 names (`AdamOptimizer()`) but never imports or defines; stated here: n_epochs full-batch
+    tf.train.AdamOptimizer steps (beta1 0.9, beta2 0.999, epsilon 1e-8, no gradient clipping) on every policy parameter including log_std.
+    The Adam state is the engine's policy optimizer state (Engine.get_policy_adam / set_policy_adam); it is never reset here, exactly as
+    FirstOrderOptimizer treats it for VPG.  Minibatches (batch_size other than None) are not built."""
+
+    def __init__(self, learning_rate=1e-3, n_epochs=10, batch_size=None, beta1=0.9, beta2=0.999, epsilon=1e-8, **kwargs):
+        if batch_size is not None:
+            raise NotImplementedError("AdamOptimizer: full-batch epochs (batch_size=None) are the setting built")
+        self.learning_rate, self.n_epochs, self.batch_size = float(learning_rate), int(n_epochs), batch_size
+        self.beta1, self.beta2, self.epsilon = float(beta1), float(beta2), float(epsilon)
+        self.last_losses = None
+        self._target = None
+
+    def update_opt(self, loss, target, inputs, diagnostic_vars=None, **kwargs):
+        self._target = target            # the loss graph itself (ppo.py:107-119) is what the HIP kernels compute
+
+    def loss(self, engine, batch, clip_lr, entropy_bonus_coeff, comm=None):
+        """ppo.py:169 / :177 optimizer.loss: the penalised clipped surrogate at the current theta, summed over the ranks (1-element tensor)."""
+        comm = comm or Comm()
+        out = engine.ppo_loss_grad(batch, clip_lr, entropy_bonus_coeff / max(1, comm.world))[:1].clone()
+        return comm.allreduce_sum_(out) if (comm.world > 1 or comm.always_reduce) else out
+
+    def optimize(self, engine, batch, clip_lr, entropy_bonus_coeff, comm=None):
+        """n_epochs Adam steps.  With a communicator attached to the engine (Comm.attach_engine) or at world size 1 the whole of it is
+        Engine.ppo_update (no host involvement between the epochs); otherwise each epoch's gradient share is all-reduced on the host (Comm,
+        e.g. gloo) and the step follows as Engine.policy_adam_step with no clipping.  -> the losses at the theta entering each epoch."""
+        comm = comm or Comm()
+        need = comm.world > 1 or comm.always_reduce
+        if need and not getattr(engine, 'comm_world', 0):
+            losses = []
+            for _ in range(self.n_epochs):
+                lg = comm.allreduce_sum_(engine.ppo_loss_grad(batch, clip_lr, entropy_bonus_coeff / comm.world))
+                engine.policy_adam_step(lg[1:], self.learning_rate, clip_val=None, beta1=self.beta1, beta2=self.beta2, eps=self.epsilon)
+                losses.append(lg[:1])
+            self.last_losses = torch.cat(losses) if losses else torch.empty(0, dtype=torch.float64, device=engine.device)
+        else:
+            self.last_losses = engine.ppo_update(batch, n_epochs=self.n_epochs, clip_lr=clip_lr, entropy_bonus_coeff=entropy_bonus_coeff,
+                                                 lr=self.learning_rate, beta1=self.beta1, beta2=self.beta2, eps=self.epsilon)
+        return self.last_losses

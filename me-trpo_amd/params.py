@@ -10,11 +10,13 @@ Keys read (params-swimmer.json:5-86):
     policy.hidden_layers
     policy_opt_params.{T, gamma, mode, whole, log_every, num_iters_threshold, max_iters, batch_size, sam_mode, learning_rate, grad_norm_clipping,
                        stop_critereon.{threshold, offset, percent_models_threshold}, trpo.{init_std, step_size, discount, batch_size, reset},
-                       vpg.{init_std, discount, batch_size, reset}}
+                       vpg.{init_std, discount, batch_size, reset},
+                       ppo.{init_std, discount, batch_size, reset, clip_lr, n_epochs, learning_rate, entropy_bonus_coeff}}
     dynamics_opt_params.{learning_rate.{scratch, refine}, batch_size, max_passes, log_every, num_passes_threshold, sample_mode, reinitialize,
                          stop_critereon.{threshold, offset}}
 'algo' builds 'trpo', 'vpg' (training.py:337-352: VPG with the vpg block's batch size, discount and log_std reset), 'bptt' and 'bptt-stochastic';
-svg and l-bfgs raise.  Everything else in the files (rollout_params, sweep_iters, sample_size, *_path) steers the reference's real-simulator data collection and outer
+svg and l-bfgs raise.  'ppo' (algos/ppo.py) is an EXTENSION: the reference's training.py has no such branch and its params files no ppo block; the
+block's defaults are ppo.py's (clip_lr 0.3, entropy_bonus_coeff 0), AdamOptimizer's (n_epochs 10, learning_rate 1e-3) and the vpg block's.  Everything else in the files (rollout_params, sweep_iters, sample_size, *_path) steers the reference's real-simulator data collection and outer
 sweeps, which are out of scope here; those keys are passed through untouched in `Setup.params`."""
 import json
 
@@ -51,11 +53,11 @@ def shapes_from_params(path_or_dict):
     if None in acts or len(acts) != len(dm['hidden_layers']):                    # training.py:156 asserts the lengths agree
         raise ValueError("dynamics_model.nonlinearity = %r: one of %s per hidden layer" % (dm.get('nonlinearity'), sorted(_ACTS)))
     n_drop = 2 if dm.get('ignore_xy_input') else (1 if dm.get('ignore_x_input') else 0)      # training.py:146-154
-    trpo, vpg = po.get('trpo', {}), po.get('vpg', {})
+    trpo, vpg, ppo = po.get('trpo', {}), po.get('vpg', {}), po.get('ppo', {})
     algo = p.get('algo', 'trpo')
     T = int(po['T'])
     # the sampler's batch comes from the block of the algorithm that runs (training.py:345 for vpg, :360 for trpo)
-    batch_size = int((vpg if algo == 'vpg' else trpo).get('batch_size', 5000))
+    batch_size = int((vpg if algo == 'vpg' else ppo if algo == 'ppo' else trpo).get('batch_size', 5000))
     n_envs = max(1, min(int(batch_size / T), 100))                                # vectorized_sampler.py:24-27
     sc = po.get('stop_critereon', {})
     dop = p.get('dynamics_opt_params', {})
@@ -71,6 +73,9 @@ def shapes_from_params(path_or_dict):
                   reset=bool(trpo.get('reset', True))),
         vpg=dict(discount=float(vpg.get('discount', 1.0)), init_std=float(vpg.get('init_std', 1.0)), batch_size=int(vpg.get('batch_size', 5000)),
                  reset=bool(vpg.get('reset', True))),
+        ppo=dict(discount=float(ppo.get('discount', 1.0)), init_std=float(ppo.get('init_std', 1.0)), batch_size=int(ppo.get('batch_size', 5000)),
+                 reset=bool(ppo.get('reset', True)), clip_lr=float(ppo.get('clip_lr', 0.3)), n_epochs=int(ppo.get('n_epochs', 10)),
+                 learning_rate=float(ppo.get('learning_rate', 1e-3)), entropy_bonus_coeff=float(ppo.get('entropy_bonus_coeff', 0.0))),
         optimize_policy=dict(T=T, gamma=float(po.get('gamma', 1.0)), mode=po.get('mode', 'estimated'), whole=bool(po.get('whole', True)),
                              log_every=int(po.get('log_every', 5)), num_iters_threshold=int(po.get('num_iters_threshold', 25)),
                              max_iters=int(po.get('max_iters', 400))),
@@ -107,14 +112,15 @@ def from_params(path_or_dict, device=0, init_states=None, comm=None, seed=0, n_e
     from .policy import GaussianMLPPolicy
     from .baseline import LinearFeatureBaseline
     from .imagined_env import NeuralNetEnv, InitStatePool
-    from .algos import TRPO, VPG
+    from .algos import TRPO, VPG, PPO
+    from .optimizer import AdamOptimizer
     from .bptt import BPTT
     p = _load(path_or_dict)
     sh = shapes_from_params(p)
-    if sh['algo'] not in ('trpo', 'vpg', 'bptt', 'bptt-stochastic'):
-        raise ValueError("params 'algo' = %r: this path builds 'trpo', 'vpg' (and the 'bptt' / 'bptt-stochastic' updates of section 8f); svg / l-bfgs "
+    if sh['algo'] not in ('trpo', 'vpg', 'ppo', 'bptt', 'bptt-stochastic'):
+        raise ValueError("params 'algo' = %r: this path builds 'trpo', 'vpg', 'ppo' (and the 'bptt' / 'bptt-stochastic' updates of section 8f); svg / l-bfgs "
                          "are not built from a params file (the 'l-bfgs' update runs as metrpo_amd.LBFGS)" % sh['algo'])
-    blk = sh['vpg'] if sh['algo'] == 'vpg' else sh['trpo']     # init_std / reset of the rllab algorithm that runs (training.py:350-352, 368-370)
+    blk = sh['vpg'] if sh['algo'] == 'vpg' else sh['ppo'] if sh['algo'] == 'ppo' else sh['trpo']     # init_std / reset of the rllab algorithm that runs (training.py:350-352, 368-370)
     eng = Engine(sh['env'], sh['K'], sh['dyn_hidden'], sh['pol_hidden'], n_drop=sh['n_drop'], dyn_act=sh['dyn_act'], device=device)
     policy = GaussianMLPPolicy(eng, init_std=blk['init_std'], seed=seed)
     baseline = LinearFeatureBaseline()
@@ -124,6 +130,10 @@ def from_params(path_or_dict, device=0, init_states=None, comm=None, seed=0, n_e
     if sh['algo'] == 'vpg':
         algo = VPG(env=env, policy=policy, baseline=baseline, batch_size=sh['batch_size'], max_path_length=sh['T'], discount=sh['vpg']['discount'],
                    sampler_args=sargs, comm=comm, seed=seed)
+    elif sh['algo'] == 'ppo':
+        algo = PPO(env=env, policy=policy, baseline=baseline, batch_size=sh['batch_size'], max_path_length=sh['T'], discount=blk['discount'],
+                   clip_lr=blk['clip_lr'], entropy_bonus_coeff=blk['entropy_bonus_coeff'],
+                   optimizer=AdamOptimizer(learning_rate=blk['learning_rate'], n_epochs=blk['n_epochs']), sampler_args=sargs, comm=comm, seed=seed)
     else:
         algo = TRPO(env=env, policy=policy, baseline=baseline, batch_size=sh['batch_size'], max_path_length=sh['T'], discount=sh['trpo']['discount'],
                     step_size=sh['trpo']['step_size'], sampler_args=sargs, comm=comm, seed=seed)
