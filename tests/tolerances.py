@@ -92,3 +92,14 @@ DYN_EVAL_LOSS = dict(rtol=5e-4, atol=1e-6)   # validation loss after training st
 # Observed 7.2e-7 rel-L2 and 1.3e-6 worst element (14 shapes, params-file 2 x 1024 and C4 3 x 1024 included).
 DYN_GRAD_REL_L2 = 1e-5
 DYN_GRAD_MAX = 1e-4
+
+# --- the rollout's own draws (Philox4x32-10 + Box-Muller, csrc/device_common.h) against their float64 restatement ------------------------------------------
+# |z_device - z_float64| of one standard normal, z_device recovered as (act - mean) / exp(log_std) from a rollout that drew for itself and z_float64
+# from tests/rollout_draws_ref.py (same fp32 uniform; logarithm, square root, sine and cosine in float64).  The words are integers and agree exactly;
+# what differs is the device's __logf / __sincosf on radii up to 6.8, plus the recovery's own rounding (act is one fp32 fma of O(1) terms).  Observed over
+# the 59 production-mode cases of tests/test_gpu_rollout_draws.py (254 862 normals, all seven kernel families): worst 1.49e-6; floor of the recovery
+# alone (parity-mode eps through the same kernels, 8 mixed-mode cases) 2.1e-7.  Bound = 4 x the worst, rounded up to one digit: the margin is for the
+# ~1e6 of 2^64 word pairs sampled.  Normals whose restated radius is below 2^-6 are left out of this one check (the logarithm's absolute error is
+# divided by r there); 41 of the 254 862 were (at most 9.7e-4 of a case, cap 1e-3), and they turned out closer than the rest: worst 1.8e-8.
+# A wrong chunk, a swapped sine / cosine or another word is off by O(1).  profiles/r09_rollout_draws.txt.
+PHILOX_NORMAL = 6e-6
