@@ -108,6 +108,15 @@ extern "C" int32_t metrpo_debug_fvp_us(metrpo_ctx* c, double* mean_us, int32_t* 
     return METRPO_OK;
 }
 
+// Diagnostics hook (not part of include/metrpo.h; tests/test_gpu_update_kernels.py): what the last policy-update launch of this context ran on, as the host wrote it down when it
+// enqueued the launch (no device work, no synchronisation).  out[7] = family (0 generic, 1 fused 2 x 32, 2 GEMM path, 3 fused 100-50-25; -1: none yet), UpdOp as launched,
+// index into the fused 2 x 32 kernel table (-1 elsewhere), sample tile PT of the generic kernels, partial rows of the reduction, splits and kchunk of the GEMM path.
+extern "C" int32_t metrpo_debug_last_update(const metrpo_ctx* c, int32_t* out) {
+    if (!c || !out) return METRPO_ENULL;
+    const auto& l = c->upd_last;
+    out[0] = l.family; out[1] = l.op; out[2] = l.table; out[3] = l.pt; out[4] = l.nrows; out[5] = l.splits; out[6] = l.kchunk;
+    return METRPO_OK;
+}
 
 // Diagnostics hook (tests/test_gpu_api.py): outgrown workspaces this context holds back instead of freeing them inside a launch entry point (metrpo_internal.h: ws_grow);
 // sweep != 0 frees them now (a synchronising call, like the sweep the library runs by itself past WS_RETIRED_MAX).  Returns the count in front of the sweep.

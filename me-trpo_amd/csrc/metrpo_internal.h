@@ -136,6 +136,10 @@ struct metrpo_ctx {
     int exclusive = 1;       // the caller's metrpo_set_exclusive value (1 at metrpo_create); 0: the GPU is shared with other compute processes.  Read through ctx_exclusive(), which also honours option NO_RESIDENT
     std::string opt_val[OPT_COUNT]; bool opt_set[OPT_COUNT] = {};   // METRPO_OPT_LIST: set by metrpo_create from the environment, then only by metrpo_set_option
     hipEvent_t fvp_ev[32] = {}; int fvp_ev_n = 0, fvp_ev_made = 0;   // option TIME_FVP: events around the Fisher-vector-product kernel of launch_fvp_tail (metrpo_debug_fvp_us)
+    // the last policy-update launch, written on the host when it is enqueued (metrpo_debug_last_update): family (0 generic, 1 fused 2 x 32, 2 GEMM path, 3 fused 100-50-25),
+    // UpdOp as launched (OP_FVPC where the fused kernel took it), index into policy_mfma.hip's table (-1 elsewhere), sample tile of the generic kernels (0 elsewhere),
+    // partial rows handed to k_finalize (0 on the GEMM path), splits / kchunk of the GEMM path's gradient GEMMs (0 elsewhere)
+    struct UpdLast { int family = -1, op = -1, table = -1, pt = 0, nrows = 0, splits = 0, kchunk = 0; } upd_last;
     std::string rollout_note;   // why the last metrpo_rollout left the fast dispatch table ("" when it did not): metrpo_rollout_note
     int fallback_logged = 0;  // a rollout shape that fell off the fast dispatch table has been reported once (METRPO_VERBOSE)
     std::vector<std::pair<void*, size_t>> ws_retired; size_t ws_retired_bytes = 0;   // outgrown workspaces and their sizes (ws_grow below): freed by metrpo_destroy, or by one sweep once they pass WS_RETIRED_MAX

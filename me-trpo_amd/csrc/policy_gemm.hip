@@ -295,6 +295,7 @@ int policy_gemm_run(metrpo_ctx* c, const UpdCall& u, hipStream_t st) {
     const PgLay g = pg_layout(pd, N);
     PgBufs B;
     int rc = pg_ensure(c, g, N, &B); if (rc) return rc;
+    c->upd_last = {2, (int)u.op, -1, 0, 0, g.splits, g.kchunk};
     const int L = g.L, na = pd.na, nap = g.dp[L];
     auto RB = [&](size_t o) { return B.rows + o * (size_t)N; };
     float* X = RB(g.oX); float* MU = RB(g.oMU); float* U = RB(g.oU);

@@ -509,6 +509,7 @@ static int launch_generic(metrpo_ctx* c, const UpdCall& u, int* nrows, hipStream
     const int g = (int)std::max<long long>(1, std::min<long long>(tiles, (long long)c->n_sm * 2));
     int rc = ensure_partials(c, g); if (rc) return rc;
     *nrows = g;
+    c->upd_last = {0, (int)u.op, -1, PT, g, 0, 0};
     if (u.op == OP_GRAD) {
         if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_loss_grad<PT, OP_GRAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
         hipLaunchKernelGGL((k_loss_grad<PT, OP_GRAD>), dim3(g), dim3(PT), sh, st, c->pd, k, u.theta, c->d_partials.p);
@@ -545,6 +546,8 @@ static PartRows run_mode(metrpo_ctx* c, const UpdCall& u, hipStream_t st) {
         const long long per_block = (mfma ? 8ll : 4ll) * std::max(1, c->upd_tiles_per_wave);
         const long long max_blocks = (long long)c->n_sm * ((mfma && u.op == OP_LOSSKL) ? 2 : 1);
         r.nrows = (int)std::max<long long>(1, std::min<long long>((tiles + per_block - 1) / per_block, max_blocks));
+        const bool fvpc = mfma && u.scope.cache_activations && u.op == OP_FVP && u.k.gm == nullptr;       // (policy_mfma_launch's choice)
+        c->upd_last = {mfma ? 1 : 3, fvpc ? (int)OP_FVPC : (int)u.op, mfma ? c->pol_mfma : -1, 0, r.nrows, 0, 0};
         if (!(r.rc = ensure_partials(c, r.nrows)))
             r.rc = mfma ? policy_mfma_launch(c, u, c->d_partials.p, r.nrows, st) : policy_f3_launch(c, u, c->d_partials.p, r.nrows, st);
         return r;

@@ -209,6 +209,16 @@ class Engine(object):
         self._chk(lib.metrpo_debug_fvp_us(self._ctx, C.byref(us), C.byref(n)))
         return float(us.value), int(n.value)
 
+    def last_update_launch(self):
+        """Diagnostics: what the last policy-update launch ran on, as the host noted it when it enqueued it: dict(family 'generic' | 'mfma' | 'gemm' |
+        'fused3' (None before the first launch), op (the UpdOp as launched: 0 gradient, 1 FVP, 2 loss + KL, 3 cached FVP, 4 VPG, 5 PPO), table (index of the
+        fused 2 x 32 kernel set, -1 elsewhere), pt (sample tile of the generic kernels), nrows (partial rows of the reduction), splits / kchunk (GEMM path))."""
+        out = (C.c_int32 * 7)()
+        self._chk(lib.metrpo_debug_last_update(self._ctx, out))
+        d = dict(zip(('family', 'op', 'table', 'pt', 'nrows', 'splits', 'kchunk'), (int(x) for x in out)))
+        d['family'] = {-1: None, 0: 'generic', 1: 'mfma', 2: 'gemm', 3: 'fused3'}[d['family']]
+        return d
+
     def retired_workspaces(self, sweep=False):
         """Diagnostics: (count, bytes) of outgrown workspaces the context keeps until destroy (a launch entry point never frees: hipFree waits for every stream);
         sweep=True frees them now (synchronising)."""

@@ -3,8 +3,8 @@ import numpy as np
 from oracle import metrpo_oracle as O
 
 
-def make_engine(env, K, dyn_hidden, pol_hidden, seed=0, n_pool=256, dyn_act='relu'):
-    import metrpo_amd
+def problem_data(env, K, dyn_hidden, pol_hidden, seed=0, n_pool=256, dyn_act='relu'):
+    """make_engine's problem without the engine (CPU only): (dm, theta, pdims, pool)."""
     dm, theta, pdims, pool = O.make_problem(env, K=K, dyn_hidden=dyn_hidden, pol_hidden=pol_hidden, seed=seed,
                                             n_pool=n_pool, dyn_act=dyn_act)
     rng = np.random.RandomState(seed + 1000)
@@ -16,10 +16,34 @@ def make_engine(env, K, dyn_hidden, pol_hidden, seed=0, n_pool=256, dyn_act='rel
     dm.diff_std = np.abs(0.1 + rng.randn(ns) * 0.02)
     theta = theta + rng.randn(theta.size) * 0.05
     theta[-na:] = rng.randn(na) * 0.2 - 0.3
+    return dm, theta, pdims, pool
+
+
+def engine_of(env, K, dyn_hidden, pol_hidden, dm, theta, dyn_act='relu'):
+    import metrpo_amd
     eng = metrpo_amd.Engine(env, K, dyn_hidden, pol_hidden, dyn_act=dyn_act)
     eng.set_dynamics_layers(dm.Ws, dm.bs, dm.in_mean, dm.in_std, dm.diff_mean, dm.diff_std)
     eng.set_policy(theta)
-    return eng, dm, theta, pdims, pool
+    return eng
+
+
+def make_engine(env, K, dyn_hidden, pol_hidden, seed=0, n_pool=256, dyn_act='relu'):
+    dm, theta, pdims, pool = problem_data(env, K, dyn_hidden, pol_hidden, seed=seed, n_pool=n_pool, dyn_act=dyn_act)
+    return engine_of(env, K, dyn_hidden, pol_hidden, dm, theta, dyn_act=dyn_act), dm, theta, pdims, pool
+
+
+def update_data(env='swimmer', N=5000, seed=21, pol_hidden=(32, 32)):
+    """The policy-update problem of tests/test_gpu_engine.py::_update_problem without the engine (CPU only): theta_old, a batch drawn from its own
+    distribution, centred advantages; everything rounded to fp32, the device's storage type.  -> (dm, th, pdims, obs, act, adv, old_mean, old_ls)"""
+    dm, theta, pdims, pool = problem_data(env, 2, (64, 64), pol_hidden, seed=seed)
+    rng = np.random.RandomState(seed)
+    th = theta.astype(np.float32).astype(np.float64)
+    obs = (rng.randn(N, dm.ns) * 0.5).astype(np.float32).astype(np.float64)
+    old_mean = O.policy_mean(th, pdims, obs).astype(np.float32).astype(np.float64)
+    old_ls = np.broadcast_to(O.policy_log_std(th, pdims), old_mean.shape).copy()
+    act = (old_mean + np.exp(old_ls) * rng.randn(*old_mean.shape)).astype(np.float32).astype(np.float64)
+    adv = O.center_advantages(rng.randn(N)).astype(np.float32).astype(np.float64)
+    return dm, th, pdims, obs, act, adv, old_mean, old_ls
 
 
 def draws(rng, K, B, T, ns, na, n_pool):

@@ -416,14 +416,8 @@ def test_gram_kernel_on_ragged_sample_counts(env):
 
 
 def _update_problem(env='swimmer', N=5000, seed=21, pol_hidden=(32, 32)):
-    eng, dm, theta, pdims, pool = Hh.make_engine(env, 2, (64, 64), pol_hidden, seed=seed)
-    rng = np.random.RandomState(seed)
-    th = theta.astype(np.float32).astype(np.float64)
-    obs = (rng.randn(N, dm.ns) * 0.5).astype(np.float32).astype(np.float64)
-    old_mean = O.policy_mean(th, pdims, obs).astype(np.float32).astype(np.float64)
-    old_ls = np.broadcast_to(O.policy_log_std(th, pdims), old_mean.shape).copy()
-    act = (old_mean + np.exp(old_ls) * rng.randn(*old_mean.shape)).astype(np.float32).astype(np.float64)
-    adv = O.center_advantages(rng.randn(N)).astype(np.float32).astype(np.float64)
+    dm, th, pdims, obs, act, adv, old_mean, old_ls = Hh.update_data(env, N, seed=seed, pol_hidden=pol_hidden)
+    eng = Hh.engine_of(env, 2, (64, 64), pol_hidden, dm, th)
     return eng, th, pdims, obs, act, adv, old_mean, old_ls
 
 

@@ -42,6 +42,11 @@ def rel_l2(a, b):
     return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30)
 
 
+def near_bound(ratio, clip):
+    """Samples whose float64 likelihood ratio lies within BAND of a clip bound 1 +- clip: marked invalid for both sides."""
+    return (np.abs(ratio - (1 - clip)) < BAND) | (np.abs(ratio - (1 + clip)) < BAND)
+
+
 def case(family, seed=41, moved=True, epochs=0, ent=0.0, lr=1e-2):
     """The data of one case, on the CPU alone (no engine): theta_old, theta (moved off it by a fixed random direction), the batch with the old
     distribution of theta_old, and `valid` with the reference's near-bound samples removed -- at theta for the gradient cases, at the theta of
@@ -64,8 +69,7 @@ def case(family, seed=41, moved=True, epochs=0, ent=0.0, lr=1e-2):
     base = valid.copy()
 
     def near(th):
-        ratio = R.ratios(th, pdims, obs, act, old_mean, old_ls)[0]
-        return (np.abs(ratio - (1 - clip)) < BAND) | (np.abs(ratio - (1 + clip)) < BAND)
+        return near_bound(R.ratios(th, pdims, obs, act, old_mean, old_ls)[0], clip)
     if epochs == 0:
         valid[near(theta)] = 0
     else:

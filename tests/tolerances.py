@@ -61,6 +61,9 @@ NORMAL_EQ = 2e-6            # entries of A^T A / A^T y relative to sqrt(G_ii G_j
 LOSS_RTOL = 1e-5            # surrogate loss relative to max(1, |loss|): per-sample fp32, float64 block reduction (rtol 1e-5)
 KL_ATOL = 1e-7              # mean KL at theta_old (atol 1e-7); at a trial theta also 1e-4 relative (KL is a difference of O(1) terms)
 KL_RTOL = 1e-4
+# Both vector rows also hold per variable (W_l, b_l, log_std), dealt out by block size: block_bound() below.  tests/test_gpu_update_kernels.py holds every
+# instantiation of the update kernels to these rows at the tile edges (328 cases); worst share of a bound observed there: loss 0.12, KL 0.42,
+# gradient 0.31 whole / 0.58 per block, FVP 0.50 whole / 0.52 per block (profiles/r10_update_kernels.txt).
 GRAD_REL_L2 = 1e-5          # gradient g (1e-5): per-sample back-propagation in fp32, sums over N in float64.  Observed 1.1e-6
 FVP_REL_L2 = 1e-5           # Fisher-vector product (1e-4; held 10x tighter): tangent + back-propagation in fp32, float64 sums over N.  Observed 1.2e-7
 CG_COS = 0.9999             # step direction d after 10 CG iterations (cosine >= 0.9999, rel-L2 <= 1e-3: ten FVPs amplify rounding by the
@@ -77,6 +80,18 @@ MULTI_RANK_THETA = 2e-3     # x |step|: as THETA_STEP_REL_L2
 def wide_or_step(hidden):
     """Row 1 for the 2x64-class nets, row 2 from 128 hidden units on."""
     return STEP if max(hidden) <= 64 else WIDE
+
+
+def block_bound(row, ref_blk, ref):
+    """Bound on ||got_blk - ref_blk||_2 for one variable (W_l, b_l or log_std) of a gradient or Fisher-vector product whose whole vector is held
+    to rel-L2 `row` (GRAD_REL_L2 / FVP_REL_L2):  row * max(||ref_blk||_2, sqrt(n_blk / P) * ||ref||_2).
+    This is the whole-vector bound dealt out by block size, nothing newly measured: the vector's error budget row * ||ref||_2 split evenly over
+    its P entries gives a block of n_blk entries sqrt(n_blk / P) of it, and a block that carries more than its even share of the norm is held
+    to `row` of itself.  The whole-vector figure cannot see a narrow block: log_std (na of 1 476 entries at C1) or b_2 wrong by O(1) of itself
+    moves it by less than `row`; this bound fails such a block by ||ref_blk|| / bound >= 1 / (row * max(1, sqrt(n_blk / P) ||ref|| / ||ref_blk||))."""
+    import numpy as np
+    nb, n = float(np.linalg.norm(ref_blk)), float(np.linalg.norm(ref))
+    return row * max(nb, (float(np.size(ref_blk)) / float(np.size(ref))) ** 0.5 * n)
 
 
 # --- widened rows (SURVEY 8f): BPTT policy update and ensemble training -----------------------------------------------------------------------------
