@@ -295,8 +295,8 @@ int32_t metrpo_vpg_update(metrpo_ctx* ctx, const metrpo_batch* batch, const metr
  *     loss = -mean_i min(lr_i A_i, clip(lr_i, 1 - clip_lr, 1 + clip_lr) A_i) - entropy_bonus_coeff * mean_i H_i        (ppo.py:112-119)
  * H = sum_j log_std_j + na / 2 (1 + log 2 pi) of the clamped log_std (ppo.py:109), means over the valid samples (inv_n_global).  The gradient is
  * tf.minimum's / tf.clip_by_value's: a sample contributes -A_i lr_i grad(logli_i) / N when lr_i A_i <= clip(lr_i) A_i (ties: the unclipped
- * branch) and nothing otherwise; the entropy term adds -entropy_bonus_coeff on every unclamped log_std slot.  use_kl_penalty (ppo.py:120-121)
- * is not built.  The optimiser ppo.py:61-62 names (an AdamOptimizer the file never imports or defines) is stated here: n_epochs full-batch
+ * branch) and nothing otherwise; the entropy term adds -entropy_bonus_coeff on every unclamped log_std slot.  use_kl_penalty (ppo.py:120-121):
+ * the block below.  The optimiser ppo.py:61-62 names (an AdamOptimizer the file never imports or defines) is stated here: n_epochs full-batch
  * tf.train.AdamOptimizer steps, no clipping, every policy parameter incl. log_std. */
 typedef struct {
     double clip_lr, entropy_bonus_coeff;   /* ppo.py:19, :24: 0.3, 0 */
@@ -312,6 +312,33 @@ int32_t metrpo_ppo_loss_grad(metrpo_ctx* ctx, const metrpo_batch* batch, const m
  * one-shot exchange in its tail; with an RCCL communicator (and on the GEMM path) the all-reduce and a stand-alone step follow the reduction.
  * d_losses (optional, n_epochs doubles): d_losses[e] = the loss at the theta entering epoch e. */
 int32_t metrpo_ppo_update(metrpo_ctx* ctx, const metrpo_batch* batch, const metrpo_ppo_params* params, int32_t n_epochs, double* d_losses, void* stream);
+
+/* ---- PPO's KL penalty (use_kl_penalty, ppo.py:120-121).  With beta = kl_penalty, delta = step_size (ppo.py:34: 0.01) and mean_kl = the mean over the valid
+ * samples (inv_n_global) of dist.kl_sym(old, new) -- the quantity metrpo_loss_kl returns in d_out[1], with the same log_std clamp:
+ *     loss = [the PPO loss above] + beta * max(0, mean_kl - delta)
+ * Gate: tf.maximum's gradient (MaximumGrad) sends a tie to the constant 0., so the penalty contributes to the gradient iff mean_kl - delta > 0, strictly.
+ * The gate is decided on the float64 REDUCED mean_kl (one device cell every kernel of the launch reads), never on a sample's or a rank's float32 share.
+ * Gate open: sample i adds beta * inv_n_global * d kl_i / d theta to the clipped surrogate's seed; with sigma = exp(clamped log_std)
+ *     d kl_i / d mean_j = (mean_j - old_mean_j) / sigma_j^2,    d kl_i / d log_std_j = 1 - (sigma_old_j^2 + (old_mean_j - mean_j)^2) / sigma_j^2,
+ * the log_std gradient being zero on a clamped slot like every other term; a sample whose surrogate is clipped still carries its KL gradient.  The loss
+ * term is accumulated per sample as beta * inv_n_global * (kl_i - delta), which sums to beta * (mean_kl - delta) over all ranks' valid samples.
+ * Gate closed: loss and gradient are metrpo_ppo_loss_grad's, bit for bit.
+ * mean_kl is GLOBAL: over all ranks' valid samples, summed before the gate is taken.  Rank sums: the surrogate and the KL parts of d_out are this rank's
+ * share (no / W rule for the penalty); the entropy term keeps metrpo_ppo_loss_grad's convention; d_out[0] summed over the ranks is the global loss. */
+typedef struct { double kl_penalty, step_size; } metrpo_ppo_kl_params;   /* ppo.py:27 initial_kl_penalty = 1 (the caller's current value), :34 step_size = 0.01 */
+/* metrpo_ppo_loss_grad with the penalty.  d_mean_kl: device pointer to the global mean KL at the ctx theta (one double; a host-driven all-reduce sums
+ * metrpo_loss_kl's d_out[1] over the ranks first), or NULL: computed by the call (the launches of metrpo_loss_kl at the ctx theta in front of the gradient
+ * launch, summed over the ranks by an attached communicator).  kl_penalty < 0, a non-finite kl_penalty or step_size and a NULL old distribution are
+ * METRPO_EINVAL. */
+int32_t metrpo_ppo_kl_loss_grad(metrpo_ctx* ctx, const metrpo_batch* batch, const metrpo_ppo_params* params, const metrpo_ppo_kl_params* kl,
+                                const double* d_mean_kl, double* d_out, void* stream);
+/* metrpo_ppo_update with the penalty: per epoch the loss + KL launch and its reduction at the theta entering the epoch (into a ctx-owned float64 pair;
+ * sharded with an attached communicator the reduction carries the exchange, as the line-search trials do), the gradient launch that reads that pair and
+ * takes the gate itself, and the reduction with entropy term and Adam step.  No synchronisation and no host read between the epochs; on the RCCL / GEMM
+ * path metrpo_ppo_update's stand-alone step sequence applies unchanged.  d_losses (optional, n_epochs doubles) as there, penalty included; d_mean_kls
+ * (optional, n_epochs doubles): the global mean KL at the theta entering each epoch.  An open TRPO update is METRPO_ESTATE. */
+int32_t metrpo_ppo_kl_update(metrpo_ctx* ctx, const metrpo_batch* batch, const metrpo_ppo_params* params, const metrpo_ppo_kl_params* kl, int32_t n_epochs,
+                             double* d_losses, double* d_mean_kls, void* stream);
 
 /* ---- multi-GPU: one process and one ctx per GPU, the env batch B sharded over the ranks.  The only exchanges on
  * the path are sum all-reduces of small float64 vectors.  Attach an RCCL communicator to the ctx and metrpo_trpo_update issues

@@ -69,6 +69,10 @@ class PpoParams(C.Structure):
                 ('eps', C.c_double)]
 
 
+class PpoKlParams(C.Structure):
+    _fields_ = [('kl_penalty', C.c_double), ('step_size', C.c_double)]
+
+
 class LbfgsOpts(C.Structure):
     _fields_ = [('m', C.c_int32), ('maxls', C.c_int32), ('maxiter', C.c_int32), ('maxfun', C.c_int32), ('ftol', C.c_double),
                 ('gtol', C.c_double), ('lookahead', C.c_int32), ('round_f32', C.c_int32)]
@@ -119,6 +123,8 @@ SYMBOLS = {
     'metrpo_vpg_update': (_I, [_P, C.POINTER(Batch), C.POINTER(VpgParams), _P, _P]),
     'metrpo_ppo_loss_grad': (_I, [_P, C.POINTER(Batch), C.POINTER(PpoParams), _P, _P]),
     'metrpo_ppo_update': (_I, [_P, C.POINTER(Batch), C.POINTER(PpoParams), C.c_int32, _P, _P]),
+    'metrpo_ppo_kl_loss_grad': (_I, [_P, C.POINTER(Batch), C.POINTER(PpoParams), C.POINTER(PpoKlParams), _P, _P, _P]),
+    'metrpo_ppo_kl_update': (_I, [_P, C.POINTER(Batch), C.POINTER(PpoParams), C.POINTER(PpoKlParams), C.c_int32, _P, _P, _P]),
     'metrpo_trpo_update': (_I, [_P, C.POINTER(Batch), C.POINTER(TrpoParams), C.POINTER(TrpoDiag), _P, _P, _P]),
     'metrpo_trpo_update_begin': (_I, [_P, C.POINTER(Batch), C.POINTER(TrpoParams), _I, _P, _P, _P]),
     'metrpo_trpo_update_end': (_I, [_P, C.POINTER(TrpoDiag), C.POINTER(C.c_int32), _P]),

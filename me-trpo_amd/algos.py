@@ -6,6 +6,8 @@ unchanged:
     algo.start_worker(); paths = algo.obtain_samples(j); samples_data = algo.process_samples(j, paths)
     algo.optimize_policy(j, samples_data)
 """
+import numpy as np
+
 from .optimizer import ConjugateGradientOptimizer, AdamOptimizer
 from .parallel import Comm
 from .sampler import VectorizedSampler
@@ -190,17 +192,24 @@ class VPG(BatchPolopt):
 class PPO(BatchPolopt):
     """Proximal Policy Optimization (algos/ppo.py) with the reference's constructor signature.  The loss is ppo.py:107-119's clipped
     likelihood-ratio surrogate with the entropy bonus; the optimiser ppo.py:61-62 names is never defined there and is optimizer.AdamOptimizer
-    here.  use_kl_penalty=True (ppo.py:120-121; the reference never calls its f_increase_penalty / f_decrease_penalty) is not built.  The other
-    arguments the reference's constructor stores and never reads (use_line_search, max_backtracks, backtrack_ratio, step_size, min_n_epochs,
-    adaptive_learning_rate, max / min_learning_rate, gradient_clipping, the penalty factors and bounds, log_loss_kl_before / _after) are stored
-    and not acted on, as there.  Recurrent policies are out of scope (ppo.py:103)."""
+    here.  use_kl_penalty=True adds ppo.py:120-121's kl_penalty * max(0, mean_kl - step_size): self.kl_penalty (the TF variable kl_penalty_var,
+    a float32 that starts at initial_kl_penalty) and self.step_size go to the optimiser with every call; f_increase_penalty / f_decrease_penalty /
+    f_reset_penalty do ppo.py:133-153's arithmetic on it -- the reference never calls them, and neither does any loop here.  It needs a policy
+    whose engine has the penalty's entry points (Engine.ppo_kl_update / ppo_kl_loss_grad) and raises NotImplementedError without one.  The other
+    arguments the reference's constructor stores and never reads (use_line_search, max_backtracks, backtrack_ratio, min_n_epochs,
+    adaptive_learning_rate, max / min_learning_rate, gradient_clipping, log_loss_kl_before / _after) are stored and not acted on, as there.  Recurrent policies are out of scope (ppo.py:103)."""
 
     def __init__(self, clip_lr=0.3, increase_penalty_factor=2, decrease_penalty_factor=0.5, min_penalty=1e-3, max_penalty=1e6,
                  entropy_bonus_coeff=0., gradient_clipping=40., log_loss_kl_before=True, log_loss_kl_after=True, use_kl_penalty=False,
                  initial_kl_penalty=1., use_line_search=True, max_backtracks=10, backtrack_ratio=0.5, optimizer=None, step_size=0.01,
                  min_n_epochs=2, adaptive_learning_rate=False, max_learning_rate=1e-3, min_learning_rate=1e-5, **kwargs):
         if use_kl_penalty:
-            raise NotImplementedError("PPO: use_kl_penalty (ppo.py:120-121) is not built: its gate needs the batch-mean KL in front of the gradient")
+            # the penalty runs in the engine's OP_PPOKL kernels: refuse, before anything is built, where there is no engine that has them (no policy, an
+            # engine object of another kind) instead of failing at the first optimize_policy
+            eng = getattr(kwargs.get('policy'), 'engine', None)
+            if not (hasattr(eng, 'ppo_kl_update') and hasattr(eng, 'ppo_kl_loss_grad')):
+                raise NotImplementedError("PPO: use_kl_penalty (ppo.py:120-121) needs a policy whose engine has ppo_kl_update / ppo_kl_loss_grad "
+                                          "(metrpo_amd.Engine); got engine %r" % (eng,))
         self.clip_lr, self.entropy_bonus_coeff = clip_lr, entropy_bonus_coeff
         self.increase_penalty_factor, self.decrease_penalty_factor = increase_penalty_factor, decrease_penalty_factor
         self.min_penalty, self.max_penalty, self.initial_kl_penalty = min_penalty, max_penalty, initial_kl_penalty
@@ -216,7 +225,24 @@ class PPO(BatchPolopt):
             optimizer = AdamOptimizer()
         self.optimizer = optimizer
         self.opt_info = None
+        self.kl_penalty = float(np.float32(initial_kl_penalty))      # kl_penalty_var (a float32 TF variable)
         super(PPO, self).__init__(**kwargs)
+
+    # ppo.py:133-153: assignments to kl_penalty_var, computed and stored in float32 as TF does; each returns the new value
+    def f_increase_penalty(self):
+        self.kl_penalty = float(np.minimum(np.float32(self.kl_penalty) * np.float32(self.increase_penalty_factor), np.float32(self.max_penalty)))
+        return self.kl_penalty
+
+    def f_decrease_penalty(self):
+        self.kl_penalty = float(np.maximum(np.float32(self.kl_penalty) * np.float32(self.decrease_penalty_factor), np.float32(self.min_penalty)))
+        return self.kl_penalty
+
+    def f_reset_penalty(self):
+        self.kl_penalty = float(np.float32(self.initial_kl_penalty))
+        return self.kl_penalty
+
+    def _penalty_args(self):
+        return dict(kl_penalty=self.kl_penalty, step_size=self.step_size) if self.use_kl_penalty else dict()
 
     def init_opt(self):
         self.optimizer.update_opt(loss=None, target=self.policy, inputs=None)
@@ -225,7 +251,7 @@ class PPO(BatchPolopt):
 
     def optimize_policy(self, itr, samples_data):
         """ppo.py:157-183: inputs = (observations, actions, advantages, agent_infos[mean], agent_infos[log_std]); loss and mean KL before,
-        optimizer.optimize, mean KL and loss after.  The reference computes the five diagnostics and returns an empty dict (its record_tabular
+        optimizer.optimize, mean KL and loss after (both losses with the KL penalty under use_kl_penalty).  The reference computes the five diagnostics and returns an empty dict (its record_tabular
         lines are commented out); they are returned here, as 1-element device tensors (no synchronisation)."""
         agent_infos = samples_data["agent_infos"]
         batch = self.engine.make_batch(samples_data["observations"], samples_data["actions"], samples_data["advantages"],
@@ -235,9 +261,9 @@ class PPO(BatchPolopt):
         reduce_ = (lambda t: comm.allreduce_sum_(t)) if (comm.world > 1 or comm.always_reduce) else (lambda t: t)
         with self.timers.phase('policy_opt'):
             lk_before = reduce_(eng.loss_kl(batch))                              # [unclipped surrogate, mean KL] at the entry theta
-            losses = self.optimizer.optimize(eng, batch, self.clip_lr, self.entropy_bonus_coeff, comm=comm)
+            losses = self.optimizer.optimize(eng, batch, self.clip_lr, self.entropy_bonus_coeff, comm=comm, **self._penalty_args())
             lk_after = reduce_(eng.loss_kl(batch))
-            loss_after = self.optimizer.loss(eng, batch, self.clip_lr, self.entropy_bonus_coeff, comm=comm)
+            loss_after = self.optimizer.loss(eng, batch, self.clip_lr, self.entropy_bonus_coeff, comm=comm, **self._penalty_args())
         if hasattr(self.sampler, 'finish_baseline_fit') and not getattr(self, 'defer_baseline_fit', False):
             self.sampler.finish_baseline_fit()
         loss_before = losses[:1] if len(losses) else loss_after

@@ -538,6 +538,23 @@ extern "C" int32_t metrpo_ppo_update(metrpo_ctx* c, const metrpo_batch* b, const
     if (c->upd_pending) return set_err(c, METRPO_ESTATE, "ppo_update: a TRPO update is still open (metrpo_trpo_update_end first)");
     return run_ppo_update(c, b, pr, n_epochs, d_losses, (hipStream_t)stream);
 }
+// algos/ppo.py:120-121 (use_kl_penalty: clipped_surr_pen_loss += kl_penalty_var * max(0, mean_kl - step_size)), policy_update.hip
+extern "C" int32_t metrpo_ppo_kl_loss_grad(metrpo_ctx* c, const metrpo_batch* b, const metrpo_ppo_params* pr, const metrpo_ppo_kl_params* kp, const double* d_mean_kl,
+                                           double* out, void* stream) {
+    if (!c) return METRPO_ENULL;
+    if (!pr || !kp) return set_err(c, METRPO_ENULL, "ppo_kl_loss_grad: params NULL");
+    if (!out) return set_err(c, METRPO_ENULL, "ppo_kl_loss_grad: out NULL");
+    NEED_POL(c);
+    return launch_ppo_kl_loss_grad(c, b, pr, kp, d_mean_kl, out, (hipStream_t)stream);
+}
+extern "C" int32_t metrpo_ppo_kl_update(metrpo_ctx* c, const metrpo_batch* b, const metrpo_ppo_params* pr, const metrpo_ppo_kl_params* kp, int32_t n_epochs, double* d_losses,
+                                        double* d_mean_kls, void* stream) {
+    if (!c) return METRPO_ENULL;
+    if (!pr || !kp) return set_err(c, METRPO_ENULL, "ppo_kl_update: params NULL");
+    NEED_POL(c);
+    if (c->upd_pending) return set_err(c, METRPO_ESTATE, "ppo_kl_update: a TRPO update is still open (metrpo_trpo_update_end first)");
+    return run_ppo_kl_update(c, b, pr, kp, n_epochs, d_losses, d_mean_kls, (hipStream_t)stream);
+}
 // model_based_rl.py:391-398 (ScipyOptimizerInterface, method='L-BFGS-B') and :1197-1202 (the 'l-bfgs' branch), lbfgs.hip
 static int lbfgs_opts_check(metrpo_ctx* c, const metrpo_lbfgs_opts* o, const char* who) {
     if (!o) return set_err(c, METRPO_ENULL, std::string(who) + ": opts NULL");

@@ -26,6 +26,19 @@ __device__ __forceinline__ float ppo_gate(float lr, float adv, float lo, float h
     *surr = pass ? un : cl;
     return pass ? un : 0.0f;
 }
+// PPO's KL penalty (ppo.py:120-121) for one action dim of one sample: the dim's term of DiagonalGaussian.kl_sym(old, new) exactly as the OP_LOSSKL
+// kernels write it (returned), and its derivatives with sigma = exp(ls), ls the clamped log_std and inv_std = exp(-ls):
+//   d kl / d mean = (mean - old_mean) / sigma^2,   d kl / d log_std = 1 - (sigma_old^2 + (old_mean - mean)^2) / sigma^2      (os2 = sigma_old^2 = exp(2 ols))
+// (The derivatives are those of the exact KL, as include/metrpo.h states them: kl_sym's 1e-8 in the denominator changes them by 1e-8 / (2 sigma^2) relative.)
+__device__ __forceinline__ float ppo_kl_dim(float mu, float omu, float ls, float ols, float os2, float inv_std, float* dmu, float* dls) {
+    const float s2 = expf(2.0f * ls), dm = omu - mu, iv = inv_std * inv_std;
+    *dmu = -dm * iv;
+    *dls = 1.0f - (os2 + dm * dm) * iv;
+    return (dm * dm + os2 - s2) / (2.0f * s2 + KL_EPS) + ls - ols;
+}
+// The penalty's gate, tf.maximum(0., mean_kl - step_size) with MaximumGrad's tie rule (a tie sends the gradient to the constant): open iff strictly
+// positive, decided on the float64 reduced mean KL.  Every wave of the launch reads the same cell.
+__device__ __forceinline__ bool ppo_kl_open(const double* __restrict__ mean_kl, double delta) { return mean_kl[0] - delta > 0.0; }
 #define ENTROPY_CONST 1.4189385332046727f    // 0.5 (1 + log(2 pi)): DiagonalGaussian.entropy_sym's constant per action dim
 
 // tanh(x) = 1 - 2 / (1 + exp(2x)) in 5 VALU ops (v_mul, v_exp_f32, v_add, v_rcp_f32, v_fma): absolute error

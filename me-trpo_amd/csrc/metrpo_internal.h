@@ -99,6 +99,7 @@ struct metrpo_ctx {
     DevBuf<double> d_gram_part;    // per-block Gram partials (process.hip)
     DevBuf<unsigned int> d_ticket; // arrival counter of k_finalize's fused CG tail
     DevBuf<float> d_hcache;        // activation cache of one CG solve (policy_mfma.hip OP_FVPC)
+    DevBuf<double> d_ppo_kl;       // run_ppo_kl_update / launch_ppo_kl_loss_grad: one [loss, mean KL] pair per epoch, written by the OP_LOSSKL reduction and read by the OP_PPOKL kernels
     DevBuf<void> d_mig; int mig_epoch = 0;        // rollout_coop.hip: hand-over slots of migrating tiles (flag | ts | model | obs per tile)
     void* nccl_comm = nullptr; int comm_world = 0, comm_rank = 0;   // comm.hip: RCCL communicator attached by metrpo_comm_init (NULL: single rank)
     // comm.hip: one-shot direct all-reduce (xchg_device.h).  xg_region = this rank's receive region (IPC-exported), xg_peer[q] = rank q's
@@ -239,6 +240,9 @@ struct PolK {
     const double* skip;      // non-NULL: a line-search trial that leaves at once when skip[0] >= 0 (the search already stopped: CgTail::ls)
     float* imgval;           // policy_mfma.hip: non-NULL under SolveScope::publish_image -- gradient kernel: block 0 publishes its image here; OP_FVPC: the image to copy
     float* hcache;           // policy_mfma.hip: hidden activations of (theta, batch): written by the gradient kernel, read by OP_FVPC
+    // OP_PPOKL (ppo.py:120-121; last, so that every member above keeps its offset): the reduced GLOBAL mean KL at the theta of this launch, one float64 on
+    // the device (read by every wave, a uniform load; the gate mean_kl[0] - kl_delta > 0 is taken in float64), step_size, kl_penalty
+    const double* mean_kl; double kl_delta; float kl_beta;
 };
 
 // ---- one policy-update launch (policy_update.hip run_update) ------------------------------------------------------------------------------------
@@ -252,6 +256,8 @@ enum UpdOp {
     OP_VPG = 4,       // OP_GRAD with the VPG surrogate's head (algos/vpg.py: ratio 1, loss = -mean(logli * adv))
     OP_PPO = 5,       // OP_GRAD with PPO's clipped head (algos/ppo.py:107-117): loss = -mean(min(lr adv, clip(lr) adv)), a clipped sample carries no gradient;
                       // block 0 also leaves the entropy sum(ls) + na/2 (1 + log 2 pi) of the entry theta in column P+1 of its partial row (ppo_entropy_term)
+    OP_PPOKL = 6,     // OP_PPO plus ppo.py:120-121's penalty kl_penalty * max(0, mean_kl - step_size): with the gate open (PolK::mean_kl, ppo_kl_open) every valid sample
+                      // adds kl_beta * inv_n * (kl_i - kl_delta) to the loss and kl_beta * inv_n * d kl_i / d (mean, log_std) to its seed; gate closed: OP_PPO's results
 };
 // What the enclosing solve lets a launch rely on; run_trpo_update / run_vpg_update build one on their stack, every launch outside a solve passes the all-off default.
 struct SolveScope {
@@ -350,6 +356,9 @@ int run_vpg_update(metrpo_ctx*, const metrpo_batch*, const metrpo_vpg_params*, d
 // 'ppo' policy update (algos/ppo.py): the OP_PPO instantiations, the entropy term in the reduction, n_epochs Adam steps with the old distribution fixed
 int launch_ppo_loss_grad(metrpo_ctx*, const metrpo_batch*, const metrpo_ppo_params*, double* out, hipStream_t);
 int run_ppo_update(metrpo_ctx*, const metrpo_batch*, const metrpo_ppo_params*, int n_epochs, double* d_losses, hipStream_t);
+// ... with use_kl_penalty (ppo.py:120-121): the OP_PPOKL instantiations behind an OP_LOSSKL launch that leaves the mean KL of the same theta on the device
+int launch_ppo_kl_loss_grad(metrpo_ctx*, const metrpo_batch*, const metrpo_ppo_params*, const metrpo_ppo_kl_params*, const double* d_mean_kl, double* out, hipStream_t);
+int run_ppo_kl_update(metrpo_ctx*, const metrpo_batch*, const metrpo_ppo_params*, const metrpo_ppo_kl_params*, int n_epochs, double* d_losses, double* d_mean_kls, hipStream_t);
 // 'l-bfgs' policy update (lbfgs.hip): the reverse-communication L-BFGS-B core and the BPTT-driven minimisation
 int lbfgs_begin(metrpo_ctx*, int n, const double* x0, const float* x0_f32, const metrpo_lbfgs_opts*, double* x_eval, hipStream_t);
 int lbfgs_iterate(metrpo_ctx*, const double* f, const double* g, double* x_eval, int32_t* task, hipStream_t);

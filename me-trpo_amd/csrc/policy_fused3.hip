@@ -36,6 +36,7 @@ struct F3K {                    // kernel arguments
     f32x4* hc; f32x4* u;        // activation cache / mean-adjoint: [tile][block][64 lanes] 16-byte words in the MFMA D layout
     float* partials; int row_stride, P, ls_off;
     int w_off[4], b_off[4];
+    const double* mean_kl; double kl_delta; float kl_beta;      // OP_PPOKL (PolK's members of the same names); last: no other member moves
 };
 constexpr int cdiv3(int a, int b) { return (a + b - 1) / b; }
 constexpr int cbp_of(int cb) { return cb <= 1 ? 1 : cb <= 2 ? 2 : cb <= 4 ? 4 : 8; }
@@ -169,7 +170,7 @@ template <class S> __device__ __forceinline__ void fix_xb(float (&xb)[S::KS0], i
 }
 
 // MODE of k_f3_fwd: OP_GRAD, OP_LOSSKL, OP_VPG, OP_PPO (the gradient mode with ppo.py:112-117's clipped head, ppo_gate; block 0 leaves the entropy of theta in
-// column P+1) of UpdOp (metrpo_internal.h), and the forward pass that only fills the activation cache for a Fisher-vector product
+// column P+1), OP_PPOKL (OP_PPO plus ppo.py:120-121's KL penalty under the gate read from F3K::mean_kl: ppo_kl_open, ppo_kl_dim) of UpdOp (metrpo_internal.h), and the forward pass that only fills the activation cache for a Fisher-vector product
 // whose gradient launch was not kept.  That one is no UpdOp: a file-local constant, whose value 3 is part of the kernel's mangled name.
 constexpr int F3_FILL_CACHE = 3;
 enum { IMG_WHAT_F = 1, IMG_WHAT_V = 2, IMG_WHAT_B = 4 };
@@ -209,11 +210,14 @@ __global__ void __launch_bounds__(256) k_f3_image(F3K k, float* __restrict__ img
 // forward + head
 template <class S, int MODE_, int NW>
 __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
-    constexpr bool VPG = (MODE_ == OP_VPG), PPO = (MODE_ == OP_PPO);
+    constexpr bool VPG = (MODE_ == OP_VPG), PPOKL = (MODE_ == OP_PPOKL), PPO = (MODE_ == OP_PPO) || PPOKL;
     constexpr int MODE = (VPG || PPO) ? OP_GRAD : MODE_;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), c = lane & 15, q = lane >> 4;
     if (MODE == OP_LOSSKL && k.skip != nullptr && k.skip[0] >= 0.0) return;        // speculative line-search trial after the search stopped
+    bool kl_open = false;                                   // OP_PPOKL: the KL penalty's gate (ppo.py:120-121), one cell, the same for every wave of the launch
+    if constexpr (PPOKL) kl_open = ppo_kl_open(k.mean_kl, k.kl_delta);
+    const float kl_w = PPOKL ? k.kl_beta * k.inv_n : 0.f, kl_d = PPOKL ? (float)k.kl_delta : 0.f;
     float* T0 = lds; float* T1 = T0 + S::F0; float* T2 = T1 + S::F1; float* T3 = T2 + S::F2;
     const float* __restrict__ th = k.theta;
     copy_tab<S::LDS_FWD, NW * 64>(lds, k.img + S::IMG_F, tid);
@@ -290,12 +294,13 @@ __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
         chain<S::KS3, S::CB4, false>(T3, lane, [&](int kk) { return h3[kk >> 2][kk & 3]; }, mu);
         // ---- head (npo.py:69-75; DiagonalGaussian.log_likelihood_sym / kl_sym), this lane's action dims of sample c
         float llr = 0.f, kl = 0.f, zz[S::CB4][4];
+        float kmu[S::CB4][4], kls[S::CB4][4];               // OP_PPOKL, gate open: d kl_i / d mean, d kl_i / d log_std of this lane's action dims
 #pragma unroll
         for (int cb = 0; cb < S::CB4; ++cb)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int d = 16 * cb + 4 * q + r;
-                zz[cb][r] = 0.f;
+                zz[cb][r] = 0.f; kmu[cb][r] = 0.f; kls[cb][r] = 0.f;
                 if (VPG && d < S::D4 && ok) {              // DiagonalGaussian.log_likelihood_sym, less its constant (added per sample below)
                     const float z = (in.act[cb][r] - mu[cb][r]) * inv_std[cb][r];
                     llr -= ls[cb][r] + 0.5f * z * z;
@@ -310,6 +315,7 @@ __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
                         const float s2 = expf(2.f * ls[cb][r]), os2 = expf(2.f * ols), dm = omu - mu[cb][r];
                         kl += (dm * dm + os2 - s2) / (2.f * s2 + KL_EPS) + ls[cb][r] - ols;
                     }
+                    if constexpr (PPOKL) { if (kl_open) kl += ppo_kl_dim(mu[cb][r], omu, ls[cb][r], ols, expf(2.f * ols), inv_std[cb][r], &kmu[cb][r], &kls[cb][r]); }
                 }
             }
         llr = xsum_q3(llr);                                 // the four q-lanes of sample c hold its action dims between them
@@ -319,6 +325,9 @@ __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
         if (q == 0) acc0 -= surr * k.inv_n;                 // surr_loss = -mean(lr * adv) | -mean(logli * adv) | clipped_surr_loss (ppo.py:115), once per sample
         if (MODE == OP_LOSSKL) { acc1 += kl * k.inv_n; continue; }
         const float w = -la * k.inv_n;
+        if constexpr (PPOKL) {                              // the penalty's loss term (kl is zero for an invalid sample): sum_i kl_beta / N (kl_i - step_size)
+            if (kl_open) { acc0 += kl_w * kl; if (q == 0 && ok) acc0 -= kl_w * kl_d; }
+        }
         f32x4* __restrict__ uw = k.u + (size_t)tile * S::CB4 * 64 + lane;
 #pragma unroll
         for (int cb = 0; cb < S::CB4; ++cb) {
@@ -327,6 +336,12 @@ __global__ void __launch_bounds__(NW * 64) k_f3_fwd(F3K k) {
             for (int r = 0; r < 4; ++r) {
                 um[r] = w * zz[cb][r] * inv_std[cb][r];                               // d loss / d mean = w (a - mu) / std^2
                 if (16 * cb + 4 * q + r < S::D4) dls[cb][r] += w * (zz[cb][r] * zz[cb][r] - 1.f);      // d loss / d log_std
+            }
+            if constexpr (PPOKL) {                          // the penalty's seed, in statements of their own: with the gate closed the arithmetic is OP_PPO's
+                if (kl_open) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { um[r] += kl_w * kmu[cb][r]; if (16 * cb + 4 * q + r < S::D4) dls[cb][r] += kl_w * kls[cb][r]; }
+                }
             }
             uw[cb * 64] = um;
         }
@@ -706,7 +721,13 @@ int policy_f3_launch(metrpo_ctx* c, const UpdCall& u, float* partials, int nbloc
         HIP_TRY(c, hipGetLastError());
         return METRPO_OK;
     }
-    if (u.op == OP_PPO) {
+    if (u.op == OP_PPOKL) {
+        k.clip_lo = b.clip_lo; k.clip_hi = b.clip_hi; k.mean_kl = b.mean_kl; k.kl_delta = b.kl_delta; k.kl_beta = b.kl_beta;
+        build_image(IMG_WHAT_F | IMG_WHAT_B); c->f3_img_ok = 1;
+        if ((rc = f3_attr(c, k_f3_fwd<S, OP_PPOKL, FWD_NW>, sh_fwd))) return rc;
+        hipLaunchKernelGGL((k_f3_fwd<S, OP_PPOKL, FWD_NW>), g, dim3(FWD_NW * 64), sh_fwd, st, k);
+        c->f3_rows = -1;                                    // (theta moves between the epochs: nothing to keep)
+    } else if (u.op == OP_PPO) {
         k.clip_lo = b.clip_lo; k.clip_hi = b.clip_hi;
         build_image(IMG_WHAT_F | IMG_WHAT_B); c->f3_img_ok = 1;
         if ((rc = f3_attr(c, k_f3_fwd<S, OP_PPO, FWD_NW>, sh_fwd))) return rc;

@@ -112,13 +112,17 @@ __global__ void k_pg_pad_obs(const float* __restrict__ obs, long long N, int ns,
 // part row (doubles): [0] loss, [1] kl, [2] valid weight, [3 .. 3+na) dls.  VPG (OP_GRAD only): the VPG surrogate (vpg.py:88), la = adv, loss = -mean(logli * adv)
 // HEAD: OP_GRAD / OP_VPG / OP_PPO (the gradient mode with ppo.py:112-117's clipped head, ppo_gate; the entropy term follows the reduction: k_ppo_step).
 // HEAD = OP_GRAD and OP_VPG compile to the code k_pg_head<false> and <true> had.
+// HEAD = OP_PPOKL: OP_PPO plus ppo.py:120-121's KL penalty under the gate read from PolK::mean_kl (ppo_kl_open, ppo_kl_dim); gate closed: OP_PPO's arithmetic.
 template <int HEAD>
 __global__ void __launch_bounds__(256) k_pg_head(int mode, PolK k, int na, int nap, const float* __restrict__ MU, const float* __restrict__ log_std,
                                                  float* __restrict__ U, double* __restrict__ parts) {
-    constexpr bool VPG = (HEAD == OP_VPG), PPO = (HEAD == OP_PPO);
+    constexpr bool VPG = (HEAD == OP_VPG), PPOKL = (HEAD == OP_PPOKL), PPO = (HEAD == OP_PPO) || PPOKL;
     __shared__ double sh[16];
     double acc[35];
     for (int i = 0; i < 3 + na; ++i) acc[i] = 0.0;
+    bool kl_open = false;                                    // OP_PPOKL: the KL penalty's gate (ppo.py:120-121), the same for every thread of the launch
+    if constexpr (PPOKL) kl_open = ppo_kl_open(k.mean_kl, k.kl_delta);
+    const float kl_w = PPOKL ? k.kl_beta * k.inv_n : 0.0f;
     for (long long n = (long long)blockIdx.x * 256 + threadIdx.x; n < k.N; n += (long long)gridDim.x * 256) {
         const bool ok = (k.valid == nullptr || k.valid[n]);
         if (mode == OP_FVP) {                                // FVP: U = tangent(mean) / (s^2 + eps/2) / N
@@ -166,8 +170,18 @@ __global__ void __launch_bounds__(256) k_pg_head(int mode, PolK k, int na, int n
         for (int d = 0; d < nap; ++d) {
             float u = 0.0f;
             if (d < na) { const float is = expf(-fmaxf(log_std[d], LOG_MIN_STD)); u = w * zz[d] * is; acc[3 + d] += (double)(w * (zz[d] * zz[d] - 1.0f)); }
+            if constexpr (PPOKL) {                           // the penalty's seed and loss term, in statements of their own
+                if (kl_open && ok && d < na) {
+                    const float ls = fmaxf(log_std[d], LOG_MIN_STD), ols = k.old_ls[(size_t)n * k.ls_stride + d];
+                    float kmu, kls;
+                    const float kl = ppo_kl_dim(MU[n * nap + d], k.old_mean[n * na + d], ls, ols, expf(2.0f * ols), expf(-ls), &kmu, &kls);
+                    acc[0] += (double)(kl_w * kl);
+                    u += kl_w * kmu; acc[3 + d] += (double)(kl_w * kls);
+                }
+            }
             U[n * nap + d] = u;
         }
+        if constexpr (PPOKL) { if (kl_open && ok) acc[0] -= (double)kl_w * k.kl_delta; }      // sum_i kl_beta / N (kl_i - step_size) = kl_beta (mean_kl - step_size)
     }
     for (int i = 0; i < 3 + na; ++i) {
         const double t = block_sum(acc[i], sh);
@@ -281,14 +295,14 @@ static int pg_ensure(metrpo_ctx* c, const PgLay& g, long long N, PgBufs* B) {
     return METRPO_OK;
 }
 
-// OP_GRAD (+ VJP when u.k.gm), OP_FVP, OP_LOSSKL, OP_VPG and OP_PPO (out as OP_GRAD; OP_PPO without the entropy term: k_ppo_step, policy_update.hip).  Writes u.out like k_finalize and then runs u.tail (may be NULL).
+// OP_GRAD (+ VJP when u.k.gm), OP_FVP, OP_LOSSKL, OP_VPG, OP_PPO and OP_PPOKL (out as OP_GRAD; OP_PPO / OP_PPOKL without the entropy term: k_ppo_step, policy_update.hip).  Writes u.out like k_finalize and then runs u.tail (may be NULL).
 int policy_gemm_run(metrpo_ctx* c, const UpdCall& u, hipStream_t st) {
     const ProblemDesc& pd = c->pd;
     const PolK& k = u.k;
     const long long N = k.N;
     if (N > 2000000000LL) return set_err(c, METRPO_EUNSUPPORTED, "policy_gemm: N too large");
     const bool vpg = (u.op == OP_VPG);                       // the gradient mode with the VPG head
-    const bool ppo = (u.op == OP_PPO);                       // ... with PPO's clipped head
+    const bool ppo = (u.op == OP_PPO || u.op == OP_PPOKL);   // ... with PPO's clipped head (OP_PPOKL: and the KL penalty)
     const int mode = (vpg || ppo) ? OP_GRAD : u.op;
     const float* theta = u.theta;
     const bool cache = u.scope.cache_activations;
@@ -348,6 +362,7 @@ int policy_gemm_run(metrpo_ctx* c, const UpdCall& u, hipStream_t st) {
     const bool head_elem = (mode == OP_FVP && k.gm == nullptr);
     const int nblk = head_elem ? (int)std::min<long long>(1024, (N * nap + 2047) / 2048) : (int)std::min<long long>(1024, (N + 255) / 256);
     if (head_elem) hipLaunchKernelGGL(k_pg_head_fvp, dim3(nblk), dim3(256), 0, st, k, na, nap, MU, theta + pd.pol.n_params, U, B.hparts);
+    else if (u.op == OP_PPOKL) hipLaunchKernelGGL(k_pg_head<OP_PPOKL>, dim3(nblk), dim3(256), 0, st, mode, k, na, nap, MU, theta + pd.pol.n_params, U, B.hparts);
     else if (ppo) hipLaunchKernelGGL(k_pg_head<OP_PPO>, dim3(nblk), dim3(256), 0, st, mode, k, na, nap, MU, theta + pd.pol.n_params, U, B.hparts);
     else if (vpg) hipLaunchKernelGGL(k_pg_head<OP_VPG>, dim3(nblk), dim3(256), 0, st, mode, k, na, nap, MU, theta + pd.pol.n_params, U, B.hparts);
     else hipLaunchKernelGGL(k_pg_head<OP_GRAD>, dim3(nblk), dim3(256), 0, st, mode, k, na, nap, MU, theta + pd.pol.n_params, U, B.hparts);

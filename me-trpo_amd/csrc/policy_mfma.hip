@@ -86,6 +86,10 @@ __device__ __forceinline__ float xsum_c(float v) {
 // distribution is not read.  Everything else is OP_GRAD's code.
 // OP_PPO: the gradient kernel with PPO's clipped head (algos/ppo.py:112-117, ppo_gate): a sample on the clipped branch carries no gradient; the clip
 // bounds are PolK::clip_lo / clip_hi.  Block 0 leaves the entropy of the theta it read in column P+1 of its partial row (ppo_entropy_term).
+// OP_PPOKL: OP_PPO plus the KL penalty (ppo.py:120-121): under the gate ppo_kl_open(PolK::mean_kl, kl_delta), read once per wave, every valid sample adds
+// kl_beta * inv_n * d kl_i to its mean-adjoint and log_std sums and kl_beta * inv_n * (kl_i - kl_delta) to the loss (ppo_kl_dim).  Gate closed: the kernel runs
+// OP_PPO's body instead (k_policy_mfma) -- its bits, which statements added to this body could not promise: the compiler contracts um's last product into
+// the bias-gradient sum (gb2 += um) only where nothing else writes um in between.
 // (Measured and parked, tools/experiments/policy_mfma_with_cgp.hip + profiles/r05_update_levers.txt: issue priorities per SIMD wave pair (POL_PRIO), h0 recomputed instead of
 // cached (POL_H0R, +4.8 us per product), weight-gradient products deferred into the next tile's vector stretch (POL_DEFER_S7, 60.5 vs 59.8 us), the CG solve as one launch.)
 // OP_FVPC: Fisher-vector product with the hidden activations h0, h1 = tanh(.) read from the cache the gradient kernel of the
@@ -109,7 +113,7 @@ struct PolImg {
 template <int NS, int NA, int PH, int MODE_>
 __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict__ theta, const float* __restrict__ v, float* __restrict__ partials) {
     using I = PolImg<NS, NA, PH>;
-    constexpr bool CACHED = (MODE_ == OP_FVPC), VPG = (MODE_ == OP_VPG), PPO = (MODE_ == OP_PPO);
+    constexpr bool CACHED = (MODE_ == OP_FVPC), VPG = (MODE_ == OP_VPG), PPOKL = (MODE_ == OP_PPOKL), PPO = (MODE_ == OP_PPO) || PPOKL;
     constexpr int MODE = CACHED ? OP_FVP : (VPG || PPO) ? OP_GRAD : MODE_;
     constexpr int NS_KS = I::NS_KS, NSI = cdiv_(NS, 16), HB = I::HB, KK = I::KK;
     constexpr int pW0 = 0, pb0 = NS * PH, pW1 = pb0 + PH, pb1 = pW1 + PH * PH, pW2 = pb1 + PH, pb2 = pW2 + PH * NA,
@@ -222,6 +226,8 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
         for (int r = 0; r < 4; ++r)
             if (4 * q + r < NA) { ols_c[r] = k.old_ls[4 * q + r]; eo_c[r] = expf(-ols_c[r]); os2_c[r] = expf(2.f * ols_c[r]); }
     }
+    constexpr bool kl_open = PPOKL;                         // the KL penalty's gate: k_policy_mfma<.., OP_PPOKL> runs this body only when it is open
+    const float kl_w = PPOKL ? k.kl_beta * k.inv_n : 0.f, kl_d = PPOKL ? (float)k.kl_delta : 0.f;
     f32x4 vb0f[HB], vb1f[HB], vb2f;
     if (MODE == OP_FVP) {
 #pragma unroll
@@ -439,6 +445,7 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
                 mu = m0 + m1;
             }
             float llr = 0.f, kl = 0.f, zz[4] = {0.f, 0.f, 0.f, 0.f};
+            float kmu[4] = {0.f, 0.f, 0.f, 0.f}, kls[4] = {0.f, 0.f, 0.f, 0.f};      // OP_PPOKL, gate open: d kl_i / d mean, d kl_i / d log_std of this lane's action dims
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int d = 4 * q + r;
@@ -454,7 +461,7 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
                         ols = in.ols[r];
                         asm volatile("" : "+v"(ols));                                          // keeps the exponentials on this side of the branch
                         eo = expf(-ols);
-                        if (MODE == OP_LOSSKL) os2 = expf(2.f * ols);
+                        if (MODE == OP_LOSSKL || (PPOKL && kl_open)) os2 = expf(2.f * ols);
                     }
                     const float z = (a - mu[r]) * inv_std[r], zo = (a - omu) * eo;
                     llr += (ols - ls[r]) + 0.5f * (zo * zo - z * z);
@@ -463,6 +470,7 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
                         const float s2 = expf(2.f * ls[r]), dm = omu - mu[r];
                         kl += (dm * dm + os2 - s2) / (2.f * s2 + KL_EPS) + ls[r] - ols;
                     }
+                    if constexpr (PPOKL) { if (kl_open) kl += ppo_kl_dim(mu[r], omu, ls[r], ols, os2, inv_std[r], &kmu[r], &kls[r]); }
                 }
             }
             llr = xsum_q(llr);                              // sum over action dims held by the 4 q-lanes of sample c
@@ -476,6 +484,14 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
             for (int r = 0; r < 4; ++r) {
                 um[r] = w * zz[r] * inv_std[r];             // d loss / d mean = w (a-mu)/std^2
                 if (4 * q + r < NA) dls[r] += w * (zz[r] * zz[r] - 1.f);      // d loss / d log_std
+            }
+            if constexpr (PPOKL) {                          // the penalty's seed and loss term, in statements of their own: with the gate closed the arithmetic is OP_PPO's
+                if (kl_open) {                              // (kl, kmu, kls are zero for an invalid sample and a padded action dim)
+                    acc0 += kl_w * kl;                      // this lane's action dims of kl_i; every lane's acc0 is summed at the end
+                    if (q == 0 && ok) acc0 -= kl_w * kl_d;  // sum_i kl_beta / N (kl_i - step_size) = kl_beta (mean_kl - step_size), once per sample
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { um[r] += kl_w * kmu[r]; if (4 * q + r < NA) dls[r] += kl_w * kls[r]; }
+                }
             }
         } else {
             // ---- S4: tangent of the mean: m1 = V2^T h1 (VALU inside: t1 *= 1 - h1^2), then m0 = vb2 + W2^T t1 ----------
@@ -698,6 +714,9 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
 template <int NS, int NA, int PH, int MODE_>
 __global__ void __launch_bounds__(NWAVES * 64, 1) k_policy_mfma(PolK k, const float* __restrict__ theta, const float* __restrict__ v,
                                                         float* __restrict__ partials) {
+    if constexpr (MODE_ == OP_PPOKL) {                      // the gate is the same for every wave of the launch: closed -> OP_PPO's body
+        if (!ppo_kl_open(k.mean_kl, k.kl_delta)) { pol_body<NS, NA, PH, OP_PPO>(k, theta, v, partials); return; }
+    }
     pol_body<NS, NA, PH, MODE_>(k, theta, v, partials);
 }
 
@@ -735,7 +754,7 @@ static void pol_image_map(std::vector<int>& map) {
 
 // -------------------------------------------------------------------------------------------------
 typedef void (*pol_kernel_t)(PolK, const float*, const float*, float*);
-struct PolEntry { int ns, na, ph; pol_kernel_t kern[6] /* indexed by UpdOp */; int lds_floats, lds_floats_eval; void (*build_map)(std::vector<int>&); };
+struct PolEntry { int ns, na, ph; pol_kernel_t kern[7] /* indexed by UpdOp */; int lds_floats, lds_floats_eval; void (*build_map)(std::vector<int>&); };
 template <int NS, int NA, int PH> constexpr int pol_lds() {
     constexpr int HB = cdiv_(PH, 16);
     constexpr int a = PolImg<NS, NA, PH>::TOTAL + NWAVES * (3 * HB + (NA <= 2 ? 0 : 1)) * 16 * 20;      // 20 = TS of the kernel's transpose tiles
@@ -748,7 +767,7 @@ template <int NS, int NA, int PH> constexpr int pol_lds_eval() {       // OP_LOS
     constexpr int a = PolImg<NS, NA, PH>::TOTAL, b = NWAVES * (P + PART_EXTRA);
     return a > b ? a : b;
 }
-#define PENTRY(NS, NA, PH) {NS, NA, PH, {k_policy_mfma<NS, NA, PH, OP_GRAD>, k_policy_mfma<NS, NA, PH, OP_FVP>, k_policy_mfma<NS, NA, PH, OP_LOSSKL>, k_policy_mfma<NS, NA, PH, OP_FVPC>, k_policy_mfma<NS, NA, PH, OP_VPG>, k_policy_mfma<NS, NA, PH, OP_PPO>}, pol_lds<NS, NA, PH>(), pol_lds_eval<NS, NA, PH>(), pol_image_map<NS, NA, PH>}
+#define PENTRY(NS, NA, PH) {NS, NA, PH, {k_policy_mfma<NS, NA, PH, OP_GRAD>, k_policy_mfma<NS, NA, PH, OP_FVP>, k_policy_mfma<NS, NA, PH, OP_LOSSKL>, k_policy_mfma<NS, NA, PH, OP_FVPC>, k_policy_mfma<NS, NA, PH, OP_VPG>, k_policy_mfma<NS, NA, PH, OP_PPO>, k_policy_mfma<NS, NA, PH, OP_PPOKL>}, pol_lds<NS, NA, PH>(), pol_lds_eval<NS, NA, PH>(), pol_image_map<NS, NA, PH>}
 static const PolEntry kPol[] = {
     PENTRY(10, 2, 32),    // swimmer
     PENTRY(18, 6, 32),    // half-cheetah

@@ -109,9 +109,10 @@ __device__ __forceinline__ void backward_accumulate(const NetDesc& net, const fl
 // log_std) = -sum(ls) - 0.5 sum(z^2) - 0.5 na log(2 pi); its gradient is NPO's at ratio 1 (la = adv).  old_mean / old_log_std are not read.
 // PPO (HEAD = OP_PPO): NPO's ratio through ppo_gate (ppo.py:112-117); block 0 leaves the entropy of the entry theta in column P+1 (ppo_entropy_term).
 // HEAD = OP_GRAD and OP_VPG compile to the code k_loss_grad<PT, OP_GRAD> and <PT, true> had (only the template argument's type changed with the third head).
+// PPOKL (HEAD = OP_PPOKL): PPO plus the KL penalty's seed and loss term (ppo.py:120-121; ppo_kl_open / ppo_kl_dim) under the gate read from PolK::mean_kl.
 template <int PT, int HEAD>
 __global__ void __launch_bounds__(PT) k_loss_grad(ProblemDesc pd, PolK k, const float* __restrict__ theta, float* __restrict__ partials) {
-    constexpr bool VPG = (HEAD == OP_VPG), PPO = (HEAD == OP_PPO);
+    constexpr bool VPG = (HEAD == OP_VPG), PPOKL = (HEAD == OP_PPOKL), PPO = (HEAD == OP_PPO) || PPOKL;
     constexpr int PLD = PT + 1;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ double red[16];
@@ -128,6 +129,9 @@ __global__ void __launch_bounds__(PT) k_loss_grad(ProblemDesc pd, PolK k, const 
     float dls_acc[32];            // na <= 32 enforced by the launcher
 #pragma unroll
     for (int d = 0; d < 32; ++d) dls_acc[d] = 0.0f;
+    bool kl_open = false;                                        // the penalty's gate: the same for every thread of the launch
+    if constexpr (PPOKL) kl_open = ppo_kl_open(k.mean_kl, k.kl_delta);
+    const float kl_w = PPOKL ? k.kl_beta * k.inv_n : 0.0f;
     for (long long base = (long long)blockIdx.x * PT; base < k.N; base += (long long)gridDim.x * PT) {
         __syncthreads();
         const bool ok = load_obs_tile<PT>(k, ns, base, H, tid);
@@ -176,10 +180,21 @@ __global__ void __launch_bounds__(PT) k_loss_grad(ProblemDesc pd, PolK k, const 
                 const float ls = fmaxf(raw_ls[d], LOG_MIN_STD);
                 const float inv_std = expf(-ls);
                 const float z = ok ? (k.act[n * na + d] - DM[d * PLD + tid]) * inv_std : 0.0f;
+                float kmu = 0.0f, kls = 0.0f;
+                if constexpr (PPOKL) {
+                    if (kl_open && ok) {                         // the KL seed (a clipped sample carries it too); DM still holds the mean here
+                        const float ols = k.old_ls[(size_t)n * k.ls_stride + d];
+                        loss_acc += (double)(kl_w * ppo_kl_dim(DM[d * PLD + tid], k.old_mean[n * na + d], ls, ols, expf(2.0f * ols), inv_std, &kmu, &kls));
+                    }
+                }
                 DM[d * PLD + tid] = w * z * inv_std;             // d loss / d mean
                 dls_acc[d] += w * (z * z - 1.0f);                // d loss / d log_std
+                if constexpr (PPOKL) {                           // + kl_penalty / N * d kl_i, in statements of their own: with the gate closed the arithmetic is OP_PPO's
+                    if (kl_open && ok) { DM[d * PLD + tid] += kl_w * kmu; dls_acc[d] += kl_w * kls; }
+                }
             }
         }
+        if constexpr (PPOKL) { if (kl_open && ok) loss_acc -= (double)kl_w * k.kl_delta; }      // sum_i kl_penalty / N (kl_i - step_size) = kl_penalty (mean_kl - step_size)
         backward_accumulate<PT>(net, theta, H, DM, part, tid);
     }
     // block-reduce the per-thread scalars into the partial row
@@ -444,28 +459,34 @@ static int ensure_partials(metrpo_ctx* c, int nrows) {
 }
 
 // the descriptor of `op` on batch b at the context's theta, everything else off; validates what the operation reads
-// (OP_FVP: no targets; OP_VPG: the VPG surrogate reads no old distribution -- d_old_mean / d_old_log_std may be NULL; OP_PPO: pr carries the clip)
-static int make_call(metrpo_ctx* c, UpdOp op, const metrpo_batch* b, UpdCall* u, const metrpo_ppo_params* pr = nullptr) {
-    const bool vpg = (op == OP_VPG);
+// (OP_FVP: no targets; OP_VPG: the VPG surrogate reads no old distribution -- d_old_mean / d_old_log_std may be NULL; OP_PPO: pr carries the clip; OP_PPOKL: and kp the penalty)
+static int make_call(metrpo_ctx* c, UpdOp op, const metrpo_batch* b, UpdCall* u, const metrpo_ppo_params* pr = nullptr, const metrpo_ppo_kl_params* kp = nullptr) {
+    const bool vpg = (op == OP_VPG), ppo = (op == OP_PPO || op == OP_PPOKL);
     if (!b || !b->d_obs) return set_err(c, METRPO_ENULL, "batch/d_obs is NULL");
     if (b->N <= 0) return set_err(c, METRPO_EINVAL, "batch N must be positive");
     if (c->pd.na > 32) return set_err(c, METRPO_EUNSUPPORTED, "na > 32");
-    if (op == OP_PPO) {
+    if (ppo) {
         if (!pr) return set_err(c, METRPO_ENULL, "ppo: params NULL");
         if (!b->d_old_mean || !b->d_old_log_std)
             return set_err(c, METRPO_EINVAL, "ppo: the PPO surrogate needs the old distribution (batch d_old_mean / d_old_log_std is NULL)");
         if (!(pr->clip_lr >= 0.0) || !std::isfinite(pr->entropy_bonus_coeff))
             return set_err(c, METRPO_EINVAL, "ppo: need clip_lr >= 0 and a finite entropy_bonus_coeff");
     }
+    if (op == OP_PPOKL) {
+        if (!kp) return set_err(c, METRPO_ENULL, "ppo_kl: KL penalty params NULL");
+        if (!(kp->kl_penalty >= 0.0) || !std::isfinite(kp->kl_penalty) || !std::isfinite(kp->step_size))
+            return set_err(c, METRPO_EINVAL, "ppo_kl: need a finite kl_penalty >= 0 and a finite step_size");
+    }
     if (op != OP_FVP && (!b->d_act || !b->d_adv || (!vpg && (!b->d_old_mean || !b->d_old_log_std))))
         return set_err(c, METRPO_ENULL, "batch pointer is NULL");
-    if ((vpg || op == OP_PPO) && !(b->inv_n_global > 0.0)) return set_err(c, METRPO_EINVAL, "batch inv_n_global must be positive");
+    if ((vpg || ppo) && !(b->inv_n_global > 0.0)) return set_err(c, METRPO_EINVAL, "batch inv_n_global must be positive");
     *u = UpdCall{};
     u->op = op; u->theta = c->d_theta.p;
     PolK& k = u->k;
     k.obs = b->d_obs; k.act = b->d_act; k.adv = b->d_adv; k.old_mean = b->d_old_mean; k.old_ls = b->d_old_log_std;
     k.ls_stride = b->old_log_std_stride; k.valid = b->d_valid; k.N = b->N; k.inv_n = (float)b->inv_n_global;
-    if (op == OP_PPO) { k.clip_lo = (float)(1.0 - pr->clip_lr); k.clip_hi = (float)(1.0 + pr->clip_lr); u->ent_coeff = pr->entropy_bonus_coeff; u->ent_in_reduction = true; }
+    if (op == OP_PPOKL) { k.kl_beta = (float)kp->kl_penalty; k.kl_delta = kp->step_size; }      // (k.mean_kl: set by the caller, to where the reduced mean KL will be)
+    if (ppo) { k.clip_lo = (float)(1.0 - pr->clip_lr); k.clip_hi = (float)(1.0 + pr->clip_lr); u->ent_coeff = pr->entropy_bonus_coeff; u->ent_in_reduction = true; }
     return METRPO_OK;
 }
 
@@ -479,10 +500,11 @@ static void finalize(metrpo_ctx* c, const UpdCall& u, const PartRows& r, hipStre
     // inside a fused update of a sharded run the reduction carries the cross-rank sum in its tail
     const XchgK xc = (u.scope.exchange_in_tail && c->xg_world > 1) ? xchg_next(c) : xchg_none();
     const dim3 grid((nout + FIN_C - 1) / FIN_C);
-    if (u.op == OP_PPO && u.adam)
+    const bool ppo = (u.op == OP_PPO || u.op == OP_PPOKL);   // (the penalty is all in the gradient kernel: both reduce alike)
+    if (ppo && u.adam)
         hipLaunchKernelGGL((k_finalize<true, true>), grid, dim3(1024), 0, st, c->pd, mode, r.nrows, r.stride, r.lk_col,
                            c->d_partials.p, c->d_theta.p, u.v64, u.out, none, xc, *u.adam);
-    else if (u.op == OP_PPO && u.ent_in_reduction) {
+    else if (ppo && u.ent_in_reduction) {
         AdamTail ent = {}; ent.ent_coeff = u.ent_coeff;
         hipLaunchKernelGGL((k_finalize<false, true>), grid, dim3(1024), 0, st, c->pd, mode, r.nrows, r.stride, r.lk_col,
                            c->d_partials.p, c->d_theta.p, u.v64, u.out, none, xc, ent);
@@ -501,7 +523,7 @@ static int launch_generic(metrpo_ctx* c, const UpdCall& u, int* nrows, hipStream
     const NetDesc& net = c->pd.pol;
     const PolK& k = u.k;
     int hrows = 0; for (int l = 0; l < net.n_layers; ++l) hrows += net.dims[l];
-    size_t rows = (u.op == OP_GRAD || u.op == OP_VPG || u.op == OP_PPO) ? hrows + c->pd.na : (u.op == OP_FVP) ? hrows + c->pd.na + (hrows - net.dims[0])
+    size_t rows = (u.op == OP_GRAD || u.op == OP_VPG || u.op == OP_PPO || u.op == OP_PPOKL) ? hrows + c->pd.na : (u.op == OP_FVP) ? hrows + c->pd.na + (hrows - net.dims[0])
                                                                          : (size_t)c->pd.ns + 2 * net.max_width;
     const size_t sh = rows * (PT + 1) * sizeof(float);
     if (sh > 160 * 1024) return METRPO_EUNSUPPORTED;
@@ -519,6 +541,9 @@ static int launch_generic(metrpo_ctx* c, const UpdCall& u, int* nrows, hipStream
     } else if (u.op == OP_PPO) {
         if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_loss_grad<PT, OP_PPO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
         hipLaunchKernelGGL((k_loss_grad<PT, OP_PPO>), dim3(g), dim3(PT), sh, st, c->pd, k, u.theta, c->d_partials.p);
+    } else if (u.op == OP_PPOKL) {
+        if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_loss_grad<PT, OP_PPOKL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+        hipLaunchKernelGGL((k_loss_grad<PT, OP_PPOKL>), dim3(g), dim3(PT), sh, st, c->pd, k, u.theta, c->d_partials.p);
     } else if (u.op == OP_FVP) {
         if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)k_fvp<PT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
         hipLaunchKernelGGL(k_fvp<PT>, dim3(g), dim3(PT), sh, st, c->pd, k, u.theta, u.vf, c->d_partials.p);
@@ -722,5 +747,73 @@ int run_ppo_update(metrpo_ctx* c, const metrpo_batch* b, const metrpo_ppo_params
         HIP_TRY(c, hipGetLastError());
         c->pol_adam_t = t1;
     }
+    return METRPO_OK;
+}
+
+// ---- 'ppo' with use_kl_penalty (ppo.py:120-121): loss += kl_penalty * max(0, mean_kl - step_size), semantics in include/metrpo.h ----
+// The [loss, mean KL] pair(s) the OP_LOSSKL reduction writes and the OP_PPOKL kernels read.
+static int ensure_ppo_kl(metrpo_ctx* c, int n_pairs) { return ws_grow(c, c->d_ppo_kl, sizeof(double) * 2 * (size_t)std::max(1, n_pairs)); }
+
+// OP_LOSSKL at the ctx theta + its reduction into pair[0..1]; summed over the ranks when `global` (in the reduction's tail where the scope says so, else by a
+// stand-alone all-reduce).  pair[1] = mean KL: every rank's share is over inv_n_global, so the ranks' sum is the global mean.
+static int ppo_kl_mean_kl(metrpo_ctx* c, const metrpo_batch* b, double* pair, bool exchange_in_tail, bool global, hipStream_t st) {
+    UpdCall u; int rc = make_call(c, OP_LOSSKL, b, &u); if (rc) return rc;
+    u.out = pair; u.scope.exchange_in_tail = exchange_in_tail;
+    if ((rc = run_update(c, u, st))) return rc;
+    if (global && !(exchange_in_tail && c->xg_world > 1) && (c->xg_world > 1 || c->nccl_comm)) return comm_allreduce_f64(c, pair, 2, st);
+    return METRPO_OK;
+}
+
+int launch_ppo_kl_loss_grad(metrpo_ctx* c, const metrpo_batch* b, const metrpo_ppo_params* pr, const metrpo_ppo_kl_params* kp, const double* d_mean_kl, double* out, hipStream_t st) {
+    UpdCall u; int rc = make_call(c, OP_PPOKL, b, &u, pr, kp); if (rc) return rc;
+    if (d_mean_kl == nullptr) {                              // computed here: the same launches metrpo_loss_kl makes, summed over an attached communicator's ranks
+        if ((rc = ensure_ppo_kl(c, 1)) || (rc = ppo_kl_mean_kl(c, b, c->d_ppo_kl.p, false, true, st))) return rc;
+        d_mean_kl = c->d_ppo_kl.p + 1;
+    }
+    u.k.mean_kl = d_mean_kl; u.out = out;
+    if ((rc = run_update(c, u, st))) return rc;
+    if (policy_gemm_applicable(c, b->N, false)) {            // (its own reduction: the entropy term follows as a launch, as in launch_ppo_loss_grad)
+        AdamTail ad = {}; ad.theta = c->d_theta.p; ad.ent_coeff = u.ent_coeff;
+        hipLaunchKernelGGL(k_ppo_step, dim3(1), dim3(1024), 0, st, out, c->pd.P, c->pd.pol.n_params, c->pd.na, 0, ad);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return METRPO_OK;
+}
+
+// run_ppo_update with, in front of each epoch's gradient launch, the OP_LOSSKL launch and reduction that leave the global mean KL of the theta entering the epoch
+// in pair e of d_ppo_kl; the OP_PPOKL kernels read it there and take the gate themselves.  Nothing here reads the device.
+int run_ppo_kl_update(metrpo_ctx* c, const metrpo_batch* b, const metrpo_ppo_params* pr, const metrpo_ppo_kl_params* kp, int n_epochs, double* d_losses, double* d_mean_kls,
+                      hipStream_t st) {
+    const int P = c->pd.P;
+    if (!pr) return set_err(c, METRPO_ENULL, "ppo_kl_update: params NULL");
+    if (n_epochs < 0) return set_err(c, METRPO_EINVAL, "ppo_kl_update: n_epochs must be >= 0");
+    if (!(pr->lr >= 0.0) || !(pr->beta1 >= 0.0 && pr->beta1 < 1.0) || !(pr->beta2 >= 0.0 && pr->beta2 < 1.0) || !(pr->eps >= 0.0))
+        return set_err(c, METRPO_EINVAL, "ppo_kl_update: need lr >= 0, 0 <= beta1, beta2 < 1, eps >= 0");
+    UpdCall u; int rc = make_call(c, OP_PPOKL, b, &u, pr, kp); if (rc) return rc;
+    if ((rc = ensure_policy_adam(c)) || (rc = ensure_ppo_kl(c, n_epochs))) return rc;
+    float* am = (float*)c->d_pol_adam.p;
+    double* gout = c->d_cg.p;                               // [1 + P] of the CG workspace (no update is open across this call)
+    const UpdFusion f = update_fusion(c, b->N, false);      // as run_ppo_update: the ranks must agree on it
+    const bool fused = f.carries_next_step();
+    u.out = gout; u.scope.exchange_in_tail = f.exchange_in_tail;
+    if (!fused) u.ent_in_reduction = false;
+    for (int e = 0; e < n_epochs; ++e) {
+        double* pair = c->d_ppo_kl.p + 2 * (size_t)e;
+        if ((rc = ppo_kl_mean_kl(c, b, pair, f.exchange_in_tail, true, st))) return rc;
+        u.k.mean_kl = pair + 1;
+        const int t1 = c->pol_adam_t + 1;                   // launch_policy_adam's bias correction (bptt.hip)
+        const double lr_t = pr->lr * std::sqrt(1.0 - std::pow(pr->beta2, (double)t1)) / (1.0 - std::pow(pr->beta1, (double)t1));
+        const AdamTail ad = {c->d_theta.p, am, am + P, (float)lr_t, (float)pr->beta1, (float)pr->beta2, (float)pr->eps, d_losses ? d_losses + e : nullptr, u.ent_coeff};
+        u.adam = fused ? &ad : nullptr;
+        if ((rc = run_update(c, u, st))) return rc;
+        if (!fused) {                                       // the stand-alone sequence of run_ppo_update, unchanged
+            if ((c->xg_world > 1 || c->nccl_comm) && (rc = comm_allreduce_f64(c, gout, P + 1, st))) return rc;
+            hipLaunchKernelGGL(k_ppo_step, dim3(1), dim3(1024), 0, st, gout, P, c->pd.pol.n_params, c->pd.na, 1, ad);
+        }
+        HIP_TRY(c, hipGetLastError());
+        c->pol_adam_t = t1;
+    }
+    if (d_mean_kls && n_epochs > 0)                         // column 1 of the pairs, one strided device-to-device copy behind the last epoch
+        HIP_TRY(c, hipMemcpy2DAsync(d_mean_kls, sizeof(double), c->d_ppo_kl.p + 1, 2 * sizeof(double), sizeof(double), (size_t)n_epochs, hipMemcpyDeviceToDevice, st));
     return METRPO_OK;
 }

@@ -211,7 +211,7 @@ class Engine(object):
 
     def last_update_launch(self):
         """Diagnostics: what the last policy-update launch ran on, as the host noted it when it enqueued it: dict(family 'generic' | 'mfma' | 'gemm' |
-        'fused3' (None before the first launch), op (the UpdOp as launched: 0 gradient, 1 FVP, 2 loss + KL, 3 cached FVP, 4 VPG, 5 PPO), table (index of the
+        'fused3' (None before the first launch), op (the UpdOp as launched: 0 gradient, 1 FVP, 2 loss + KL, 3 cached FVP, 4 VPG, 5 PPO, 6 PPO with the KL penalty), table (index of the
         fused 2 x 32 kernel set, -1 elsewhere), pt (sample tile of the generic kernels), nrows (partial rows of the reduction), splits / kchunk (GEMM path))."""
         out = (C.c_int32 * 7)()
         self._chk(lib.metrpo_debug_last_update(self._ctx, out))
@@ -521,6 +521,37 @@ class Engine(object):
         losses = torch.empty(int(n_epochs), dtype=torch.float64, device=self.device) if want_losses else None
         self._chk(lib.metrpo_ppo_update(self._ctx, C.byref(batch), C.byref(p), int(n_epochs), _ptr(losses), self._stream()))
         return losses
+
+    @staticmethod
+    def _ppo_kl_params(kl_penalty, step_size):
+        p = _lib.PpoKlParams()
+        p.kl_penalty, p.step_size = float(kl_penalty), float(step_size)
+        return p
+
+    def ppo_kl_loss_grad(self, batch, clip_lr=0.3, entropy_bonus_coeff=0.0, kl_penalty=1.0, step_size=0.01, mean_kl=None):
+        """ppo_loss_grad with the KL penalty kl_penalty * max(0, mean_kl - step_size) (algos/ppo.py:120-121): tensor [1 + P] float64.  mean_kl:
+        a float64 device tensor holding the GLOBAL mean KL at the ctx policy (loss_kl(batch)[1:2], summed over the ranks); None: computed by the
+        call.  The kernels read it on the device and take the gate (mean_kl - step_size > 0, strictly) themselves.  The surrogate and KL parts
+        are this rank's share; the entropy term follows ppo_loss_grad's convention."""
+        out = torch.empty(self.P + 1, dtype=torch.float64, device=self.device)
+        p, kp = self._ppo_params(clip_lr, entropy_bonus_coeff), self._ppo_kl_params(kl_penalty, step_size)
+        if mean_kl is not None:
+            mean_kl = torch.as_tensor(mean_kl, device=self.device).to(torch.float64).reshape(-1)[:1].contiguous()
+        self._chk(lib.metrpo_ppo_kl_loss_grad(self._ctx, C.byref(batch), C.byref(p), C.byref(kp), _ptr(mean_kl), _ptr(out), self._stream()))
+        return out
+
+    def ppo_kl_update(self, batch, n_epochs=10, clip_lr=0.3, entropy_bonus_coeff=0.0, kl_penalty=1.0, step_size=0.01, lr=1e-3, beta1=0.9, beta2=0.999,
+                      eps=1e-8, want_losses=True, want_mean_kls=False):
+        """ppo_update with the KL penalty: each epoch first leaves the global mean KL of the theta entering it on the device (loss_kl's launches,
+        summed over the ranks by the communicator attached to this engine), then runs the gradient launch that reads it and the reduction with
+        the Adam step.  Stream-ordered, no synchronisation and no host read between the epochs.  -> the n_epochs losses (None with
+        want_losses=False); with want_mean_kls=True the pair (losses, mean_kls), mean_kls[e] = the mean KL entering epoch e."""
+        self._close_open_update()
+        p, kp = self._ppo_params(clip_lr, entropy_bonus_coeff, lr, beta1, beta2, eps), self._ppo_kl_params(kl_penalty, step_size)
+        losses = torch.empty(int(n_epochs), dtype=torch.float64, device=self.device) if want_losses else None
+        kls = torch.empty(int(n_epochs), dtype=torch.float64, device=self.device) if want_mean_kls else None
+        self._chk(lib.metrpo_ppo_kl_update(self._ctx, C.byref(batch), C.byref(p), C.byref(kp), int(n_epochs), _ptr(losses), _ptr(kls), self._stream()))
+        return (losses, kls) if want_mean_kls else losses
 
     def fvp(self, batch, v):
         v = torch.as_tensor(v, device=self.device).to(torch.float64).contiguous()

@@ -182,7 +182,8 @@ class AdamOptimizer(object):
     """The optimiser algos/ppo.py:61-62 names (`AdamOptimizer()`) but never imports or defines; stated here: n_epochs full-batch
     tf.train.AdamOptimizer steps (beta1 0.9, beta2 0.999, epsilon 1e-8, no gradient clipping) on every policy parameter including log_std.
     The Adam state is the engine's policy optimizer state (Engine.get_policy_adam / set_policy_adam); it is never reset here, exactly as
-    FirstOrderOptimizer treats it for VPG.  Minibatches (batch_size other than None) are not built."""
+    FirstOrderOptimizer treats it for VPG.  Minibatches (batch_size other than None) are not built.
+    loss / optimize take PPO's KL penalty as kl_penalty and step_size (ppo.py:120-121; None: the loss without it)."""
 
     def __init__(self, learning_rate=1e-3, n_epochs=10, batch_size=None, beta1=0.9, beta2=0.999, epsilon=1e-8, **kwargs):
         if batch_size is not None:
@@ -195,13 +196,25 @@ class AdamOptimizer(object):
     def update_opt(self, loss, target, inputs, diagnostic_vars=None, **kwargs):
         self._target = target            # the loss graph itself (ppo.py:107-119) is what the HIP kernels compute
 
-    def loss(self, engine, batch, clip_lr, entropy_bonus_coeff, comm=None):
+    @staticmethod
+    def _kl_loss_grad(engine, batch, clip_lr, ent, kl_penalty, step_size, comm, need):
+        """ppo_kl_loss_grad behind the global mean KL: a host-driven all-reduce sums loss_kl's share first and hands the result to the gradient call."""
+        if need and not getattr(engine, 'comm_world', 0):
+            mean_kl = comm.allreduce_sum_(engine.loss_kl(batch))[1:2]
+            return engine.ppo_kl_loss_grad(batch, clip_lr, ent, kl_penalty, step_size, mean_kl=mean_kl)
+        return engine.ppo_kl_loss_grad(batch, clip_lr, ent, kl_penalty, step_size)
+
+    def loss(self, engine, batch, clip_lr, entropy_bonus_coeff, comm=None, kl_penalty=None, step_size=0.01):
         """ppo.py:169 / :177 optimizer.loss: the penalised clipped surrogate at the current theta, summed over the ranks (1-element tensor)."""
         comm = comm or Comm()
-        out = engine.ppo_loss_grad(batch, clip_lr, entropy_bonus_coeff / max(1, comm.world))[:1].clone()
-        return comm.allreduce_sum_(out) if (comm.world > 1 or comm.always_reduce) else out
+        need = comm.world > 1 or comm.always_reduce
+        if kl_penalty is None:
+            out = engine.ppo_loss_grad(batch, clip_lr, entropy_bonus_coeff / max(1, comm.world))[:1].clone()
+        else:
+            out = self._kl_loss_grad(engine, batch, clip_lr, entropy_bonus_coeff / max(1, comm.world), kl_penalty, step_size, comm, need)[:1].clone()
+        return comm.allreduce_sum_(out) if need else out
 
-    def optimize(self, engine, batch, clip_lr, entropy_bonus_coeff, comm=None):
+    def optimize(self, engine, batch, clip_lr, entropy_bonus_coeff, comm=None, kl_penalty=None, step_size=0.01):
         """n_epochs Adam steps.  With a communicator attached to the engine (Comm.attach_engine) or at world size 1 the whole of it is
         Engine.ppo_update (no host involvement between the epochs); otherwise each epoch's gradient share is all-reduced on the host (Comm,
         e.g. gloo) and the step follows as Engine.policy_adam_step with no clipping.  -> the losses at the theta entering each epoch."""
@@ -210,10 +223,18 @@ class AdamOptimizer(object):
         if need and not getattr(engine, 'comm_world', 0):
             losses = []
             for _ in range(self.n_epochs):
-                lg = comm.allreduce_sum_(engine.ppo_loss_grad(batch, clip_lr, entropy_bonus_coeff / comm.world))
+                if kl_penalty is None:
+                    lg = engine.ppo_loss_grad(batch, clip_lr, entropy_bonus_coeff / comm.world)
+                else:                                   # the ranks' KL shares are summed first: the gate is taken on the global mean
+                    lg = self._kl_loss_grad(engine, batch, clip_lr, entropy_bonus_coeff / comm.world, kl_penalty, step_size, comm, True)
+                lg = comm.allreduce_sum_(lg)
                 engine.policy_adam_step(lg[1:], self.learning_rate, clip_val=None, beta1=self.beta1, beta2=self.beta2, eps=self.epsilon)
                 losses.append(lg[:1])
             self.last_losses = torch.cat(losses) if losses else torch.empty(0, dtype=torch.float64, device=engine.device)
+        elif kl_penalty is not None:
+            self.last_losses = engine.ppo_kl_update(batch, n_epochs=self.n_epochs, clip_lr=clip_lr, entropy_bonus_coeff=entropy_bonus_coeff,
+                                                    kl_penalty=kl_penalty, step_size=step_size, lr=self.learning_rate, beta1=self.beta1,
+                                                    beta2=self.beta2, eps=self.epsilon)
         else:
             self.last_losses = engine.ppo_update(batch, n_epochs=self.n_epochs, clip_lr=clip_lr, entropy_bonus_coeff=entropy_bonus_coeff,
                                                  lr=self.learning_rate, beta1=self.beta1, beta2=self.beta2, eps=self.epsilon)

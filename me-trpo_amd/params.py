@@ -11,12 +11,13 @@ Keys read (params-swimmer.json:5-86):
     policy_opt_params.{T, gamma, mode, whole, log_every, num_iters_threshold, max_iters, batch_size, sam_mode, learning_rate, grad_norm_clipping,
                        stop_critereon.{threshold, offset, percent_models_threshold}, trpo.{init_std, step_size, discount, batch_size, reset},
                        vpg.{init_std, discount, batch_size, reset},
-                       ppo.{init_std, discount, batch_size, reset, clip_lr, n_epochs, learning_rate, entropy_bonus_coeff}}
+                       ppo.{init_std, discount, batch_size, reset, clip_lr, n_epochs, learning_rate, entropy_bonus_coeff,
+                            use_kl_penalty, initial_kl_penalty, step_size}}
     dynamics_opt_params.{learning_rate.{scratch, refine}, batch_size, max_passes, log_every, num_passes_threshold, sample_mode, reinitialize,
                          stop_critereon.{threshold, offset}}
 'algo' builds 'trpo', 'vpg' (training.py:337-352: VPG with the vpg block's batch size, discount and log_std reset), 'bptt' and 'bptt-stochastic';
 svg and l-bfgs raise.  'ppo' (algos/ppo.py) is an EXTENSION: the reference's training.py has no such branch and its params files no ppo block; the
-block's defaults are ppo.py's (clip_lr 0.3, entropy_bonus_coeff 0), AdamOptimizer's (n_epochs 10, learning_rate 1e-3) and the vpg block's.  Everything else in the files (rollout_params, sweep_iters, sample_size, *_path) steers the reference's real-simulator data collection and outer
+block's defaults are ppo.py's (clip_lr 0.3, entropy_bonus_coeff 0, use_kl_penalty false, initial_kl_penalty 1, step_size 0.01), AdamOptimizer's (n_epochs 10, learning_rate 1e-3) and the vpg block's.  Everything else in the files (rollout_params, sweep_iters, sample_size, *_path) steers the reference's real-simulator data collection and outer
 sweeps, which are out of scope here; those keys are passed through untouched in `Setup.params`."""
 import json
 
@@ -76,6 +77,9 @@ def shapes_from_params(path_or_dict):
         ppo=dict(discount=float(ppo.get('discount', 1.0)), init_std=float(ppo.get('init_std', 1.0)), batch_size=int(ppo.get('batch_size', 5000)),
                  reset=bool(ppo.get('reset', True)), clip_lr=float(ppo.get('clip_lr', 0.3)), n_epochs=int(ppo.get('n_epochs', 10)),
                  learning_rate=float(ppo.get('learning_rate', 1e-3)), entropy_bonus_coeff=float(ppo.get('entropy_bonus_coeff', 0.0))),
+        # the KL penalty's keys of the same params block (ppo.py:27-28, :34), kept apart from the dict above
+        ppo_kl=dict(use_kl_penalty=bool(ppo.get('use_kl_penalty', False)), initial_kl_penalty=float(ppo.get('initial_kl_penalty', 1.0)),
+                    step_size=float(ppo.get('step_size', 0.01))),
         optimize_policy=dict(T=T, gamma=float(po.get('gamma', 1.0)), mode=po.get('mode', 'estimated'), whole=bool(po.get('whole', True)),
                              log_every=int(po.get('log_every', 5)), num_iters_threshold=int(po.get('num_iters_threshold', 25)),
                              max_iters=int(po.get('max_iters', 400))),
@@ -132,7 +136,8 @@ def from_params(path_or_dict, device=0, init_states=None, comm=None, seed=0, n_e
                    sampler_args=sargs, comm=comm, seed=seed)
     elif sh['algo'] == 'ppo':
         algo = PPO(env=env, policy=policy, baseline=baseline, batch_size=sh['batch_size'], max_path_length=sh['T'], discount=blk['discount'],
-                   clip_lr=blk['clip_lr'], entropy_bonus_coeff=blk['entropy_bonus_coeff'],
+                   clip_lr=blk['clip_lr'], entropy_bonus_coeff=blk['entropy_bonus_coeff'], use_kl_penalty=sh['ppo_kl']['use_kl_penalty'],
+                   initial_kl_penalty=sh['ppo_kl']['initial_kl_penalty'], step_size=sh['ppo_kl']['step_size'],
                    optimizer=AdamOptimizer(learning_rate=blk['learning_rate'], n_epochs=blk['n_epochs']), sampler_args=sargs, comm=comm, seed=seed)
     else:
         algo = TRPO(env=env, policy=policy, baseline=baseline, batch_size=sh['batch_size'], max_path_length=sh['T'], discount=sh['trpo']['discount'],
