@@ -425,6 +425,37 @@ int32_t metrpo_trpo_update_begin(metrpo_ctx* ctx, const metrpo_batch* batch, con
                                  double* d_g_out, double* d_dir_out, void* stream);
 int32_t metrpo_trpo_update_end(metrpo_ctx* ctx, metrpo_trpo_diag* diag, int32_t* late_out, void* stream);
 
+/* ---- subsampled Fisher-vector products ([rllab] ConjugateGradientOptimizer(subsample_factor < 1).optimize):
+ *         n = len(inputs[0]);  inds = np.random.choice(n, int(n * subsample_factor), replace=False)
+ *         subsample_inputs = tuple(x[inds] for x in inputs)
+ *     loss_before, flat_g and every f_loss_constraint trial use `inputs`; Hx = f_Hx_plain(subsample_inputs) + reg_coeff * x is what krylov.cg and
+ *     descent_direction.dot(Hx(descent_direction)) see, the mean KL inside it being the mean over the subsample; one draw per optimize call.
+ * All additions to ABI 4: no struct of this header changes, METRPO_ABI_VERSION stays. */
+/* The gather x[inds] on the device.  d_idx [m] int32 row indices into `batch` (any order, duplicates allowed); rows are gathered in index order into
+ * compact arrays in a ctx-owned workspace and *out is filled to describe them: d_obs [m][ns], d_old_mean [m][na] (NULL if the source's is), d_old_log_std
+ * [m][na] for a per-sample source (stride na) -- a broadcast source (stride 0) stays the CALLER's pointer, not expanded --, d_valid [m] (NULL if the
+ * source's is), N = m, inv_n_global as given (the sub-batch's: 1 / its valid samples over all ranks; the caller may overwrite the field of *out later).
+ * d_act and d_adv of *out are NULL: these are the fields the Fisher-vector-product kernels and the old distribution need; the sub-batch serves
+ * metrpo_fvp and the fvp_batch argument below, not the loss entry points.
+ * The workspace, and with it *out, stays valid until the next metrpo_subsample_batch on this ctx or metrpo_destroy (it grows by the rule of the
+ * Conventions: an outgrown buffer is kept, never freed here, so launches already enqueued on it stay correct).
+ * d_valid_count (optional, one device double): the number of valid gathered rows is ADDED to it (caller zeroes; a sharded caller all-reduces it
+ * with metrpo_allreduce_sum_f64 / its own transport to obtain the denominator of inv_n_global).
+ * An index outside [0, N) is clamped into the batch -- no read outside it -- and raises a sticky device cell: the next metrpo_trpo_update_fvp on this
+ * ctx (after it completed) or metrpo_comm_check returns METRPO_EINVAL once.  Stream-ordered, no synchronisation.  N and m below 2^31. */
+int32_t metrpo_subsample_batch(metrpo_ctx* ctx, const metrpo_batch* batch, const int32_t* d_idx, int64_t m, double inv_n_global, metrpo_batch* out,
+                               double* d_valid_count, void* stream);
+/* metrpo_trpo_update / metrpo_trpo_update_begin with a separate batch for Hx: the cg_iters Fisher-vector products, and the explicit final one under
+ * explicit_final_hvp, run on fvp_batch (their partials pre-scaled by ITS inv_n_global); gradient, loss_before and the line search run on batch.
+ * The activation caches a whole-batch solve keeps between its gradient launch and its products belong to `batch`: with a separate fvp_batch the
+ * products run uncached and nothing is cached.  fvp_batch NULL, == batch, or equal to it field by field: exactly the launches
+ * and results of metrpo_trpo_update / _begin.  A _begin of this form is closed by metrpo_trpo_update_end like any other (its trials see `batch` only);
+ * fvp_batch must stay valid until the launches of _begin have run (a metrpo_subsample_batch workspace does: it changes only in stream order). */
+int32_t metrpo_trpo_update_fvp(metrpo_ctx* ctx, const metrpo_batch* batch, const metrpo_batch* fvp_batch, const metrpo_trpo_params* params,
+                               metrpo_trpo_diag* diag, double* d_g_out, double* d_dir_out, void* stream);
+int32_t metrpo_trpo_update_fvp_begin(metrpo_ctx* ctx, const metrpo_batch* batch, const metrpo_batch* fvp_batch, const metrpo_trpo_params* params,
+                                     int32_t spec_trials, double* d_g_out, double* d_dir_out, void* stream);
+
 /* ---- "next" rows of the scope table: ensemble dynamics training + normaliser statistics ---- */
 typedef struct {
     double lr;                   /* dynamics_opt_params.learning_rate["scratch"|"refine"] (model_based_rl.py:905-918)      */

@@ -211,13 +211,13 @@ extern "C" int32_t metrpo_create(metrpo_ctx** out, int32_t device, const metrpo_
     if (hipSetDevice(device) != hipSuccess) { c->err = "hipSetDevice failed"; return METRPO_EHIP; }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_sm = prop.multiProcessorCount;
-    const size_t ncg = (size_t)(1 + pd.P) + 5 * (size_t)pd.P + 8 + 2 + 4 + 1;      // ... | scal[8] | lk[2] | ls[4] | validation time-out cell (val_err_cell)
+    const size_t ncg = (size_t)(1 + pd.P) + 5 * (size_t)pd.P + 8 + 2 + 4 + 2;      // ... | scal[8] | lk[2] | ls[4] | validation time-out cell (val_err_cell) | sub-batch index cell (sub_err_cell)
     int rc;
     if ((rc = ws_grow(c, c->d_dyn, sizeof(float) * (size_t)pd.K * pd.dyn.n_params)) || (rc = ws_grow(c, c->d_norm, sizeof(float) * (2 * (pd.ns + pd.na) + 2 * pd.ns))) ||
         (rc = ws_grow(c, c->d_theta, sizeof(float) * pd.P)) || (rc = ws_grow(c, c->d_vf, sizeof(float) * pd.P)) || (rc = ws_grow(c, c->d_theta_try, sizeof(float) * pd.P)) ||
         (rc = ws_grow(c, c->d_cg, sizeof(double) * ncg)) || (rc = ws_grow(c, c->d_valbuf, sizeof(double) * pd.K)) || (rc = ws_grow(c, c->d_ticket, sizeof(unsigned int))))
         return rc;
-    if (hipHostMalloc(&c->h_pinned, sizeof(double) * 16) != hipSuccess) { c->err = "pinned host allocation failed"; return METRPO_EHIP; }
+    if (hipHostMalloc(&c->h_pinned, sizeof(double) * 24) != hipSuccess) { c->err = "pinned host allocation failed"; return METRPO_EHIP; }
     if (hipMemset(c->d_dyn.p, 0, sizeof(float) * (size_t)pd.K * pd.dyn.n_params) != hipSuccess) { c->err = "hipMemset failed"; return METRPO_EHIP; }
     if (hipMemset(c->d_cg.p, 0, sizeof(double) * ncg) != hipSuccess) { c->err = "hipMemset failed"; return METRPO_EHIP; }   // scal[S_COMMERR] starts clear
     if (hipMemset(c->d_ticket.p, 0, sizeof(unsigned int)) != hipSuccess) { c->err = "hipMemset failed"; return METRPO_EHIP; }   // the reductions' arrival counter resets itself
@@ -758,13 +758,13 @@ __global__ void k_try_theta(int P, double ratio, const float* __restrict__ prev,
 //        1 = metrpo_trpo_update_begin: solve + the first `spec` line-search trials enqueued with the accept test on the DEVICE (ls_decide), no
 //            synchronisation; 2 = metrpo_trpo_update_end: fetch the outcome, continue on the host from trial `spec` if the search has not stopped
 static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metrpo_trpo_params* pr, metrpo_trpo_diag* diag,
-                                double* g_out, double* dir_out, hipStream_t st, int phase, int spec);
+                                double* g_out, double* dir_out, hipStream_t st, int phase, int spec, const metrpo_batch* fb);
 // The arrival counter of the fused tails (d_ticket) resets itself in the last block of every reduction, so a completed update leaves it
 // at zero.  An update that FAILED half-way (a launch error, a time-out) may not: it is cleared on the error path, where the cost of a
 // 4-byte memset does not matter -- a stale count would silently disable every later CG tail.
 int run_trpo_update(metrpo_ctx* c, const metrpo_batch* b, const metrpo_trpo_params* pr, metrpo_trpo_diag* diag,
-                    double* g_out, double* dir_out, hipStream_t st, int phase, int spec) {
-    const int rc = run_trpo_update_impl(c, b, pr, diag, g_out, dir_out, st, phase, spec);
+                    double* g_out, double* dir_out, hipStream_t st, int phase, int spec, const metrpo_batch* fb) {
+    const int rc = run_trpo_update_impl(c, b, pr, diag, g_out, dir_out, st, phase, spec, fb);
     if (rc != METRPO_OK) {
         (void)hipGetLastError(); (void)hipMemsetAsync(c->d_ticket.p, 0, sizeof(unsigned int), st); c->upd_pending = 0;
     }
@@ -775,9 +775,18 @@ int run_trpo_update(metrpo_ctx* c, const metrpo_batch* b, const metrpo_trpo_para
 static bool device_line_search_ok(const metrpo_ctx* c, const metrpo_batch* b, const metrpo_trpo_params* pr) {
     return update_fusion(c, b->N, pr->allreduce != nullptr).carries_next_step();
 }
+// fb == b in every field (or NULL) is the whole-batch update: the launches and results of ABI 4's entry points, bit for bit
+static bool same_batch(const metrpo_batch* a, const metrpo_batch* b) {
+    return a->d_obs == b->d_obs && a->d_act == b->d_act && a->d_adv == b->d_adv && a->d_old_mean == b->d_old_mean && a->d_old_log_std == b->d_old_log_std &&
+           a->old_log_std_stride == b->old_log_std_stride && a->d_valid == b->d_valid && a->N == b->N && a->inv_n_global == b->inv_n_global;
+}
 static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metrpo_trpo_params* pr, metrpo_trpo_diag* diag,
-                                double* g_out, double* dir_out, hipStream_t st, int phase, int spec) {
+                                double* g_out, double* dir_out, hipStream_t st, int phase, int spec, const metrpo_batch* fb) {
     const int P = c->pd.P;
+    // [rllab] optimize(): loss_before, flat_g and every f_loss_constraint trial see `inputs` (b); Hx -- the cg_iters products of krylov.cg and the
+    // d.(H d) of the step scale -- sees subsample_inputs (fb).  The partials of those launches are pre-scaled by fb's inv_n_global.
+    const bool sub = fb != nullptr && fb != b && !same_batch(fb, b);
+    const metrpo_batch* hb = sub ? fb : b;
     CgView v = cg_view(c);
     int rc;
     // sum over ranks: the caller's callback if given, else the RCCL communicator attached to the ctx (comm.hip), else single rank
@@ -811,6 +820,9 @@ static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metr
     solve.cache_activations = true;      // the gradient kernel publishes tanh activations, the CG products of this solve reuse them
     // ... and, when every CG vector comes out of a fused tail, its weight-fragment image; the tails add the tangent entries (policy_mfma.hip)
     solve.publish_image = fused && c->pol_mfma >= 0 && fusion.finalize_reduces;
+    // A separate FVP batch: the activation caches and the weight-fragment image a gradient launch leaves (d_hcache / OP_FVPC, d_f3, the GEMM path's forward pass)
+    // belong to `b` and must not be read for `fb`.  Its products run uncached (OP_FVP) and nothing is cached for them: DESIGN.md section 1 (row a16s)
+    if (sub) solve = search;
     if (solve.publish_image) {
         if ((rc = policy_mfma_image_buffers(c))) return rc;
         tl.vpos = c->d_pol_vpos.p; tl.imgval = c->d_pol_imgval.p;
@@ -829,7 +841,7 @@ static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metr
     for (int i = 0; i < pr->cg_iters; ++i) {
         tl.op = 1; tl.last = (i == pr->cg_iters - 1) ? 1 : 0;
         if (fold_try && tl.last && implicit_hd) arm_try0();
-        if ((rc = launch_fvp_tail(c, b, c->d_vf.p, v.p, v.z, fused ? &tl : nullptr, st, solve))) return rc;
+        if ((rc = launch_fvp_tail(c, hb, c->d_vf.p, v.p, v.z, fused ? &tl : nullptr, st, solve))) return rc;
         if (fused) continue;
         AR(v.z, P);
         hipLaunchKernelGGL(k_cg_step, dim3(1), dim3(1024), 0, st, tl, pr->cg_iters);
@@ -837,7 +849,7 @@ static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metr
     if (!implicit_hd && pr->cg_iters > 0) {                      // rllab's literal route: one more f_Hx on the descent direction
         tl.op = 2; tl.last = 0;
         if (fused && fold_try) arm_try0();
-        if ((rc = launch_fvp_tail(c, b, c->d_vf.p, v.x, v.z, fused ? &tl : nullptr, st, solve))) return rc;
+        if ((rc = launch_fvp_tail(c, hb, c->d_vf.p, v.x, v.z, fused ? &tl : nullptr, st, solve))) return rc;
         if (!fused) {
             AR(v.z, P);
             hipLaunchKernelGGL(k_cg_finish, dim3(1), dim3(1024), 0, st, P, pr->reg_coeff, pr->max_kl, v.x, v.z, v.step, v.scal);
@@ -871,6 +883,7 @@ static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metr
         return METRPO_OK;
     }
     // read-backs: ONE copy per line-search trial fetches scal[8] | lk[2] | ls[4] (loss at theta, beta, CG iterations, trial loss and KL)
+    if (sub) HIP_TRY(c, hipMemcpyAsync(c->h_pinned + 16, sub_err_cell(c), sizeof(double), hipMemcpyDeviceToHost, st));      // (rides in front of the first trial's synchronisation)
     double loss = NAN, kl = NAN, loss_before = NAN;
     int n_iter = 0, n_start = 0;
     bool first = true, stopped = false, taken = false;
@@ -928,6 +941,10 @@ static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metr
     }
     HIP_TRY(c, hipGetLastError());
 #undef AR
+    if (sub && c->h_pinned[16] != 0.0) {                        // the update is complete; the sub-batch it used was gathered from clamped rows
+        (void)hipMemsetAsync(sub_err_cell(c), 0, sizeof(double), st);
+        return set_err(c, METRPO_EINVAL, "trpo_update: the FVP sub-batch was gathered with a row index outside [0, N) (clamped by metrpo_subsample_batch)");
+    }
     return METRPO_OK;
 }
 
@@ -963,6 +980,41 @@ extern "C" int32_t metrpo_trpo_update_begin(metrpo_ctx* c, const metrpo_batch* b
         return rc;
     }
     return run_trpo_update(c, b, pr, nullptr, g_out, dir_out, (hipStream_t)stream, 1, spec_trials);
+}
+// ---- subsampled Fisher-vector products ([rllab] ConjugateGradientOptimizer subsample_factor < 1; include/metrpo.h) ----
+extern "C" int32_t metrpo_subsample_batch(metrpo_ctx* c, const metrpo_batch* b, const int32_t* d_idx, int64_t m, double inv_n_global, metrpo_batch* out,
+                                          double* d_valid_count, void* stream) {
+    TraceRange trace_("metrpo:subsample_batch");
+    if (!c) return METRPO_ENULL;
+    if (!b || !d_idx || !out || !b->d_obs) return set_err(c, METRPO_ENULL, "subsample_batch: NULL pointer");
+    if (b->N <= 0 || m <= 0 || m > 2147483647LL) return set_err(c, METRPO_EINVAL, "subsample_batch: N and m must be positive (m < 2^31)");
+    if (!(inv_n_global > 0.0)) return set_err(c, METRPO_EINVAL, "subsample_batch: inv_n_global must be positive");
+    return launch_subsample(c, b, d_idx, m, inv_n_global, out, d_valid_count, (hipStream_t)stream);
+}
+extern "C" int32_t metrpo_trpo_update_fvp(metrpo_ctx* c, const metrpo_batch* b, const metrpo_batch* fvp_batch, const metrpo_trpo_params* pr,
+                                          metrpo_trpo_diag* diag, double* g_out, double* dir_out, void* stream) {
+    TraceRange trace_("metrpo:trpo_update_fvp (optimize_policy, subsampled Hx)");
+    if (!c) return METRPO_ENULL;
+    NEED_POL(c);
+    if (!b || !pr) return set_err(c, METRPO_ENULL, "trpo_update_fvp: NULL pointer");
+    if (pr->cg_iters < 0 || pr->max_backtracks < 1) return set_err(c, METRPO_EINVAL, "trpo_update_fvp: bad cg_iters/max_backtracks");
+    if (c->upd_pending) return set_err(c, METRPO_ESTATE, "trpo_update_fvp: an update begun with metrpo_trpo_update_begin is still open (call metrpo_trpo_update_end)");
+    return run_trpo_update(c, b, pr, diag, g_out, dir_out, (hipStream_t)stream, 0, 0, fvp_batch);
+}
+extern "C" int32_t metrpo_trpo_update_fvp_begin(metrpo_ctx* c, const metrpo_batch* b, const metrpo_batch* fvp_batch, const metrpo_trpo_params* pr,
+                                                int32_t spec_trials, double* g_out, double* dir_out, void* stream) {
+    TraceRange trace_("metrpo:trpo_update_fvp_begin (optimize_policy, subsampled Hx, line search decided on the device)");
+    if (!c) return METRPO_ENULL;
+    NEED_POL(c);
+    if (!b || !pr) return set_err(c, METRPO_ENULL, "trpo_update_fvp_begin: NULL pointer");
+    if (pr->cg_iters < 0 || pr->max_backtracks < 1 || spec_trials < 1) return set_err(c, METRPO_EINVAL, "trpo_update_fvp_begin: bad cg_iters / max_backtracks / spec_trials");
+    if (c->upd_pending) return set_err(c, METRPO_ESTATE, "trpo_update_fvp_begin: the previous update is still open (call metrpo_trpo_update_end)");
+    if (!device_line_search_ok(c, b, pr)) {
+        const int rc = run_trpo_update(c, b, pr, &c->upd_diag, g_out, dir_out, (hipStream_t)stream, 0, 0, fvp_batch);
+        if (rc == METRPO_OK) { c->upd_pending = 2; c->upd_spec = pr->max_backtracks; }
+        return rc;
+    }
+    return run_trpo_update(c, b, pr, nullptr, g_out, dir_out, (hipStream_t)stream, 1, spec_trials, fvp_batch);      // (the line search of _end sees `b` alone)
 }
 extern "C" int32_t metrpo_trpo_update_end(metrpo_ctx* c, metrpo_trpo_diag* diag, int32_t* late_out, void* stream) {
     TraceRange trace_("metrpo:trpo_update_end");

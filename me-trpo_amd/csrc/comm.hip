@@ -220,9 +220,14 @@ extern "C" int32_t metrpo_comm_transport(const metrpo_ctx* c) {
 extern "C" int32_t metrpo_comm_check(metrpo_ctx* c, void* stream) {
     if (!c) return METRPO_ENULL;
     HIP_TRY(c, hipMemcpyAsync(c->h_pinned + 14, comm_err_cell(c), 2 * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(c, hipMemcpyAsync(c->h_pinned + 16, sub_err_cell(c), sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIP_TRY(c, hipStreamSynchronize((hipStream_t)stream));
     if (c->h_pinned[15] != 0.0) return rollout_error_seen(c, (hipStream_t)stream);
     if (c->h_pinned[14] != 0.0) return set_err(c, METRPO_EHIP, "one-shot all-reduce: a rank did not arrive within the time limit (METRPO_XCHG_TIMEOUT_MS)");
+    if (c->h_pinned[16] != 0.0) {                              // metrpo_subsample_batch clamped a row index (cleared: the next gather starts clean)
+        (void)hipMemsetAsync(sub_err_cell(c), 0, sizeof(double), (hipStream_t)stream);
+        return set_err(c, METRPO_EINVAL, "subsample_batch: a row index outside [0, N) was clamped into the batch");
+    }
     return METRPO_OK;
 }
 

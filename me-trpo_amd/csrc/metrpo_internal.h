@@ -99,6 +99,7 @@ struct metrpo_ctx {
     DevBuf<double> d_gram_part;    // per-block Gram partials (process.hip)
     DevBuf<unsigned int> d_ticket; // arrival counter of k_finalize's fused CG tail
     DevBuf<float> d_hcache;        // activation cache of one CG solve (policy_mfma.hip OP_FVPC)
+    DevBuf<void> d_sub;            // metrpo_subsample_batch: the gathered sub-batch (obs | old_mean | old_log_std | valid), valid until the next call of that entry point
     DevBuf<double> d_ppo_kl;       // run_ppo_kl_update / launch_ppo_kl_loss_grad: one [loss, mean KL] pair per epoch, written by the OP_LOSSKL reduction and read by the OP_PPOKL kernels
     DevBuf<void> d_mig; int mig_epoch = 0;        // rollout_coop.hip: hand-over slots of migrating tiles (flag | ts | model | obs per tile)
     void* nccl_comm = nullptr; int comm_world = 0, comm_rank = 0;   // comm.hip: RCCL communicator attached by metrpo_comm_init (NULL: single rank)
@@ -373,6 +374,9 @@ static inline double* comm_err_cell(metrpo_ctx* c) { return c->d_cg.p + (size_t)
 // time-out cell of the resident VALIDATION launches (behind scal | lk | ls): cleared in front of every such launch, so an earlier rollout's sticky S_ROLLERR
 // cannot poison validation costs and a validation time-out cannot be mistaken for a rollout's
 static inline double* val_err_cell(metrpo_ctx* c) { return comm_err_cell(c) + 8; }
+// sticky cell of metrpo_subsample_batch (behind the validation cell): raised by the gather kernel when it had to clamp a row index outside [0, N);
+// reported and cleared by the next metrpo_trpo_update_fvp / metrpo_comm_check
+static inline double* sub_err_cell(metrpo_ctx* c) { return comm_err_cell(c) + 9; }
 // A rollout kernel reported a timed-out hand-over (scal[S_ROLLERR]): the trajectories of that launch are invalid.  The cell is cleared so the
 // context can go on, and the resident kernel -- the one whose hand-overs need every workgroup of its grid on the chip at once -- is retired.
 static inline int rollout_error_seen(metrpo_ctx* c, hipStream_t st) {
@@ -415,5 +419,8 @@ int launch_fvp(metrpo_ctx*, const metrpo_batch*, const double*, double*, hipStre
 // vf = float copy of v already on the device (skips the conversion launch); v is still needed for the log_std rows
 int launch_fvp_tail(metrpo_ctx*, const metrpo_batch*, const float* vf, const double* v, double* hv, const CgTail* tail, hipStream_t, SolveScope = {});
 int launch_loss_kl(metrpo_ctx*, const metrpo_batch*, const float*, double*, hipStream_t, const CgTail* decide = nullptr, SolveScope = {});   // decide: op 4 tail (device-side accept test)
+// fvp_batch: the batch the Fisher-vector products see ([rllab] subsample_inputs); NULL or the same batch = the whole batch (the launches of ABI 4's update)
 int run_trpo_update(metrpo_ctx*, const metrpo_batch*, const metrpo_trpo_params*, metrpo_trpo_diag*, double*,
-                    double*, hipStream_t, int phase = 0, int spec = 0);
+                    double*, hipStream_t, int phase = 0, int spec = 0, const metrpo_batch* fvp_batch = nullptr);
+// policy_update.hip: gather of the rows d_idx[0 .. m) of `b` into c->d_sub (metrpo_subsample_batch)
+int launch_subsample(metrpo_ctx*, const metrpo_batch* b, const int32_t* d_idx, long long m, double inv_n_global, metrpo_batch* out, double* d_valid_count, hipStream_t);

@@ -473,6 +473,40 @@ class Engine(object):
         b._keep = (obs, act, adv, old_mean, old_log_std, valid)
         return b
 
+    def subsample_batch(self, batch, idx, n_global_sub=None):
+        """[rllab] ConjugateGradientOptimizer.optimize, subsample_factor < 1: subsample_inputs = tuple(x[inds] for x in inputs), gathered on the
+        device (metrpo_subsample_batch).  idx: int32 row indices into `batch` (any order, duplicates allowed).  -> a Batch of len(idx) rows for fvp()
+        and trpo_update(fvp_batch=...): observations, old distribution and valid flags live in an engine-owned workspace that stays valid until the
+        next subsample_batch of this engine; actions and advantages are not gathered.  n_global_sub = the sub-batch's valid samples over all ranks
+        (the denominator of its means); None: this rank's count -- len(idx) without a valid mask, else the gathered flags' sum, read once.
+        .valid_count (1-element float64 device tensor) holds this rank's count either way (a sharded caller all-reduces it and sets .inv_n_global)."""
+        idx = _i32(idx, self.device).reshape(-1)
+        m = int(idx.numel())
+        if m == 0:
+            raise ValueError("subsample_batch: empty index vector")
+        count = torch.zeros(1, dtype=torch.float64, device=self.device)
+        sub = _lib.Batch()
+        inv = 1.0 / float(n_global_sub) if n_global_sub is not None else 1.0 / m
+        self._chk(lib.metrpo_subsample_batch(self._ctx, C.byref(batch), _ptr(idx), m, inv, C.byref(sub), _ptr(count), self._stream()))
+        sub.valid_count = count
+        sub._keep = (idx, batch)             # (a broadcast old_log_std is still the source batch's tensor)
+        if n_global_sub is None and batch.d_valid:
+            n = int(count.item())
+            if n == 0:
+                raise ValueError("subsample_batch: none of the %d gathered rows is valid" % m)
+            sub.inv_n_global = 1.0 / n
+        return sub
+
+    def batch_tensors(self, batch):
+        """Copies of the device arrays a Batch points to (diagnostics / tests): dict(obs, old_mean, old_log_std, valid); None where the pointer is."""
+        N, dev = int(batch.N), self.device
+
+        def view(ptr, count, typestr, shape):
+            return torch.as_tensor(_DevView(ptr, count, typestr), device=dev).clone().reshape(shape) if ptr else None
+        n_ls = N * self.na if batch.old_log_std_stride else self.na
+        return dict(obs=view(batch.d_obs, N * self.ns, '<f4', (N, self.ns)), old_mean=view(batch.d_old_mean, N * self.na, '<f4', (N, self.na)),
+                    old_log_std=view(batch.d_old_log_std, n_ls, '<f4', (-1, self.na)), valid=view(batch.d_valid, N, '|u1', (N,)))
+
     def loss_grad(self, batch):
         out = torch.empty(self.P + 1, dtype=torch.float64, device=self.device)
         self._chk(lib.metrpo_loss_grad(self._ctx, C.byref(batch), _ptr(out), self._stream()))
@@ -566,9 +600,12 @@ class Engine(object):
         return out
 
     def trpo_update(self, batch, max_kl=0.01, cg_iters=10, reg_coeff=1e-5, backtrack_ratio=0.8, max_backtracks=15,
-                    accept_violation=False, residual_tol=1e-10, allreduce=None, want_vectors=False, explicit_final_hvp=False, spec_trials=0):
+                    accept_violation=False, residual_tol=1e-10, allreduce=None, want_vectors=False, explicit_final_hvp=False, spec_trials=0,
+                    fvp_batch=None):
         """One ConjugateGradientOptimizer.optimize; `allreduce(tensor_f64)` reduces in place across ranks.  spec_trials = S > 0: only
-        enqueue it, with the first S line-search trials decided on the device (no synchronisation; see trpo_update_end)."""
+        enqueue it, with the first S line-search trials decided on the device (no synchronisation; see trpo_update_end).
+        fvp_batch (subsample_batch's result, or any Batch): the Fisher-vector products of the CG solve and of the step scale run on it, gradient and
+        line search on `batch` (metrpo_trpo_update_fvp / _fvp_begin); None: metrpo_trpo_update / _begin, as before."""
         p = _lib.TrpoParams()
         p.max_kl, p.cg_iters, p.reg_coeff, p.backtrack_ratio = max_kl, cg_iters, reg_coeff, backtrack_ratio
         p.max_backtracks, p.accept_violation, p.residual_tol = max_backtracks, int(accept_violation), residual_tol
@@ -594,10 +631,18 @@ class Engine(object):
             g = torch.empty(self.P, dtype=torch.float64, device=self.device); d = torch.empty_like(g)
         if spec_trials:
             # first half only (metrpo_trpo_update_begin): no synchronisation; trpo_update_end() returns the diagnostics
-            self._chk(lib.metrpo_trpo_update_begin(self._ctx, C.byref(batch), C.byref(p), int(spec_trials), _ptr(g), _ptr(d), self._stream()))
+            if fvp_batch is not None:
+                self._chk(lib.metrpo_trpo_update_fvp_begin(self._ctx, C.byref(batch), C.byref(fvp_batch), C.byref(p), int(spec_trials), _ptr(g), _ptr(d),
+                                                           self._stream()))
+            else:
+                self._chk(lib.metrpo_trpo_update_begin(self._ctx, C.byref(batch), C.byref(p), int(spec_trials), _ptr(g), _ptr(d), self._stream()))
             self._upd_open = (batch, p, g, d, int(spec_trials))              # keeps the batch struct and the output tensors alive until _end
+            self._upd_fvp_batch = fvp_batch
             return None
-        self._chk(lib.metrpo_trpo_update(self._ctx, C.byref(batch), C.byref(p), C.byref(diag), _ptr(g), _ptr(d), self._stream()))
+        if fvp_batch is not None:
+            self._chk(lib.metrpo_trpo_update_fvp(self._ctx, C.byref(batch), C.byref(fvp_batch), C.byref(p), C.byref(diag), _ptr(g), _ptr(d), self._stream()))
+        else:
+            self._chk(lib.metrpo_trpo_update(self._ctx, C.byref(batch), C.byref(p), C.byref(diag), _ptr(g), _ptr(d), self._stream()))
         out = dict(loss_before=diag.loss_before, loss=diag.loss, kl=diag.kl, beta=diag.beta,
                    n_backtrack=diag.n_backtrack, accepted=bool(diag.accepted), cg_iters_run=diag.cg_iters_run)
         if want_vectors:
@@ -622,6 +667,7 @@ class Engine(object):
             self._chk(lib.metrpo_trpo_update_end(self._ctx, C.byref(diag), C.byref(late), self._stream()))
         finally:
             self._upd_open = None
+            self._upd_fvp_batch = None
         out = dict(loss_before=diag.loss_before, loss=diag.loss, kl=diag.kl, beta=diag.beta,
                    n_backtrack=diag.n_backtrack, accepted=bool(diag.accepted), cg_iters_run=diag.cg_iters_run)
         out['late'] = bool(late.value)
@@ -798,10 +844,10 @@ class Engine(object):
 
 
 class _DevView(object):
-    """Zero-copy float64 view of library-owned device memory for torch (CUDA array interface)."""
+    """Zero-copy view (float64 unless told otherwise) of library-owned device memory for torch (CUDA array interface)."""
 
-    def __init__(self, ptr, count):
-        self.__cuda_array_interface__ = {'shape': (int(count),), 'typestr': '<f8', 'data': (int(ptr), False), 'version': 2}
+    def __init__(self, ptr, count, typestr='<f8'):
+        self.__cuda_array_interface__ = {'shape': (int(count),), 'typestr': typestr, 'data': (int(ptr), False), 'version': 2}
 
 
 def xavier_policy_theta(ns, hidden, na, init_std=1.0, seed=0):

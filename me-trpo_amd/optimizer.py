@@ -8,6 +8,11 @@ Two execution forms over the same kernels:
   fused=False            the reference-shaped host loop (NumPy float64 vectors, one kernel call per
                          f_loss / f_grad / f_Hx / f_loss_constraint evaluation).  Same arithmetic; used for
                          debugging and by the multi-process CPU tests with an injected evaluator.
+subsample_factor < 1 ([rllab] optimize(): inds = np.random.choice(n, int(n * subsample_factor), replace=False)): loss, gradient and line search
+see the whole batch; Hx -- the cg_iters products of krylov.cg and the d.Hd of the step scale -- sees the rows `inds` of it, gathered on the device
+(Engine.subsample_batch), its mean KL being the mean over the subsample.  One draw per optimize() call, from a torch.Generator this optimiser owns
+(seeded from `seed` and the rank; rllab draws from NumPy's global RNG on the host, which this cannot be pinned to: pass subsample_indices for that
+stream).  Both execution forms build the same sub-batch and walk the same arithmetic.
 Sharded runs: every evaluation returns this rank's pre-scaled share; a sum all-reduce (Comm) makes it the
 global mean, so every rank walks the identical CG / line-search trajectory."""
 import numpy as np
@@ -37,14 +42,23 @@ def cg(f_Ax, b, cg_iters=10, residual_tol=1e-10):
 class EngineEvaluator(object):
     """f_loss/f_grad/f_Hx_plain/f_loss_constraint of the compiled graph, served by the HIP kernels."""
 
-    def __init__(self, engine, batch):
+    def __init__(self, engine, batch, fvp_batch=None):
         self.engine, self.batch = engine, batch
+        self.fvp_batch = batch if fvp_batch is None else fvp_batch      # what f_Hx_plain sees (subsample_inputs)
+
+    @property
+    def n_samples(self):
+        return int(self.batch.N)
+
+    def subsample(self, idx, comm=None):
+        """f_Hx_plain sees the rows idx of the batch from now on (ConjugateGradientOptimizer.optimize with subsample_factor < 1)."""
+        self.fvp_batch = build_sub_batch(self.engine, self.batch, idx, comm or Comm())
 
     def loss_grad(self):
         return self.engine.loss_grad(self.batch)                  # tensor [1+P] f64 (this rank's share)
 
     def hvp(self, v):
-        return self.engine.fvp(self.batch, v)                     # tensor [P] f64
+        return self.engine.fvp(self.fvp_batch, v)                 # tensor [P] f64
 
     def loss_constraint(self, theta):
         return self.engine.loss_kl(self.batch, theta)             # tensor [2] f64
@@ -56,10 +70,29 @@ class EngineEvaluator(object):
         self.engine.set_policy(np.asarray(theta, dtype=np.float32))
 
 
+def build_sub_batch(engine, batch, idx, comm):
+    """The sub-batch of rows idx with the denominator of its means.  A batch known to be all valid on every rank (1 / inv_n_global == world * N: the
+    fixed-horizon case of sampler.py) gives world * len(idx) without a host read; otherwise the gather's valid count is summed over the ranks and
+    read once (the read the sampler already takes for those envs)."""
+    m = int(idx.numel())
+    if abs(1.0 / batch.inv_n_global - comm.world * int(batch.N)) < 0.5:
+        return engine.subsample_batch(batch, idx, n_global_sub=comm.world * m)
+    sub = engine.subsample_batch(batch, idx, n_global_sub=comm.world * m)      # (placeholder denominator, replaced below)
+    n = int(comm.allreduce_sum_(sub.valid_count).item())
+    if n == 0:
+        raise ValueError("subsampled Hx: none of the gathered rows is valid on any rank (%d rows drawn here)" % m)
+    sub.inv_n_global = 1.0 / n
+    return sub
+
+
 class ConjugateGradientOptimizer(object):
     def __init__(self, cg_iters=10, reg_coeff=1e-5, subsample_factor=1.0, backtrack_ratio=0.8, max_backtracks=15,
-                 accept_violation=False, hvp_approach=None, num_slices=1, fused=True):
-        assert subsample_factor == 1.0, "subsampled Hx is not used on this path (algos/trpo.py:18-20 passes no args)"
+                 accept_violation=False, hvp_approach=None, num_slices=1, fused=True, seed=0):
+        subsample_factor = float(subsample_factor)
+        if not (0.0 < subsample_factor <= 1.0):
+            raise ValueError("subsample_factor = %r: must be in (0, 1]" % (subsample_factor,))
+        self._subsample_factor, self._seed = subsample_factor, int(seed)
+        self._gen = None                     # torch.Generator of the subsample draws: made at the first draw, on the batch's device
         self._cg_iters, self._reg_coeff = cg_iters, reg_coeff
         self._backtrack_ratio, self._max_backtracks = backtrack_ratio, max_backtracks
         self._accept_violation, self._fused = accept_violation, fused
@@ -118,12 +151,31 @@ class ConjugateGradientOptimizer(object):
         t = comm.allreduce_sum_(t)
         return t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
 
-    def optimize(self, engine_or_evaluator, batch=None, comm=None, defer=False):
+    def subsample_size(self, n_local):
+        """m = int(n * subsample_factor) of rllab's optimize(); a factor that leaves no row raises."""
+        m = int(n_local * self._subsample_factor)
+        if m == 0:
+            raise ValueError("subsample_factor = %r leaves no row of this rank's N = %d samples" % (self._subsample_factor, n_local))
+        return m
+
+    def draw_indices(self, n_local, device='cpu', rank=0):
+        """np.random.choice(n, m, replace=False) of rllab's optimize(), as the head of a device permutation: int32 [m], no host read."""
+        m = self.subsample_size(n_local)
+        device = torch.device(device)
+        if self._gen is None or self._gen.device.type != device.type:
+            self._gen = torch.Generator(device=device)
+            self._gen.manual_seed((self._seed * 1000003 + 7919 * int(rank)) & 0x7FFFFFFFFFFFFFFF)
+        return torch.randperm(n_local, generator=self._gen, device=device)[:m].to(torch.int32)
+
+    def optimize(self, engine_or_evaluator, batch=None, comm=None, defer=False, subsample_indices=None):
         """defer=True (fused form only): enqueue the update with its first `spec_trials` line-search trials decided on the device and
-        return at once (None); finish() / last_diag complete it.  The caller may enqueue the next rollout in between (algos.BatchPolopt)."""
+        return at once (None); finish() / last_diag complete it.  The caller may enqueue the next rollout in between (algos.BatchPolopt).
+        subsample_indices: the rows Hx sees, instead of this call's draw (tests; callers who bring rllab's own np.random.choice stream)."""
         comm = comm or Comm()
         if self._open is not None:
             self.finish()
+        if self._subsample_factor < 1.0 or subsample_indices is not None:
+            return self._optimize_subsampled(engine_or_evaluator, batch, comm, defer, subsample_indices)
         if self._fused and batch is not None:
             # ranks > 1: the ctx's own RCCL communicator when one is attached (all-reduces issued from C), else a host callback
             need = comm.world > 1 or comm.always_reduce
@@ -142,6 +194,38 @@ class ConjugateGradientOptimizer(object):
             return self.last_diag
         ev = engine_or_evaluator if batch is None else EngineEvaluator(engine_or_evaluator, batch)
         self.last_diag = self._optimize_host(ev, comm)
+        return self.last_diag
+
+    def _optimize_subsampled(self, engine_or_evaluator, batch, comm, defer, indices):
+        """optimize() with Hx on a sub-batch: one draw, one gather, then the same two forms."""
+        ev = engine_or_evaluator if batch is None else None
+        if ev is not None and not (hasattr(ev, 'n_samples') and hasattr(ev, 'subsample')):
+            raise TypeError("subsampled Hx needs an evaluator with n_samples and subsample(idx, comm) (EngineEvaluator has them)")
+        n_local = int(ev.n_samples) if ev is not None else int(batch.N)
+        if indices is None:
+            device = getattr(engine_or_evaluator, 'device', None) or getattr(getattr(ev, 'engine', None), 'device', 'cpu')
+            indices = self.draw_indices(n_local, device=device, rank=comm.rank)
+        else:
+            indices = torch.as_tensor(indices).reshape(-1).to(torch.int32)
+            if indices.numel() == 0:
+                raise ValueError("subsample_indices is empty (N = %d)" % n_local)
+        if ev is not None or not self._fused:
+            if ev is None:
+                ev = EngineEvaluator(engine_or_evaluator, batch)
+            ev.subsample(indices, comm)
+            self.last_diag = self._optimize_host(ev, comm)
+            return self.last_diag
+        eng = engine_or_evaluator
+        sub = build_sub_batch(eng, batch, indices, comm)
+        need = comm.world > 1 or comm.always_reduce
+        ar = (lambda t: comm.allreduce_sum_(t)) if (need and not getattr(eng, 'comm_world', 0)) else None
+        kw = dict(max_kl=self._max_constraint_val, cg_iters=self._cg_iters, reg_coeff=self._reg_coeff, backtrack_ratio=self._backtrack_ratio,
+                  max_backtracks=self._max_backtracks, accept_violation=self._accept_violation, fvp_batch=sub)
+        if defer and ar is None:
+            eng.trpo_update(batch, spec_trials=self.spec_trials, **kw)
+            self._open = eng
+            return None
+        self.last_diag = eng.trpo_update(batch, allreduce=ar, **kw)
         return self.last_diag
 
     def _optimize_host(self, ev, comm):

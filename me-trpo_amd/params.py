@@ -9,14 +9,16 @@ Keys read (params-swimmer.json:5-86):
     dynamics_model.{hidden_layers, nonlinearity, ignore_xy_input | ignore_x_input, prediction_type, use_logit_weights, regularization.constant}
     policy.hidden_layers
     policy_opt_params.{T, gamma, mode, whole, log_every, num_iters_threshold, max_iters, batch_size, sam_mode, learning_rate, grad_norm_clipping,
-                       stop_critereon.{threshold, offset, percent_models_threshold}, trpo.{init_std, step_size, discount, batch_size, reset},
+                       stop_critereon.{threshold, offset, percent_models_threshold}, trpo.{init_std, step_size, discount, batch_size, reset,
+                                                                                             subsample_factor (EXTENSION, see below)},
                        vpg.{init_std, discount, batch_size, reset},
                        ppo.{init_std, discount, batch_size, reset, clip_lr, n_epochs, learning_rate, entropy_bonus_coeff,
                             use_kl_penalty, initial_kl_penalty, step_size}}
     dynamics_opt_params.{learning_rate.{scratch, refine}, batch_size, max_passes, log_every, num_passes_threshold, sample_mode, reinitialize,
                          stop_critereon.{threshold, offset}}
 'algo' builds 'trpo', 'vpg' (training.py:337-352: VPG with the vpg block's batch size, discount and log_std reset), 'bptt' and 'bptt-stochastic';
-svg and l-bfgs raise.  'ppo' (algos/ppo.py) is an EXTENSION: the reference's training.py has no such branch and its params files no ppo block; the
+svg and l-bfgs raise.  trpo.subsample_factor is an EXTENSION key (default 1.0: the reference's run; below 1 the Fisher-vector products of the update
+see that fraction of the batch, [rllab] ConjugateGradientOptimizer(subsample_factor)); it is reported as shapes['trpo_ext'].  'ppo' (algos/ppo.py) is an EXTENSION: the reference's training.py has no such branch and its params files no ppo block; the
 block's defaults are ppo.py's (clip_lr 0.3, entropy_bonus_coeff 0, use_kl_penalty false, initial_kl_penalty 1, step_size 0.01), AdamOptimizer's (n_epochs 10, learning_rate 1e-3) and the vpg block's.  Everything else in the files (rollout_params, sweep_iters, sample_size, *_path) steers the reference's real-simulator data collection and outer
 sweeps, which are out of scope here; those keys are passed through untouched in `Setup.params`."""
 import json
@@ -77,6 +79,9 @@ def shapes_from_params(path_or_dict):
         ppo=dict(discount=float(ppo.get('discount', 1.0)), init_std=float(ppo.get('init_std', 1.0)), batch_size=int(ppo.get('batch_size', 5000)),
                  reset=bool(ppo.get('reset', True)), clip_lr=float(ppo.get('clip_lr', 0.3)), n_epochs=int(ppo.get('n_epochs', 10)),
                  learning_rate=float(ppo.get('learning_rate', 1e-3)), entropy_bonus_coeff=float(ppo.get('entropy_bonus_coeff', 0.0))),
+        # EXTENSION key of the trpo block (no reference params file has it): [rllab] ConjugateGradientOptimizer(subsample_factor), the fraction of the batch
+        # the Fisher-vector products see; 1.0 = the reference's run (algos/trpo.py:18-20 passes no optimizer_args).  Kept apart from the reference's keys above.
+        trpo_ext=dict(subsample_factor=float(trpo.get('subsample_factor', 1.0))),
         # the KL penalty's keys of the same params block (ppo.py:27-28, :34), kept apart from the dict above
         ppo_kl=dict(use_kl_penalty=bool(ppo.get('use_kl_penalty', False)), initial_kl_penalty=float(ppo.get('initial_kl_penalty', 1.0)),
                     step_size=float(ppo.get('step_size', 0.01))),
@@ -141,7 +146,8 @@ def from_params(path_or_dict, device=0, init_states=None, comm=None, seed=0, n_e
                    optimizer=AdamOptimizer(learning_rate=blk['learning_rate'], n_epochs=blk['n_epochs']), sampler_args=sargs, comm=comm, seed=seed)
     else:
         algo = TRPO(env=env, policy=policy, baseline=baseline, batch_size=sh['batch_size'], max_path_length=sh['T'], discount=sh['trpo']['discount'],
-                    step_size=sh['trpo']['step_size'], sampler_args=sargs, comm=comm, seed=seed)
+                    step_size=sh['trpo']['step_size'], sampler_args=sargs, comm=comm, seed=seed,
+                    optimizer_args=dict(subsample_factor=sh['trpo_ext']['subsample_factor'], seed=seed))
     stop_fn = early_stop.stop_critereon(sh['stop_critereon']['threshold'], sh['stop_critereon']['offset'], sh['stop_critereon']['percent_models_threshold'])
     okw = dict(sh['optimize_policy'], stop_fn=stop_fn, reset_log_std=blk['reset'])
     bptt, bkw = None, None
