@@ -42,6 +42,7 @@ class SurrogateRealEnv(object):
         """n_traj trajectories of T+1 observations / T+1 actions (the reference's sample_trajectories shape) under `policy_actions`."""
         s = self.pool[self.rng.randint(len(self.pool), size=n_traj)]
         Os, As, cost = [s], [], 0.0
+        self.last_rewards = []                                               # per-step rewards of these trajectories, [T] x [n_traj]: the Rs of the model diagnostic
         for t in range(T + 1):
             a = policy_actions(s)
             As.append(a)
@@ -49,6 +50,7 @@ class SurrogateRealEnv(object):
                 break
             sn, rew, _ = self.eng.step(s, np.clip(a, -1, 1), 'one_model')
             cost += float(-rew.mean())
+            self.last_rewards.append(rew.cpu().numpy())
             s = sn.cpu().numpy()
             Os.append(s)
         O = np.stack(Os, axis=1); A = np.stack(As, axis=1)                   # [n_traj][T+1][.]
@@ -95,6 +97,13 @@ def main(argv=None):
         # ---- optimize_models (:881-1051)
         info = DT.optimize_models(eng, data['training_dynamics'], val['training_dynamics'], dict(scratch=1e-3, refine=1e-3), batch_size=256,
                                   max_passes=args.model_passes, log_every=5, num_passes_threshold=10, reinitialize=(it == 0), init_seed=it)
+        # ---- evaluate_model_predictions (env_helpers.py:96-172; the reference's call sits commented out at model_based_rl.py:619-635, between
+        #      "Dynamics Optimization" and "Policy Optimization"): how far can the ensemble just trained be trusted?  The h-step open-loop error
+        #      of its mean prediction under the current policy, against the trajectories just collected -- one fused rollout from every window.
+        errors = M.evaluate_model_predictions(eng, np.stack(Os)[:, :T + 1], None, np.stack(real.last_rewards, axis=1),
+                                              timesteps=[h for h in M.model_error.TIMESTEPS if h <= T], model=-1)
+        say("outer %d: model error |s - s_hat| summed over the state, by horizon: %s" %
+            (it, ', '.join('h=%d: %.3g' % (h, e) for h, e in zip(errors['timesteps'], errors['l1_sum']))))
         t2 = time.time()
         # ---- optimize_policy (:1082-1301): TRPO on the imagined env, early stopping on the per-model validation costs
         res = early_stop.optimize_policy(algo, validation_init, T, 1.0, mode='estimated', log_every=5, num_iters_threshold=10,
@@ -102,7 +111,8 @@ def main(argv=None):
         t3 = time.time()
         history.append(dict(real_cost=real_cost, n_data=data['training_dynamics'].get_num_data(),
                             model_val=float(np.sum(info['min_validation_losses'])) if 'min_validation_losses' in info else float('nan'),
-                            est_cost=float(np.mean(res['min_validation_costs']['estimated'])), best_index=res['best_index']))
+                            est_cost=float(np.mean(res['min_validation_costs']['estimated'])), best_index=res['best_index'],
+                            model_l1=dict(zip(errors['timesteps'], errors['l1_sum']))))
         say("outer %d: real-cost/step %.4f | data %d | model val loss %.4g (%d updates) | policy est-cost %.4f (best iter %d of %d) | "
             "collect %.2fs models %.2fs policy %.2fs" % (it, real_cost / T, history[-1]['n_data'], history[-1]['model_val'],
                                                        info.get('n_model_updates', -1), history[-1]['est_cost'], res['best_index'],

@@ -559,6 +559,43 @@ int32_t metrpo_lbfgs_get_result(metrpo_ctx* ctx, metrpo_lbfgs_result* out, void*
 int32_t metrpo_lbfgs_policy(metrpo_ctx* ctx, const float* d_init, int32_t B, int32_t T, double gamma, const metrpo_lbfgs_opts* opts,
                             metrpo_lbfgs_result* out, void* stream);
 
+/* ---- multi-horizon open-loop prediction error of the dynamics ensemble (env_helpers.py:96-172 evaluate_model_predictions, :175-269
+ * get_error_distribution; call sites model_based_rl.py:619-651).  Additions to ABI 4: no struct above changes, METRPO_ABI_VERSION stays.
+ * Recorded real trajectories: d_Os [n][T+1][ns] observations, d_As [n][T][na] actions as recorded (unclipped), d_Rs [n][T] rewards, fp32 on the device.
+ * A WINDOW is a start (i, t), t in [0, T); the batch has W = n * T of them, window w = i * T + t (t0_only: W = n, t = 0 only).  From every window start
+ * ONE deterministic rollout of hmax = hs[n_h - 1] steps is run (the reference rolls each horizon out separately from Os[:, :-h], :143-156; a
+ * deterministic rollout does not depend on how long it runs, so the state after h steps is row h of the one trajectory).
+ *   model = -1: METRPO_SAM_MODEL_MEAN, the mean over the heads (avg_prediction, model_based_rl.py:626); model = k >= 0: head k alone
+ *     (training_models[0], :638) -- run as METRPO_SAM_EPS_RAND with every env's cur_model_idx = k, because METRPO_SAM_ONE_MODEL is head 0 by definition
+ *     (env_helpers.py:631-632).
+ *   known_actions = 0: the ctx policy's clipped mean action (:149-150), through metrpo_rollout's own dispatch (metrpo_last_rollout_kernel reports the family)
+ *     with determ = 1, T = hmax, H = hmax + 1 (so the path-length limit never ends a window), d_init_obs = the window starts, d_init_ts = 0.
+ *   known_actions = 1 (:216-222): the recorded actions, clipped; hmax launches of metrpo_step's kernel -- the diagnostic's slow mode.
+ * Window (i, t) SERVES horizon h iff t + h <= T (the pairing Os[:, :-h] / Os[:, h:]: T + 1 - h windows per trajectory) and its rollout reported no
+ * `done` at any step < h (only Ant can: a finished env is reset from the pool, its state is no prediction any more; the reference's diagnostic never
+ * terminates).  Per (horizon index p, window w), zero where the window does not serve:
+ *   d_state_diff [n_h][W][ns] = |Os[i, t + h] - pred|   (:159)        d_cost_diff [n_h][W] = |costs + rewards|   (:160)        d_valid [n_h][W] uint8
+ *   with costs = -sum of the rollout's rewards and rewards = sum_s Rs[i, t + s], both fp32 sums in step order (:153-154).  signed_diff = 1 drops the
+ *   absolute values: pred - Os[i, t + h] and costs + rewards (e_state, e_cost of :232-233).
+ *   d_sums [n_h][4] float64, OVERWRITTEN: serving windows, sum_w sum_j state_diff, sum_w state_diff[:, ns - 1], sum_w cost_diff; per workgroup in a fixed
+ *   shape, the workgroups' partials added in workgroup order.
+ * hs is a HOST array, strictly increasing, 1 <= h <= T, n_h <= METRPO_MODEL_ERROR_MAX_HORIZONS.  Stream-ordered, no synchronisation; the trajectory lives
+ * in a ctx-owned workspace.  Neither the policy, the dynamics nor an optimizer state is written.
+ * d_dbg_* (all four or none): a caller-made trajectory d_dbg_obs [hmax][W][ns], d_dbg_rew [hmax][W], d_dbg_done [hmax][W], d_dbg_last_obs [W][ns] is
+ * compared instead and no rollout runs (tests; timing of the comparison alone). */
+#define METRPO_MODEL_ERROR_MAX_HORIZONS 32
+typedef struct {
+    const float* d_Os; const float* d_As; const float* d_Rs;     /* d_As may be NULL unless known_actions */
+    int32_t n, T;
+    const int32_t* hs; int32_t n_h;
+    int32_t model, known_actions, t0_only, signed_diff;
+    float* d_state_diff; float* d_cost_diff; uint8_t* d_valid; double* d_sums;
+    const float* d_dbg_obs; const float* d_dbg_rew; const uint8_t* d_dbg_done; const float* d_dbg_last_obs;
+} metrpo_model_error_args;
+/* The window gather alone: d_init_obs [n * T][ns] <- Os[i, t], i.e. Os[:, :-1] flattened. */
+int32_t metrpo_model_error_windows(metrpo_ctx* ctx, const float* d_Os, int32_t n, int32_t T, float* d_init_obs, void* stream);
+int32_t metrpo_model_error(metrpo_ctx* ctx, const metrpo_model_error_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

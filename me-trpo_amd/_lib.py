@@ -83,6 +83,16 @@ class LbfgsResult(C.Structure):
                 ('task_code', C.c_int32), ('pad_', C.c_int32)]
 
 
+class ModelErrorArgs(C.Structure):
+    _fields_ = [('d_Os', C.c_void_p), ('d_As', C.c_void_p), ('d_Rs', C.c_void_p), ('n', C.c_int32), ('T', C.c_int32),
+                ('hs', C.POINTER(C.c_int32)), ('n_h', C.c_int32), ('model', C.c_int32), ('known_actions', C.c_int32), ('t0_only', C.c_int32),
+                ('signed_diff', C.c_int32), ('d_state_diff', C.c_void_p), ('d_cost_diff', C.c_void_p), ('d_valid', C.c_void_p), ('d_sums', C.c_void_p),
+                ('d_dbg_obs', C.c_void_p), ('d_dbg_rew', C.c_void_p), ('d_dbg_done', C.c_void_p), ('d_dbg_last_obs', C.c_void_p)]
+
+
+MODEL_ERROR_MAX_HORIZONS = 32          # include/metrpo.h
+
+
 # every symbol include/metrpo.h declares: name -> (restype, argtypes)
 _P, _I, _L, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 SYMBOLS = {
@@ -131,6 +141,8 @@ SYMBOLS = {
     'metrpo_subsample_batch': (_I, [_P, C.POINTER(Batch), _P, _L, _D, C.POINTER(Batch), _P, _P]),
     'metrpo_trpo_update_fvp': (_I, [_P, C.POINTER(Batch), C.POINTER(Batch), C.POINTER(TrpoParams), C.POINTER(TrpoDiag), _P, _P, _P]),
     'metrpo_trpo_update_fvp_begin': (_I, [_P, C.POINTER(Batch), C.POINTER(Batch), C.POINTER(TrpoParams), _I, _P, _P, _P]),
+    'metrpo_model_error_windows': (_I, [_P, _P, _I, _I, _P, _P]),
+    'metrpo_model_error': (_I, [_P, C.POINTER(ModelErrorArgs), _P]),
     'metrpo_dyn_train_reset': (_I, [_P, _P]),
     'metrpo_dyn_train_step': (_I, [_P, _P, _P, C.POINTER(TrainParams), _P, _P]),
     'metrpo_dyn_eval_losses': (_I, [_P, _P, _P, _L, _D, _P, _P]),

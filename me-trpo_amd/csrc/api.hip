@@ -981,6 +981,41 @@ extern "C" int32_t metrpo_trpo_update_begin(metrpo_ctx* c, const metrpo_batch* b
     }
     return run_trpo_update(c, b, pr, nullptr, g_out, dir_out, (hipStream_t)stream, 1, spec_trials);
 }
+// ---- open-loop prediction error of the ensemble (env_helpers.py:96-172, :175-269; include/metrpo.h) ----
+extern "C" int32_t metrpo_model_error_windows(metrpo_ctx* c, const float* d_Os, int32_t n, int32_t T, float* d_init_obs, void* stream) {
+    if (!c) return METRPO_ENULL;
+    if (!d_Os || !d_init_obs) return set_err(c, METRPO_ENULL, "model_error_windows: NULL pointer");
+    if (n <= 0 || T <= 0 || (long long)n * T > 2147483647LL / c->pd.ns) return set_err(c, METRPO_EINVAL, "model_error_windows: n and T must be positive (n * T * ns < 2^31)");
+    return launch_window_starts(c, d_Os, n, T, T, d_init_obs, (hipStream_t)stream);
+}
+extern "C" int32_t metrpo_model_error(metrpo_ctx* c, const metrpo_model_error_args* a, void* stream) {
+    TraceRange trace_("metrpo:model_error (evaluate_model_predictions / get_error_distribution)");
+    if (!c) return METRPO_ENULL;
+    if (!a) return set_err(c, METRPO_ENULL, "model_error: args NULL");
+    if (!a->d_Os || !a->d_Rs || !a->hs) return set_err(c, METRPO_ENULL, "model_error: d_Os, d_Rs and hs are required");
+    if (!a->d_state_diff || !a->d_cost_diff || !a->d_valid || !a->d_sums) return set_err(c, METRPO_ENULL, "model_error: NULL output buffer");
+    if (a->n <= 0 || a->T <= 0) return set_err(c, METRPO_EINVAL, "model_error: n and T must be positive");
+    if (a->n_h <= 0 || a->n_h > METRPO_MODEL_ERROR_MAX_HORIZONS) return set_err(c, METRPO_EINVAL, "model_error: n_h must be in 1 ... " + std::to_string(METRPO_MODEL_ERROR_MAX_HORIZONS));
+    if (a->hs[0] < 1) return set_err(c, METRPO_EINVAL, "model_error: horizons start at 1");
+    for (int i = 1; i < a->n_h; ++i)
+        if (a->hs[i] <= a->hs[i - 1]) return set_err(c, METRPO_EINVAL, "model_error: hs is not sorted (strictly increasing)");
+    if (a->hs[a->n_h - 1] > a->T) return set_err(c, METRPO_EINVAL, "model_error: horizon h = " + std::to_string(a->hs[a->n_h - 1]) + " > T = " + std::to_string(a->T));
+    if (a->model < -1 || a->model >= c->pd.K) return set_err(c, METRPO_EINVAL, "model_error: model = " + std::to_string(a->model) + " is neither -1 nor a head below K = " + std::to_string(c->pd.K));
+    {   // every index of the call fits an int: the largest is (hmax + 1) * W * ns
+        const long long W = (long long)a->n * (a->t0_only ? 1 : a->T);
+        if (W * (a->hs[a->n_h - 1] + 1) > 2147483647LL / std::max(c->pd.ns, c->pd.na) || (long long)a->n * (a->T + 1) > 2147483647LL / c->pd.ns)
+            return set_err(c, METRPO_EINVAL, "model_error: (hmax + 1) * windows * ns must stay below 2^31");
+    }
+    const bool any_dbg = a->d_dbg_obs || a->d_dbg_rew || a->d_dbg_done || a->d_dbg_last_obs;
+    const bool all_dbg = a->d_dbg_obs && a->d_dbg_rew && a->d_dbg_done && a->d_dbg_last_obs;
+    if (any_dbg != all_dbg) return set_err(c, METRPO_EINVAL, "model_error: the d_dbg_* trajectory must be given whole or not at all");
+    if (!all_dbg) {
+        NEED_DYN(c);
+        if (a->known_actions) { if (!a->d_As) return set_err(c, METRPO_ENULL, "model_error: known_actions needs d_As"); }
+        else NEED_POL(c);
+    }
+    return run_model_error(c, a, (hipStream_t)stream);
+}
 // ---- subsampled Fisher-vector products ([rllab] ConjugateGradientOptimizer subsample_factor < 1; include/metrpo.h) ----
 extern "C" int32_t metrpo_subsample_batch(metrpo_ctx* c, const metrpo_batch* b, const int32_t* d_idx, int64_t m, double inv_n_global, metrpo_batch* out,
                                           double* d_valid_count, void* stream) {

@@ -100,6 +100,7 @@ struct metrpo_ctx {
     DevBuf<unsigned int> d_ticket; // arrival counter of k_finalize's fused CG tail
     DevBuf<float> d_hcache;        // activation cache of one CG solve (policy_mfma.hip OP_FVPC)
     DevBuf<void> d_sub;            // metrpo_subsample_batch: the gathered sub-batch (obs | old_mean | old_log_std | valid), valid until the next call of that entry point
+    DevBuf<void> d_merr; DevBuf<double> d_merr_part;   // model_error.hip: trajectory of the diagnostic's rollout (obs | act | mean | rew | tpath | done | window starts | ts | model) | arrival ticket + per-workgroup sums of k_pred_error
     DevBuf<double> d_ppo_kl;       // run_ppo_kl_update / launch_ppo_kl_loss_grad: one [loss, mean KL] pair per epoch, written by the OP_LOSSKL reduction and read by the OP_PPOKL kernels
     DevBuf<void> d_mig; int mig_epoch = 0;        // rollout_coop.hip: hand-over slots of migrating tiles (flag | ts | model | obs per tile)
     void* nccl_comm = nullptr; int comm_world = 0, comm_rank = 0;   // comm.hip: RCCL communicator attached by metrpo_comm_init (NULL: single rank)
@@ -423,4 +424,7 @@ int launch_loss_kl(metrpo_ctx*, const metrpo_batch*, const float*, double*, hipS
 int run_trpo_update(metrpo_ctx*, const metrpo_batch*, const metrpo_trpo_params*, metrpo_trpo_diag*, double*,
                     double*, hipStream_t, int phase = 0, int spec = 0, const metrpo_batch* fvp_batch = nullptr);
 // policy_update.hip: gather of the rows d_idx[0 .. m) of `b` into c->d_sub (metrpo_subsample_batch)
+// model_error.hip: window gather and the whole diagnostic (metrpo_model_error_windows / metrpo_model_error; arguments checked by the entry points)
+int launch_window_starts(metrpo_ctx*, const float* Os, int n, int T, int Tw, float* init_obs, hipStream_t);
+int run_model_error(metrpo_ctx*, const metrpo_model_error_args*, hipStream_t);
 int launch_subsample(metrpo_ctx*, const metrpo_batch* b, const int32_t* d_idx, long long m, double inv_n_global, metrpo_batch* out, double* d_valid_count, hipStream_t);
