@@ -104,6 +104,13 @@ def main(argv=None):
                                               timesteps=[h for h in M.model_error.TIMESTEPS if h <= T], model=-1)
         say("outer %d: model error |s - s_hat| summed over the state, by horizon: %s" %
             (it, ', '.join('h=%d: %.3g' % (h, e) for h, e in zip(errors['timesteps'], errors['l1_sum']))))
+        # ---- "what does the ensemble predict for THESE actions?" (get_error_distribution(known_actions=True), env_helpers.py:216-222): the recorded
+        #      actions replayed open-loop from the recorded starts, all T steps in one fused launch; the error left is the model's alone
+        O_rec = np.stack(Os)[:, :T + 1]
+        states, _, _ = M.open_loop_predictions(eng, O_rec[:, 0], np.stack(As)[:, :T], model=-1)
+        replay_l1 = np.abs(states.cpu().numpy() - O_rec).sum(axis=2).mean(axis=0)
+        say("outer %d: the same under the recorded actions (open-loop replay, %s): %s" %
+            (it, eng.last_rollout_actions_kernel(), ', '.join('h=%d: %.3g' % (h, replay_l1[h]) for h in errors['timesteps'])))
         t2 = time.time()
         # ---- optimize_policy (:1082-1301): TRPO on the imagined env, early stopping on the per-model validation costs
         res = early_stop.optimize_policy(algo, validation_init, T, 1.0, mode='estimated', log_every=5, num_iters_threshold=10,

@@ -570,7 +570,9 @@ int32_t metrpo_lbfgs_policy(metrpo_ctx* ctx, const float* d_init, int32_t B, int
  *     (env_helpers.py:631-632).
  *   known_actions = 0: the ctx policy's clipped mean action (:149-150), through metrpo_rollout's own dispatch (metrpo_last_rollout_kernel reports the family)
  *     with determ = 1, T = hmax, H = hmax + 1 (so the path-length limit never ends a window), d_init_obs = the window starts, d_init_ts = 0.
- *   known_actions = 1 (:216-222): the recorded actions, clipped; hmax launches of metrpo_step's kernel -- the diagnostic's slow mode.
+ *   known_actions = 1 (:216-222): the recorded actions, clipped; one gather of As[i, min(t + s, T - 1)] for all hmax steps, then the body of
+ *     metrpo_rollout_actions below (its dispatch; metrpo_last_rollout_actions_kernel reports the path).  A done (Ant) does not reset here: the window
+ *     is dropped from that horizon on all the same.
  * Window (i, t) SERVES horizon h iff t + h <= T (the pairing Os[:, :-h] / Os[:, h:]: T + 1 - h windows per trajectory) and its rollout reported no
  * `done` at any step < h (only Ant can: a finished env is reset from the pool, its state is no prediction any more; the reference's diagnostic never
  * terminates).  Per (horizon index p, window w), zero where the window does not serve:
@@ -595,6 +597,40 @@ typedef struct {
 /* The window gather alone: d_init_obs [n * T][ns] <- Os[i, t], i.e. Os[:, :-1] flattened. */
 int32_t metrpo_model_error_windows(metrpo_ctx* ctx, const float* d_Os, int32_t n, int32_t T, float* d_init_obs, void* stream);
 int32_t metrpo_model_error(metrpo_ctx* ctx, const metrpo_model_error_args* args, void* stream);
+
+/* ---- open-loop rollout of the ensemble under SUPPLIED actions: "what does the model predict for these actions?" -- the loop of
+ * get_error_distribution(known_actions=True), env_helpers.py:216-222 (clip the recorded actions once, then per step a = actions[:, t], the model's
+ * prediction, its cost), over VecSimpleEnv.step's arithmetic, env_helpers.py:597-603.  Addition to ABI 4: no struct above changes, METRPO_ABI_VERSION stays.
+ * The meaning is exactly that of T chained metrpo_step calls: no policy, no reset, no path-length limit and no Philox draw -- a deterministic function
+ * of its inputs.  Stepping CONTINUES BEHIND A DONE: d_done[t][b] reports is_done(s_t+1, s_t+1) (:603; only Ant can) and the env is neither stopped nor
+ * reset, row t + 2 of d_obs is the model's prediction from row t + 1 whatever d_done says (the reference's diagnostic never terminates, :218-230).
+ * Which kernel runs (metrpo_last_rollout_actions_kernel: -1 none yet, 0 step loop, 1 fused):
+ *   fused (rollout_actions.hip: all T steps in one launch) -- swimmer, half-cheetah, Ant, hopper, snake at their own dims with two relu hidden layers of 64
+ *     and a 2 x 32 policy (the shape class of the fused rollout kernels), narrower hidden layers through the zero-padded copy, K <= 8, sam_mode model_mean,
+ *     eps_rand or one_model, force_step_loop = 0;
+ *   step loop (metrpo_step's kernel once per step on row t of d_actions, writing row t + 1 of d_obs) -- everything else: humanoid, hidden widths above 64,
+ *     other depths / activations / policy shapes, K > 8, step_rand, model_mean_std, model_med.  Bit for bit what T metrpo_step calls give.
+ * The two agree to rounding, not bits: the fused kernel normalises by the reciprocal std and sums on the matrix core.
+ * Stream-ordered, neither frees nor synchronises; workspace (the step loop's head vector under uniform_model) is ctx-owned.  Needs metrpo_set_dynamics only:
+ * theta is never read.  Leaves metrpo_last_rollout_kernel, metrpo_rollout_note, the Philox state, both Adam states, theta and the ensemble untouched.
+ * B == 0 or T == 0: METRPO_OK, nothing written. */
+typedef struct {
+    int32_t B, T;
+    int32_t sam_mode;             /* metrpo_sam_mode, all six accepted (see dispatch)                         */
+    int32_t uniform_model;        /* >= 0: the caller's promise that every env uses this head (eps_rand only;
+                                     d_model then ignored and may be NULL); -1: per-env d_model               */
+    int32_t force_step_loop;      /* test / A-B hook: 1 = run the step-wise path whatever the shape           */
+    const float*   d_init_obs;    /* [B][ns]                                                                   */
+    const float*   d_actions;     /* [T][B][na] UNCLIPPED, clipped inside as metrpo_step does (env_helpers.py:599); never written */
+    const int32_t* d_model;       /* [B] eps_rand head per env                                                 */
+    const int32_t* d_model_idx;   /* [T][B] step_rand (supplied only)                                          */
+    const float*   d_sel_noise;   /* [T][B][ns] model_mean_std (supplied only)                                 */
+    float*   d_obs;               /* [T+1][B][ns]: row 0 = d_init_obs, row t+1 = state after step t            */
+    float*   d_rew;               /* [T][B]   = -cost_np_vec(s_t, clip(a_t), s_t+1)                            */
+    uint8_t* d_done;              /* [T][B]   is_done(s_t+1, s_t+1); stepping CONTINUES behind a done          */
+} metrpo_rollout_actions_args;
+int32_t metrpo_rollout_actions(metrpo_ctx* ctx, const metrpo_rollout_actions_args* args, void* stream);
+int32_t metrpo_last_rollout_actions_kernel(const metrpo_ctx* ctx);   /* -1 none yet, 0 step loop, 1 fused */
 
 #ifdef __cplusplus
 }

@@ -90,6 +90,12 @@ class ModelErrorArgs(C.Structure):
                 ('d_dbg_obs', C.c_void_p), ('d_dbg_rew', C.c_void_p), ('d_dbg_done', C.c_void_p), ('d_dbg_last_obs', C.c_void_p)]
 
 
+class RolloutActionsArgs(C.Structure):
+    _fields_ = [('B', C.c_int32), ('T', C.c_int32), ('sam_mode', C.c_int32), ('uniform_model', C.c_int32), ('force_step_loop', C.c_int32),
+                ('d_init_obs', C.c_void_p), ('d_actions', C.c_void_p), ('d_model', C.c_void_p), ('d_model_idx', C.c_void_p), ('d_sel_noise', C.c_void_p),
+                ('d_obs', C.c_void_p), ('d_rew', C.c_void_p), ('d_done', C.c_void_p)]
+
+
 MODEL_ERROR_MAX_HORIZONS = 32          # include/metrpo.h
 
 
@@ -143,6 +149,8 @@ SYMBOLS = {
     'metrpo_trpo_update_fvp_begin': (_I, [_P, C.POINTER(Batch), C.POINTER(Batch), C.POINTER(TrpoParams), _I, _P, _P, _P]),
     'metrpo_model_error_windows': (_I, [_P, _P, _I, _I, _P, _P]),
     'metrpo_model_error': (_I, [_P, C.POINTER(ModelErrorArgs), _P]),
+    'metrpo_rollout_actions': (_I, [_P, C.POINTER(RolloutActionsArgs), _P]),
+    'metrpo_last_rollout_actions_kernel': (_I, [_P]),
     'metrpo_dyn_train_reset': (_I, [_P, _P]),
     'metrpo_dyn_train_step': (_I, [_P, _P, _P, C.POINTER(TrainParams), _P, _P]),
     'metrpo_dyn_eval_losses': (_I, [_P, _P, _P, _L, _D, _P, _P]),

@@ -1017,6 +1017,25 @@ extern "C" int32_t metrpo_model_error(metrpo_ctx* c, const metrpo_model_error_ar
     return run_model_error(c, a, (hipStream_t)stream);
 }
 // ---- subsampled Fisher-vector products ([rllab] ConjugateGradientOptimizer subsample_factor < 1; include/metrpo.h) ----
+// T chained metrpo_step calls under supplied actions, fused where the shape allows (rollout_actions.hip)
+extern "C" int32_t metrpo_rollout_actions(metrpo_ctx* c, const metrpo_rollout_actions_args* a, void* stream) {
+    TraceRange trace_("metrpo:rollout_actions (open-loop replay of supplied actions)");
+    if (!c) return METRPO_ENULL;
+    if (!a) return set_err(c, METRPO_ENULL, "rollout_actions: args NULL");
+    NEED_DYN(c);
+    if (!sam_ok(a->sam_mode)) return set_err(c, METRPO_EINVAL, "sam mode is not defined");
+    if (a->B < 0 || a->T < 0) return set_err(c, METRPO_EINVAL, "rollout_actions: bad B/T");
+    if (a->uniform_model < -1 || a->uniform_model >= c->pd.K)
+        return set_err(c, METRPO_EINVAL, "rollout_actions: uniform_model = " + std::to_string(a->uniform_model) + " is neither -1 nor a head below K = " + std::to_string(c->pd.K));
+    if (a->B == 0 || a->T == 0) return METRPO_OK;
+    if (!a->d_init_obs || !a->d_actions || !a->d_obs || !a->d_rew || !a->d_done) return set_err(c, METRPO_ENULL, "rollout_actions: required pointer is NULL");
+    if (a->sam_mode == METRPO_SAM_EPS_RAND && a->uniform_model < 0 && !a->d_model) return set_err(c, METRPO_ENULL, "rollout_actions: eps_rand needs d_model or uniform_model");
+    if (a->sam_mode == METRPO_SAM_STEP_RAND && !a->d_model_idx) return set_err(c, METRPO_ENULL, "rollout_actions: d_model_idx required for step_rand");
+    if (a->sam_mode == METRPO_SAM_MODEL_MEAN_STD && !a->d_sel_noise) return set_err(c, METRPO_ENULL, "rollout_actions: d_sel_noise required for model_mean_std");
+    return run_rollout_actions(c, a, (hipStream_t)stream);
+}
+extern "C" int32_t metrpo_last_rollout_actions_kernel(const metrpo_ctx* c) { return c ? c->last_ract_kernel : METRPO_ENULL; }
+
 extern "C" int32_t metrpo_subsample_batch(metrpo_ctx* c, const metrpo_batch* b, const int32_t* d_idx, int64_t m, double inv_n_global, metrpo_batch* out,
                                           double* d_valid_count, void* stream) {
     TraceRange trace_("metrpo:subsample_batch");

@@ -121,6 +121,8 @@ struct metrpo_ctx {
     std::vector<int> skp_tab_host;                    // host copy of the table below, as raw 32-bit words (source of its asynchronous upload; SkRec: mlp_streamk.h)
     DevBuf<void> d_skp_tab; long long skp_key[8] = {-1, -1, -1, -1, -1, -1, -1, -1}; int skp_Jx[8] = {}, skp_Jmax = 0, skp_L = 0, skp_NSL = 0; int persist_failed = 0;   // mlp_persist.h: cached chunk-record table of the persistent stream-K rollout (key: the launch's shape) | a persistent launch timed out
     int res_failed = 0;                                   // a resident launch gave up (its grid was not co-resident): this context stays on the step-wise path from then on
+    int last_ract_kernel = -1;                            // metrpo_rollout_actions (rollout_actions.hip): -1 none yet, 0 step loop, 1 fused
+    DevBuf<int32_t> d_ract_model;                         // ... its step loop's [B] head vector when the caller gave uniform_model instead of d_model
     int last_rollout_kernel = -1;                         // which kernel family the last metrpo_rollout ran on: 0 generic, 1 head-per-wave MFMA, 2 cooperative MFMA, 3 step-wise GEMM, 4 resident
     // metrpo_trpo_update_begin / _end: an update whose line search is still undecided on the host
     // metrpo_trpo_update_begin's outcome lands in pinned host memory straight from its last kernel (k_ls_publish: scal | lk | ls, then a
@@ -427,4 +429,6 @@ int run_trpo_update(metrpo_ctx*, const metrpo_batch*, const metrpo_trpo_params*,
 // model_error.hip: window gather and the whole diagnostic (metrpo_model_error_windows / metrpo_model_error; arguments checked by the entry points)
 int launch_window_starts(metrpo_ctx*, const float* Os, int n, int T, int Tw, float* init_obs, hipStream_t);
 int run_model_error(metrpo_ctx*, const metrpo_model_error_args*, hipStream_t);
+// rollout_actions.hip: the body of metrpo_rollout_actions (arguments checked by the entry point; B, T > 0).  d_init_obs may BE row 0 of d_obs (model_error.hip)
+int run_rollout_actions(metrpo_ctx*, const metrpo_rollout_actions_args*, hipStream_t);
 int launch_subsample(metrpo_ctx*, const metrpo_batch* b, const int32_t* d_idx, long long m, double inv_n_global, metrpo_batch* out, double* d_valid_count, hipStream_t);

@@ -4,8 +4,8 @@
 //
 // The reference rolls every horizon h out separately from the windows Os[:, :-h] (:143-156).  A deterministic rollout does not depend on how long it
 // will run, so here ONE rollout of hmax = max(hs) steps from every window start serves all horizons: the state after h steps is row h of the
-// trajectory.  k_window_starts gathers the starts, the rollout is metrpo_rollout's own dispatch (or, with known_actions, metrpo_step's kernel fed
-// with the recorded actions), k_pred_error compares and reduces in one pass.
+// trajectory.  k_window_starts gathers the starts, the rollout is metrpo_rollout's own dispatch (or, with known_actions, metrpo_rollout_actions' on the
+// recorded actions, gathered per window by k_window_actions), k_pred_error compares and reduces in one pass.
 //
 // Both kernels are bandwidth-bound.  Trajectory tensors are time-major [h][W][ns]: the ns floats of 64 consecutive windows are one contiguous range of
 // 64 * ns floats, and so are the recorded states they are compared against (consecutive windows of a trajectory are consecutive rows of Os), so a
@@ -37,12 +37,14 @@ __global__ void __launch_bounds__(ME_WG) k_window_starts(const float* __restrict
     }
 }
 
-// known_actions: d_act [W][na] <- As[i, min(t + s, T - 1)] (a window whose step s lies beyond its trajectory serves no horizon > s; the clamp keeps
-// the read inside As).  Unclipped: metrpo_step clips (env_helpers.py:216, :599).
-__global__ void __launch_bounds__(ME_WG) k_window_actions(const float* __restrict__ As, float* __restrict__ dst, int W, int Tw, int T, int na, int s) {
-    const long long n = (long long)W * na;
+// known_actions: d_act [hmax][W][na] <- As[i, min(t + s, T - 1)] for every step s of the rollout in ONE launch (a window whose step s lies beyond its
+// trajectory serves no horizon > s; the clamp keeps the read inside As).  Unclipped: metrpo_rollout_actions clips (env_helpers.py:216, :599).
+__global__ void __launch_bounds__(ME_WG) k_window_actions(const float* __restrict__ As, float* __restrict__ dst, int W, int Tw, int T, int na, int hmax) {
+    const long long per = (long long)W * na, n = per * hmax;
     for (long long e = (long long)blockIdx.x * ME_WG + threadIdx.x; e < n; e += (long long)gridDim.x * ME_WG) {
-        const int w = (int)(e / na), j = (int)(e - (long long)w * na);
+        const int s = (int)(e / per);
+        const long long r = e - (long long)s * per;
+        const int w = (int)(r / na), j = (int)(r - (long long)w * na);
         const int i = w / Tw, t = w - i * Tw;
         const int ts = min(t + s, T - 1);
         dst[e] = As[((long long)i * T + ts) * na + j];
@@ -229,16 +231,18 @@ int run_model_error(metrpo_ctx* c, const metrpo_model_error_args* a, hipStream_t
             const int rc = metrpo_rollout(c, &r, (void*)st);
             if (rc) return rc;
         } else {
-            // get_error_distribution(known_actions=True) (env_helpers.py:216-222): the dynamics stepped with the recorded actions, one metrpo_step launch per step
+            // get_error_distribution(known_actions=True) (env_helpers.py:216-222): the recorded actions of every step gathered once, then the body of
+            // metrpo_rollout_actions (rollout_actions.hip) from the window starts in row 0 of obs
             { const int rc = launch_window_starts(c, a->d_Os, a->n, a->T, Tw, obs, st); if (rc) return rc; }
             float* act = (float*)(ws + o_act);
-            for (int s = 0; s < hmax; ++s) {
-                hipLaunchKernelGGL(k_window_actions, dim3(flat_grid(c, (long long)W * na)), dim3(ME_WG), 0, st, a->d_As, act, W, Tw, a->T, na, s);
-                HIP_TRY(c, hipGetLastError());
-                const int rc = launch_step(c, obs + (size_t)s * W * ns, act, W, sam, d_model, nullptr, obs + (size_t)(s + 1) * W * ns, rew + (size_t)s * W,
-                                           done + (size_t)s * W, nullptr, st);
-                if (rc) return rc;
-            }
+            hipLaunchKernelGGL(k_window_actions, dim3(flat_grid(c, (long long)HW * na)), dim3(ME_WG), 0, st, a->d_As, act, W, Tw, a->T, na, hmax);
+            HIP_TRY(c, hipGetLastError());
+            metrpo_rollout_actions_args ra = {};
+            ra.B = W; ra.T = hmax; ra.sam_mode = sam; ra.uniform_model = one_head ? a->model : -1;
+            ra.d_init_obs = obs; ra.d_actions = act; ra.d_model = d_model;
+            ra.d_obs = obs; ra.d_rew = rew; ra.d_done = done;
+            const int rc = run_rollout_actions(c, &ra, st);
+            if (rc) return rc;
         }
         t_obs = obs; t_rew = rew; t_done = done; t_last = last;
     }

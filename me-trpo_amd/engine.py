@@ -290,6 +290,49 @@ class Engine(object):
                                   _ptr(s_next), _ptr(rew), _ptr(done), _ptr(nall), self._stream()))
         return (s_next, rew, done, nall) if want_all else (s_next, rew, done)
 
+    # ------------------------------------------------------------------ open-loop replay of supplied actions
+    def rollout_actions(self, init_obs, actions, sam_mode='model_mean', model=None, model_idx=None, noise=None, force_step_loop=False, out=None):
+        """metrpo_rollout_actions: T chained step() calls in one call -- init_obs [B, ns], actions [T, B, na] unclipped (clipped inside, never written).
+        model: an int (eps_rand: every env uses that head) or a [B] int tensor (eps_rand: a head per env); model_idx [T, B] for step_rand, noise
+        [T, B, ns] for model_mean_std.  -> (obs [T+1, B, ns] with row 0 = init_obs, rew [T, B], done [T, B] uint8), device tensors, nothing
+        synchronised.  A done neither stops nor resets an env.  out = (obs, rew, done): write into these tensors instead (contiguous, at least that large)."""
+        dev = self.device
+        init_obs = _f32(init_obs, dev)
+        if init_obs.dim() != 2 or init_obs.shape[1] != self.ns:
+            raise ValueError("init_obs: expected [B, %d], got %s" % (self.ns, tuple(init_obs.shape)))
+        B = init_obs.shape[0]
+        actions = _f32(actions, dev)
+        if actions.dim() != 3 or actions.shape[1] != B or actions.shape[2] != self.na:
+            raise ValueError("actions: expected [T, %d, %d], got %s" % (B, self.na, tuple(actions.shape)))
+        T = actions.shape[0]
+        a = _lib.RolloutActionsArgs()
+        a.B, a.T, a.sam_mode, a.uniform_model, a.force_step_loop = B, T, _lib.SAM_MODES[sam_mode], -1, int(bool(force_step_loop))
+        d_model = None
+        if model is not None:
+            if isinstance(model, (int, np.integer)):
+                a.uniform_model = int(model)
+            else:
+                d_model = _i32(model, dev, (B,))
+        model_idx = _i32(model_idx, dev, (T, B)); noise = _f32(noise, dev, (T, B, self.ns))
+        if out is None:
+            out = (torch.empty(T + 1, B, self.ns, dtype=torch.float32, device=dev), torch.empty(T, B, dtype=torch.float32, device=dev),
+                   torch.empty(T, B, dtype=torch.uint8, device=dev))
+        obs, rew, done = out
+        assert obs.dtype == torch.float32 and rew.dtype == torch.float32 and done.dtype == torch.uint8 and all(t.is_contiguous() for t in out)
+        assert obs.numel() >= (T + 1) * B * self.ns and rew.numel() >= T * B and done.numel() >= T * B
+        a.d_init_obs, a.d_actions = init_obs.data_ptr(), actions.data_ptr()
+        for name, t in (('d_model', d_model), ('d_model_idx', model_idx), ('d_sel_noise', noise)):
+            setattr(a, name, t.data_ptr() if t is not None else None)
+        a.d_obs, a.d_rew, a.d_done = obs.data_ptr(), rew.data_ptr(), done.data_ptr()
+        self._chk(lib.metrpo_rollout_actions(self._ctx, C.byref(a), self._stream()))
+        self._ra_keep = (init_obs, actions, d_model, model_idx, noise)             # alive until the stream has consumed them
+        return obs, rew, done
+
+    def last_rollout_actions_kernel(self):
+        """Path the last rollout_actions() (or model_error(known_actions=True)) of this engine took: 'fused' (all steps in one launch,
+        rollout_actions.hip), 'step-loop' (step()'s kernel once per step); None before the first."""
+        return {0: 'step-loop', 1: 'fused'}.get(int(lib.metrpo_last_rollout_actions_kernel(self._ctx)))
+
     # ------------------------------------------------------------------ fused rollout
     def rollout(self, B, T, H, sam_mode, pool, determ=False, eval_all_heads=True, seed=0, stream_offset=0,
                 eps=None, model_idx=None, sel_noise=None, reset_idx=None, reset_model=None, out=None,

@@ -88,6 +88,30 @@ def model_error_windows(engine, Os):
     return out
 
 
+def open_loop_predictions(engine, initial_states, actions, model=-1):
+    """Replay recorded actions through the ensemble: the loop of get_error_distribution(known_actions=True), env_helpers.py:216-230, without the
+    comparison.  initial_states [n, ns]; actions [n, T, na], trajectory-major as recorded, unclipped (clipped on the device, :216).
+    model = -1: the mean over the heads, else that head.  -> (states [n, T+1, ns] with states[:, 0] = initial_states, costs [n, T], done [n, T]
+    uint8) device tensors, trajectory-major.  A done (Ant's is_done of the predicted state) neither stops nor resets a trajectory.
+    One fused launch on the shapes Engine.last_rollout_actions_kernel() reports as 'fused', step()'s kernel once per step otherwise."""
+    dev = engine.device
+    init = torch.as_tensor(initial_states, device=dev).to(torch.float32)
+    if init.dim() != 2 or init.shape[1] != engine.ns or init.shape[0] < 1:
+        raise ValueError("initial_states: expected [n, %d] with n >= 1, got %s" % (engine.ns, tuple(init.shape)))
+    n = init.shape[0]
+    act = torch.as_tensor(actions, device=dev).to(torch.float32)
+    if act.dim() != 3 or act.shape[0] != n or act.shape[2] != engine.na or act.shape[1] < 1:
+        raise ValueError("actions: expected [%d, T, %d] with T >= 1, got %s" % (n, engine.na, tuple(act.shape)))
+    if not (-1 <= int(model) < engine.K):
+        raise ValueError("model = %r is neither -1 (ensemble mean) nor a head below K = %d" % (model, engine.K))
+    act_tm = act.transpose(0, 1).contiguous()                                      # time-major [T, n, na], the device layout
+    if int(model) < 0:
+        obs, rew, done = engine.rollout_actions(init.contiguous(), act_tm, 'model_mean')
+    else:
+        obs, rew, done = engine.rollout_actions(init.contiguous(), act_tm, 'eps_rand', model=int(model))
+    return obs.transpose(0, 1).contiguous(), (-rew).transpose(0, 1).contiguous(), done.transpose(0, 1).contiguous()
+
+
 def _write_stats(stats, data):
     """write_stats (env_helpers.py:61-70) on a device tensor [N] or [N, ns]; percentiles by linear interpolation, as np.percentile."""
     q = torch.quantile(data.to(torch.float64), torch.tensor([1.0, 0.0, 0.75, 0.25, 0.5], dtype=torch.float64, device=data.device), dim=0)
