@@ -73,6 +73,7 @@ def main(argv=None):
     np.random.seed(0)
     env, K, T = args.env, args.K, args.T
     eng = M.Engine(env, K, (64, 64), (32, 32))
+    # eng.set_dyn_precision('bf16')     # wide nets only (hidden (512, 512), (1024, 1024): the step-wise GEMM shapes): imagined rollouts on bf16 operands, f32 elsewhere
     Ws, bs, norm = synthetic.make_dynamics(env, K, (64, 64), seed=1)
     eng.set_dynamics_layers(Ws, bs, norm['in_mean'], norm['in_std'], norm['diff_mean'], norm['diff_std'])
     policy = M.GaussianMLPPolicy(eng, init_std=1.0, seed=0)

@@ -195,12 +195,36 @@ typedef struct {
 } metrpo_rollout_args;
 int32_t metrpo_rollout(metrpo_ctx* ctx, const metrpo_rollout_args* args, void* stream);
 /* Which kernel family the last metrpo_rollout of this context ran on (-1 none yet; 0 thread-per-env, 1 head-per-wave fused, 2 cooperative fused, 3 step-wise
- * GEMM, 4 resident, 5 step-wise stream-K, 6 persistent stream-K), and -- when the shape fell off the fast dispatch table (2 x 64 nets with more heads than the
+ * GEMM, 4 resident, 5 step-wise stream-K, 6 persistent stream-K, 7 step-wise GEMM with bf16 operands: metrpo_set_dyn_precision below), and -- when the shape fell off the fast dispatch table (2 x 64 nets with more heads than the
  * fused kernels hold: K > 10, Ant > 8, half-cheetah > 9, or K > 5 on a shared device; hidden widths that are neither 64 nor multiples of 256; INTEGRATION.md
  * section 9 has the table and the measured cost) -- why ("" otherwise; also printed once per context on stderr unless option QUIET is set).  The reference has one code path for every shape
  * (env_helpers.py:609-635); these two calls are how a caller learns which of this library's it got. */
 int32_t metrpo_last_rollout_kernel(const metrpo_ctx* ctx);
 const char* metrpo_rollout_note(const metrpo_ctx* ctx);
+
+/* ---- opt-in bf16-operand dynamics forward inside metrpo_rollout (an EXTENSION: the reference computes in f32 throughout) ----
+ * The f32 matrix instruction of gfx950 runs at 1/16 of the bf16 one's rate and there is no xf32 form.  The dynamics model is a residual,
+ * s' = s + diff_mean + diff_std * net(...) (training.py:257): the state itself stays f32, operand rounding touches only the predicted change.
+ * With METRPO_DYN_BF16 every dynamics layer l of every head computes, inside metrpo_rollout,
+ *     out[b][j] = act_l( b_l[j] + sum_i bf16(in[b][i]) * bf16(W_l[i][j]) )
+ *   - bf16(.) is round-to-nearest-even from f32, applied to the layer's input (the normalised, column-dropped [s, clip(a)] for layer 0, the previous
+ *     layer's activations otherwise) and to the weights.  A hidden activation is rounded exactly once: the f32 value act(b + sum) is what gets rounded.
+ *   - products are exact in f32; the sum is accumulated in f32 in the matrix instruction's order (v_mfma_f32_32x32x16_bf16, k ascending in steps of 16).
+ *   - bias add and activation stay f32, and so does everything outside the matrix products: normalisation, the column drop, de-normalisation plus
+ *     residual, head selection (all six sam_modes), reward, is_done, reset, the policy, and every Philox draw -- the same code and the same draws as under F32.
+ *   - metrpo_rollout ONLY.  metrpo_step, metrpo_validation_cost, metrpo_bptt_grad*, metrpo_lbfgs_*, metrpo_dyn_train_*, metrpo_dyn_eval_losses,
+ *     metrpo_model_error and metrpo_rollout_actions compute in f32 whatever the setting: the models are trained and validated in f32 and early stopping
+ *     judges the policy on the f32 models; only the sampling that feeds the TRPO / VPG / PPO update runs on rounded operands.
+ *   - supported exactly on the contexts whose f32 rollout runs on a step-wise GEMM family (3, 5, 6 of metrpo_last_rollout_kernel): every hidden layer
+ *     >= 16 units, ns <= 64, and not a fused 2 x 64-class shape.  On any other context the setter returns METRPO_EUNSUPPORTED, metrpo_last_error names
+ *     the shape, and the precision stays F32: there is no silent f32 under a bf16 label.
+ *   - such a rollout reports family 7 and an empty metrpo_rollout_note.  It launches per step: stop_batch / d_stop_cum are ignored (see above); the
+ *     continuation fields (t0, d_init_*, d_last_*, d_stop) work as on family 3.  The bf16 weight image is rebuilt from the context's f32 weights at
+ *     the start of every such call (no cache), so metrpo_set_dynamics*, metrpo_dyn_train_step and checkpoint loads are always seen.
+ * The setter takes effect at the next metrpo_rollout; the default is METRPO_DYN_F32, under which nothing changes.  Unknown value: METRPO_EINVAL. */
+typedef enum { METRPO_DYN_F32 = 0, METRPO_DYN_BF16 = 1 } metrpo_dyn_precision;
+int32_t metrpo_set_dyn_precision(metrpo_ctx* ctx, int32_t precision);
+int32_t metrpo_get_dyn_precision(const metrpo_ctx* ctx);
 
 /* Loop condition of obtain_samples (samplers/vectorized_sampler.py:60,104): n_samples counts the samples of COMPLETED paths
  * only and is tested once per time step.  For the chunk [t0, t0+T) just rolled out (d_done, d_tpath [T][B]) this adds each

@@ -11,6 +11,7 @@ MAX_LAYERS = 6
 
 ENV_IDS = {'swimmer': 0, 'half_cheetah': 1, 'half-cheetah': 1, 'ant': 2, 'humanoid': 3, 'hopper': 4, 'snake': 5}
 SAM_MODES = {'step_rand': 0, 'eps_rand': 1, 'model_mean_std': 2, 'model_mean': 3, 'model_med': 4, 'one_model': 5}
+DYN_PRECISIONS = {'f32': 0, 'bf16': 1}          # metrpo_dyn_precision
 ACTS = {'identity': 0, 'tf.identity': 0, 'relu': 1, 'tf.nn.relu': 1, 'tanh': 2, 'tf.nn.tanh': 2, 'tf.tanh': 2}
 
 
@@ -166,6 +167,8 @@ SYMBOLS = {
     'metrpo_option_name': (C.c_char_p, [_I]),
     'metrpo_last_rollout_kernel': (_I, [_P]),
     'metrpo_rollout_note': (C.c_char_p, [_P]),
+    'metrpo_set_dyn_precision': (_I, [_P, _I]),
+    'metrpo_get_dyn_precision': (_I, [_P]),
     'metrpo_policy_adam_reset': (_I, [_P, _P]),
     'metrpo_policy_adam_step': (_I, [_P, _P, _D, _D, _D, _D, _D, _P]),
     'metrpo_lbfgs_begin': (_I, [_P, _I, _P, C.POINTER(LbfgsOpts), _P, _P]),

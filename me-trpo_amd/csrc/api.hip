@@ -356,6 +356,10 @@ extern "C" int32_t metrpo_rollout(metrpo_ctx* c, const metrpo_rollout_args* a, v
         return set_err(c, METRPO_EINVAL, "rollout: d_init_obs, d_init_ts and d_init_model must be given together");
     if (a->B == 0 || a->T == 0) return METRPO_OK;
     c->rollout_note.clear();
+    if (c->dyn_precision == METRPO_DYN_BF16) {                                               // opt-in (metrpo_set_dyn_precision: GEMM-class shapes only)
+        c->last_rollout_kernel = 7;
+        return launch_rollout_gemm(c, a, (hipStream_t)stream);
+    }
     if (c->mfma_cfg >= 0 || c->coop_cfg >= 0 || c->coop_pad_cfg >= 0) {
         int coop = 0;
         const int rc = launch_rollout_mfma(c, a, (hipStream_t)stream, &coop);
@@ -400,8 +404,24 @@ extern "C" int32_t metrpo_rollout(metrpo_ctx* c, const metrpo_rollout_args* a, v
 // why the last metrpo_rollout of this context ran outside the fast dispatch table ("" when it did not)
 extern "C" const char* metrpo_rollout_note(const metrpo_ctx* c) { return c ? c->rollout_note.c_str() : ""; }
 // which kernel family the last metrpo_rollout of this context ran on (-1: none yet): 0 generic, 1 head-per-wave MFMA, 2 cooperative MFMA,
-// 3 step-wise GEMM, 4 resident (rollout_resident.hip), 5 step-wise with the stream-K fused ensemble kernel (mlp_streamk.h)
+// 3 step-wise GEMM, 4 resident (rollout_resident.hip), 5 step-wise with the stream-K fused ensemble kernel (mlp_streamk.h), 6 persistent stream-K (mlp_persist.h:
+// all steps of a chunk in one launch), 7 step-wise GEMM with bf16 operands (rollout_bf16.hip; metrpo_set_dyn_precision below)
 extern "C" int32_t metrpo_last_rollout_kernel(const metrpo_ctx* c) { return c ? c->last_rollout_kernel : METRPO_ENULL; }
+// Operand precision of the dynamics forward inside metrpo_rollout.  BF16 exactly where the f32 rollout runs on a GEMM-class family (3, 5, 6): the GEMM path takes
+// the shape and it is not one of the fused 2 x 64-class shapes; anywhere else the setter refuses and the precision stays what it was
+extern "C" int32_t metrpo_set_dyn_precision(metrpo_ctx* c, int32_t precision) {
+    if (!c) return METRPO_ENULL;
+    if (precision != METRPO_DYN_F32 && precision != METRPO_DYN_BF16) return set_err(c, METRPO_EINVAL, "set_dyn_precision: unknown precision " + std::to_string(precision));
+    if (precision == METRPO_DYN_BF16 && (!gemm_path_applicable(c) || c->mfma_cfg >= 0 || c->coop_cfg >= 0 || c->coop_pad_cfg >= 0 || mfma_shape_config(c) >= 0)) {
+        std::string w;
+        for (int l = 1; l < c->pd.dyn.n_layers; ++l) w += (l > 1 ? "x" : "") + std::to_string(c->pd.dyn.dims[l]);
+        return set_err(c, METRPO_EUNSUPPORTED, "set_dyn_precision: bf16 operands need a shape of the step-wise GEMM rollout families (every hidden layer >= 16 units, ns <= 64, not a fused "
+                                               "2 x 64-class shape); dynamics hidden " + w + ", ns = " + std::to_string(c->pd.ns) + ", K = " + std::to_string(c->pd.K) + " is not one: precision stays f32");
+    }
+    c->dyn_precision = precision;
+    return METRPO_OK;
+}
+extern "C" int32_t metrpo_get_dyn_precision(const metrpo_ctx* c) { return c ? c->dyn_precision : METRPO_ENULL; }
 
 extern "C" int32_t metrpo_sampler_progress(metrpo_ctx* c, const uint8_t* done, const int32_t* tpath, int32_t T, int32_t B, int32_t t0,
                                            int64_t batch_size, double* counts, double* state, int32_t* stop, void* stream) {

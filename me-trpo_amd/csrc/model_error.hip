@@ -228,7 +228,10 @@ int run_model_error(metrpo_ctx* c, const metrpo_model_error_args* a, hipStream_t
             r.d_obs = obs; r.d_act = (float*)(ws + o_act); r.d_rew = rew; r.d_mean = (float*)(ws + o_mean); r.d_done = done;
             r.d_tpath = (int32_t*)(ws + o_tpath); r.d_last_obs = last;
             r.d_init_obs = init; r.d_init_ts = d_ts; r.d_init_model = d_model;
+            const int prec = c->dyn_precision;       // the diagnostic judges the f32 models whatever metrpo_set_dyn_precision says
+            c->dyn_precision = METRPO_DYN_F32;
             const int rc = metrpo_rollout(c, &r, (void*)st);
+            c->dyn_precision = prec;
             if (rc) return rc;
         } else {
             // get_error_distribution(known_actions=True) (env_helpers.py:216-222): the recorded actions of every step gathered once, then the body of

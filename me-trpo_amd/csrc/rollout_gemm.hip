@@ -779,7 +779,13 @@ static int rollout_gemm_chunk(metrpo_ctx* c, const metrpo_rollout_args* a, hipSt
     for (int l = 1; l < L; ++l) maxh = std::max(maxh, pd.dyn.dims[l]);
     // workspace (floats): S, X, U, HA, HB, OUT + ints ts, cur_model
     auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };       // keep every sub-buffer 16-byte aligned
-    SkPath sk = sk_select(c, B);
+    // The ONE place where the operand precision (metrpo_set_dyn_precision) shapes this function's plan: bf16 takes the plain tile-GEMM branch below -- no
+    // stream-K (hence no persistent launch), no fused output tile, no split-K partials -- with hidden buffers of bf16; its layers are launched by
+    // rollout_bf16.hip where the f32 layer loop stands.  With f32 every value here is what it was before the branch existed.
+    const bool bf = c->dyn_precision == METRPO_DYN_BF16;
+    SkPath sk = bf ? SkPath{} : sk_select(c, B);
+    const bool fuse_allowed = !bf, skinny_parts = !bf;
+    const size_t hid_floats = bf ? bf16_hidden_floats(pd, B) : (size_t)K * B * maxh;      // one hidden-activation buffer
     // stored layer 0 (modes 2, 3) by k_l0_rows: the bias rides as input row n_in, as for the producer of mode 1 (METRPO_NO_L0_ROWS: the tile GEMM)
     const int S0all = (pd.nin + 1 + 3) / 4;
     // (below one tile per CU -- the late split -- the 64 x 64-tile GEMM is the faster layer 0: 11.9 vs 21.2 us at 500 rows per head)
@@ -787,9 +793,9 @@ static int rollout_gemm_chunk(metrpo_ctx* c, const metrpo_rollout_args* a, hipSt
     const bool l0r = sk.mode >= 2 && !sk_small && l0_rows_ok(S0all) && pd.dyn.dims[1] % 256 == 0 && pd.dyn.act[0] == METRPO_ACT_RELU &&
                      pd.dyn.b_off[0] == pd.dyn.w_off[0] + pd.nin * pd.dyn.dims[1] && ctx_opt(c, OPT_NO_L0_ROWS) == nullptr;
     const int ldx = (sk.mode == 1) ? 4 * sk.S0 : (l0r ? 4 * S0all : ((pd.nin + 3) & ~3));
-    const size_t nS = up4((size_t)B * pd.ns), nX = up4((size_t)B * ldx), nU = up4((size_t)B * pd.na), nH = (sk.mode == 1) ? 0 : up4((size_t)K * B * maxh), nO = up4((size_t)K * B * pd.ns);
+    const size_t nS = up4((size_t)B * pd.ns), nX = up4((size_t)B * ldx), nU = up4((size_t)B * pd.na), nH = (sk.mode == 1) ? 0 : up4(hid_floats), nO = up4((size_t)K * B * pd.ns);
     size_t nP = 0;
-    for (int l = 0; l < L; ++l) nP = std::max(nP, up4(skinny_part_floats(B, pd.dyn.dims[l + 1], pd.dyn.dims[l], K)));
+    for (int l = 0; l < L && skinny_parts; ++l) nP = std::max(nP, up4(skinny_part_floats(B, pd.dyn.dims[l + 1], pd.dyn.dims[l], K)));
     // stream-K path: output-layer partials per 256-column block, epilogue images, schedules, accumulator hand-over slots + flags
     const SkArgs& ska = (sk.mode == 2) ? sk.a2 : sk.a1;                      // the launch that carries the output layer
     size_t nSkImg = 0, nSkSched = 0, nSkX = 0, nSkFlag = 0;
@@ -802,7 +808,7 @@ static int rollout_gemm_chunk(metrpo_ctx* c, const metrpo_rollout_args* a, hipSt
     }
     // last hidden layer + output layer as ONE launch when the hidden layer runs on 64x64 tiles anyway (C0-params-file, C2, C3 shapes): its
     // activations (K x B x width floats: 51 MB at C3) are then neither written nor read back; k_big_post adds the width/64 partials
-    const int fuse_tile = (!sk.mode && L >= 2 && pd.dyn.act[L - 2] == METRPO_ACT_RELU && pd.dyn.act[L - 1] == METRPO_ACT_IDENTITY && ctx_opt(c, OPT_NO_FUSED_OUT) == nullptr)
+    const int fuse_tile = (fuse_allowed && !sk.mode && L >= 2 && pd.dyn.act[L - 2] == METRPO_ACT_RELU && pd.dyn.act[L - 1] == METRPO_ACT_IDENTITY && ctx_opt(c, OPT_NO_FUSED_OUT) == nullptr)
                               ? gemm_fused_out_tile(B, pd.dyn.dims[L - 1], K, pd.ns) : 0;
     const bool fuse_out = fuse_tile > 0;
     if (fuse_out) nP = std::max(nP, up4(gemm_fused_out_part_floats(B, pd.dyn.dims[L - 1], K, pd.ns, fuse_tile)));
@@ -987,6 +993,8 @@ static int rollout_gemm_chunk(metrpo_ctx* c, const metrpo_rollout_args* a, hipSt
                 HIP_TRY(c, sk.v2.launch(sk.a2, sk.p2, st));
             }
         }
+        if (bf) { const int rc = launch_bf16_layers(c, bs.X, bs.ldx, bs.HA, bs.HB, bs.OUT, B, st); if (rc) return rc; }      // OUT [K][B][ns], out_splits = 0
+        else
         for (int l = 0; l < L && !sk.mode; ++l) {
             // layer 0 contracts over the PADDED input row (X's pad columns are 0, the weight rows they meet are the first bias entries that follow
             // W0 in the resident layout: finite x 0): a contraction length that is a multiple of 4 takes the GEMM's aligned load path
@@ -1067,6 +1075,7 @@ int launch_rollout_gemm(metrpo_ctx* c, const metrpo_rollout_args* a, hipStream_t
     // GEMMs over R B rows instead of R GEMMs over B (B = 100 fills 100 of 128 tile rows, 500 fill 500 of 512; params-humanoid.json: 27.7 -> see DESIGN).
     // Row b of the merged batch = env b % B of round b / B (RolloutK::vB / vR); same draws, same trajectory rows as the round-by-round loop.
     const bool merged = par && (long long)R * B <= 1024 && ctx_opt(c, OPT_NO_MERGED_ROUNDS) == nullptr;
+    if (c->dyn_precision == METRPO_DYN_BF16) { const int rc = launch_bf16_dyn_image(c, st); if (rc) return rc; }      // in front of the fork: every round reads it
     size_t need1 = 0;
     {
         metrpo_rollout_args probe = *a;

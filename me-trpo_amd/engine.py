@@ -168,6 +168,19 @@ class Engine(object):
         launch (resident rollout / validation, migrating tiles) are never selected.  Default True."""
         self._chk(lib.metrpo_set_exclusive(self._ctx, int(bool(exclusive))))
 
+    def set_dyn_precision(self, precision):
+        """Operand precision of the dynamics forward inside rollout() (`metrpo_set_dyn_precision`): 'f32' (default, exact) or 'bf16' -- layer inputs and
+        weights rounded to bf16 (nearest even), f32 accumulation, everything outside the matrix products unchanged (include/metrpo.h has the full
+        semantics).  rollout() only: step, validation_cost, bptt_grad, training, eval_losses, model_error and rollout_actions stay f32.  Shapes outside
+        the step-wise GEMM rollout families raise MetrpoError (the precision then stays 'f32').  Takes effect at the next rollout()."""
+        if precision not in _lib.DYN_PRECISIONS:
+            raise ValueError("dyn precision %r: one of %s" % (precision, sorted(_lib.DYN_PRECISIONS)))
+        self._chk(lib.metrpo_set_dyn_precision(self._ctx, _lib.DYN_PRECISIONS[precision]))
+
+    @property
+    def dyn_precision(self):
+        return {v: k for k, v in _lib.DYN_PRECISIONS.items()}[int(lib.metrpo_get_dyn_precision(self._ctx))]
+
     def set_option(self, key, value=None):
         """Variant / tuning switch of THIS engine (`metrpo_set_option`): `key` is one of `Engine.option_names()` (the former METRPO_<KEY> environment
         variables; the environment only fills the defaults when the engine is created), `value` a string / number, None unsets.  Read at the next launch."""
@@ -399,15 +412,19 @@ class Engine(object):
                                               _ptr(counts), _ptr(state), _ptr(stop), self._stream()))
 
     def rollout_path(self):
-        """3 step-wise GEMM (large nets), 2 cooperative-heads MFMA, 1 head-per-wave MFMA, 0 generic (current selection)."""
+        """7 step-wise GEMM with bf16 operands (set_dyn_precision('bf16')), 3 step-wise GEMM (large nets), 2 cooperative-heads MFMA, 1 head-per-wave MFMA,
+        0 generic (current selection)."""
+        if self.dyn_precision == 'bf16':
+            return 7
         return int(lib.metrpo_set_rollout_variant(self._ctx, int(getattr(self, '_variant', 0))))
 
     def last_rollout_kernel(self):
         """Kernel family the last rollout() of this engine ran on: 'generic', 'mfma-head-per-wave', 'mfma-cooperative', 'gemm-stepwise',
         'resident' (whole time loop in one launch, rollout_resident.hip), 'gemm-streamk' (step-wise, the whole ensemble of a step in one
-        evenly split launch, mlp_streamk.h), 'streamk-persistent' (all steps of a chunk in one launch, rollout_persist.hip); None before the first rollout."""
+        evenly split launch, mlp_streamk.h), 'streamk-persistent' (all steps of a chunk in one launch, rollout_persist.hip), 'gemm-bf16' (step-wise tile GEMMs
+        on bf16 operands, rollout_bf16.hip: set_dyn_precision('bf16')); None before the first rollout."""
         k = int(lib.metrpo_last_rollout_kernel(self._ctx))
-        return {0: 'generic', 1: 'mfma-head-per-wave', 2: 'mfma-cooperative', 3: 'gemm-stepwise', 4: 'resident', 5: 'gemm-streamk', 6: 'streamk-persistent'}.get(k)
+        return {0: 'generic', 1: 'mfma-head-per-wave', 2: 'mfma-cooperative', 3: 'gemm-stepwise', 4: 'resident', 5: 'gemm-streamk', 6: 'streamk-persistent', 7: 'gemm-bf16'}.get(k)
 
     def rollout_note(self):
         """Why the last rollout() ran outside the fast dispatch table (K != 5 at 2x64, hidden widths 65..127, ...); '' when it did not."""

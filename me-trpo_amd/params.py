@@ -6,7 +6,8 @@ half: it only reads the keys and says which shapes the run has -- what tests/tes
 
 Keys read (params-swimmer.json:5-86):
     env, algo, n_models
-    dynamics_model.{hidden_layers, nonlinearity, ignore_xy_input | ignore_x_input, prediction_type, use_logit_weights, regularization.constant}
+    dynamics_model.{hidden_layers, nonlinearity, ignore_xy_input | ignore_x_input, prediction_type, use_logit_weights, regularization.constant,
+                    rollout_precision (EXTENSION, see below)}
     policy.hidden_layers
     policy_opt_params.{T, gamma, mode, whole, log_every, num_iters_threshold, max_iters, batch_size, sam_mode, learning_rate, grad_norm_clipping,
                        stop_critereon.{threshold, offset, percent_models_threshold}, trpo.{init_std, step_size, discount, batch_size, reset,
@@ -18,7 +19,9 @@ Keys read (params-swimmer.json:5-86):
                          stop_critereon.{threshold, offset}}
 'algo' builds 'trpo', 'vpg' (training.py:337-352: VPG with the vpg block's batch size, discount and log_std reset), 'bptt' and 'bptt-stochastic';
 svg and l-bfgs raise.  trpo.subsample_factor is an EXTENSION key (default 1.0: the reference's run; below 1 the Fisher-vector products of the update
-see that fraction of the batch, [rllab] ConjugateGradientOptimizer(subsample_factor)); it is reported as shapes['trpo_ext'].  'ppo' (algos/ppo.py) is an EXTENSION: the reference's training.py has no such branch and its params files no ppo block; the
+see that fraction of the batch, [rllab] ConjugateGradientOptimizer(subsample_factor)); it is reported as shapes['trpo_ext'].  dynamics_model.rollout_precision is an EXTENSION key too ('f32' default: the reference's arithmetic; 'bf16': the
+imagined rollouts that feed the TRPO / VPG / PPO update run their dynamics layers on bf16 operands, Engine.set_dyn_precision; training, validation and
+early stopping stay f32); it is reported as shapes['dyn_ext'] and applied by from_params once the engine exists.  'ppo' (algos/ppo.py) is an EXTENSION: the reference's training.py has no such branch and its params files no ppo block; the
 block's defaults are ppo.py's (clip_lr 0.3, entropy_bonus_coeff 0, use_kl_penalty false, initial_kl_penalty 1, step_size 0.01), AdamOptimizer's (n_epochs 10, learning_rate 1e-3) and the vpg block's.  Everything else in the files (rollout_params, sweep_iters, sample_size, *_path) steers the reference's real-simulator data collection and outer
 sweeps, which are out of scope here; those keys are passed through untouched in `Setup.params`."""
 import json
@@ -56,6 +59,9 @@ def shapes_from_params(path_or_dict):
     if None in acts or len(acts) != len(dm['hidden_layers']):                    # training.py:156 asserts the lengths agree
         raise ValueError("dynamics_model.nonlinearity = %r: one of %s per hidden layer" % (dm.get('nonlinearity'), sorted(_ACTS)))
     n_drop = 2 if dm.get('ignore_xy_input') else (1 if dm.get('ignore_x_input') else 0)      # training.py:146-154
+    rollout_precision = dm.get('rollout_precision', 'f32')
+    if rollout_precision not in ('f32', 'bf16'):
+        raise ValueError("dynamics_model.rollout_precision = %r: 'f32' or 'bf16'" % (rollout_precision,))
     trpo, vpg, ppo = po.get('trpo', {}), po.get('vpg', {}), po.get('ppo', {})
     algo = p.get('algo', 'trpo')
     T = int(po['T'])
@@ -82,6 +88,9 @@ def shapes_from_params(path_or_dict):
         # EXTENSION key of the trpo block (no reference params file has it): [rllab] ConjugateGradientOptimizer(subsample_factor), the fraction of the batch
         # the Fisher-vector products see; 1.0 = the reference's run (algos/trpo.py:18-20 passes no optimizer_args).  Kept apart from the reference's keys above.
         trpo_ext=dict(subsample_factor=float(trpo.get('subsample_factor', 1.0))),
+        # EXTENSION key of the dynamics_model block (no reference params file has it): operand precision of the dynamics forward inside the imagined rollouts
+        # (Engine.set_dyn_precision); 'f32' = the reference's arithmetic.  Kept apart from the reference's keys above.
+        dyn_ext=dict(rollout_precision=rollout_precision),
         # the KL penalty's keys of the same params block (ppo.py:27-28, :34), kept apart from the dict above
         ppo_kl=dict(use_kl_penalty=bool(ppo.get('use_kl_penalty', False)), initial_kl_penalty=float(ppo.get('initial_kl_penalty', 1.0)),
                     step_size=float(ppo.get('step_size', 0.01))),
@@ -131,6 +140,8 @@ def from_params(path_or_dict, device=0, init_states=None, comm=None, seed=0, n_e
                          "are not built from a params file (the 'l-bfgs' update runs as metrpo_amd.LBFGS)" % sh['algo'])
     blk = sh['vpg'] if sh['algo'] == 'vpg' else sh['ppo'] if sh['algo'] == 'ppo' else sh['trpo']     # init_std / reset of the rllab algorithm that runs (training.py:350-352, 368-370)
     eng = Engine(sh['env'], sh['K'], sh['dyn_hidden'], sh['pol_hidden'], n_drop=sh['n_drop'], dyn_act=sh['dyn_act'], device=device)
+    if sh['dyn_ext']['rollout_precision'] != 'f32':
+        eng.set_dyn_precision(sh['dyn_ext']['rollout_precision'])      # a shape outside the GEMM rollout families raises the library's message
     policy = GaussianMLPPolicy(eng, init_std=blk['init_std'], seed=seed)
     baseline = LinearFeatureBaseline()
     pool = InitStatePool(synthetic.make_pool(sh['env']) if init_states is None else init_states, sh['na'])

@@ -201,7 +201,7 @@ class VectorizedSampler(BaseSampler):
         buf, (last_ts, last_model) = self._ant_buf, self._ant_state
         state = torch.tensor([0.0, -1.0], dtype=torch.float64, device=dev)
         stop = torch.zeros(1, dtype=torch.int32, device=dev)
-        poll = eng.rollout_path() == 3
+        poll = eng.rollout_path() in (3, 7)            # the per-step GEMM families (f32 and bf16 operands): their GEMMs do not look at the stop flag
 
         def view(t_lo, t_hi):
             from .engine import Trajectory
