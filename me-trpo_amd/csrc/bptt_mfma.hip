@@ -10,9 +10,9 @@
 // so activations and deltas never leave registers between layers.  Constant factors are folded into the fragments: diff_std
 // into the first adjoint layer, 1/in_std and the column drop into the last one, which is split into a state part (rows = state
 // dims: lands in the layout of the residual path) and an action part (rows = action dims).
-// Forward dynamics fragments are register-resident; adjoint fragments and the policy's live in an LDS image shared by the 4
-// waves of a workgroup (same model).
-#include "mfma_common.h"
+// The forward dynamics head is dyn_head_mfma.h's (register-resident fragments; the layout is described there); adjoint fragments
+// and the policy's live in an LDS image shared by the 4 waves of a workgroup (same model).
+#include "dyn_head_mfma.h"
 
 enum { DET_FWD = 0, DET_BWD = 1 };
 
@@ -57,8 +57,7 @@ __global__ void __launch_bounds__(256, 2) k_det_mfma(int K, int B, int T, double
                                                     float* __restrict__ GM, double* __restrict__ cost_part, BpttNoise nz) {
     using L = DetL<ENV>;
     using C = typename L::C;
-    constexpr int NS = C::NS, NA = C::NA, NDROP = C::NDROP, NIN = C::NIN, DH = 64, PH = 32, OUT_CB = C::OUT_CB, NS_KS = C::NS_KS,
-                  NIN_KS = C::NIN_KS, RK = L::RK;
+    constexpr int NS = C::NS, NA = C::NA, NDROP = C::NDROP, DH = 64, PH = 32, OUT_CB = C::OUT_CB, NS_KS = C::NS_KS, RK = L::RK;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, q = lane >> 4;
@@ -72,26 +71,25 @@ __global__ void __launch_bounds__(256, 2) k_det_mfma(int K, int B, int T, double
     const float* dstd_p = norm + 2 * (NS + NA) + NS;
 
     // ---------------- LDS image: fragment tables (see header) and biases; each element written by one thread ----------------
-    auto chained = [&](int kk, int qq) { return 16 * (kk >> 2) + 4 * qq + (kk & 3); };
     for (int i = tid; i < L::IMG; i += 256) {
         float w = 0.0f;
         const int ln = i & 63, cc = ln & 15, qq = ln >> 4;
         if (i < L::O_PF1) { const int f = i >> 6, s = f >> 1, cb = f & 1, in = 4 * s + qq; if (in < NS) w = theta[C::pW0 + in * PH + 16 * cb + cc]; }
-        else if (i < L::O_PF2) { const int f = (i - L::O_PF1) >> 6, kk = f >> 1, cb = f & 1; w = theta[C::pW1 + chained(kk, qq) * PH + 16 * cb + cc]; }
-        else if (i < L::O_PB2) { const int kk = (i - L::O_PF2) >> 6; if (cc < NA) w = theta[C::pW2 + chained(kk, qq) * NA + cc]; }
+        else if (i < L::O_PF2) { const int f = (i - L::O_PF1) >> 6, kk = f >> 1, cb = f & 1; w = theta[C::pW1 + chained_in(kk, qq) * PH + 16 * cb + cc]; }
+        else if (i < L::O_PB2) { const int kk = (i - L::O_PF2) >> 6; if (cc < NA) w = theta[C::pW2 + chained_in(kk, qq) * NA + cc]; }
         else if (i < L::O_PB1) { const int f = (i - L::O_PB2) >> 6, r = f >> 1, cb = f & 1, d = 4 * qq + r; if (d < NA) w = theta[C::pW2 + (16 * cb + cc) * NA + d]; }
-        else if (i < L::O_PB0) { const int f = (i - L::O_PB1) >> 6, kk = f >> 1, cb = f & 1; w = theta[C::pW1 + (16 * cb + cc) * PH + chained(kk, qq)]; }
-        else if (i < L::O_DB2) { const int f = (i - L::O_PB0) >> 6, kk = f / OUT_CB, cb = f % OUT_CB, dim = 16 * cb + cc; if (dim < NS) w = theta[C::pW0 + dim * PH + chained(kk, qq)]; }
+        else if (i < L::O_PB0) { const int f = (i - L::O_PB1) >> 6, kk = f >> 1, cb = f & 1; w = theta[C::pW1 + (16 * cb + cc) * PH + chained_in(kk, qq)]; }
+        else if (i < L::O_DB2) { const int f = (i - L::O_PB0) >> 6, kk = f / OUT_CB, cb = f % OUT_CB, dim = 16 * cb + cc; if (dim < NS) w = theta[C::pW0 + dim * PH + chained_in(kk, qq)]; }
         else if (i < L::O_DB1) {                 // first adjoint layer of the dynamics: k-steps (cbd, r) over state dims, diff_std folded in
-            const int f = (i - L::O_DB2) >> 6, ks = f >> 2, cb = f & 3, dim = 16 * (ks >> 2) + 4 * qq + (ks & 3);
+            const int f = (i - L::O_DB2) >> 6, ks = f >> 2, cb = f & 3, dim = chained_in(ks, qq);
             if (dim < NS) w = pk[C::dW2 + (16 * cb + cc) * NS + dim] * dstd_p[dim];
         }
-        else if (i < L::O_DAS) { const int f = (i - L::O_DB1) >> 6, kk = f >> 2, cb = f & 3; w = pk[C::dW1 + (16 * cb + cc) * DH + chained(kk, qq)]; }
+        else if (i < L::O_DAS) { const int f = (i - L::O_DB1) >> 6, kk = f >> 2, cb = f & 3; w = pk[C::dW1 + (16 * cb + cc) * DH + chained_in(kk, qq)]; }
         else if (i < L::O_DAA) {                 // last adjoint layer, state rows: column drop and 1/in_std folded in
             const int f = (i - L::O_DAS) >> 6, kk = f / OUT_CB, cb = f % OUT_CB, dim = 16 * cb + cc;
-            if (dim >= NDROP && dim < NS) w = pk[C::dW0 + (dim - NDROP) * DH + chained(kk, qq)] / in_std[dim];
+            if (dim >= NDROP && dim < NS) w = pk[C::dW0 + (dim - NDROP) * DH + chained_in(kk, qq)] / in_std[dim];
         }
-        else if (i < L::O_BD0) { const int kk = (i - L::O_DAA) >> 6; if (cc < NA) w = pk[C::dW0 + (NS - NDROP + cc) * DH + chained(kk, qq)] / in_std[NS + cc]; }
+        else if (i < L::O_BD0) { const int kk = (i - L::O_DAA) >> 6; if (cc < NA) w = pk[C::dW0 + (NS - NDROP + cc) * DH + chained_in(kk, qq)] / in_std[NS + cc]; }
         else if (i < L::O_BD1) w = pk[C::db0 + (i - L::O_BD0)];
         else if (i < L::O_BD2) w = pk[C::db1 + (i - L::O_BD1)];
         else if (i < L::O_BP0) { const int u = i - L::O_BD2; if (u < NS) w = pk[C::db2 + u]; }
@@ -102,41 +100,12 @@ __global__ void __launch_bounds__(256, 2) k_det_mfma(int K, int B, int T, double
     }
 #define TAB2(off, ks, cb, ncb) IMG[(off) + (((ks) * (ncb)) + (cb)) * 64 + lane]
     // ---------------- register-resident forward dynamics fragments ----------------
-    float wd0[NIN_KS][4], wd1[16][4], wd2[MODE == DET_FWD ? 16 : 1][OUT_CB];
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb) {
-#pragma unroll
-        for (int s = 0; s < NIN_KS; ++s) { const int i = 4 * s + q; wd0[s][cb] = (i < NIN) ? pk[C::dW0 + i * DH + 16 * cb + c] : 0.0f; }
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk) wd1[kk][cb] = pk[C::dW1 + (16 * (kk >> 2) + 4 * q + (kk & 3)) * DH + 16 * cb + c];
-    }
-    if (MODE == DET_FWD) {
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk)
-#pragma unroll
-            for (int cb = 0; cb < OUT_CB; ++cb) { const int o = 16 * cb + c; wd2[kk][cb] = (o < NS) ? pk[C::dW2 + (16 * (kk >> 2) + 4 * q + (kk & 3)) * NS + o] : 0.0f; }
-    }
-    float nmean[NIN_KS], nstd[NIN_KS];
-    int nsrc[NIN_KS];
-#pragma unroll
-    for (int s = 0; s < NIN_KS; ++s) {
-        const int i = 4 * s + q;
-        int f = 0;
-        if (i < NS - NDROP) { f = i + NDROP; nsrc[s] = f; }
-        else if (i < NIN) { f = NS + (i - (NS - NDROP)); nsrc[s] = -(i - (NS - NDROP)) - 1; }
-        else { nsrc[s] = -1000000; }
-        nmean[s] = (i < NIN) ? norm[f] : 0.0f;
-        nstd[s] = (i < NIN) ? 1.0f / norm[(NS + NA) + f] : 1.0f;
-    }
-    f32x4 dmean[OUT_CB], dstd[OUT_CB];
-#pragma unroll
-    for (int cb = 0; cb < OUT_CB; ++cb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int dim = 16 * cb + 4 * q + r;
-            dmean[cb][r] = (dim < NS) ? norm[2 * (NS + NA) + dim] : 0.0f;
-            dstd[cb][r] = (dim < NS) ? norm[2 * (NS + NA) + NS + dim] : 0.0f;
-        }
+    DynHeadFrags<C, MODE == DET_FWD> head;                                   // the reverse sweep recomputes layers 0 and 1 only
+    DynInNorm<C> in;
+    DynOutNorm<C> out;
+    head.load(pk, c, q);
+    in.load(norm, q);
+    out.load(norm, q);
     const size_t xs_model = (size_t)model * (T + 1) * B * NS;
     float sd[4];                                                             // exp(log_std) of the action dims 4q .. 4q+3 (STOCH)
 #pragma unroll
@@ -192,35 +161,15 @@ __global__ void __launch_bounds__(256, 2) k_det_mfma(int K, int B, int T, double
             }
         }
         wave_lds_sync();
+        float xin[C::NIN_KS];
 #pragma unroll
-        for (int cb = 0; cb < 4; ++cb) h0[cb] = *(const f32x4*)&IMG[L::O_BD0 + 16 * cb + 4 * q];
-#pragma unroll
-        for (int s = 0; s < NIN_KS; ++s) {
-            float x = 0.0f;
-            if (nsrc[s] >= 0) x = ST[c * NS + nsrc[s]];
-            else if (nsrc[s] > -1000000) x = ACT[c * NA + (-nsrc[s] - 1)];
-            x = (nsrc[s] > -1000000) ? (x - nmean[s]) * nstd[s] : 0.0f;
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) h0[cb] = MFMA16(wd0[s][cb], x, h0[cb]);
-        }
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) {
-            h1[cb] = *(const f32x4*)&IMG[L::O_BD1 + 16 * cb + 4 * q];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) h0[cb][r] = fmaxf(h0[cb][r], 0.0f);
-        }
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk)
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) h1[cb] = MFMA16(wd1[kk][cb], h0[kk >> 2][kk & 3], h1[cb]);
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) h1[cb][r] = fmaxf(h1[cb][r], 0.0f);
+        for (int s = 0; s < C::NIN_KS; ++s) xin[s] = in.get(ST, NS, ACT, c, s);
+        head.layer0(h0, IMG + L::O_BD0, xin, ReluFmax());
+        head.layer1(h1, IMG + L::O_BD1, h0, ReluFmax());
     };
     const int lim = min(16, max(0, B - b0)) * NS;                            // floats of this tile in one [B][ns] slice
 
-    if (MODE == DET_FWD) {
+    if constexpr (MODE == DET_FWD) {
         // ------------------------------------------------ forward sweep ------------------------------------------------
         for (int i = lane; i < 16 * NS; i += 64) ST[i] = (i < lim) ? s0[(size_t)b0 * NS + i] : 0.0f;
         wave_lds_sync();
@@ -230,21 +179,13 @@ __global__ void __launch_bounds__(256, 2) k_det_mfma(int K, int B, int T, double
             if (XS != nullptr) for (int i = lane; i < lim; i += 64) XS[xs_model + ((size_t)t * B + b0) * NS + i] = ST[i];
             step_forward(t);
             f32x4 oa[OUT_CB], ob[OUT_CB];
-#pragma unroll
-            for (int cb = 0; cb < OUT_CB; ++cb) { oa[cb] = *(const f32x4*)&IMG[L::O_BD2 + 16 * cb + 4 * q]; ob[cb] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-            for (int kk = 0; kk < 16; kk += 2)
-#pragma unroll
-                for (int cb = 0; cb < OUT_CB; ++cb) {
-                    oa[cb] = MFMA16(wd2[kk][cb], h1[kk >> 2][kk & 3], oa[cb]);
-                    ob[cb] = MFMA16(wd2[kk + 1][cb], h1[(kk + 1) >> 2][(kk + 1) & 3], ob[cb]);
-                }
+            head.layer2(oa, ob, IMG + L::O_BD2, h1);
 #pragma unroll
             for (int cb = 0; cb < OUT_CB; ++cb)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int dim = 16 * cb + 4 * q + r;
-                    if (dim < NS) NX[c * NS + dim] = fmaf(dstd[cb][r], oa[cb][r] + ob[cb][r], dmean[cb][r]) + ST[c * NS + dim];      // training.py:257
+                    if (dim < NS) NX[c * NS + dim] = out.apply(cb, r, oa[cb][r] + ob[cb][r], ST[c * NS + dim]);
                 }
             wave_lds_sync();
             if (q == 0) {                                        // one lane per env: cost, dones, weight

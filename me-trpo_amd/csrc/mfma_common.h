@@ -1,4 +1,5 @@
-// Shared definitions of the MFMA rollout kernels (rollout_mfma.hip: head-per-wave; rollout_coop.hip: cooperative heads).
+// Shared definitions of the MFMA rollout kernels (rollout_mfma.hip: head-per-wave; rollout_coop.hip: cooperative heads); dyn_head_mfma.h has
+// the dynamics head they and bptt_mfma.hip share.
 #pragma once
 #include "device_common.h"
 
@@ -51,7 +52,7 @@ constexpr int al4(int a) { return (a + 3) & ~3; }
 template <int ENV, int DH, int PH>
 struct Cfg {
     static constexpr int NS = EnvDim<ENV>::NS, NA = EnvDim<ENV>::NA, NDROP = EnvDim<ENV>::NDROP;
-    static constexpr int NIN = NS + NA - NDROP;
+    static constexpr int NIN = NS + NA - NDROP, DYN_H = DH;
     static constexpr int NIN_KS = cdiv(NIN, 4), NS_KS = cdiv(NS, 4);
     static constexpr int DH_CB = cdiv(DH, 16), PH_CB = cdiv(PH, 16), OUT_CB = cdiv(NS, 16);
     static constexpr int NSP = 16 * OUT_CB;                        // padded state row in the exchange buffer

@@ -2,13 +2,11 @@
 // env_helpers.py:216-222, over VecSimpleEnv.step's arithmetic, :597-603.  T chained metrpo_step calls in meaning: no policy, no reset, no path-length
 // limit, no draw; stepping continues behind a done.
 //
-// Fused kernel (k_rollout_actions): the dynamics half of rollout_mfma.hip with the policy taken out and the action read from memory instead.
-//   * one workgroup = one tile of 16 envs, walked through all T steps.  Every layer is computed TRANSPOSED on v_mfma_f32_16x16x4_f32 with the fragment
-//     conventions of mfma_common.h; the D fragment of a layer is the B operand of the next, activations never leave registers between layers.
+// Fused kernel (k_rollout_actions): rollout_mfma.hip's dynamics step without the policy, the action read from memory instead.
+//   * one workgroup = one tile of 16 envs, walked through all T steps, on the shared head of dyn_head_mfma.h (layout and arithmetic are described there).
 //   * the head's weight fragments are register-resident for the whole loop (swimmer 92, Ant 132 registers), biases, normalisers' source map and the
 //     tile's state live in LDS; the state is [env][ns], the layout of one row of d_obs, so a row is one linear coalesced store.
-//   * arithmetic of the existing fused kernels: (x - mean) * (1 / std) in, out * diff_std + diff_mean + s out; cost and is_done are device_common.h's
-//     env_cost / env_is_done on the LDS rows (the functions metrpo_step's kernel calls).
+//   * cost and is_done are device_common.h's env_cost / env_is_done on the LDS rows (the functions metrpo_step's kernel calls).
 //   * the ONLY global load of the step loop is the tile's action block of the NEXT step (16 * na contiguous floats of d_actions, <= 2 per lane), issued
 //     at the top of a step and read behind that step's matrix instructions into the other of two LDS action buffers -- IN FRONT of the step's stores.
 //     The vector-memory counter is in order, so the wait for a load is also a wait for every older store (rollout_coop_kernel.h, DRAWS): placed
@@ -22,7 +20,7 @@
 //   * edge tile (B % 16 != 0): rows >= B are zero state and zero action in LDS, never read from or written to memory.
 //
 // Step loop (everything the fused kernel does not hold): launch_step on row t of d_actions, writing row t + 1 of d_obs.  No gather, no action copy.
-#include "mfma_common.h"
+#include "dyn_head_mfma.h"
 
 struct RactK {
     int B, T;
@@ -37,7 +35,7 @@ template <int ENV> constexpr int ract_wave_floats() { return Cfg<ENV, 64, 32>::W
 template <int ENV, bool ONE>
 __global__ void __launch_bounds__(ONE ? 64 : 512) k_rollout_actions(RactK r, int K, const float* __restrict__ dynp, const float* __restrict__ norm) {
     using C = Cfg<ENV, 64, 32>;
-    constexpr int NS = C::NS, NA = C::NA, NSP = C::NSP, DH = 64;
+    constexpr int NS = C::NS, NA = C::NA, NSP = C::NSP;
     constexpr int W_ACT2 = C::W_BP0, W_SZ = ract_wave_floats<ENV>();   // per-wave LDS (floats): ST | NX | ACT | dynamics biases | second ACT
     constexpr int NLD = cdiv(16 * NA, 64), NST = cdiv(16 * NS, 64);
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -54,48 +52,14 @@ __global__ void __launch_bounds__(ONE ? 64 : 512) k_rollout_actions(RactK r, int
 
     // ---------------- one-time: weight fragments -> registers, biases -> LDS ----------------------
     const float* __restrict__ pk = dynp + (size_t)(ONE ? r.head : wave) * C::PD;
-    float wd0[C::NIN_KS][C::DH_CB], wd1[C::DH_CB * 4][C::DH_CB], wd2[C::DH_CB * 4][C::OUT_CB];
-#pragma unroll
-    for (int s = 0; s < C::NIN_KS; ++s)
-#pragma unroll
-        for (int cb = 0; cb < C::DH_CB; ++cb) {
-            const int i = 4 * s + q, o = 16 * cb + e;
-            wd0[s][cb] = (i < C::NIN) ? pk[C::dW0 + i * DH + o] : 0.0f;
-        }
-#pragma unroll
-    for (int kk = 0; kk < C::DH_CB * 4; ++kk) {
-        const int i = 16 * (kk >> 2) + 4 * q + (kk & 3);
-#pragma unroll
-        for (int cb = 0; cb < C::DH_CB; ++cb) wd1[kk][cb] = pk[C::dW1 + i * DH + 16 * cb + e];
-#pragma unroll
-        for (int cb = 0; cb < C::OUT_CB; ++cb) {
-            const int o = 16 * cb + e;
-            wd2[kk][cb] = (o < NS) ? pk[C::dW2 + i * NS + o] : 0.0f;
-        }
-    }
+    DynHeadFrags<C> head;
+    head.load(pk, e, q);
     for (int i = lane; i < C::BD; i += 64) { W[C::W_BD0 + i] = pk[C::db0 + i]; W[C::W_BD1 + i] = pk[C::db1 + i]; }
     for (int i = lane; i < NSP; i += 64) W[C::W_BD2 + i] = (i < NS) ? pk[C::db2 + i] : 0.0f;
-    float nmean[C::NIN_KS], nstd[C::NIN_KS];
-    int nsrc[C::NIN_KS];                                   // >= 0: state feature, < 0: -(action dim + 1), -1000000: padding
-#pragma unroll
-    for (int s = 0; s < C::NIN_KS; ++s) {
-        const int i = 4 * s + q;
-        int f = 0;
-        if (i < NS - C::NDROP) { f = i + C::NDROP; nsrc[s] = f; }
-        else if (i < C::NIN) { f = NS + (i - (NS - C::NDROP)); nsrc[s] = -(i - (NS - C::NDROP)) - 1; }
-        else { nsrc[s] = -1000000; }
-        nmean[s] = (i < C::NIN) ? norm[f] : 0.0f;
-        nstd[s] = (i < C::NIN) ? 1.0f / norm[(NS + NA) + f] : 1.0f;   // reciprocal: (x - mean) * (1/std), as the fused rollout kernels
-    }
-    f32x4 dmean[C::OUT_CB], dstd[C::OUT_CB];
-#pragma unroll
-    for (int cb = 0; cb < C::OUT_CB; ++cb)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-            const int dim = 16 * cb + 4 * q + rr;
-            dmean[cb][rr] = (dim < NS) ? norm[2 * (NS + NA) + dim] : 0.0f;
-            dstd[cb][rr] = (dim < NS) ? norm[2 * (NS + NA) + NS + dim] : 0.0f;
-        }
+    DynInNorm<C> in;
+    DynOutNorm<C> out;
+    in.load(norm, q);
+    out.load(norm, q);
 
     // ---------------- the tile's initial state and the actions of step 0 ---------------------------
 #pragma unroll
@@ -135,42 +99,13 @@ __global__ void __launch_bounds__(ONE ? 64 : 512) k_rollout_actions(RactK r, int
             for (int j = 0; j < NLD; ++j) a_nx[j] = an[min(lane + 64 * j, nrows * NA - 1)];
         }
         // ---- the head: normalise, drop columns, 3 layers (training.py:218-269) ----------------------
-        f32x4 h0[C::DH_CB], h1[C::DH_CB];
+        f32x4 h0[C::DH_CB], h1[C::DH_CB], oa[C::OUT_CB], ob[C::OUT_CB];
+        float xin[C::NIN_KS];
 #pragma unroll
-        for (int cb = 0; cb < C::DH_CB; ++cb) h0[cb] = *(const f32x4*)&W[C::W_BD0 + 16 * cb + 4 * q];
-#pragma unroll
-        for (int s = 0; s < C::NIN_KS; ++s) {
-            float x = 0.0f;
-            if (nsrc[s] >= 0) x = ST[e * NS + nsrc[s]];
-            else if (nsrc[s] > -1000000) x = ACT[e * NA + (-nsrc[s] - 1)];
-            x = (nsrc[s] > -1000000) ? (x - nmean[s]) * nstd[s] : 0.0f;      // (xgu - in_mean)/in_std, training.py:228
-#pragma unroll
-            for (int cb = 0; cb < C::DH_CB; ++cb) h0[cb] = MFMA16(wd0[s][cb], x, h0[cb]);
-        }
-#pragma unroll
-        for (int cb = 0; cb < C::DH_CB; ++cb) {
-            h1[cb] = *(const f32x4*)&W[C::W_BD1 + 16 * cb + 4 * q];
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) h0[cb][rr] = relu1(h0[cb][rr]);
-        }
-#pragma unroll
-        for (int kk = 0; kk < C::DH_CB * 4; ++kk)
-#pragma unroll
-            for (int cb = 0; cb < C::DH_CB; ++cb) h1[cb] = MFMA16(wd1[kk][cb], h0[kk >> 2][kk & 3], h1[cb]);
-#pragma unroll
-        for (int cb = 0; cb < C::DH_CB; ++cb)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) h1[cb][rr] = relu1(h1[cb][rr]);
-        f32x4 oa[C::OUT_CB], ob[C::OUT_CB];
-#pragma unroll
-        for (int cb = 0; cb < C::OUT_CB; ++cb) { oa[cb] = *(const f32x4*)&W[C::W_BD2 + 16 * cb + 4 * q]; ob[cb] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-        for (int kk = 0; kk < C::DH_CB * 4; kk += 2)                          // two accumulators per block: half the dependent chain
-#pragma unroll
-            for (int cb = 0; cb < C::OUT_CB; ++cb) {
-                oa[cb] = MFMA16(wd2[kk][cb], h1[kk >> 2][kk & 3], oa[cb]);
-                ob[cb] = MFMA16(wd2[kk + 1][cb], h1[(kk + 1) >> 2][(kk + 1) & 3], ob[cb]);
-            }
+        for (int s = 0; s < C::NIN_KS; ++s) xin[s] = in.get(ST, NS, ACT, e, s);
+        head.layer0(h0, W + C::W_BD0, xin, ReluBits());
+        head.layer1(h1, W + C::W_BD1, h0, ReluBits());
+        head.layer2(oa, ob, W + C::W_BD2, h1);
         f32x4 nx[C::OUT_CB];
 #pragma unroll
         for (int cb = 0; cb < C::OUT_CB; ++cb) {
@@ -179,7 +114,7 @@ __global__ void __launch_bounds__(ONE ? 64 : 512) k_rollout_actions(RactK r, int
             for (int rr = 0; rr < 4; ++rr) {
                 const int dim = 16 * cb + 4 * q + rr;
                 const float sv = (dim < NS) ? ST[e * NS + dim] : 0.0f;
-                o[rr] = fmaf(dstd[cb][rr], o[rr], dmean[cb][rr]) + sv;          // diff_mean + diff_std*out + s, training.py:257
+                o[rr] = out.apply(cb, rr, o[rr], sv);
             }
             nx[cb] = o;
         }

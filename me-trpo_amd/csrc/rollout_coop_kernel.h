@@ -14,7 +14,7 @@
 // (their own col-block and wave 0's) and wave 1 the next step's Philox draws; launches with up to 1.55 tiles per CU run ONE workgroup
 // per CU with the tile-steps dealt out evenly and tiles migrating between workgroups (see the kernel and launch_rollout_coop);
 // this file is compiled with -amdgpu-mfma-vgpr-form (Makefile) so that MFMA results stay in the vector half of the register file.
-#include "mfma_common.h"
+#include "dyn_head_mfma.h"
 
 // Developer instrumentation (tools/build_variant.sh timing -DCOOP_TIMING=0xFFF): per-phase shader-clock sums of the four waves of
 // workgroup 0, read back with metrpo_debug_coop_phases (tools/coop_phases.py).  Not part of the shipped library.
@@ -101,7 +101,7 @@ __global__ void __launch_bounds__(256, ONE ? 1 : 2) k_rollout_coop(RolloutK r, c
 #pragma unroll
         for (int s = 0; s < C::NIN_KS; ++s) { const int i = 4 * s + q; wd0[k][s] = (i < C::NIN) ? pk[C::dW0 + i * DH + 16 * wave + e] : 0.0f; }
 #pragma unroll
-        for (int kk = 0; kk < 16; ++kk) { const int i = 16 * (kk >> 2) + 4 * q + (kk & 3); wd1[k][kk] = pk[C::dW1 + i * DH + 16 * wave + e]; }
+        for (int kk = 0; kk < 16; ++kk) { const int i = chained_in(kk, q); wd1[k][kk] = pk[C::dW1 + i * DH + 16 * wave + e]; }
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr)
 #pragma unroll
@@ -131,36 +131,19 @@ __global__ void __launch_bounds__(256, ONE ? 1 : 2) k_rollout_coop(RolloutK r, c
     for (int i = tid; i < L::NPF * 64; i += 256) {
         const int f = i >> 6, ln = i & 63, ee = ln & 15, qq = ln >> 4;
         float w = 0.0f;
-        if (f < L::P0KS * 2) { const int j = f >> 1, cb = f & 1, in = 16 * (j >> 2) + 4 * qq + (j & 3); w = (in < NS) ? theta[C::pW0 + in * PH + 16 * cb + ee] : 0.0f; }
-        else if (f < L::P0KS * 2 + 16) { const int g = f - L::P0KS * 2, kk = g >> 1, cb = g & 1, in = 16 * (kk >> 2) + 4 * qq + (kk & 3); w = theta[C::pW1 + in * PH + 16 * cb + ee]; }
-        else { const int kk = f - L::P0KS * 2 - 16, in = 16 * (kk >> 2) + 4 * qq + (kk & 3); w = (ee < NA) ? theta[C::pW2 + in * NA + ee] : 0.0f; }
+        if (f < L::P0KS * 2) { const int j = f >> 1, cb = f & 1, in = chained_in(j, qq); w = (in < NS) ? theta[C::pW0 + in * PH + 16 * cb + ee] : 0.0f; }
+        else if (f < L::P0KS * 2 + 16) { const int g = f - L::P0KS * 2, kk = g >> 1, cb = g & 1, in = chained_in(kk, qq); w = theta[C::pW1 + in * PH + 16 * cb + ee]; }
+        else { const int kk = f - L::P0KS * 2 - 16, in = chained_in(kk, qq); w = (ee < NA) ? theta[C::pW2 + in * NA + ee] : 0.0f; }
         PW[i] = w;
     }
     const float* pw0 = PW + lane, *pw1 = PW + L::P0KS * 2 * 64 + lane, *pw2 = PW + (L::P0KS * 2 + 16) * 64 + lane;
     float sig[4];
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) sig[rr] = (4 * q + rr < NA) ? expf(fmaxf(theta[C::pLS + 4 * q + rr], LOG_MIN_STD)) : 0.0f;
-    float nmean[C::NIN_KS], nstd[C::NIN_KS];
-    int nsrc[C::NIN_KS];
-#pragma unroll
-    for (int s = 0; s < C::NIN_KS; ++s) {
-        const int i = 4 * s + q;
-        int f = 0;
-        if (i < NS - C::NDROP) { f = i + C::NDROP; nsrc[s] = f; }
-        else if (i < C::NIN) { f = NS + (i - (NS - C::NDROP)); nsrc[s] = -(i - (NS - C::NDROP)) - 1; }
-        else { nsrc[s] = -1000000; }
-        nmean[s] = (i < C::NIN) ? norm[f] : 0.0f;
-        nstd[s] = (i < C::NIN) ? 1.0f / norm[(NS + NA) + f] : 1.0f;   // reciprocal: (x - mean) * (1/std), <= 1 ulp from the division
-    }
-    f32x4 dmean[OUT_CB], dstd[OUT_CB];
-#pragma unroll
-    for (int cb = 0; cb < OUT_CB; ++cb)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-            const int dim = 16 * cb + 4 * q + rr;
-            dmean[cb][rr] = (dim < NS) ? norm[2 * (NS + NA) + dim] : 0.0f;
-            dstd[cb][rr] = (dim < NS) ? norm[2 * (NS + NA) + NS + dim] : 0.0f;
-        }
+    DynInNorm<C> in;
+    DynOutNorm<C> out;
+    in.load(norm, q);
+    out.load(norm, q);
     // Per-step draws (Philox block 0 of RNG_STEP: action noise dims 0,1 | step model | reset row/model) are produced ONE STEP AHEAD.
     auto step_draws = [&](int tt, uint4& ds, float (&zz)[4]) {
         ds = rng_draw(r.seed, genv, tt, RNG_STEP, 0);
@@ -274,7 +257,7 @@ __global__ void __launch_bounds__(256, ONE ? 1 : 2) k_rollout_coop(RolloutK r, c
             for (int j = 0; j < XH; ++j) { const int hx = XH * (wave - 1) + j; hx0[j] = *(const f32x4*)&BD0[(hx < K ? hx : 0) * 64 + 4 * q]; }
 #pragma unroll
             for (int s = 0; s < KS_STATE; ++s) {
-                const float x = (ST[e * NSP + nsrc[s]] - nmean[s]) * nstd[s];             // training.py:228
+                const float x = in.get_state(ST, NSP, e, s);
 #pragma unroll
                 for (int k = 0; k < K; ++k) { if (COOP_SKIP & 32) h0[k][0] += x; else h0[k] = MFMA16(wd0[k][s], x, h0[k]); }
 #pragma unroll
@@ -377,12 +360,7 @@ __global__ void __launch_bounds__(256, ONE ? 1 : 2) k_rollout_coop(RolloutK r, c
         if (wave != 0) {
             float xin[C::NIN_KS];
 #pragma unroll
-            for (int s = KS_STATE; s < C::NIN_KS; ++s) {
-                float x = 0.0f;
-                if (nsrc[s] >= 0) x = ST[e * NSP + nsrc[s]];
-                else if (nsrc[s] > -1000000) x = ACT[e * NA + (-nsrc[s] - 1)];
-                xin[s] = (nsrc[s] > -1000000) ? (x - nmean[s]) * nstd[s] : 0.0f;          // training.py:228
-            }
+            for (int s = KS_STATE; s < C::NIN_KS; ++s) xin[s] = in.get(ST, NSP, ACT, e, s);
 #pragma unroll
             for (int s = KS_STATE; s < C::NIN_KS; ++s) {
 #pragma unroll
@@ -501,7 +479,7 @@ __global__ void __launch_bounds__(256, ONE ? 1 : 2) k_rollout_coop(RolloutK r, c
                 const float* pp = PART + (size_t)k * 4 * 16 * NSP + off;
                 f32x4 o = *(const f32x4*)&BD2[k * NSP + 16 * cb + 4 * q];
                 o += (*(const f32x4*)&pp[0] + *(const f32x4*)&pp[16 * NSP]) + (*(const f32x4*)&pp[2 * 16 * NSP] + *(const f32x4*)&pp[3 * 16 * NSP]);
-                return dstd[cb] * o + dmean[cb] + sv;                     // training.py:257
+                return out.apply(cb, o, sv);
             };
             if (simple) nx[cb] = head(sel);
             else {

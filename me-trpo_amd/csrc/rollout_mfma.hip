@@ -6,18 +6,13 @@
 //   * one workgroup = one tile of 16 imagined envs; wave w of the workgroup owns dynamics head w
 //     (K <= 8 waves).  Every wave also evaluates the (tiny) policy redundantly, so the only
 //     cross-wave traffic is the K head outputs, exchanged through LDS with ONE barrier per step.
-//   * every layer is computed TRANSPOSED on the f32 matrix core, H^T[unit][env] = W^T . X^T, with
-//     v_mfma_f32_16x16x4_f32: A = weights (lane l holds W[in = 4s + (l>>4)][out = 16cb + (l&15)]),
-//     B = activations (lane l holds x[in = 4s + (l>>4)] of env l&15).  The D fragment of layer n
-//     (lane l: units 16cb + 4(l>>4) + r, env l&15) IS the B operand of layer n+1 when that layer's
-//     k-steps are enumerated as (cb, r) and its weight fragment is permuted to match -- activations
-//     never leave registers between layers.  f32 MFMA is an exact fmaf chain (guide section 3), so the
-//     numerics are plain fp32.
+//   * every layer, dynamics and policy, is computed TRANSPOSED on v_mfma_f32_16x16x4_f32 in the fragment layout of dyn_head_mfma.h (the dynamics head
+//     is that header's; the policy chain follows the same conventions): activations never leave registers between layers, numerics are plain fp32.
 //   * all weights of the wave's head + the policy are register-resident for the whole rollout
 //     (~120 VGPRs); biases live in LDS and enter as the MFMA C operand.
 //   * state of the tile is kept per wave in LDS in [env][ns] order == the global layout of one
 //     time step of the trajectory, so the obs store is a fully coalesced linear copy.
-#include "mfma_common.h"
+#include "dyn_head_mfma.h"
 #include <cstdlib>
 
 template <int ENV, int DH, int PH>
@@ -38,28 +33,8 @@ __global__ void __launch_bounds__(512) k_rollout_mfma(RolloutK r, int K, const f
 
     // ---------------- one-time: weight fragments -> registers, biases -> LDS ----------------------
     const float* __restrict__ pk = dynp + (size_t)wave * C::PD;
-    float wd0[C::NIN_KS][C::DH_CB], wd1[C::DH_CB * 4][C::DH_CB], wd2[C::DH_CB * 4][C::OUT_CB];
-#pragma unroll
-    for (int s = 0; s < C::NIN_KS; ++s)
-#pragma unroll
-        for (int cb = 0; cb < C::DH_CB; ++cb) {
-            const int i = 4 * s + q, o = 16 * cb + e;
-            wd0[s][cb] = (i < C::NIN && o < DH) ? pk[C::dW0 + i * DH + o] : 0.0f;
-        }
-#pragma unroll
-    for (int kk = 0; kk < C::DH_CB * 4; ++kk) {
-        const int i = 16 * (kk >> 2) + 4 * q + (kk & 3);
-#pragma unroll
-        for (int cb = 0; cb < C::DH_CB; ++cb) {
-            const int o = 16 * cb + e;
-            wd1[kk][cb] = (i < DH && o < DH) ? pk[C::dW1 + i * DH + o] : 0.0f;
-        }
-#pragma unroll
-        for (int cb = 0; cb < C::OUT_CB; ++cb) {
-            const int o = 16 * cb + e;
-            wd2[kk][cb] = (i < DH && o < NS) ? pk[C::dW2 + i * NS + o] : 0.0f;
-        }
-    }
+    DynHeadFrags<C> head;
+    head.load(pk, e, q);
     float wp0[C::NS_KS][C::PH_CB], wp1[C::PH_CB * 4][C::PH_CB], wp2[C::PH_CB * 4];
 #pragma unroll
     for (int s = 0; s < C::NS_KS; ++s)
@@ -70,7 +45,7 @@ __global__ void __launch_bounds__(512) k_rollout_mfma(RolloutK r, int K, const f
         }
 #pragma unroll
     for (int kk = 0; kk < C::PH_CB * 4; ++kk) {
-        const int i = 16 * (kk >> 2) + 4 * q + (kk & 3);
+        const int i = chained_in(kk, q);
 #pragma unroll
         for (int cb = 0; cb < C::PH_CB; ++cb) {
             const int o = 16 * cb + e;
@@ -88,31 +63,14 @@ __global__ void __launch_bounds__(512) k_rollout_mfma(RolloutK r, int K, const f
         W[C::W_BP1 + i] = (i < PH) ? theta[C::pb1 + i] : 0.0f;
     }
     if (lane < 16) W[C::W_BP2 + lane] = (lane < NA) ? theta[C::pb2 + lane] : 0.0f;
-    // per-lane constants: policy sigma for its 4 action dims, input normalisers for its k-step features
+    // per-lane constants: policy sigma for its 4 action dims, the normalisers of its k-step features and output dims
     float sig[4];
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) sig[rr] = (4 * q + rr < NA) ? expf(fmaxf(theta[C::pLS + 4 * q + rr], LOG_MIN_STD)) : 0.0f;
-    float nmean[C::NIN_KS], nstd[C::NIN_KS];
-    int nsrc[C::NIN_KS];                                   // >= 0: state feature, < 0: -(action dim + 1), INT_MIN: padding
-#pragma unroll
-    for (int s = 0; s < C::NIN_KS; ++s) {
-        const int i = 4 * s + q;
-        int f = 0;
-        if (i < NS - C::NDROP) { f = i + C::NDROP; nsrc[s] = f; }
-        else if (i < C::NIN) { f = NS + (i - (NS - C::NDROP)); nsrc[s] = -(i - (NS - C::NDROP)) - 1; }
-        else { nsrc[s] = -1000000; }
-        nmean[s] = (i < C::NIN) ? norm[f] : 0.0f;
-        nstd[s] = (i < C::NIN) ? 1.0f / norm[(NS + NA) + f] : 1.0f;   // reciprocal: (x - mean) * (1/std), <= 1 ulp from the division
-    }
-    f32x4 dmean[C::OUT_CB], dstd[C::OUT_CB];
-#pragma unroll
-    for (int cb = 0; cb < C::OUT_CB; ++cb)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-            const int dim = 16 * cb + 4 * q + rr;
-            dmean[cb][rr] = (dim < NS) ? norm[2 * (NS + NA) + dim] : 0.0f;
-            dstd[cb][rr] = (dim < NS) ? norm[2 * (NS + NA) + NS + dim] : 0.0f;
-        }
+    DynInNorm<C> in;
+    DynOutNorm<C> out;
+    in.load(norm, q);
+    out.load(norm, q);
 
     // ---------------- vec_env.reset(): initial state + cur_model_idx (env_helpers.py:585-595) ------
     const bool resume = r.init_obs != nullptr;
@@ -201,42 +159,13 @@ __global__ void __launch_bounds__(512) k_rollout_mfma(RolloutK r, int K, const f
         su2 = xor_sum(su2);
         wave_lds_sync();
         // ---- dynamics head `wave`: normalise, drop columns, 3 layers (training.py:218-269) ----------
-        f32x4 h0[C::DH_CB], h1[C::DH_CB];
+        f32x4 h0[C::DH_CB], h1[C::DH_CB], oa[C::OUT_CB], ob[C::OUT_CB];
+        float xin[C::NIN_KS];
 #pragma unroll
-        for (int cb = 0; cb < C::DH_CB; ++cb) h0[cb] = *(const f32x4*)&W[C::W_BD0 + 16 * cb + 4 * q];
-#pragma unroll
-        for (int s = 0; s < C::NIN_KS; ++s) {
-            float x = 0.0f;
-            if (nsrc[s] >= 0) x = ST[e * NS + nsrc[s]];
-            else if (nsrc[s] > -1000000) x = ACT[e * NA + (-nsrc[s] - 1)];
-            x = (nsrc[s] > -1000000) ? (x - nmean[s]) * nstd[s] : 0.0f;      // (xgu - in_mean)/in_std, training.py:228
-#pragma unroll
-            for (int cb = 0; cb < C::DH_CB; ++cb) h0[cb] = MFMA16(wd0[s][cb], x, h0[cb]);
-        }
-#pragma unroll
-        for (int cb = 0; cb < C::DH_CB; ++cb) {
-            h1[cb] = *(const f32x4*)&W[C::W_BD1 + 16 * cb + 4 * q];
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) h0[cb][rr] = fmaxf(h0[cb][rr], 0.0f);
-        }
-#pragma unroll
-        for (int kk = 0; kk < C::DH_CB * 4; ++kk)
-#pragma unroll
-            for (int cb = 0; cb < C::DH_CB; ++cb) h1[cb] = MFMA16(wd1[kk][cb], h0[kk >> 2][kk & 3], h1[cb]);
-#pragma unroll
-        for (int cb = 0; cb < C::DH_CB; ++cb)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) h1[cb][rr] = fmaxf(h1[cb][rr], 0.0f);
-        f32x4 oa[C::OUT_CB], ob[C::OUT_CB];
-#pragma unroll
-        for (int cb = 0; cb < C::OUT_CB; ++cb) { oa[cb] = *(const f32x4*)&W[C::W_BD2 + 16 * cb + 4 * q]; ob[cb] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-        for (int kk = 0; kk < C::DH_CB * 4; kk += 2)
-#pragma unroll
-            for (int cb = 0; cb < C::OUT_CB; ++cb) {
-                oa[cb] = MFMA16(wd2[kk][cb], h1[kk >> 2][kk & 3], oa[cb]);
-                ob[cb] = MFMA16(wd2[kk + 1][cb], h1[(kk + 1) >> 2][(kk + 1) & 3], ob[cb]);
-            }
+        for (int s = 0; s < C::NIN_KS; ++s) xin[s] = in.get(ST, NS, ACT, e, s);
+        head.layer0(h0, W + C::W_BD0, xin, ReluFmax());
+        head.layer1(h1, W + C::W_BD1, h0, ReluFmax());
+        head.layer2(oa, ob, W + C::W_BD2, h1);
         const int par = t & 1;
         float* nxt_w = NXT + ((size_t)(par * K + wave) * 16 + e) * NSP;
 #pragma unroll
@@ -246,7 +175,7 @@ __global__ void __launch_bounds__(512) k_rollout_mfma(RolloutK r, int K, const f
             for (int rr = 0; rr < 4; ++rr) {
                 const int dim = 16 * cb + 4 * q + rr;
                 sv[rr] = (dim < NS) ? ST[e * NS + dim] : 0.0f;
-                o[rr] = fmaf(dstd[cb][rr], o[rr], dmean[cb][rr]) + sv[rr];      // diff_mean + diff_std*out + s, training.py:257
+                o[rr] = out.apply(cb, rr, o[rr], sv[rr]);
             }
             *(f32x4*)&nxt_w[16 * cb + 4 * q] = o;
         }
@@ -361,9 +290,10 @@ __global__ void __launch_bounds__(512) k_rollout_mfma(RolloutK r, int K, const f
 
 // -------------------------------------------------------------------------------------------------
 typedef void (*mfma_kernel_t)(RolloutK, int, const float*, const float*, const float*);
-struct MfmaEntry { int env, dh, ph; mfma_kernel_t kern; int w_total, nsp; };
+struct MfmaEntry { int env, dh, ph; mfma_kernel_t kern; int w_total, nsp, ns, na, n_drop; };
 
-#define ENTRY(ENVID, DH, PH) {ENVID, DH, PH, k_rollout_mfma<ENVID, DH, PH>, Cfg<ENVID, DH, PH>::W_TOTAL, Cfg<ENVID, DH, PH>::NSP}
+#define ENTRY(ENVID, DH, PH) {ENVID, DH, PH, k_rollout_mfma<ENVID, DH, PH>, Cfg<ENVID, DH, PH>::W_TOTAL, Cfg<ENVID, DH, PH>::NSP, \
+                              EnvDim<ENVID>::NS, EnvDim<ENVID>::NA, EnvDim<ENVID>::NDROP}
 static const MfmaEntry kTable[] = {
     ENTRY(METRPO_ENV_SWIMMER, 64, 32),
     ENTRY(METRPO_ENV_HALF_CHEETAH, 64, 32),
@@ -384,15 +314,7 @@ int mfma_shape_config(const metrpo_ctx* c) {
         const MfmaEntry& en = kTable[i];
         if (en.env != pd.env || en.dh != pd.dyn.dims[1] || en.ph != pd.pol.dims[1]) continue;
         // the template's env dims must be the ctx dims (custom ns/na/n_drop -> generic path)
-        bool ok = false;
-        switch (pd.env) {
-        case METRPO_ENV_SWIMMER: ok = pd.ns == 10 && pd.na == 2 && pd.n_drop == 2; break;
-        case METRPO_ENV_HALF_CHEETAH: ok = pd.ns == 18 && pd.na == 6 && pd.n_drop == 1; break;
-        case METRPO_ENV_HOPPER: ok = pd.ns == 11 && pd.na == 3 && pd.n_drop == 0; break;
-        case METRPO_ENV_SNAKE: ok = pd.ns == 14 && pd.na == 4 && pd.n_drop == 2; break;
-        case METRPO_ENV_ANT: ok = pd.ns == 29 && pd.na == 8 && pd.n_drop == 2; break;
-        }
-        if (ok) return i;
+        if (pd.ns == en.ns && pd.na == en.na && pd.n_drop == en.n_drop) return i;
     }
     return -1;
 }
