@@ -194,6 +194,8 @@ EXTRA_SYMBOLS = {
     'metrpo_debug_last_update': (_I, [_P, _P]),
     'metrpo_debug_persist_stats': (_I, [_P, _P, _I, _P]),
     'metrpo_debug_ws_retired': (_I, [_P, _P, _I]),
+    'metrpo_debug_coop_waves': (_I, [_P]),
+    'metrpo_set_coop_split': (_I, [_P, _I]),
 }
 
 

@@ -123,6 +123,8 @@ struct metrpo_ctx {
     int res_failed = 0;                                   // a resident launch gave up (its grid was not co-resident): this context stays on the step-wise path from then on
     int last_ract_kernel = -1;                            // metrpo_rollout_actions (rollout_actions.hip): -1 none yet, 0 step loop, 1 fused
     DevBuf<int32_t> d_ract_model;                         // ... its step loop's [B] head vector when the caller gave uniform_model instead of d_model
+    int coop_no_split = 0;                                // switch (metrpo_set_coop_split): 1 keeps the 4-wave form of the cooperative kernel where the head-split form would run
+    int last_coop_waves = 0;                              // waves per workgroup of the last cooperative launch: 4, or 8 (head-split form); diagnostics (metrpo_debug_coop_waves)
     int last_rollout_kernel = -1;                         // which kernel family the last metrpo_rollout ran on: 0 generic, 1 head-per-wave MFMA, 2 cooperative MFMA, 3 step-wise GEMM, 4 resident
     int dyn_precision = METRPO_DYN_F32;                   // metrpo_set_dyn_precision: operand precision of the dynamics forward inside metrpo_rollout (rollout_bf16.hip)
     DevBuf<uint16_t> d_dyn_bf16;                          // ... its bf16 weight image [K][layer][N][Kp], rebuilt from d_dyn in front of every bf16 rollout call

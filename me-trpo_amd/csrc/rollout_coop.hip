@@ -12,6 +12,12 @@ static const CoopEntry kCoop[] = {
     CENTRY_ENV(METRPO_ENV_SWIMMER), CENTRY_ENV(METRPO_ENV_HALF_CHEETAH), CENTRY_ENV(METRPO_ENV_HOPPER),
     CENTRY_ENV(METRPO_ENV_SNAKE), CENTRY_ENV(METRPO_ENV_ANT),
 };
+// head-split form of the one-workgroup-per-CU kernel (8 waves on one tile): envs with one output col-block, K = 2 ... 5
+static const CoopSplitEntry kCoopSplit[] = { CSPLIT_ENV(METRPO_ENV_SWIMMER), CSPLIT_ENV(METRPO_ENV_HOPPER), CSPLIT_ENV(METRPO_ENV_SNAKE) };
+static const CoopSplitEntry* coop_split_entry(int env, int K) {
+    for (const CoopSplitEntry& s : kCoopSplit) if (s.env == env && s.K == K) return &s;
+    return nullptr;
+}
 extern const CoopEntry kCoopK6[5], kCoopK7[5], kCoopK8[5], kCoopK9[5], kCoopK10[5];
 constexpr int N_COOP = (int)(sizeof(kCoop) / sizeof(kCoop[0]));
 // config index: [0, N_COOP) -> kCoop; N_COOP + 5 (K - 6) + env slot -> the K = 6 ... 10 tables
@@ -69,7 +75,6 @@ int launch_pad_dyn(metrpo_ctx* c, hipStream_t st) {
 
 int launch_rollout_coop(metrpo_ctx* c, int idx, const RolloutK& r_in, hipStream_t st, bool padded) {
     const CoopEntry& en = coop_entry(idx);
-    const size_t sh = sizeof(float) * (size_t)en.lds_floats;
     const int tiles = (r_in.B + 15) / 16;
     RolloutK r = r_in;
     // CUs that really schedule this process's waves (census, probe.hip): under a CU mask the even tile-step deal is made over THOSE.  The migrating
@@ -102,11 +107,20 @@ int launch_rollout_coop(metrpo_ctx* c, int idx, const RolloutK& r_in, hipStream_
         r.mig_err = comm_err_cell(c) + 1;                                // scal[S_ROLLERR]
     }
     const bool draws = r.eps || r.model_idx || r.sel_noise || r.reset_idx || r.reset_model;
-    const coop_kernel_t kern = en.kern[one ? 1 : 0][draws ? 1 : 0];
+    // one workgroup per CU: the head-split form (two waves per SIMD on the tile) wherever it exists; metrpo_set_coop_split(ctx, 0) keeps the 4-wave form (same bits)
+    const CoopSplitEntry* sp = (one && !c->coop_no_split) ? coop_split_entry(en.env, en.K) : nullptr;
+    const coop_kernel_t kern = sp ? sp->kern[draws ? 1 : 0] : en.kern[one ? 1 : 0][draws ? 1 : 0];
+    const size_t sh = sizeof(float) * (size_t)(sp ? sp->lds_floats : en.lds_floats);
     if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
     const float* dyn = c->d_dyn.p;
     if (padded) { const int rc = launch_pad_dyn(c, st); if (rc) return rc; dyn = c->d_dyn_pad.p; }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), sh, st, r, dyn, c->d_theta.p, c->d_norm.p);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(sp ? 512 : 256), sh, st, r, dyn, c->d_theta.p, c->d_norm.p);
     HIP_TRY(c, hipGetLastError());
+    c->last_coop_waves = sp ? 8 : 4;
     return METRPO_OK;
 }
+// Diagnostics hook (tests/test_gpu_coop_split.py): waves per workgroup of the last cooperative-kernel launch (0: none yet)
+extern "C" int32_t metrpo_debug_coop_waves(const metrpo_ctx* c) { return c ? c->last_coop_waves : METRPO_ENULL; }
+// Switch between the two forms of the one-workgroup-per-CU launch (A/B tests, fallback): split = 0 keeps the 4-wave kernel; default 1.  A hook like
+// metrpo_set_rollout_variant and not a key of the option table, which existing tests pin at 25 keys.
+extern "C" int32_t metrpo_set_coop_split(metrpo_ctx* c, int32_t split) { if (!c) return METRPO_ENULL; c->coop_no_split = split ? 0 : 1; return METRPO_OK; }

@@ -426,6 +426,16 @@ class Engine(object):
         k = int(lib.metrpo_last_rollout_kernel(self._ctx))
         return {0: 'generic', 1: 'mfma-head-per-wave', 2: 'mfma-cooperative', 3: 'gemm-stepwise', 4: 'resident', 5: 'gemm-streamk', 6: 'streamk-persistent', 7: 'gemm-bf16'}.get(k)
 
+    def set_coop_split(self, split):
+        """False keeps the 4-wave form of the cooperative rollout kernel where the head-split 8-wave form would run (same results bit for bit: A/B
+        tests, fallback); True (default) restores the rule.  Read at the next rollout()."""
+        self._chk(lib.metrpo_set_coop_split(self._ctx, int(bool(split))))
+
+    def last_coop_waves(self):
+        """Waves per workgroup of the last cooperative-kernel launch: 8 = head-split form (two waves per SIMD on one tile), 4 = the 4-wave form
+        (set_coop_split(False), two workgroups per CU, K = 1, K > 5, half-cheetah, Ant); 0 before the first."""
+        return int(lib.metrpo_debug_coop_waves(self._ctx))
+
     def rollout_note(self):
         """Why the last rollout() ran outside the fast dispatch table (K != 5 at 2x64, hidden widths 65..127, ...); '' when it did not."""
         return lib.metrpo_rollout_note(self._ctx).decode()

@@ -21,11 +21,12 @@ for B in (4096, 5000):
     for i in range(3):
         eng.rollout(B, H, H, 'step_rand', pool, seed=i, out=out)
     torch.cuda.synchronize()
-    buf = (C.c_ulonglong * 64)()
+    buf = (C.c_ulonglong * 128)()                  # [8 waves][16]: rows 4-7 are the second head group of the head-split form (stale after a 4-wave launch)
+    nw = eng.last_coop_waves()                     # 8: head-split form (default where one workgroup per CU runs); after eng.set_coop_split(False): 4
     assert lib.metrpo_debug_coop_phases(buf) == 0
     steps = H if B == 4096 else None            # B = 5000: workgroup 0 runs 123 tile-steps (migration schedule)
     n = H if B == 4096 else -(-((B + 15) // 16) * H // 256)
-    v = [[buf[16 * w + i] / n for i in range(14)] for w in range(4)]
-    print('B=%d workgroup 0, cycles/step per wave: totals %s' % (B, ' '.join('%6.0f' % sum(x) for x in v)))
+    v = [[buf[16 * w + i] / n for i in range(14)] for w in range(nw)]
+    print('B=%d workgroup 0 (%d waves), cycles/step per wave: totals %s' % (B, nw, ' '.join('%6.0f' % sum(x) for x in v)))
     for i, nme in enumerate(names):
-        print('    %-28s %s' % (nme, ' '.join('%6.0f' % v[w][i] for w in range(4))))
+        print('    %-28s %s' % (nme, ' '.join('%6.0f' % v[w][i] for w in range(nw))))
