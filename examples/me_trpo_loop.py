@@ -112,6 +112,13 @@ def main(argv=None):
         replay_l1 = np.abs(states.cpu().numpy() - O_rec).sum(axis=2).mean(axis=0)
         say("outer %d: the same under the recorded actions (open-loop replay, %s): %s" %
             (it, eng.last_rollout_actions_kernel(), ', '.join('h=%d: %.3g' % (h, replay_l1[h]) for h in errors['timesteps'])))
+        # ---- the 'svg' branch's gradient on the same recorded rollouts (svg_utils.py:27-66 on collect_data's rollout_data, :797-805): the value
+        #      gradient of the current policy ALONG the real trajectories through head 0 -- every Jacobian of every recorded step in one call.
+        #      Printed as a diagnostic; SVG(...).svg_update / early_stop.optimize_policy(svg, ..., init_pool=rollout_data) would train on it.
+        if env != 'ant':
+            svg_g = M.SVG(eng, learning_rate=1e-3).svg_gradient(M.rollout_triplets(Os, As))
+            say("outer %d: svg gradient along the recorded rollouts (%s path): |g_theta| = %.3g, |g_state| = %.3g" %
+                (it, eng.last_svg_path(), float(svg_g['theta'].norm()), float(svg_g['state'].norm())))
         t2 = time.time()
         # ---- optimize_policy (:1082-1301): TRPO on the imagined env, early stopping on the per-model validation costs
         res = early_stop.optimize_policy(algo, validation_init, T, 1.0, mode='estimated', log_every=5, num_iters_threshold=10,

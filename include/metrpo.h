@@ -656,6 +656,48 @@ typedef struct {
 int32_t metrpo_rollout_actions(metrpo_ctx* ctx, const metrpo_rollout_actions_args* args, void* stream);
 int32_t metrpo_last_rollout_actions_kernel(const metrpo_ctx* ctx);   /* -1 none yet, 0 step loop, 1 fused */
 
+/* ---- 'svg' policy update: value gradients along RECORDED rollouts (svg_utils.py:12-66; wired at model_based_rl.py:381-389, :654-660 and the 'svg'
+ * branch of optimize_policy, :1204-1205).  Additions to ABI 4: no struct above changes, no option key is added, METRPO_ABI_VERSION stays.
+ * metrpo_svg_grad replaces svg_gradient (svg_utils.py:12-53) and the three gradient callables it is given (:81-121): for each rollout, a list of
+ * (s_t, a_t, s_t+1) triplets of which s_t+1 is never read, with lambda = 0 and t = L-1 ... 0
+ *   c_s, c_a = d cost_tf(None, a_t, s_t) / d (s_t, a_t)      the "current state cost" of svg_utils.py:123-125: the cost's x_next IS s_t
+ *   Pi_t     = d policy_model(s_t) / d s_t   [na x ns]        the raw mean net (training.py:96-117), stochastic = 0, NO clip
+ *   F_t      = d dynamics_model([s_t, a_t]) / d [s_t, a_t]    head `model` (the reference: 'model0', model_based_rl.py:382); normalisers, column
+ *              [ns x (ns + na)]                               drop and residual included; a_t fed as recorded
+ *   q_t      = c_a + gamma lambda F_t[:, ns:]
+ *   g_theta  = q_t (d mean / d theta)(s_t) + gamma g_theta    so g_theta_final = sum_t gamma^t q_t J_theta(s_t)
+ *   lambda   = c_s + q_t Pi_t + gamma lambda F_t[:, :ns]
+ * d_grad = avg_grads['theta'] = the mean over the n rollouts of g_theta, d_state_grad = avg_grads['state'] = the mean of lambda_0 (:44-53).
+ * F_t and Pi_t are formed in float32 fmaf chains for all n T samples at once (path 1: one thread per (sample, output row), any widths and
+ * activations; path 2: tile GEMMs with the output row as the batch axis -- relu hidden layers of >= 16 units, two weight layers or more, ns <= 64;
+ * path 0 takes 2 where it applies), lambda and q are carried in float64 by one wave per rollout in a fixed summation order: repeated calls are
+ * bit-identical.  chunk bounds the Jacobian stage's workspace; 0: 65 536 samples (path 1), or as many as keep the transposed chain's two buffers,
+ * 2 ns chunk max_width floats, within 2^26 floats (path 2; a multiple of 64, at least 64).
+ * Rows at or behind a rollout's length are never read into a result, whatever they hold (NaN included).  Ant: its cost_tf takes a fourth argument
+ * (com_ant_env.py:70), the reference's cost_tf(None, a_in, s_in) raises for it: METRPO_EUNSUPPORTED, metrpo_last_error says so.
+ * Needs metrpo_set_dynamics and metrpo_set_policy only.  Stream-ordered, neither synchronises nor frees; workspace is ctx-owned.  metrpo_svg_grad
+ * leaves theta, both Adam states, the Philox state, the ensemble, metrpo_last_rollout_kernel and metrpo_rollout_note untouched.
+ * METRPO_EINVAL: n < 1, T < 1, model outside [0, K), path outside 0 ... 2, chunk < 0, n T ns (ns + na) >= 2^31; METRPO_ENULL: d_obs, d_act or d_grad. */
+typedef struct {
+    const float*   d_obs;        /* [n][T][ns]  recorded s_t, trajectory-major                                        */
+    const float*   d_act;        /* [n][T][na]  recorded a_t                                                          */
+    const int32_t* d_len;        /* [n] steps of each rollout, clamped into [1, T] on the device; NULL: all T         */
+    int32_t n, T, model, path;   /* model: head (reference: 0).  path: 0 auto, 1 generic, 2 GEMM (tests, A/B)         */
+    int32_t chunk;               /* samples per Jacobian chunk; 0: the library's choice                               */
+    double  gamma;               /* reference never passes one: 1.0                                                   */
+    double* d_grad;              /* [P] avg_grads['theta'] in metrpo_get_policy's layout, log_std slots exactly 0     */
+    double* d_state_grad;        /* [ns] avg_grads['state'], optional                                                 */
+    float*  d_mean_adj;          /* [n][T][na] gamma^t q_t (rows at or behind len: 0), optional                       */
+    float*  d_dyn_jac;           /* [n][T][ns][ns+na] F_t, optional                                                   */
+    float*  d_pol_jac;           /* [n][T][na][ns] Pi_t, optional                                                     */
+} metrpo_svg_args;
+int32_t metrpo_svg_grad(metrpo_ctx* ctx, const metrpo_svg_args* args, void* stream);
+/* svg_update (svg_utils.py:56-66): metrpo_svg_grad, then theta_vars += float32(-lr) * float32(avg_grads['theta']) through assign_add on the W and b
+ * of the mean network (get_policy_parameters, svg_utils.py:7-10) of the ctx policy; log_std is never touched.  METRPO_ESTATE while a TRPO update is open. */
+int32_t metrpo_svg_update(metrpo_ctx* ctx, const metrpo_svg_args* args, double lr, void* stream);
+/* which Jacobian path the last metrpo_svg_grad / metrpo_svg_update of this ctx took (no reference counterpart: diagnostics) */
+int32_t metrpo_last_svg_path(const metrpo_ctx* ctx);                                           /* -1 none yet, 1 generic, 2 GEMM */
+
 #ifdef __cplusplus
 }
 #endif

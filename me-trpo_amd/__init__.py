@@ -19,6 +19,8 @@ from . import early_stop
 from . import dynamics_training
 from .bptt import BPTT
 from .lbfgs import LBFGS
+from . import svg
+from .svg import SVG, rollout_triplets, pack_rollouts
 from . import formats
 from . import tf_checkpoint
 from .params import from_params, shapes_from_params
@@ -27,4 +29,4 @@ from .model_error import evaluate_model_predictions, get_error_distribution, ope
 
 __all__ = ['Engine', 'Trajectory', 'xavier_policy_theta', 'Comm', 'NeuralNetEnv', 'VecSimpleEnv', 'InitStatePool',
            'Box', 'EnvSpec', 'GaussianMLPPolicy', 'LinearFeatureBaseline', 'VectorizedSampler', 'BaseSampler',
-           'DevicePaths', 'ConjugateGradientOptimizer', 'BatchPolopt', 'NPO', 'TRPO', 'VPG', 'PPO', 'FirstOrderOptimizer', 'AdamOptimizer', 'LBFGS', 'early_stop', 'dynamics_training', 'from_params', 'shapes_from_params', 'model_error', 'evaluate_model_predictions', 'get_error_distribution', 'open_loop_predictions']
+           'DevicePaths', 'ConjugateGradientOptimizer', 'BatchPolopt', 'NPO', 'TRPO', 'VPG', 'PPO', 'FirstOrderOptimizer', 'AdamOptimizer', 'LBFGS', 'svg', 'SVG', 'rollout_triplets', 'pack_rollouts', 'early_stop', 'dynamics_training', 'from_params', 'shapes_from_params', 'model_error', 'evaluate_model_predictions', 'get_error_distribution', 'open_loop_predictions']

@@ -97,6 +97,13 @@ class RolloutActionsArgs(C.Structure):
                 ('d_obs', C.c_void_p), ('d_rew', C.c_void_p), ('d_done', C.c_void_p)]
 
 
+class SvgArgs(C.Structure):
+    _fields_ = [('d_obs', C.c_void_p), ('d_act', C.c_void_p), ('d_len', C.c_void_p), ('n', C.c_int32), ('T', C.c_int32), ('model', C.c_int32),
+                ('path', C.c_int32), ('chunk', C.c_int32), ('gamma', C.c_double), ('d_grad', C.c_void_p), ('d_state_grad', C.c_void_p),
+                ('d_mean_adj', C.c_void_p), ('d_dyn_jac', C.c_void_p), ('d_pol_jac', C.c_void_p)]
+
+
+SVG_PATHS = {'auto': 0, 'generic': 1, 'gemm': 2}          # metrpo_svg_args.path
 MODEL_ERROR_MAX_HORIZONS = 32          # include/metrpo.h
 
 
@@ -152,6 +159,9 @@ SYMBOLS = {
     'metrpo_model_error': (_I, [_P, C.POINTER(ModelErrorArgs), _P]),
     'metrpo_rollout_actions': (_I, [_P, C.POINTER(RolloutActionsArgs), _P]),
     'metrpo_last_rollout_actions_kernel': (_I, [_P]),
+    'metrpo_svg_grad': (_I, [_P, C.POINTER(SvgArgs), _P]),
+    'metrpo_svg_update': (_I, [_P, C.POINTER(SvgArgs), _D, _P]),
+    'metrpo_last_svg_path': (_I, [_P]),
     'metrpo_dyn_train_reset': (_I, [_P, _P]),
     'metrpo_dyn_train_step': (_I, [_P, _P, _P, C.POINTER(TrainParams), _P, _P]),
     'metrpo_dyn_eval_losses': (_I, [_P, _P, _P, _L, _D, _P, _P]),

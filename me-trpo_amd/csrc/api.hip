@@ -1056,6 +1056,37 @@ extern "C" int32_t metrpo_rollout_actions(metrpo_ctx* c, const metrpo_rollout_ac
 }
 extern "C" int32_t metrpo_last_rollout_actions_kernel(const metrpo_ctx* c) { return c ? c->last_ract_kernel : METRPO_ENULL; }
 
+// ---- 'svg' policy update: value gradients along recorded rollouts (svg_utils.py:12-66; svg.hip) ----
+static int svg_check(metrpo_ctx* c, const metrpo_svg_args* a) {
+    if (!a) return set_err(c, METRPO_ENULL, "svg: args NULL");
+    NEED_DYN(c); NEED_POL(c);
+    if (c->pd.env == METRPO_ENV_ANT)
+        return set_err(c, METRPO_EUNSUPPORTED, "svg: Ant's cost_tf takes a fourth argument (com_ant_env.py:70); the reference's cost_tf(None, a_in, s_in) "
+                                               "(svg_utils.py:123-125) raises for it, so 'svg' is not defined on Ant");
+    if (a->n < 1 || a->T < 1) return set_err(c, METRPO_EINVAL, "svg: n and T must be at least 1");
+    if (a->model < 0 || a->model >= c->pd.K) return set_err(c, METRPO_EINVAL, "svg: model = " + std::to_string(a->model) + " is no head below K = " + std::to_string(c->pd.K));
+    if (a->path < 0 || a->path > 2) return set_err(c, METRPO_EINVAL, "svg: path must be 0 (auto), 1 (generic) or 2 (GEMM)");
+    if (a->chunk < 0) return set_err(c, METRPO_EINVAL, "svg: chunk must not be negative");
+    if ((long long)a->n * a->T > 2147483647LL / ((long long)c->pd.ns * (c->pd.ns + c->pd.na))) return set_err(c, METRPO_EINVAL, "svg: n * T * ns * (ns + na) must stay below 2^31");
+    if (!a->d_obs || !a->d_act || !a->d_grad) return set_err(c, METRPO_ENULL, "svg: d_obs, d_act and d_grad are required");
+    return METRPO_OK;
+}
+extern "C" int32_t metrpo_svg_grad(metrpo_ctx* c, const metrpo_svg_args* a, void* stream) {
+    TraceRange trace_("metrpo:svg_grad (svg_gradient)");
+    if (!c) return METRPO_ENULL;
+    if (const int rc = svg_check(c, a)) return rc;
+    return run_svg(c, a, 0.0, false, (hipStream_t)stream);
+}
+extern "C" int32_t metrpo_svg_update(metrpo_ctx* c, const metrpo_svg_args* a, double lr, void* stream) {
+    TraceRange trace_("metrpo:svg_update (svg_gradient + svg_update)");
+    if (!c) return METRPO_ENULL;
+    if (const int rc = svg_check(c, a)) return rc;
+    if (c->upd_pending) return set_err(c, METRPO_ESTATE, "svg_update: an update begun with metrpo_trpo_update_begin is still open (call metrpo_trpo_update_end)");
+    if (!std::isfinite(lr)) return set_err(c, METRPO_EINVAL, "svg_update: bad learning rate");
+    return run_svg(c, a, lr, true, (hipStream_t)stream);
+}
+extern "C" int32_t metrpo_last_svg_path(const metrpo_ctx* c) { return c ? c->last_svg_path : METRPO_ENULL; }
+
 extern "C" int32_t metrpo_subsample_batch(metrpo_ctx* c, const metrpo_batch* b, const int32_t* d_idx, int64_t m, double inv_n_global, metrpo_batch* out,
                                           double* d_valid_count, void* stream) {
     TraceRange trace_("metrpo:subsample_batch");

@@ -50,18 +50,6 @@ __device__ __forceinline__ float* mlp_col_store(const NetDesc& net, const float*
     return const_cast<float*>(cur);
 }
 
-// dout[j] = sum_i W[j][i] * din[i]   (W row-major n_in x n_out: the VJP of  out = in . W)
-__device__ __forceinline__ void dense_col_T(const float* __restrict__ W, int n_in, int n_out, const float* din, float* dout, int LD, int tid) {
-    for (int j = 0; j < n_in; ++j) {
-        const float* __restrict__ w = W + (size_t)j * n_out;
-        float s0 = 0.0f, s1 = 0.0f;
-        int i = 0;
-        for (; i + 1 < n_out; i += 2) { s0 = fmaf(w[i], din[i * LD + tid], s0); s1 = fmaf(w[i + 1], din[(i + 1) * LD + tid], s1); }
-        if (i < n_out) s0 = fmaf(w[i], din[i * LD + tid], s0);
-        dout[j * LD + tid] = s0 + s1;
-    }
-}
-
 // d(w * cost)/du -> gU (written), d(w * cost)/dx_next -> added into G
 __device__ __forceinline__ void cost_adjoint(int env, int ns, int na, const float* xn, const float* u, float w, float* gU, float* G, int LD, int tid) {
     float su2 = 0.0f;

@@ -212,6 +212,19 @@ __device__ __forceinline__ float* mlp_col(const NetDesc& net, const float* __res
     return const_cast<float*>(cur);
 }
 
+// dout[j] = sum_i W[j][i] * din[i]   (W row-major n_in x n_out: the VJP of  out = in . W); shared by the BPTT sweeps (bptt.hip) and the
+// Jacobian rows of svg.hip
+__device__ __forceinline__ void dense_col_T(const float* __restrict__ W, int n_in, int n_out, const float* din, float* dout, int LD, int tid) {
+    for (int j = 0; j < n_in; ++j) {
+        const float* __restrict__ w = W + (size_t)j * n_out;
+        float s0 = 0.0f, s1 = 0.0f;
+        int i = 0;
+        for (; i + 1 < n_out; i += 2) { s0 = fmaf(w[i], din[i * LD + tid], s0); s1 = fmaf(w[i + 1], din[(i + 1) * LD + tid], s1); }
+        if (i < n_out) s0 = fmaf(w[i], din[i * LD + tid], s0);
+        dout[j * LD + tid] = s0 + s1;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // analytic cost (reward = -cost) and termination; s_next/u accessed through column pointers
 //   envs/com_*_env.py cost_np_vec / is_done -- see include/metrpo.h metrpo_env for file:line

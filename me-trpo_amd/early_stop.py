@@ -66,11 +66,23 @@ def optimize_policy(algo, validation_init, T, gamma, mode='estimated', whole=Tru
                     logger=None, init_pool=None):
     """TRPO branch of model_based_rl.py:optimize_policy (a VPG object runs the same branch: optimize_policy_vpg); a BPTT object as `algo` runs its
     'bptt' / 'bptt-stochastic' branch instead, and an LBFGS object the 'l-bfgs' branch: that loop with log_every = 1 and max_iters = 1
-    (optimize_policy_bptt; `init_pool` is then its source of reset states).  `real_cost_fn()` stands in for
+    (optimize_policy_bptt; `init_pool` is then its source of reset states).  An SVG object runs the 'svg' branch (:1204-1206) through the same
+    loop (optimize_policy_svg; `init_pool` is then the recorded rollout_data): one svg_update on the same rollout_data per iteration, training
+    cost 0.0, validation every log_every iterations, keep-or-restore.  This DIVERGES from the reference as written, whose loop breaks after
+    the first validation round (:1280-1282) and restores the entry checkpoint (:1400), leaving the policy unchanged.  `real_cost_fn()` stands in for
     evaluate_fixed_init_trajectories on the real simulator (out of scope; None -> 0.0)."""
     from .bptt import BPTT
     from .algos import VPG, PPO
     from .lbfgs import LBFGS
+    from .svg import SVG
+    if isinstance(algo, SVG):
+        # 'svg' branch (:1204-1206).  DIVERGENCE from the reference as written: its loop breaks unconditionally after the first validation round
+        # (:1280-1282) and log_and_restore (:1400) then restores the checkpoint saved at entry (:1127-1129) -- the run leaves the policy unchanged.
+        # Here: the 'bptt' branch's loop, one svg_update on the same rollout_data per iteration, training cost 0.0, validation every log_every
+        # iterations, keep-or-restore.  `init_pool` carries rollout_data (collect_data's list of triplet lists) unless algo.rollout_data is set.
+        return optimize_policy_svg(algo, validation_init, T, gamma, init_pool, mode=mode, whole=whole, log_every=log_every,
+                                   num_iters_threshold=num_iters_threshold, max_iters=max_iters, stop_fn=stop_fn, real_cost_fn=real_cost_fn,
+                                   logger=logger)
     if isinstance(algo, LBFGS):
         # run_model_based_rl.py:114-117 (l_bfgs_exception, applied on every launch path): log_every = 1, max_iters = 1 -- one whole
         # minimisation, one validation round, one keep-or-restore decision of the 'bptt' branch's loop (which carries theta only)
@@ -177,6 +189,19 @@ def optimize_policy_vpg(vpg, validation_init, T, gamma, mode='estimated', whole=
     return dict(best_index=best_index, last_index=j, min_validation_costs=min_costs, history=history)
 
 
+def optimize_policy_svg(svg, validation_init, T, gamma, rollout_data=None, **loop_kwargs):
+    """'svg' branch of model_based_rl.py:optimize_policy (:1204-1206) on the 'bptt' branch's loop (optimize_policy_bptt: snapshot, iterate, validate
+    every log_every iterations, keep or restore theta).  Every iteration is one svg_update on the SAME rollout_data -- the reference feeds the one
+    rollout_data of the outer iteration to every policy iteration -- and its training cost is 0.0 (:1206).  The reference's own loop breaks after the
+    first validation round and restores the entry checkpoint (:1280-1282, :1400); that is not copied (see me-trpo_amd/svg.py)."""
+    if rollout_data is not None:
+        svg.rollout_data = rollout_data
+    if svg.rollout_data is None:
+        raise ValueError("the svg branch differentiates along recorded rollouts: pass rollout_data (collect_data's list of triplet lists, "
+                         "svg.rollout_triplets) as init_pool, or set SVG.rollout_data")
+    return optimize_policy_bptt(svg, validation_init, T, gamma, svg.rollout_data, **loop_kwargs)
+
+
 def optimize_policy_bptt(bptt, validation_init, T, gamma, init_pool, mode='estimated', whole=True, log_every=5, num_iters_threshold=25,
                          max_iters=400, stop_fn=None, real_cost_fn=None, logger=None):
     """'bptt' / 'bptt-stochastic' branches of model_based_rl.py:optimize_policy (:1181-1196, 1209-1215, 1286-1298): every iteration
@@ -184,7 +209,7 @@ def optimize_policy_bptt(bptt, validation_init, T, gamma, init_pool, mode='estim
     every 'bptt-stochastic' step sees the noise); every `log_every` iterations the K validation costs, deterministic as in the reference
     (which sets stochastic back to 0 first, :1211-1215); the stop rule and the snapshot / restore of the TRPO branch.  No reset_opt: the
     reference builds it for trpo / vpg only.  `mode` 'trpo_mean' has no TRPO sampler here and compares 0.0, as for the other branches."""
-    if init_pool is None or not (hasattr(init_pool, 'sample') or hasattr(init_pool, 'reset')):
+    if getattr(bptt, 'needs_init_pool', True) and (init_pool is None or not (hasattr(init_pool, 'sample') or hasattr(init_pool, 'reset'))):
         raise ValueError("the bptt branches draw their batch from init_pool: an InitStatePool or an env with reset() (from_params: "
                          "Setup.bptt_optimize_policy_kwargs carries it)")
     eng = bptt.engine

@@ -912,6 +912,53 @@ class Engine(object):
                                               float(clip_val) if clip_val else 0.0, self._stream()))
         self._keep_adam = g
 
+    # ------------------------------------------------------------------ 'svg' policy update (csrc/svg.hip; svg_utils.py:12-66)
+    def _svg_call(self, obs, act, lengths, model, gamma, path, chunk, jacobians, lr):
+        dev = self.device
+        obs = _f32(obs, dev); act = _f32(act, dev)
+        if obs.dim() != 3 or obs.shape[2] != self.ns:
+            raise ValueError("obs: expected [n, T, %d], got %s" % (self.ns, tuple(obs.shape)))
+        n, T = int(obs.shape[0]), int(obs.shape[1])
+        if tuple(act.shape) != (n, T, self.na):
+            raise ValueError("act: expected [%d, %d, %d], got %s" % (n, T, self.na, tuple(act.shape)))
+        lengths = _i32(lengths, dev, (n,))
+        a = _lib.SvgArgs()
+        a.d_obs, a.d_act, a.d_len = obs.data_ptr(), act.data_ptr(), (lengths.data_ptr() if lengths is not None else None)
+        a.n, a.T, a.model, a.chunk, a.gamma = n, T, int(model), int(chunk), float(gamma)
+        a.path = _lib.SVG_PATHS[path] if isinstance(path, str) else int(path)
+        out = dict(theta=torch.empty(self.P, dtype=torch.float64, device=dev), state=torch.empty(self.ns, dtype=torch.float64, device=dev))
+        a.d_grad, a.d_state_grad = out['theta'].data_ptr(), out['state'].data_ptr()
+        if jacobians:
+            out['mean_adj'] = torch.empty(n, T, self.na, dtype=torch.float32, device=dev)
+            out['dyn_jac'] = torch.empty(n, T, self.ns, self.ns + self.na, dtype=torch.float32, device=dev)
+            out['pol_jac'] = torch.empty(n, T, self.na, self.ns, dtype=torch.float32, device=dev)
+            a.d_mean_adj, a.d_dyn_jac, a.d_pol_jac = out['mean_adj'].data_ptr(), out['dyn_jac'].data_ptr(), out['pol_jac'].data_ptr()
+        if lr is None:
+            self._chk(lib.metrpo_svg_grad(self._ctx, C.byref(a), self._stream()))
+        else:
+            self._close_open_update()
+            self._chk(lib.metrpo_svg_update(self._ctx, C.byref(a), float(lr), self._stream()))
+        self._keep_svg = (obs, act, lengths)                                        # alive until the stream has consumed them
+        return out
+
+    def svg_grad(self, obs, act, lengths=None, model=0, gamma=1.0, path=0, chunk=0, jacobians=False):
+        """metrpo_svg_grad: svg_gradient (svg_utils.py:12-53) on recorded rollouts -- obs [n, T, ns] = s_t, act [n, T, na] = a_t as recorded,
+        trajectory-major and padded to T; lengths [n] int (None: all T; rows at or behind a length are never read into a result).  model: the
+        dynamics head (the reference: 0).  path: 0 / 'auto', 1 / 'generic', 2 / 'gemm'; chunk: samples per Jacobian chunk (0: the library's choice).
+        -> dict(theta [P] float64 = avg_grads['theta'] in get_policy's layout with the log_std slots 0, state [ns] float64 = avg_grads['state']);
+        with jacobians also mean_adj [n, T, na] = gamma^t q_t, dyn_jac [n, T, ns, ns+na] = F_t, pol_jac [n, T, na, ns] = Pi_t (float32).
+        Device tensors, nothing synchronised."""
+        return self._svg_call(obs, act, lengths, model, gamma, path, chunk, jacobians, None)
+
+    def svg_update(self, obs, act, lr, lengths=None, model=0, gamma=1.0, path=0, chunk=0, jacobians=False):
+        """metrpo_svg_update: svg_grad, then svg_update's step (svg_utils.py:56-66) theta += float32(-lr) * float32(grad) on the W / b of the ctx
+        policy's mean network (log_std untouched).  -> svg_grad's dict (the gradient the step used)."""
+        return self._svg_call(obs, act, lengths, model, gamma, path, chunk, jacobians, lr)
+
+    def last_svg_path(self):
+        """Jacobian path of the last svg_grad() / svg_update() of this engine: 'generic', 'gemm'; None before the first."""
+        return {1: 'generic', 2: 'gemm'}.get(int(lib.metrpo_last_svg_path(self._ctx)))
+
 
 class _DevView(object):
     """Zero-copy view (float64 unless told otherwise) of library-owned device memory for torch (CUDA array interface)."""

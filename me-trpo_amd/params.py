@@ -137,7 +137,8 @@ def from_params(path_or_dict, device=0, init_states=None, comm=None, seed=0, n_e
     sh = shapes_from_params(p)
     if sh['algo'] not in ('trpo', 'vpg', 'ppo', 'bptt', 'bptt-stochastic'):
         raise ValueError("params 'algo' = %r: this path builds 'trpo', 'vpg', 'ppo' (and the 'bptt' / 'bptt-stochastic' updates of section 8f); svg / l-bfgs "
-                         "are not built from a params file (the 'l-bfgs' update runs as metrpo_amd.LBFGS)" % sh['algo'])
+                         "are not built from a params file (the 'l-bfgs' update runs as metrpo_amd.LBFGS, the 'svg' update as metrpo_amd.SVG on recorded rollouts)"
+                         % sh['algo'])
     blk = sh['vpg'] if sh['algo'] == 'vpg' else sh['ppo'] if sh['algo'] == 'ppo' else sh['trpo']     # init_std / reset of the rllab algorithm that runs (training.py:350-352, 368-370)
     eng = Engine(sh['env'], sh['K'], sh['dyn_hidden'], sh['pol_hidden'], n_drop=sh['n_drop'], dyn_act=sh['dyn_act'], device=device)
     if sh['dyn_ext']['rollout_precision'] != 'f32':
