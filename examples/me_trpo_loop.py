@@ -68,6 +68,8 @@ def main(argv=None):
     ap.add_argument('--policy-iters', type=int, default=20)
     ap.add_argument('--model-passes', type=int, default=30)
     ap.add_argument('--quiet', action='store_true')
+    ap.add_argument('--disagreement', action='store_true',
+                    help="after every policy optimisation, log where in one imagined batch the K heads stop agreeing (an extra obtain_samples per outer iteration)")
     args = ap.parse_args(argv)
     say = (lambda *a: None) if args.quiet else print
     np.random.seed(0)
@@ -124,6 +126,15 @@ def main(argv=None):
         res = early_stop.optimize_policy(algo, validation_init, T, 1.0, mode='estimated', log_every=5, num_iters_threshold=10,
                                          max_iters=args.policy_iters, reset_log_std=True)
         t3 = time.time()
+        if args.disagreement:
+            # ---- the only uncertainty signal an ensemble gives without new real data: the spread of the K heads' next states at every (s, a) the
+            #      optimised policy visits in imagination, by steps since the env's last reset -- a curve that rises where the policy leaves the model's support
+            algo.start_worker()
+            dis = M.ensemble_disagreement(eng, algo.obtain_samples(it))
+            curve = dis['by_path_step'].cpu().numpy()
+            say("outer %d: head disagreement ||std_k s'||_2 by steps since reset (%s): %s | whole batch mean %.3g, max %.3g" %
+                (it, eng.last_disagreement_kernel(), ', '.join('t=%d: %.3g' % (t, curve[t]) for t in sorted(set([0, len(curve) // 4, len(curve) // 2, len(curve) - 1]))),
+                 float(dis['score'].double().mean()), float(dis['sums'][:, 3].max())))
         history.append(dict(real_cost=real_cost, n_data=data['training_dynamics'].get_num_data(),
                             model_val=float(np.sum(info['min_validation_losses'])) if 'min_validation_losses' in info else float('nan'),
                             est_cost=float(np.mean(res['min_validation_costs']['estimated'])), best_index=res['best_index'],

@@ -698,6 +698,53 @@ int32_t metrpo_svg_update(metrpo_ctx* ctx, const metrpo_svg_args* args, double l
 /* which Jacobian path the last metrpo_svg_grad / metrpo_svg_update of this ctx took (no reference counterpart: diagnostics) */
 int32_t metrpo_last_svg_path(const metrpo_ctx* ctx);                                           /* -1 none yet, 1 generic, 2 GEMM */
 
+/* ---- disagreement of the ensemble's heads at SUPPLIED (s, a) rows: "where do the K models stop agreeing?" -- the quantity model_mean_std forms inside
+ * the step, np.std(next_possible_observations, axis=0) (env_helpers.py:625), returned instead of consumed, for N independent rows in one call (the N = T B
+ * rows of an imagined batch; no chain of dependent steps).  Additions to ABI 4: no struct above changes, no option key is added, METRPO_ABI_VERSION stays.
+ * Per row n and head k, s'_k is exactly what metrpo_step gives for head k on (d_obs[n], clip(d_actions[n])) (its d_next_all).  From the K next states:
+ *   mean[d]  = (s'_0[d] + s'_1[d] + ... + s'_K-1[d]) / K           the f32 sum in head order divided by K, as model_mean forms it (:621-622)
+ *   std[d]   = sqrt((sum_k (s'_k[d] - mean[d])^2) / K)             TWO-PASS: deviations from that mean, squares summed in head order by fmaf, divided by K
+ *                                                                  (np.std's ddof = 0), then the root; never E[x^2] - mean^2, which loses everything when
+ *                                                                  |s'| is large and the heads are close
+ *   score    = sqrt(sum_d std[d]^2)  = ||std||_2                   the sum over dims of the population variances (the values under the root above), then the root
+ *   maxdev   = max_k sqrt(sum_d (s'_k[d] - mean[d])^2)
+ *   rew_std  = the same two-pass population std over r_k = -cost_np_vec(s, clip(a), s'_k), one reward per head (:601 with every head's own next state)
+ * K = 1 gives exact zeros in std, score, maxdev and rew_std.
+ * d_valid[n] = 0 skips row n: zeros are written to every requested output of that row, the row is left out of d_sums, and whatever d_obs / d_actions hold
+ * there (NaN included) enters no result.  Rows at or behind N are neither read nor written.
+ * d_sums [G][4] float64, OVERWRITTEN: per group g (rows_per_group > 0: rows g * rows_per_group ... , G = ceil(N / rows_per_group) -- a time-major [T][B]
+ * batch flattened with rows_per_group = B gives one group per rollout step; 0: one group of all rows): valid rows, sum score, sum score^2, max score (0 for
+ * a group without a valid row).  A second small launch forms them from d_score / d_valid, one fixed-shape workgroup per group adding in a fixed order: a
+ * function of the inputs alone, repeated calls are bit-identical; no workgroup waits on another.  d_score may be NULL (a ctx workspace then carries it).
+ * Which kernel runs (metrpo_last_disagreement_kernel: -1 none yet, 0 generic, 1 fused):
+ *   fused (disagreement.hip: one launch over all rows, a wave per head with its weights in registers, striding over 16-row tiles) -- the shape class of
+ *     metrpo_rollout_actions' fused kernel: swimmer, half-cheetah, Ant, hopper, snake at their own dims with two relu hidden layers of 64, narrower
+ *     ones through the zero-padded copy, K <= 8, force_generic = 0.  s'_k carries the bits of that kernel's step.
+ *   generic (metrpo_step's kernel once with its d_next_all, then a reduction kernel) -- everything else: humanoid, hidden widths above 64, other depths /
+ *     activations, K > 8.  d_next_all is bit for bit metrpo_step's.
+ * The two agree to rounding, not bits (as the two paths of metrpo_rollout_actions).
+ * Stream-ordered, neither frees nor synchronises; workspaces are ctx-owned.  Needs metrpo_set_dynamics only; reads the ensemble and the normalisers and
+ * writes nothing else in the context: theta, both Adam states, the Philox state, metrpo_last_rollout_kernel, metrpo_rollout_note and
+ * metrpo_last_rollout_actions_kernel are untouched.  N == 0: METRPO_OK, nothing written.  METRPO_ENULL: ctx, args, d_obs, d_actions; METRPO_EINVAL: N < 0,
+ * N >= 2^31, rows_per_group < 0; METRPO_ESTATE before metrpo_set_dynamics. */
+typedef struct {
+    int64_t N;                    /* rows */
+    int32_t rows_per_group;       /* > 0: row n belongs to group n / rows_per_group (time-major [T][B] flattened, rows_per_group = B: group = step); 0: one group */
+    int32_t force_generic;        /* test / A-B hook, as force_step_loop of metrpo_rollout_actions */
+    const float*   d_obs;         /* [N][ns] */
+    const float*   d_actions;     /* [N][na] UNCLIPPED, clipped inside as metrpo_step does (env_helpers.py:599); never written */
+    const uint8_t* d_valid;       /* optional [N]; 0 = row skipped: zeros written, left out of d_sums */
+    float* d_score;               /* [N]      ||std over heads of s'||_2  (sqrt of the sum over dims of the population variance, np.std's ddof = 0, :625) */
+    float* d_maxdev;              /* optional [N]      max_k ||s'_k - mean||_2 */
+    float* d_std;                 /* optional [N][ns]  np.std(next_possible_observations, axis=0) */
+    float* d_mean;                /* optional [N][ns]  the model_mean next state */
+    float* d_next_all;            /* optional [K][N][ns], metrpo_step's layout */
+    float* d_rew_std;             /* optional [N]      population std over heads of r_k = -cost_np_vec(s, clip(a), s'_k) */
+    double* d_sums;               /* optional [G][4] float64, OVERWRITTEN: valid rows, sum score, sum score^2, max score; G = ceil(N / rows_per_group) or 1 */
+} metrpo_disagreement_args;
+int32_t metrpo_ensemble_disagreement(metrpo_ctx* ctx, const metrpo_disagreement_args* args, void* stream);
+int32_t metrpo_last_disagreement_kernel(const metrpo_ctx* ctx);   /* -1 none yet, 0 generic, 1 fused */
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,12 @@ class SvgArgs(C.Structure):
                 ('d_mean_adj', C.c_void_p), ('d_dyn_jac', C.c_void_p), ('d_pol_jac', C.c_void_p)]
 
 
+class DisagreementArgs(C.Structure):
+    _fields_ = [('N', C.c_int64), ('rows_per_group', C.c_int32), ('force_generic', C.c_int32), ('d_obs', C.c_void_p), ('d_actions', C.c_void_p),
+                ('d_valid', C.c_void_p), ('d_score', C.c_void_p), ('d_maxdev', C.c_void_p), ('d_std', C.c_void_p), ('d_mean', C.c_void_p),
+                ('d_next_all', C.c_void_p), ('d_rew_std', C.c_void_p), ('d_sums', C.c_void_p)]
+
+
 SVG_PATHS = {'auto': 0, 'generic': 1, 'gemm': 2}          # metrpo_svg_args.path
 MODEL_ERROR_MAX_HORIZONS = 32          # include/metrpo.h
 
@@ -162,6 +168,8 @@ SYMBOLS = {
     'metrpo_svg_grad': (_I, [_P, C.POINTER(SvgArgs), _P]),
     'metrpo_svg_update': (_I, [_P, C.POINTER(SvgArgs), _D, _P]),
     'metrpo_last_svg_path': (_I, [_P]),
+    'metrpo_ensemble_disagreement': (_I, [_P, C.POINTER(DisagreementArgs), _P]),
+    'metrpo_last_disagreement_kernel': (_I, [_P]),
     'metrpo_dyn_train_reset': (_I, [_P, _P]),
     'metrpo_dyn_train_step': (_I, [_P, _P, _P, C.POINTER(TrainParams), _P, _P]),
     'metrpo_dyn_eval_losses': (_I, [_P, _P, _P, _L, _D, _P, _P]),

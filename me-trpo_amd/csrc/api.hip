@@ -1056,6 +1056,20 @@ extern "C" int32_t metrpo_rollout_actions(metrpo_ctx* c, const metrpo_rollout_ac
 }
 extern "C" int32_t metrpo_last_rollout_actions_kernel(const metrpo_ctx* c) { return c ? c->last_ract_kernel : METRPO_ENULL; }
 
+// ---- disagreement of the heads at supplied (s, a) rows (env_helpers.py:625 returned instead of consumed; disagreement.hip) ----
+extern "C" int32_t metrpo_ensemble_disagreement(metrpo_ctx* c, const metrpo_disagreement_args* a, void* stream) {
+    TraceRange trace_("metrpo:ensemble_disagreement (std over the heads at supplied rows)");
+    if (!c) return METRPO_ENULL;
+    if (!a) return set_err(c, METRPO_ENULL, "ensemble_disagreement: args NULL");
+    NEED_DYN(c);
+    if (a->N < 0 || a->N > 2147483647LL) return set_err(c, METRPO_EINVAL, "ensemble_disagreement: N must be in 0 ... 2^31 - 1");
+    if (a->rows_per_group < 0) return set_err(c, METRPO_EINVAL, "ensemble_disagreement: rows_per_group must not be negative");
+    if (a->N == 0) return METRPO_OK;
+    if (!a->d_obs || !a->d_actions) return set_err(c, METRPO_ENULL, "ensemble_disagreement: d_obs and d_actions are required");
+    return run_disagreement(c, a, (hipStream_t)stream);
+}
+extern "C" int32_t metrpo_last_disagreement_kernel(const metrpo_ctx* c) { return c ? c->last_dis_kernel : METRPO_ENULL; }
+
 // ---- 'svg' policy update: value gradients along recorded rollouts (svg_utils.py:12-66; svg.hip) ----
 static int svg_check(metrpo_ctx* c, const metrpo_svg_args* a) {
     if (!a) return set_err(c, METRPO_ENULL, "svg: args NULL");

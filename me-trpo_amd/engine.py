@@ -346,6 +346,67 @@ class Engine(object):
         rollout_actions.hip), 'step-loop' (step()'s kernel once per step); None before the first."""
         return {0: 'step-loop', 1: 'fused'}.get(int(lib.metrpo_last_rollout_actions_kernel(self._ctx)))
 
+    # ------------------------------------------------------------------ disagreement of the heads at supplied rows
+    DISAGREEMENT_OUTPUTS = ('score', 'maxdev', 'std', 'mean', 'next_all', 'rew_std', 'sums')
+
+    def ensemble_disagreement(self, obs, actions, valid=None, rows_per_group=0, want=('score',), force_generic=False, out=None):
+        """metrpo_ensemble_disagreement: how far the K heads' next states lie apart at every supplied (s, a) row -- obs [N, ns] and actions [N, na]
+        (unclipped, clipped inside, never written), or time-major [T, B, .] (flattened; rows_per_group then defaults to B: one group per step).
+        valid [N] (nonzero = use the row; a skipped row reads 0 in every output and is left out of `sums`).  want: any of
+        score [N] (||std over the heads||_2), maxdev [N] (max_k ||s'_k - mean||_2), std [N, ns], mean [N, ns], next_all [K, N, ns], rew_std [N],
+        sums [G, 4] float64 (valid rows, sum score, sum score^2, max score per group of rows_per_group rows; 0: one group).
+        -> dict of device tensors (time-major inputs: the leading N is [T, B]), nothing synchronised.  out: dict name -> tensor to write into instead
+        (contiguous, at least that large)."""
+        dev = self.device
+        obs = _f32(obs, dev); actions = _f32(actions, dev)
+        lead = tuple(obs.shape[:-1])
+        if obs.dim() not in (2, 3) or obs.shape[-1] != self.ns:
+            raise ValueError("obs: expected [N, %d] or [T, B, %d], got %s" % (self.ns, self.ns, tuple(obs.shape)))
+        if tuple(actions.shape) != lead + (self.na,):
+            raise ValueError("actions: expected %s, got %s" % (lead + (self.na,), tuple(actions.shape)))
+        want = (want,) if isinstance(want, str) else tuple(want)
+        for w in want:
+            if w not in self.DISAGREEMENT_OUTPUTS:
+                raise ValueError("want: %r is none of %s" % (w, self.DISAGREEMENT_OUTPUTS))
+        rows_per_group = int(rows_per_group)
+        if rows_per_group < 0:
+            raise ValueError("rows_per_group must not be negative")
+        if obs.dim() == 3 and rows_per_group == 0:
+            rows_per_group = int(obs.shape[1])
+        N = 1
+        for n in lead:
+            N *= int(n)
+        if valid is not None:
+            valid = torch.as_tensor(valid, device=dev)
+            valid = (valid != 0).to(torch.uint8).contiguous()
+            if tuple(valid.shape) != lead:
+                raise ValueError("valid: expected %s, got %s" % (lead, tuple(valid.shape)))
+        G = (N + rows_per_group - 1) // rows_per_group if rows_per_group > 0 else 1
+        shapes = {'score': lead, 'maxdev': lead, 'std': lead + (self.ns,), 'mean': lead + (self.ns,), 'next_all': (self.K,) + lead + (self.ns,),
+                  'rew_std': lead, 'sums': (G, 4)}
+        res = {}
+        for w in want:
+            dt = torch.float64 if w == 'sums' else torch.float32
+            if out is not None and w in out:
+                t = out[w]
+                assert t.dtype == dt and t.is_contiguous() and t.device == dev and t.numel() >= int(np.prod(shapes[w], dtype=np.int64))
+            else:
+                t = torch.empty(shapes[w], dtype=dt, device=dev)
+            res[w] = t
+        a = _lib.DisagreementArgs()
+        a.N, a.rows_per_group, a.force_generic = N, rows_per_group, int(bool(force_generic))
+        a.d_obs, a.d_actions, a.d_valid = obs.data_ptr(), actions.data_ptr(), (valid.data_ptr() if valid is not None else None)
+        for w in self.DISAGREEMENT_OUTPUTS:
+            setattr(a, 'd_' + w, res[w].data_ptr() if w in res else None)
+        self._chk(lib.metrpo_ensemble_disagreement(self._ctx, C.byref(a), self._stream()))
+        self._dis_keep = (obs, actions, valid)                                     # alive until the stream has consumed them
+        return res
+
+    def last_disagreement_kernel(self):
+        """Path the last ensemble_disagreement() of this engine took: 'fused' (disagreement.hip: one launch over all rows), 'generic' (step()'s kernel
+        with want_all, then a reduction kernel); None before the first."""
+        return {0: 'generic', 1: 'fused'}.get(int(lib.metrpo_last_disagreement_kernel(self._ctx)))
+
     # ------------------------------------------------------------------ fused rollout
     def rollout(self, B, T, H, sam_mode, pool, determ=False, eval_all_heads=True, seed=0, stream_offset=0,
                 eps=None, model_idx=None, sel_noise=None, reset_idx=None, reset_model=None, out=None,

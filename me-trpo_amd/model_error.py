@@ -112,6 +112,31 @@ def open_loop_predictions(engine, initial_states, actions, model=-1):
     return obs.transpose(0, 1).contiguous(), (-rew).transpose(0, 1).contiguous(), done.transpose(0, 1).contiguous()
 
 
+def ensemble_disagreement(engine, traj, force_generic=False):
+    """Where in an imagined batch the K heads stop agreeing: metrpo_ensemble_disagreement on every visited (s, a) of a rollout.  traj: a Trajectory
+    (Engine.rollout) or a DevicePaths (VectorizedSampler.obtain_samples; its .traj); obs [T, B, ns] and act [T, B, na] are used, every row is a
+    visited pair, so there is no mask.  -> dict of device tensors (one synchronisation, for the length of by_path_step):
+      score [T, B]         ||std over the heads of s'||_2 per row (np.std(next_possible_observations, axis=0), env_helpers.py:625)
+      sums [T, 4]          float64 per rollout step, from the device: rows, sum score, sum score^2, max score
+      by_step [T]          float64 mean score per rollout step, sums[:, 1] / sums[:, 0]
+      by_path_step [L]     float64 mean score by steps since the env's last reset (traj.tpath; L = its largest value + 1; NaN where no row has that
+                           count) -- the curve that shows the policy walking out of the model's support.  Formed HERE, on the host side, with torch in
+                           float64 (index_add_ over tpath on the device), not by the library
+      path_step_count [L]  int64 rows per tpath value."""
+    tr = getattr(traj, 'traj', traj)
+    obs, act, tpath = tr.obs, tr.act, tr.tpath
+    if obs.dim() != 3 or act.dim() != 3 or tuple(tpath.shape) != tuple(obs.shape[:2]):
+        raise ValueError("traj: expected time-major obs [T, B, ns], act [T, B, na], tpath [T, B]; got %s, %s, %s"
+                         % (tuple(obs.shape), tuple(act.shape), tuple(tpath.shape)))
+    r = engine.ensemble_disagreement(obs, act, want=('score', 'sums'), force_generic=force_generic)
+    score, sums = r['score'], r['sums']
+    idx = tpath.reshape(-1).to(torch.int64)
+    L = int(idx.max().item()) + 1 if idx.numel() else 0                             # synchronises: the curve's length is data
+    tot = torch.zeros(L, dtype=torch.float64, device=score.device).index_add_(0, idx, score.reshape(-1).to(torch.float64))
+    cnt = torch.zeros(L, dtype=torch.int64, device=score.device).index_add_(0, idx, torch.ones_like(idx))
+    return dict(score=score, sums=sums, by_step=sums[:, 1] / sums[:, 0], by_path_step=tot / cnt.to(torch.float64), path_step_count=cnt)
+
+
 def _write_stats(stats, data):
     """write_stats (env_helpers.py:61-70) on a device tensor [N] or [N, ns]; percentiles by linear interpolation, as np.percentile."""
     q = torch.quantile(data.to(torch.float64), torch.tensor([1.0, 0.0, 0.75, 0.25, 0.5], dtype=torch.float64, device=data.device), dim=0)
