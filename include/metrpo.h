@@ -745,6 +745,49 @@ typedef struct {
 int32_t metrpo_ensemble_disagreement(metrpo_ctx* ctx, const metrpo_disagreement_args* args, void* stream);
 int32_t metrpo_last_disagreement_kernel(const metrpo_ctx* ctx);   /* -1 none yet, 0 generic, 1 fused */
 
+/* ---- the discounted return EVERY head predicts for each of B candidate action sequences: "which of these plans does the ensemble like?" -- the cost sum
+ * of build_policy_graph (model_based_rl.py:122-141: model i fixed for the whole trajectory, cost_i = sum_t gamma^t cost) under SUPPLIED actions instead of
+ * the policy's, per candidate instead of averaged, negated (reward = -cost, env_helpers.py:601).  Additions to ABI 4: no struct above changes, no option key
+ * is added, METRPO_ABI_VERSION stays.
+ * For every head k and candidate b, head k rolls ITS OWN trajectory: s_0 = d_init_obs[b / (B / S)], s_t+1 = head k's next state from (s_t, clip(a_t)) --
+ * exactly what metrpo_rollout_actions gives with eps_rand, uniform_model = k -- and r_t = -cost_np_vec(s_t, clip(a_t), s_t+1).  Per (k, b):
+ *   alive_0   = 1
+ *   ret       = sum_t gamma^t alive_t r_t                      carried in float64 in step order, gamma^t by repeated float64 multiplication, rounded
+ *                                                              to fp32 ONCE, at the store; a step that is not counted adds nothing
+ *   alive_t+1 = alive_t and not is_done(s_t+1, s_t+1)          stop_at_done = 1: the mask of model_based_rl.py:134-137, updated AFTER the step's cost,
+ *                                                              so the step that ends an Ant episode still counts; stop_at_done = 0: alive = 1 throughout
+ *                                                              (metrpo_rollout_actions' meaning: stepping continues behind a done)
+ *   len       = steps counted: index of the first done + 1, else T
+ *   ret_mean[b] = (ret_0 + ... + ret_K-1) / K                  from the stored fp32 values, summed in head order
+ *   ret_std[b]  = sqrt((sum_k (ret_k - ret_mean)^2) / K)       two-pass, squares summed in head order by fmaf: rew_std of metrpo_ensemble_disagreement
+ * K = 1 gives exact zeros in ret_std.
+ * Which kernel runs (metrpo_last_score_actions_kernel: -1 none yet, 0 generic, 1 fused):
+ *   fused (score_actions.hip: one launch, one wave per (16-candidate tile, head) for all T steps, weights in registers, no store inside the step loop) --
+ *     the shape class of metrpo_rollout_actions' fused kernel WITHOUT its K <= 8: swimmer, half-cheetah, Ant, hopper, snake at their own dims with two
+ *     relu hidden layers of 64, narrower ones through the zero-padded copy, force_generic = 0.  s' and r carry the bits of that kernel's one-head step.
+ *   generic (per head the step loop of metrpo_rollout_actions into a ctx workspace, chunked over candidates to stay within 2^26 floats, then a
+ *     reduction kernel) -- everything else: humanoid, hidden widths above 64, other depths / activations.
+ * The two agree to rounding, not bits.  d_ret_mean / d_ret_std come from a second small launch over d_ret on either path (fixed order, no workgroup
+ * waits on another): repeated calls are bit-identical.
+ * Stream-ordered, neither frees nor synchronises; workspaces are ctx-owned.  Needs metrpo_set_dynamics only.  Leaves theta, both Adam states, the Philox
+ * state, the ensemble, metrpo_last_rollout_kernel, metrpo_rollout_note, metrpo_last_rollout_actions_kernel and metrpo_last_disagreement_kernel untouched.
+ * B == 0 or T == 0: METRPO_OK, nothing written.  METRPO_ENULL: ctx, args, d_init_obs, d_actions, d_ret; METRPO_EINVAL: B < 0, T < 0, S < 1, B % S != 0,
+ * gamma not finite; METRPO_ESTATE before metrpo_set_dynamics. */
+typedef struct {
+    int32_t B, T, S;            /* B candidates, T steps; S start states, B % S == 0: candidate b starts from d_init_obs[b / (B / S)] */
+    int32_t stop_at_done;       /* 1: build_policy_graph's mask (model_based_rl.py:134-137); 0: every step counts (metrpo_rollout_actions' meaning) */
+    int32_t force_generic;      /* test / A-B hook, as metrpo_ensemble_disagreement's */
+    double  gamma;
+    const float* d_init_obs;    /* [S][ns] */
+    const float* d_actions;     /* [T][B][na] UNCLIPPED, clipped inside (env_helpers.py:599); never written */
+    float*   d_ret;             /* [K][B] required */
+    int32_t* d_len;             /* optional [K][B] */
+    float*   d_ret_mean;        /* optional [B] */
+    float*   d_ret_std;         /* optional [B] */
+} metrpo_score_actions_args;
+int32_t metrpo_score_actions(metrpo_ctx* ctx, const metrpo_score_actions_args* args, void* stream);
+int32_t metrpo_last_score_actions_kernel(const metrpo_ctx* ctx);   /* -1 none yet, 0 generic, 1 fused */
+
 #ifdef __cplusplus
 }
 #endif

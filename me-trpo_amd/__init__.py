@@ -26,7 +26,10 @@ from . import tf_checkpoint
 from .params import from_params, shapes_from_params
 from . import model_error
 from .model_error import evaluate_model_predictions, get_error_distribution, open_loop_predictions, ensemble_disagreement
+from . import planning
+from .planning import score_action_sequences, plan_random_shooting, plan_cem, ShootingController
 
 __all__ = ['Engine', 'Trajectory', 'xavier_policy_theta', 'Comm', 'NeuralNetEnv', 'VecSimpleEnv', 'InitStatePool',
            'Box', 'EnvSpec', 'GaussianMLPPolicy', 'LinearFeatureBaseline', 'VectorizedSampler', 'BaseSampler',
-           'DevicePaths', 'ConjugateGradientOptimizer', 'BatchPolopt', 'NPO', 'TRPO', 'VPG', 'PPO', 'FirstOrderOptimizer', 'AdamOptimizer', 'LBFGS', 'svg', 'SVG', 'rollout_triplets', 'pack_rollouts', 'early_stop', 'dynamics_training', 'from_params', 'shapes_from_params', 'model_error', 'evaluate_model_predictions', 'get_error_distribution', 'open_loop_predictions', 'ensemble_disagreement']
+           'DevicePaths', 'ConjugateGradientOptimizer', 'BatchPolopt', 'NPO', 'TRPO', 'VPG', 'PPO', 'FirstOrderOptimizer', 'AdamOptimizer', 'LBFGS', 'svg', 'SVG', 'rollout_triplets', 'pack_rollouts', 'early_stop', 'dynamics_training', 'from_params', 'shapes_from_params', 'model_error', 'evaluate_model_predictions', 'get_error_distribution', 'open_loop_predictions', 'ensemble_disagreement',
+           'planning', 'score_action_sequences', 'plan_random_shooting', 'plan_cem', 'ShootingController']

@@ -1070,6 +1070,21 @@ extern "C" int32_t metrpo_ensemble_disagreement(metrpo_ctx* c, const metrpo_disa
 }
 extern "C" int32_t metrpo_last_disagreement_kernel(const metrpo_ctx* c) { return c ? c->last_dis_kernel : METRPO_ENULL; }
 
+// ---- every head's discounted return of supplied action sequences (model_based_rl.py:122-141 under supplied actions; score_actions.hip) ----
+extern "C" int32_t metrpo_score_actions(metrpo_ctx* c, const metrpo_score_actions_args* a, void* stream) {
+    TraceRange trace_("metrpo:score_actions (per-head returns of candidate action sequences)");
+    if (!c) return METRPO_ENULL;
+    if (!a) return set_err(c, METRPO_ENULL, "score_actions: args NULL");
+    NEED_DYN(c);
+    if (a->B < 0 || a->T < 0) return set_err(c, METRPO_EINVAL, "score_actions: bad B/T");
+    if (a->S < 1 || a->B % a->S != 0) return set_err(c, METRPO_EINVAL, "score_actions: S = " + std::to_string(a->S) + " must be at least 1 and divide B = " + std::to_string(a->B));
+    if (!std::isfinite(a->gamma)) return set_err(c, METRPO_EINVAL, "score_actions: gamma is not finite");
+    if (a->B == 0 || a->T == 0) return METRPO_OK;
+    if (!a->d_init_obs || !a->d_actions || !a->d_ret) return set_err(c, METRPO_ENULL, "score_actions: required pointer is NULL");
+    return run_score_actions(c, a, (hipStream_t)stream);
+}
+extern "C" int32_t metrpo_last_score_actions_kernel(const metrpo_ctx* c) { return c ? c->last_sact_kernel : METRPO_ENULL; }
+
 // ---- 'svg' policy update: value gradients along recorded rollouts (svg_utils.py:12-66; svg.hip) ----
 static int svg_check(metrpo_ctx* c, const metrpo_svg_args* a) {
     if (!a) return set_err(c, METRPO_ENULL, "svg: args NULL");

@@ -1,0 +1,276 @@
+// metrpo_score_actions (include/metrpo.h): the discounted return every head of the ensemble predicts for each of B candidate action sequences -- per
+// (head k, candidate b) the loop of build_policy_graph's cost sum, model_based_rl.py:122-141 (head fixed for the whole trajectory, the done mask updated
+// AFTER the step's cost, :134-137), under SUPPLIED actions (clipped as VecSimpleEnv.step does, env_helpers.py:599) instead of the policy's.
+//
+// Fused kernel (k_score_actions): the ONE-head body of k_rollout_actions (rollout_actions.hip) without its stores.
+//   * one wave owns one (16-candidate tile, head) pair for all T steps, on the shared head of dyn_head_mfma.h: weight fragments register-resident
+//     (swimmer 92, Ant 132 registers), biases and the tile's state in the wave's LDS, every activation in registers, no barrier.  The statements of a
+//     step -- normalise, three layers, de-normalise, env_cost / env_is_done on the LDS rows -- are that kernel's, so s' and r carry its bits.
+//   * PACKING: one wave per workgroup on a (tiles, K) grid.  The (tile, head) pairs share nothing but read-only inputs, so a workgroup of several waves
+//     would buy no exchange and no reuse; it would only tie the waves' placement together (a workgroup starts when ALL its waves fit one CU, and its LDS
+//     and registers are held until the slowest tile of it ends).  One-wave workgroups let the dispatcher fill whatever SIMD has the registers free, which
+//     is what matters below 1024 waves (B = 512, K = 5: 160 waves on 1024 SIMDs).  blockIdx.x is the tile: neighbouring workgroups read the same head's
+//     weights (22 .. 26 KB, out of the cache) and neighbouring action blocks.
+//   * the ONLY global load of the step loop is the tile's action block of the NEXT step, issued at the top of a step and read behind that step's matrix
+//     instructions into the other of two LDS action buffers (k_rollout_actions).  There is NO global store inside the loop: every lane carries its env's
+//     float64 sum, float64 discount (repeated multiplication), alive flag and step count; quad 0 writes d_ret / d_len once behind the loop.
+//   * the tile's start rows are gathered per row (candidate b starts from d_init_obs[b / (B / S)]; a tile may straddle two start states).
+//   * edge tile (B % 16 != 0): rows >= B are zero state and zero action in LDS, never read from or written to memory.
+//
+// Generic path (every other shape, and force_generic): per head k the step loop of run_rollout_actions (eps_rand, uniform_model = k) into a ctx
+// workspace, chunked over candidates so that the workspace stays within 2^26 floats (svg.hip's rule), then k_sact_reduce, one thread per candidate,
+// applies the same float64 sum to the workspace's rew / done.
+//
+// d_ret_mean / d_ret_std: k_sact_aggregate, a second small launch over d_ret, one thread per candidate adding in head order; no workgroup waits on another.
+#include "dyn_head_mfma.h"
+#include <algorithm>
+#include <cmath>
+
+struct SactK {
+    int B, T, per;            // per = B / S: candidates per start state
+    int stop;                 // 1: a candidate stops counting behind its first done
+    double gamma;
+    const float* init_obs; const float* actions;
+    float* ret; int32_t* len;
+};
+
+// one step of the return: ret += gamma^t alive_t r_t in float64, then the discount, then the mask (model_based_rl.py:134-137: the step that ends an
+// episode still counts).  A step that is not counted adds nothing (no 0 * r).
+struct SactSum {
+    double sum = 0.0, disc = 1.0;
+    int n = 0;
+    bool alive = true;
+    __device__ __forceinline__ void step(float rew, bool done, double gamma, int stop) {
+        if (alive) { sum += disc * (double)rew; ++n; }
+        disc *= gamma;
+        if (stop && done) alive = false;
+    }
+};
+
+// per-wave LDS (floats): ST | NX | ACT | dynamics biases | second ACT (k_rollout_actions' layout)
+template <int ENV> constexpr int sact_wave_floats() { return Cfg<ENV, 64, 32>::W_BP0 + al4(16 * Cfg<ENV, 64, 32>::NA); }
+
+template <int ENV>
+__global__ void __launch_bounds__(64) k_score_actions(SactK r, const float* __restrict__ dynp, const float* __restrict__ norm) {
+    using C = Cfg<ENV, 64, 32>;
+    constexpr int NS = C::NS, NA = C::NA;
+    constexpr int W_ACT2 = C::W_BP0;
+    constexpr int NLD = cdiv(16 * NA, 64), NST = cdiv(16 * NS, 64);
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int lane = threadIdx.x & 63;
+    const int e = lane & 15, q = lane >> 4;
+    const int b0 = blockIdx.x * 16, b = b0 + e, k = blockIdx.y;
+    const bool active = b < r.B;
+    const int nrows = min(16, r.B - b0);                      // rows of this tile inside the batch
+    float* W = lds;
+    float* ST = W + C::W_ST;  float* NX = W + C::W_NX;
+
+    // ---------------- one-time: weight fragments -> registers, biases -> LDS ----------------------
+    const float* __restrict__ pk = dynp + (size_t)k * C::PD;
+    DynHeadFrags<C> head;
+    head.load(pk, e, q);
+    for (int i = lane; i < C::BD; i += 64) { W[C::W_BD0 + i] = pk[C::db0 + i]; W[C::W_BD1 + i] = pk[C::db1 + i]; }
+    for (int i = lane; i < C::NSP; i += 64) W[C::W_BD2 + i] = (i < NS) ? pk[C::db2 + i] : 0.0f;
+    DynInNorm<C> in;
+    DynOutNorm<C> out;
+    in.load(norm, q);
+    out.load(norm, q);
+
+    // ---------------- the tile's start rows (gathered per row) and the actions of step 0 -----------
+#pragma unroll
+    for (int j = 0; j < NST; ++j) {
+        const int i = lane + 64 * j;
+        const int row = i / NS, col = i - row * NS;
+        if (i < 16 * NS) ST[i] = (row < nrows) ? r.init_obs[(size_t)((b0 + row) / r.per) * NS + col] : 0.0f;
+    }
+#pragma unroll
+    for (int j = 0; j < NLD; ++j) {
+        const int i = lane + 64 * j;
+        const float a0 = (i < nrows * NA) ? r.actions[(size_t)b0 * NA + i] : 0.0f;
+        if (i < 16 * NA) W[C::W_ACT + i] = fminf(fmaxf(a0, -1.0f), 1.0f);            // np.clip(actions, *bounds), env_helpers.py:599
+    }
+    wave_lds_sync();
+    // every global load above is complete before the step loop (rollout_coop_kernel.h: else the wait for the loop-invariant loads lands inside it)
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+
+    SactSum acc;
+    for (int t = 0; t < r.T; ++t) {
+        // ---- the action block of step t + 1 (the last step reads its own row again: no branch, nothing out of bounds), issued now and read
+        //      behind the matrix instructions.  Every lane loads (index clamped into the tile's block) ----
+        float* ACT = W + ((t & 1) ? W_ACT2 : C::W_ACT);
+        float* ACTN = W + ((t & 1) ? C::W_ACT : W_ACT2);
+        float a_nx[NLD];
+        {
+            const float* __restrict__ an = r.actions + ((size_t)min(t + 1, r.T - 1) * r.B + b0) * NA;
+#pragma unroll
+            for (int j = 0; j < NLD; ++j) a_nx[j] = an[min(lane + 64 * j, nrows * NA - 1)];
+        }
+        // ---- the head: normalise, drop columns, 3 layers (training.py:218-269); the statements of k_rollout_actions ----
+        f32x4 h0[C::DH_CB], h1[C::DH_CB], oa[C::OUT_CB], ob[C::OUT_CB];
+        float xin[C::NIN_KS];
+#pragma unroll
+        for (int s = 0; s < C::NIN_KS; ++s) xin[s] = in.get(ST, NS, ACT, e, s);
+        head.layer0(h0, W + C::W_BD0, xin, ReluBits());
+        head.layer1(h1, W + C::W_BD1, h0, ReluBits());
+        head.layer2(oa, ob, W + C::W_BD2, h1);
+#pragma unroll
+        for (int cb = 0; cb < C::OUT_CB; ++cb) {
+            f32x4 o = oa[cb] + ob[cb];
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                const int dim = 16 * cb + 4 * q + rr;
+                const float sv = (dim < NS) ? ST[e * NS + dim] : 0.0f;
+                o[rr] = out.apply(cb, rr, o[rr], sv);
+                if (dim < NS) NX[e * NS + dim] = o[rr];
+            }
+        }
+        // ---- the prefetched actions become step t + 1's (the empty statement takes the loaded values on EVERY path, k_rollout_actions) ----
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) asm volatile("" ::"v"(a_nx[j]));
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            const int i = lane + 64 * j;
+            if (i < 16 * NA) ACTN[i] = (i < nrows * NA) ? fminf(fmaxf(a_nx[j], -1.0f), 1.0f) : 0.0f;
+        }
+        wave_lds_sync();
+        // ---- reward = -cost_np_vec(s, a_clipped, s') (:601) and is_done(s', s') (:603) into the lane's own sum ----
+        const float cost = env_cost(ENV, NS, NA, NX + e * NS, ACT + e * NA, 1, 0);
+        const bool dn = env_is_done(ENV, NS, NX + e * NS, 1, 0);
+        acc.step(-cost, dn, r.gamma, r.stop);
+#pragma unroll
+        for (int j = 0; j < NST; ++j) {
+            const int i = lane + 64 * j;
+            if (i < 16 * NS) ST[i] = NX[i];
+        }
+        wave_lds_sync();
+    }
+    if (q == 0 && active) {                                   // rounded to fp32 once, here
+        const size_t kb = (size_t)k * r.B + b;
+        r.ret[kb] = (float)acc.sum;
+        if (r.len != nullptr) r.len[kb] = acc.n;
+    }
+}
+
+// -------------------------------------------------------------------------------------------------
+// Generic path.  k_sact_starts: row 0 of the chunk's trajectory <- the start state of candidates c0 .. c0 + Bc - 1, and (a chunk narrower than B) the
+// chunk's columns of d_actions [T][B][na] -> [T][Bc][na].
+__global__ void __launch_bounds__(256) k_sact_starts(const float* __restrict__ init_obs, const float* __restrict__ actions, int B, int T, int per, int c0, int Bc,
+                                                     int ns, int na, float* __restrict__ obs0, float* __restrict__ act_c) {
+    const size_t n_obs = (size_t)Bc * ns, n_act = act_c != nullptr ? (size_t)T * Bc * na : 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_obs + n_act; i += (size_t)gridDim.x * blockDim.x) {
+        if (i < n_obs) {
+            const size_t row = i / ns, col = i - row * ns;
+            obs0[i] = init_obs[(size_t)((c0 + (int)row) / per) * ns + col];
+        } else {
+            const size_t j = i - n_obs, t = j / ((size_t)Bc * na), rest = j - t * (size_t)Bc * na;
+            act_c[j] = actions[(t * B + c0) * na + rest];
+        }
+    }
+}
+// k_sact_reduce: one thread per candidate of the chunk over the step loop's rew / done [T][Bc]; SactSum is the fused kernel's.  ret / len point at [k][c0].
+__global__ void __launch_bounds__(256) k_sact_reduce(const float* __restrict__ rew, const uint8_t* __restrict__ done, int Bc, int T, int stop, double gamma,
+                                                     float* __restrict__ ret, int32_t* __restrict__ len) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= Bc) return;
+    SactSum acc;
+    for (int t = 0; t < T; ++t) acc.step(rew[(size_t)t * Bc + i], done[(size_t)t * Bc + i] != 0, gamma, stop);
+    ret[i] = (float)acc.sum;
+    if (len != nullptr) len[i] = acc.n;
+}
+
+// d_ret_mean / d_ret_std from the stored fp32 returns [K][B]: the mean in head order divided by K, the population std two-pass by fmaf in head order --
+// rew_std's arithmetic in disagreement.hip.  K = 1: d = r - r / 1 = 0 exactly.
+__global__ void __launch_bounds__(256) k_sact_aggregate(const float* __restrict__ ret, int B, int K, float* __restrict__ mean, float* __restrict__ sd) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const float fK = (float)K;
+    float rs = 0.0f;
+    for (int k = 0; k < K; ++k) rs += ret[(size_t)k * B + b];
+    const float rm = rs / fK;
+    if (mean != nullptr) mean[b] = rm;
+    if (sd != nullptr) {
+        float rv = 0.0f;
+        for (int k = 0; k < K; ++k) { const float d = ret[(size_t)k * B + b] - rm; rv = fmaf(d, d, rv); }
+        sd[b] = sqrtf(rv / fK);
+    }
+}
+
+// -------------------------------------------------------------------------------------------------
+typedef void (*sact_kernel_t)(SactK, const float*, const float*);
+struct SactEntry { int env; sact_kernel_t kern; int w_sz; };
+#define SENTRY(ENVID) {ENVID, k_score_actions<ENVID>, sact_wave_floats<ENVID>()}
+static const SactEntry kSact[] = {SENTRY(METRPO_ENV_SWIMMER), SENTRY(METRPO_ENV_HALF_CHEETAH), SENTRY(METRPO_ENV_HOPPER), SENTRY(METRPO_ENV_SNAKE), SENTRY(METRPO_ENV_ANT)};
+
+// the shape class of rollout_actions.hip's ract_entry() WITHOUT its K <= 8 (no workgroup holds a wave per head here): the fused rollout kernels' shapes
+// with two hidden layers of 64 (*padded = false), or narrower ones through the zero-padded copy d_dyn_pad (*padded = true)
+static const SactEntry* sact_entry(const metrpo_ctx* c, bool* padded) {
+    const ProblemDesc& pd = c->pd;
+    if (pd.K > 65535) return nullptr;                            // gridDim.y
+    if (mfma_shape_config(c) >= 0 && pd.dyn.dims[1] == 64 && pd.dyn.dims[2] == 64) *padded = false;
+    else if (c->coop_pad_cfg >= 0) *padded = true;
+    else return nullptr;
+    for (const SactEntry& en : kSact)
+        if (en.env == pd.env) return &en;
+    return nullptr;
+}
+
+static int launch_sact_fused(metrpo_ctx* c, const SactEntry& en, bool padded, const metrpo_score_actions_args* a, hipStream_t st) {
+    SactK r = {};
+    r.B = a->B; r.T = a->T; r.per = a->B / a->S; r.stop = a->stop_at_done ? 1 : 0; r.gamma = a->gamma;
+    r.init_obs = a->d_init_obs; r.actions = a->d_actions; r.ret = a->d_ret; r.len = a->d_len;
+    const float* dyn = c->d_dyn.p;
+    if (padded) { const int rc = launch_pad_dyn(c, st); if (rc) return rc; dyn = c->d_dyn_pad.p; }
+    const size_t sh = sizeof(float) * (size_t)en.w_sz;
+    hipLaunchKernelGGL(en.kern, dim3((a->B + 15) / 16, c->pd.K), dim3(64), sh, st, r, dyn, c->d_norm.p);
+    HIP_TRY(c, hipGetLastError());
+    return METRPO_OK;
+}
+
+static int launch_sact_generic(metrpo_ctx* c, const metrpo_score_actions_args* a, hipStream_t st) {
+    const size_t ns = c->pd.ns, na = c->pd.na, B = a->B, T = a->T;
+    const int K = c->pd.K, per = a->B / a->S;
+    // ---- a chunk's workspace (floats): obs [T + 1][Bc][ns] | rew [T][Bc] | done [T][Bc] bytes | (Bc < B) actions [T][Bc][na]; within 2^26 floats ----
+    const size_t per_cand = (T + 1) * ns + T + (T + 3) / 4 + T * na;
+    const size_t Bc = std::min<size_t>(B, std::max<size_t>(1, ((size_t)1 << 26) / per_cand));
+    const size_t o_obs = 0, o_rew = o_obs + (T + 1) * Bc * ns, o_done = o_rew + T * Bc, o_act = o_done + (T * Bc + 3) / 4;
+    const size_t total = o_act + (Bc < B ? T * Bc * na : 0);
+    { const int rc = ws_grow(c, c->d_sact, sizeof(float) * total); if (rc) return rc; }
+    float* ws = (float*)c->d_sact.p;
+    const int keep_ract = c->last_ract_kernel;                   // run_rollout_actions reports itself there; this entry point leaves it untouched
+    int rc = METRPO_OK;
+    for (size_t c0 = 0; c0 < B && rc == METRPO_OK; c0 += Bc) {
+        const int n = (int)std::min(Bc, B - c0);
+        float* act_c = Bc < B ? ws + o_act : nullptr;
+        const size_t work = (size_t)n * ns + (act_c ? T * n * na : 0);
+        hipLaunchKernelGGL(k_sact_starts, dim3((unsigned)std::min<size_t>((work + 255) / 256, 4096)), dim3(256), 0, st, a->d_init_obs, a->d_actions, a->B, a->T, per,
+                           (int)c0, n, (int)ns, (int)na, ws + o_obs, act_c);
+        if (hipGetLastError() != hipSuccess) { rc = set_err(c, METRPO_EHIP, "score_actions: launch failed"); break; }
+        metrpo_rollout_actions_args ra = {};
+        ra.B = n; ra.T = a->T; ra.sam_mode = METRPO_SAM_EPS_RAND; ra.force_step_loop = 1;
+        ra.d_init_obs = ws + o_obs; ra.d_actions = act_c ? act_c : a->d_actions;
+        ra.d_obs = ws + o_obs; ra.d_rew = ws + o_rew; ra.d_done = (uint8_t*)(ws + o_done);
+        for (int k = 0; k < K && rc == METRPO_OK; ++k) {
+            ra.uniform_model = k;
+            rc = run_rollout_actions(c, &ra, st);
+            if (rc) break;
+            hipLaunchKernelGGL(k_sact_reduce, dim3((n + 255) / 256), dim3(256), 0, st, ra.d_rew, ra.d_done, n, a->T, a->stop_at_done ? 1 : 0, a->gamma,
+                               a->d_ret + (size_t)k * B + c0, a->d_len ? a->d_len + (size_t)k * B + c0 : nullptr);
+            if (hipGetLastError() != hipSuccess) rc = set_err(c, METRPO_EHIP, "score_actions: launch failed");
+        }
+    }
+    c->last_ract_kernel = keep_ract;
+    return rc;
+}
+
+int run_score_actions(metrpo_ctx* c, const metrpo_score_actions_args* a, hipStream_t st) {
+    bool padded = false;
+    const SactEntry* en = a->force_generic ? nullptr : sact_entry(c, &padded);
+    const int rc = en != nullptr ? launch_sact_fused(c, *en, padded, a, st) : launch_sact_generic(c, a, st);
+    if (rc) return rc;
+    if (a->d_ret_mean != nullptr || a->d_ret_std != nullptr) {
+        hipLaunchKernelGGL(k_sact_aggregate, dim3((a->B + 255) / 256), dim3(256), 0, st, a->d_ret, a->B, c->pd.K, a->d_ret_mean, a->d_ret_std);
+        HIP_TRY(c, hipGetLastError());
+    }
+    c->last_sact_kernel = en != nullptr ? 1 : 0;
+    return METRPO_OK;
+}

@@ -407,6 +407,57 @@ class Engine(object):
         with want_all, then a reduction kernel); None before the first."""
         return {0: 'generic', 1: 'fused'}.get(int(lib.metrpo_last_disagreement_kernel(self._ctx)))
 
+    # ------------------------------------------------------------------ every head's return of candidate action sequences
+    SCORE_ACTIONS_OUTPUTS = ('ret', 'len', 'ret_mean', 'ret_std')
+
+    def score_actions(self, init_obs, actions, gamma=1.0, stop_at_done=True, want=('ret',), force_generic=False, out=None):
+        """metrpo_score_actions: the discounted return each of the K heads predicts for each of B candidate action sequences -- init_obs [S, ns] or
+        [ns] (S start states, B % S == 0: candidate b starts from init_obs[b // (B // S)]), actions [T, B, na] unclipped (clipped inside, never written).
+        Head k rolls its own trajectory (rollout_actions(sam_mode='eps_rand', model=k)); stop_at_done: a candidate stops counting behind its first done
+        (the step that ends it still counts), False: every step counts.  want: any of ret [K, B], len [K, B] int32 (steps counted), ret_mean [B],
+        ret_std [B] (population std over the heads); ret is always computed.  -> dict of device tensors, nothing synchronised.  out: dict name ->
+        tensor to write into instead (contiguous, at least that large)."""
+        dev = self.device
+        init_obs = _f32(init_obs, dev)
+        if init_obs.dim() == 1:
+            init_obs = init_obs.unsqueeze(0)
+        if init_obs.dim() != 2 or init_obs.shape[1] != self.ns or init_obs.shape[0] < 1:
+            raise ValueError("init_obs: expected [S, %d] or [%d], got %s" % (self.ns, self.ns, tuple(init_obs.shape)))
+        S = init_obs.shape[0]
+        actions = _f32(actions, dev)
+        if actions.dim() != 3 or actions.shape[2] != self.na or actions.shape[1] % S != 0:
+            raise ValueError("actions: expected [T, B, %d] with B a multiple of %d, got %s" % (self.na, S, tuple(actions.shape)))
+        T, B = int(actions.shape[0]), int(actions.shape[1])
+        want = (want,) if isinstance(want, str) else tuple(want)
+        for w in want:
+            if w not in self.SCORE_ACTIONS_OUTPUTS:
+                raise ValueError("want: %r is none of %s" % (w, self.SCORE_ACTIONS_OUTPUTS))
+        if not np.isfinite(float(gamma)):
+            raise ValueError("gamma must be finite")
+        shapes = {'ret': (self.K, B), 'len': (self.K, B), 'ret_mean': (B,), 'ret_std': (B,)}
+        res = {}
+        for w in ('ret',) + tuple(x for x in want if x != 'ret'):
+            dt = torch.int32 if w == 'len' else torch.float32
+            if out is not None and w in out:
+                t = out[w]
+                assert t.dtype == dt and t.is_contiguous() and t.device == dev and t.numel() >= int(np.prod(shapes[w], dtype=np.int64))
+            else:
+                t = torch.empty(shapes[w], dtype=dt, device=dev)
+            res[w] = t
+        a = _lib.ScoreActionsArgs()
+        a.B, a.T, a.S, a.stop_at_done, a.force_generic, a.gamma = B, T, S, int(bool(stop_at_done)), int(bool(force_generic)), float(gamma)
+        a.d_init_obs, a.d_actions = init_obs.data_ptr(), actions.data_ptr()
+        for w in self.SCORE_ACTIONS_OUTPUTS:
+            setattr(a, 'd_' + w, res[w].data_ptr() if w in res else None)
+        self._chk(lib.metrpo_score_actions(self._ctx, C.byref(a), self._stream()))
+        self._sa_keep = (init_obs, actions)                                        # alive until the stream has consumed them
+        return res
+
+    def last_score_actions_kernel(self):
+        """Path the last score_actions() of this engine took: 'fused' (score_actions.hip: one launch, a wave per (tile, head)), 'generic' (per head
+        the step loop of rollout_actions, then a reduction kernel); None before the first."""
+        return {0: 'generic', 1: 'fused'}.get(int(lib.metrpo_last_score_actions_kernel(self._ctx)))
+
     # ------------------------------------------------------------------ fused rollout
     def rollout(self, B, T, H, sam_mode, pool, determ=False, eval_all_heads=True, seed=0, stream_offset=0,
                 eps=None, model_idx=None, sel_noise=None, reset_idx=None, reset_model=None, out=None,

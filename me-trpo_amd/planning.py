@@ -1,0 +1,192 @@
+"""Planning by shooting through the learned ensemble: candidate action sequences are scored by every head in ONE device call
+(Engine.score_actions / metrpo_score_actions) and the planner loop -- sample, score, top-k, refit -- is a few lines of torch on device tensors.
+Nothing here reads a device tensor back inside a loop (no .item(), no .cpu()); the caller synchronises once, when it uses a result.
+
+Every function takes `scorer=` in place of the engine's own: any callable (actions [T, B, na], init [S, ns]) -> ret [K, B] with candidate b starting
+from init[b // (B // S)].  With a scorer the engine may be None and the logic runs on whatever device the states live on (then pass na=).
+
+Layouts: states [S, ns]; a batch of candidates is [S, N, T, na] towards the caller (trajectory-major, as open_loop_predictions) and [T, S * N, na]
+towards the device, candidate b = s * N + n."""
+import numpy as np
+import torch
+
+
+def engine_scorer(engine, gamma=1.0, stop_at_done=True, force_generic=False):
+    """The engine's own scorer: (actions [T, B, na], init [S, ns]) -> ret [K, B], one metrpo_score_actions call, nothing synchronised."""
+    def scorer(actions, init):
+        return engine.score_actions(init, actions, gamma=gamma, stop_at_done=stop_at_done, force_generic=force_generic)['ret']
+    return scorer
+
+
+def aggregate_heads(ret, aggregate='mean'):
+    """ret [K, B] -> [B]: 'mean' over the heads, 'min' (the worst head), or ('pessimistic', beta): mean - beta * population std over the heads."""
+    if isinstance(aggregate, str):
+        if aggregate == 'mean':
+            return ret.mean(dim=0)
+        if aggregate == 'min':
+            return ret.min(dim=0).values
+        raise ValueError("aggregate: %r is none of 'mean', 'min', ('pessimistic', beta)" % (aggregate,))
+    if isinstance(aggregate, (tuple, list)) and len(aggregate) == 2 and aggregate[0] == 'pessimistic':
+        return ret.mean(dim=0) - float(aggregate[1]) * ret.std(dim=0, unbiased=False)
+    raise ValueError("aggregate: %r is none of 'mean', 'min', ('pessimistic', beta)" % (aggregate,))
+
+
+def _setup(engine, states, scorer, na, gamma, stop_at_done):
+    if scorer is None:
+        if engine is None:
+            raise ValueError("an engine or a scorer is needed")
+        scorer = engine_scorer(engine, gamma, stop_at_done)
+    dev = engine.device if engine is not None else None
+    states = torch.as_tensor(states, device=dev).to(torch.float32)
+    if states.dim() == 1:
+        states = states.unsqueeze(0)
+    ns = engine.ns if engine is not None else states.shape[-1]
+    if states.dim() != 2 or states.shape[1] != ns or states.shape[0] < 1:
+        raise ValueError("states: expected [S, %d] with S >= 1, got %s" % (ns, tuple(states.shape)))
+    if engine is not None:
+        na = engine.na
+    if na is None or int(na) < 1:
+        raise ValueError("na is needed when there is no engine")
+    return scorer, states.contiguous(), int(na)
+
+
+def _device_major(cand):
+    """[S, N, T, na] -> [T, S * N, na], candidate b = s * N + n"""
+    S, N, T, na = cand.shape
+    return cand.permute(2, 0, 1, 3).reshape(T, S * N, na).contiguous()
+
+
+def score_action_sequences(engine, states, actions, gamma=1.0, stop_at_done=True, aggregate='mean', scorer=None):
+    """Score supplied action sequences: states [S, ns], actions [S, N, T, na] (N candidates per state) or [S, T, na] (one each), trajectory-major
+    and unclipped (clipped on the device).  -> scores [S, N] (or [S]): the heads' discounted returns folded by `aggregate`.  A device tensor."""
+    act = torch.as_tensor(actions)
+    scorer, states, na = _setup(engine, states, scorer, act.shape[-1] if act.dim() >= 1 else None, gamma, stop_at_done)
+    act = act.to(device=states.device, dtype=torch.float32)
+    S = states.shape[0]
+    single = act.dim() == 3
+    if single:
+        act = act.unsqueeze(1)
+    if act.dim() != 4 or act.shape[0] != S or act.shape[3] != na or act.shape[1] < 1 or act.shape[2] < 1:
+        raise ValueError("actions: expected [%d, N, T, %d] or [%d, T, %d], got %s" % (S, na, S, na, tuple(torch.as_tensor(actions).shape)))
+    scores = aggregate_heads(scorer(_device_major(act), states), aggregate).reshape(S, act.shape[1])
+    return scores[:, 0] if single else scores
+
+
+def _check_counts(horizon, n_candidates):
+    if int(horizon) < 1 or int(n_candidates) < 1:
+        raise ValueError("horizon and n_candidates must be positive, got %r and %r" % (horizon, n_candidates))
+    return int(horizon), int(n_candidates)
+
+
+def plan_random_shooting(engine, states, horizon, n_candidates, generator=None, gamma=1.0, stop_at_done=True, aggregate='mean', scorer=None, na=None):
+    """Random shooting: per state, n_candidates sequences of `horizon` actions drawn uniformly from [-1, 1], scored in one call, the best taken.
+    -> dict(actions [S, T, na] the best sequence, score [S] its score, scores [S, N] all of them), device tensors."""
+    T, N = _check_counts(horizon, n_candidates)
+    scorer, states, na = _setup(engine, states, scorer, na, gamma, stop_at_done)
+    S, dev = states.shape[0], states.device
+    cand = torch.rand(T, S, N, na, generator=generator, device=dev, dtype=torch.float32) * 2.0 - 1.0
+    scores = aggregate_heads(scorer(cand.reshape(T, S * N, na), states), aggregate).reshape(S, N)
+    score, best = scores.max(dim=1)
+    idx = best.view(1, S, 1, 1).expand(T, S, 1, na)
+    return dict(actions=cand.gather(2, idx)[:, :, 0].permute(1, 0, 2).contiguous(), score=score, scores=scores)
+
+
+def _time_major_param(x, T, S, na, dev, name):
+    """a scalar, [T, na] or [S, T, na] -> [T, S, 1, na]"""
+    x = torch.as_tensor(x, device=dev, dtype=torch.float32)
+    if x.dim() == 0:
+        return x.expand(T, S, 1, na).clone()
+    if tuple(x.shape) == (T, na):
+        return x.view(T, 1, 1, na).expand(T, S, 1, na).clone()
+    if tuple(x.shape) == (S, T, na):
+        return x.permute(1, 0, 2).reshape(T, S, 1, na).clone()
+    raise ValueError("%s: expected a scalar, [%d, %d] or [%d, %d, %d], got %s" % (name, T, na, S, T, na, tuple(x.shape)))
+
+
+def plan_cem(engine, states, horizon, n_candidates, n_elites, n_iters, init_mean=None, init_std=1.0, alpha=0.0, min_std=0.0, gamma=1.0,
+             aggregate='mean', generator=None, stop_at_done=True, scorer=None, na=None):
+    """Cross-entropy method over action sequences, per state.  Each iteration: eps = randn(T, S, N, na); a = clip(mean + std * eps, -1, 1); one scoring
+    call for all S * N candidates; the n_elites best per state (topk); elite mean and population std (ddof 0) of the CLIPPED elites, formed in float64
+    and rounded to fp32; mean <- alpha * mean + (1 - alpha) * elite_mean, the same for std, floored at min_std.
+    init_mean / init_std: a scalar, [T, na] or [S, T, na] (None: zeros).
+    -> dict(actions [S, T, na] the final mean, std [S, T, na], best_actions [S, T, na] / best_score [S] the best candidate seen in any iteration,
+    history [n_iters, S] the elites' mean score per iteration, elites [S, n_elites] the candidate indices of the LAST iteration's elites, best first),
+    device tensors; nothing is read back."""
+    T, N = _check_counts(horizon, n_candidates)
+    E, n_iters = int(n_elites), int(n_iters)
+    if not (1 <= E <= N):
+        raise ValueError("n_elites must be in 1 ... n_candidates = %d, got %r" % (N, n_elites))
+    if n_iters < 1:
+        raise ValueError("n_iters must be positive, got %r" % (n_iters,))
+    if not (0.0 <= float(alpha) < 1.0):
+        raise ValueError("alpha must be in [0, 1), got %r" % (alpha,))
+    scorer, states, na = _setup(engine, states, scorer, na, gamma, stop_at_done)
+    S, dev = states.shape[0], states.device
+    mean = _time_major_param(0.0 if init_mean is None else init_mean, T, S, na, dev, 'init_mean')
+    std = _time_major_param(init_std, T, S, na, dev, 'init_std')
+    alpha, min_std = float(alpha), float(min_std)
+    best_score = torch.full((S,), float('-inf'), device=dev, dtype=torch.float32)
+    best_actions = torch.zeros(T, S, na, device=dev, dtype=torch.float32)
+    history = torch.empty(n_iters, S, device=dev, dtype=torch.float32)
+    for it in range(n_iters):
+        eps = torch.randn(T, S, N, na, generator=generator, device=dev, dtype=torch.float32)
+        a = torch.clamp(mean + std * eps, -1.0, 1.0)
+        scores = aggregate_heads(scorer(a.reshape(T, S * N, na), states), aggregate).reshape(S, N)
+        vals, idx = torch.topk(scores, E, dim=1)                                          # sorted: column 0 is the iteration's best
+        elites = a.gather(2, idx.view(1, S, E, 1).expand(T, S, E, na)).double()
+        e_mean = elites.sum(dim=2, keepdim=True) / E
+        e_std = torch.sqrt(((elites - e_mean) ** 2).sum(dim=2, keepdim=True) / E)
+        mean = alpha * mean + (1.0 - alpha) * e_mean.float()
+        std = torch.clamp(alpha * std + (1.0 - alpha) * e_std.float(), min=min_std)
+        better = vals[:, 0] > best_score
+        best_score = torch.where(better, vals[:, 0], best_score)
+        best_actions = torch.where(better.view(1, S, 1), elites[:, :, 0].float(), best_actions)
+        history[it] = vals.mean(dim=1)
+    tm = lambda x: x.permute(1, 0, 2).contiguous()
+    return dict(actions=tm(mean[:, :, 0]), std=tm(std[:, :, 0]), best_actions=tm(best_actions), best_score=best_score, history=history, elites=idx)
+
+
+class ShootingController(object):
+    """Model-predictive control by CEM with a warm start, with the policy's call shape: get_actions(obs [S, ns]) -> (actions [S, na], {}).
+    Every call plans `horizon` steps ahead from obs, returns the first action of the plan's mean and keeps the rest: the next call starts from the
+    previous mean shifted by one step, its last row reset to init_mean's last row (std starts from init_std every time).
+    The action comes back as float64 NumPy, as GaussianMLPPolicy.get_actions gives it -- one read-back per call, behind the planner."""
+
+    def __init__(self, engine, horizon, n_candidates, n_elites, n_iters, init_mean=None, init_std=1.0, alpha=0.0, min_std=0.0, gamma=1.0,
+                 aggregate='mean', generator=None, stop_at_done=True, scorer=None, na=None):
+        self.engine, self.horizon, self.scorer, self.na = engine, int(horizon), scorer, (engine.na if engine is not None else na)
+        self.init_mean, self.init_std = init_mean, init_std
+        self.kw = dict(n_candidates=n_candidates, n_elites=n_elites, n_iters=n_iters, alpha=alpha, min_std=min_std, gamma=gamma, aggregate=aggregate,
+                       generator=generator, stop_at_done=stop_at_done)
+        self._mean = None                                                                 # [S, T, na]: the warm start of the next call
+        self.last_plan = None
+
+    def reset(self, dones=None):
+        """Forget the warm start: of every env (dones None) or of the envs whose entry of dones is set."""
+        if dones is None or self._mean is None:
+            self._mean = None
+            return
+        d = torch.as_tensor(np.asarray(dones).astype(bool), device=self._mean.device)
+        self._mean = torch.where(d.view(-1, 1, 1), self._fresh(self._mean.shape[0], self._mean.device), self._mean)
+
+    def _fresh(self, S, dev):
+        m = _time_major_param(0.0 if self.init_mean is None else self.init_mean, self.horizon, S, self.na, dev, 'init_mean')
+        return m[:, :, 0].permute(1, 0, 2).contiguous()
+
+    def shifted(self, mean):
+        """[S, T, na] -> the same one step on: row t <- row t + 1, the last row <- init_mean's last row"""
+        fresh = self._fresh(mean.shape[0], mean.device)
+        return torch.cat([mean[:, 1:], fresh[:, -1:]], dim=1)
+
+    def get_actions(self, observations):
+        obs = torch.as_tensor(np.asarray(observations) if not torch.is_tensor(observations) else observations)
+        S = obs.shape[0] if obs.dim() == 2 else 1
+        start = self._mean if (self._mean is not None and self._mean.shape[0] == S) else self.init_mean
+        plan = plan_cem(self.engine, obs, self.horizon, init_mean=start, init_std=self.init_std, scorer=self.scorer, na=self.na, **self.kw)
+        self.last_plan = plan
+        self._mean = self.shifted(plan['actions'])
+        return plan['actions'][:, 0].double().cpu().numpy(), {}
+
+    def get_action(self, observation):
+        a, info = self.get_actions(np.asarray(observation)[None])
+        return a[0], info
