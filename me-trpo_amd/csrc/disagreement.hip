@@ -1,7 +1,10 @@
 // metrpo_ensemble_disagreement (include/metrpo.h): the spread of the K heads' next states at N supplied (s, a) rows -- np.std(next_possible_observations,
 // axis=0), env_helpers.py:625, returned instead of consumed.  One step of the model on N independent rows: no chain of dependent steps.
 //
-// Fused kernel (k_disagreement): k_rollout_actions' ALL-heads step (rollout_actions.hip) with T = 1, turned into a loop over tiles.
+// Fused kernel (k_disagreement): k_rollout_actions' ALL-heads step (rollout_actions.hip) with T = 1, turned into a loop over tiles.  From
+// dyn_tile_step.h it takes the wave's head (DynWaveHead: set-up and step) and the K-head exchange with its head-order mean (HeadExchange).  The double
+// buffer of input rows is its own (load_tile / commit below), not that header's ActTile: a tile brings state rows and validity bytes with its actions,
+// rows are zeroed by the row's flag in LDS and not by the row count alone, and the walk is over 64-bit tile indices, not the steps of one tile.
 //   * wave k of the workgroup owns head k (K <= 8 waves) on the shared head of dyn_head_mfma.h; its weight fragments are register-resident (swimmer 92,
 //     Ant 132 registers).  k_rollout_actions amortises them over the T steps of one tile; here a workgroup STRIDES over the 16-row tiles with the
 //     weights resident, and the grid is the workgroups the CUs this process reaches can hold (probe.hip's census), not one workgroup per tile.
@@ -20,7 +23,7 @@
 // go to the workspace and are dropped), then k_dis_reduce, one thread per row.
 //
 // d_sums: k_dis_sums, a second small launch on d_score / d_valid, one workgroup of a fixed shape per group adding in a fixed order.
-#include "dyn_head_mfma.h"
+#include "dyn_tile_step.h"
 
 struct DisK {
     long long N;
@@ -45,21 +48,13 @@ __global__ void __launch_bounds__(512) k_disagreement(DisK r, int K, const float
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int e = lane & 15, q = lane >> 4;
     float* W = lds + wave * L::W_SZ;
-    float* NXT = lds + K * L::W_SZ;                              // [2][K][16][NSP] exchange buffer
+    const HeadExchange<C> xch = {lds + K * L::W_SZ, K};
     const long long ntiles = (r.N + 15) >> 4;
     long long tile = blockIdx.x;                                 // the grid never exceeds the tiles
     if (tile >= ntiles) return;
 
-    // ---------------- one-time: weight fragments -> registers, biases -> LDS ----------------------
-    const float* __restrict__ pk = dynp + (size_t)wave * C::PD;
-    DynHeadFrags<C> head;
-    head.load(pk, e, q);
-    for (int i = lane; i < C::BD; i += 64) { W[L::BD0 + i] = pk[C::db0 + i]; W[L::BD1 + i] = pk[C::db1 + i]; }
-    for (int i = lane; i < NSP; i += 64) W[L::BD2 + i] = (i < NS) ? pk[C::db2 + i] : 0.0f;
-    DynInNorm<C> in;
-    DynOutNorm<C> out;
-    in.load(norm, q);
-    out.load(norm, q);
+    DynWaveHead<C> head;
+    head.load(dynp + (size_t)wave * C::PD, norm, W + L::BD0, W + L::BD1, W + L::BD2, lane);
 
     // a tile's rows as every lane loads them: straight-line loads, the index clamped into the tile's block (nothing out of bounds, no masked branch:
     // the compiler waits for them where they are used).  Without d_valid the byte comes from d_obs and is dropped.
@@ -101,8 +96,7 @@ __global__ void __launch_bounds__(512) k_disagreement(DisK r, int K, const float
 
     load_tile(tile);
     commit(0, tile);
-    // every global load above is complete before the tile loop (rollout_coop_kernel.h: else the wait for the loop-invariant loads lands inside it)
-    __builtin_amdgcn_s_waitcnt(0x0F70);
+    loop_invariant_loads_done();
 
     // The wave that forms a tile's outputs.  The barrier keeps the waves in step, so whatever one wave does on top of its head is on every tile's critical
     // path -- unless that wave has a SIMD to itself.  A workgroup's waves go to the CU's four SIMDs cyclically, so waves w and w + 4 share one: at K = 5 .. 7
@@ -120,34 +114,13 @@ __global__ void __launch_bounds__(512) k_disagreement(DisK r, int K, const float
         const float* ST = W + L::ST + par * L::ST_SZ;
         const float* ACT = W + L::ACT + par * L::ACT_SZ;
         const float* ROKc = W + L::ROK + 16 * par;
-        // ---- the head: normalise, drop columns, 3 layers (training.py:218-269); the statements of k_rollout_actions ----
-        f32x4 h0[C::DH_CB], h1[C::DH_CB], oa[C::OUT_CB], ob[C::OUT_CB];
-        float xin[C::NIN_KS];
-#pragma unroll
-        for (int s = 0; s < C::NIN_KS; ++s) xin[s] = in.get(ST, NS, ACT, e, s);
-        head.layer0(h0, W + L::BD0, xin, ReluBits());
-        head.layer1(h1, W + L::BD1, h0, ReluBits());
-        head.layer2(oa, ob, W + L::BD2, h1);
         f32x4 nx[C::OUT_CB];
-#pragma unroll
-        for (int cb = 0; cb < C::OUT_CB; ++cb) {
-            f32x4 o = oa[cb] + ob[cb];
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int dim = 16 * cb + 4 * q + rr;
-                const float sv = (dim < NS) ? ST[e * NS + dim] : 0.0f;
-                o[rr] = out.apply(cb, rr, o[rr], sv);
-            }
-            nx[cb] = o;
-        }
-        // ---- the K heads of the tile meet in LDS ----
-        float* nxt_w = NXT + ((size_t)(par * K + wave) * 16 + e) * NSP;
-#pragma unroll
-        for (int cb = 0; cb < C::OUT_CB; ++cb) *(f32x4*)&nxt_w[16 * cb + 4 * q] = nx[cb];
+        head.step(nx, ST, NS, ACT, e);
+        xch.put(par, wave, e, q, nx);
         __syncthreads();                                                         // all K heads of this tile are in NXT[par]
         // ---- the prefetched rows become the next tile's.  The wait for them is the loop's only vmcnt wait; it also covers the stores of the tile before
         //      -- a whole tile of matrix work old -- and none of this tile's, which follow below (the empty statements take the loaded values on EVERY
-        //      path, k_rollout_actions) ----
+        //      path: dyn_tile_step.h, ActTile::commit) ----
 #pragma unroll
         for (int j = 0; j < NST; ++j) asm volatile("" ::"v"(s_nx[j]));
 #pragma unroll
@@ -173,18 +146,16 @@ __global__ void __launch_bounds__(512) k_disagreement(DisK r, int K, const float
         if (wave == turn) {
             // ---- get_next_observation's mean and std (env_helpers.py:621-625) over the K heads, from LDS; lane (e, q) holds dims 16 cb + 4 q + r of row e.
             //      The padded dims are exact zeros in every head (zero weights, bias, normaliser and state) and add exact zeros ----
-            const float* nxt_all = NXT + (size_t)par * K * 16 * NSP;
+            const float* nxt_all = xch.heads(par);
             const float fK = (float)K;
             float ssq = 0.0f;
 #pragma unroll
             for (int cb = 0; cb < C::OUT_CB; ++cb) {
                 const int off = e * NSP + 16 * cb + 4 * q;
-                f32x4 m = {0.f, 0.f, 0.f, 0.f};
-                for (int k = 0; k < K; ++k) m += *(const f32x4*)&nxt_all[(size_t)k * 16 * NSP + off];        // head order, as metrpo_step
-                m = m / fK;
+                const f32x4 m = xch.mean(nxt_all, K, off);
                 f32x4 var = {0.f, 0.f, 0.f, 0.f};
                 for (int k = 0; k < K; ++k) {
-                    const f32x4 d = *(const f32x4*)&nxt_all[(size_t)k * 16 * NSP + off] - m;
+                    const f32x4 d = xch.head(nxt_all, k, off) - m;
 #pragma unroll
                     for (int rr = 0; rr < 4; ++rr) var[rr] = fmaf(d[rr], d[rr], var[rr]);
                 }
@@ -207,10 +178,7 @@ __global__ void __launch_bounds__(512) k_disagreement(DisK r, int K, const float
 #pragma unroll
                     for (int cb = 0; cb < C::OUT_CB; ++cb) {
                         const int off = e * NSP + 16 * cb + 4 * q;
-                        f32x4 m = {0.f, 0.f, 0.f, 0.f};
-                        for (int kk = 0; kk < K; ++kk) m += *(const f32x4*)&nxt_all[(size_t)kk * 16 * NSP + off];
-                        m = m / fK;
-                        const f32x4 d = *(const f32x4*)&nxt_all[(size_t)k * 16 * NSP + off] - m;
+                        const f32x4 d = xch.head(nxt_all, k, off) - xch.mean(nxt_all, K, off);
 #pragma unroll
                         for (int rr = 0; rr < 4; ++rr) dk = fmaf(d[rr], d[rr], dk);
                     }
@@ -341,27 +309,14 @@ static int launch_dis_sums(metrpo_ctx* c, const float* score, const metrpo_disag
 typedef void (*dis_kernel_t)(DisK, int, const float*, const float*);
 struct DisEntry { int env; dis_kernel_t kern; int w_sz, nsp; };
 #define DENTRY(ENVID) {ENVID, k_disagreement<ENVID>, DisLds<ENVID>::W_SZ, Cfg<ENVID, 64, 32>::NSP}
-static const DisEntry kDis[] = {DENTRY(METRPO_ENV_SWIMMER), DENTRY(METRPO_ENV_HALF_CHEETAH), DENTRY(METRPO_ENV_HOPPER), DENTRY(METRPO_ENV_SNAKE), DENTRY(METRPO_ENV_ANT)};
-
-// the shape class of rollout_actions.hip's ract_entry(): the fused rollout kernels' shapes with two hidden layers of 64 (*padded = false), or narrower
-// ones through the zero-padded copy d_dyn_pad (*padded = true); K <= 8 (a wave per head)
-static const DisEntry* dis_entry(const metrpo_ctx* c, bool* padded) {
-    const ProblemDesc& pd = c->pd;
-    if (pd.K > 8) return nullptr;
-    if (mfma_shape_config(c) >= 0 && pd.dyn.dims[1] == 64 && pd.dyn.dims[2] == 64) *padded = false;
-    else if (c->coop_pad_cfg >= 0) *padded = true;
-    else return nullptr;
-    for (const DisEntry& en : kDis)
-        if (en.env == pd.env) return &en;
-    return nullptr;
-}
+static const DisEntry kDis[] = {FUSED_HEAD_ENVS(DENTRY)};
 
 static int launch_dis_fused(metrpo_ctx* c, const DisEntry& en, bool padded, const DisK& r, hipStream_t st) {
     const int K = c->pd.K;
-    const float* dyn = c->d_dyn.p;
-    if (padded) { const int rc = launch_pad_dyn(c, st); if (rc) return rc; dyn = c->d_dyn_pad.p; }
-    const size_t sh = sizeof(float) * ((size_t)K * en.w_sz + 2 * (size_t)K * 16 * en.nsp);
-    if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)en.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+    const float* dyn;
+    { const int rc = fused_head_dyn(c, padded, st, &dyn); if (rc) return rc; }
+    const size_t sh = sizeof(float) * ((size_t)K * en.w_sz + head_exchange_floats(K, en.nsp));
+    { const int rc = allow_dynamic_lds(c, (const void*)en.kern, sh); if (rc) return rc; }
     if (c->dis_per_cu <= 0) {                                    // workgroups a CU holds (registers, LDS): asked once, the shape is the context's
         int per_cu = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)en.kern, K * 64, sh) != hipSuccess) { (void)hipGetLastError(); per_cu = 1; }
@@ -378,7 +333,7 @@ int run_disagreement(metrpo_ctx* c, const metrpo_disagreement_args* a, hipStream
     const ProblemDesc& pd = c->pd;
     const size_t N = (size_t)a->N, ns = pd.ns, K = pd.K;
     bool padded = false;
-    const DisEntry* en = a->force_generic ? nullptr : dis_entry(c, &padded);
+    const DisEntry* en = a->force_generic ? nullptr : fused_head_entry(kDis, c, 8, &padded);      // a wave per head
     // ---- workspace: scores (only d_sums asked for) | generic: every head's next state (unless the caller takes it) | s_next | reward | done ----
     const bool ws_score = a->d_score == nullptr && a->d_sums != nullptr;
     const bool ws_all = en == nullptr && a->d_next_all == nullptr;

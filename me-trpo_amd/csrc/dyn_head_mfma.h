@@ -1,6 +1,6 @@
 // One dynamics head of the ensemble (training.py:218-269) for a tile of 16 envs, TRANSPOSED on v_mfma_f32_16x16x4_f32: the one statement of
-// what rollout_mfma.hip, rollout_actions.hip and bptt_mfma.hip instantiate (all three pieces) and rollout_coop_kernel.h (the two normalisers;
-// its layers are split across waves with a fragment layout of its own).
+// what rollout_mfma.hip, bptt_mfma.hip and dyn_tile_step.h (for rollout_actions.hip, score_actions.hip and disagreement.hip) instantiate (all three
+// pieces) and rollout_coop_kernel.h (the two normalisers; its layers are split across waves with a fragment layout of its own).
 //
 // Layout.  Lane l = (e = l & 15, q = l >> 4).  Every layer is H^T[unit][env] = W^T . X^T:
 //   A = weights      lane l holds W[in = k-step's input of q][out = 16 cb + e]

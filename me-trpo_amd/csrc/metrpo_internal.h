@@ -358,6 +358,21 @@ int mfma_shape_config(const metrpo_ctx*);
 int coop_select_config(metrpo_ctx*);
 int launch_rollout_coop(metrpo_ctx*, int idx, const RolloutK&, hipStream_t, bool padded = false);
 int launch_pad_dyn(metrpo_ctx*, hipStream_t);      // d_dyn -> d_dyn_pad (zero-padded 64 x 64 layout)
+// Host side of the fused head kernels on dyn_tile_step.h (rollout_actions.hip, which has these functions; score_actions.hip; disagreement.hip).
+// Do they hold this context?  The fused rollout kernels' shape class with two hidden layers of 64 (*padded = false), or narrower ones through the
+// zero-padded copy d_dyn_pad that metrpo_create made for them (*padded = true), and at most k_cap heads: 8 where a workgroup has a wave per head,
+// 65535 where the heads are gridDim.y.
+bool fused_head_class(const metrpo_ctx*, int k_cap, bool* padded);
+int fused_head_dyn(metrpo_ctx*, bool padded, hipStream_t, const float** dyn);   // the ensemble to launch with: d_dyn, or d_dyn_pad behind launch_pad_dyn
+int allow_dynamic_lds(metrpo_ctx*, const void* kernel, size_t bytes);           // above 64 KB a kernel needs the attribute before it is launched
+// their per-env tables: one ENTRY(env id) per env of the class, rows with a member `env`
+#define FUSED_HEAD_ENVS(ENTRY) ENTRY(METRPO_ENV_SWIMMER), ENTRY(METRPO_ENV_HALF_CHEETAH), ENTRY(METRPO_ENV_HOPPER), ENTRY(METRPO_ENV_SNAKE), ENTRY(METRPO_ENV_ANT)
+template <class E, size_t N> static inline const E* fused_head_entry(const E (&tab)[N], const metrpo_ctx* c, int k_cap, bool* padded) {
+    if (!fused_head_class(c, k_cap, padded)) return nullptr;
+    for (const E& en : tab)
+        if (en.env == c->pd.env) return &en;
+    return nullptr;
+}
 int launch_validation_cost(metrpo_ctx*, const float*, int, int, double, double*, hipStream_t);
 int launch_gae(metrpo_ctx*, const float*, const float*, const uint8_t*, const int32_t*, int, int, const double*,
                double, double, float*, float*, uint8_t*, double*, hipStream_t);

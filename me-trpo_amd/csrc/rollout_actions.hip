@@ -2,7 +2,8 @@
 // env_helpers.py:216-222, over VecSimpleEnv.step's arithmetic, :597-603.  T chained metrpo_step calls in meaning: no policy, no reset, no path-length
 // limit, no draw; stepping continues behind a done.
 //
-// Fused kernel (k_rollout_actions): rollout_mfma.hip's dynamics step without the policy, the action read from memory instead.
+// Fused kernel (k_rollout_actions): rollout_mfma.hip's dynamics step without the policy, the action read from memory instead.  Its body is
+// dyn_tile_step.h's tile_rollout (shared with k_score_actions) with the sink below, which stores the trajectory; what follows describes that body.
 //   * one workgroup = one tile of 16 envs, walked through all T steps, on the shared head of dyn_head_mfma.h (layout and arithmetic are described there).
 //   * the head's weight fragments are register-resident for the whole loop (swimmer 92, Ant 132 registers), biases, normalisers' source map and the
 //     tile's state live in LDS; the state is [env][ns], the layout of one row of d_obs, so a row is one linear coalesced store.
@@ -20,7 +21,7 @@
 //   * edge tile (B % 16 != 0): rows >= B are zero state and zero action in LDS, never read from or written to memory.
 //
 // Step loop (everything the fused kernel does not hold): launch_step on row t of d_actions, writing row t + 1 of d_obs.  No gather, no action copy.
-#include "dyn_head_mfma.h"
+#include "dyn_tile_step.h"
 
 struct RactK {
     int B, T;
@@ -30,171 +31,59 @@ struct RactK {
     float* obs; float* rew; uint8_t* done;
 };
 
-template <int ENV> constexpr int ract_wave_floats() { return Cfg<ENV, 64, 32>::W_BP0 + al4(16 * Cfg<ENV, 64, 32>::NA); }
+// tile_rollout's sink that stores the trajectory: a row of d_obs is the tile's LDS state as one linear coalesced store
+template <int NS>
+struct RactSink {
+    static constexpr int NST = cdiv(16 * NS, 64);
+    const RactK& r;
+    __device__ __forceinline__ void rows(float* __restrict__ orow, const float* ST, int nrows, int lane) const {
+#pragma unroll
+        for (int j = 0; j < NST; ++j) {
+            const int i = lane + 64 * j;
+            if (i < nrows * NS) orow[i] = ST[i];
+        }
+    }
+    // row 0 of d_obs = d_init_obs, bit for bit
+    __device__ __forceinline__ void start(const float* ST, int b0, int nrows, int lane) const { rows(r.obs + (size_t)b0 * NS, ST, nrows, lane); }
+    // row t + 1 of d_obs, reward = -cost and done of step t; the env goes on either way
+    __device__ __forceinline__ void step(int t, const float* ST, float cost, bool dn, int b0, int nrows, int lane) const {
+        rows(r.obs + ((size_t)(t + 1) * r.B + b0) * NS, ST, nrows, lane);
+        const int b = b0 + (lane & 15);
+        if ((lane >> 4) == 0 && b < r.B) { const size_t tb = (size_t)t * r.B + b; r.rew[tb] = -cost; r.done[tb] = dn ? 1 : 0; }
+    }
+};
 
 template <int ENV, bool ONE>
 __global__ void __launch_bounds__(ONE ? 64 : 512) k_rollout_actions(RactK r, int K, const float* __restrict__ dynp, const float* __restrict__ norm) {
-    using C = Cfg<ENV, 64, 32>;
-    constexpr int NS = C::NS, NA = C::NA, NSP = C::NSP;
-    constexpr int W_ACT2 = C::W_BP0, W_SZ = ract_wave_floats<ENV>();   // per-wave LDS (floats): ST | NX | ACT | dynamics biases | second ACT
-    constexpr int NLD = cdiv(16 * NA, 64), NST = cdiv(16 * NS, 64);
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int e = lane & 15, q = lane >> 4;
-    const int b0 = blockIdx.x * 16, b = b0 + e;
-    const bool active = b < r.B;
-    const int nrows = min(16, r.B - b0);                      // rows of this tile inside the batch
-    const int NW = ONE ? 1 : K;
-    float* W = lds + wave * W_SZ;
-    float* ST = W + C::W_ST;  float* NX = W + C::W_NX;
-    // (clipped actions of even steps at W_ACT, of odd steps at W_ACT2)
-    float* NXT = lds + NW * W_SZ;                             // ALL: [2][K][16][NSP] exchange buffer
-
-    // ---------------- one-time: weight fragments -> registers, biases -> LDS ----------------------
-    const float* __restrict__ pk = dynp + (size_t)(ONE ? r.head : wave) * C::PD;
-    DynHeadFrags<C> head;
-    head.load(pk, e, q);
-    for (int i = lane; i < C::BD; i += 64) { W[C::W_BD0 + i] = pk[C::db0 + i]; W[C::W_BD1 + i] = pk[C::db1 + i]; }
-    for (int i = lane; i < NSP; i += 64) W[C::W_BD2 + i] = (i < NS) ? pk[C::db2 + i] : 0.0f;
-    DynInNorm<C> in;
-    DynOutNorm<C> out;
-    in.load(norm, q);
-    out.load(norm, q);
-
-    // ---------------- the tile's initial state and the actions of step 0 ---------------------------
-#pragma unroll
-    for (int j = 0; j < NST; ++j) {
-        const int i = lane + 64 * j;
-        if (i < 16 * NS) ST[i] = (i < nrows * NS) ? r.init_obs[(size_t)b0 * NS + i] : 0.0f;
-    }
-#pragma unroll
-    for (int j = 0; j < NLD; ++j) {
-        const int i = lane + 64 * j;
-        const float a0 = (i < nrows * NA) ? r.actions[(size_t)b0 * NA + i] : 0.0f;
-        if (i < 16 * NA) W[C::W_ACT + i] = fminf(fmaxf(a0, -1.0f), 1.0f);            // np.clip(actions, *bounds), env_helpers.py:599 / :216
-    }
-    int sel = 0;
-    if (!ONE && !r.mean && active) sel = min(max(r.model[b], 0), K - 1);
-    wave_lds_sync();
-    if (wave == 0) {                                                              // row 0 of d_obs = d_init_obs, bit for bit
-#pragma unroll
-        for (int j = 0; j < NST; ++j) {
-            const int i = lane + 64 * j;
-            if (i < nrows * NS) r.obs[(size_t)b0 * NS + i] = ST[i];
-        }
-    }
-    // every global load above is complete before the step loop (rollout_coop_kernel.h: else the wait for the loop-invariant loads lands inside it)
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-
-    for (int t = 0; t < r.T; ++t) {
-        // ---- the action block of step t + 1 (the last step reads its own row again: no branch, nothing out of bounds), issued now and read
-        //      behind the matrix instructions, IN FRONT of this step's stores ----
-        //      Every lane loads (index clamped into the tile's block): a straight-line load the compiler waits for at its use, not in a masked branch.
-        float* ACT = W + ((t & 1) ? W_ACT2 : C::W_ACT);
-        float* ACTN = W + ((t & 1) ? C::W_ACT : W_ACT2);
-        float a_nx[NLD];
-        {
-            const float* __restrict__ an = r.actions + ((size_t)min(t + 1, r.T - 1) * r.B + b0) * NA;
-#pragma unroll
-            for (int j = 0; j < NLD; ++j) a_nx[j] = an[min(lane + 64 * j, nrows * NA - 1)];
-        }
-        // ---- the head: normalise, drop columns, 3 layers (training.py:218-269) ----------------------
-        f32x4 h0[C::DH_CB], h1[C::DH_CB], oa[C::OUT_CB], ob[C::OUT_CB];
-        float xin[C::NIN_KS];
-#pragma unroll
-        for (int s = 0; s < C::NIN_KS; ++s) xin[s] = in.get(ST, NS, ACT, e, s);
-        head.layer0(h0, W + C::W_BD0, xin, ReluBits());
-        head.layer1(h1, W + C::W_BD1, h0, ReluBits());
-        head.layer2(oa, ob, W + C::W_BD2, h1);
-        f32x4 nx[C::OUT_CB];
-#pragma unroll
-        for (int cb = 0; cb < C::OUT_CB; ++cb) {
-            f32x4 o = oa[cb] + ob[cb];
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int dim = 16 * cb + 4 * q + rr;
-                const float sv = (dim < NS) ? ST[e * NS + dim] : 0.0f;
-                o[rr] = out.apply(cb, rr, o[rr], sv);
-            }
-            nx[cb] = o;
-        }
-        if (!ONE) {
-            // ---- get_next_observation (env_helpers.py:617-634): the K heads meet in LDS, every wave selects redundantly ----
-            const int par = t & 1;
-            float* nxt_w = NXT + ((size_t)(par * K + wave) * 16 + e) * NSP;
-#pragma unroll
-            for (int cb = 0; cb < C::OUT_CB; ++cb) *(f32x4*)&nxt_w[16 * cb + 4 * q] = nx[cb];
-            __syncthreads();                                                     // all K heads of step t are in NXT[par]
-            const float* nxt_all = NXT + (size_t)par * K * 16 * NSP;
-#pragma unroll
-            for (int cb = 0; cb < C::OUT_CB; ++cb) {
-                const int off = e * NSP + 16 * cb + 4 * q;
-                if (!r.mean) {
-                    nx[cb] = *(const f32x4*)&nxt_all[(size_t)sel * 16 * NSP + off];
-                } else {
-                    f32x4 m = {0.f, 0.f, 0.f, 0.f};
-                    for (int k = 0; k < K; ++k) m += *(const f32x4*)&nxt_all[(size_t)k * 16 * NSP + off];    // head order, as metrpo_step
-                    nx[cb] = m / (float)K;
-                }
-            }
-        }
-#pragma unroll
-        for (int cb = 0; cb < C::OUT_CB; ++cb)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int dim = 16 * cb + 4 * q + rr;
-                if (dim < NS) NX[e * NS + dim] = nx[cb][rr];
-            }
-        // ---- the prefetched actions become step t + 1's.  The wait for them is the loop's only vmcnt wait; the vector-memory counter is in order, so
-        //      it also covers the stores of step t - 1 -- a whole step old by now -- and none of step t's, which follow below ----
-        //      (the empty statement takes the loaded values on EVERY path: were they read only inside the masked write below, the load could
-        //      still be in flight at the loop's back edge and the compiler would wait for it -- and the stores -- at the top of the next step)
-#pragma unroll
-        for (int j = 0; j < NLD; ++j) asm volatile("" ::"v"(a_nx[j]));
-#pragma unroll
-        for (int j = 0; j < NLD; ++j) {
-            const int i = lane + 64 * j;
-            if (i < 16 * NA) ACTN[i] = (i < nrows * NA) ? fminf(fmaxf(a_nx[j], -1.0f), 1.0f) : 0.0f;
-        }
-        wave_lds_sync();
-        // ---- reward = -cost_np_vec(s, a_clipped, s') (:601) and is_done(s', s') (:603); the env goes on either way ----
-        const float cost = env_cost(ENV, NS, NA, NX + e * NS, ACT + e * NA, 1, 0);
-        const bool dn = env_is_done(ENV, NS, NX + e * NS, 1, 0);
-#pragma unroll
-        for (int j = 0; j < NST; ++j) {
-            const int i = lane + 64 * j;
-            if (i < 16 * NS) ST[i] = NX[i];
-        }
-        wave_lds_sync();
-        if (wave == 0) {
-            float* __restrict__ orow = r.obs + ((size_t)(t + 1) * r.B + b0) * NS;
-#pragma unroll
-            for (int j = 0; j < NST; ++j) {
-                const int i = lane + 64 * j;
-                if (i < nrows * NS) orow[i] = ST[i];
-            }
-            if (q == 0 && active) { const size_t tb = (size_t)t * r.B + b; r.rew[tb] = -cost; r.done[tb] = dn ? 1 : 0; }
-        }
-    }
+    const TileRollK tr = {r.B, r.T, 1, r.init_obs, r.actions, r.head, r.mean, r.model};
+    RactSink<Cfg<ENV, 64, 32>::NS> sink = {r};
+    tile_rollout<ENV, ONE>(lds, tr, K, blockIdx.x * 16, dynp, norm, sink);
 }
 
 // -------------------------------------------------------------------------------------------------
 typedef void (*ract_kernel_t)(RactK, int, const float*, const float*);
 struct RactEntry { int env; ract_kernel_t all, one; int w_sz, nsp; };
-#define RENTRY(ENVID) {ENVID, k_rollout_actions<ENVID, false>, k_rollout_actions<ENVID, true>, ract_wave_floats<ENVID>(), Cfg<ENVID, 64, 32>::NSP}
-static const RactEntry kRact[] = {RENTRY(METRPO_ENV_SWIMMER), RENTRY(METRPO_ENV_HALF_CHEETAH), RENTRY(METRPO_ENV_HOPPER), RENTRY(METRPO_ENV_SNAKE), RENTRY(METRPO_ENV_ANT)};
+#define RENTRY(ENVID) {ENVID, k_rollout_actions<ENVID, false>, k_rollout_actions<ENVID, true>, act_wave_floats<ENVID>(), Cfg<ENVID, 64, 32>::NSP}
+static const RactEntry kRact[] = {FUSED_HEAD_ENVS(RENTRY)};
 
-// the fused kernel holds this context's shape: the fused rollout kernels' shape class with two hidden layers of 64 (*padded = false), or narrower ones
-// through the zero-padded copy d_dyn_pad that metrpo_create made for them (*padded = true); K <= 8 (a wave per head)
-static const RactEntry* ract_entry(const metrpo_ctx* c, bool* padded) {
+// ---- what the host sides of the fused head kernels share (metrpo_internal.h) ----
+bool fused_head_class(const metrpo_ctx* c, int k_cap, bool* padded) {
     const ProblemDesc& pd = c->pd;
-    if (pd.K > 8) return nullptr;
+    if (pd.K > k_cap) return false;
     if (mfma_shape_config(c) >= 0 && pd.dyn.dims[1] == 64 && pd.dyn.dims[2] == 64) *padded = false;
     else if (c->coop_pad_cfg >= 0) *padded = true;
-    else return nullptr;
-    for (const RactEntry& en : kRact)
-        if (en.env == pd.env) return &en;
-    return nullptr;
+    else return false;
+    return true;
+}
+int fused_head_dyn(metrpo_ctx* c, bool padded, hipStream_t st, const float** dyn) {
+    *dyn = c->d_dyn.p;
+    if (padded) { const int rc = launch_pad_dyn(c, st); if (rc) return rc; *dyn = c->d_dyn_pad.p; }
+    return METRPO_OK;
+}
+int allow_dynamic_lds(metrpo_ctx* c, const void* kernel, size_t bytes) {
+    if (bytes > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return METRPO_OK;
 }
 
 static int launch_rollout_actions_fused(metrpo_ctx* c, const RactEntry& en, bool padded, const metrpo_rollout_actions_args* a, hipStream_t st) {
@@ -207,13 +96,13 @@ static int launch_rollout_actions_fused(metrpo_ctx* c, const RactEntry& en, bool
     else if (a->sam_mode == METRPO_SAM_EPS_RAND && a->uniform_model >= 0) { one = true; r.head = a->uniform_model; }
     else if (a->sam_mode == METRPO_SAM_EPS_RAND) { r.mean = 0; r.model = a->d_model; }
     else r.mean = 1;
-    const float* dyn = c->d_dyn.p;
-    if (padded) { const int rc = launch_pad_dyn(c, st); if (rc) return rc; dyn = c->d_dyn_pad.p; }
+    const float* dyn;
+    { const int rc = fused_head_dyn(c, padded, st, &dyn); if (rc) return rc; }
     const int grid = (a->B + 15) / 16;
     const ract_kernel_t kern = one ? en.one : en.all;
     const int nw = one ? 1 : K;
-    const size_t sh = sizeof(float) * ((size_t)nw * en.w_sz + (one ? 0 : 2 * (size_t)K * 16 * en.nsp));
-    if (sh > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+    const size_t sh = sizeof(float) * ((size_t)nw * en.w_sz + (one ? 0 : head_exchange_floats(K, en.nsp)));
+    { const int rc = allow_dynamic_lds(c, (const void*)kern, sh); if (rc) return rc; }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(nw * 64), sh, st, r, K, dyn, c->d_norm.p);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
@@ -224,7 +113,7 @@ int run_rollout_actions(metrpo_ctx* c, const metrpo_rollout_actions_args* a, hip
     const int sam = a->sam_mode;
     bool padded = false;
     const RactEntry* en = nullptr;
-    if (!a->force_step_loop && (sam == METRPO_SAM_MODEL_MEAN || sam == METRPO_SAM_EPS_RAND || sam == METRPO_SAM_ONE_MODEL)) en = ract_entry(c, &padded);
+    if (!a->force_step_loop && (sam == METRPO_SAM_MODEL_MEAN || sam == METRPO_SAM_EPS_RAND || sam == METRPO_SAM_ONE_MODEL)) en = fused_head_entry(kRact, c, 8, &padded);      // a wave per head
     if (en != nullptr) {
         const int rc = launch_rollout_actions_fused(c, *en, padded, a, st);
         if (rc == METRPO_OK) c->last_ract_kernel = 1;

@@ -2,10 +2,11 @@
 // (head k, candidate b) the loop of build_policy_graph's cost sum, model_based_rl.py:122-141 (head fixed for the whole trajectory, the done mask updated
 // AFTER the step's cost, :134-137), under SUPPLIED actions (clipped as VecSimpleEnv.step does, env_helpers.py:599) instead of the policy's.
 //
-// Fused kernel (k_score_actions): the ONE-head body of k_rollout_actions (rollout_actions.hip) without its stores.
+// Fused kernel (k_score_actions): the ONE-head body of k_rollout_actions (rollout_actions.hip) without its stores -- dyn_tile_step.h's tile_rollout
+// with a sink that sums instead of storing.
 //   * one wave owns one (16-candidate tile, head) pair for all T steps, on the shared head of dyn_head_mfma.h: weight fragments register-resident
 //     (swimmer 92, Ant 132 registers), biases and the tile's state in the wave's LDS, every activation in registers, no barrier.  The statements of a
-//     step -- normalise, three layers, de-normalise, env_cost / env_is_done on the LDS rows -- are that kernel's, so s' and r carry its bits.
+//     step -- normalise, three layers, de-normalise, env_cost / env_is_done on the LDS rows -- are that kernel's own, so s' and r carry its bits.
 //   * PACKING: one wave per workgroup on a (tiles, K) grid.  The (tile, head) pairs share nothing but read-only inputs, so a workgroup of several waves
 //     would buy no exchange and no reuse; it would only tie the waves' placement together (a workgroup starts when ALL its waves fit one CU, and its LDS
 //     and registers are held until the slowest tile of it ends).  One-wave workgroups let the dispatcher fill whatever SIMD has the registers free, which
@@ -22,7 +23,7 @@
 // applies the same float64 sum to the workspace's rew / done.
 //
 // d_ret_mean / d_ret_std: k_sact_aggregate, a second small launch over d_ret, one thread per candidate adding in head order; no workgroup waits on another.
-#include "dyn_head_mfma.h"
+#include "dyn_tile_step.h"
 #include <algorithm>
 #include <cmath>
 
@@ -47,108 +48,30 @@ struct SactSum {
     }
 };
 
-// per-wave LDS (floats): ST | NX | ACT | dynamics biases | second ACT (k_rollout_actions' layout)
-template <int ENV> constexpr int sact_wave_floats() { return Cfg<ENV, 64, 32>::W_BP0 + al4(16 * Cfg<ENV, 64, 32>::NA); }
+// tile_rollout's sink that stores nothing inside the step loop: every lane carries its env's sum, quad 0 writes d_ret / d_len once behind the loop
+struct SactSink {
+    const SactK& r;
+    SactSum acc;
+    __device__ __forceinline__ void start(const float*, int, int, int) const {}
+    __device__ __forceinline__ void step(int, const float*, float cost, bool dn, int, int, int) { acc.step(-cost, dn, r.gamma, r.stop); }
+    __device__ __forceinline__ void finish(int k, int b0, int lane) const {
+        const int b = b0 + (lane & 15);
+        if ((lane >> 4) == 0 && b < r.B) {                       // rounded to fp32 once, here
+            const size_t kb = (size_t)k * r.B + b;
+            r.ret[kb] = (float)acc.sum;
+            if (r.len != nullptr) r.len[kb] = acc.n;
+        }
+    }
+};
 
 template <int ENV>
 __global__ void __launch_bounds__(64) k_score_actions(SactK r, const float* __restrict__ dynp, const float* __restrict__ norm) {
-    using C = Cfg<ENV, 64, 32>;
-    constexpr int NS = C::NS, NA = C::NA;
-    constexpr int W_ACT2 = C::W_BP0;
-    constexpr int NLD = cdiv(16 * NA, 64), NST = cdiv(16 * NS, 64);
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int lane = threadIdx.x & 63;
-    const int e = lane & 15, q = lane >> 4;
-    const int b0 = blockIdx.x * 16, b = b0 + e, k = blockIdx.y;
-    const bool active = b < r.B;
-    const int nrows = min(16, r.B - b0);                      // rows of this tile inside the batch
-    float* W = lds;
-    float* ST = W + C::W_ST;  float* NX = W + C::W_NX;
-
-    // ---------------- one-time: weight fragments -> registers, biases -> LDS ----------------------
-    const float* __restrict__ pk = dynp + (size_t)k * C::PD;
-    DynHeadFrags<C> head;
-    head.load(pk, e, q);
-    for (int i = lane; i < C::BD; i += 64) { W[C::W_BD0 + i] = pk[C::db0 + i]; W[C::W_BD1 + i] = pk[C::db1 + i]; }
-    for (int i = lane; i < C::NSP; i += 64) W[C::W_BD2 + i] = (i < NS) ? pk[C::db2 + i] : 0.0f;
-    DynInNorm<C> in;
-    DynOutNorm<C> out;
-    in.load(norm, q);
-    out.load(norm, q);
-
-    // ---------------- the tile's start rows (gathered per row) and the actions of step 0 -----------
-#pragma unroll
-    for (int j = 0; j < NST; ++j) {
-        const int i = lane + 64 * j;
-        const int row = i / NS, col = i - row * NS;
-        if (i < 16 * NS) ST[i] = (row < nrows) ? r.init_obs[(size_t)((b0 + row) / r.per) * NS + col] : 0.0f;
-    }
-#pragma unroll
-    for (int j = 0; j < NLD; ++j) {
-        const int i = lane + 64 * j;
-        const float a0 = (i < nrows * NA) ? r.actions[(size_t)b0 * NA + i] : 0.0f;
-        if (i < 16 * NA) W[C::W_ACT + i] = fminf(fmaxf(a0, -1.0f), 1.0f);            // np.clip(actions, *bounds), env_helpers.py:599
-    }
-    wave_lds_sync();
-    // every global load above is complete before the step loop (rollout_coop_kernel.h: else the wait for the loop-invariant loads lands inside it)
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-
-    SactSum acc;
-    for (int t = 0; t < r.T; ++t) {
-        // ---- the action block of step t + 1 (the last step reads its own row again: no branch, nothing out of bounds), issued now and read
-        //      behind the matrix instructions.  Every lane loads (index clamped into the tile's block) ----
-        float* ACT = W + ((t & 1) ? W_ACT2 : C::W_ACT);
-        float* ACTN = W + ((t & 1) ? C::W_ACT : W_ACT2);
-        float a_nx[NLD];
-        {
-            const float* __restrict__ an = r.actions + ((size_t)min(t + 1, r.T - 1) * r.B + b0) * NA;
-#pragma unroll
-            for (int j = 0; j < NLD; ++j) a_nx[j] = an[min(lane + 64 * j, nrows * NA - 1)];
-        }
-        // ---- the head: normalise, drop columns, 3 layers (training.py:218-269); the statements of k_rollout_actions ----
-        f32x4 h0[C::DH_CB], h1[C::DH_CB], oa[C::OUT_CB], ob[C::OUT_CB];
-        float xin[C::NIN_KS];
-#pragma unroll
-        for (int s = 0; s < C::NIN_KS; ++s) xin[s] = in.get(ST, NS, ACT, e, s);
-        head.layer0(h0, W + C::W_BD0, xin, ReluBits());
-        head.layer1(h1, W + C::W_BD1, h0, ReluBits());
-        head.layer2(oa, ob, W + C::W_BD2, h1);
-#pragma unroll
-        for (int cb = 0; cb < C::OUT_CB; ++cb) {
-            f32x4 o = oa[cb] + ob[cb];
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int dim = 16 * cb + 4 * q + rr;
-                const float sv = (dim < NS) ? ST[e * NS + dim] : 0.0f;
-                o[rr] = out.apply(cb, rr, o[rr], sv);
-                if (dim < NS) NX[e * NS + dim] = o[rr];
-            }
-        }
-        // ---- the prefetched actions become step t + 1's (the empty statement takes the loaded values on EVERY path, k_rollout_actions) ----
-#pragma unroll
-        for (int j = 0; j < NLD; ++j) asm volatile("" ::"v"(a_nx[j]));
-#pragma unroll
-        for (int j = 0; j < NLD; ++j) {
-            const int i = lane + 64 * j;
-            if (i < 16 * NA) ACTN[i] = (i < nrows * NA) ? fminf(fmaxf(a_nx[j], -1.0f), 1.0f) : 0.0f;
-        }
-        wave_lds_sync();
-        // ---- reward = -cost_np_vec(s, a_clipped, s') (:601) and is_done(s', s') (:603) into the lane's own sum ----
-        const float cost = env_cost(ENV, NS, NA, NX + e * NS, ACT + e * NA, 1, 0);
-        const bool dn = env_is_done(ENV, NS, NX + e * NS, 1, 0);
-        acc.step(-cost, dn, r.gamma, r.stop);
-#pragma unroll
-        for (int j = 0; j < NST; ++j) {
-            const int i = lane + 64 * j;
-            if (i < 16 * NS) ST[i] = NX[i];
-        }
-        wave_lds_sync();
-    }
-    if (q == 0 && active) {                                   // rounded to fp32 once, here
-        const size_t kb = (size_t)k * r.B + b;
-        r.ret[kb] = (float)acc.sum;
-        if (r.len != nullptr) r.len[kb] = acc.n;
-    }
+    const int b0 = blockIdx.x * 16, k = blockIdx.y;
+    const TileRollK tr = {r.B, r.T, r.per, r.init_obs, r.actions, k, 0, nullptr};
+    SactSink sink = {r};
+    tile_rollout<ENV, true>(lds, tr, 1, b0, dynp, norm, sink);
+    sink.finish(k, b0, threadIdx.x & 63);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -198,28 +121,15 @@ __global__ void __launch_bounds__(256) k_sact_aggregate(const float* __restrict_
 // -------------------------------------------------------------------------------------------------
 typedef void (*sact_kernel_t)(SactK, const float*, const float*);
 struct SactEntry { int env; sact_kernel_t kern; int w_sz; };
-#define SENTRY(ENVID) {ENVID, k_score_actions<ENVID>, sact_wave_floats<ENVID>()}
-static const SactEntry kSact[] = {SENTRY(METRPO_ENV_SWIMMER), SENTRY(METRPO_ENV_HALF_CHEETAH), SENTRY(METRPO_ENV_HOPPER), SENTRY(METRPO_ENV_SNAKE), SENTRY(METRPO_ENV_ANT)};
-
-// the shape class of rollout_actions.hip's ract_entry() WITHOUT its K <= 8 (no workgroup holds a wave per head here): the fused rollout kernels' shapes
-// with two hidden layers of 64 (*padded = false), or narrower ones through the zero-padded copy d_dyn_pad (*padded = true)
-static const SactEntry* sact_entry(const metrpo_ctx* c, bool* padded) {
-    const ProblemDesc& pd = c->pd;
-    if (pd.K > 65535) return nullptr;                            // gridDim.y
-    if (mfma_shape_config(c) >= 0 && pd.dyn.dims[1] == 64 && pd.dyn.dims[2] == 64) *padded = false;
-    else if (c->coop_pad_cfg >= 0) *padded = true;
-    else return nullptr;
-    for (const SactEntry& en : kSact)
-        if (en.env == pd.env) return &en;
-    return nullptr;
-}
+#define SENTRY(ENVID) {ENVID, k_score_actions<ENVID>, act_wave_floats<ENVID>()}
+static const SactEntry kSact[] = {FUSED_HEAD_ENVS(SENTRY)};
 
 static int launch_sact_fused(metrpo_ctx* c, const SactEntry& en, bool padded, const metrpo_score_actions_args* a, hipStream_t st) {
     SactK r = {};
     r.B = a->B; r.T = a->T; r.per = a->B / a->S; r.stop = a->stop_at_done ? 1 : 0; r.gamma = a->gamma;
     r.init_obs = a->d_init_obs; r.actions = a->d_actions; r.ret = a->d_ret; r.len = a->d_len;
-    const float* dyn = c->d_dyn.p;
-    if (padded) { const int rc = launch_pad_dyn(c, st); if (rc) return rc; dyn = c->d_dyn_pad.p; }
+    const float* dyn;
+    { const int rc = fused_head_dyn(c, padded, st, &dyn); if (rc) return rc; }
     const size_t sh = sizeof(float) * (size_t)en.w_sz;
     hipLaunchKernelGGL(en.kern, dim3((a->B + 15) / 16, c->pd.K), dim3(64), sh, st, r, dyn, c->d_norm.p);
     HIP_TRY(c, hipGetLastError());
@@ -264,7 +174,7 @@ static int launch_sact_generic(metrpo_ctx* c, const metrpo_score_actions_args* a
 
 int run_score_actions(metrpo_ctx* c, const metrpo_score_actions_args* a, hipStream_t st) {
     bool padded = false;
-    const SactEntry* en = a->force_generic ? nullptr : sact_entry(c, &padded);
+    const SactEntry* en = a->force_generic ? nullptr : fused_head_entry(kSact, c, 65535, &padded);      // the heads are gridDim.y: no workgroup holds a wave per head
     const int rc = en != nullptr ? launch_sact_fused(c, *en, padded, a, st) : launch_sact_generic(c, a, st);
     if (rc) return rc;
     if (a->d_ret_mean != nullptr || a->d_ret_std != nullptr) {
