@@ -788,6 +788,51 @@ typedef struct {
 int32_t metrpo_score_actions(metrpo_ctx* ctx, const metrpo_score_actions_args* args, void* stream);
 int32_t metrpo_last_score_actions_kernel(const metrpo_ctx* ctx);   /* -1 none yet, 0 generic, 1 fused */
 
+/* ---- the GRADIENT of every head's predicted return with respect to the supplied action sequences: first-order information for planners that refine
+ * shooting candidates (metrpo_bptt_grad gives d/d theta under the policy's own actions, not this).  Additions to ABI 4: no struct above changes, no option
+ * key is added, METRPO_ABI_VERSION stays.
+ * Per (head k, candidate b), R = ret[k][b] EXACTLY as metrpo_score_actions defines it above -- the loop of model_based_rl.py:122-141 with the head fixed,
+ * the actions clipped as env_helpers.py:599 does, the done mask updated after the step's cost (:134-137) -- i.e. R = -sum_t w_t c_t with c = cost_tf and
+ * w_t = gamma^t alive_t.  SIGN: everything here is the gradient of the RETURN, the ascent direction (the negative of the BPTT sweep's cost gradient).
+ *   grad[k][t][b][:] = dR / d a_t          with respect to the UNCLIPPED action
+ *   lam0[k][b][:]    = dR / d s_0
+ *   grad_mean        = (grad_0 + ... + grad_K-1) / K     from the stored fp32 values, summed in head order
+ * Reverse recursion from lambda_T = 0, F the head's Jacobian including both normalisers, the column drop and the residual identity (training.py:218-269):
+ *   G        = lambda_t+1 - w_t dc/dx_next
+ *   gU       = -w_t dc/du + (action rows of F^T G)
+ *   lambda_t = G + (state rows of F^T G)
+ * Conventions, all of them the BPTT sweep's (metrpo_bptt_grad): the clip gate passes the gradient iff -1 <= a <= 1 (tf.clip_by_value); relu'(h) = [h > 0];
+ * the half-cheetah reward clip passes inside [-10, 10]; hopper's max terms pass on strict inequality; the alive mask is a constant of the differentiation
+ * (TF's cast of a comparison); gamma^t is carried in float64 by repeated multiplication and rounded to fp32 when it becomes a weight; a step that is not
+ * counted has weight 0.  Steps behind a candidate's last counted step read 0, and so does a clipped action.  ret / len are metrpo_score_actions'.
+ * Which kernel runs (metrpo_last_score_actions_grad_kernel: -1 none yet, 0 generic, 1 fused):
+ *   fused (score_actions_grad.hip: per chunk two stream-ordered launches -- the forward sweep is metrpo_score_actions' fused kernel with the states and
+ *     weights stored, the reverse sweep runs four 16-candidate tiles of one head per workgroup on transposed matrix-instruction chains) -- exactly
+ *     metrpo_score_actions' fused shape class: swimmer, half-cheetah, Ant, hopper, snake with two relu hidden layers of 64 or narrower, any K.
+ *   generic (one thread per (candidate, head), activations in LDS) -- everything else: humanoid, hidden widths above 64, tanh layers, other depths.
+ * The two agree to rounding, not bits.  The workspace (every state and weight of a chunk of candidates) is ctx-owned and stays within 2^26 floats by
+ * chunking over candidates; chunk > 0 sets the candidates per pass instead.  Chunking changes no bit of any output.  No atomics: repeated calls are
+ * bit-identical.  Stream-ordered, neither frees nor synchronises.  Needs metrpo_set_dynamics only.  Leaves theta, both Adam states, the Philox state, the
+ * ensemble, metrpo_last_rollout_kernel, metrpo_last_rollout_actions_kernel, metrpo_last_score_actions_kernel and metrpo_last_disagreement_kernel untouched.
+ * B == 0 or T == 0: METRPO_OK, nothing written.  METRPO_ENULL: ctx, args, d_init_obs, d_actions, d_grad; METRPO_EINVAL: B < 0, T < 0, S < 1, B % S != 0,
+ * gamma not finite, chunk < 0; METRPO_ESTATE before metrpo_set_dynamics. */
+typedef struct {
+    int32_t B, T, S;            /* as metrpo_score_actions_args */
+    int32_t stop_at_done;
+    int32_t force_generic;
+    int32_t chunk;              /* candidates per pass of the workspace; 0: the library's rule (the workspace within 2^26 floats) */
+    double  gamma;
+    const float* d_init_obs;    /* [S][ns] */
+    const float* d_actions;     /* [T][B][na] UNCLIPPED; never written */
+    float*   d_grad;            /* [K][T][B][na] required */
+    float*   d_ret;             /* optional [K][B] */
+    int32_t* d_len;             /* optional [K][B] */
+    float*   d_grad_mean;       /* optional [T][B][na] */
+    float*   d_lam0;            /* optional [K][B][ns] */
+} metrpo_score_actions_grad_args;
+int32_t metrpo_score_actions_grad(metrpo_ctx* ctx, const metrpo_score_actions_grad_args* args, void* stream);
+int32_t metrpo_last_score_actions_grad_kernel(const metrpo_ctx* ctx);   /* -1 none yet, 0 generic, 1 fused */
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,8 +28,10 @@ from . import model_error
 from .model_error import evaluate_model_predictions, get_error_distribution, open_loop_predictions, ensemble_disagreement
 from . import planning
 from .planning import score_action_sequences, plan_random_shooting, plan_cem, ShootingController
+from .planning import engine_grad_scorer, aggregate_heads_grad, refine_actions, plan_cem_gd
 
 __all__ = ['Engine', 'Trajectory', 'xavier_policy_theta', 'Comm', 'NeuralNetEnv', 'VecSimpleEnv', 'InitStatePool',
            'Box', 'EnvSpec', 'GaussianMLPPolicy', 'LinearFeatureBaseline', 'VectorizedSampler', 'BaseSampler',
            'DevicePaths', 'ConjugateGradientOptimizer', 'BatchPolopt', 'NPO', 'TRPO', 'VPG', 'PPO', 'FirstOrderOptimizer', 'AdamOptimizer', 'LBFGS', 'svg', 'SVG', 'rollout_triplets', 'pack_rollouts', 'early_stop', 'dynamics_training', 'from_params', 'shapes_from_params', 'model_error', 'evaluate_model_predictions', 'get_error_distribution', 'open_loop_predictions', 'ensemble_disagreement',
-           'planning', 'score_action_sequences', 'plan_random_shooting', 'plan_cem', 'ShootingController']
+           'planning', 'score_action_sequences', 'plan_random_shooting', 'plan_cem', 'ShootingController',
+           'engine_grad_scorer', 'aggregate_heads_grad', 'refine_actions', 'plan_cem_gd']

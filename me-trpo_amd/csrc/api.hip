@@ -1085,6 +1085,22 @@ extern "C" int32_t metrpo_score_actions(metrpo_ctx* c, const metrpo_score_action
 }
 extern "C" int32_t metrpo_last_score_actions_kernel(const metrpo_ctx* c) { return c ? c->last_sact_kernel : METRPO_ENULL; }
 
+// ---- gradient of every head's return with respect to the supplied action sequences (score_actions_grad.hip) ----
+extern "C" int32_t metrpo_score_actions_grad(metrpo_ctx* c, const metrpo_score_actions_grad_args* a, void* stream) {
+    TraceRange trace_("metrpo:score_actions_grad (per-head return gradients of candidate action sequences)");
+    if (!c) return METRPO_ENULL;
+    if (!a) return set_err(c, METRPO_ENULL, "score_actions_grad: args NULL");
+    NEED_DYN(c);
+    if (a->B < 0 || a->T < 0) return set_err(c, METRPO_EINVAL, "score_actions_grad: bad B/T");
+    if (a->S < 1 || a->B % a->S != 0) return set_err(c, METRPO_EINVAL, "score_actions_grad: S = " + std::to_string(a->S) + " must be at least 1 and divide B = " + std::to_string(a->B));
+    if (!std::isfinite(a->gamma)) return set_err(c, METRPO_EINVAL, "score_actions_grad: gamma is not finite");
+    if (a->chunk < 0) return set_err(c, METRPO_EINVAL, "score_actions_grad: chunk must not be negative");
+    if (a->B == 0 || a->T == 0) return METRPO_OK;
+    if (!a->d_init_obs || !a->d_actions || !a->d_grad) return set_err(c, METRPO_ENULL, "score_actions_grad: required pointer is NULL");
+    return run_score_actions_grad(c, a, (hipStream_t)stream);
+}
+extern "C" int32_t metrpo_last_score_actions_grad_kernel(const metrpo_ctx* c) { return c ? c->last_sagr_kernel : METRPO_ENULL; }
+
 // ---- 'svg' policy update: value gradients along recorded rollouts (svg_utils.py:12-66; svg.hip) ----
 static int svg_check(metrpo_ctx* c, const metrpo_svg_args* a) {
     if (!a) return set_err(c, METRPO_ENULL, "svg: args NULL");

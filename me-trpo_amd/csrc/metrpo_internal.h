@@ -126,7 +126,8 @@ struct metrpo_ctx {
     int last_dis_kernel = -1;                             // metrpo_ensemble_disagreement (disagreement.hip): -1 none yet, 0 generic, 1 fused
     DevBuf<void> d_dis; int dis_per_cu = 0;               // ... its workspace (generic: every head's next state | metrpo_step's s_next, reward, done; either path: the scores when only d_sums is asked for) | workgroups of the fused kernel per CU (0: not asked yet)
     int last_sact_kernel = -1; DevBuf<void> d_sact;       // metrpo_score_actions (score_actions.hip): -1 none yet, 0 generic, 1 fused | the generic path's chunk workspace (obs | rew | done | the chunk's actions)
-    DevBuf<void> d_svg; int last_svg_path = -1;          // svg.hip: workspace of metrpo_svg_grad / _update (zeroed copy of the rollouts | mean-adjoint | F | Pi | chunk buffers | lambda_0 | gradient) | -1 none yet, 1 generic, 2 GEMM
+    int last_sagr_kernel = -1; DevBuf<void> d_sagr;       // metrpo_score_actions_grad (score_actions_grad.hip): -1 none yet, 0 generic, 1 fused | a chunk's states and weights (XS | WT)
+    DevBuf<void> d_svg; int last_svg_path = -1;         // svg.hip: workspace of metrpo_svg_grad / _update (zeroed copy of the rollouts | mean-adjoint | F | Pi | chunk buffers | lambda_0 | gradient) | -1 none yet, 1 generic, 2 GEMM
     int coop_no_split = 0;                                // switch (metrpo_set_coop_split): 1 keeps the 4-wave form of the cooperative kernel where the head-split form would run
     int last_coop_waves = 0;                              // waves per workgroup of the last cooperative launch: 4, or 8 (head-split form); diagnostics (metrpo_debug_coop_waves)
     int last_rollout_kernel = -1;                         // which kernel family the last metrpo_rollout ran on: 0 generic, 1 head-per-wave MFMA, 2 cooperative MFMA, 3 step-wise GEMM, 4 resident
@@ -464,6 +465,8 @@ int run_rollout_actions(metrpo_ctx*, const metrpo_rollout_actions_args*, hipStre
 int run_disagreement(metrpo_ctx*, const metrpo_disagreement_args*, hipStream_t);
 // score_actions.hip: the body of metrpo_score_actions (arguments checked by the entry point; B, T > 0, B % S == 0)
 int run_score_actions(metrpo_ctx*, const metrpo_score_actions_args*, hipStream_t);
+// score_actions_grad.hip: the body of metrpo_score_actions_grad (arguments checked by the entry point; B, T > 0, B % S == 0, chunk >= 0)
+int run_score_actions_grad(metrpo_ctx*, const metrpo_score_actions_grad_args*, hipStream_t);
 // svg.hip: the body of metrpo_svg_grad / metrpo_svg_update (arguments checked by the entry points); update: the SGD step with `lr` on the ctx theta
 int run_svg(metrpo_ctx*, const metrpo_svg_args*, double lr, bool update, hipStream_t);
 int launch_subsample(metrpo_ctx*, const metrpo_batch* b, const int32_t* d_idx, long long m, double inv_n_global, metrpo_batch* out, double* d_valid_count, hipStream_t);

@@ -458,6 +458,59 @@ class Engine(object):
         the step loop of rollout_actions, then a reduction kernel); None before the first."""
         return {0: 'generic', 1: 'fused'}.get(int(lib.metrpo_last_score_actions_kernel(self._ctx)))
 
+    # ------------------------------------------------------------------ gradient of every head's return with respect to the candidate actions
+    SCORE_ACTIONS_GRAD_OUTPUTS = ('grad', 'ret', 'len', 'grad_mean', 'lam0')
+
+    def score_actions_grad(self, init_obs, actions, gamma=1.0, stop_at_done=True, want=('grad', 'ret'), force_generic=False, chunk=0, out=None):
+        """metrpo_score_actions_grad: the gradient of each head's predicted return (score_actions' ret) with respect to the UNCLIPPED candidate actions
+        -- the ascent direction -- for init_obs [S, ns] or [ns] and actions [T, B, na] as in score_actions.  want: any of grad [K, T, B, na] (always
+        computed; 0 where the action is clipped and behind a candidate's last counted step), ret [K, B], len [K, B] int32, grad_mean [T, B, na] (the
+        heads' mean, summed in head order), lam0 [K, B, ns] (the gradient with respect to the start state).  chunk: candidates per pass of the
+        workspace (0: the library's rule); it changes no bit of any output.  -> dict of device tensors, nothing synchronised.  out: dict name ->
+        tensor to write into instead (contiguous, at least that large)."""
+        dev = self.device
+        init_obs = _f32(init_obs, dev)
+        if init_obs.dim() == 1:
+            init_obs = init_obs.unsqueeze(0)
+        if init_obs.dim() != 2 or init_obs.shape[1] != self.ns or init_obs.shape[0] < 1:
+            raise ValueError("init_obs: expected [S, %d] or [%d], got %s" % (self.ns, self.ns, tuple(init_obs.shape)))
+        S = init_obs.shape[0]
+        actions = _f32(actions, dev)
+        if actions.dim() != 3 or actions.shape[2] != self.na or actions.shape[1] % S != 0:
+            raise ValueError("actions: expected [T, B, %d] with B a multiple of %d, got %s" % (self.na, S, tuple(actions.shape)))
+        T, B = int(actions.shape[0]), int(actions.shape[1])
+        want = (want,) if isinstance(want, str) else tuple(want)
+        for w in want:
+            if w not in self.SCORE_ACTIONS_GRAD_OUTPUTS:
+                raise ValueError("want: %r is none of %s" % (w, self.SCORE_ACTIONS_GRAD_OUTPUTS))
+        if not np.isfinite(float(gamma)):
+            raise ValueError("gamma must be finite")
+        if int(chunk) < 0:
+            raise ValueError("chunk must not be negative")
+        shapes = {'grad': (self.K, T, B, self.na), 'ret': (self.K, B), 'len': (self.K, B), 'grad_mean': (T, B, self.na), 'lam0': (self.K, B, self.ns)}
+        res = {}
+        for w in ('grad',) + tuple(x for x in want if x != 'grad'):
+            dt = torch.int32 if w == 'len' else torch.float32
+            if out is not None and w in out:
+                t = out[w]
+                assert t.dtype == dt and t.is_contiguous() and t.device == dev and t.numel() >= int(np.prod(shapes[w], dtype=np.int64))
+            else:
+                t = torch.empty(shapes[w], dtype=dt, device=dev)
+            res[w] = t
+        a = _lib.ScoreActionsGradArgs()
+        a.B, a.T, a.S, a.stop_at_done, a.force_generic, a.chunk, a.gamma = B, T, S, int(bool(stop_at_done)), int(bool(force_generic)), int(chunk), float(gamma)
+        a.d_init_obs, a.d_actions = init_obs.data_ptr(), actions.data_ptr()
+        for w in self.SCORE_ACTIONS_GRAD_OUTPUTS:
+            setattr(a, 'd_' + w, res[w].data_ptr() if w in res else None)
+        self._chk(lib.metrpo_score_actions_grad(self._ctx, C.byref(a), self._stream()))
+        self._sag_keep = (init_obs, actions)                                       # alive until the stream has consumed them
+        return res
+
+    def last_score_actions_grad_kernel(self):
+        """Path the last score_actions_grad() of this engine took: 'fused' (score_actions_grad.hip: a forward and a reverse launch per chunk on the
+        matrix instructions), 'generic' (one thread per (candidate, head)); None before the first."""
+        return {0: 'generic', 1: 'fused'}.get(int(lib.metrpo_last_score_actions_grad_kernel(self._ctx)))
+
     # ------------------------------------------------------------------ fused rollout
     def rollout(self, B, T, H, sam_mode, pool, determ=False, eval_all_heads=True, seed=0, stream_offset=0,
                 eps=None, model_idx=None, sel_noise=None, reset_idx=None, reset_model=None, out=None,

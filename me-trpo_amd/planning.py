@@ -6,7 +6,12 @@ Every function takes `scorer=` in place of the engine's own: any callable (actio
 from init[b // (B // S)].  With a scorer the engine may be None and the logic runs on whatever device the states live on (then pass na=).
 
 Layouts: states [S, ns]; a batch of candidates is [S, N, T, na] towards the caller (trajectory-major, as open_loop_predictions) and [T, S * N, na]
-towards the device, candidate b = s * N + n."""
+towards the device, candidate b = s * N + n.
+
+First-order refinement (Grad-CEM / CEM-GD style): Engine.score_actions_grad / metrpo_score_actions_grad gives the gradient of every head's return with
+respect to the candidates in one call; refine_actions runs projected gradient ascent on a batch of candidates with it, plan_cem_gd refines CEM's elites
+(or all candidates) before each refit.  These take `grad_scorer=` as the others take `scorer=`: any callable
+(actions [T, B, na], init [S, ns]) -> (ret [K, B], grad [K, T, B, na])."""
 import numpy as np
 import torch
 
@@ -28,6 +33,35 @@ def aggregate_heads(ret, aggregate='mean'):
         raise ValueError("aggregate: %r is none of 'mean', 'min', ('pessimistic', beta)" % (aggregate,))
     if isinstance(aggregate, (tuple, list)) and len(aggregate) == 2 and aggregate[0] == 'pessimistic':
         return ret.mean(dim=0) - float(aggregate[1]) * ret.std(dim=0, unbiased=False)
+    raise ValueError("aggregate: %r is none of 'mean', 'min', ('pessimistic', beta)" % (aggregate,))
+
+
+def engine_grad_scorer(engine, gamma=1.0, stop_at_done=True, force_generic=False):
+    """The engine's own gradient scorer: (actions [T, B, na], init [S, ns]) -> (ret [K, B], grad [K, T, B, na]), one metrpo_score_actions_grad call,
+    nothing synchronised."""
+    def grad_scorer(actions, init):
+        out = engine.score_actions_grad(init, actions, gamma=gamma, stop_at_done=stop_at_done, want=('grad', 'ret'), force_generic=force_generic)
+        return out['ret'], out['grad']
+    return grad_scorer
+
+
+def aggregate_heads_grad(ret, grad, aggregate='mean'):
+    """ret [K, B], grad [K, T, B, na] (grad[k] the gradient of ret[k]) -> [T, B, na]: the gradient of aggregate_heads(ret, aggregate) with respect to
+    the candidates.  'mean': the head mean; 'min': the argmin head's gradient; ('pessimistic', beta): sum_k (1/K - beta (r_k - mean) / (K std)) g_k,
+    the std term dropped where std = 0."""
+    K = ret.shape[0]
+    if isinstance(aggregate, str):
+        if aggregate == 'mean':
+            return grad.mean(dim=0)
+        if aggregate == 'min':
+            idx = ret.argmin(dim=0)
+            return grad.gather(0, idx.view(1, 1, -1, 1).expand(1, grad.shape[1], grad.shape[2], grad.shape[3]))[0]
+        raise ValueError("aggregate: %r is none of 'mean', 'min', ('pessimistic', beta)" % (aggregate,))
+    if isinstance(aggregate, (tuple, list)) and len(aggregate) == 2 and aggregate[0] == 'pessimistic':
+        dev = ret - ret.mean(dim=0, keepdim=True)
+        sd = ret.std(dim=0, unbiased=False, keepdim=True)
+        coef = 1.0 / K - float(aggregate[1]) * torch.where(sd > 0, dev / (K * torch.where(sd > 0, sd, torch.ones_like(sd))), torch.zeros_like(dev))
+        return (coef.unsqueeze(1).unsqueeze(-1) * grad).sum(dim=0)
     raise ValueError("aggregate: %r is none of 'mean', 'min', ('pessimistic', beta)" % (aggregate,))
 
 
@@ -146,15 +180,154 @@ def plan_cem(engine, states, horizon, n_candidates, n_elites, n_iters, init_mean
     return dict(actions=tm(mean[:, :, 0]), std=tm(std[:, :, 0]), best_actions=tm(best_actions), best_score=best_score, history=history, elites=idx)
 
 
+def _from_device_major(x, S, N):
+    """[T, S * N, na] -> [S, N, T, na]"""
+    T, _, na = x.shape
+    return x.reshape(T, S, N, na).permute(1, 2, 0, 3).contiguous()
+
+
+def _refine(grad_scorer, states, a, n_steps, lr, optimizer, betas, eps, aggregate):
+    """refine_actions on device-major candidates a [T, B, na] -> (best [T, B, na], best_score [B], last [T, B, na], last_score [B], first_score [B])"""
+    lr, b1, b2, eps = float(lr), float(betas[0]), float(betas[1]), float(eps)
+    m = v = None
+    best = best_score = first_score = None
+    for it in range(n_steps + 1):
+        ret, grad = grad_scorer(a, states)
+        score = aggregate_heads(ret, aggregate)
+        if it == 0:
+            best, best_score, first_score = a, score, score
+        else:
+            better = score > best_score
+            best_score = torch.where(better, score, best_score)
+            best = torch.where(better.view(1, -1, 1), a, best)
+        if it == n_steps:
+            break
+        g = aggregate_heads_grad(ret, grad, aggregate)
+        if optimizer == 'sgd':
+            step = lr * g
+        else:                                                                             # Adam, ascent: written out in torch ops
+            m = (1.0 - b1) * g if m is None else b1 * m + (1.0 - b1) * g
+            v = (1.0 - b2) * g * g if v is None else b2 * v + (1.0 - b2) * g * g
+            step = lr * (m / (1.0 - b1 ** (it + 1))) / (torch.sqrt(v / (1.0 - b2 ** (it + 1))) + eps)
+        a = torch.clamp(a + step, -1.0, 1.0)
+    return best, best_score, a, score, first_score
+
+
+def _check_refine(n_steps, lr, optimizer):
+    if int(n_steps) < 0:
+        raise ValueError("n_steps must not be negative, got %r" % (n_steps,))
+    if not (float(lr) > 0.0 and np.isfinite(float(lr))):
+        raise ValueError("lr must be positive and finite, got %r" % (lr,))
+    if optimizer not in ('adam', 'sgd'):
+        raise ValueError("optimizer: %r is neither 'adam' nor 'sgd'" % (optimizer,))
+    return int(n_steps)
+
+
+def _setup_grad(engine, grad_scorer, gamma, stop_at_done):
+    if grad_scorer is None:
+        if engine is None:
+            raise ValueError("an engine or a grad_scorer is needed")
+        grad_scorer = engine_grad_scorer(engine, gamma, stop_at_done)
+    return grad_scorer
+
+
+def refine_actions(engine, states, actions, n_steps, lr, optimizer='adam', betas=(0.9, 0.999), eps=1e-8, gamma=1.0, stop_at_done=True, aggregate='mean',
+                   grad_scorer=None):
+    """Projected gradient ASCENT on candidate action sequences: states [S, ns], actions [S, N, T, na] (or [S, T, na]: one each).  n_steps times
+    a <- clip(a + step, -1, 1) with step = lr * g ('sgd') or Adam's lr * m_hat / (sqrt(v_hat) + eps) ('adam', moments per candidate entry), g =
+    aggregate_heads_grad of one gradient call; n_steps + 1 calls in all (the last iterate is scored too).  Keep-best: `actions` / `score` are the
+    best-scoring iterate seen per candidate, so the result is never worse than the input.
+    -> dict(actions [S, N, T, na], score [S, N], last / last_score the final iterate, initial_score [S, N]), device tensors; nothing is read back."""
+    n_steps = _check_refine(n_steps, lr, optimizer)
+    grad_scorer = _setup_grad(engine, grad_scorer, gamma, stop_at_done)
+    act = torch.as_tensor(actions)
+    _, states, na = _setup(engine, states, grad_scorer, act.shape[-1] if act.dim() >= 1 else None, gamma, stop_at_done)
+    act = act.to(device=states.device, dtype=torch.float32)
+    S = states.shape[0]
+    single = act.dim() == 3
+    if single:
+        act = act.unsqueeze(1)
+    if act.dim() != 4 or act.shape[0] != S or act.shape[3] != na or act.shape[1] < 1 or act.shape[2] < 1:
+        raise ValueError("actions: expected [%d, N, T, %d] or [%d, T, %d], got %s" % (S, na, S, na, tuple(torch.as_tensor(actions).shape)))
+    N = act.shape[1]
+    best, best_score, last, last_score, first = _refine(grad_scorer, states, _device_major(act), n_steps, lr, optimizer, betas, eps, aggregate)
+    res = dict(actions=_from_device_major(best, S, N), score=best_score.reshape(S, N), last=_from_device_major(last, S, N),
+               last_score=last_score.reshape(S, N), initial_score=first.reshape(S, N))
+    return {k: x[:, 0] for k, x in res.items()} if single else res
+
+
+def plan_cem_gd(engine, states, horizon, n_candidates, n_elites, n_iters, grad_steps, grad_lr=0.05, refine='elites', optimizer='adam', betas=(0.9, 0.999),
+                eps=1e-8, init_mean=None, init_std=1.0, alpha=0.0, min_std=0.0, gamma=1.0, aggregate='mean', generator=None, stop_at_done=True,
+                scorer=None, grad_scorer=None, na=None):
+    """plan_cem with gradient refinement before the refit (Grad-CEM / CEM-GD): each iteration draws and clips as plan_cem does, then
+    refine='elites': scores all candidates (one scoring call), takes the n_elites best and refines THEM by refine_actions' grad_steps steps;
+    refine='all': refines every candidate (no separate scoring call) and takes the n_elites best of the refined ones.
+    The refit uses the refined elites (keep-best: never worse than the ones drawn).  grad_steps = 0 returns plan_cem's tensors bit for bit for the
+    same generator state.  -> plan_cem's dict; `elites` indexes the drawn candidates."""
+    T, N = _check_counts(horizon, n_candidates)
+    E, n_iters = int(n_elites), int(n_iters)
+    grad_steps = _check_refine(grad_steps, grad_lr, optimizer)
+    if refine not in ('elites', 'all'):
+        raise ValueError("refine: %r is neither 'elites' nor 'all'" % (refine,))
+    if not (1 <= E <= N):
+        raise ValueError("n_elites must be in 1 ... n_candidates = %d, got %r" % (N, n_elites))
+    if n_iters < 1:
+        raise ValueError("n_iters must be positive, got %r" % (n_iters,))
+    if not (0.0 <= float(alpha) < 1.0):
+        raise ValueError("alpha must be in [0, 1), got %r" % (alpha,))
+    if grad_steps > 0 or (scorer is None and engine is None):
+        grad_scorer = _setup_grad(engine, grad_scorer, gamma, stop_at_done)
+    if scorer is None and engine is None:
+        scorer = lambda a, init: grad_scorer(a, init)[0]
+    scorer, states, na = _setup(engine, states, scorer, na, gamma, stop_at_done)
+    S, dev = states.shape[0], states.device
+    mean = _time_major_param(0.0 if init_mean is None else init_mean, T, S, na, dev, 'init_mean')
+    std = _time_major_param(init_std, T, S, na, dev, 'init_std')
+    alpha, min_std = float(alpha), float(min_std)
+    best_score = torch.full((S,), float('-inf'), device=dev, dtype=torch.float32)
+    best_actions = torch.zeros(T, S, na, device=dev, dtype=torch.float32)
+    history = torch.empty(n_iters, S, device=dev, dtype=torch.float32)
+    for it in range(n_iters):
+        eps_ = torch.randn(T, S, N, na, generator=generator, device=dev, dtype=torch.float32)
+        a = torch.clamp(mean + std * eps_, -1.0, 1.0)
+        if grad_steps > 0 and refine == 'all':
+            ref_a, ref_s = _refine(grad_scorer, states, a.reshape(T, S * N, na), grad_steps, grad_lr, optimizer, betas, eps, aggregate)[:2]
+            a, scores = ref_a.reshape(T, S, N, na), ref_s.reshape(S, N)
+        else:
+            scores = aggregate_heads(scorer(a.reshape(T, S * N, na), states), aggregate).reshape(S, N)
+        vals, idx = torch.topk(scores, E, dim=1)                                          # sorted: column 0 is the iteration's best
+        elites = a.gather(2, idx.view(1, S, E, 1).expand(T, S, E, na))
+        if grad_steps > 0 and refine == 'elites':
+            ref_a, ref_s = _refine(grad_scorer, states, elites.reshape(T, S * E, na), grad_steps, grad_lr, optimizer, betas, eps, aggregate)[:2]
+            vals, order = torch.topk(ref_s.reshape(S, E), E, dim=1)                       # sorted again: refinement may reorder the elites
+            elites = ref_a.reshape(T, S, E, na).gather(2, order.view(1, S, E, 1).expand(T, S, E, na))
+        elites = elites.double()
+        e_mean = elites.sum(dim=2, keepdim=True) / E
+        e_std = torch.sqrt(((elites - e_mean) ** 2).sum(dim=2, keepdim=True) / E)
+        mean = alpha * mean + (1.0 - alpha) * e_mean.float()
+        std = torch.clamp(alpha * std + (1.0 - alpha) * e_std.float(), min=min_std)
+        better = vals[:, 0] > best_score
+        best_score = torch.where(better, vals[:, 0], best_score)
+        best_actions = torch.where(better.view(1, S, 1), elites[:, :, 0].float(), best_actions)
+        history[it] = vals.mean(dim=1)
+    tm = lambda x: x.permute(1, 0, 2).contiguous()
+    return dict(actions=tm(mean[:, :, 0]), std=tm(std[:, :, 0]), best_actions=tm(best_actions), best_score=best_score, history=history, elites=idx)
+
+
 class ShootingController(object):
     """Model-predictive control by CEM with a warm start, with the policy's call shape: get_actions(obs [S, ns]) -> (actions [S, na], {}).
     Every call plans `horizon` steps ahead from obs, returns the first action of the plan's mean and keeps the rest: the next call starts from the
     previous mean shifted by one step, its last row reset to init_mean's last row (std starts from init_std every time).
-    The action comes back as float64 NumPy, as GaussianMLPPolicy.get_actions gives it -- one read-back per call, behind the planner."""
+    The action comes back as float64 NumPy, as GaussianMLPPolicy.get_actions gives it -- one read-back per call, behind the planner.
+    grad_steps > 0 plans with plan_cem_gd (grad_lr, refine, grad_scorer) instead."""
 
     def __init__(self, engine, horizon, n_candidates, n_elites, n_iters, init_mean=None, init_std=1.0, alpha=0.0, min_std=0.0, gamma=1.0,
-                 aggregate='mean', generator=None, stop_at_done=True, scorer=None, na=None):
+                 aggregate='mean', generator=None, stop_at_done=True, scorer=None, na=None, grad_steps=0, grad_lr=0.05, refine='elites', grad_scorer=None):
         self.engine, self.horizon, self.scorer, self.na = engine, int(horizon), scorer, (engine.na if engine is not None else na)
+        # grad_steps > 0: plan_cem_gd with these settings in plan_cem's place (0: plan_cem, as before)
+        self.grad_steps, self.grad_kw = _check_refine(grad_steps, grad_lr, 'adam'), dict(grad_lr=grad_lr, refine=refine, grad_scorer=grad_scorer)
+        if refine not in ('elites', 'all'):
+            raise ValueError("refine: %r is neither 'elites' nor 'all'" % (refine,))
         self.init_mean, self.init_std = init_mean, init_std
         self.kw = dict(n_candidates=n_candidates, n_elites=n_elites, n_iters=n_iters, alpha=alpha, min_std=min_std, gamma=gamma, aggregate=aggregate,
                        generator=generator, stop_at_done=stop_at_done)
@@ -182,7 +355,11 @@ class ShootingController(object):
         obs = torch.as_tensor(np.asarray(observations) if not torch.is_tensor(observations) else observations)
         S = obs.shape[0] if obs.dim() == 2 else 1
         start = self._mean if (self._mean is not None and self._mean.shape[0] == S) else self.init_mean
-        plan = plan_cem(self.engine, obs, self.horizon, init_mean=start, init_std=self.init_std, scorer=self.scorer, na=self.na, **self.kw)
+        if self.grad_steps > 0:
+            plan = plan_cem_gd(self.engine, obs, self.horizon, grad_steps=self.grad_steps, init_mean=start, init_std=self.init_std, scorer=self.scorer,
+                               na=self.na, **dict(self.kw, **self.grad_kw))
+        else:
+            plan = plan_cem(self.engine, obs, self.horizon, init_mean=start, init_std=self.init_std, scorer=self.scorer, na=self.na, **self.kw)
         self.last_plan = plan
         self._mean = self.shifted(plan['actions'])
         return plan['actions'][:, 0].double().cpu().numpy(), {}

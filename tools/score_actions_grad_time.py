@@ -1,0 +1,94 @@
+#!/usr/bin/env python3
+"""Time metrpo_score_actions_grad (csrc/score_actions_grad.hip) at tools/score_actions_time.py's sizes: swimmer, C1 nets (K = 5, 2x64 dynamics), T = 30,
+B = 4096 and B = 512 candidates from S = 8 start states, gamma = 0.99.
+
+Timed, as medians of interleaved rounds (CUDA events around `reps` back-to-back calls, after warm-up), [min, max] over the rounds:
+  grad       Engine.score_actions_grad, the fused path (grad and ret: a forward and a reverse launch)
+  score      Engine.score_actions in the same run: the yardstick (the forward sweep without its stores)
+  generic    Engine.score_actions_grad(force_generic=True)
+  grad+mean  the fused path with grad_mean (the third small launch) and lam0
+The forward and the reverse launch separately: run this tool under a kernel trace (rocprofv3 --kernel-trace --stats -- python tools/score_actions_grad_time.py
+--reps 5 --rounds 2) and read k_sagr<.., 0> / k_sagr<.., 1> off the kernel statistics; the events here time whole calls.
+Parity printed with the times: fused against generic, rel-L2 of the gradient per head at worst; ret against score_actions in fp32 ulps.
+Usage: score_actions_grad_time.py [--out FILE] [--reps N] [--rounds R] [--T 30] [--sizes 4096,512] [--S 8]"""
+import sys, os, argparse
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import numpy as np, torch
+import metrpo_amd
+from oracle import metrpo_oracle as O
+
+
+def timed(fn, reps):
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps): fn()
+    e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps * 1e3                   # us
+
+
+def rounds_of(sides, rounds, reps):
+    for _, fn, _ in sides: fn(); fn()
+    t = {k: [] for k, _, _ in sides}
+    for _ in range(rounds):                                    # interleaved rounds: drift of the clock hits all sides alike
+        for k, fn, div in sides:
+            t[k].append(timed(fn, max(1, reps // div)))
+    return {k: np.array(v) for k, v in t.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--reps', type=int, default=20)
+    ap.add_argument('--rounds', type=int, default=7)
+    ap.add_argument('--T', type=int, default=30)
+    ap.add_argument('--S', type=int, default=8)
+    ap.add_argument('--sizes', default='4096,512')
+    a = ap.parse_args()
+    env, K, T, S, gamma = 'swimmer', 5, a.T, a.S, 0.99
+    dm, theta, pdims, pool = O.make_problem(env, K=K, dyn_hidden=(64, 64), pol_hidden=(32, 32), seed=0, n_pool=64)
+    eng = metrpo_amd.Engine(env, K, (64, 64), (32, 32))
+    eng.set_dynamics_layers(dm.Ws, dm.bs, dm.in_mean, dm.in_std, dm.diff_mean, dm.diff_std)
+    dev = eng.device
+    rng = np.random.RandomState(0)
+    lines = ["# metrpo_score_actions_grad: %s, K = %d, 2x64 dynamics, T = %d, S = %d start states, gamma = %g.  %d interleaved rounds of %d back-to-back calls"
+             % (env, K, T, S, gamma, a.rounds, a.reps),
+             "# (generic: %d), CUDA events, 2 warm-up calls each; medians and [min, max] over the rounds.  Device: %s" % (max(1, a.reps // 4), torch.cuda.get_device_name(0))]
+    for B in [int(x) for x in a.sizes.split(',')]:
+        init = torch.as_tensor(pool[rng.randint(len(pool), size=S)].astype(np.float32), device=dev)
+        acts = torch.as_tensor((0.8 * rng.randn(T, B, dm.na)).astype(np.float32), device=dev)
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        out_f = {'grad': f32(K, T, B, dm.na), 'ret': f32(K, B)}
+        out_g = {'grad': f32(K, T, B, dm.na), 'ret': f32(K, B)}
+        out_m = {'grad': f32(K, T, B, dm.na), 'ret': f32(K, B), 'grad_mean': f32(T, B, dm.na), 'lam0': f32(K, B, dm.ns)}
+        out_s = {'ret': f32(K, B)}
+        grad = lambda: eng.score_actions_grad(init, acts, gamma=gamma, out=out_f)
+        generic = lambda: eng.score_actions_grad(init, acts, gamma=gamma, force_generic=True, out=out_g)
+        grad_mean = lambda: eng.score_actions_grad(init, acts, gamma=gamma, want=('grad', 'ret', 'grad_mean', 'lam0'), out=out_m)
+        score = lambda: eng.score_actions(init, acts, gamma=gamma, out=out_s)
+        grad(); path_f = eng.last_score_actions_grad_kernel()
+        generic(); path_g = eng.last_score_actions_grad_kernel()
+        score(); path_s = eng.last_score_actions_kernel()
+        torch.cuda.synchronize()
+        gf, gg = out_f['grad'].double().cpu().numpy(), out_g['grad'].double().cpu().numpy()
+        rel = max(float(np.linalg.norm(gf[k] - gg[k]) / max(np.linalg.norm(gg[k]), 1e-300)) for k in range(K))
+        rf, rs = out_f['ret'].double().cpu().numpy(), out_s['ret'].double().cpu().numpy()
+        ulps = float((np.abs(rf - rs) / np.spacing(np.abs(rs).astype(np.float32)).astype(np.float64)).max())
+        r = rounds_of([('grad', grad, 1), ('score', score, 1), ('generic', generic, 4), ('grad+mean', grad_mean, 1)], a.rounds, a.reps)
+        md = {k: float(np.median(v)) for k, v in r.items()}
+        fmt = lambda k: "%9.1f us [%.1f, %.1f]" % (md[k], r[k].min(), r[k].max())
+        lines += ["B = %d (%d tiles x %d heads):" % (B, (B + 15) // 16, K),
+                  "  score_actions_grad, %-7s (grad, ret)          %s   / score_actions %.2f x" % (path_f, fmt('grad'), md['grad'] / md['score']),
+                  "      ... with grad_mean and lam0                   %s" % fmt('grad+mean'),
+                  "  score_actions, %-7s (the yardstick)           %s" % (path_s, fmt('score')),
+                  "  score_actions_grad, %-7s                      %s   generic / fused %.2f x" % (path_g, fmt('generic'), md['generic'] / md['grad']),
+                  "  parity: fused against generic %.3g rel-L2 of a head's gradient at worst; ret against score_actions %.2f fp32 ulp at worst" % (rel, ulps)]
+    print("\n".join(lines), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        open(a.out, 'w').write("\n".join(lines) + "\n")
+
+
+if __name__ == '__main__':
+    main()
