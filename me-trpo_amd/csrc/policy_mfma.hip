@@ -110,11 +110,16 @@ struct PolImg {
 };
 
 
-template <int NS, int NA, int PH, int MODE_>
+// what a launch without a `valid` array reads in its place, with stride 0: the tile loop's fetch has one form, whatever the arguments
+__device__ const uint8_t g_pol_valid_one = 1;
+
+// VJP: the gradient kernel with the mean-adjoint supplied (PolK::gm, bptt.hip); a property of the launch, taken once at kernel entry (k_policy_mfma)
+template <int NS, int NA, int PH, int MODE_, bool VJP>
 __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict__ theta, const float* __restrict__ v, float* __restrict__ partials) {
     using I = PolImg<NS, NA, PH>;
     constexpr bool CACHED = (MODE_ == OP_FVPC), VPG = (MODE_ == OP_VPG), PPOKL = (MODE_ == OP_PPOKL), PPO = (MODE_ == OP_PPO) || PPOKL;
     constexpr int MODE = CACHED ? OP_FVP : (VPG || PPO) ? OP_GRAD : MODE_;
+    static_assert(!VJP || MODE_ == OP_GRAD, "the mean-adjoint is an input of the plain gradient kernel only");
     constexpr int NS_KS = I::NS_KS, NSI = cdiv_(NS, 16), HB = I::HB, KK = I::KK;
     constexpr int pW0 = 0, pb0 = NS * PH, pW1 = pb0 + PH, pb1 = pW1 + PH * PH, pW2 = pb1 + PH, pb2 = pW2 + PH * NA,
                   pLS = pb2 + NA, P = pLS + NA, ROW = P + PART_EXTRA;
@@ -135,18 +140,28 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
     const f32x4* __restrict__ hc = (const f32x4*)k.hcache;
     // a state-independent old log_std (stride 0: the reference's GaussianMLPPolicy) is one value per action dim for the whole batch: its loads
     // and its two exponentials per sample leave the tile loop (the loss / KL kernel is VALU-bound: 340 instructions per tile, 39 transcendental)
-    const bool ols_const = !VPG && (MODE != OP_FVP) && k.ls_stride == 0 && k.old_ls != nullptr;
+    const bool ols_const = !VPG && !VJP && (MODE != OP_FVP) && k.ls_stride == 0 && k.old_ls != nullptr;
     // Everything a tile reads from HBM (observations in both layouts, valid flag, cached activations, and for the loss modes the old
     // distribution / action / advantage) is fetched ONE TILE AHEAD into registers: consumed in the iteration that issued them, the
     // valid flag and the observation loads each put a full HBM round trip (~2000 cycles) on the wave's critical path, per tile.
     struct TileIn {
         float xB[NS_KS]; float xTs[4][NSI]; float ols[4], omu[4], act[4], adv; f32x4 gmv; int vld, nrem; f32x4 h[2 * HB];
     };
+    constexpr int NR = (NA < 4) ? NA : 4;                   // a lane's action dims are 4q + r: r >= na is padding in every lane, and is neither fetched nor kept
     // `tile` is wave-uniform (SGPRs): scalar base pointers + 32-bit lane offsets, and every load is issued unconditionally on a clamped
     // (always valid) address; what lies outside the batch or in the feature padding is zeroed when the tile is CONSUMED (mask_tile; a
     // select at fetch time would wait for the load).  As written before (bounds-checked 64-bit per-lane addresses) the fetch was 17
     // exec-masked branches and ~150 instructions per tile.
-    auto fetch = [&](long long tile_, TileIn& in) {
+    // No branch on a kernel argument in here: a load in one arm of a run-time branch and a constant or another load in the other meet in one
+    // register, and the compiler then waits for that load (vmcnt(0): for the whole prefetch just issued) where the arms join.  So the VJP form
+    // is a template argument, a launch without `valid` reads the constant 1 through the same load (stride 0), and a broadcast old log_std
+    // (ls_stride 0) is fetched like a per-sample one -- the same few bytes every tile, not used: ols_c, eo_c, os2_c hold its values.
+    // (the cast: a select of two pointers is a generic one to the compiler, and a flat load counts on lgkmcnt as well -- every wait for an LDS read behind it
+    // would be a wait for this HBM round trip)
+    typedef const uint8_t __attribute__((address_space(1)))* gu8_p;
+    const gu8_p vld_p = (gu8_p)((k.valid != nullptr) ? k.valid : &g_pol_valid_one);
+    const int vld_m = (k.valid != nullptr) ? -1 : 0;         // and-mask of the sample offset
+    auto fetch = [&](long long tile_, TileIn& in) __attribute__((always_inline)) {
         const long long tile = (tile_ < ntiles) ? tile_ : ntiles - 1;
         const long long n0 = tile * 16;
         const int nrem = (int)((k.N - n0 < 16) ? k.N - n0 : 16);            // samples of this tile that exist (>= 1)
@@ -163,18 +178,18 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
                 for (int ci = 0; ci < NSI; ++ci) { const int f = 16 * ci + c; in.xTs[s][ci] = ob[slc * NS + ((f < NS) ? f : NS - 1)]; }
             }
         }
-        in.vld = (k.valid == nullptr) ? 1 : (int)k.valid[n0 + cl];
+        in.vld = (int)(vld_p + (n0 & (long long)vld_m))[cl & vld_m];
         if (MODE != OP_FVP) {
             const long long nl = n0 + cl;
-            if (MODE == OP_GRAD && k.gm != nullptr) {
+            if constexpr (VJP) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { const int d = 4 * q + r; in.gmv[r] = k.gm[nl * NA + ((d < NA) ? d : NA - 1)]; }
+                for (int r = 0; r < NR; ++r) { const int d = 4 * q + r; in.gmv[r] = k.gm[nl * NA + ((d < NA) ? d : NA - 1)]; }
             } else {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
+                for (int r = 0; r < NR; ++r) {
                     const int d = 4 * q + r, dc = (d < NA) ? d : NA - 1;
                     if (VPG) { in.act[r] = k.act[nl * NA + dc]; continue; }
-                    in.ols[r] = ols_const ? 0.f : k.old_ls[(size_t)nl * k.ls_stride + dc]; in.omu[r] = k.old_mean[nl * NA + dc]; in.act[r] = k.act[nl * NA + dc];
+                    in.ols[r] = k.old_ls[(size_t)nl * k.ls_stride + dc]; in.omu[r] = k.old_mean[nl * NA + dc]; in.act[r] = k.act[nl * NA + dc];
                 }
                 in.adv = k.adv[nl];
             }
@@ -185,7 +200,7 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
             for (int j = 0; j < 2 * HB; ++j) in.h[j] = hb_[j * 64 + lane];
         }
     };
-    auto mask_tile = [&](TileIn& in) {
+    auto mask_tile = [&](TileIn& in) __attribute__((always_inline)) {
         // feature padding of the B-operand observations (k rows f >= NS meet zero weights, but 0 x garbage must stay 0)
 #pragma unroll
         for (int s = 0; s < NS_KS; ++s) if (4 * s + 3 >= NS && 4 * s + q >= NS) in.xB[s] = 0.f;
@@ -193,13 +208,14 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
         const bool inr = c < in.nrem;
 #pragma unroll
         for (int s = 0; s < NS_KS; ++s) if (!inr) in.xB[s] = 0.f;
+        if (!inr) in.vld = 0;
 #pragma unroll
         for (int s = 0; s < 4; ++s)
 #pragma unroll
             for (int ci = 0; ci < NSI; ++ci) if (4 * q + s >= in.nrem) in.xTs[s][ci] = 0.f;
-        if (!inr) { in.vld = 0; in.adv = 0.f; }
+        if (!inr) in.adv = 0.f;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) if (!inr) { in.ols[r] = 0.f; in.omu[r] = 0.f; in.act[r] = 0.f; in.gmv[r] = 0.f; }
+        for (int r = 0; r < NR; ++r) if (!inr) { in.ols[r] = 0.f; in.omu[r] = 0.f; in.act[r] = 0.f; in.gmv[r] = 0.f; }
     };
     TileIn nxt;
 
@@ -328,15 +344,32 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
     __builtin_amdgcn_s_waitcnt(0x0F70);
     PT_MARK(2)
     const long long sp_base = SPL ? (long long)blockIdx.x * 4 + (wave & 3) : (long long)blockIdx.x * NWAVES + wave, sp_stride = (long long)gridDim.x * (SPL ? 4 : NWAVES);
-    auto sp_next = [&](long long m) -> long long {
-        if constexpr (SPL == 0) return m + 1;
-        else { const int ph = (int)(m % SPL); return (wave < 4) ? ((ph == SPL - 1) ? m + 1 : m + 2) : ((ph == SPL - 2) ? m + 3 : m + 2); }
+    // The deal walks m with its phase ph = m % SPL carried beside it (a 64-bit modulo per tile was a 45-instruction multiply-high ladder): waves 0-3 take
+    // the even phases of a round and step over its end by 1, waves 4-7 the odd ones and step over it by 3.
+    const int ph_last = (wave < 4) ? SPL - 1 : SPL - 2, ph_first = (wave < 4) ? 0 : 1, m_wrap = (wave < 4) ? 1 : 3;
+    auto sp_next = [&](long long& m, int& ph) __attribute__((always_inline)) {
+        if constexpr (SPL == 0) m += 1;
+        else { const bool last = (ph == ph_last); m += last ? m_wrap : 2; ph = last ? ph_first : ph + 2; }
     };
-    for (long long m = (SPL && wave >= 4) ? 1 : 0, tile = sp_base + m * sp_stride; tile < ntiles; m = sp_next(m), tile = sp_base + m * sp_stride) {
+    // The bits of the loss head.  Which of the head's products the compiler packs in pairs and which it contracts into fmas follows from what shares their
+    // basic block, and the results on record (tests/test_gpu_update_bits.py) are those of the head as one arm of a run-time branch -- the other arm was the
+    // VJP form, now a body of its own.  In that shape z * z - 1 of ONE action dim stayed a product and a sum (its product was packed with w = -la / n) while
+    // the others became fmas, and um's last product was not contracted into gb2 += um (um was a phi).  Per shape, what reproduces it:
+    //   na <= 3 (swimmer's gradient and PPO bodies, hopper) and the PPO-KL body at every shape: HEAD_ARM -- the head stays an arm; the other one is never
+    //     taken (head_off is 0 in a scalar register the compiler cannot see through: one scalar branch a tile);
+    //   elsewhere the head joins the block before it and um is pinned instead, and with na = 4 or 8 (snake, ant) the gradient and PPO bodies also spell out z * z - 1: a
+    //     pinned product and a sum for one action dim (SQ_PIN), the one the branch shape left uncontracted, an fma for the others.
+    // This steers the compiler rather than fixing the arithmetic: an edit near the head or another compiler can move the bits again, and the fixture says so
+    // at once.  The durable form is the head under `#pragma clang fp contract(off)` with every fma written out; it changes the recorded bits once, on purpose.
+    constexpr bool HEAD_ARM = (NA == 3) || (NA == 2 && (MODE_ == OP_GRAD || MODE_ == OP_PPO)) || PPOKL;
+    constexpr int SQ_PIN = ((NA == 4 || NA == 8) && (MODE_ == OP_GRAD || MODE_ == OP_PPO)) ? 0 : -1;
+    int head_off = 0;
+    asm volatile("" : "+s"(head_off));
+    // one tile: `in` is consumed, `pre` receives the loads of tile `tile_pre`, issued before anything of `in` is touched
+    auto do_tile = [&](const long long tile, TileIn& in, const long long tile_pre, TileIn& pre) __attribute__((always_inline)) {
         const long long n0 = tile * 16, n = n0 + c;
         const bool inr = n < k.N;
-        TileIn in = nxt;
-        fetch(sp_base + sp_next(m) * sp_stride, nxt);
+        fetch(tile_pre, pre);
         asm volatile("" ::: "memory");                      // the loads are issued HERE (left alone, the compiler sinks them to the end of the iteration)
         mask_tile(in);
         const bool ok = inr && in.vld != 0;
@@ -419,9 +452,12 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
         float ual[NAV];                                     // FVP with the VALU output layer: the sample's mean-adjoint, already in all of its lanes
 #pragma unroll
         for (int d = 0; d < NAV; ++d) ual[d] = 0.f;
-        if (MODE == OP_GRAD && k.gm != nullptr) {         // VJP mode (bptt.hip): the mean-adjoint is an input
+        if constexpr (VJP) {                                // VJP mode (bptt.hip): the mean-adjoint is an input
 #pragma unroll
-            for (int r = 0; r < 4; ++r) um[r] = (ok && 4 * q + r < NA) ? in.gmv[r] : 0.f;
+            for (int r = 0; r < NR; ++r) um[r] = (ok && 4 * q + r < NA) ? in.gmv[r] : 0.f;
+        } else if (MODE == OP_GRAD && HEAD_ARM && head_off) {      // never taken (see head_off): keeps the head below a basic block of its own
+#pragma unroll
+            for (int r = 0; r < NR; ++r) um[r] = (ok && 4 * q + r < NA) ? in.act[r] : 0.f;
         } else if (MODE != OP_FVP) {
             f32x4 mu = Z4;
             if (L2V) {
@@ -447,7 +483,7 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
             float llr = 0.f, kl = 0.f, zz[4] = {0.f, 0.f, 0.f, 0.f};
             float kmu[4] = {0.f, 0.f, 0.f, 0.f}, kls[4] = {0.f, 0.f, 0.f, 0.f};      // OP_PPOKL, gate open: d kl_i / d mean, d kl_i / d log_std of this lane's action dims
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
+            for (int r = 0; r < NR; ++r) {
                 const int d = 4 * q + r;
                 if (VPG && d < NA && ok) {                  // DiagonalGaussian.log_likelihood_sym, less its constant (added per sample below)
                     const float z = (in.act[r] - mu[r]) * inv_std[r];
@@ -478,12 +514,19 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
             if constexpr (PPO) { la = ppo_gate(expf(llr), in.adv, k.clip_lo, k.clip_hi, &surr); if (!ok) { la = 0.f; surr = 0.f; } }
             else { la = ok ? (VPG ? in.adv : expf(llr) * in.adv) : 0.f; surr = VPG ? (llr - NA * HALF_LOG_2PI) * la : la; }
             if (q == 0) acc0 -= surr * k.inv_n;             // surr_loss = -mean(lr*adv) (npo.py:75) | -mean(logli*adv) (vpg.py:88) | clipped_surr_loss (ppo.py:115)
-            if (MODE == OP_LOSSKL) { acc1 += kl * k.inv_n; continue; }
+            if (MODE == OP_LOSSKL) { acc1 += kl * k.inv_n; return; }
             const float w = -la * k.inv_n;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 um[r] = w * zz[r] * inv_std[r];             // d loss / d mean = w (a-mu)/std^2
-                if (4 * q + r < NA) dls[r] += w * (zz[r] * zz[r] - 1.f);      // d loss / d log_std
+                if constexpr (SQ_PIN < 0) {
+                    if (4 * q + r < NA) dls[r] += w * (zz[r] * zz[r] - 1.f);      // d loss / d log_std
+                } else {                                    // z * z - 1 spelled out (see SQ_PIN)
+                    float zm1;
+                    if (r == SQ_PIN) { float sq = zz[r] * zz[r]; asm volatile("" : "+v"(sq)); zm1 = sq - 1.f; }
+                    else zm1 = __builtin_fmaf(zz[r], zz[r], -1.f);
+                    if (4 * q + r < NA) dls[r] += w * zm1;
+                }
             }
             if constexpr (PPOKL) {                          // the penalty's seed and loss term, in statements of their own: with the gate closed the arithmetic is OP_PPO's
                 if (kl_open) {                              // (kl, kmu, kls are zero for an invalid sample and a padded action dim)
@@ -492,6 +535,10 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { um[r] += kl_w * kmu[r]; if (4 * q + r < NA) dls[r] += kl_w * kls[r]; }
                 }
+            }
+            if constexpr (!HEAD_ARM) {                      // (see HEAD_ARM)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { float x = um[r]; asm volatile("" : "+v"(x)); um[r] = x; }
             }
         } else {
             // ---- S4: tangent of the mean: m1 = V2^T h1 (VALU inside: t1 *= 1 - h1^2), then m0 = vb2 + W2^T t1 ----------
@@ -629,6 +676,32 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
                 for (int cj = 0; cj < HB; ++cj) gW0[ci][cj] = MFMA16(xT[ci], b0_[cj], gW0[ci][cj]);
         }
         wave_sync_lds();
+    };
+    // Two tiles per trip over two input buffers that swap roles: handing `nxt` over to `in` at the top of every tile was 18 register moves, each a read
+    // of a register with a load in flight -- a full vmcnt(0) at the back edge.  The tile sequence of the wave is the one-tile loop's.
+    {
+        // (one buffer and the hand-over -- its moves and the full wait at the back edge -- in the VPG and PPO-KL bodies: with two buffers both run out of the 256
+        // registers and spill inside the loop)
+        constexpr bool TWO_BUF = !(VPG || PPOKL);
+        TileIn nxt2;
+        long long m = (SPL && wave >= 4) ? 1 : 0;
+        int ph = (int)m;
+        long long tile = sp_base + m * sp_stride;           // = first_tile: its loads went out into nxt in the prologue
+        while (tile < ntiles) {
+            sp_next(m, ph);
+            const long long tile1 = sp_base + m * sp_stride;
+            if constexpr (TWO_BUF) {
+                do_tile(tile, nxt, tile1, nxt2);
+                if (!(tile1 < ntiles)) break;
+                sp_next(m, ph);
+                tile = sp_base + m * sp_stride;
+                do_tile(tile1, nxt2, tile, nxt);
+            } else {
+                TileIn cur = nxt;
+                do_tile(tile, cur, tile1, nxt);
+                tile = tile1;
+            }
+        }
     }
 #undef FRAG2
 #undef FRAG1
@@ -637,6 +710,11 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
     PT_MARK(3)
     __syncthreads();
     PT_MARK(4)
+    // log_std is read again down here, through a pointer the compiler cannot tie to the prologue's loads: otherwise four values per lane stay in registers
+    // across the tile loop for the two uses below (in the PPO bodies, at 256 registers, they were spilled instead)
+    typedef const float __attribute__((address_space(1)))* gf32_p;
+    gf32_p th_e = (gf32_p)theta;
+    asm volatile("" : "+s"(th_e));
     float* RB = lds;                                        // [NWAVES][ROW] (weight image and transpose tiles are dead)
     float* row = RB + wave * ROW;
     // every column of the row is written exactly once below, except the log_std columns outside the gradient mode (zero there); the
@@ -683,7 +761,7 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
             const float s2 = xsum_c(gb2[r]), sl = xsum_c(dls[r]);
             if (c == 0 && 4 * q + r < NA) {
                 row[pb2 + 4 * q + r] = s2;
-                if (MODE == OP_GRAD) row[pLS + 4 * q + r] = (theta[pLS + 4 * q + r] > LOG_MIN_STD) ? sl : 0.f;
+                if (MODE == OP_GRAD) row[pLS + 4 * q + r] = (th_e[pLS + 4 * q + r] > LOG_MIN_STD) ? sl : 0.f;
             }
         }
     }
@@ -692,7 +770,7 @@ __device__ __forceinline__ void pol_body(const PolK& k, const float* __restrict_
         if (blockIdx.x == 0 && wave == 0 && c == 0) {
             acc1 = (q == 0) ? NA * ENTROPY_CONST : 0.f;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) if (4 * q + r < NA) acc1 += ls[r];
+            for (int r = 0; r < 4; ++r) if (4 * q + r < NA) acc1 += fmaxf(th_e[pLS + 4 * q + r], LOG_MIN_STD);
         }
     }
     {
@@ -715,9 +793,19 @@ template <int NS, int NA, int PH, int MODE_>
 __global__ void __launch_bounds__(NWAVES * 64, 1) k_policy_mfma(PolK k, const float* __restrict__ theta, const float* __restrict__ v,
                                                         float* __restrict__ partials) {
     if constexpr (MODE_ == OP_PPOKL) {                      // the gate is the same for every wave of the launch: closed -> OP_PPO's body
-        if (!ppo_kl_open(k.mean_kl, k.kl_delta)) { pol_body<NS, NA, PH, OP_PPO>(k, theta, v, partials); return; }
+        if (!ppo_kl_open(k.mean_kl, k.kl_delta)) {
+            // (a pointer of its own for this body: left as one value, the addresses both bodies form from theta are computed above the gate, kept in vector
+            // registers across it, and spilled)
+            typedef const float __attribute__((address_space(1)))* gf32_p;      // (kept a global pointer through the asm: a generic one makes the loads flat)
+            gf32_p th = (gf32_p)theta;
+            asm volatile("" : "+s"(th));
+            pol_body<NS, NA, PH, OP_PPO, false>(k, (const float*)th, v, partials); return;
+        }
     }
-    pol_body<NS, NA, PH, MODE_>(k, theta, v, partials);
+    if constexpr (MODE_ == OP_GRAD) {                       // the VJP form (a mean-adjoint supplied) is a body of its own: no branch on it inside the tile loop
+        if (k.gm != nullptr) { pol_body<NS, NA, PH, OP_GRAD, true>(k, theta, v, partials); return; }
+    }
+    pol_body<NS, NA, PH, MODE_, false>(k, theta, v, partials);
 }
 
 
