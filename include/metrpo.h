@@ -833,6 +833,47 @@ typedef struct {
 int32_t metrpo_score_actions_grad(metrpo_ctx* ctx, const metrpo_score_actions_grad_args* args, void* stream);
 int32_t metrpo_last_score_actions_grad_kernel(const metrpo_ctx* ctx);   /* -1 none yet, 0 generic, 1 fused */
 
+/* ---- the discounted return EVERY head predicts for each of B candidate NOISE sequences around the policy: closed-loop candidates for planners that
+ * perturb the policy's actions (CEM in noise space), the per-candidate return of the deterministic policy (no noise), and the stochastic policy's return
+ * under common random numbers on every head (noise in units of the policy's std).  Additions to ABI 4: no struct above changes, no option key is added,
+ * METRPO_ABI_VERSION stays.
+ * For every head k and candidate b, head k rolls ITS OWN trajectory from s_0 = d_init_obs[b / (B / S)]; at every step
+ *   mean_t = policy_model(s_t)                                 the raw mean net of the context's theta at call time (stream-ordered)
+ *   a_t    = mean_t + noise_t                                  noise_in_std = 0
+ *          = fmaf(noise_t, exp(max(log_std, LOG_MIN_STD)), mean_t)   noise_in_std = 1: get_actions' arithmetic, noise_t its eps
+ *          = mean_t                                            d_noise NULL
+ *   u_t    = clip(a_t, -1, 1)                                  env_helpers.py:599
+ *   s_t+1  = head k's metrpo_step of (s_t, u_t),  r_t = -cost_np_vec(s_t, u_t, s_t+1)
+ * and the done mask is updated AFTER the step's cost (model_based_rl.py:134-137).  ret, len, ret_mean, ret_std, gamma and stop_at_done are defined
+ * EXACTLY as for metrpo_score_actions above (float64 sum in step order, gamma^t by repeated multiplication, one rounding to fp32 at the store).
+ * act_out[k][t][b][:] = a_t of head k's trajectory, UNCLIPPED: fed back to metrpo_score_actions it reproduces ret[k] (the step arithmetic is shared).
+ * Which kernel runs (metrpo_last_score_policy_actions_kernel: -1 none yet, 0 generic, 1 fused):
+ *   fused (score_policy_actions.hip: one launch, one wave per (16-candidate tile, head) for all T steps, policy and head weights in registers, no store
+ *     inside the step loop unless d_act_out is given) -- metrpo_score_actions' fused shape class (which includes the 2 x 32 tanh policy), force_generic = 0.
+ *   generic (per chunk of candidates, head and step: metrpo_policy_actions' launch, a small add kernel where it is needed, metrpo_step's launch with
+ *     eps_rand and the head fixed; then metrpo_score_actions' reduction kernel) -- everything else.  It is a fallback and cross-check, not a fast path.
+ * The two agree to rounding, not bits.  Repeated calls are bit-identical.  Stream-ordered, neither frees nor synchronises; workspaces are ctx-owned.
+ * Needs metrpo_set_dynamics and metrpo_set_policy.  Leaves theta, both Adam states, the Philox state, the ensemble, every other
+ * metrpo_last_*_kernel reporter and metrpo_rollout_note untouched.
+ * B == 0 or T == 0: METRPO_OK, nothing written.  METRPO_ENULL: ctx, args, d_init_obs, d_ret; METRPO_EINVAL: B < 0, T < 0, S < 1, B % S != 0, gamma not
+ * finite; METRPO_ESTATE before metrpo_set_dynamics or metrpo_set_policy, and while an update begun with metrpo_trpo_update_begin is open. */
+typedef struct {
+    int32_t B, T, S;            /* as metrpo_score_actions_args: candidate b starts from d_init_obs[b / (B / S)] */
+    int32_t stop_at_done;
+    int32_t noise_in_std;       /* 0: a = mean + noise;  1: a = fmaf(noise, exp(max(log_std, LOG_MIN_STD)), mean), get_actions' arithmetic */
+    int32_t force_generic;      /* test / A-B hook */
+    double  gamma;
+    const float* d_init_obs;    /* [S][ns] */
+    const float* d_noise;       /* [T][B][na], or NULL: the deterministic policy (a = mean); never written */
+    float*   d_ret;             /* [K][B] required */
+    int32_t* d_len;             /* optional [K][B] */
+    float*   d_ret_mean;        /* optional [B] */
+    float*   d_ret_std;         /* optional [B] */
+    float*   d_act_out;         /* optional [K][T][B][na]: the UNCLIPPED action head k's trajectory took at step t */
+} metrpo_score_policy_actions_args;
+int32_t metrpo_score_policy_actions(metrpo_ctx* ctx, const metrpo_score_policy_actions_args* args, void* stream);
+int32_t metrpo_last_score_policy_actions_kernel(const metrpo_ctx* ctx);   /* -1 none yet, 0 generic, 1 fused */
+
 #ifdef __cplusplus
 }
 #endif

@@ -1101,6 +1101,22 @@ extern "C" int32_t metrpo_score_actions_grad(metrpo_ctx* c, const metrpo_score_a
 }
 extern "C" int32_t metrpo_last_score_actions_grad_kernel(const metrpo_ctx* c) { return c ? c->last_sagr_kernel : METRPO_ENULL; }
 
+// ---- every head's discounted return of noise sequences around the policy (closed loop: a = clip(pi(s) + noise); score_policy_actions.hip) ----
+extern "C" int32_t metrpo_score_policy_actions(metrpo_ctx* c, const metrpo_score_policy_actions_args* a, void* stream) {
+    TraceRange trace_("metrpo:score_policy_actions (per-head returns of noise sequences around the policy)");
+    if (!c) return METRPO_ENULL;
+    if (!a) return set_err(c, METRPO_ENULL, "score_policy_actions: args NULL");
+    NEED_DYN(c); NEED_POL(c);
+    if (c->upd_pending) return set_err(c, METRPO_ESTATE, "score_policy_actions: an update begun with metrpo_trpo_update_begin is still open (metrpo_trpo_update_end decides which theta stands)");
+    if (a->B < 0 || a->T < 0) return set_err(c, METRPO_EINVAL, "score_policy_actions: bad B/T");
+    if (a->S < 1 || a->B % a->S != 0) return set_err(c, METRPO_EINVAL, "score_policy_actions: S = " + std::to_string(a->S) + " must be at least 1 and divide B = " + std::to_string(a->B));
+    if (!std::isfinite(a->gamma)) return set_err(c, METRPO_EINVAL, "score_policy_actions: gamma is not finite");
+    if (a->B == 0 || a->T == 0) return METRPO_OK;
+    if (!a->d_init_obs || !a->d_ret) return set_err(c, METRPO_ENULL, "score_policy_actions: required pointer is NULL");
+    return run_score_policy_actions(c, a, (hipStream_t)stream);
+}
+extern "C" int32_t metrpo_last_score_policy_actions_kernel(const metrpo_ctx* c) { return c ? c->last_spol_kernel : METRPO_ENULL; }
+
 // ---- 'svg' policy update: value gradients along recorded rollouts (svg_utils.py:12-66; svg.hip) ----
 static int svg_check(metrpo_ctx* c, const metrpo_svg_args* a) {
     if (!a) return set_err(c, METRPO_ENULL, "svg: args NULL");

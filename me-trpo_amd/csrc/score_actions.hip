@@ -24,6 +24,7 @@
 //
 // d_ret_mean / d_ret_std: k_sact_aggregate, a second small launch over d_ret, one thread per candidate adding in head order; no workgroup waits on another.
 #include "dyn_tile_step.h"
+#include "sact_sum.h"                 // SactSum: one step of the return
 #include <algorithm>
 #include <cmath>
 
@@ -33,19 +34,6 @@ struct SactK {
     double gamma;
     const float* init_obs; const float* actions;
     float* ret; int32_t* len;
-};
-
-// one step of the return: ret += gamma^t alive_t r_t in float64, then the discount, then the mask (model_based_rl.py:134-137: the step that ends an
-// episode still counts).  A step that is not counted adds nothing (no 0 * r).
-struct SactSum {
-    double sum = 0.0, disc = 1.0;
-    int n = 0;
-    bool alive = true;
-    __device__ __forceinline__ void step(float rew, bool done, double gamma, int stop) {
-        if (alive) { sum += disc * (double)rew; ++n; }
-        disc *= gamma;
-        if (stop && done) alive = false;
-    }
 };
 
 // tile_rollout's sink that stores nothing inside the step loop: every lane carries its env's sum, quad 0 writes d_ret / d_len once behind the loop
@@ -118,6 +106,18 @@ __global__ void __launch_bounds__(256) k_sact_aggregate(const float* __restrict_
     }
 }
 
+// the three launches above for score_policy_actions.hip as well (metrpo_internal.h); none of them reports an error of its own
+void launch_sact_starts(const float* init_obs, const float* actions, int B, int T, int per, int c0, int Bc, int ns, int na, float* obs0, float* act_c, hipStream_t st) {
+    const size_t work = (size_t)Bc * ns + (act_c ? (size_t)T * Bc * na : 0);
+    hipLaunchKernelGGL(k_sact_starts, dim3((unsigned)std::min<size_t>((work + 255) / 256, 4096)), dim3(256), 0, st, init_obs, actions, B, T, per, c0, Bc, ns, na, obs0, act_c);
+}
+void launch_sact_reduce(const float* rew, const uint8_t* done, int Bc, int T, int stop, double gamma, float* ret, int32_t* len, hipStream_t st) {
+    hipLaunchKernelGGL(k_sact_reduce, dim3((Bc + 255) / 256), dim3(256), 0, st, rew, done, Bc, T, stop, gamma, ret, len);
+}
+void launch_sact_aggregate(const float* ret, int B, int K, float* mean, float* sd, hipStream_t st) {
+    hipLaunchKernelGGL(k_sact_aggregate, dim3((B + 255) / 256), dim3(256), 0, st, ret, B, K, mean, sd);
+}
+
 // -------------------------------------------------------------------------------------------------
 typedef void (*sact_kernel_t)(SactK, const float*, const float*);
 struct SactEntry { int env; sact_kernel_t kern; int w_sz; };
@@ -151,9 +151,7 @@ static int launch_sact_generic(metrpo_ctx* c, const metrpo_score_actions_args* a
     for (size_t c0 = 0; c0 < B && rc == METRPO_OK; c0 += Bc) {
         const int n = (int)std::min(Bc, B - c0);
         float* act_c = Bc < B ? ws + o_act : nullptr;
-        const size_t work = (size_t)n * ns + (act_c ? T * n * na : 0);
-        hipLaunchKernelGGL(k_sact_starts, dim3((unsigned)std::min<size_t>((work + 255) / 256, 4096)), dim3(256), 0, st, a->d_init_obs, a->d_actions, a->B, a->T, per,
-                           (int)c0, n, (int)ns, (int)na, ws + o_obs, act_c);
+        launch_sact_starts(a->d_init_obs, a->d_actions, a->B, a->T, per, (int)c0, n, (int)ns, (int)na, ws + o_obs, act_c, st);
         if (hipGetLastError() != hipSuccess) { rc = set_err(c, METRPO_EHIP, "score_actions: launch failed"); break; }
         metrpo_rollout_actions_args ra = {};
         ra.B = n; ra.T = a->T; ra.sam_mode = METRPO_SAM_EPS_RAND; ra.force_step_loop = 1;
@@ -163,8 +161,8 @@ static int launch_sact_generic(metrpo_ctx* c, const metrpo_score_actions_args* a
             ra.uniform_model = k;
             rc = run_rollout_actions(c, &ra, st);
             if (rc) break;
-            hipLaunchKernelGGL(k_sact_reduce, dim3((n + 255) / 256), dim3(256), 0, st, ra.d_rew, ra.d_done, n, a->T, a->stop_at_done ? 1 : 0, a->gamma,
-                               a->d_ret + (size_t)k * B + c0, a->d_len ? a->d_len + (size_t)k * B + c0 : nullptr);
+            launch_sact_reduce(ra.d_rew, ra.d_done, n, a->T, a->stop_at_done ? 1 : 0, a->gamma, a->d_ret + (size_t)k * B + c0,
+                               a->d_len ? a->d_len + (size_t)k * B + c0 : nullptr, st);
             if (hipGetLastError() != hipSuccess) rc = set_err(c, METRPO_EHIP, "score_actions: launch failed");
         }
     }
@@ -178,7 +176,7 @@ int run_score_actions(metrpo_ctx* c, const metrpo_score_actions_args* a, hipStre
     const int rc = en != nullptr ? launch_sact_fused(c, *en, padded, a, st) : launch_sact_generic(c, a, st);
     if (rc) return rc;
     if (a->d_ret_mean != nullptr || a->d_ret_std != nullptr) {
-        hipLaunchKernelGGL(k_sact_aggregate, dim3((a->B + 255) / 256), dim3(256), 0, st, a->d_ret, a->B, c->pd.K, a->d_ret_mean, a->d_ret_std);
+        launch_sact_aggregate(a->d_ret, a->B, c->pd.K, a->d_ret_mean, a->d_ret_std, st);
         HIP_TRY(c, hipGetLastError());
     }
     c->last_sact_kernel = en != nullptr ? 1 : 0;

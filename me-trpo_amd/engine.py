@@ -458,6 +458,66 @@ class Engine(object):
         the step loop of rollout_actions, then a reduction kernel); None before the first."""
         return {0: 'generic', 1: 'fused'}.get(int(lib.metrpo_last_score_actions_kernel(self._ctx)))
 
+    # ------------------------------------------------------------------ every head's return of candidate noise sequences around the policy
+    SCORE_POLICY_ACTIONS_OUTPUTS = ('ret', 'len', 'ret_mean', 'ret_std', 'act_out')
+
+    def score_policy_actions(self, init_obs, noise=None, T=None, gamma=1.0, stop_at_done=True, noise_in_std=False, want=('ret',), force_generic=False,
+                             out=None):
+        """metrpo_score_policy_actions: the discounted return each of the K heads predicts for each of B candidate NOISE sequences around the policy --
+        score_actions with a_t = clip(policy mean(s_t) + noise_t) formed from the head's own state at every step (noise_in_std: noise_t in units of
+        the policy's std, get_actions' arithmetic).  init_obs [S, ns] or [ns], noise [T, B, na] with B % S == 0 (candidate b starts from
+        init_obs[b // (B // S)]; never written), or None: the deterministic policy for T= steps, B = S.  want: any of ret [K, B], len [K, B] int32,
+        ret_mean [B], ret_std [B], act_out [K, T, B, na] (the UNCLIPPED action head k's trajectory took); ret is always computed.  -> dict of device
+        tensors, nothing synchronised.  out: dict name -> tensor to write into instead (contiguous, at least that large)."""
+        dev = self.device
+        init_obs = _f32(init_obs, dev)
+        if init_obs.dim() == 1:
+            init_obs = init_obs.unsqueeze(0)
+        if init_obs.dim() != 2 or init_obs.shape[1] != self.ns or init_obs.shape[0] < 1:
+            raise ValueError("init_obs: expected [S, %d] or [%d], got %s" % (self.ns, self.ns, tuple(init_obs.shape)))
+        S = init_obs.shape[0]
+        if noise is None:
+            if T is None or int(T) < 0:
+                raise ValueError("noise=None needs T= (the number of steps), got %r" % (T,))
+            T, B = int(T), S
+        else:
+            noise = _f32(noise, dev)
+            if noise.dim() != 3 or noise.shape[2] != self.na or noise.shape[1] % S != 0:
+                raise ValueError("noise: expected [T, B, %d] with B a multiple of %d, got %s" % (self.na, S, tuple(noise.shape)))
+            if T is not None and int(T) != int(noise.shape[0]):
+                raise ValueError("T = %r does not match noise %s" % (T, tuple(noise.shape)))
+            T, B = int(noise.shape[0]), int(noise.shape[1])
+        want = (want,) if isinstance(want, str) else tuple(want)
+        for w in want:
+            if w not in self.SCORE_POLICY_ACTIONS_OUTPUTS:
+                raise ValueError("want: %r is none of %s" % (w, self.SCORE_POLICY_ACTIONS_OUTPUTS))
+        if not np.isfinite(float(gamma)):
+            raise ValueError("gamma must be finite")
+        shapes = {'ret': (self.K, B), 'len': (self.K, B), 'ret_mean': (B,), 'ret_std': (B,), 'act_out': (self.K, T, B, self.na)}
+        res = {}
+        for w in ('ret',) + tuple(x for x in want if x != 'ret'):
+            dt = torch.int32 if w == 'len' else torch.float32
+            if out is not None and w in out:
+                t = out[w]
+                assert t.dtype == dt and t.is_contiguous() and t.device == dev and t.numel() >= int(np.prod(shapes[w], dtype=np.int64))
+            else:
+                t = torch.empty(shapes[w], dtype=dt, device=dev)
+            res[w] = t
+        a = _lib.ScorePolicyActionsArgs()
+        a.B, a.T, a.S, a.stop_at_done, a.noise_in_std, a.force_generic = B, T, S, int(bool(stop_at_done)), int(bool(noise_in_std)), int(bool(force_generic))
+        a.gamma = float(gamma)
+        a.d_init_obs, a.d_noise = init_obs.data_ptr(), (noise.data_ptr() if noise is not None else None)
+        for w in self.SCORE_POLICY_ACTIONS_OUTPUTS:
+            setattr(a, 'd_' + w, res[w].data_ptr() if w in res else None)
+        self._chk(lib.metrpo_score_policy_actions(self._ctx, C.byref(a), self._stream()))
+        self._spa_keep = (init_obs, noise)                                         # alive until the stream has consumed them
+        return res
+
+    def last_score_policy_actions_kernel(self):
+        """Path the last score_policy_actions() of this engine took: 'fused' (score_policy_actions.hip: one launch, a wave per (tile, head)), 'generic'
+        (per head and step the policy_actions and step launches, then a reduction kernel); None before the first."""
+        return {0: 'generic', 1: 'fused'}.get(int(lib.metrpo_last_score_policy_actions_kernel(self._ctx)))
+
     # ------------------------------------------------------------------ gradient of every head's return with respect to the candidate actions
     SCORE_ACTIONS_GRAD_OUTPUTS = ('grad', 'ret', 'len', 'grad_mean', 'lam0')
 

@@ -314,20 +314,117 @@ def plan_cem_gd(engine, states, horizon, n_candidates, n_elites, n_iters, grad_s
     return dict(actions=tm(mean[:, :, 0]), std=tm(std[:, :, 0]), best_actions=tm(best_actions), best_score=best_score, history=history, elites=idx)
 
 
+# ---------------------------------------------------------------------- planning in noise space around the policy (POPLIN-A)
+def engine_policy_scorer(engine, gamma=1.0, stop_at_done=True, noise_in_std=False, force_generic=False):
+    """The engine's closed-loop scorer: (noise [T, B, na], init [S, ns]) -> ret [K, B] of a_t = clip(policy mean(s_t) + noise_t), one
+    metrpo_score_policy_actions call, nothing synchronised.  The `scorer=` signature of the other planners."""
+    def scorer(noise, init):
+        return engine.score_policy_actions(init, noise, gamma=gamma, stop_at_done=stop_at_done, noise_in_std=noise_in_std, force_generic=force_generic)['ret']
+    return scorer
+
+
+def _setup_policy(engine, states, scorer, na, gamma, stop_at_done, noise_in_std=False):
+    if scorer is None:
+        if engine is None:
+            raise ValueError("an engine or a scorer is needed")
+        scorer = engine_policy_scorer(engine, gamma, stop_at_done, noise_in_std)
+    return _setup(engine, states, scorer, na, gamma, stop_at_done)
+
+
+def score_noise_sequences(engine, states, noise, gamma=1.0, stop_at_done=True, aggregate='mean', noise_in_std=False, scorer=None):
+    """score_action_sequences' counterpart in noise space: states [S, ns], noise [S, N, T, na] (N candidates per state) or [S, T, na] (one each),
+    trajectory-major; every candidate is the closed loop a_t = clip(policy mean(s_t) + noise_t) on each head (noise_in_std: noise in units of the
+    policy's std).  -> scores [S, N] (or [S]): the heads' discounted returns folded by `aggregate`.  A device tensor."""
+    nz = torch.as_tensor(noise)
+    scorer, states, na = _setup_policy(engine, states, scorer, nz.shape[-1] if nz.dim() >= 1 else None, gamma, stop_at_done, noise_in_std)
+    nz = nz.to(device=states.device, dtype=torch.float32)
+    S = states.shape[0]
+    single = nz.dim() == 3
+    if single:
+        nz = nz.unsqueeze(1)
+    if nz.dim() != 4 or nz.shape[0] != S or nz.shape[3] != na or nz.shape[1] < 1 or nz.shape[2] < 1:
+        raise ValueError("noise: expected [%d, N, T, %d] or [%d, T, %d], got %s" % (S, na, S, na, tuple(torch.as_tensor(noise).shape)))
+    scores = aggregate_heads(scorer(_device_major(nz), states), aggregate).reshape(S, nz.shape[1])
+    return scores[:, 0] if single else scores
+
+
+def plan_cem_policy(engine, states, horizon, n_candidates, n_elites, n_iters, init_mean=None, init_std=0.5, noise_clip=2.0, alpha=0.0, min_std=0.0,
+                    gamma=1.0, aggregate='mean', generator=None, stop_at_done=True, scorer=None, na=None, include_policy=True):
+    """Cross-entropy method over NOISE sequences around the policy, per state (POPLIN-A): a candidate is delta [T, na] and stands for the closed loop
+    a_t = clip(policy mean(s_t) + delta_t) on every head; delta = 0 is the policy itself.  plan_cem's loop over delta: eps = randn(T, S, N, na);
+    delta = clamp(mean + std * eps, -noise_clip, noise_clip) (2.0 spans the whole action range from any mean); one scoring call; the n_elites best per
+    state; elite mean and population std of the clamped elites in float64; the same mixing with alpha and floor at min_std.
+    include_policy: candidate 0 of every state in every iteration is delta = 0, so the best candidate seen is never worse than the policy under the
+    scorer.  scorer: (noise [T, B, na], init [S, ns]) -> ret [K, B] (None: engine_policy_scorer).
+    -> dict(noise [S, T, na] the final mean, std [S, T, na], best_noise [S, T, na] / best_score [S] the best candidate seen in any iteration, history
+    [n_iters, S], elites [S, n_elites] of the last iteration, policy_score [S] the score of delta = 0 in the first iteration (None without
+    include_policy)), device tensors; nothing is read back."""
+    T, N = _check_counts(horizon, n_candidates)
+    E, n_iters = int(n_elites), int(n_iters)
+    if not (1 <= E <= N):
+        raise ValueError("n_elites must be in 1 ... n_candidates = %d, got %r" % (N, n_elites))
+    if n_iters < 1:
+        raise ValueError("n_iters must be positive, got %r" % (n_iters,))
+    if not (0.0 <= float(alpha) < 1.0):
+        raise ValueError("alpha must be in [0, 1), got %r" % (alpha,))
+    noise_clip = float(noise_clip)
+    if not (noise_clip > 0.0 and np.isfinite(noise_clip)):
+        raise ValueError("noise_clip must be positive and finite, got %r" % (noise_clip,))
+    scorer, states, na = _setup_policy(engine, states, scorer, na, gamma, stop_at_done)
+    S, dev = states.shape[0], states.device
+    mean = _time_major_param(0.0 if init_mean is None else init_mean, T, S, na, dev, 'init_mean')
+    std = _time_major_param(init_std, T, S, na, dev, 'init_std')
+    alpha, min_std = float(alpha), float(min_std)
+    best_score = torch.full((S,), float('-inf'), device=dev, dtype=torch.float32)
+    best_noise = torch.zeros(T, S, na, device=dev, dtype=torch.float32)
+    history = torch.empty(n_iters, S, device=dev, dtype=torch.float32)
+    policy_score = None
+    for it in range(n_iters):
+        eps = torch.randn(T, S, N, na, generator=generator, device=dev, dtype=torch.float32)
+        d = torch.clamp(mean + std * eps, -noise_clip, noise_clip)
+        if include_policy:
+            d[:, :, 0] = 0.0                                                              # the policy itself rides along in every iteration
+        scores = aggregate_heads(scorer(d.reshape(T, S * N, na), states), aggregate).reshape(S, N)
+        if include_policy and it == 0:
+            policy_score = scores[:, 0].clone()
+        vals, idx = torch.topk(scores, E, dim=1)                                          # sorted: column 0 is the iteration's best
+        elites = d.gather(2, idx.view(1, S, E, 1).expand(T, S, E, na)).double()
+        e_mean = elites.sum(dim=2, keepdim=True) / E
+        e_std = torch.sqrt(((elites - e_mean) ** 2).sum(dim=2, keepdim=True) / E)
+        mean = alpha * mean + (1.0 - alpha) * e_mean.float()
+        std = torch.clamp(alpha * std + (1.0 - alpha) * e_std.float(), min=min_std)
+        better = vals[:, 0] > best_score
+        best_score = torch.where(better, vals[:, 0], best_score)
+        best_noise = torch.where(better.view(1, S, 1), elites[:, :, 0].float(), best_noise)
+        history[it] = vals.mean(dim=1)
+    tm = lambda x: x.permute(1, 0, 2).contiguous()
+    return dict(noise=tm(mean[:, :, 0]), std=tm(std[:, :, 0]), best_noise=tm(best_noise), best_score=best_score, history=history, elites=idx,
+                policy_score=policy_score)
+
+
 class ShootingController(object):
     """Model-predictive control by CEM with a warm start, with the policy's call shape: get_actions(obs [S, ns]) -> (actions [S, na], {}).
     Every call plans `horizon` steps ahead from obs, returns the first action of the plan's mean and keeps the rest: the next call starts from the
     previous mean shifted by one step, its last row reset to init_mean's last row (std starts from init_std every time).
     The action comes back as float64 NumPy, as GaussianMLPPolicy.get_actions gives it -- one read-back per call, behind the planner.
-    grad_steps > 0 plans with plan_cem_gd (grad_lr, refine, grad_scorer) instead."""
+    grad_steps > 0 plans with plan_cem_gd (grad_lr, refine, grad_scorer) instead.
+    policy_prior=True plans with plan_cem_policy (noise_clip) around the engine's policy instead: the warm start is the noise mean shifted by one step,
+    its last row reset to 0, and the action is clip(policy mean(obs) + noise mean[0])."""
 
     def __init__(self, engine, horizon, n_candidates, n_elites, n_iters, init_mean=None, init_std=1.0, alpha=0.0, min_std=0.0, gamma=1.0,
-                 aggregate='mean', generator=None, stop_at_done=True, scorer=None, na=None, grad_steps=0, grad_lr=0.05, refine='elites', grad_scorer=None):
+                 aggregate='mean', generator=None, stop_at_done=True, scorer=None, na=None, grad_steps=0, grad_lr=0.05, refine='elites', grad_scorer=None,
+                 policy_prior=False, noise_clip=2.0):
         self.engine, self.horizon, self.scorer, self.na = engine, int(horizon), scorer, (engine.na if engine is not None else na)
         # grad_steps > 0: plan_cem_gd with these settings in plan_cem's place (0: plan_cem, as before)
         self.grad_steps, self.grad_kw = _check_refine(grad_steps, grad_lr, 'adam'), dict(grad_lr=grad_lr, refine=refine, grad_scorer=grad_scorer)
         if refine not in ('elites', 'all'):
             raise ValueError("refine: %r is neither 'elites' nor 'all'" % (refine,))
+        # policy_prior: plan_cem_policy over noise around the engine's policy; the warm start is the shifted NOISE mean, its last row reset to 0
+        self.policy_prior, self.noise_clip = bool(policy_prior), float(noise_clip)
+        if self.policy_prior and self.grad_steps > 0:
+            raise ValueError("policy_prior=True plans in noise space; grad_steps > 0 (gradients with respect to open-loop actions) cannot be combined with it")
+        if self.policy_prior and engine is None:
+            raise ValueError("policy_prior=True needs an engine (its policy_actions gives the mean the noise is added to)")
         self.init_mean, self.init_std = init_mean, init_std
         self.kw = dict(n_candidates=n_candidates, n_elites=n_elites, n_iters=n_iters, alpha=alpha, min_std=min_std, gamma=gamma, aggregate=aggregate,
                        generator=generator, stop_at_done=stop_at_done)
@@ -351,10 +448,22 @@ class ShootingController(object):
         fresh = self._fresh(mean.shape[0], mean.device)
         return torch.cat([mean[:, 1:], fresh[:, -1:]], dim=1)
 
+    def shifted_noise(self, noise):
+        """[S, T, na] -> the same one step on: row t <- row t + 1, the last row <- 0 (the policy itself)"""
+        return torch.cat([noise[:, 1:], torch.zeros_like(noise[:, -1:])], dim=1)
+
     def get_actions(self, observations):
         obs = torch.as_tensor(np.asarray(observations) if not torch.is_tensor(observations) else observations)
         S = obs.shape[0] if obs.dim() == 2 else 1
         start = self._mean if (self._mean is not None and self._mean.shape[0] == S) else self.init_mean
+        if self.policy_prior:
+            plan = plan_cem_policy(self.engine, obs, self.horizon, init_mean=start, init_std=self.init_std, noise_clip=self.noise_clip, scorer=self.scorer,
+                                   na=self.na, **self.kw)
+            self.last_plan = plan
+            self._mean = self.shifted_noise(plan['noise'])
+            obs2 = obs.reshape(S, -1).to(device=plan['noise'].device, dtype=torch.float32)
+            pmean = self.engine.policy_actions(obs2)[1]                                   # one policy forward, not a second scoring call
+            return torch.clamp(pmean + plan['noise'][:, 0], -1.0, 1.0).double().cpu().numpy(), {}
         if self.grad_steps > 0:
             plan = plan_cem_gd(self.engine, obs, self.horizon, grad_steps=self.grad_steps, init_mean=start, init_std=self.init_std, scorer=self.scorer,
                                na=self.na, **dict(self.kw, **self.grad_kw))
