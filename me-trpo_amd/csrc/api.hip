@@ -118,6 +118,18 @@ extern "C" int32_t metrpo_debug_last_update(const metrpo_ctx* c, int32_t* out) {
     return METRPO_OK;
 }
 
+// Diagnostics hook (not part of include/metrpo.h; tests/test_gpu_trpo_solve.py): the Fisher-vector products of the last CG solve metrpo_trpo_update / _begin (and their _fvp forms)
+// enqueued, as the host wrote them down (no device work, no synchronisation; after an update the last noted LAUNCH is a line-search evaluation).  out[8] = family and UpdOp as
+// launched of the products (op 1, or 3 = OP_FVPC where they read the gradient launch's activation cache; -1: the solve made none, -2: they disagree), index into the fused 2 x 32
+// kernel table (-1 elsewhere), number of products (the explicit step-scale product included), then four flags: SolveScope::cache_activations, SolveScope::publish_image, the CG
+// vector steps ran as tails of the reductions (0: stand-alone k_cg_* kernels), a separate FVP batch was in force.  family = -1: no solve yet.
+extern "C" int32_t metrpo_debug_last_solve(const metrpo_ctx* c, int32_t* out) {
+    if (!c || !out) return METRPO_ENULL;
+    const auto& s = c->solve_last;
+    out[0] = s.family; out[1] = s.op; out[2] = s.table; out[3] = s.n_fvp; out[4] = s.cache_activations; out[5] = s.publish_image; out[6] = s.fused_tails; out[7] = s.fvp_batch;
+    return METRPO_OK;
+}
+
 // Diagnostics hook (tests/test_gpu_api.py): outgrown workspaces this context holds back instead of freeing them inside a launch entry point (metrpo_internal.h: ws_grow);
 // sweep != 0 frees them now (a synchronising call, like the sweep the library runs by itself past WS_RETIRED_MAX).  Returns the count in front of the sweep.
 extern "C" int32_t metrpo_debug_ws_retired(metrpo_ctx* c, unsigned long long* bytes, int32_t sweep) {
@@ -848,6 +860,14 @@ static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metr
         tl.vpos = c->d_pol_vpos.p; tl.imgval = c->d_pol_imgval.p;
     }
     if ((rc = launch_loss_grad(c, b, v.gout, st, fused ? &tl : nullptr, solve))) return rc;
+    // host-side record of this solve's products (metrpo_debug_last_solve): the gradient launch fixes the family, every product adds what upd_last says of it
+    c->solve_last = {c->upd_last.family, -1, c->upd_last.table, 0, solve.cache_activations ? 1 : 0, solve.publish_image ? 1 : 0, fused ? 1 : 0, sub ? 1 : 0};
+    auto note_fvp = [&]() {
+        auto& s = c->solve_last;
+        if (s.n_fvp > 0 && (s.op != c->upd_last.op || s.family != c->upd_last.family || s.table != c->upd_last.table)) s.op = -2;      // (the products of one solve disagree)
+        else { s.family = c->upd_last.family; s.op = c->upd_last.op; s.table = c->upd_last.table; }
+        s.n_fvp += 1;
+    };
     if (!fused) {
         AR(v.gout, 1 + P);
         hipLaunchKernelGGL(k_cg_init, dim3(1), dim3(1024), 0, st, P, v.gout, v.x, v.r, v.p, c->d_vf.p, v.scal);   // same block shape as the fused tail: identical summation order
@@ -862,6 +882,7 @@ static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metr
         tl.op = 1; tl.last = (i == pr->cg_iters - 1) ? 1 : 0;
         if (fold_try && tl.last && implicit_hd) arm_try0();
         if ((rc = launch_fvp_tail(c, hb, c->d_vf.p, v.p, v.z, fused ? &tl : nullptr, st, solve))) return rc;
+        note_fvp();
         if (fused) continue;
         AR(v.z, P);
         hipLaunchKernelGGL(k_cg_step, dim3(1), dim3(1024), 0, st, tl, pr->cg_iters);
@@ -870,6 +891,7 @@ static int run_trpo_update_impl(metrpo_ctx* c, const metrpo_batch* b, const metr
         tl.op = 2; tl.last = 0;
         if (fused && fold_try) arm_try0();
         if ((rc = launch_fvp_tail(c, hb, c->d_vf.p, v.x, v.z, fused ? &tl : nullptr, st, solve))) return rc;
+        note_fvp();
         if (!fused) {
             AR(v.z, P);
             hipLaunchKernelGGL(k_cg_finish, dim3(1), dim3(1024), 0, st, P, pr->reg_coeff, pr->max_kl, v.x, v.z, v.step, v.scal);

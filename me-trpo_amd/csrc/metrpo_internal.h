@@ -156,6 +156,9 @@ struct metrpo_ctx {
     // UpdOp as launched (OP_FVPC where the fused kernel took it), index into policy_mfma.hip's table (-1 elsewhere), sample tile of the generic kernels (0 elsewhere),
     // partial rows handed to k_finalize (0 on the GEMM path), splits / kchunk of the GEMM path's gradient GEMMs (0 elsewhere)
     struct UpdLast { int family = -1, op = -1, table = -1, pt = 0, nrows = 0, splits = 0, kchunk = 0; } upd_last;
+    // the Fisher-vector products of the last CG solve run_trpo_update enqueued (metrpo_debug_last_solve), written on the host from upd_last after each of them:
+    // family / op / table of the last product (-1: the solve made none), their count (step-scale product included), and the SolveScope / fusion the solve ran under
+    struct SolveLast { int family = -1, op = -1, table = -1, n_fvp = 0, cache_activations = 0, publish_image = 0, fused_tails = 0, fvp_batch = 0; } solve_last;
     std::string rollout_note;   // why the last metrpo_rollout left the fast dispatch table ("" when it did not): metrpo_rollout_note
     int fallback_logged = 0;  // a rollout shape that fell off the fast dispatch table has been reported once (METRPO_VERBOSE)
     std::vector<std::pair<void*, size_t>> ws_retired; size_t ws_retired_bytes = 0;   // outgrown workspaces and their sizes (ws_grow below): freed by metrpo_destroy, or by one sweep once they pass WS_RETIRED_MAX

@@ -232,6 +232,17 @@ class Engine(object):
         d['family'] = {-1: None, 0: 'generic', 1: 'mfma', 2: 'gemm', 3: 'fused3'}[d['family']]
         return d
 
+    def last_solve_launch(self):
+        """Diagnostics: the Fisher-vector products of the last CG solve a trpo_update enqueued, as the host noted them: dict(family (as last_update_launch), op (1 FVP,
+        3 cached FVP of the fused 2 x 32 kernels; -1: the solve made no product, -2: its products disagree), table, n_fvp (the explicit step-scale product included),
+        cache_activations, publish_image, fused_tails (False: stand-alone CG kernels), fvp_batch (a separate FVP batch was in force))."""
+        out = (C.c_int32 * 8)()
+        self._chk(lib.metrpo_debug_last_solve(self._ctx, out))
+        d = dict(zip(('family', 'op', 'table', 'n_fvp'), (int(x) for x in out[:4])))
+        d['family'] = {-1: None, 0: 'generic', 1: 'mfma', 2: 'gemm', 3: 'fused3'}[d['family']]
+        d.update(zip(('cache_activations', 'publish_image', 'fused_tails', 'fvp_batch'), (bool(x) for x in out[4:8])))
+        return d
+
     def retired_workspaces(self, sweep=False):
         """Diagnostics: (count, bytes) of outgrown workspaces the context keeps until destroy (a launch entry point never frees: hipFree waits for every stream);
         sweep=True frees them now (synchronising)."""

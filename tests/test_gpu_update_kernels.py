@@ -6,7 +6,8 @@ exactly one valid sample; in the per-sample and the broadcast form of old_log_st
 the CPU by tests/test_update_cases.py).  Bounds: the rows LOSS_RTOL, KL_ATOL / KL_RTOL, GRAD_REL_L2, FVP_REL_L2 of tests/tolerances.py on the
 whole vector, and tolerances.block_bound on every variable W_l, b_l, log_std of each gradient and FVP.
 That a case runs on the kernel it names is asserted from what the library reports of its launches (Engine.last_update_launch), here and in
-test_cases_reach_every_instantiation.  Out of scope: the cached FVP (OP_FVPC), the CG / Adam tails, the line search, the VJP.
+test_cases_reach_every_instantiation.  Out of scope: the Adam tails, the VJP; the cached FVP (OP_FVPC), the CG tails and the
+line search are held by tests/test_gpu_trpo_solve.py, on the same case table.
 
 Observed on an MI355X (worst share of each bound over the file, per family): profiles/r10_update_kernels.txt."""
 import json

@@ -64,6 +64,8 @@ KL_RTOL = 1e-4
 # Both vector rows also hold per variable (W_l, b_l, log_std), dealt out by block size: block_bound() below.  tests/test_gpu_update_kernels.py holds every
 # instantiation of the update kernels to these rows at the tile edges (328 cases); worst share of a bound observed there: loss 0.12, KL 0.42,
 # gradient 0.31 whole / 0.58 per block, FVP 0.50 whole / 0.52 per block (profiles/r10_update_kernels.txt).
+# The solve built from those kernels -- cached products, CG tails, step scale, line search -- is held on the same cases by tests/test_gpu_trpo_solve.py (the
+# SOLVE_* rule below; profiles/r12_trpo_solve.txt).
 GRAD_REL_L2 = 1e-5          # gradient g (1e-5): per-sample back-propagation in fp32, sums over N in float64.  Observed 1.1e-6
 FVP_REL_L2 = 1e-5           # Fisher-vector product (1e-4; held 10x tighter): tangent + back-propagation in fp32, float64 sums over N.  Observed 1.2e-7
 CG_COS = 0.9999             # step direction d after 10 CG iterations (cosine >= 0.9999, rel-L2 <= 1e-3: ten FVPs amplify rounding by the
@@ -71,6 +73,16 @@ CG_REL_L2 = 3e-4            # Fisher matrix's condition number, ~1e3 on the fixt
 STEP_SCALE_RTOL = 1e-3      # beta = sqrt(2 delta / d.Hd): inherits d's figure
 THETA_STEP_REL_L2 = 5e-4    # theta_new - theta_old = -ratio * beta * d: d's and beta's figures added.  Observed 8.3e-5
 POST_UPDATE_RTOL = 5e-3     # loss / KL evaluated at the (slightly different) accepted theta
+
+# The CG solve at the tile edges (tests/test_gpu_trpo_solve.py; table and float64 side tests/solve_cases.py): d after k = 0 ... 10 iterations, beta and
+# step = beta d, whole vector and per variable W_l, b_l, log_std, are held to a bound derived per case from the REFERENCE, not to the ten-iteration
+# figures above: the movement of the float64 solve (oracle.metrpo_oracle, started from the device's gradient) when each of its products z_i is
+# perturbed by what the FVP_REL_L2 row already admits -- a seeded random direction whose norm per variable block is block_bound(FVP_REL_L2, z_i[blk], z_i)
+# -- worst over SOLVE_DRAWS draws, times SOLVE_MARGIN because random directions underestimate the worst direction.  No bound lies below 1e-12 of the
+# reference's norm (the float64 side's own rounding).  tests/test_solve_cases.py holds, without the library: every per-block bound is <= 0.1 of its
+# block, and a product with one block scaled by 1 + 1e-3, a left-out tile, included invalid samples, a stale CG vector or a missing reg term exceeds one.
+SOLVE_DRAWS = 4
+SOLVE_MARGIN = 2.0
 
 # --- several ranks against one (sharded sums exchanged in float64): row 13 ------------------------------------------------------------------------------
 MULTI_RANK_GRAD = 2e-6      # x max |g|: the same float64 partial sums added in another order, over fp32 per-sample terms
