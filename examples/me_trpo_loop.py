@@ -76,6 +76,8 @@ def main(argv=None):
                     help="with --shooting: refine each CEM iteration's elites by this many gradient steps on the ensemble's return (planning.plan_cem_gd); 0: plain CEM")
     ap.add_argument('--shooting-policy-prior', action='store_true',
                     help="with --shooting: plan in noise space around the current policy (planning.plan_cem_policy: a = clip(policy(s) + noise), noise = 0 is the policy) instead of over open-loop actions")
+    ap.add_argument('--shooting-noise-grad-steps', type=int, default=0,
+                    help="with --shooting --shooting-policy-prior: refine each CEM iteration's elite noise sequences by this many gradient steps on the closed-loop return, the policy path included (planning.plan_cem_policy_gd); 0: plain CEM in noise space")
     args = ap.parse_args(argv)
     say = (lambda *a: None) if args.quiet else print
     np.random.seed(0)
@@ -104,7 +106,7 @@ def main(argv=None):
             # the shifted plan as the next step's warm start
             actor = M.ShootingController(eng, horizon=10, n_candidates=64, n_elites=8, n_iters=3, init_std=0.5, gamma=0.99,
                                          generator=torch.Generator(device=eng.device).manual_seed(it), grad_steps=args.shooting_grad_steps,
-                                         policy_prior=args.shooting_policy_prior)
+                                         policy_prior=args.shooting_policy_prior, noise_grad_steps=args.shooting_noise_grad_steps)
         Os, As, real_cost = real.rollouts(lambda s: actor.get_actions(s)[0], T, args.traj)
         x_all, y_all = DT.trajectories_to_pairs(Os, As)
         DT.add_rollouts(x_all, y_all, data, val, 'triplet', True, 0.1, in_rms, out_rms)

@@ -874,6 +874,54 @@ typedef struct {
 int32_t metrpo_score_policy_actions(metrpo_ctx* ctx, const metrpo_score_policy_actions_args* args, void* stream);
 int32_t metrpo_last_score_policy_actions_kernel(const metrpo_ctx* ctx);   /* -1 none yet, 0 generic, 1 fused */
 
+/* ---- the GRADIENT of every head's closed-loop return with respect to the NOISE sequences around the policy: the fourth corner of the return / gradient
+ * family (open loop: metrpo_score_actions / metrpo_score_actions_grad; closed loop: metrpo_score_policy_actions / this), first-order information for
+ * planners that refine candidates in noise space.  Additions to ABI 4: no struct above changes, no option key is added, METRPO_ABI_VERSION stays.
+ * Per (head k, candidate b), R = ret[k][b] EXACTLY as metrpo_score_policy_actions defines it above; ret, len and act_out carry that call's bits on the
+ * same path.  SIGN: the gradient of the RETURN, the ascent direction.
+ *   grad[k][t][b][:] = dR / d noise_t      TOTAL: every later step's policy sees the states this noise moved
+ *   lam0[k][b][:]    = dR / d s_0          policy path included
+ *   grad_mean        = (grad_0 + ... + grad_K-1) / K     from the stored fp32 values, summed in head order
+ * Reverse recursion from lambda_T = 0, metrpo_score_actions_grad's with one more term:
+ *   G        = lambda_t+1 - w_t dc/dx_next
+ *   gU       = -w_t dc/du + (action rows of F^T G)
+ *   gm       = gate(a_t) gU                                    dR / d a_t, total
+ *   grad_t   = gm                                              noise_in_std = 0
+ *            = gm * exp(max(log_std, LOG_MIN_STD))             noise_in_std = 1 (the sigma of the forward sweep)
+ *   lambda_t = G + (state rows of F^T G) + J_pi(s_t)^T gm      the policy path
+ * Conventions: those of metrpo_score_actions_grad and the BPTT sweep -- the clip gate passes iff -1 <= a_t <= 1 on the head's own UNCLIPPED
+ * a_t = mean_t + noise_t sigma (stored by the forward sweep, so the two sweeps cannot disagree by a rounding); relu'(h) = [h > 0]; tanh' = 1 - p^2 of
+ * the recomputed activation; the alive mask is a constant; gamma^t in float64, rounded to fp32 where it becomes a weight.  A step behind a candidate's
+ * last counted step reads 0, and so does a clipped action.  d_noise NULL: the gradient at noise = 0 (bit for bit that of a zero tensor).
+ * Which kernel runs (metrpo_last_score_policy_actions_grad_kernel: -1 none yet, 0 generic, 1 fused):
+ *   fused (score_policy_actions_grad.hip: per chunk two stream-ordered launches -- metrpo_score_policy_actions' fused step with states, weights and the
+ *     head's unclipped actions stored, then a reverse sweep of four 16-candidate tiles of one head per workgroup with the policy's input adjoint behind
+ *     the clip gate) -- exactly metrpo_score_policy_actions' fused shape class.
+ *   generic (one thread per (candidate, head), activations in LDS) -- everything else, and force_generic.
+ * The two agree to rounding, not bits.  The workspace (XS | WT | AW of a chunk of candidates) is ctx-owned and stays within 2^26 floats by chunking;
+ * chunk > 0 sets the candidates per pass instead.  Chunking changes no bit of any output.  No atomics: repeated calls are bit-identical.  Stream-ordered,
+ * neither frees nor synchronises.  Leaves theta, both Adam states, the Philox state, the ensemble and every other metrpo_last_* reporter untouched.
+ * B == 0 or T == 0: METRPO_OK, nothing written.  METRPO_ENULL: ctx, args, d_init_obs, d_grad; METRPO_EINVAL: B < 0, T < 0, S < 1, B % S != 0, gamma not
+ * finite, chunk < 0; METRPO_ESTATE: as metrpo_score_policy_actions. */
+typedef struct {
+    int32_t B, T, S;            /* as metrpo_score_policy_actions_args */
+    int32_t stop_at_done;
+    int32_t noise_in_std;
+    int32_t force_generic;
+    int32_t chunk;              /* candidates per workspace pass; 0: the library's rule (2^26 floats) */
+    double  gamma;
+    const float* d_init_obs;    /* [S][ns] */
+    const float* d_noise;       /* [T][B][na], or NULL: gradient at noise = 0 (the deterministic policy); never written */
+    float*   d_grad;            /* [K][T][B][na] required: dR_k / d noise_t */
+    float*   d_ret;             /* optional [K][B] */
+    int32_t* d_len;             /* optional [K][B] */
+    float*   d_grad_mean;       /* optional [T][B][na] */
+    float*   d_lam0;            /* optional [K][B][ns]: dR_k / d s_0, policy path included */
+    float*   d_act_out;         /* optional [K][T][B][na]: the unclipped actions taken */
+} metrpo_score_policy_actions_grad_args;
+int32_t metrpo_score_policy_actions_grad(metrpo_ctx* ctx, const metrpo_score_policy_actions_grad_args* args, void* stream);
+int32_t metrpo_last_score_policy_actions_grad_kernel(const metrpo_ctx* ctx);   /* -1 none yet, 0 generic, 1 fused */
+
 #ifdef __cplusplus
 }
 #endif

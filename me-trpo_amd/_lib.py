@@ -127,6 +127,12 @@ class ScorePolicyActionsArgs(C.Structure):
                 ('d_ret_mean', C.c_void_p), ('d_ret_std', C.c_void_p), ('d_act_out', C.c_void_p)]
 
 
+class ScorePolicyActionsGradArgs(C.Structure):
+    _fields_ = [('B', C.c_int32), ('T', C.c_int32), ('S', C.c_int32), ('stop_at_done', C.c_int32), ('noise_in_std', C.c_int32), ('force_generic', C.c_int32),
+                ('chunk', C.c_int32), ('gamma', C.c_double), ('d_init_obs', C.c_void_p), ('d_noise', C.c_void_p), ('d_grad', C.c_void_p),
+                ('d_ret', C.c_void_p), ('d_len', C.c_void_p), ('d_grad_mean', C.c_void_p), ('d_lam0', C.c_void_p), ('d_act_out', C.c_void_p)]
+
+
 SVG_PATHS = {'auto': 0, 'generic': 1, 'gemm': 2}          # metrpo_svg_args.path
 MODEL_ERROR_MAX_HORIZONS = 32          # include/metrpo.h
 
@@ -194,6 +200,8 @@ SYMBOLS = {
     'metrpo_last_score_actions_grad_kernel': (_I, [_P]),
     'metrpo_score_policy_actions': (_I, [_P, C.POINTER(ScorePolicyActionsArgs), _P]),
     'metrpo_last_score_policy_actions_kernel': (_I, [_P]),
+    'metrpo_score_policy_actions_grad': (_I, [_P, C.POINTER(ScorePolicyActionsGradArgs), _P]),
+    'metrpo_last_score_policy_actions_grad_kernel': (_I, [_P]),
     'metrpo_dyn_train_reset': (_I, [_P, _P]),
     'metrpo_dyn_train_step': (_I, [_P, _P, _P, C.POINTER(TrainParams), _P, _P]),
     'metrpo_dyn_eval_losses': (_I, [_P, _P, _P, _L, _D, _P, _P]),

@@ -1139,6 +1139,23 @@ extern "C" int32_t metrpo_score_policy_actions(metrpo_ctx* c, const metrpo_score
 }
 extern "C" int32_t metrpo_last_score_policy_actions_kernel(const metrpo_ctx* c) { return c ? c->last_spol_kernel : METRPO_ENULL; }
 
+// ---- gradient of every head's closed-loop return with respect to the noise sequences around the policy (score_policy_actions_grad.hip) ----
+extern "C" int32_t metrpo_score_policy_actions_grad(metrpo_ctx* c, const metrpo_score_policy_actions_grad_args* a, void* stream) {
+    TraceRange trace_("metrpo:score_policy_actions_grad (per-head return gradients of noise sequences around the policy)");
+    if (!c) return METRPO_ENULL;
+    if (!a) return set_err(c, METRPO_ENULL, "score_policy_actions_grad: args NULL");
+    NEED_DYN(c); NEED_POL(c);
+    if (c->upd_pending) return set_err(c, METRPO_ESTATE, "score_policy_actions_grad: an update begun with metrpo_trpo_update_begin is still open (metrpo_trpo_update_end decides which theta stands)");
+    if (a->B < 0 || a->T < 0) return set_err(c, METRPO_EINVAL, "score_policy_actions_grad: bad B/T");
+    if (a->S < 1 || a->B % a->S != 0) return set_err(c, METRPO_EINVAL, "score_policy_actions_grad: S = " + std::to_string(a->S) + " must be at least 1 and divide B = " + std::to_string(a->B));
+    if (!std::isfinite(a->gamma)) return set_err(c, METRPO_EINVAL, "score_policy_actions_grad: gamma is not finite");
+    if (a->chunk < 0) return set_err(c, METRPO_EINVAL, "score_policy_actions_grad: chunk must not be negative");
+    if (a->B == 0 || a->T == 0) return METRPO_OK;
+    if (!a->d_init_obs || !a->d_grad) return set_err(c, METRPO_ENULL, "score_policy_actions_grad: required pointer is NULL");
+    return run_score_policy_actions_grad(c, a, (hipStream_t)stream);
+}
+extern "C" int32_t metrpo_last_score_policy_actions_grad_kernel(const metrpo_ctx* c) { return c ? c->last_spag_kernel : METRPO_ENULL; }
+
 // ---- 'svg' policy update: value gradients along recorded rollouts (svg_utils.py:12-66; svg.hip) ----
 static int svg_check(metrpo_ctx* c, const metrpo_svg_args* a) {
     if (!a) return set_err(c, METRPO_ENULL, "svg: args NULL");

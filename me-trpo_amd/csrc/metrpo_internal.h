@@ -128,6 +128,7 @@ struct metrpo_ctx {
     int last_sact_kernel = -1; DevBuf<void> d_sact;       // metrpo_score_actions (score_actions.hip): -1 none yet, 0 generic, 1 fused | the generic path's chunk workspace (obs | rew | done | the chunk's actions)
     int last_sagr_kernel = -1; DevBuf<void> d_sagr;       // metrpo_score_actions_grad (score_actions_grad.hip): -1 none yet, 0 generic, 1 fused | a chunk's states and weights (XS | WT)
     int last_spol_kernel = -1; DevBuf<void> d_spol;       // metrpo_score_policy_actions (score_policy_actions.hip): -1 none yet, 0 generic, 1 fused | the generic path's chunk workspace (start | two state rows | act | mean | rew | done | head vectors)
+    int last_spag_kernel = -1; DevBuf<void> d_spag;       // metrpo_score_policy_actions_grad (score_policy_actions_grad.hip): -1 none yet, 0 generic, 1 fused | a chunk's states, weights and per-head actions (XS | WT | AW)
     int spol_chunk_cap = 0;                               // ... test hook (metrpo_debug_score_policy_chunk): at most this many candidates per chunk of its generic path; 0: the 2^26-float rule alone
     DevBuf<void> d_svg; int last_svg_path = -1;         // svg.hip: workspace of metrpo_svg_grad / _update (zeroed copy of the rollouts | mean-adjoint | F | Pi | chunk buffers | lambda_0 | gradient) | -1 none yet, 1 generic, 2 GEMM
     int coop_no_split = 0;                                // switch (metrpo_set_coop_split): 1 keeps the 4-wave form of the cooperative kernel where the head-split form would run
@@ -478,6 +479,10 @@ void launch_sact_aggregate(const float* ret, int B, int K, float* mean, float* s
 int run_score_policy_actions(metrpo_ctx*, const metrpo_score_policy_actions_args*, hipStream_t);
 // score_actions_grad.hip: the body of metrpo_score_actions_grad (arguments checked by the entry point; B, T > 0, B % S == 0, chunk >= 0)
 int run_score_actions_grad(metrpo_ctx*, const metrpo_score_actions_grad_args*, hipStream_t);
+// ... its head-order mean of d_grad [K][n] (k_sagr_mean), for score_policy_actions_grad.hip as well; reports no error of its own
+void launch_sagr_mean(const float* grad, size_t n, int K, float* mean, hipStream_t);
+// score_policy_actions_grad.hip: the body of metrpo_score_policy_actions_grad (arguments checked by the entry point; B, T > 0, B % S == 0, chunk >= 0, policy and dynamics set)
+int run_score_policy_actions_grad(metrpo_ctx*, const metrpo_score_policy_actions_grad_args*, hipStream_t);
 // svg.hip: the body of metrpo_svg_grad / metrpo_svg_update (arguments checked by the entry points); update: the SGD step with `lr` on the ctx theta
 int run_svg(metrpo_ctx*, const metrpo_svg_args*, double lr, bool update, hipStream_t);
 int launch_subsample(metrpo_ctx*, const metrpo_batch* b, const int32_t* d_idx, long long m, double inv_n_global, metrpo_batch* out, double* d_valid_count, hipStream_t);

@@ -4,9 +4,12 @@
 // its first user; the kernels that carry their own copy of the chain keep it.
 //   PolWaveHead     a wave's policy: weight fragments in registers (swimmer 6 + 16 + 8, Ant 16 + 16 + 8), its three bias rows in LDS;
 //                   mean() = the mean's action dims 4 q .. 4 q + 3 of env e in D layout
+//   NoiseTile       the tile's noise block, double-buffered in LDS and committed unclipped (ActTile's prefetch)
+//   PolHeadAdjoint  the policy's input adjoint J_pi(s)^T gm on fragment tables in LDS (at the end of this file; score_policy_actions_grad.hip)
 // No LDS is declared here: every pointer into it is the caller's.  Lane l = (e = l & 15, q = l >> 4).
 #pragma once
 #include "dyn_head_mfma.h"
+#include "dyn_tile_step.h"
 
 // per-wave LDS (floats) of a tile that runs the policy AND a dynamics head under supplied noise: Cfg<>'s whole W_* layout -- ST | NX | ACT | dynamics
 // biases | policy biases at W_BP0 .. W_BP2 (act_wave_floats<> reuses W_BP0 as its second action buffer; here the bias rows are needed) -- and the second
@@ -81,5 +84,113 @@ struct PolWaveHead {
             m1 = MFMA16(wp2[kk + 1], p1[(kk + 1) >> 2][(kk + 1) & 3], m1);
         }
         return m0 + m1;
+    }
+};
+
+// The noise block of a tile ([16][NA] of d_noise [T][B][na] at rows b0 ..): ActTile's two LDS buffers and its prefetch, committed UNCLIPPED (the
+// action is clipped where it is formed).  Rows at and beyond nrows are zero noise and are never read from memory.
+template <class C>
+struct NoiseTile : ActTile<C> {
+    using A = ActTile<C>;
+    __device__ __forceinline__ void commit(int t) {
+        float* dst = A::cur(t);
+#pragma unroll
+        for (int j = 0; j < A::NLD; ++j) asm volatile("" ::"v"(A::a_nx[j]));   // the loaded values are taken on every path (ActTile::commit)
+#pragma unroll
+        for (int j = 0; j < A::NLD; ++j) {
+            const int i = A::lane + 64 * j;
+            if (i < 16 * A::NA) dst[i] = (i < A::nact) ? A::a_nx[j] : 0.0f;
+        }
+    }
+};
+
+// The policy's INPUT adjoint for a tile of 16 envs, on the same transposed chains: given the adjoint gm of the (pre-clip) mean (D layout: register r of lane
+// (e, q) is action dim 4 q + r of env e) it adds J_pi(s)^T gm into gS (D layout of the state, as DynHeadAdjoint returns it).  This restates the policy part
+// of k_det_mfma<DET_BWD> (bptt_mfma.hip: its O_PF0 / O_PF1 forward and O_PB2 / O_PB1 / O_PB0 adjoint fragment tables, the recomputed hidden layers and the
+// three chains behind the clip gate) for score_policy_actions_grad.hip; bptt_mfma.hip keeps its own copy (the note in dyn_head_adjoint.h).
+//   hidden()  p0, p1 = the two tanh layers of env e from its LDS state row: PolWaveHead::mean's statements on LDS fragments (the mean itself is not formed)
+//   run()     e1 = W2 . gm * (1 - p1^2);  e0 = W1 . e1 * (1 - p0^2);  gS += W0 . e0
+// The fragment tables and the two hidden bias rows are one LDS image shared by the waves of a workgroup.
+template <class C>
+struct PolHeadAdjoint {
+    static constexpr int NS = C::NS, NA = C::NA, OUT_CB = C::OUT_CB, NS_KS = C::NS_KS, PH = 32;
+    static_assert(C::PH_CB == 2 && C::pW1 - C::pb0 == PH, "the tables are laid out for the 2 x 32 policy");
+    static constexpr int RK = (NA < 4) ? NA : 4;                       // k-steps of the first adjoint layer that are not padding
+    // table (floats): [k-step][col-block][64 lanes] per layer, then the bias rows of the hidden layers
+    static constexpr int O_PF0 = 0, O_PF1 = O_PF0 + NS_KS * 2 * 64, O_PB2 = O_PF1 + 8 * 2 * 64, O_PB1 = O_PB2 + RK * 2 * 64, O_PB0 = O_PB1 + 8 * 2 * 64,
+                         O_BP0 = O_PB0 + 8 * OUT_CB * 64, O_BP1 = O_BP0 + PH, FLOATS = O_BP1 + PH;
+    const float* tab;
+    int lane;
+
+    // every thread of the workgroup calls it (nthr threads, thread tid); each element is written by one thread; the caller's barrier follows
+    static __device__ __forceinline__ void fill(float* tab, const float* __restrict__ theta, int tid, int nthr) {
+        for (int i = tid; i < FLOATS; i += nthr) {
+            float w = 0.0f;
+            const int ln = i & 63, cc = ln & 15, qq = ln >> 4;
+            if (i < O_PF1) { const int f = i >> 6, s = f >> 1, cb = f & 1, in = 4 * s + qq; if (in < NS) w = theta[C::pW0 + in * PH + 16 * cb + cc]; }
+            else if (i < O_PB2) { const int f = (i - O_PF1) >> 6, kk = f >> 1, cb = f & 1; w = theta[C::pW1 + chained_in(kk, qq) * PH + 16 * cb + cc]; }
+            else if (i < O_PB1) { const int f = (i - O_PB2) >> 6, r = f >> 1, cb = f & 1, d = 4 * qq + r; if (d < NA) w = theta[C::pW2 + (16 * cb + cc) * NA + d]; }
+            else if (i < O_PB0) { const int f = (i - O_PB1) >> 6, kk = f >> 1, cb = f & 1; w = theta[C::pW1 + (16 * cb + cc) * PH + chained_in(kk, qq)]; }
+            else if (i < O_BP0) { const int f = (i - O_PB0) >> 6, kk = f / OUT_CB, cb = f % OUT_CB, dim = 16 * cb + cc; if (dim < NS) w = theta[C::pW0 + dim * PH + chained_in(kk, qq)]; }
+            else if (i < O_BP1) w = theta[C::pb0 + (i - O_BP0)];
+            else w = theta[C::pb1 + (i - O_BP1)];
+            tab[i] = w;
+        }
+    }
+
+    __device__ __forceinline__ float frag(int off, int ks, int cb, int ncb) const { return tab[off + (ks * ncb + cb) * 64 + lane]; }
+
+    __device__ __forceinline__ void hidden(f32x4 (&p0)[2], f32x4 (&p1)[2], const float* ST, int e) const {
+        const int q = lane >> 4;
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) p0[cb] = *(const f32x4*)&tab[O_BP0 + 16 * cb + 4 * q];
+#pragma unroll
+        for (int s = 0; s < NS_KS; ++s) {
+            const int f = 4 * s + q;
+            const float x = (f < NS) ? ST[e * NS + f] : 0.0f;
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) p0[cb] = MFMA16(frag(O_PF0, s, cb, 2), x, p0[cb]);
+        }
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) {
+            p1[cb] = *(const f32x4*)&tab[O_BP1 + 16 * cb + 4 * q];
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) p0[cb][rr] = tanh_fast(p0[cb][rr]);
+        }
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk)
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) p1[cb] = MFMA16(frag(O_PF1, kk, cb, 2), p0[kk >> 2][kk & 3], p1[cb]);
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) p1[cb][rr] = tanh_fast(p1[cb][rr]);
+    }
+
+    __device__ __forceinline__ void run(f32x4 (&gS)[OUT_CB], const f32x4& gm, const f32x4 (&p0)[2], const f32x4 (&p1)[2]) const {
+        f32x4 e1[2], e0[2];
+        e1[0] = e1[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int r = 0; r < RK; ++r)
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) e1[cb] = MFMA16(frag(O_PB2, r, cb, 2), gm[r], e1[cb]);
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) {
+            e0[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int r = 0; r < 4; ++r) e1[cb][r] *= fmaf(-p1[cb][r], p1[cb][r], 1.0f);
+        }
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk)
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) e0[cb] = MFMA16(frag(O_PB1, kk, cb, 2), e1[kk >> 2][kk & 3], e0[cb]);
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) e0[cb][r] *= fmaf(-p0[cb][r], p0[cb][r], 1.0f);
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk)
+#pragma unroll
+            for (int cb = 0; cb < OUT_CB; ++cb) gS[cb] = MFMA16(frag(O_PB0, kk, cb, OUT_CB), e0[kk >> 2][kk & 3], gS[cb]);
     }
 };

@@ -28,6 +28,7 @@
 // launch over d_grad adding in head order (k_sact_aggregate's style).  No atomics anywhere: repeated calls are bit-identical.
 #include "dyn_tile_step.h"
 #include "dyn_head_adjoint.h"
+#include "sact_sum.h"
 #include <algorithm>
 #include <cmath>
 
@@ -42,21 +43,6 @@ struct SagrK {
     float* XS; float* WT;     // [K][T+1][n][ns], [K][T][n]
     float* ret; int32_t* len; // [K][B], optional
     float* grad; float* lam0; // [K][T][B][na], optional [K][B][ns]
-};
-
-// metrpo_score_actions' step of the return (score_actions.hip: SactSum) with the step's weight handed out: gamma^t carried in float64 by repeated
-// multiplication and rounded to fp32 where it becomes a weight; a step that is not counted has weight 0 and adds nothing
-struct SagrSum {
-    double sum = 0.0, disc = 1.0;
-    int n = 0;
-    bool alive = true;
-    __device__ __forceinline__ float step(float rew, bool done, double gamma, int stop) {
-        const float w = alive ? (float)disc : 0.0f;
-        if (alive) { sum += disc * (double)rew; ++n; }
-        disc *= gamma;
-        if (stop && done) alive = false;
-        return w;
-    }
 };
 
 // tile_rollout's sink of the forward sweep: b0 is the tile's first candidate in the batch, the chunk's column is b - c0
@@ -316,33 +302,6 @@ __global__ void k_sagr_gen_fwd(ProblemDesc pd, SagrK r, const float* __restrict_
     }
 }
 
-// d(w cost)/du -> gU (written), d(w cost)/dx_next -> added into G: bptt.hip's cost_adjoint (:54-78), called with w = -w_t for the gradient of the return
-__device__ __forceinline__ void sagr_cost_adjoint(int env, int ns, int na, const float* xn, const float* u, float w, float* gU, float* G, int LD, int tid) {
-    float su2 = 0.0f;
-    for (int d = 0; d < na; ++d) { const float a = u[d * LD + tid]; su2 = fmaf(a, a, su2); }
-    float cu = 0.0f;                                         // gU[d] = cu * u[d]
-    switch (env) {
-    case METRPO_ENV_SWIMMER: G[5 * LD + tid] -= w; cu = w * 1e-2f * 2.0f / (float)na; break;
-    case METRPO_ENV_HALF_CHEETAH: {
-        const float inner = xn[9 * LD + tid] - 1e-1f * 0.5f * su2;
-        const float p = (inner >= -10.0f && inner <= 10.0f) ? 1.0f : 0.0f;
-        G[9 * LD + tid] -= w * p; cu = w * p * 1e-1f; break;
-    }
-    case METRPO_ENV_ANT: G[15 * LD + tid] -= w; cu = w * 1e-2f; break;
-    case METRPO_ENV_HUMANOID: G[(ns - 1) * LD + tid] += w * 2.0f * (xn[(ns - 1) * LD + tid] - 1.5f); cu = w * 2e-5f; break;
-    case METRPO_ENV_HOPPER: {
-        G[5 * LD + tid] -= w; cu = w * 0.01f;
-        if (0.45f - xn[0 * LD + tid] > 0.0f) G[0 * LD + tid] -= w * 10.0f;
-        const float a1 = xn[1 * LD + tid];
-        if (fabsf(a1) - 0.2f > 0.0f) G[1 * LD + tid] += w * 10.0f * (a1 > 0.0f ? 1.0f : -1.0f);
-        for (int i = 2; i < ns; ++i) { const float v = xn[i * LD + tid]; if (fabsf(v) - 100.0f > 0.0f) G[i * LD + tid] += w * (v > 0.0f ? 1.0f : -1.0f); }
-        break;
-    }
-    case METRPO_ENV_SNAKE: G[7 * LD + tid] -= w; cu = w * 1e-2f; break;
-    }
-    for (int d = 0; d < na; ++d) gU[d * LD + tid] = cu * u[d * LD + tid];
-}
-
 __global__ void k_sagr_gen_bwd(ProblemDesc pd, SagrK r, const float* __restrict__ dynp, const float* __restrict__ norm) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int LD = blockDim.x, tid = threadIdx.x;
@@ -427,6 +386,11 @@ __global__ void __launch_bounds__(256) k_sagr_mean(const float* __restrict__ gra
     }
 }
 
+// ... for score_policy_actions_grad.hip as well (metrpo_internal.h); it reports no error of its own
+void launch_sagr_mean(const float* grad, size_t n, int K, float* mean, hipStream_t st) {
+    hipLaunchKernelGGL(k_sagr_mean, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st, grad, n, K, mean);
+}
+
 // -------------------------------------------------------------------------------------------------
 typedef void (*sagr_kernel_t)(SagrK, const float*, const float*);
 struct SagrEntry { int env; sagr_kernel_t fwd, bwd; int fwd_floats, bwd_floats; };
@@ -477,8 +441,7 @@ int run_score_actions_grad(metrpo_ctx* c, const metrpo_score_actions_grad_args* 
         HIP_TRY(c, hipGetLastError());
     }
     if (a->d_grad_mean != nullptr) {
-        const size_t n = T * B * pd.na;
-        hipLaunchKernelGGL(k_sagr_mean, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st, a->d_grad, n, (int)K, a->d_grad_mean);
+        launch_sagr_mean(a->d_grad, T * B * pd.na, (int)K, a->d_grad_mean, st);
         HIP_TRY(c, hipGetLastError());
     }
     c->last_sagr_kernel = en != nullptr ? 1 : 0;

@@ -34,23 +34,6 @@ struct SpolK {
     float* ret; int32_t* len; float* act_out;
 };
 
-// The noise block of a tile ([16][NA] of d_noise [T][B][na] at rows b0 ..): ActTile's two LDS buffers and its prefetch, committed UNCLIPPED (the
-// action is clipped where it is formed).  Rows at and beyond nrows are zero noise and are never read from memory.
-template <class C>
-struct NoiseTile : ActTile<C> {
-    using A = ActTile<C>;
-    __device__ __forceinline__ void commit(int t) {
-        float* dst = A::cur(t);
-#pragma unroll
-        for (int j = 0; j < A::NLD; ++j) asm volatile("" ::"v"(A::a_nx[j]));   // the loaded values are taken on every path (ActTile::commit)
-#pragma unroll
-        for (int j = 0; j < A::NLD; ++j) {
-            const int i = A::lane + 64 * j;
-            if (i < 16 * A::NA) dst[i] = (i < A::nact) ? A::a_nx[j] : 0.0f;
-        }
-    }
-};
-
 template <int ENV, bool NOISE, bool AOUT>
 __global__ void __launch_bounds__(64) k_score_policy_actions(SpolK r, const float* __restrict__ dynp, const float* __restrict__ theta, const float* __restrict__ norm) {
     using C = Cfg<ENV, 64, 32>;

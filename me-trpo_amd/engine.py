@@ -582,6 +582,71 @@ class Engine(object):
         matrix instructions), 'generic' (one thread per (candidate, head)); None before the first."""
         return {0: 'generic', 1: 'fused'}.get(int(lib.metrpo_last_score_actions_grad_kernel(self._ctx)))
 
+    # ------------------------------------------------------------------ gradient of every head's closed-loop return with respect to the noise
+    SCORE_POLICY_ACTIONS_GRAD_OUTPUTS = ('grad', 'ret', 'len', 'grad_mean', 'lam0', 'act_out')
+
+    def score_policy_actions_grad(self, init_obs, noise=None, T=None, gamma=1.0, stop_at_done=True, noise_in_std=False, want=('grad', 'ret'),
+                                  force_generic=False, chunk=0, out=None):
+        """metrpo_score_policy_actions_grad: the gradient of each head's closed-loop return (score_policy_actions' ret) with respect to the candidate
+        NOISE sequences -- the ascent direction, TOTAL: the policy of every later step sees the states a noise moved -- for init_obs [S, ns] or [ns]
+        and noise [T, B, na] as in score_policy_actions (None: the gradient at noise = 0 for T= steps, B = S).  want: any of grad [K, T, B, na]
+        (always computed; 0 where the head's action is clipped and behind a candidate's last counted step), ret [K, B], len [K, B] int32, grad_mean
+        [T, B, na] (the heads' mean, summed in head order), lam0 [K, B, ns] (the gradient with respect to the start state, policy path included),
+        act_out [K, T, B, na].  ret, len and act_out carry score_policy_actions' bits on the same path.  chunk: candidates per pass of the workspace
+        (0: the library's rule); it changes no bit of any output.  -> dict of device tensors, nothing synchronised.  out: dict name -> tensor to
+        write into instead (contiguous, at least that large)."""
+        dev = self.device
+        init_obs = _f32(init_obs, dev)
+        if init_obs.dim() == 1:
+            init_obs = init_obs.unsqueeze(0)
+        if init_obs.dim() != 2 or init_obs.shape[1] != self.ns or init_obs.shape[0] < 1:
+            raise ValueError("init_obs: expected [S, %d] or [%d], got %s" % (self.ns, self.ns, tuple(init_obs.shape)))
+        S = init_obs.shape[0]
+        if noise is None:
+            if T is None or int(T) < 0:
+                raise ValueError("noise=None needs T= (the number of steps), got %r" % (T,))
+            T, B = int(T), S
+        else:
+            noise = _f32(noise, dev)
+            if noise.dim() != 3 or noise.shape[2] != self.na or noise.shape[1] % S != 0:
+                raise ValueError("noise: expected [T, B, %d] with B a multiple of %d, got %s" % (self.na, S, tuple(noise.shape)))
+            if T is not None and int(T) != int(noise.shape[0]):
+                raise ValueError("T = %r does not match noise %s" % (T, tuple(noise.shape)))
+            T, B = int(noise.shape[0]), int(noise.shape[1])
+        want = (want,) if isinstance(want, str) else tuple(want)
+        for w in want:
+            if w not in self.SCORE_POLICY_ACTIONS_GRAD_OUTPUTS:
+                raise ValueError("want: %r is none of %s" % (w, self.SCORE_POLICY_ACTIONS_GRAD_OUTPUTS))
+        if not np.isfinite(float(gamma)):
+            raise ValueError("gamma must be finite")
+        if int(chunk) < 0:
+            raise ValueError("chunk must not be negative")
+        shapes = {'grad': (self.K, T, B, self.na), 'ret': (self.K, B), 'len': (self.K, B), 'grad_mean': (T, B, self.na), 'lam0': (self.K, B, self.ns),
+                  'act_out': (self.K, T, B, self.na)}
+        res = {}
+        for w in ('grad',) + tuple(x for x in want if x != 'grad'):
+            dt = torch.int32 if w == 'len' else torch.float32
+            if out is not None and w in out:
+                t = out[w]
+                assert t.dtype == dt and t.is_contiguous() and t.device == dev and t.numel() >= int(np.prod(shapes[w], dtype=np.int64))
+            else:
+                t = torch.empty(shapes[w], dtype=dt, device=dev)
+            res[w] = t
+        a = _lib.ScorePolicyActionsGradArgs()
+        a.B, a.T, a.S, a.stop_at_done, a.noise_in_std, a.force_generic = B, T, S, int(bool(stop_at_done)), int(bool(noise_in_std)), int(bool(force_generic))
+        a.chunk, a.gamma = int(chunk), float(gamma)
+        a.d_init_obs, a.d_noise = init_obs.data_ptr(), (noise.data_ptr() if noise is not None else None)
+        for w in self.SCORE_POLICY_ACTIONS_GRAD_OUTPUTS:
+            setattr(a, 'd_' + w, res[w].data_ptr() if w in res else None)
+        self._chk(lib.metrpo_score_policy_actions_grad(self._ctx, C.byref(a), self._stream()))
+        self._spag_keep = (init_obs, noise)                                        # alive until the stream has consumed them
+        return res
+
+    def last_score_policy_actions_grad_kernel(self):
+        """Path the last score_policy_actions_grad() of this engine took: 'fused' (score_policy_actions_grad.hip: a forward and a reverse launch per
+        chunk on the matrix instructions), 'generic' (one thread per (candidate, head)); None before the first."""
+        return {0: 'generic', 1: 'fused'}.get(int(lib.metrpo_last_score_policy_actions_grad_kernel(self._ctx)))
+
     # ------------------------------------------------------------------ fused rollout
     def rollout(self, B, T, H, sam_mode, pool, determ=False, eval_all_heads=True, seed=0, stream_offset=0,
                 eps=None, model_idx=None, sel_noise=None, reset_idx=None, reset_model=None, out=None,

@@ -11,7 +11,11 @@ towards the device, candidate b = s * N + n.
 First-order refinement (Grad-CEM / CEM-GD style): Engine.score_actions_grad / metrpo_score_actions_grad gives the gradient of every head's return with
 respect to the candidates in one call; refine_actions runs projected gradient ascent on a batch of candidates with it, plan_cem_gd refines CEM's elites
 (or all candidates) before each refit.  These take `grad_scorer=` as the others take `scorer=`: any callable
-(actions [T, B, na], init [S, ns]) -> (ret [K, B], grad [K, T, B, na])."""
+(actions [T, B, na], init [S, ns]) -> (ret [K, B], grad [K, T, B, na]).
+
+The same in NOISE space around the policy: Engine.score_policy_actions_grad / metrpo_score_policy_actions_grad gives dR / d noise with the policy path
+included; refine_noise is refine_actions there (projection clamp(+-noise_clip)), plan_cem_policy_gd refines plan_cem_policy's elites (or all) before
+each refit, and ShootingController(policy_prior=True, noise_grad_steps=n) plans with it."""
 import numpy as np
 import torch
 
@@ -186,9 +190,10 @@ def _from_device_major(x, S, N):
     return x.reshape(T, S, N, na).permute(1, 2, 0, 3).contiguous()
 
 
-def _refine(grad_scorer, states, a, n_steps, lr, optimizer, betas, eps, aggregate):
-    """refine_actions on device-major candidates a [T, B, na] -> (best [T, B, na], best_score [B], last [T, B, na], last_score [B], first_score [B])"""
-    lr, b1, b2, eps = float(lr), float(betas[0]), float(betas[1]), float(eps)
+def _refine(grad_scorer, states, a, n_steps, lr, optimizer, betas, eps, aggregate, bound=1.0):
+    """refine_actions on device-major candidates a [T, B, na] -> (best [T, B, na], best_score [B], last [T, B, na], last_score [B], first_score [B]).
+    bound: the projection is clamp(-bound, bound) -- 1 for actions, noise_clip for noise around the policy (refine_noise)"""
+    lr, b1, b2, eps, bound = float(lr), float(betas[0]), float(betas[1]), float(eps), float(bound)
     m = v = None
     best = best_score = first_score = None
     for it in range(n_steps + 1):
@@ -209,7 +214,7 @@ def _refine(grad_scorer, states, a, n_steps, lr, optimizer, betas, eps, aggregat
             m = (1.0 - b1) * g if m is None else b1 * m + (1.0 - b1) * g
             v = (1.0 - b2) * g * g if v is None else b2 * v + (1.0 - b2) * g * g
             step = lr * (m / (1.0 - b1 ** (it + 1))) / (torch.sqrt(v / (1.0 - b2 ** (it + 1))) + eps)
-        a = torch.clamp(a + step, -1.0, 1.0)
+        a = torch.clamp(a + step, -bound, bound)
     return best, best_score, a, score, first_score
 
 
@@ -402,6 +407,124 @@ def plan_cem_policy(engine, states, horizon, n_candidates, n_elites, n_iters, in
                 policy_score=policy_score)
 
 
+def engine_policy_grad_scorer(engine, gamma=1.0, stop_at_done=True, noise_in_std=False, force_generic=False):
+    """The engine's closed-loop gradient scorer: (noise [T, B, na], init [S, ns]) -> (ret [K, B], grad [K, T, B, na] = d ret / d noise, the policy path
+    included), one metrpo_score_policy_actions_grad call, nothing synchronised.  The `grad_scorer=` signature of the other planners."""
+    def grad_scorer(noise, init):
+        out = engine.score_policy_actions_grad(init, noise, gamma=gamma, stop_at_done=stop_at_done, noise_in_std=noise_in_std, want=('grad', 'ret'),
+                                               force_generic=force_generic)
+        return out['ret'], out['grad']
+    return grad_scorer
+
+
+def _setup_policy_grad(engine, grad_scorer, gamma, stop_at_done, noise_in_std=False):
+    if grad_scorer is None:
+        if engine is None:
+            raise ValueError("an engine or a grad_scorer is needed")
+        grad_scorer = engine_policy_grad_scorer(engine, gamma, stop_at_done, noise_in_std)
+    return grad_scorer
+
+
+def _check_noise_clip(noise_clip):
+    noise_clip = float(noise_clip)
+    if not (noise_clip > 0.0 and np.isfinite(noise_clip)):
+        raise ValueError("noise_clip must be positive and finite, got %r" % (noise_clip,))
+    return noise_clip
+
+
+def refine_noise(engine, states, noise, n_steps, lr, noise_clip=2.0, optimizer='adam', betas=(0.9, 0.999), eps=1e-8, gamma=1.0, stop_at_done=True,
+                 aggregate='mean', noise_in_std=False, grad_scorer=None):
+    """refine_actions in noise space: projected gradient ASCENT on candidate noise sequences around the policy, states [S, ns], noise [S, N, T, na] (or
+    [S, T, na]: one each).  n_steps times delta <- clamp(delta + step, -noise_clip, noise_clip) with refine_actions' steps, g = aggregate_heads_grad of
+    one closed-loop gradient call (d ret / d noise with the policy path included); n_steps + 1 calls in all.  Keep-best: `noise` / `score` are the
+    best-scoring iterate seen per candidate, so the result is never worse than the input.
+    -> dict(noise [S, N, T, na], score [S, N], last / last_score the final iterate, initial_score [S, N]), device tensors; nothing is read back."""
+    n_steps = _check_refine(n_steps, lr, optimizer)
+    noise_clip = _check_noise_clip(noise_clip)
+    grad_scorer = _setup_policy_grad(engine, grad_scorer, gamma, stop_at_done, noise_in_std)
+    nz = torch.as_tensor(noise)
+    _, states, na = _setup(engine, states, grad_scorer, nz.shape[-1] if nz.dim() >= 1 else None, gamma, stop_at_done)
+    nz = nz.to(device=states.device, dtype=torch.float32)
+    S = states.shape[0]
+    single = nz.dim() == 3
+    if single:
+        nz = nz.unsqueeze(1)
+    if nz.dim() != 4 or nz.shape[0] != S or nz.shape[3] != na or nz.shape[1] < 1 or nz.shape[2] < 1:
+        raise ValueError("noise: expected [%d, N, T, %d] or [%d, T, %d], got %s" % (S, na, S, na, tuple(torch.as_tensor(noise).shape)))
+    N = nz.shape[1]
+    best, best_score, last, last_score, first = _refine(grad_scorer, states, _device_major(nz), n_steps, lr, optimizer, betas, eps, aggregate, noise_clip)
+    res = dict(noise=_from_device_major(best, S, N), score=best_score.reshape(S, N), last=_from_device_major(last, S, N),
+               last_score=last_score.reshape(S, N), initial_score=first.reshape(S, N))
+    return {k: x[:, 0] for k, x in res.items()} if single else res
+
+
+def plan_cem_policy_gd(engine, states, horizon, n_candidates, n_elites, n_iters, grad_steps, grad_lr=0.05, refine='elites', optimizer='adam',
+                       betas=(0.9, 0.999), eps=1e-8, init_mean=None, init_std=0.5, noise_clip=2.0, alpha=0.0, min_std=0.0, gamma=1.0, aggregate='mean',
+                       generator=None, stop_at_done=True, scorer=None, grad_scorer=None, na=None, include_policy=True):
+    """plan_cem_policy with gradient refinement before the refit, as plan_cem_gd is plan_cem's: each iteration draws and clamps as plan_cem_policy does
+    (include_policy still plants delta = 0 as candidate 0), then
+    refine='elites': scores all candidates (one scoring call), takes the n_elites best and refines THEM by refine_noise's grad_steps steps;
+    refine='all': refines every candidate (no separate scoring call) and takes the n_elites best of the refined ones.
+    The refit uses the refined elites (keep-best: never worse than the ones drawn, so the best candidate seen is still never worse than the policy).
+    grad_steps = 0 returns plan_cem_policy's tensors bit for bit for the same generator state.  -> plan_cem_policy's dict; `elites` indexes the drawn
+    candidates; policy_score is the score of delta = 0 itself, before any refinement."""
+    T, N = _check_counts(horizon, n_candidates)
+    E, n_iters = int(n_elites), int(n_iters)
+    grad_steps = _check_refine(grad_steps, grad_lr, optimizer)
+    if refine not in ('elites', 'all'):
+        raise ValueError("refine: %r is neither 'elites' nor 'all'" % (refine,))
+    if not (1 <= E <= N):
+        raise ValueError("n_elites must be in 1 ... n_candidates = %d, got %r" % (N, n_elites))
+    if n_iters < 1:
+        raise ValueError("n_iters must be positive, got %r" % (n_iters,))
+    if not (0.0 <= float(alpha) < 1.0):
+        raise ValueError("alpha must be in [0, 1), got %r" % (alpha,))
+    noise_clip = _check_noise_clip(noise_clip)
+    if grad_steps > 0 or (scorer is None and engine is None):
+        grad_scorer = _setup_policy_grad(engine, grad_scorer, gamma, stop_at_done)
+    if scorer is None and engine is None:
+        scorer = lambda d, init: grad_scorer(d, init)[0]
+    scorer, states, na = _setup_policy(engine, states, scorer, na, gamma, stop_at_done)
+    S, dev = states.shape[0], states.device
+    mean = _time_major_param(0.0 if init_mean is None else init_mean, T, S, na, dev, 'init_mean')
+    std = _time_major_param(init_std, T, S, na, dev, 'init_std')
+    alpha, min_std = float(alpha), float(min_std)
+    best_score = torch.full((S,), float('-inf'), device=dev, dtype=torch.float32)
+    best_noise = torch.zeros(T, S, na, device=dev, dtype=torch.float32)
+    history = torch.empty(n_iters, S, device=dev, dtype=torch.float32)
+    policy_score = None
+    for it in range(n_iters):
+        eps_ = torch.randn(T, S, N, na, generator=generator, device=dev, dtype=torch.float32)
+        d = torch.clamp(mean + std * eps_, -noise_clip, noise_clip)
+        if include_policy:
+            d[:, :, 0] = 0.0                                                              # the policy itself rides along in every iteration
+        if grad_steps > 0 and refine == 'all':
+            ref_d, ref_s, _, _, first = _refine(grad_scorer, states, d.reshape(T, S * N, na), grad_steps, grad_lr, optimizer, betas, eps, aggregate, noise_clip)
+            d, scores, drawn = ref_d.reshape(T, S, N, na), ref_s.reshape(S, N), first.reshape(S, N)
+        else:
+            scores = drawn = aggregate_heads(scorer(d.reshape(T, S * N, na), states), aggregate).reshape(S, N)
+        if include_policy and it == 0:
+            policy_score = drawn[:, 0].clone()
+        vals, idx = torch.topk(scores, E, dim=1)                                          # sorted: column 0 is the iteration's best
+        elites = d.gather(2, idx.view(1, S, E, 1).expand(T, S, E, na))
+        if grad_steps > 0 and refine == 'elites':
+            ref_d, ref_s = _refine(grad_scorer, states, elites.reshape(T, S * E, na), grad_steps, grad_lr, optimizer, betas, eps, aggregate, noise_clip)[:2]
+            vals, order = torch.topk(ref_s.reshape(S, E), E, dim=1)                       # sorted again: refinement may reorder the elites
+            elites = ref_d.reshape(T, S, E, na).gather(2, order.view(1, S, E, 1).expand(T, S, E, na))
+        elites = elites.double()
+        e_mean = elites.sum(dim=2, keepdim=True) / E
+        e_std = torch.sqrt(((elites - e_mean) ** 2).sum(dim=2, keepdim=True) / E)
+        mean = alpha * mean + (1.0 - alpha) * e_mean.float()
+        std = torch.clamp(alpha * std + (1.0 - alpha) * e_std.float(), min=min_std)
+        better = vals[:, 0] > best_score
+        best_score = torch.where(better, vals[:, 0], best_score)
+        best_noise = torch.where(better.view(1, S, 1), elites[:, :, 0].float(), best_noise)
+        history[it] = vals.mean(dim=1)
+    tm = lambda x: x.permute(1, 0, 2).contiguous()
+    return dict(noise=tm(mean[:, :, 0]), std=tm(std[:, :, 0]), best_noise=tm(best_noise), best_score=best_score, history=history, elites=idx,
+                policy_score=policy_score)
+
+
 class ShootingController(object):
     """Model-predictive control by CEM with a warm start, with the policy's call shape: get_actions(obs [S, ns]) -> (actions [S, na], {}).
     Every call plans `horizon` steps ahead from obs, returns the first action of the plan's mean and keeps the rest: the next call starts from the
@@ -409,11 +532,13 @@ class ShootingController(object):
     The action comes back as float64 NumPy, as GaussianMLPPolicy.get_actions gives it -- one read-back per call, behind the planner.
     grad_steps > 0 plans with plan_cem_gd (grad_lr, refine, grad_scorer) instead.
     policy_prior=True plans with plan_cem_policy (noise_clip) around the engine's policy instead: the warm start is the noise mean shifted by one step,
-    its last row reset to 0, and the action is clip(policy mean(obs) + noise mean[0])."""
+    its last row reset to 0, and the action is clip(policy mean(obs) + noise mean[0]).
+    policy_prior=True with noise_grad_steps > 0 plans with plan_cem_policy_gd (noise_grad_lr, refine, noise_grad_scorer): gradients with respect to the
+    NOISE, the policy path included."""
 
     def __init__(self, engine, horizon, n_candidates, n_elites, n_iters, init_mean=None, init_std=1.0, alpha=0.0, min_std=0.0, gamma=1.0,
                  aggregate='mean', generator=None, stop_at_done=True, scorer=None, na=None, grad_steps=0, grad_lr=0.05, refine='elites', grad_scorer=None,
-                 policy_prior=False, noise_clip=2.0):
+                 policy_prior=False, noise_clip=2.0, noise_grad_steps=0, noise_grad_lr=0.05, noise_grad_scorer=None):
         self.engine, self.horizon, self.scorer, self.na = engine, int(horizon), scorer, (engine.na if engine is not None else na)
         # grad_steps > 0: plan_cem_gd with these settings in plan_cem's place (0: plan_cem, as before)
         self.grad_steps, self.grad_kw = _check_refine(grad_steps, grad_lr, 'adam'), dict(grad_lr=grad_lr, refine=refine, grad_scorer=grad_scorer)
@@ -425,6 +550,11 @@ class ShootingController(object):
             raise ValueError("policy_prior=True plans in noise space; grad_steps > 0 (gradients with respect to open-loop actions) cannot be combined with it")
         if self.policy_prior and engine is None:
             raise ValueError("policy_prior=True needs an engine (its policy_actions gives the mean the noise is added to)")
+        # noise_grad_steps > 0 (with policy_prior): plan_cem_policy_gd in plan_cem_policy's place
+        self.noise_grad_steps = _check_refine(noise_grad_steps, noise_grad_lr, 'adam')
+        self.noise_grad_kw = dict(grad_lr=noise_grad_lr, refine=refine, grad_scorer=noise_grad_scorer)
+        if self.noise_grad_steps > 0 and not self.policy_prior:
+            raise ValueError("noise_grad_steps > 0 refines noise around the policy: it needs policy_prior=True (grad_steps refines open-loop actions)")
         self.init_mean, self.init_std = init_mean, init_std
         self.kw = dict(n_candidates=n_candidates, n_elites=n_elites, n_iters=n_iters, alpha=alpha, min_std=min_std, gamma=gamma, aggregate=aggregate,
                        generator=generator, stop_at_done=stop_at_done)
@@ -457,8 +587,12 @@ class ShootingController(object):
         S = obs.shape[0] if obs.dim() == 2 else 1
         start = self._mean if (self._mean is not None and self._mean.shape[0] == S) else self.init_mean
         if self.policy_prior:
-            plan = plan_cem_policy(self.engine, obs, self.horizon, init_mean=start, init_std=self.init_std, noise_clip=self.noise_clip, scorer=self.scorer,
-                                   na=self.na, **self.kw)
+            if self.noise_grad_steps > 0:
+                plan = plan_cem_policy_gd(self.engine, obs, self.horizon, grad_steps=self.noise_grad_steps, init_mean=start, init_std=self.init_std,
+                                          noise_clip=self.noise_clip, scorer=self.scorer, na=self.na, **dict(self.kw, **self.noise_grad_kw))
+            else:
+                plan = plan_cem_policy(self.engine, obs, self.horizon, init_mean=start, init_std=self.init_std, noise_clip=self.noise_clip,
+                                       scorer=self.scorer, na=self.na, **self.kw)
             self.last_plan = plan
             self._mean = self.shifted_noise(plan['noise'])
             obs2 = obs.reshape(S, -1).to(device=plan['noise'].device, dtype=torch.float32)
