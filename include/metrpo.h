@@ -922,6 +922,34 @@ typedef struct {
 int32_t metrpo_score_policy_actions_grad(metrpo_ctx* ctx, const metrpo_score_policy_actions_grad_args* args, void* stream);
 int32_t metrpo_last_score_policy_actions_grad_kernel(const metrpo_ctx* ctx);   /* -1 none yet, 0 generic, 1 fused */
 
+/* ---- a TERMINAL VALUE for the four corners above: "what is the state behind the horizon worth?"  Without one every corner scores a candidate by
+ * sum_{t<T} gamma^t alive_t r_t and stops, so a planner prefers plans that cash in inside the window.  With one set, ret gains gamma^T alive_T V(s_T) and
+ * the two gradient calls start their reverse recursion from the matching seed.  Additions to ABI 4: no struct above changes, no option key is added,
+ * METRPO_ABI_VERSION stays.
+ * V is LinearFeatureBaseline's form once its time features are evaluated at a fixed step (metrpo_baseline_gram's feature row [o, o^2, al, al^2, al^3, 1]
+ * with al fixed): a diagonal quadratic in the clipped state plus a bias,
+ *   o_d     = clip(s_d, -10, 10)
+ *   V(s)    = bias + sum_d (w1[d] o_d + w2[d] o_d^2)      fp32, dims in order: v = bias; v = fmaf(o_d, fmaf(w2[d], o_d, w1[d]), v)
+ *   dV/ds_d = fmaf(2 w2[d], o_d, w1[d])  if -10 <= s_d <= 10,  else 0      tf.clip_by_value's convention, as at the action clip
+ * V is context state, like theta and the dynamics: d_w1, d_w2 [ns] and d_bias [n_bias] are DEVICE pointers, copied stream-ordered into ctx-owned memory
+ * (metrpo_set_policy's stream discipline; neither frees nor synchronises).  n_bias is 1 (one bias for every candidate) or the scoring call's S
+ * (candidate b uses bias[b / (B / S)]: the start states of a vectorised controller sit at different path steps, and the baseline's time features
+ * move the bias).  metrpo_clear_terminal_value unsets it; metrpo_has_terminal_value: 0, or the n_bias that is set.
+ * While a value is set, in all four calls and on both of their paths:
+ *   ret      with the sum's fields behind the T-th step (disc = gamma^T, alive after the last step's mask update): if (alive) sum += disc * (double)V(s_T),
+ *            in front of the single rounding to fp32.  A candidate that met a done, at the last step included, gets no bootstrap.  len is unchanged;
+ *            ret_mean / ret_std come from the stored values, as always.
+ *   grad     w_T = alive_T ? (float)gamma^T : 0; the recursion starts from lambda_T = w_T dV/ds_T instead of 0 and is otherwise the one stated above
+ *            (closed loop: the seed reaches J_pi through G like any lambda).  w_T is stored by the forward sweep, one more slice of WT.
+ *   ret, len and act_out of a gradient call keep carrying the bits of the matching scoring call; chunking changes no bit; repeated calls are
+ *   bit-identical; B == 0 or T == 0 still writes nothing.  A scoring call while n_bias is neither 1 nor its S: METRPO_EINVAL, nothing written.
+ * With none set every output of the four calls is what it was.  Every other entry point ignores the terminal value.
+ * The fused kernels evaluate V once per lane BEHIND the step loop from the state rows the loop leaves in LDS: nothing is added inside the loop.
+ * metrpo_set_terminal_value: METRPO_ENULL: ctx or a pointer; METRPO_EINVAL: n_bias < 1. */
+int32_t metrpo_set_terminal_value(metrpo_ctx* ctx, const float* d_w1, const float* d_w2, const float* d_bias, int32_t n_bias, void* stream);
+int32_t metrpo_clear_terminal_value(metrpo_ctx* ctx);
+int32_t metrpo_has_terminal_value(const metrpo_ctx* ctx);   /* 0 / n_bias */
+
 #ifdef __cplusplus
 }
 #endif

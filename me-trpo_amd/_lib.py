@@ -202,6 +202,9 @@ SYMBOLS = {
     'metrpo_last_score_policy_actions_kernel': (_I, [_P]),
     'metrpo_score_policy_actions_grad': (_I, [_P, C.POINTER(ScorePolicyActionsGradArgs), _P]),
     'metrpo_last_score_policy_actions_grad_kernel': (_I, [_P]),
+    'metrpo_set_terminal_value': (_I, [_P, _P, _P, _P, _I, _P]),
+    'metrpo_clear_terminal_value': (_I, [_P]),
+    'metrpo_has_terminal_value': (_I, [_P]),
     'metrpo_dyn_train_reset': (_I, [_P, _P]),
     'metrpo_dyn_train_step': (_I, [_P, _P, _P, C.POINTER(TrainParams), _P, _P]),
     'metrpo_dyn_eval_losses': (_I, [_P, _P, _P, _L, _D, _P, _P]),

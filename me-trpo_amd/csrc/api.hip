@@ -1092,6 +1092,32 @@ extern "C" int32_t metrpo_ensemble_disagreement(metrpo_ctx* c, const metrpo_disa
 }
 extern "C" int32_t metrpo_last_disagreement_kernel(const metrpo_ctx* c) { return c ? c->last_dis_kernel : METRPO_ENULL; }
 
+// ---- the terminal value of the four scoring calls below (sact_sum.h: TermVal): context state like theta, copied stream-ordered into d_tv = w1 | w2 | bias ----
+extern "C" int32_t metrpo_set_terminal_value(metrpo_ctx* c, const float* d_w1, const float* d_w2, const float* d_bias, int32_t n_bias, void* stream) {
+    if (!c) return METRPO_ENULL;
+    if (!d_w1 || !d_w2 || !d_bias) return set_err(c, METRPO_ENULL, "set_terminal_value: NULL pointer");
+    if (n_bias < 1) return set_err(c, METRPO_EINVAL, "set_terminal_value: n_bias = " + std::to_string(n_bias) + " must be at least 1");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ns = c->pd.ns;
+    // a larger n_bias than any before: the outgrown buffer is retired, not freed -- a scoring call already enqueued may still read it
+    { const int rc = ws_grow(c, c->d_tv, sizeof(float) * (2 * ns + (size_t)n_bias)); if (rc) { c->tv_n_bias = 0; return rc; } }
+    c->tv_n_bias = 0;                                            // a failed copy leaves none set
+    HIP_TRY(c, hipMemcpyAsync(c->d_tv.p, d_w1, sizeof(float) * ns, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_tv.p + ns, d_w2, sizeof(float) * ns, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_tv.p + 2 * ns, d_bias, sizeof(float) * (size_t)n_bias, hipMemcpyDeviceToDevice, st));
+    c->tv_n_bias = n_bias;
+    return METRPO_OK;
+}
+extern "C" int32_t metrpo_clear_terminal_value(metrpo_ctx* c) {
+    if (!c) return METRPO_ENULL;
+    c->tv_n_bias = 0;                                            // the buffer stays: enqueued calls may still read it
+    return METRPO_OK;
+}
+extern "C" int32_t metrpo_has_terminal_value(const metrpo_ctx* c) { return c ? c->tv_n_bias : METRPO_ENULL; }
+// a scoring call's S against the n_bias that is set: one bias for every candidate, or one per start state
+#define TV_FITS(c, a, name) if ((c)->tv_n_bias > 1 && (c)->tv_n_bias != (a)->S)                                                                          \
+    return set_err((c), METRPO_EINVAL, std::string(name) + ": the terminal value has n_bias = " + std::to_string((c)->tv_n_bias) + ", neither 1 nor S = " + std::to_string((a)->S))
+
 // ---- every head's discounted return of supplied action sequences (model_based_rl.py:122-141 under supplied actions; score_actions.hip) ----
 extern "C" int32_t metrpo_score_actions(metrpo_ctx* c, const metrpo_score_actions_args* a, void* stream) {
     TraceRange trace_("metrpo:score_actions (per-head returns of candidate action sequences)");
@@ -1101,6 +1127,7 @@ extern "C" int32_t metrpo_score_actions(metrpo_ctx* c, const metrpo_score_action
     if (a->B < 0 || a->T < 0) return set_err(c, METRPO_EINVAL, "score_actions: bad B/T");
     if (a->S < 1 || a->B % a->S != 0) return set_err(c, METRPO_EINVAL, "score_actions: S = " + std::to_string(a->S) + " must be at least 1 and divide B = " + std::to_string(a->B));
     if (!std::isfinite(a->gamma)) return set_err(c, METRPO_EINVAL, "score_actions: gamma is not finite");
+    TV_FITS(c, a, "score_actions");
     if (a->B == 0 || a->T == 0) return METRPO_OK;
     if (!a->d_init_obs || !a->d_actions || !a->d_ret) return set_err(c, METRPO_ENULL, "score_actions: required pointer is NULL");
     return run_score_actions(c, a, (hipStream_t)stream);
@@ -1116,6 +1143,7 @@ extern "C" int32_t metrpo_score_actions_grad(metrpo_ctx* c, const metrpo_score_a
     if (a->B < 0 || a->T < 0) return set_err(c, METRPO_EINVAL, "score_actions_grad: bad B/T");
     if (a->S < 1 || a->B % a->S != 0) return set_err(c, METRPO_EINVAL, "score_actions_grad: S = " + std::to_string(a->S) + " must be at least 1 and divide B = " + std::to_string(a->B));
     if (!std::isfinite(a->gamma)) return set_err(c, METRPO_EINVAL, "score_actions_grad: gamma is not finite");
+    TV_FITS(c, a, "score_actions_grad");
     if (a->chunk < 0) return set_err(c, METRPO_EINVAL, "score_actions_grad: chunk must not be negative");
     if (a->B == 0 || a->T == 0) return METRPO_OK;
     if (!a->d_init_obs || !a->d_actions || !a->d_grad) return set_err(c, METRPO_ENULL, "score_actions_grad: required pointer is NULL");
@@ -1133,6 +1161,7 @@ extern "C" int32_t metrpo_score_policy_actions(metrpo_ctx* c, const metrpo_score
     if (a->B < 0 || a->T < 0) return set_err(c, METRPO_EINVAL, "score_policy_actions: bad B/T");
     if (a->S < 1 || a->B % a->S != 0) return set_err(c, METRPO_EINVAL, "score_policy_actions: S = " + std::to_string(a->S) + " must be at least 1 and divide B = " + std::to_string(a->B));
     if (!std::isfinite(a->gamma)) return set_err(c, METRPO_EINVAL, "score_policy_actions: gamma is not finite");
+    TV_FITS(c, a, "score_policy_actions");
     if (a->B == 0 || a->T == 0) return METRPO_OK;
     if (!a->d_init_obs || !a->d_ret) return set_err(c, METRPO_ENULL, "score_policy_actions: required pointer is NULL");
     return run_score_policy_actions(c, a, (hipStream_t)stream);
@@ -1149,6 +1178,7 @@ extern "C" int32_t metrpo_score_policy_actions_grad(metrpo_ctx* c, const metrpo_
     if (a->B < 0 || a->T < 0) return set_err(c, METRPO_EINVAL, "score_policy_actions_grad: bad B/T");
     if (a->S < 1 || a->B % a->S != 0) return set_err(c, METRPO_EINVAL, "score_policy_actions_grad: S = " + std::to_string(a->S) + " must be at least 1 and divide B = " + std::to_string(a->B));
     if (!std::isfinite(a->gamma)) return set_err(c, METRPO_EINVAL, "score_policy_actions_grad: gamma is not finite");
+    TV_FITS(c, a, "score_policy_actions_grad");
     if (a->chunk < 0) return set_err(c, METRPO_EINVAL, "score_policy_actions_grad: chunk must not be negative");
     if (a->B == 0 || a->T == 0) return METRPO_OK;
     if (!a->d_init_obs || !a->d_grad) return set_err(c, METRPO_ENULL, "score_policy_actions_grad: required pointer is NULL");

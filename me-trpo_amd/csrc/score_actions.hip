@@ -22,6 +22,10 @@
 // workspace, chunked over candidates so that the workspace stays within 2^26 floats (svg.hip's rule), then k_sact_reduce, one thread per candidate,
 // applies the same float64 sum to the workspace's rew / done.
 //
+// Terminal value (metrpo_set_terminal_value; sact_sum.h: TermVal): while one is set, ret gains gamma^T alive_T V(s_T) in front of the single rounding.  Fused: tile_rollout
+// leaves s_T in the wave's ST rows behind the loop and the sink's finish evaluates V there once per lane -- nothing is added inside the loop; the value is a
+// template parameter of the kernel.  Generic: k_sact_reduce applies the same statement to row T of the chunk's stored trajectory.
+//
 // d_ret_mean / d_ret_std: k_sact_aggregate, a second small launch over d_ret, one thread per candidate adding in head order; no workgroup waits on another.
 #include "dyn_tile_step.h"
 #include "sact_sum.h"                 // SactSum: one step of the return
@@ -34,17 +38,24 @@ struct SactK {
     double gamma;
     const float* init_obs; const float* actions;
     float* ret; int32_t* len;
+    TermVal tv;               // the context's terminal value; unset: all NULL
 };
 
-// tile_rollout's sink that stores nothing inside the step loop: every lane carries its env's sum, quad 0 writes d_ret / d_len once behind the loop
+// tile_rollout's sink that stores nothing inside the step loop: every lane carries its env's sum, quad 0 writes d_ret / d_len once behind the loop.
+// TV: with a terminal value -- a template parameter, so that the kernel without one is the kernel it was (the runtime test's operands cost it 8 .. 14
+// scalar registers held across the loop, and 0.3 .. 0.7 % of its time: profiles/r26_terminal_value.txt)
+template <bool TV>
 struct SactSink {
     const SactK& r;
     SactSum acc;
     __device__ __forceinline__ void start(const float*, int, int, int) const {}
     __device__ __forceinline__ void step(int, const float*, float cost, bool dn, int, int, int) { acc.step(-cost, dn, r.gamma, r.stop); }
-    __device__ __forceinline__ void finish(int k, int b0, int lane) const {
+    // ST: the tile's rows behind the loop, s_T.  The terminal value is evaluated here, once per lane, in front of the single rounding
+    template <int NS>
+    __device__ __forceinline__ void finish(int k, int b0, int lane, const float* ST) {
         const int b = b0 + (lane & 15);
         if ((lane >> 4) == 0 && b < r.B) {                       // rounded to fp32 once, here
+            if (TV) acc.terminal(r.tv.value(ST + (lane & 15) * NS, 1, NS, b, r.per));
             const size_t kb = (size_t)k * r.B + b;
             r.ret[kb] = (float)acc.sum;
             if (r.len != nullptr) r.len[kb] = acc.n;
@@ -52,14 +63,14 @@ struct SactSink {
     }
 };
 
-template <int ENV>
+template <int ENV, bool TV>
 __global__ void __launch_bounds__(64) k_score_actions(SactK r, const float* __restrict__ dynp, const float* __restrict__ norm) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int b0 = blockIdx.x * 16, k = blockIdx.y;
     const TileRollK tr = {r.B, r.T, r.per, r.init_obs, r.actions, k, 0, nullptr};
-    SactSink sink = {r};
+    SactSink<TV> sink = {r};
     tile_rollout<ENV, true>(lds, tr, 1, b0, dynp, norm, sink);
-    sink.finish(k, b0, threadIdx.x & 63);
+    sink.template finish<Cfg<ENV, 64, 32>::NS>(k, b0, threadIdx.x & 63, lds + Cfg<ENV, 64, 32>::W_ST);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -79,12 +90,14 @@ __global__ void __launch_bounds__(256) k_sact_starts(const float* __restrict__ i
     }
 }
 // k_sact_reduce: one thread per candidate of the chunk over the step loop's rew / done [T][Bc]; SactSum is the fused kernel's.  ret / len point at [k][c0].
+// tv set: sT holds the chunk's states behind step T, [Bc][ns]; c0 is the chunk's first candidate (the bias row is (c0 + i) / per).
 __global__ void __launch_bounds__(256) k_sact_reduce(const float* __restrict__ rew, const uint8_t* __restrict__ done, int Bc, int T, int stop, double gamma,
-                                                     float* __restrict__ ret, int32_t* __restrict__ len) {
+                                                     float* __restrict__ ret, int32_t* __restrict__ len, TermVal tv, const float* __restrict__ sT, int ns, int c0, int per) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Bc) return;
     SactSum acc;
     for (int t = 0; t < T; ++t) acc.step(rew[(size_t)t * Bc + i], done[(size_t)t * Bc + i] != 0, gamma, stop);
+    if (tv.set()) acc.terminal(tv.value(sT + (size_t)i * ns, 1, ns, c0 + i, per));
     ret[i] = (float)acc.sum;
     if (len != nullptr) len[i] = acc.n;
 }
@@ -111,8 +124,9 @@ void launch_sact_starts(const float* init_obs, const float* actions, int B, int 
     const size_t work = (size_t)Bc * ns + (act_c ? (size_t)T * Bc * na : 0);
     hipLaunchKernelGGL(k_sact_starts, dim3((unsigned)std::min<size_t>((work + 255) / 256, 4096)), dim3(256), 0, st, init_obs, actions, B, T, per, c0, Bc, ns, na, obs0, act_c);
 }
-void launch_sact_reduce(const float* rew, const uint8_t* done, int Bc, int T, int stop, double gamma, float* ret, int32_t* len, hipStream_t st) {
-    hipLaunchKernelGGL(k_sact_reduce, dim3((Bc + 255) / 256), dim3(256), 0, st, rew, done, Bc, T, stop, gamma, ret, len);
+void launch_sact_reduce(const float* rew, const uint8_t* done, int Bc, int T, int stop, double gamma, float* ret, int32_t* len, const TermVal& tv, const float* sT, int ns,
+                        int c0, int per, hipStream_t st) {
+    hipLaunchKernelGGL(k_sact_reduce, dim3((Bc + 255) / 256), dim3(256), 0, st, rew, done, Bc, T, stop, gamma, ret, len, tv, sT, ns, c0, per);
 }
 void launch_sact_aggregate(const float* ret, int B, int K, float* mean, float* sd, hipStream_t st) {
     hipLaunchKernelGGL(k_sact_aggregate, dim3((B + 255) / 256), dim3(256), 0, st, ret, B, K, mean, sd);
@@ -120,18 +134,18 @@ void launch_sact_aggregate(const float* ret, int B, int K, float* mean, float* s
 
 // -------------------------------------------------------------------------------------------------
 typedef void (*sact_kernel_t)(SactK, const float*, const float*);
-struct SactEntry { int env; sact_kernel_t kern; int w_sz; };
-#define SENTRY(ENVID) {ENVID, k_score_actions<ENVID>, act_wave_floats<ENVID>()}
+struct SactEntry { int env; sact_kernel_t kern[2]; int w_sz; };      // kern[terminal value set]
+#define SENTRY(ENVID) {ENVID, {k_score_actions<ENVID, false>, k_score_actions<ENVID, true>}, act_wave_floats<ENVID>()}
 static const SactEntry kSact[] = {FUSED_HEAD_ENVS(SENTRY)};
 
 static int launch_sact_fused(metrpo_ctx* c, const SactEntry& en, bool padded, const metrpo_score_actions_args* a, hipStream_t st) {
     SactK r = {};
     r.B = a->B; r.T = a->T; r.per = a->B / a->S; r.stop = a->stop_at_done ? 1 : 0; r.gamma = a->gamma;
-    r.init_obs = a->d_init_obs; r.actions = a->d_actions; r.ret = a->d_ret; r.len = a->d_len;
+    r.init_obs = a->d_init_obs; r.actions = a->d_actions; r.ret = a->d_ret; r.len = a->d_len; r.tv = ctx_term_val(c);
     const float* dyn;
     { const int rc = fused_head_dyn(c, padded, st, &dyn); if (rc) return rc; }
     const size_t sh = sizeof(float) * (size_t)en.w_sz;
-    hipLaunchKernelGGL(en.kern, dim3((a->B + 15) / 16, c->pd.K), dim3(64), sh, st, r, dyn, c->d_norm.p);
+    hipLaunchKernelGGL(en.kern[r.tv.w1 ? 1 : 0], dim3((a->B + 15) / 16, c->pd.K), dim3(64), sh, st, r, dyn, c->d_norm.p);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
 }
@@ -162,7 +176,7 @@ static int launch_sact_generic(metrpo_ctx* c, const metrpo_score_actions_args* a
             rc = run_rollout_actions(c, &ra, st);
             if (rc) break;
             launch_sact_reduce(ra.d_rew, ra.d_done, n, a->T, a->stop_at_done ? 1 : 0, a->gamma, a->d_ret + (size_t)k * B + c0,
-                               a->d_len ? a->d_len + (size_t)k * B + c0 : nullptr, st);
+                               a->d_len ? a->d_len + (size_t)k * B + c0 : nullptr, ctx_term_val(c), ra.d_obs + T * n * ns, (int)ns, (int)c0, per, st);      // row T of the chunk's trajectory
             if (hipGetLastError() != hipSuccess) rc = set_err(c, METRPO_EHIP, "score_actions: launch failed");
         }
     }

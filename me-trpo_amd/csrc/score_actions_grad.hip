@@ -24,7 +24,13 @@
 // Generic path (every other shape, and force_generic): k_sagr_gen_fwd / k_sagr_gen_bwd, one thread per (candidate, head) with activations in LDS
 // columns -- k_bptt_forward / k_bptt_backward (bptt.hip) with the policy removed; block size by bptt.hip's LDS rule.  Same outputs, workspace, chunking.
 //
-// Workspace: ctx->d_sagr = XS | WT of one chunk, within 2^26 floats (svg.hip's rule; args.chunk > 0 overrides).  d_grad_mean: k_sagr_mean, a small
+// Terminal value (metrpo_set_terminal_value; sact_sum.h: TermVal): the forward sweeps add gamma^T alive_T V(s_T) to the sum behind the loop (score_actions.hip's
+// statement, so ret keeps that call's bits) and STORE w_T = alive_T ? (float)gamma^T : 0 into WE [K][Bc], one more slice of WT that exists only while a value is
+// set -- stored, not re-derived: the reverse sweep would have to redo the done test of s_T and the float64 discount to form it.  The reverse sweeps start from
+// lambda_T = w_T dV/ds_T, formed from the stored XS[T] tile in lambda's own layout (fused: the x_T buffer in LDS, behind its commit) instead of 0.  The forward
+// sweeps take the value as a template parameter (k_sagr<.., SAGR_FWD, TV>, k_sagr_gen_fwd<TV>), the reverse sweeps by the runtime-uniform pointer test.
+//
+// Workspace: ctx->d_sagr = XS | WT (| WE) of one chunk, within 2^26 floats (svg.hip's rule; args.chunk > 0 overrides).  d_grad_mean: k_sagr_mean, a small
 // launch over d_grad adding in head order (k_sact_aggregate's style).  No atomics anywhere: repeated calls are bit-identical.
 #include "dyn_tile_step.h"
 #include "dyn_head_adjoint.h"
@@ -41,12 +47,14 @@ struct SagrK {
     double gamma;
     const float* init_obs; const float* actions;
     float* XS; float* WT;     // [K][T+1][n][ns], [K][T][n]
+    float* WE;                // [K][n]: w_T, one more slice of WT, only while a terminal value is set
+    TermVal tv;               // the context's terminal value; unset: all NULL
     float* ret; int32_t* len; // [K][B], optional
     float* grad; float* lam0; // [K][T][B][na], optional [K][B][ns]
 };
 
 // tile_rollout's sink of the forward sweep: b0 is the tile's first candidate in the batch, the chunk's column is b - c0
-template <int NS>
+template <int NS, bool TV>
 struct SagrSink {
     const SagrK& r;
     int k;
@@ -64,9 +72,11 @@ struct SagrSink {
         if ((lane >> 4) == 0 && b < r.c0 + r.n) r.WT[((size_t)k * r.T + t) * r.n + (b - r.c0)] = w;
         rows(t + 1, ST, b0, lane);
     }
-    __device__ __forceinline__ void finish(int b0, int lane) const {
+    // ST: the tile's rows behind the loop, s_T.  The terminal value once per lane, in front of the single rounding; its weight w_T into WE
+    __device__ __forceinline__ void finish(int b0, int lane, const float* ST) {
         const int b = b0 + (lane & 15);
         if ((lane >> 4) == 0 && b < r.c0 + r.n) {
+            if (TV) r.WE[(size_t)k * r.n + (b - r.c0)] = acc.terminal(r.tv.value(ST + (lane & 15) * NS, 1, NS, b, r.per));
             const size_t kb = (size_t)k * r.B + b;
             if (r.ret != nullptr) r.ret[kb] = (float)acc.sum;
             if (r.len != nullptr) r.len[kb] = acc.n;
@@ -84,7 +94,9 @@ struct SagrL {
     static constexpr int TOTAL = IMG + 4 * WV;
 };
 
-template <int ENV, int MODE>
+// TV: the forward sweep with a terminal value.  A template parameter there, not the runtime-uniform pointer test of the other kernels: the test's
+// operands live in scalar registers across the step loop, the Ant instantiation has none to spare, and what spills costs it a wave per SIMD.
+template <int ENV, int MODE, bool TV = false>
 __global__ void __launch_bounds__(MODE == SAGR_FWD ? 64 : 256, MODE == SAGR_FWD ? 1 : 2)
 k_sagr(SagrK r, const float* __restrict__ dynp, const float* __restrict__ norm) {
     using L = SagrL<ENV>;
@@ -96,9 +108,9 @@ k_sagr(SagrK r, const float* __restrict__ dynp, const float* __restrict__ norm) 
         // ------------------------------------------------ forward sweep: k_score_actions' body, a storing sink ------------------------------------------------
         const int b0 = r.c0 + blockIdx.x * 16;
         const TileRollK tr = {r.B, r.T, r.per, r.init_obs, r.actions, k, 0, nullptr};
-        SagrSink<NS> sink = {r, k};
+        SagrSink<NS, TV> sink = {r, k};
         tile_rollout<ENV, true>(lds, tr, 1, b0, dynp, norm, sink);
-        sink.finish(b0, threadIdx.x & 63);
+        sink.finish(b0, threadIdx.x & 63, lds + C::W_ST);
     } else {
         // ------------------------------------------------ reverse sweep ------------------------------------------------
         const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -158,6 +170,18 @@ k_sagr(SagrK r, const float* __restrict__ dynp, const float* __restrict__ norm) 
         f32x4 lam[OUT_CB];
 #pragma unroll
         for (int cb = 0; cb < OUT_CB; ++cb) lam[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // the terminal value's seed, lambda_T = w_T dV/ds_T, from the x_T tile in lambda's own layout; w_T is the forward sweep's (WE)
+        if (r.tv.set()) {
+            const float* XT = W + (r.T & 1) * L::SB;
+            const float wT = active ? r.WE[(size_t)k * r.n + min(lc, r.n - 1)] : 0.0f;
+#pragma unroll
+            for (int cb = 0; cb < OUT_CB; ++cb)
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) {
+                    const int dim = 16 * cb + 4 * q + rr;
+                    if (dim < NS) lam[cb][rr] = wT * r.tv.grad(dim, XT[c * NS + dim]);
+                }
+        }
         loop_invariant_loads_done();
         for (int t = r.T - 1; t >= 0; --t) {
             const float* ST = W + (t & 1) * L::SB;
@@ -264,6 +288,8 @@ __device__ __forceinline__ SagrBufs sagr_carve(float* lds, const ProblemDesc& pd
     return e;
 }
 
+// TV: with a terminal value -- a template parameter, so that the instantiation without one is the kernel it was (the runtime test costs it a stack slot)
+template <bool TV>
 __global__ void k_sagr_gen_fwd(ProblemDesc pd, SagrK r, const float* __restrict__ dynp, const float* __restrict__ norm) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int LD = blockDim.x, tid = threadIdx.x;
@@ -297,6 +323,7 @@ __global__ void k_sagr_gen_fwd(ProblemDesc pd, SagrK r, const float* __restrict_
         for (int i = 0; i < ns; ++i) e.S[i * LD + tid] = e.XN[i * LD + tid];
     }
     if (active) {
+        if (TV) r.WE[(size_t)k * r.n + lc] = acc.terminal(r.tv.value(e.S + tid, LD, ns, b, r.per));      // S holds s_T behind the loop
         if (r.ret != nullptr) r.ret[(size_t)k * r.B + b] = (float)acc.sum;
         if (r.len != nullptr) r.len[(size_t)k * r.B + b] = acc.n;
     }
@@ -315,6 +342,10 @@ __global__ void k_sagr_gen_bwd(ProblemDesc pd, SagrK r, const float* __restrict_
     const float* __restrict__ pk = dynp + (size_t)k * dn.n_params;
     const float* xs = r.XS + (size_t)k * (r.T + 1) * r.n * ns;
     for (int i = 0; i < ns; ++i) e.LAM[i * LD + tid] = 0.0f;
+    if (r.tv.set() && active) {                              // the terminal value's seed: lambda_T = w_T dV/ds_T
+        const float wT = r.WE[(size_t)k * r.n + lc];
+        for (int i = 0; i < ns; ++i) e.LAM[i * LD + tid] = wT * r.tv.grad(i, xs[((size_t)r.T * r.n + lc) * ns + i]);
+    }
     for (int t = r.T - 1; t >= 0; --t) {
         for (int i = 0; i < ns; ++i) {
             e.S[i * LD + tid] = active ? xs[((size_t)t * r.n + lc) * ns + i] : 0.0f;
@@ -393,8 +424,8 @@ void launch_sagr_mean(const float* grad, size_t n, int K, float* mean, hipStream
 
 // -------------------------------------------------------------------------------------------------
 typedef void (*sagr_kernel_t)(SagrK, const float*, const float*);
-struct SagrEntry { int env; sagr_kernel_t fwd, bwd; int fwd_floats, bwd_floats; };
-#define GENTRY(ENVID) {ENVID, k_sagr<ENVID, SAGR_FWD>, k_sagr<ENVID, SAGR_BWD>, act_wave_floats<ENVID>(), SagrL<ENVID>::TOTAL}
+struct SagrEntry { int env; sagr_kernel_t fwd[2], bwd; int fwd_floats, bwd_floats; };      // fwd[terminal value set]
+#define GENTRY(ENVID) {ENVID, {k_sagr<ENVID, SAGR_FWD>, k_sagr<ENVID, SAGR_FWD, true>}, k_sagr<ENVID, SAGR_BWD>, act_wave_floats<ENVID>(), SagrL<ENVID>::TOTAL}
 static const SagrEntry kSagr[] = {FUSED_HEAD_ENVS(GENTRY)};
 
 int run_score_actions_grad(metrpo_ctx* c, const metrpo_score_actions_grad_args* a, hipStream_t st) {
@@ -402,19 +433,22 @@ int run_score_actions_grad(metrpo_ctx* c, const metrpo_score_actions_grad_args* 
     const size_t ns = pd.ns, B = a->B, T = a->T, K = pd.K;
     bool padded = false;
     const SagrEntry* en = a->force_generic ? nullptr : fused_head_entry(kSagr, c, 65535, &padded);      // the heads are gridDim.y
-    // ---- a chunk's workspace (floats): XS [K][T + 1][Bc][ns] | WT [K][T][Bc]; within 2^26 floats unless args.chunk says otherwise ----
-    const size_t per_cand = K * ((T + 1) * ns + T);
+    // ---- a chunk's workspace (floats): XS [K][T + 1][Bc][ns] | WT [K][T][Bc] | (a terminal value is set) WE [K][Bc]; within 2^26 floats unless args.chunk says otherwise ----
+    const TermVal tv = ctx_term_val(c);
+    const size_t per_cand = K * ((T + 1) * ns + T + (tv.w1 ? 1 : 0));
     const size_t Bc = a->chunk > 0 ? std::min<size_t>(B, (size_t)a->chunk) : std::min<size_t>(B, std::max<size_t>(1, ((size_t)1 << 26) / per_cand));
     const size_t o_wt = (K * (T + 1) * Bc * ns + 3) & ~(size_t)3;
-    { const int rc = ws_grow(c, c->d_sagr, sizeof(float) * (o_wt + K * T * Bc)); if (rc) return rc; }
+    const size_t o_we = o_wt + K * T * Bc;
+    { const int rc = ws_grow(c, c->d_sagr, sizeof(float) * (o_we + (tv.w1 ? K * Bc : 0))); if (rc) return rc; }
     float* ws = (float*)c->d_sagr.p;
     SagrK r = {};
     r.B = a->B; r.T = a->T; r.per = a->B / a->S; r.stop = a->stop_at_done ? 1 : 0; r.gamma = a->gamma;
-    r.init_obs = a->d_init_obs; r.actions = a->d_actions; r.XS = ws; r.WT = ws + o_wt;
+    r.init_obs = a->d_init_obs; r.actions = a->d_actions; r.XS = ws; r.WT = ws + o_wt; r.WE = tv.w1 ? ws + o_we : nullptr; r.tv = tv;
     r.ret = a->d_ret; r.len = a->d_len; r.grad = a->d_grad; r.lam0 = a->d_lam0;
     const float* dyn = c->d_dyn.p;
     size_t sh_f = 0, sh_b = 0;
     int bs = 64;
+    void (*gen_fwd)(ProblemDesc, SagrK, const float*, const float*) = nullptr;
     if (en != nullptr) {
         { const int rc = fused_head_dyn(c, padded, st, &dyn); if (rc) return rc; }
         sh_f = sizeof(float) * (size_t)en->fwd_floats; sh_b = sizeof(float) * (size_t)en->bwd_floats;
@@ -424,18 +458,19 @@ int run_score_actions_grad(metrpo_ctx* c, const metrpo_score_actions_grad_args* 
         while (bs > 1 && fpt * bs * sizeof(float) > LDS_MAX) bs >>= 1;
         if (fpt * bs * sizeof(float) > LDS_MAX) return set_err(c, METRPO_EUNSUPPORTED, "score_actions_grad: layer widths exceed the LDS budget of the generic kernel");
         sh_f = sh_b = fpt * bs * sizeof(float);
-        int rc = allow_dynamic_lds(c, (const void*)k_sagr_gen_fwd, sh_f);
+        gen_fwd = tv.w1 ? k_sagr_gen_fwd<true> : k_sagr_gen_fwd<false>;
+        int rc = allow_dynamic_lds(c, (const void*)gen_fwd, sh_f);
         if (!rc) rc = allow_dynamic_lds(c, (const void*)k_sagr_gen_bwd, sh_b);
         if (rc) return rc;
     }
     for (size_t c0 = 0; c0 < B; c0 += Bc) {
         r.c0 = (int)c0; r.n = (int)std::min(Bc, B - c0);
         if (en != nullptr) {
-            hipLaunchKernelGGL(en->fwd, dim3((r.n + 15) / 16, (unsigned)K), dim3(64), sh_f, st, r, dyn, c->d_norm.p);
+            hipLaunchKernelGGL(en->fwd[tv.w1 ? 1 : 0], dim3((r.n + 15) / 16, (unsigned)K), dim3(64), sh_f, st, r, dyn, c->d_norm.p);
             hipLaunchKernelGGL(en->bwd, dim3((r.n + 63) / 64, (unsigned)K), dim3(256), sh_b, st, r, dyn, c->d_norm.p);
         } else {
             const dim3 grid((r.n + bs - 1) / bs, (unsigned)K);
-            hipLaunchKernelGGL(k_sagr_gen_fwd, grid, dim3(bs), sh_f, st, pd, r, dyn, c->d_norm.p);
+            hipLaunchKernelGGL(gen_fwd, grid, dim3(bs), sh_f, st, pd, r, dyn, c->d_norm.p);
             hipLaunchKernelGGL(k_sagr_gen_bwd, grid, dim3(bs), sh_b, st, pd, r, dyn, c->d_norm.p);
         }
         HIP_TRY(c, hipGetLastError());

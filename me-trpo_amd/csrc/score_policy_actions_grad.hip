@@ -26,7 +26,12 @@
 // sigma by __expf as there), so ret, len and act_out carry the bits of metrpo_score_policy_actions' generic path; the reverse is k_bptt_backward's policy
 // VJP (bptt.hip) behind the clip gate.  Block size by bptt.hip's LDS rule.  Same outputs, workspace, chunking.
 //
-// Workspace: ctx->d_spag = XS | WT | AW of one chunk, within 2^26 floats (args.chunk > 0 overrides).  d_grad_mean: k_sagr_mean.  No atomics anywhere.
+// Terminal value (sact_sum.h: TermVal), as in score_actions_grad.hip: the forward sweeps add the term behind the loop and STORE w_T into WE [K][Bc] (one more slice
+// of WT, only while a value is set; stored, not re-derived); the reverse sweeps start from lambda_T = w_T dV/ds_T formed from the stored XS[T] tile.  The seed
+// enters step T-1 through G and so reaches J_pi(s_T-1) like any lambda.  k_spag_gen_fwd<TV> takes the value as a template parameter (the runtime test reserved
+// a stack slot there); k_spag_fwd, k_spag_bwd and k_spag_gen_bwd test the pointer, runtime-uniform: none of them loses a register or a wave to it.
+//
+// Workspace: ctx->d_spag = XS | WT | AW (| WE) of one chunk, within 2^26 floats (args.chunk > 0 overrides).  d_grad_mean: k_sagr_mean.  No atomics anywhere.
 #include "dyn_tile_step.h"
 #include "dyn_head_adjoint.h"
 #include "pol_head_mfma.h"
@@ -42,6 +47,8 @@ struct SpagK {
     double gamma;
     const float* init_obs; const float* noise;
     float* XS; float* WT; float* AW;      // [K][T+1][n][ns], [K][T][n], [K][T][n][na]
+    float* WE;                            // [K][n]: w_T, one more slice of WT, only while a terminal value is set
+    TermVal tv;                           // the context's terminal value; unset: all NULL
     float* ret; int32_t* len; float* act_out;
     float* grad; float* lam0;             // [K][T][B][na], optional [K][B][ns]
 };
@@ -130,6 +137,7 @@ __global__ void __launch_bounds__(64) k_spag_fwd(SpagK r, const float* __restric
         for (int i = lane; i < lim; i += 64) dst[i] = ST[i];
     }
     if (q == 0 && mine) {                                      // rounded to fp32 once, here
+        if (r.tv.set()) r.WE[(size_t)k * r.n + lc] = acc.terminal(r.tv.value(ST + e * NS, 1, NS, b, r.per));      // ST holds s_T behind the loop
         const size_t kb = (size_t)k * r.B + b;
         if (r.ret != nullptr) r.ret[kb] = (float)acc.sum;
         if (r.len != nullptr) r.len[kb] = acc.n;
@@ -220,6 +228,18 @@ __global__ void __launch_bounds__(256, 2) k_spag_bwd(SpagK r, const float* __res
     f32x4 lam[OUT_CB];
 #pragma unroll
     for (int cb = 0; cb < OUT_CB; ++cb) lam[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // the terminal value's seed, lambda_T = w_T dV/ds_T, from the x_T tile in lambda's own layout; w_T is the forward sweep's (WE)
+    if (r.tv.set()) {
+        const float* XT = W + (r.T & 1) * L::SB;
+        const float wT = active ? r.WE[(size_t)k * r.n + min(lc, r.n - 1)] : 0.0f;
+#pragma unroll
+        for (int cb = 0; cb < OUT_CB; ++cb)
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                const int dim = 16 * cb + 4 * q + rr;
+                if (dim < NS) lam[cb][rr] = wT * r.tv.grad(dim, XT[c * NS + dim]);
+            }
+    }
     loop_invariant_loads_done();
     for (int t = r.T - 1; t >= 0; --t) {
         const float* ST = W + (t & 1) * L::SB;
@@ -331,6 +351,8 @@ __device__ __forceinline__ SpagBufs spag_carve(float* lds, const ProblemDesc& pd
     return e;
 }
 
+// TV: with a terminal value -- a template parameter, so that the instantiation without one is the kernel it was (the runtime test costs it a stack slot)
+template <bool TV>
 __global__ void k_spag_gen_fwd(ProblemDesc pd, SpagK r, const float* __restrict__ dynp, const float* __restrict__ theta, const float* __restrict__ norm) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int LD = blockDim.x, tid = threadIdx.x;
@@ -378,6 +400,7 @@ __global__ void k_spag_gen_fwd(ProblemDesc pd, SpagK r, const float* __restrict_
         for (int i = 0; i < ns; ++i) e.S[i * LD + tid] = e.XN[i * LD + tid];
     }
     if (active) {
+        if (TV) r.WE[(size_t)k * r.n + lc] = acc.terminal(r.tv.value(e.S + tid, LD, ns, b, r.per));      // S holds s_T behind the loop
         if (r.ret != nullptr) r.ret[(size_t)k * r.B + b] = (float)acc.sum;
         if (r.len != nullptr) r.len[(size_t)k * r.B + b] = acc.n;
     }
@@ -427,6 +450,10 @@ __global__ void k_spag_gen_bwd(ProblemDesc pd, SpagK r, const float* __restrict_
     const float* __restrict__ log_std = theta + pn.n_params;
     const float* xs = r.XS + (size_t)k * (r.T + 1) * r.n * ns;
     for (int i = 0; i < ns; ++i) e.LAM[i * LD + tid] = 0.0f;
+    if (r.tv.set() && active) {                              // the terminal value's seed: lambda_T = w_T dV/ds_T; it reaches J_pi through G like any lambda
+        const float wT = r.WE[(size_t)k * r.n + lc];
+        for (int i = 0; i < ns; ++i) e.LAM[i * LD + tid] = wT * r.tv.grad(i, xs[((size_t)r.T * r.n + lc) * ns + i]);
+    }
     for (int t = r.T - 1; t >= 0; --t) {
         for (int i = 0; i < ns; ++i) {
             e.S[i * LD + tid] = active ? xs[((size_t)t * r.n + lc) * ns + i] : 0.0f;
@@ -482,20 +509,23 @@ int run_score_policy_actions_grad(metrpo_ctx* c, const metrpo_score_policy_actio
     const size_t ns = pd.ns, na = pd.na, B = a->B, T = a->T, K = pd.K;
     bool padded = false;
     const SpagEntry* en = a->force_generic ? nullptr : fused_head_entry(kSpag, c, 65535, &padded);      // the heads are gridDim.y; the class holds the 2 x 32 tanh policy
-    // ---- a chunk's workspace (floats): XS [K][T + 1][Bc][ns] | WT [K][T][Bc] | AW [K][T][Bc][na]; within 2^26 floats unless args.chunk says otherwise ----
-    const size_t per_cand = K * ((T + 1) * ns + T + T * na);
+    // ---- a chunk's workspace (floats): XS [K][T + 1][Bc][ns] | WT [K][T][Bc] | AW [K][T][Bc][na] | (a terminal value is set) WE [K][Bc]; within 2^26 floats unless args.chunk says otherwise ----
+    const TermVal tv = ctx_term_val(c);
+    const size_t per_cand = K * ((T + 1) * ns + T + T * na + (tv.w1 ? 1 : 0));
     const size_t Bc = a->chunk > 0 ? std::min<size_t>(B, (size_t)a->chunk) : std::min<size_t>(B, std::max<size_t>(1, ((size_t)1 << 26) / per_cand));
     const size_t o_wt = (K * (T + 1) * Bc * ns + 3) & ~(size_t)3, o_aw = (o_wt + K * T * Bc + 3) & ~(size_t)3;
-    { const int rc = ws_grow(c, c->d_spag, sizeof(float) * (o_aw + K * T * Bc * na)); if (rc) return rc; }
+    const size_t o_we = o_aw + K * T * Bc * na;
+    { const int rc = ws_grow(c, c->d_spag, sizeof(float) * (o_we + (tv.w1 ? K * Bc : 0))); if (rc) return rc; }
     float* ws = (float*)c->d_spag.p;
     SpagK r = {};
     r.B = a->B; r.T = a->T; r.per = a->B / a->S; r.stop = a->stop_at_done ? 1 : 0; r.in_std = a->noise_in_std ? 1 : 0; r.gamma = a->gamma;
-    r.init_obs = a->d_init_obs; r.noise = a->d_noise; r.XS = ws; r.WT = ws + o_wt; r.AW = ws + o_aw;
+    r.init_obs = a->d_init_obs; r.noise = a->d_noise; r.XS = ws; r.WT = ws + o_wt; r.AW = ws + o_aw; r.WE = tv.w1 ? ws + o_we : nullptr; r.tv = tv;
     r.ret = a->d_ret; r.len = a->d_len; r.act_out = a->d_act_out; r.grad = a->d_grad; r.lam0 = a->d_lam0;
     const float* dyn = c->d_dyn.p;
     size_t sh_f = 0, sh_b = 0;
     int bs = 64;
     spag_kernel_t fwd = nullptr;
+    void (*gen_fwd)(ProblemDesc, SpagK, const float*, const float*, const float*) = nullptr;
     if (en != nullptr) {
         { const int rc = fused_head_dyn(c, padded, st, &dyn); if (rc) return rc; }
         fwd = en->fwd[a->d_noise != nullptr ? 1 : 0];
@@ -508,7 +538,8 @@ int run_score_policy_actions_grad(metrpo_ctx* c, const metrpo_score_policy_actio
         while (bs > 1 && fpt * bs * sizeof(float) > LDS_MAX) bs >>= 1;
         if (fpt * bs * sizeof(float) > LDS_MAX) return set_err(c, METRPO_EUNSUPPORTED, "score_policy_actions_grad: layer widths exceed the LDS budget of the generic kernel");
         sh_f = sh_b = fpt * bs * sizeof(float);
-        int rc = allow_dynamic_lds(c, (const void*)k_spag_gen_fwd, sh_f);
+        gen_fwd = tv.w1 ? k_spag_gen_fwd<true> : k_spag_gen_fwd<false>;
+        int rc = allow_dynamic_lds(c, (const void*)gen_fwd, sh_f);
         if (!rc) rc = allow_dynamic_lds(c, (const void*)k_spag_gen_bwd, sh_b);
         if (rc) return rc;
     }
@@ -519,7 +550,7 @@ int run_score_policy_actions_grad(metrpo_ctx* c, const metrpo_score_policy_actio
             hipLaunchKernelGGL(en->bwd, dim3((r.n + 63) / 64, (unsigned)K), dim3(256), sh_b, st, r, dyn, c->d_theta.p, c->d_norm.p);
         } else {
             const dim3 grid((r.n + bs - 1) / bs, (unsigned)K);
-            hipLaunchKernelGGL(k_spag_gen_fwd, grid, dim3(bs), sh_f, st, pd, r, dyn, c->d_theta.p, c->d_norm.p);
+            hipLaunchKernelGGL(gen_fwd, grid, dim3(bs), sh_f, st, pd, r, dyn, c->d_theta.p, c->d_norm.p);
             hipLaunchKernelGGL(k_spag_gen_bwd, grid, dim3(bs), sh_b, st, pd, r, dyn, c->d_theta.p, c->d_norm.p);
         }
         HIP_TRY(c, hipGetLastError());

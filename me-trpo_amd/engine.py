@@ -647,6 +647,27 @@ class Engine(object):
         chunk on the matrix instructions), 'generic' (one thread per (candidate, head)); None before the first."""
         return {0: 'generic', 1: 'fused'}.get(int(lib.metrpo_last_score_policy_actions_grad_kernel(self._ctx)))
 
+    # ------------------------------------------------------------------ terminal value of the four scoring calls
+    def set_terminal_value(self, w1, w2, bias):
+        """Terminal value of score_actions / score_actions_grad / score_policy_actions / score_policy_actions_grad (include/metrpo.h):
+        V(s) = bias + sum_d (w1[d] o_d + w2[d] o_d^2), o = clip(s, -10, 10); ret gains gamma^T alive_T V(s_T), the gradients start from the
+        matching seed.  w1, w2 [ns]; bias a scalar, or [S]: one per start state of the scoring call (candidate b uses bias[b // (B // S)]).
+        Tensors or arrays.  planning.baseline_terminal_value forms the three from a LinearFeatureBaseline fit.  Stays set until
+        clear_terminal_value(); every other call ignores it.  Stream-ordered like the scoring calls: nothing is synchronised."""
+        dev = self.device
+        a = _f32(w1, dev, (self.ns,)); b = _f32(w2, dev, (self.ns,))
+        c = _f32(bias, dev).reshape(-1)
+        self._chk(lib.metrpo_set_terminal_value(self._ctx, _ptr(a), _ptr(b), _ptr(c), int(c.numel()), self._stream()))
+        self._tv_keep = (a, b, c)                                                  # alive until the stream has consumed them
+
+    def clear_terminal_value(self):
+        self._chk(lib.metrpo_clear_terminal_value(self._ctx))
+
+    @property
+    def terminal_value(self):
+        """0 while no terminal value is set, else the number of biases it holds (1, or S)."""
+        return int(lib.metrpo_has_terminal_value(self._ctx))
+
     # ------------------------------------------------------------------ fused rollout
     def rollout(self, B, T, H, sam_mode, pool, determ=False, eval_all_heads=True, seed=0, stream_offset=0,
                 eps=None, model_idx=None, sel_noise=None, reset_idx=None, reset_model=None, out=None,

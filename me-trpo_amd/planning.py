@@ -15,7 +15,11 @@ respect to the candidates in one call; refine_actions runs projected gradient as
 
 The same in NOISE space around the policy: Engine.score_policy_actions_grad / metrpo_score_policy_actions_grad gives dR / d noise with the policy path
 included; refine_noise is refine_actions there (projection clamp(+-noise_clip)), plan_cem_policy_gd refines plan_cem_policy's elites (or all) before
-each refit, and ShootingController(policy_prior=True, noise_grad_steps=n) plans with it."""
+each refit, and ShootingController(policy_prior=True, noise_grad_steps=n) plans with it.
+
+A value behind the horizon: Engine.set_terminal_value / metrpo_set_terminal_value adds gamma^T alive_T V(s_T) to every return above and seeds the
+gradients to match.  The scorers are closures over the engine, so every planner here has it without a signature change: set it, plan, clear it.
+baseline_terminal_value forms V from a LinearFeatureBaseline fit; ShootingController(terminal_value=baseline) does the setting and clearing."""
 import numpy as np
 import torch
 
@@ -525,6 +529,29 @@ def plan_cem_policy_gd(engine, states, horizon, n_candidates, n_elites, n_iters,
                 policy_score=policy_score)
 
 
+def baseline_terminal_value(baseline, t_index, ns):
+    """(w1 [ns], w2 [ns], bias) for Engine.set_terminal_value from a LinearFeatureBaseline fit (or its coefficient vector
+    [o, o^2, al, al^2, al^3, 1], length 2 ns + 4) with the time features evaluated at path step t_index, al = t_index / 100:
+    w1 = c[:ns], w2 = c[ns:2 ns], bias = c[2 ns] al + c[2 ns + 1] al^2 + c[2 ns + 2] al^3 + c[2 ns + 3] -- LinearFeatureBaseline.predict at row t_index.
+    t_index is a scalar (bias a scalar) or [S] (bias [S]: one per start state).  Coefficients that live on the device stay there: nothing is read back."""
+    c = getattr(baseline, 'coeffs_for_kernel', baseline)
+    if c is None:
+        raise ValueError("baseline_terminal_value: the baseline has not been fitted")
+    ns = int(ns)
+    if torch.is_tensor(c):
+        c = c.to(torch.float64).reshape(-1)
+        al = torch.as_tensor(t_index, device=c.device).to(torch.float64) / 100.0
+    else:
+        c = np.asarray(c, dtype=np.float64).reshape(-1)
+        al = np.asarray(t_index, dtype=np.float64) / 100.0
+    if c.shape[0] != 2 * ns + 4:
+        raise ValueError("baseline_terminal_value: %d coefficients, expected 2 * %d + 4" % (c.shape[0], ns))
+    if al.ndim > 1:
+        raise ValueError("baseline_terminal_value: t_index is a scalar or [S]")
+    bias = c[2 * ns] * al + c[2 * ns + 1] * al ** 2 + c[2 * ns + 2] * al ** 3 + c[2 * ns + 3]
+    return c[:ns], c[ns:2 * ns], bias
+
+
 class ShootingController(object):
     """Model-predictive control by CEM with a warm start, with the policy's call shape: get_actions(obs [S, ns]) -> (actions [S, na], {}).
     Every call plans `horizon` steps ahead from obs, returns the first action of the plan's mean and keeps the rest: the next call starts from the
@@ -534,11 +561,14 @@ class ShootingController(object):
     policy_prior=True plans with plan_cem_policy (noise_clip) around the engine's policy instead: the warm start is the noise mean shifted by one step,
     its last row reset to 0, and the action is clip(policy mean(obs) + noise mean[0]).
     policy_prior=True with noise_grad_steps > 0 plans with plan_cem_policy_gd (noise_grad_lr, refine, noise_grad_scorer): gradients with respect to the
-    NOISE, the policy path included."""
+    NOISE, the policy path included.
+    terminal_value=baseline (a fitted LinearFeatureBaseline, or its coefficient vector) plans with a value behind the horizon: the controller counts
+    every env's path steps (one per get_actions call, zeroed by reset), and around each plan sets the engine's terminal value to the baseline at
+    path step counter + horizon -- one bias per env -- and clears it again.  None: nothing is set, cleared or counted."""
 
     def __init__(self, engine, horizon, n_candidates, n_elites, n_iters, init_mean=None, init_std=1.0, alpha=0.0, min_std=0.0, gamma=1.0,
                  aggregate='mean', generator=None, stop_at_done=True, scorer=None, na=None, grad_steps=0, grad_lr=0.05, refine='elites', grad_scorer=None,
-                 policy_prior=False, noise_clip=2.0, noise_grad_steps=0, noise_grad_lr=0.05, noise_grad_scorer=None):
+                 policy_prior=False, noise_clip=2.0, noise_grad_steps=0, noise_grad_lr=0.05, noise_grad_scorer=None, terminal_value=None):
         self.engine, self.horizon, self.scorer, self.na = engine, int(horizon), scorer, (engine.na if engine is not None else na)
         # grad_steps > 0: plan_cem_gd with these settings in plan_cem's place (0: plan_cem, as before)
         self.grad_steps, self.grad_kw = _check_refine(grad_steps, grad_lr, 'adam'), dict(grad_lr=grad_lr, refine=refine, grad_scorer=grad_scorer)
@@ -560,13 +590,28 @@ class ShootingController(object):
                        generator=generator, stop_at_done=stop_at_done)
         self._mean = None                                                                 # [S, T, na]: the warm start of the next call
         self.last_plan = None
+        # terminal_value: the baseline whose value at path step counter + horizon is the engine's terminal value during a plan
+        self.terminal_value = terminal_value
+        if terminal_value is not None and engine is None:
+            raise ValueError("terminal_value needs an engine (the value is set on it around each plan)")
+        self._steps = None                                                                # [S] int64: path steps taken since the env's last reset
 
     def reset(self, dones=None):
-        """Forget the warm start: of every env (dones None) or of the envs whose entry of dones is set."""
+        """Forget the warm start: of every env (dones None) or of the envs whose entry of dones is set.  Their step counters start from 0 again."""
+        if self._steps is not None:
+            if dones is None:
+                self._steps = None
+            else:
+                d = np.asarray(dones).astype(bool).reshape(-1)
+                # another number of envs than the counter was made for: every counter starts afresh, as get_actions does with the warm start
+                self._steps = np.where(d, 0, self._steps) if d.shape[0] == self._steps.shape[0] else None
         if dones is None or self._mean is None:
             self._mean = None
             return
         d = torch.as_tensor(np.asarray(dones).astype(bool), device=self._mean.device)
+        if d.numel() != self._mean.shape[0]:                                              # another number of envs: get_actions would drop the warm start too
+            self._mean = None
+            return
         self._mean = torch.where(d.view(-1, 1, 1), self._fresh(self._mean.shape[0], self._mean.device), self._mean)
 
     def _fresh(self, S, dev):
@@ -583,6 +628,21 @@ class ShootingController(object):
         return torch.cat([noise[:, 1:], torch.zeros_like(noise[:, -1:])], dim=1)
 
     def get_actions(self, observations):
+        if self.terminal_value is None:
+            return self._plan(observations)
+        obs = observations if torch.is_tensor(observations) else np.asarray(observations)
+        S = obs.shape[0] if obs.ndim == 2 else 1
+        if self._steps is None or self._steps.shape[0] != S:
+            self._steps = np.zeros(S, dtype=np.int64)
+        self.engine.set_terminal_value(*baseline_terminal_value(self.terminal_value, self._steps + self.horizon, self.engine.ns))
+        try:
+            out = self._plan(observations)
+        finally:
+            self.engine.clear_terminal_value()
+        self._steps = self._steps + 1
+        return out
+
+    def _plan(self, observations):
         obs = torch.as_tensor(np.asarray(observations) if not torch.is_tensor(observations) else observations)
         S = obs.shape[0] if obs.dim() == 2 else 1
         start = self._mean if (self._mean is not None and self._mean.shape[0] == S) else self.init_mean
