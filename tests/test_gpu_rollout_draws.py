@@ -5,7 +5,7 @@ the restated draws of the same (seed, stream_offset, t0) and checks, against the
   * heads: last_model is the cur_model the restated reset_model implies; done / tpath are the oracle's (free-running for horizon-terminated envs);
   * normals: z = (act - mean) / exp(log_std) against the restated eps within TOL.PHILOX_NORMAL;
   * the step, teacher-forced: helpers.oracle_rollout on the restated draws and the device's observations -> mean, act, rew, next state within the
-    family's row of tests/tolerances.py (STEP, WIDE from 128 hidden units).  The K heads of make_problem differ by ~1e-2: a wrong step_rand / eps_rand
+    family's row of tests/tolerances.py (STEP, WIDE from 128 hidden units).  The comparison itself is tests/rollout_check.py (_device_run, _check).  The K heads of make_problem differ by ~1e-2: a wrong step_rand / eps_rand
     head, a wrong noise chunk or a swapped sine is off by orders.
 
 Widening of the step tolerances by the draws' own error (the device's Box-Muller uses __logf / __sincosf): a normal may be off by PHILOX_NORMAL, so
@@ -21,17 +21,12 @@ from oracle import metrpo_oracle as O
 import helpers as Hh
 import tolerances as TOL
 import rollout_draws_ref as R
+from rollout_check import _device_run, _check              # the comparison itself: shared with tests/test_gpu_rollout_edges.py
 
 pytestmark = pytest.mark.gpu
 
 N_POOL = 1000
-SMALL_R = 2.0 ** -6            # normals of a smaller restated radius are left out of the normals check (only)
-EXCLUDE_CAP = 1e-3             # ... at most this share of a case's normals (expected 1.2e-4)
 HUMANOID_POL = (100, 50, 25)
-
-
-def cpu(t):
-    return t.detach().cpu().numpy().astype(np.float64)
 
 
 def seed_of(i):
@@ -52,96 +47,6 @@ class Problem(object):
         assert len({r.tobytes() for r in self.pool32}) == N_POOL    # distinct rows: a pool row identifies its index
         self.tol = TOL.STEP if max(hidden) < 128 else TOL.WIDE
         self.pool_t = torch.tensor(self.pool, dtype=torch.float32, device=self.eng.device)
-
-
-def _device_run(p, B, T, H, mode, kernel, seed, stream_offset=0, determ=False, force_generic=False, supplied=None, chunks=None):
-    """One production-mode rollout (or the chunks of one: `chunks` = lengths summing to T, continued with t0 / resume / last_state) -> NumPy fields."""
-    eng, dev = p.eng, p.eng.device
-    lts, lmd = torch.zeros(B, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.int32, device=dev)
-    parts, resume, t0 = [], None, 0
-    for Tc in (chunks or (T,)):
-        kw = {k: v[t0:t0 + Tc + (1 if k.startswith('reset') else 0)] for k, v in (supplied or {}).items()}
-        tr = eng.rollout(B, Tc, H, mode, p.pool_t, determ=determ, seed=seed, stream_offset=stream_offset, force_generic=force_generic,
-                         t0=t0, resume=resume, last_state=(lts, lmd), **kw)
-        if not force_generic:                                      # metrpo_rollout_generic IS the kernel: it goes through no dispatch and records none
-            assert eng.last_rollout_kernel() == kernel, (eng.last_rollout_kernel(), eng.rollout_note())
-        parts.append({k: cpu(getattr(tr, k)) for k in ('obs', 'act', 'mean', 'rew', 'done', 'tpath', 'last_obs')})
-        resume = (tr.last_obs.clone(), lts.clone(), lmd.clone())
-        t0 += Tc
-    assert t0 == T
-    out = {k: np.concatenate([q[k] for q in parts], 0) for k in ('obs', 'act', 'mean', 'rew', 'done', 'tpath')}
-    out['done'] = out['done'].astype(bool); out['tpath'] = out['tpath'].astype(np.int64)
-    out['last_obs'] = parts[-1]['last_obs']
-    out['last_model'], out['last_ts'] = cpu(lmd).astype(np.int64), cpu(lts).astype(np.int64)
-    return out
-
-
-def _close(got, ref, tol, extra, what):
-    lim = tol['atol'] + extra + tol['rtol'] * np.abs(ref)
-    err = np.abs(got - ref)
-    used = float((err / lim).max()) if err.size else 0.0
-    print('    %-8s max |err| %.3g  = %.2f of the bound' % (what, float(err.max()) if err.size else 0.0, used))
-    assert np.isfinite(got).all() and used <= 1.0, (what, float(err.max()), used)
-
-
-def _check(p, dev, dr, rad, B, T, H, mode, determ, label, own=('eps', 'model_idx', 'sel_noise', 'reset_idx', 'reset_model')):
-    """`dr`: the draws the device must have used; `own`: those it drew itself (the restated ones; the others were supplied)."""
-    env, K, ns, na, tol = p.env, p.K, p.dm.ns, p.dm.na, p.tol
-    dn, tpath = dev['done'], dev['tpath']
-    print('%s: B %d T %d H %d %s, %d resets' % (label, B, T, H, mode, int(dn.sum())))
-    # ---- pool rows, exact
-    np.testing.assert_array_equal(dev['obs'][0], p.pool32[dr['reset_idx'][0]])
-    nxt_obs = np.concatenate([dev['obs'][1:], dev['last_obs'][None]], 0)
-    assert dn.any()
-    np.testing.assert_array_equal(nxt_obs[dn], p.pool32[dr['reset_idx'][1:]][dn])
-    # ---- heads and episode structure, exact
-    cm, ts = dr['reset_model'][0].copy(), np.zeros(B, np.int64)
-    for t in range(T):
-        np.testing.assert_array_equal(tpath[t], ts)
-        cm = np.where(dn[t], dr['reset_model'][t + 1], cm)
-        ts = np.where(dn[t], 0, ts + 1)
-    np.testing.assert_array_equal(dev['last_model'], cm)
-    np.testing.assert_array_equal(dev['last_ts'], ts)
-    assert dn[tpath == H - 1].all()
-    ref = Hh.oracle_rollout(p.dm, p.th, p.pdims, env, p.pool32, dr, B, T, H, mode, determ, teacher_obs=dev['obs'])
-    assert np.array_equal(dn, ref['done']) and np.array_equal(tpath, ref['tpath'])
-    if env != 'ant':
-        free = Hh.oracle_rollout(p.dm, p.th, p.pdims, env, p.pool32, dr, B, T, H, mode, determ)
-        assert np.array_equal(dn, free['done']) and np.array_equal(tpath, free['tpath'])
-        assert np.array_equal(dn, tpath == H - 1)
-    else:
-        assert (dn & (tpath < H - 1)).any()                           # some episodes did end on the state
-    # ---- normals
-    sd = np.exp(np.maximum(p.th[-na:], O.LOG_MIN_STD))
-    bound = TOL.PHILOX_NORMAL
-    extra_act = np.zeros((T, B, na))
-    if determ:
-        np.testing.assert_array_equal(dev['act'], dev['mean'])
-    else:
-        z = (dev['act'] - dev['mean']) / sd
-        keep = (rad['eps'] >= SMALL_R) if 'eps' in own else np.ones(z.shape, bool)
-        share = 1.0 - keep.mean()
-        err = np.abs(z - dr['eps'])
-        worst = float(err[keep].max())
-        print('    PHILOX_NORMAL %s %s worst %.4g excluded %.3g (%d of %d; worst among them %.3g)' % (
-            label, 'drawn' if 'eps' in own else 'floor', worst, share, int((~keep).sum()), keep.size, float(err[~keep].max()) if (~keep).any() else 0.0))
-        assert share <= EXCLUDE_CAP, share
-        assert worst <= bound, worst
-        if 'eps' in own:
-            extra_act = bound * sd * np.where(keep, 1.0, SMALL_R / np.maximum(rad['eps'], 1e-300))
-    # ---- the step, teacher-forced
-    extra_tb = extra_act.max(axis=2)
-    extra_next = np.repeat(extra_tb[:, :, None], ns, axis=2)
-    if mode == 'model_mean_std' and 'sel_noise' in own:
-        grow = np.where(rad['sel_noise'] >= SMALL_R, 1.0, SMALL_R / np.maximum(rad['sel_noise'], 1e-300))
-        assert (grow > 1.0).mean() <= EXCLUDE_CAP
-        for t in range(T):
-            heads = O.dynamics_forward_all(p.dm, dev['obs'][t], np.clip(ref['act'][t], -1, 1))
-            extra_next[t] += bound * np.std(heads, axis=0) * grow[t]
-    _close(dev['mean'], ref['mean'], tol, 0.0, 'mean')
-    _close(dev['act'], ref['act'], tol, extra_act, 'act')
-    _close(dev['rew'], ref['rew'], tol, extra_next.max(axis=2) + extra_tb, 'rew')
-    _close(nxt_obs[~dn], ref['next'][~dn], tol, extra_next[~dn], 'next')
 
 
 def _production(p, B, T, H, mode, kernel, seed, label, stream_offset=0, determ=False, force_generic=False, chunks=None):
