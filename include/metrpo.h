@@ -201,6 +201,18 @@ int32_t metrpo_rollout(metrpo_ctx* ctx, const metrpo_rollout_args* args, void* s
  * (env_helpers.py:609-635); these two calls are how a caller learns which of this library's it got. */
 int32_t metrpo_last_rollout_kernel(const metrpo_ctx* ctx);
 const char* metrpo_rollout_note(const metrpo_ctx* ctx);
+/* Diagnostics: the sub-form of the last metrpo_rollout on a GEMM-class (3, 5, 6, 7) or resident (4) family, as the host noted it while it enqueued the launches
+ * (no device work, no synchronisation).  out[16]:
+ *   [0]  family, as metrpo_last_rollout_kernel
+ *   [1]  pre-step: 0 2 x 32 MFMA, 1 the same with the previous step's post merged in, 2 Humanoid MFMA3, 3 MFMA3 split (a tile per workgroup), 4 GEMM chain,
+ *        5 VALU k_big_pre, 6 MFMA3 with the post merged in; -1 none (resident, fused 2 x 64 families)
+ *   [2]  k_big_post's lanes per env, 32 or 64; 0 where a persistent or resident launch closes the steps
+ *   [3]  stream-K mode 0 ... 3      [4] late split of the launch that carries the output layer      [5] layer 0: 0 producer, 1 k_l0_rows, 2 tile GEMM
+ *   [6]  fused output tile 0, 1, 2  [7] partials of the output layer added in the closing kernel (0: the output layer was unsplit)
+ *   [8]  persistent: two-block tiles     [9] persistent: closing workgroups     [10] rounds: 0 single, 1 side by side (streams / one resident grid), 2 merged
+ *   [11] resident: slice width   [12] threads per workgroup   [13] post waves per workgroup   [14] rounds per launch group   [15] rotating deal
+ * Everything behind [0] is 0 ([1]: -1) on the other families. */
+int32_t metrpo_debug_last_rollout_launch(const metrpo_ctx* ctx, int32_t* out);
 
 /* ---- opt-in bf16-operand dynamics forward inside metrpo_rollout (an EXTENSION: the reference computes in f32 throughout) ----
  * The f32 matrix instruction of gfx950 runs at 1/16 of the bf16 one's rate and there is no xf32 form.  The dynamics model is a residual,

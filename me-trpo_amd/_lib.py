@@ -220,6 +220,7 @@ SYMBOLS = {
     'metrpo_option_name': (C.c_char_p, [_I]),
     'metrpo_last_rollout_kernel': (_I, [_P]),
     'metrpo_rollout_note': (C.c_char_p, [_P]),
+    'metrpo_debug_last_rollout_launch': (_I, [_P, _P]),
     'metrpo_set_dyn_precision': (_I, [_P, _I]),
     'metrpo_get_dyn_precision': (_I, [_P]),
     'metrpo_policy_adam_reset': (_I, [_P, _P]),

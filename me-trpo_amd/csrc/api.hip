@@ -118,6 +118,18 @@ extern "C" int32_t metrpo_debug_last_update(const metrpo_ctx* c, int32_t* out) {
     return METRPO_OK;
 }
 
+// Diagnostics hook (tests/test_gpu_wide_rollout_edges.py): what the last metrpo_rollout of this context launched, as the host wrote it down while it enqueued it (no device work,
+// no synchronisation).  out[16] = family (as metrpo_last_rollout_kernel), then metrpo_ctx::RollLast field by field; everything behind the family is 0 (pre-step kind: -1)
+// on the families that are neither GEMM-class nor resident.
+extern "C" int32_t metrpo_debug_last_rollout_launch(const metrpo_ctx* c, int32_t* out) {
+    if (!c || !out) return METRPO_ENULL;
+    const auto& l = c->roll_last;
+    const int v[16] = {c->last_rollout_kernel, l.pre, l.post_width, l.sk_mode, l.late, l.l0_route, l.fuse_tile, l.out_splits, l.persist_wide, l.nclose, l.rounds,
+                       l.res_ws, l.res_threads, l.res_pw, l.res_rg, l.res_rot};
+    for (int i = 0; i < 16; ++i) out[i] = v[i];
+    return METRPO_OK;
+}
+
 // Diagnostics hook (not part of include/metrpo.h; tests/test_gpu_trpo_solve.py): the Fisher-vector products of the last CG solve metrpo_trpo_update / _begin (and their _fvp forms)
 // enqueued, as the host wrote them down (no device work, no synchronisation; after an update the last noted LAUNCH is a line-search evaluation).  out[8] = family and UpdOp as
 // launched of the products (op 1, or 3 = OP_FVPC where they read the gradient launch's activation cache; -1: the solve made none, -2: they disagree), index into the fused 2 x 32
@@ -368,6 +380,7 @@ extern "C" int32_t metrpo_rollout(metrpo_ctx* c, const metrpo_rollout_args* a, v
         return set_err(c, METRPO_EINVAL, "rollout: d_init_obs, d_init_ts and d_init_model must be given together");
     if (a->B == 0 || a->T == 0) return METRPO_OK;
     c->rollout_note.clear();
+    c->roll_last = metrpo_ctx::RollLast();
     if (c->dyn_precision == METRPO_DYN_BF16) {                                               // opt-in (metrpo_set_dyn_precision: GEMM-class shapes only)
         c->last_rollout_kernel = 7;
         return launch_rollout_gemm(c, a, (hipStream_t)stream);

@@ -161,6 +161,14 @@ struct metrpo_ctx {
     // the Fisher-vector products of the last CG solve run_trpo_update enqueued (metrpo_debug_last_solve), written on the host from upd_last after each of them:
     // family / op / table of the last product (-1: the solve made none), their count (step-scale product included), and the SolveScope / fusion the solve ran under
     struct SolveLast { int family = -1, op = -1, table = -1, n_fvp = 0, cache_activations = 0, publish_image = 0, fused_tails = 0, fvp_batch = 0; } solve_last;
+    // the last metrpo_rollout on a GEMM-class or resident family, written on the host while it is enqueued (metrpo_debug_last_rollout_launch; rollout_gemm.hip,
+    // rollout_resident.hip): pre-step kind (0 2 x 32 MFMA, 1 the same with the previous step's post merged in, 2 Humanoid MFMA3, 3 MFMA3 split, 4 GEMM chain,
+    // 5 VALU k_big_pre, 6 MFMA3 with the post merged in; -1: none), k_big_post's lanes per env (0: a persistent or resident launch closes the steps), SkPath::mode,
+    // SkArgs::late of the launch that carries the output layer, layer-0 route (0 producer, 1 k_l0_rows, 2 tile GEMM), fused output tile, partials of the output
+    // layer that k_big_post adds (0: unsplit), persistent: two-block tiles | closing workgroups, rounds (0 single, 1 parallel streams, 2 merged),
+    // resident: slice width | threads | post waves per workgroup | rounds per launch group | rotating deal.  All 0 / -1 on every other family.
+    struct RollLast { int pre = -1, post_width = 0, sk_mode = 0, late = 0, l0_route = 0, fuse_tile = 0, out_splits = 0, persist_wide = 0, nclose = 0, rounds = 0,
+                      res_ws = 0, res_threads = 0, res_pw = 0, res_rg = 0, res_rot = 0; } roll_last;
     std::string rollout_note;   // why the last metrpo_rollout left the fast dispatch table ("" when it did not): metrpo_rollout_note
     int fallback_logged = 0;  // a rollout shape that fell off the fast dispatch table has been reported once (METRPO_VERBOSE)
     std::vector<std::pair<void*, size_t>> ws_retired; size_t ws_retired_bytes = 0;   // outgrown workspaces and their sizes (ws_grow below): freed by metrpo_destroy, or by one sweep once they pass WS_RETIRED_MAX

@@ -772,7 +772,8 @@ bool gemm_path_applicable(const metrpo_ctx* c) {
 }
 
 // One chunk of the step loop on stream `st`.  ws == nullptr: only report the workspace size (bytes, 256-aligned) through *need_out.
-static int rollout_gemm_chunk(metrpo_ctx* c, const metrpo_rollout_args* a, hipStream_t st, char* ws, size_t* need_out, int vB = 0, int vR = 0) {
+// note: write this chunk's plan into c->roll_last (metrpo_debug_last_rollout_launch); the parallel rounds' side threads do not
+static int rollout_gemm_chunk(metrpo_ctx* c, const metrpo_rollout_args* a, hipStream_t st, char* ws, size_t* need_out, int vB = 0, int vR = 0, bool note = true) {
     const ProblemDesc& pd = c->pd;
     const int B = a->B, K = pd.K, L = pd.dyn.n_layers;
     int maxh = 0;
@@ -875,6 +876,16 @@ static int rollout_gemm_chunk(metrpo_ctx* c, const metrpo_rollout_args* a, hipSt
     bs.ts = (int*)p; bs.cur_model = bs.ts + B;
     bs.out_ld = pd.ns; bs.xone = (sk.mode == 1 || l0r) ? 1 : 0;
     if (sk.mode) c->last_rollout_kernel = 5;
+    const bool pre_split = !persist && pre_mfma != nullptr && pre_lds != 0 && B <= 16 * c->n_sm && ctx_opt(c, OPT_NO_PRE_SPLIT) == nullptr;
+    const bool pre_merged = !persist && pre_post != nullptr && a->T >= 2;                 // steps t >= 1 close step t - 1 themselves
+    if (note) {
+        auto& n = c->roll_last;
+        n.pre = pre_mfma ? (pre_lds ? (pre_merged ? 6 : pre_split ? 3 : 2) : (pre_merged ? 1 : 0)) : (pre_gemm ? 4 : 5);
+        n.post_width = persist ? 0 : (pd.ns <= 32 ? 32 : 64);
+        n.sk_mode = sk.mode; n.late = sk.mode ? ska.late : 0; n.l0_route = (sk.mode == 1) ? 0 : (l0r ? 1 : 2);
+        n.fuse_tile = fuse_tile; n.out_splits = sk.mode ? ska.N / 256 : 0;
+        n.persist_wide = (persist && skp.wide) ? 1 : 0; n.nclose = 0;
+    }
     unsigned sk_epoch = 0;                                   // flags are zeroed below; every launch of this chain takes the next epoch
     if (sk.mode) {
         const int Lo = L - 1;                                // output layer
@@ -923,6 +934,7 @@ static int rollout_gemm_chunk(metrpo_ctx* c, const metrpo_rollout_args* a, hipSt
         pa.G8 = skp_grid / 8; pa.T = a->T;
         // closing workgroups: each closes ~17 us per (row block, step); enough of them to stay under ~60 % busy at this launch's step time, at most one per XCD
         { const char* nc = ctx_opt(c, OPT_PERSIST_NCLOSE); pa.nclose = nc ? std::max(1, std::min((int)SKP_NCLOSE, atoi(nc))) : skp_nclose; }
+        if (note) c->roll_last.nclose = pa.nclose;
         pa.xflag = skp_flags; pa.arrive = (unsigned*)(skp_flags + (B + 127) / 128); pa.stop = r.stop; pa.post = skp_post;
         HIP_TRY(c, hipMemsetAsync(skp_flags, 0, nSkpFlag * sizeof(float), st));
         if (ctx_opt(c, OPT_PERSIST_STATS) != nullptr) {           // developer statistics of this launch (metrpo_debug_persist_stats)
@@ -950,8 +962,7 @@ static int rollout_gemm_chunk(metrpo_ctx* c, const metrpo_rollout_args* a, hipSt
         c->last_rollout_kernel = 6;
         return METRPO_OK;
     }
-    // Humanoid's 100-50-25 pre-step at small batches: a tile per workgroup, column blocks over its waves (k_big_pre_mfma3_split)
-    const bool pre_split = pre_mfma != nullptr && pre_lds != 0 && B <= 16 * c->n_sm && ctx_opt(c, OPT_NO_PRE_SPLIT) == nullptr;
+    // Humanoid's 100-50-25 pre-step at small batches: a tile per workgroup, column blocks over its waves (k_big_pre_mfma3_split: pre_split above)
     for (int t = 0; t < a->T; ++t) {
         if (pre_split && !(pre_post && t > 0)) hipLaunchKernelGGL((k_big_pre_mfma3_split<55, 21, 0, 100, 50, 25>), dim3((B + 15) / 16), dim3(256), 0, st, pd, r, t, c->d_theta.p, c->d_norm.p, bs);
         else if (pre_post && t > 0) hipLaunchKernelGGL(pre_post, dim3((B + 63) / 64), dim3(256), pre_lds_post, st, pd, r, t, c->d_theta.p, c->d_norm.p, bs);
@@ -1020,6 +1031,7 @@ static int rollout_gemm_chunk(metrpo_ctx* c, const metrpo_rollout_args* a, hipSt
         if (pd.ns <= 32) hipLaunchKernelGGL(k_big_post<32>, dim3((B + 7) / 8), dim3(256), 0, st, pd, r, t, c->d_norm.p, bs);
         else hipLaunchKernelGGL(k_big_post<64>, dim3((B + 3) / 4), dim3(256), 0, st, pd, r, t, c->d_norm.p, bs);
     }
+    if (note && !sk.mode && !bf) c->roll_last.out_splits = bs.out_splits;       // the tile GEMMs' output layer: fused-tile partials, deferred split-K partials, or 0
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
 }
@@ -1099,9 +1111,11 @@ int launch_rollout_gemm(metrpo_ctx* c, const metrpo_rollout_args* a, hipStream_t
         metrpo_rollout_args am = *a;
         am.B = R * B; am.T = H;
         am.d_init_obs = init_obs; am.d_init_ts = init_ts; am.d_init_model = init_model;
+        c->roll_last.rounds = 2;
         return rollout_gemm_chunk(c, &am, st, base, nullptr, B, R);
     }
     if (!par) return rollout_gemm_chunk(c, a, st, (char*)c->d_big.p, nullptr);
+    c->roll_last.rounds = 1;
     if (!c->side_ready) {
         for (int i = 0; i < METRPO_MAX_PAR_ROUNDS - 1; ++i) {
             HIP_TRY(c, hipStreamCreateWithFlags(&c->side_stream[i], hipStreamNonBlocking));
@@ -1135,7 +1149,7 @@ int launch_rollout_gemm(metrpo_ctx* c, const metrpo_rollout_args* a, hipStream_t
             if (hipSetDevice(c->device) != hipSuccess) return METRPO_EHIP;                 // a fresh host thread has no current device
             if (hipStreamWaitEvent(rs, c->ev_fork, 0) != hipSuccess) return METRPO_EHIP;
         }
-        const int rc = rollout_gemm_chunk(c, &ar, rs, base + (size_t)round * need1, nullptr);
+        const int rc = rollout_gemm_chunk(c, &ar, rs, base + (size_t)round * need1, nullptr, 0, 0, round == 0);
         if (rc != METRPO_OK) return rc;
         if (round > 0 && hipEventRecord(c->ev_join[round - 1], rs) != hipSuccess) return METRPO_EHIP;
         return METRPO_OK;

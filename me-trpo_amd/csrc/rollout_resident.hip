@@ -1103,6 +1103,7 @@ int launch_rollout_resident(metrpo_ctx* c, const metrpo_rollout_args* a, hipStre
         if (pick->fn_rot) HIP_TRY(c, hipFuncSetAttribute((const void*)pick->fn_rot, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pick->lds));
     }
     RolloutK rk = make_rollout_k(a);
+    { auto& n = c->roll_last; n.res_ws = pick->ws; n.res_threads = pick->threads; n.res_pw = PW; n.res_rg = Rg; n.rounds = R > 1 ? 1 : 0; }      // metrpo_debug_last_rollout_launch
     for (int round0 = 0; round0 < R; round0 += Rg) {
         const int rg = std::min(Rg, R - round0);
         ResidentK z;
@@ -1116,6 +1117,7 @@ int launch_rollout_resident(metrpo_ctx* c, const metrpo_rollout_args* a, hipStre
             const int cols = z.U / (K * NSL);
             z.rot = (may_rot && cols > 1 && z.NTC <= 4 && G % cols != 0 && G >= cols) ? 1 : 0;
         }
+        c->roll_last.res_rot = z.rot;
         z.seq0 = c->res_seq; c->res_seq += (unsigned int)steps + 1u;
         z.skip_block = -1;
         // few tiles per column (Ant's chunks, single rounds): the step is a latency chain and the post wave's polling rounds are on it; with many tiles per

@@ -748,6 +748,25 @@ class Engine(object):
         k = int(lib.metrpo_last_rollout_kernel(self._ctx))
         return {0: 'generic', 1: 'mfma-head-per-wave', 2: 'mfma-cooperative', 3: 'gemm-stepwise', 4: 'resident', 5: 'gemm-streamk', 6: 'streamk-persistent', 7: 'gemm-bf16'}.get(k)
 
+    ROLLOUT_LAUNCH_FIELDS = ('family', 'pre', 'post_width', 'sk_mode', 'late', 'l0', 'fuse_tile', 'out_splits', 'persist_wide', 'nclose', 'rounds',
+                             'res_ws', 'res_threads', 'res_pw', 'res_rg', 'res_rot')
+
+    def last_rollout_launch(self):
+        """Diagnostics: the sub-form of the last rollout() on a GEMM-class or resident family, as the host noted it while it enqueued it: dict(family (as
+        last_rollout_kernel), pre 'mfma' | 'mfma-merged' | 'mfma3' | 'mfma3-split' | 'gemm-chain' | 'valu' | 'mfma3-merged' (None: no pre-step launch),
+        post_width (k_big_post's lanes per env, 0 where a persistent or resident launch closes the steps), sk_mode 0 ... 3, late, l0 'producer' | 'rows' |
+        'gemm', fuse_tile 0 ... 2, out_splits (partials of the output layer added by the closing kernel), persist_wide, nclose, rounds 'single' |
+        'parallel' | 'merged', res_ws / res_threads / res_pw / res_rg / res_rot (resident: slice width, threads, post waves per workgroup, rounds per
+        launch group, rotating deal))."""
+        out = (C.c_int32 * 16)()
+        self._chk(lib.metrpo_debug_last_rollout_launch(self._ctx, out))
+        d = dict(zip(self.ROLLOUT_LAUNCH_FIELDS, (int(x) for x in out)))
+        d['family'] = self.last_rollout_kernel()
+        d['pre'] = {0: 'mfma', 1: 'mfma-merged', 2: 'mfma3', 3: 'mfma3-split', 4: 'gemm-chain', 5: 'valu', 6: 'mfma3-merged'}.get(d['pre'])
+        d['l0'] = {0: 'producer', 1: 'rows', 2: 'gemm'}.get(d['l0'])
+        d['rounds'] = {0: 'single', 1: 'parallel', 2: 'merged'}.get(d['rounds'])
+        return d
+
     def set_coop_split(self, split):
         """False keeps the 4-wave form of the cooperative rollout kernel where the head-split 8-wave form would run (same results bit for bit: A/B
         tests, fallback); True (default) restores the rule.  Read at the next rollout()."""

@@ -97,18 +97,18 @@ def f32(x):
 
 
 class Problem(object):
-    """helpers.problem_data(env, K, hidden, (32, 32)) with a pool of 257 distinct rows, everything rounded to fp32 (the device's storage type)."""
+    """helpers.problem_data(env, K, hidden, pol) with a pool of 257 distinct rows, everything rounded to fp32 (the device's storage type)."""
 
-    def __init__(self, env, K, hidden=(64, 64)):
-        self.env, self.K, self.hidden = env, K, tuple(hidden)
-        dm, theta, self.pdims, pool = Hh.problem_data(env, K, hidden, (32, 32), seed=PROBLEM_SEED, n_pool=N_POOL)
+    def __init__(self, env, K, hidden=(64, 64), pol=(32, 32), row=TOL.STEP):
+        self.env, self.K, self.hidden, self.pol = env, K, tuple(hidden), tuple(pol)
+        dm, theta, self.pdims, pool = Hh.problem_data(env, K, hidden, pol, seed=PROBLEM_SEED, n_pool=N_POOL)
         if env == 'ant':                                           # some envs start near the lower z bound: state-dependent dones inside the call
             pool[::3, 2] = 0.21; dm.diff_mean[2] = -0.02
         self.dm = dm.astype(np.float32).astype(np.float64)
         self.th, self.pool32 = f32(theta), f32(pool)
         assert len({r.tobytes() for r in self.pool32}) == N_POOL    # distinct rows: a pool row identifies its index
         self.tol = TOL.wide_or_step(hidden)
-        assert self.tol is TOL.STEP
+        assert self.tol is row, (hidden, row)                       # this table is row 1's: no wide net by accident (tests/wide_rollout_cases.py passes row 2)
         self._draws = {}
 
     # ---- draws of a case: (draws, radii or None, seed)

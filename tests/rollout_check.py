@@ -54,12 +54,14 @@ def _close(got, ref, tol, extra, what, form=None):
     assert np.isfinite(got).all() and used <= 1.0, (what, float(err.max()), used)
 
 
-def _check(p, dev, dr, rad, B, T, H, mode, determ, label, own=ALL_DRAWS, expect_resets=True, ant_free_run=False, form=None, act_tol=None, rew_tol=None):
+def _check(p, dev, dr, rad, B, T, H, mode, determ, label, own=ALL_DRAWS, expect_resets=True, ant_free_run=False, form=None, act_tol=None, rew_tol=None,
+           mean_tol=None):
     """`dr`: the draws the device must have used; `own`: those it drew itself (the restated ones; the others were supplied).
     expect_resets=False: the case is not required to hold a reset (B = 1, T < H): that is then a property of the case table, not of the device.
     ant_free_run=True: the case was drawn clear of Ant's done thresholds, so done / tpath must equal the FREE-RUNNING oracle's on every row for Ant too.
     form: record the worst share of every bound under this name in REPORT.  act_tol / rew_tol: the row for the action / the reward where it is not the
-    state's (TOL.ACTION / TOL.REWARD beside TOL.STEP)."""
+    state's (TOL.ACTION / TOL.REWARD beside TOL.STEP); mean_tol: the row of the policy mean where the policy's width class is not the dynamics net's (a 2 x 32
+    policy in front of a wide ensemble: TOL.STEP beside TOL.WIDE)."""
     env, K, ns, na, tol = p.env, p.K, p.dm.ns, p.dm.na, p.tol
     dn, tpath = dev['done'], dev['tpath']
     print('%s: B %d T %d H %d %s, %d resets' % (label, B, T, H, mode, int(dn.sum())))
@@ -115,7 +117,7 @@ def _check(p, dev, dr, rad, B, T, H, mode, determ, label, own=ALL_DRAWS, expect_
         for t in range(T):
             heads = O.dynamics_forward_all(p.dm, dev['obs'][t], np.clip(ref['act'][t], -1, 1))
             extra_next[t] += bound * np.std(heads, axis=0) * grow[t]
-    _close(dev['mean'], ref['mean'], tol, 0.0, 'mean', form)
+    _close(dev['mean'], ref['mean'], mean_tol or tol, 0.0, 'mean', form)
     _close(dev['act'], ref['act'], act_tol or tol, extra_act, 'act', form)
     _close(dev['rew'], ref['rew'], rew_tol or tol, extra_next.max(axis=2) + extra_tb, 'rew', form)
     _close(nxt_obs[~dn], ref['next'][~dn], tol, extra_next[~dn], 'next', form)

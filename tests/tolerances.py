@@ -22,6 +22,11 @@ ACTION = dict(rtol=1e-5, atol=2e-6)
 # --- one step, wide nets (hidden 128 ... 1024; the MFMA paths): row 2 ------------------------------------------------------------------------------------
 # sums 2x ... 16x longer, formed in the MFMA's own order (4 partial chains of k mod 16, chunks of 32): sqrt(n) growth -> 4x row 1's absolute bound,
 # 2x its relative one.  Observed 8.6e-7 absolute.  SURVEY 8d has no separate figure (its row 1 figure is for the 2x64 nets).
+# tests/test_gpu_wide_rollout_edges.py holds the wide-net rollout kernels in every sub-form the dispatch chooses between (52 forms: tile GEMMs, every
+# pre-step, stream-K modes 1 - 3 with and without the late split, persistent, the ten resident entries; 1126 cases) to this row at the edges of their own
+# tilings (the 2 x 32 policy's mean and the widths 72 / 96 to row 1, the action to ACTION).  Worst share observed there, per family -- tile GEMMs: mean
+# 0.33, act 0.16, rew 0.036, next state 0.014; stream-K: 0.41, 0.17, 0.010, 0.006; persistent: 0.41, 0.18, 0.011, 0.007; resident: 0.36, 0.20, 0.010,
+# 0.005 (profiles/r27_wide_rollout_edges.txt).
 WIDE = dict(rtol=2e-5, atol=5e-6)
 
 # --- free-running rollouts: rows 3, 4 --------------------------------------------------------------------------------------------------------------
