@@ -1127,20 +1127,30 @@ extern "C" int32_t metrpo_clear_terminal_value(metrpo_ctx* c) {
     return METRPO_OK;
 }
 extern "C" int32_t metrpo_has_terminal_value(const metrpo_ctx* c) { return c ? c->tv_n_bias : METRPO_ENULL; }
-// a scoring call's S against the n_bias that is set: one bias for every candidate, or one per start state
-#define TV_FITS(c, a, name) if ((c)->tv_n_bias > 1 && (c)->tv_n_bias != (a)->S)                                                                          \
-    return set_err((c), METRPO_EINVAL, std::string(name) + ": the terminal value has n_bias = " + std::to_string((c)->tv_n_bias) + ", neither 1 nor S = " + std::to_string((a)->S))
+// What the four scoring entry points check alike, in this order: dynamics (need_pol: and a policy, with no update left open), B / T, S, gamma, the terminal
+// value's n_bias against S (one bias for every candidate, or one per start state), chunk (0 where the call has none).  Each call's own pointers stay with it.
+static int score_check(metrpo_ctx* c, const char* name, int32_t B, int32_t T, int32_t S, double gamma, int32_t chunk, bool need_pol) {
+    const std::string n(name);
+    NEED_DYN(c);
+    if (need_pol) {
+        NEED_POL(c);
+        if (c->upd_pending) return set_err(c, METRPO_ESTATE, n + ": an update begun with metrpo_trpo_update_begin is still open (metrpo_trpo_update_end decides which theta stands)");
+    }
+    if (B < 0 || T < 0) return set_err(c, METRPO_EINVAL, n + ": bad B/T");
+    if (S < 1 || B % S != 0) return set_err(c, METRPO_EINVAL, n + ": S = " + std::to_string(S) + " must be at least 1 and divide B = " + std::to_string(B));
+    if (!std::isfinite(gamma)) return set_err(c, METRPO_EINVAL, n + ": gamma is not finite");
+    if (c->tv_n_bias > 1 && c->tv_n_bias != S)
+        return set_err(c, METRPO_EINVAL, n + ": the terminal value has n_bias = " + std::to_string(c->tv_n_bias) + ", neither 1 nor S = " + std::to_string(S));
+    if (chunk < 0) return set_err(c, METRPO_EINVAL, n + ": chunk must not be negative");
+    return METRPO_OK;
+}
 
 // ---- every head's discounted return of supplied action sequences (model_based_rl.py:122-141 under supplied actions; score_actions.hip) ----
 extern "C" int32_t metrpo_score_actions(metrpo_ctx* c, const metrpo_score_actions_args* a, void* stream) {
     TraceRange trace_("metrpo:score_actions (per-head returns of candidate action sequences)");
     if (!c) return METRPO_ENULL;
     if (!a) return set_err(c, METRPO_ENULL, "score_actions: args NULL");
-    NEED_DYN(c);
-    if (a->B < 0 || a->T < 0) return set_err(c, METRPO_EINVAL, "score_actions: bad B/T");
-    if (a->S < 1 || a->B % a->S != 0) return set_err(c, METRPO_EINVAL, "score_actions: S = " + std::to_string(a->S) + " must be at least 1 and divide B = " + std::to_string(a->B));
-    if (!std::isfinite(a->gamma)) return set_err(c, METRPO_EINVAL, "score_actions: gamma is not finite");
-    TV_FITS(c, a, "score_actions");
+    { const int rc = score_check(c, "score_actions", a->B, a->T, a->S, a->gamma, 0, false); if (rc) return rc; }
     if (a->B == 0 || a->T == 0) return METRPO_OK;
     if (!a->d_init_obs || !a->d_actions || !a->d_ret) return set_err(c, METRPO_ENULL, "score_actions: required pointer is NULL");
     return run_score_actions(c, a, (hipStream_t)stream);
@@ -1152,12 +1162,7 @@ extern "C" int32_t metrpo_score_actions_grad(metrpo_ctx* c, const metrpo_score_a
     TraceRange trace_("metrpo:score_actions_grad (per-head return gradients of candidate action sequences)");
     if (!c) return METRPO_ENULL;
     if (!a) return set_err(c, METRPO_ENULL, "score_actions_grad: args NULL");
-    NEED_DYN(c);
-    if (a->B < 0 || a->T < 0) return set_err(c, METRPO_EINVAL, "score_actions_grad: bad B/T");
-    if (a->S < 1 || a->B % a->S != 0) return set_err(c, METRPO_EINVAL, "score_actions_grad: S = " + std::to_string(a->S) + " must be at least 1 and divide B = " + std::to_string(a->B));
-    if (!std::isfinite(a->gamma)) return set_err(c, METRPO_EINVAL, "score_actions_grad: gamma is not finite");
-    TV_FITS(c, a, "score_actions_grad");
-    if (a->chunk < 0) return set_err(c, METRPO_EINVAL, "score_actions_grad: chunk must not be negative");
+    { const int rc = score_check(c, "score_actions_grad", a->B, a->T, a->S, a->gamma, a->chunk, false); if (rc) return rc; }
     if (a->B == 0 || a->T == 0) return METRPO_OK;
     if (!a->d_init_obs || !a->d_actions || !a->d_grad) return set_err(c, METRPO_ENULL, "score_actions_grad: required pointer is NULL");
     return run_score_actions_grad(c, a, (hipStream_t)stream);
@@ -1169,12 +1174,7 @@ extern "C" int32_t metrpo_score_policy_actions(metrpo_ctx* c, const metrpo_score
     TraceRange trace_("metrpo:score_policy_actions (per-head returns of noise sequences around the policy)");
     if (!c) return METRPO_ENULL;
     if (!a) return set_err(c, METRPO_ENULL, "score_policy_actions: args NULL");
-    NEED_DYN(c); NEED_POL(c);
-    if (c->upd_pending) return set_err(c, METRPO_ESTATE, "score_policy_actions: an update begun with metrpo_trpo_update_begin is still open (metrpo_trpo_update_end decides which theta stands)");
-    if (a->B < 0 || a->T < 0) return set_err(c, METRPO_EINVAL, "score_policy_actions: bad B/T");
-    if (a->S < 1 || a->B % a->S != 0) return set_err(c, METRPO_EINVAL, "score_policy_actions: S = " + std::to_string(a->S) + " must be at least 1 and divide B = " + std::to_string(a->B));
-    if (!std::isfinite(a->gamma)) return set_err(c, METRPO_EINVAL, "score_policy_actions: gamma is not finite");
-    TV_FITS(c, a, "score_policy_actions");
+    { const int rc = score_check(c, "score_policy_actions", a->B, a->T, a->S, a->gamma, 0, true); if (rc) return rc; }
     if (a->B == 0 || a->T == 0) return METRPO_OK;
     if (!a->d_init_obs || !a->d_ret) return set_err(c, METRPO_ENULL, "score_policy_actions: required pointer is NULL");
     return run_score_policy_actions(c, a, (hipStream_t)stream);
@@ -1186,13 +1186,7 @@ extern "C" int32_t metrpo_score_policy_actions_grad(metrpo_ctx* c, const metrpo_
     TraceRange trace_("metrpo:score_policy_actions_grad (per-head return gradients of noise sequences around the policy)");
     if (!c) return METRPO_ENULL;
     if (!a) return set_err(c, METRPO_ENULL, "score_policy_actions_grad: args NULL");
-    NEED_DYN(c); NEED_POL(c);
-    if (c->upd_pending) return set_err(c, METRPO_ESTATE, "score_policy_actions_grad: an update begun with metrpo_trpo_update_begin is still open (metrpo_trpo_update_end decides which theta stands)");
-    if (a->B < 0 || a->T < 0) return set_err(c, METRPO_EINVAL, "score_policy_actions_grad: bad B/T");
-    if (a->S < 1 || a->B % a->S != 0) return set_err(c, METRPO_EINVAL, "score_policy_actions_grad: S = " + std::to_string(a->S) + " must be at least 1 and divide B = " + std::to_string(a->B));
-    if (!std::isfinite(a->gamma)) return set_err(c, METRPO_EINVAL, "score_policy_actions_grad: gamma is not finite");
-    TV_FITS(c, a, "score_policy_actions_grad");
-    if (a->chunk < 0) return set_err(c, METRPO_EINVAL, "score_policy_actions_grad: chunk must not be negative");
+    { const int rc = score_check(c, "score_policy_actions_grad", a->B, a->T, a->S, a->gamma, a->chunk, true); if (rc) return rc; }
     if (a->B == 0 || a->T == 0) return METRPO_OK;
     if (!a->d_init_obs || !a->d_grad) return set_err(c, METRPO_ENULL, "score_policy_actions_grad: required pointer is NULL");
     return run_score_policy_actions_grad(c, a, (hipStream_t)stream);

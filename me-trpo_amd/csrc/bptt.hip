@@ -319,10 +319,8 @@ int launch_bptt_grad(metrpo_ctx* c, const float* init, int B, int T, double gamm
         if ((rc1 = launch_dg_backward(c, B, T, XS, WT, GM, st, nz))) return rc1;
     } else {
         const size_t fpt = bptt_floats(pd);
-        const size_t LDS_MAX = 160 * 1024;
-        int bs = 64;
-        while (bs > 1 && fpt * bs * sizeof(float) > LDS_MAX) bs >>= 1;
-        if (fpt * bs * sizeof(float) > LDS_MAX) return set_err(c, METRPO_EUNSUPPORTED, "bptt: layer widths exceed the LDS budget of the generic kernel");
+        const int bs = lds_block_size(fpt);
+        if (bs == 0) return set_err(c, METRPO_EUNSUPPORTED, "bptt: layer widths exceed the LDS budget of the generic kernel");
         const size_t sh = fpt * bs * sizeof(float);
         const void* fwd = nz ? (const void*)k_bptt_forward<true> : (const void*)k_bptt_forward<false>;
         const void* bwd = nz ? (const void*)k_bptt_backward<true> : (const void*)k_bptt_backward<false>;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <algorithm>
 #include <atomic>
 #include <utility>
 #include <vector>
@@ -478,6 +479,19 @@ int run_model_error(metrpo_ctx*, const metrpo_model_error_args*, hipStream_t);
 int run_rollout_actions(metrpo_ctx*, const metrpo_rollout_actions_args*, hipStream_t);
 // disagreement.hip: the body of metrpo_ensemble_disagreement (arguments checked by the entry point; 0 < N < 2^31)
 int run_disagreement(metrpo_ctx*, const metrpo_disagreement_args*, hipStream_t);
+// candidates per chunk of a scoring call whose workspace takes per_cand floats a candidate: the workspace stays within 2^26 floats (svg.hip's rule) unless
+// the caller's own chunk (override > 0) says otherwise; never more than B, never less than 1
+static inline size_t score_chunk(size_t B, size_t per_cand, size_t override_ = 0) {
+    return std::min(B, override_ > 0 ? override_ : std::max<size_t>(1, ((size_t)1 << 26) / per_cand));
+}
+// threads per block of a generic kernel that keeps floats_per_thread LDS columns: the largest of 64, 32, .. 1 (<= 64 lanes, so a block is one wave and needs
+// no barrier) whose columns fit 160 KB; 0: none does
+static inline int lds_block_size(size_t floats_per_thread) {
+    const size_t LDS_MAX = 160 * 1024;
+    int bs = 64;
+    while (bs > 1 && floats_per_thread * bs * sizeof(float) > LDS_MAX) bs >>= 1;
+    return floats_per_thread * bs * sizeof(float) > LDS_MAX ? 0 : bs;
+}
 // score_actions.hip: the body of metrpo_score_actions (arguments checked by the entry point; B, T > 0, B % S == 0)
 int run_score_actions(metrpo_ctx*, const metrpo_score_actions_args*, hipStream_t);
 // ... its generic path's start-row gather (act_c NULL: the start rows only), its reduction over a stored rew / done [T][Bc], and the head statistics of d_ret

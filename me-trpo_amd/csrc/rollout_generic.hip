@@ -287,10 +287,8 @@ __global__ void k_validation(ProblemDesc pd, const float* __restrict__ dynp, con
 static int pick_block(metrpo_ctx* c, size_t floats_per_thread, int B, int* block, size_t* shmem) {
     // largest power-of-two block (<= 64 lanes so a block is one wave: no barriers needed) whose LDS fits;
     // prefer >= 2 blocks per CU when it does not cost lanes.
-    const size_t LDS_MAX = 160 * 1024;
-    int bs = 64;
-    while (bs > 1 && floats_per_thread * bs * sizeof(float) > LDS_MAX) bs >>= 1;
-    if (floats_per_thread * bs * sizeof(float) > LDS_MAX)
+    const int bs = lds_block_size(floats_per_thread);
+    if (bs == 0)
         return set_err(c, METRPO_EUNSUPPORTED, "layer widths exceed the LDS budget of the generic kernel");
     *block = bs;
     *shmem = floats_per_thread * bs * sizeof(float);

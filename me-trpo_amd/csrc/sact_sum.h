@@ -1,7 +1,7 @@
 // The per-candidate return of metrpo_score_actions and metrpo_score_policy_actions (include/metrpo.h): what score_actions.hip's and
 // score_policy_actions.hip's fused kernels carry per lane and what k_sact_reduce applies to a stored trajectory.
-// Below it: what the two gradient files (score_actions_grad.hip, score_policy_actions_grad.hip) share -- the same sum handing out the step's weight, and the
-// generic kernels' cost adjoint.
+// Below it: what the generic kernels of the two gradient files (score_actions_grad.hip, score_policy_actions_grad.hip) share -- their LDS columns, a net's
+// hidden layers and its vector-Jacobian product, and the cost adjoint.
 #pragma once
 #include "device_common.h"
 
@@ -37,23 +37,11 @@ static inline TermVal ctx_term_val(const metrpo_ctx* c) {
 }
 
 // one step of the return: ret += gamma^t alive_t r_t in float64, then the discount, then the mask (model_based_rl.py:134-137: the step that ends an
-// episode still counts).  A step that is not counted adds nothing (no 0 * r).
-// terminal(v), behind the T-th step: ret += gamma^T alive_T v -- a candidate that met a done, at the last step included, gets no bootstrap; n stands.
+// episode still counts).  A step that is not counted adds nothing (no 0 * r).  step() hands out the step's weight for the gradient kernels: gamma^t carried
+// in float64 by repeated multiplication and rounded to fp32 where it becomes a weight; a step that is not counted has weight 0.  The scorers drop it.
+// terminal(v), behind the T-th step: ret += gamma^T alive_T v -- a candidate that met a done, at the last step included, gets no bootstrap; n stands.  It hands
+// out w_T = alive_T ? (float)gamma^T : 0, the weight of the reverse recursion's seed lambda_T = w_T dV/ds_T.
 struct SactSum {
-    double sum = 0.0, disc = 1.0;
-    int n = 0;
-    bool alive = true;
-    __device__ __forceinline__ void step(float rew, bool done, double gamma, int stop) {
-        if (alive) { sum += disc * (double)rew; ++n; }
-        disc *= gamma;
-        if (stop && done) alive = false;
-    }
-    __device__ __forceinline__ void terminal(float v) { if (alive) sum += disc * (double)v; }
-};
-
-// metrpo_score_actions' step of the return (score_actions.hip: SactSum) with the step's weight handed out: gamma^t carried in float64 by repeated
-// multiplication and rounded to fp32 where it becomes a weight; a step that is not counted has weight 0 and adds nothing
-struct SagrSum {
     double sum = 0.0, disc = 1.0;
     int n = 0;
     bool alive = true;
@@ -64,13 +52,60 @@ struct SagrSum {
         if (stop && done) alive = false;
         return w;
     }
-    // behind the T-th step: SactSum::terminal, handing out w_T = alive_T ? (float)gamma^T : 0, the weight of the reverse recursion's seed lambda_T = w_T dV/ds_T
     __device__ __forceinline__ float terminal(float v) {
         if (alive) sum += disc * (double)v;
         return alive ? (float)disc : 0.0f;
     }
 };
 
+// -------------------------------------------------------------------------------------------------
+// Generic gradient kernels: thread = (column of the chunk, head k = blockIdx.y), activations in LDS columns (device_common.h), LD = blockDim.x.
+// PH: the policy's hidden layers, only with `pol` (score_policy_actions_grad.hip)
+struct GradBufs { float *S, *XN, *LAM, *U, *UR, *X, *PH, *DH, *GA, *GB; };
+__host__ __device__ inline int net_hidden_rows(const NetDesc& n) {
+    int rows = 0;
+    for (int l = 1; l < n.n_layers; ++l) rows += n.dims[l];
+    return rows;
+}
+__host__ __device__ inline int grad_mw(const ProblemDesc& pd, bool pol) { return max(pol ? max(pd.dyn.max_width, pd.pol.max_width) : pd.dyn.max_width, pd.ns + pd.na); }
+__host__ __device__ inline size_t grad_gen_floats(const ProblemDesc& pd, bool pol) {
+    return (size_t)(3 * pd.ns + 2 * pd.na + (pd.ns + pd.na) + (pol ? net_hidden_rows(pd.pol) : 0) + net_hidden_rows(pd.dyn) + 2 * grad_mw(pd, pol));
+}
+__device__ __forceinline__ GradBufs grad_carve(float* lds, const ProblemDesc& pd, int LD, bool pol) {
+    GradBufs e;
+    e.S = lds; e.XN = e.S + pd.ns * LD; e.LAM = e.XN + pd.ns * LD; e.U = e.LAM + pd.ns * LD; e.UR = e.U + pd.na * LD; e.X = e.UR + pd.na * LD;
+    e.PH = e.X + (pd.ns + pd.na) * LD; e.DH = e.PH + (pol ? net_hidden_rows(pd.pol) : 0) * LD; e.GA = e.DH + net_hidden_rows(pd.dyn) * LD; e.GB = e.GA + grad_mw(pd, pol) * LD;
+    return e;
+}
+// the hidden layers of a net into `store` (all outputs kept; the output layer is not formed)
+__device__ __forceinline__ void net_hidden(const NetDesc& n, const float* __restrict__ params, const float* in, float* store, int LD, int tid) {
+    const float* cur = in; float* dst = store;
+    for (int l = 0; l < n.n_layers - 1; ++l) {
+        dense_col(params + n.w_off[l], params + n.b_off[l], n.dims[l], n.dims[l + 1], n.act[l], cur, dst, LD, tid);
+        cur = dst; dst += n.dims[l + 1] * LD;
+    }
+}
+// dout = W . (din * act'(h)) chains of one net, back from `da` (the adjoint of the net's output, n_out rows) to the adjoint of its input; `store` holds the
+// hidden layers' outputs in layer order (k_bptt_backward's loops, bptt.hip).  Returns the buffer (da or db) that holds the result.
+__device__ __forceinline__ float* net_vjp(const NetDesc& n, const float* __restrict__ params, const float* store, float* da, float* db, int LD, int tid) {
+    int off = 0;
+    for (int l = 1; l < n.n_layers - 1; ++l) off += n.dims[l];                // rows of the LAST hidden layer in the store
+    for (int l = n.n_layers - 1; l >= 0; --l) {
+        dense_col_T(params + n.w_off[l], n.dims[l], n.dims[l + 1], da, db, LD, tid);
+        if (l > 0) {
+            const float* h = store + off * LD;                                 // output of layer l-1 (post-activation)
+            for (int j = 0; j < n.dims[l]; ++j) {
+                const float hv = h[j * LD + tid];
+                const float dact = (n.act[l - 1] == METRPO_ACT_RELU) ? (hv > 0.0f ? 1.0f : 0.0f)
+                                  : (n.act[l - 1] == METRPO_ACT_TANH) ? (1.0f - hv * hv) : 1.0f;
+                db[j * LD + tid] *= dact;
+            }
+            if (l > 1) off -= n.dims[l - 1];
+        }
+        float* tmp = da; da = db; db = tmp;
+    }
+    return da;
+}
 // d(w cost)/du -> gU (written), d(w cost)/dx_next -> added into G: bptt.hip's cost_adjoint (:54-78), called with w = -w_t for the gradient of the return
 __device__ __forceinline__ void sagr_cost_adjoint(int env, int ns, int na, const float* xn, const float* u, float w, float* gU, float* G, int LD, int tid) {
     float su2 = 0.0f;

@@ -19,7 +19,7 @@
 //   * edge tile (B % 16 != 0): rows >= B are zero state and zero action in LDS, never read from or written to memory.
 //
 // Generic path (every other shape, and force_generic): per head k the step loop of run_rollout_actions (eps_rand, uniform_model = k) into a ctx
-// workspace, chunked over candidates so that the workspace stays within 2^26 floats (svg.hip's rule), then k_sact_reduce, one thread per candidate,
+// workspace, chunked over candidates so that the workspace stays within 2^26 floats (score_chunk, metrpo_internal.h), then k_sact_reduce, one thread per candidate,
 // applies the same float64 sum to the workspace's rew / done.
 //
 // Terminal value (metrpo_set_terminal_value; sact_sum.h: TermVal): while one is set, ret gains gamma^T alive_T V(s_T) in front of the single rounding.  Fused: tile_rollout
@@ -155,7 +155,7 @@ static int launch_sact_generic(metrpo_ctx* c, const metrpo_score_actions_args* a
     const int K = c->pd.K, per = a->B / a->S;
     // ---- a chunk's workspace (floats): obs [T + 1][Bc][ns] | rew [T][Bc] | done [T][Bc] bytes | (Bc < B) actions [T][Bc][na]; within 2^26 floats ----
     const size_t per_cand = (T + 1) * ns + T + (T + 3) / 4 + T * na;
-    const size_t Bc = std::min<size_t>(B, std::max<size_t>(1, ((size_t)1 << 26) / per_cand));
+    const size_t Bc = score_chunk(B, per_cand);
     const size_t o_obs = 0, o_rew = o_obs + (T + 1) * Bc * ns, o_done = o_rew + T * Bc, o_act = o_done + (T * Bc + 3) / 4;
     const size_t total = o_act + (Bc < B ? T * Bc * na : 0);
     { const int rc = ws_grow(c, c->d_sact, sizeof(float) * total); if (rc) return rc; }

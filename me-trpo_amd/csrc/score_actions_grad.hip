@@ -22,7 +22,8 @@
 //   gathered per row (a tile may straddle two start states).
 //
 // Generic path (every other shape, and force_generic): k_sagr_gen_fwd / k_sagr_gen_bwd, one thread per (candidate, head) with activations in LDS
-// columns -- k_bptt_forward / k_bptt_backward (bptt.hip) with the policy removed; block size by bptt.hip's LDS rule.  Same outputs, workspace, chunking.
+// columns (sact_sum.h: GradBufs, net_hidden, net_vjp, sagr_cost_adjoint) -- k_bptt_forward / k_bptt_backward (bptt.hip) with the policy removed; block size by
+// lds_block_size (metrpo_internal.h).  Same outputs, workspace, chunking.
 //
 // Terminal value (metrpo_set_terminal_value; sact_sum.h: TermVal): the forward sweeps add gamma^T alive_T V(s_T) to the sum behind the loop (score_actions.hip's
 // statement, so ret keeps that call's bits) and STORE w_T = alive_T ? (float)gamma^T : 0 into WE [K][Bc], one more slice of WT that exists only while a value is
@@ -30,7 +31,7 @@
 // lambda_T = w_T dV/ds_T, formed from the stored XS[T] tile in lambda's own layout (fused: the x_T buffer in LDS, behind its commit) instead of 0.  The forward
 // sweeps take the value as a template parameter (k_sagr<.., SAGR_FWD, TV>, k_sagr_gen_fwd<TV>), the reverse sweeps by the runtime-uniform pointer test.
 //
-// Workspace: ctx->d_sagr = XS | WT (| WE) of one chunk, within 2^26 floats (svg.hip's rule; args.chunk > 0 overrides).  d_grad_mean: k_sagr_mean, a small
+// Workspace: ctx->d_sagr = XS | WT (| WE) of one chunk, within 2^26 floats (score_chunk, metrpo_internal.h; args.chunk > 0 overrides).  d_grad_mean: k_sagr_mean, a small
 // launch over d_grad adding in head order (k_sact_aggregate's style).  No atomics anywhere: repeated calls are bit-identical.
 #include "dyn_tile_step.h"
 #include "dyn_head_adjoint.h"
@@ -58,7 +59,7 @@ template <int NS, bool TV>
 struct SagrSink {
     const SagrK& r;
     int k;
-    SagrSum acc;
+    SactSum acc;
     __device__ __forceinline__ int lim(int b0) const { return min(16, r.c0 + r.n - b0) * NS; }      // floats of the tile's rows inside the chunk
     __device__ __forceinline__ void rows(int t, const float* ST, int b0, int lane) const {
         float* dst = r.XS + (((size_t)k * (r.T + 1) + t) * r.n + (b0 - r.c0)) * NS;
@@ -269,25 +270,7 @@ k_sagr(SagrK r, const float* __restrict__ dynp, const float* __restrict__ norm) 
 }
 
 // -------------------------------------------------------------------------------------------------
-// Generic path: thread = (column of the chunk, head k = blockIdx.y), activations in LDS columns (device_common.h), LD = blockDim.x.
-struct SagrBufs { float *S, *XN, *LAM, *U, *UR, *X, *DH, *GA, *GB; };
-__host__ __device__ inline int sagr_hidden_rows(const NetDesc& n) {
-    int rows = 0;
-    for (int l = 1; l < n.n_layers; ++l) rows += n.dims[l];
-    return rows;
-}
-__host__ __device__ inline size_t sagr_gen_floats(const ProblemDesc& pd) {
-    const int mw = max(pd.dyn.max_width, pd.ns + pd.na);
-    return (size_t)(3 * pd.ns + 2 * pd.na + (pd.ns + pd.na) + sagr_hidden_rows(pd.dyn) + 2 * mw);
-}
-__device__ __forceinline__ SagrBufs sagr_carve(float* lds, const ProblemDesc& pd, int LD) {
-    const int mw = max(pd.dyn.max_width, pd.ns + pd.na);
-    SagrBufs e;
-    e.S = lds; e.XN = e.S + pd.ns * LD; e.LAM = e.XN + pd.ns * LD; e.U = e.LAM + pd.ns * LD; e.UR = e.U + pd.na * LD; e.X = e.UR + pd.na * LD;
-    e.DH = e.X + (pd.ns + pd.na) * LD; e.GA = e.DH + sagr_hidden_rows(pd.dyn) * LD; e.GB = e.GA + mw * LD;
-    return e;
-}
-
+// Generic path (sact_sum.h: GradBufs without the policy's rows).
 // TV: with a terminal value -- a template parameter, so that the instantiation without one is the kernel it was (the runtime test costs it a stack slot)
 template <bool TV>
 __global__ void k_sagr_gen_fwd(ProblemDesc pd, SagrK r, const float* __restrict__ dynp, const float* __restrict__ norm) {
@@ -296,7 +279,7 @@ __global__ void k_sagr_gen_fwd(ProblemDesc pd, SagrK r, const float* __restrict_
     const int lc = blockIdx.x * blockDim.x + tid, k = blockIdx.y, b = r.c0 + lc;
     const bool active = lc < r.n;
     const int ns = pd.ns, na = pd.na;
-    SagrBufs e = sagr_carve(lds, pd, LD);
+    GradBufs e = grad_carve(lds, pd, LD, false);
     const float* in_mean = norm; const float* in_std = norm + (ns + na);
     const float* diff_mean = norm + 2 * (ns + na); const float* diff_std = diff_mean + ns;
     const float* __restrict__ pk = dynp + (size_t)k * pd.dyn.n_params;
@@ -306,7 +289,7 @@ __global__ void k_sagr_gen_fwd(ProblemDesc pd, SagrK r, const float* __restrict_
         e.S[i * LD + tid] = v;
         if (active) xs[(size_t)lc * ns + i] = v;
     }
-    SagrSum acc;
+    SactSum acc;
     for (int t = 0; t < r.T; ++t) {
         for (int d = 0; d < na; ++d) e.U[d * LD + tid] = active ? fminf(fmaxf(r.actions[((size_t)t * r.B + b) * na + d], -1.0f), 1.0f) : 0.0f;
         for (int i = 0; i < ns; ++i) e.X[i * LD + tid] = (e.S[i * LD + tid] - in_mean[i]) / in_std[i];
@@ -336,7 +319,7 @@ __global__ void k_sagr_gen_bwd(ProblemDesc pd, SagrK r, const float* __restrict_
     const bool active = lc < r.n;
     const int ns = pd.ns, na = pd.na;
     const NetDesc& dn = pd.dyn;
-    SagrBufs e = sagr_carve(lds, pd, LD);
+    GradBufs e = grad_carve(lds, pd, LD, false);
     const float* in_mean = norm; const float* in_std = norm + (ns + na);
     const float* diff_std = norm + 2 * (ns + na) + ns;
     const float* __restrict__ pk = dynp + (size_t)k * dn.n_params;
@@ -360,37 +343,13 @@ __global__ void k_sagr_gen_bwd(ProblemDesc pd, SagrK r, const float* __restrict_
         }
         for (int i = 0; i < ns; ++i) e.X[i * LD + tid] = (e.S[i * LD + tid] - in_mean[i]) / in_std[i];
         for (int d = 0; d < na; ++d) e.X[(ns + d) * LD + tid] = (e.U[d * LD + tid] - in_mean[ns + d]) / in_std[ns + d];
-        {
-            const float* cur = e.X + pd.n_drop * LD; float* dst = e.DH;
-            for (int l = 0; l < dn.n_layers - 1; ++l) {
-                dense_col(pk + dn.w_off[l], pk + dn.b_off[l], dn.dims[l], dn.dims[l + 1], dn.act[l], cur, dst, LD, tid);
-                cur = dst; dst += dn.dims[l + 1] * LD;
-            }
-        }
+        net_hidden(dn, pk, e.X + pd.n_drop * LD, e.DH, LD, tid);
         // ---- adjoints of the return: G = lambda_t+1 - w dc/dx_next; gU_cost = -w dc/du (in X's place: the normalised input is dead) ----
         float* G = e.LAM;
         float* gUc = e.X;
         sagr_cost_adjoint(pd.env, ns, na, e.XN, e.U, -w, gUc, G, LD, tid);
-        float* da = e.GA; float* db = e.GB;
-        for (int i = 0; i < ns; ++i) da[i * LD + tid] = diff_std[i] * G[i * LD + tid];
-        {
-            int off = 0;
-            for (int l = 1; l < dn.n_layers - 1; ++l) off += dn.dims[l];          // rows of the LAST hidden layer in DH
-            for (int l = dn.n_layers - 1; l >= 0; --l) {
-                dense_col_T(pk + dn.w_off[l], dn.dims[l], dn.dims[l + 1], da, db, LD, tid);
-                if (l > 0) {
-                    const float* h = e.DH + off * LD;                              // output of layer l-1 (post-activation)
-                    for (int j = 0; j < dn.dims[l]; ++j) {
-                        const float hv = h[j * LD + tid];
-                        const float dact = (dn.act[l - 1] == METRPO_ACT_RELU) ? (hv > 0.0f ? 1.0f : 0.0f)
-                                          : (dn.act[l - 1] == METRPO_ACT_TANH) ? (1.0f - hv * hv) : 1.0f;
-                        db[j * LD + tid] *= dact;
-                    }
-                    if (l > 1) off -= dn.dims[l - 1];
-                }
-                float* tmp = da; da = db; db = tmp;
-            }
-        }
+        for (int i = 0; i < ns; ++i) e.GA[i * LD + tid] = diff_std[i] * G[i * LD + tid];
+        const float* da = net_vjp(dn, pk, e.DH, e.GA, e.GB, LD, tid);
         // da = adjoint of the (dropped) normalised input [nin].  Action part -> the gated gradient; state part: residual + normaliser -> lambda_t
         for (int d = 0; d < na; ++d) {
             const float gu = gUc[d * LD + tid] + da[(ns - pd.n_drop + d) * LD + tid] / in_std[ns + d];
@@ -436,7 +395,7 @@ int run_score_actions_grad(metrpo_ctx* c, const metrpo_score_actions_grad_args* 
     // ---- a chunk's workspace (floats): XS [K][T + 1][Bc][ns] | WT [K][T][Bc] | (a terminal value is set) WE [K][Bc]; within 2^26 floats unless args.chunk says otherwise ----
     const TermVal tv = ctx_term_val(c);
     const size_t per_cand = K * ((T + 1) * ns + T + (tv.w1 ? 1 : 0));
-    const size_t Bc = a->chunk > 0 ? std::min<size_t>(B, (size_t)a->chunk) : std::min<size_t>(B, std::max<size_t>(1, ((size_t)1 << 26) / per_cand));
+    const size_t Bc = score_chunk(B, per_cand, (size_t)a->chunk);
     const size_t o_wt = (K * (T + 1) * Bc * ns + 3) & ~(size_t)3;
     const size_t o_we = o_wt + K * T * Bc;
     { const int rc = ws_grow(c, c->d_sagr, sizeof(float) * (o_we + (tv.w1 ? K * Bc : 0))); if (rc) return rc; }
@@ -454,9 +413,8 @@ int run_score_actions_grad(metrpo_ctx* c, const metrpo_score_actions_grad_args* 
         sh_f = sizeof(float) * (size_t)en->fwd_floats; sh_b = sizeof(float) * (size_t)en->bwd_floats;
         { const int rc = allow_dynamic_lds(c, (const void*)en->bwd, sh_b); if (rc) return rc; }
     } else {
-        const size_t fpt = sagr_gen_floats(pd), LDS_MAX = 160 * 1024;             // bptt.hip's rule
-        while (bs > 1 && fpt * bs * sizeof(float) > LDS_MAX) bs >>= 1;
-        if (fpt * bs * sizeof(float) > LDS_MAX) return set_err(c, METRPO_EUNSUPPORTED, "score_actions_grad: layer widths exceed the LDS budget of the generic kernel");
+        const size_t fpt = grad_gen_floats(pd, false);
+        if ((bs = lds_block_size(fpt)) == 0) return set_err(c, METRPO_EUNSUPPORTED, "score_actions_grad: layer widths exceed the LDS budget of the generic kernel");
         sh_f = sh_b = fpt * bs * sizeof(float);
         gen_fwd = tv.w1 ? k_sagr_gen_fwd<true> : k_sagr_gen_fwd<false>;
         int rc = allow_dynamic_lds(c, (const void*)gen_fwd, sh_f);

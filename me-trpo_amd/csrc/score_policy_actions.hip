@@ -164,7 +164,7 @@ static int launch_spol_generic(metrpo_ctx* c, const metrpo_score_policy_actions_
     // A chunk of n < Bc candidates (the last one) uses the front of every area with n as its row stride: rew / done are [T][n], as k_sact_reduce reads them.
     // `mean` is never read: launch_policy_actions writes both of its outputs.  spol_chunk_cap (metrpo_debug_score_policy_chunk) lowers Bc for tests. ----
     const size_t per_cand = 3 * ns + 2 * na + T + (T + 3) / 4 + K;
-    size_t Bc = std::min<size_t>(B, std::max<size_t>(1, ((size_t)1 << 26) / per_cand));
+    size_t Bc = score_chunk(B, per_cand);
     if (c->spol_chunk_cap > 0) Bc = std::min<size_t>(Bc, (size_t)c->spol_chunk_cap);
     const size_t o_s0 = 0, o_st = o_s0 + Bc * ns, o_act = o_st + 2 * Bc * ns, o_mean = o_act + Bc * na, o_rew = o_mean + Bc * na, o_done = o_rew + T * Bc,
                  o_head = o_done + (T * Bc + 3) / 4, total = o_head + (size_t)K * Bc;

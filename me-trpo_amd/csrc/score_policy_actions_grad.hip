@@ -13,8 +13,8 @@
 //   k_spag_bwd  k_sagr<ENV, SAGR_BWD>'s structure: a workgroup is 4 waves = four 16-candidate tiles of the SAME head (blockIdx.y), launch bound (256, 2);
 //               one LDS image of the head's adjoint tables (dyn_head_adjoint.h) AND the policy's forward and adjoint tables (pol_head_mfma.h:
 //               PolHeadAdjoint), 41 KB swimmer .. 55 KB Ant, with the waves' buffers 47 .. 73 KB a workgroup (SpagL: two fit a CU's 160 KB);
-//               layers 0 and 1 of the head recomputed from XS[t] and AW[t]; the cost adjoint in D layout (k_sagr's statements, kept apart from
-//               that kernel's copy so that its code object stays as it is); DynHeadAdjoint::run; the clip gate on AW[t]; the store of grad[k][t]; then the policy's two hidden layers recomputed from XS[t] and its
+//               layers 0 and 1 of the head recomputed from XS[t] and AW[t]; the cost adjoint in D layout (k_sagr's statements; a shared
+//               function costs instantiations of both kernels registers: profiles/r28_score_bodies.txt); DynHeadAdjoint::run; the clip gate on AW[t]; the store of grad[k][t]; then the policy's two hidden layers recomputed from XS[t] and its
 //               three-chain input adjoint accumulated INTO gS.  The prefetch is k_sagr's: one state block, one action block (now per head, from AW: the
 //               tile's rows of a step are one linear run there too) and one weight per step, issued at the top of step t, committed behind it; two state
 //               buffers alternate.
@@ -22,9 +22,9 @@
 //   forward sweep computes rows of a later chunk that share its last tile and drops them, so chunking changes no bit.
 //
 // Generic path (every other shape, and force_generic): k_spag_gen_fwd / k_spag_gen_bwd, one thread per (candidate, head) with activations in LDS
-// columns -- k_sagr_gen_fwd / k_sagr_gen_bwd with the policy in the loop: the forward is k_policy_actions' and k_step's arithmetic (rollout_generic.hip;
+// columns -- k_sagr_gen_fwd / k_sagr_gen_bwd with the policy in the loop (both on sact_sum.h's GradBufs, net_hidden, net_vjp and sagr_cost_adjoint): the forward is k_policy_actions' and k_step's arithmetic (rollout_generic.hip;
 // sigma by __expf as there), so ret, len and act_out carry the bits of metrpo_score_policy_actions' generic path; the reverse is k_bptt_backward's policy
-// VJP (bptt.hip) behind the clip gate.  Block size by bptt.hip's LDS rule.  Same outputs, workspace, chunking.
+// VJP (bptt.hip) behind the clip gate.  Block size by lds_block_size (metrpo_internal.h).  Same outputs, workspace, chunking.
 //
 // Terminal value (sact_sum.h: TermVal), as in score_actions_grad.hip: the forward sweeps add the term behind the loop and STORE w_T into WE [K][Bc] (one more slice
 // of WT, only while a value is set; stored, not re-derived); the reverse sweeps start from lambda_T = w_T dV/ds_T formed from the stored XS[T] tile.  The seed
@@ -93,7 +93,7 @@ __global__ void __launch_bounds__(64) k_spag_fwd(SpagK r, const float* __restric
     for (int i = lane; i < lim; i += 64) xs_k[i] = ST[i];
     loop_invariant_loads_done();
 
-    SagrSum acc;
+    SactSum acc;
     for (int t = 0; t < r.T; ++t) {
         float* ACT = NOISE ? nz.cur(t) : W + C::W_ACT;       // the step's noise rows, overwritten by the clipped action
         if (NOISE) nz.prefetch(t + 1);                         // committed behind the matrix instructions
@@ -333,24 +333,7 @@ __global__ void __launch_bounds__(256, 2) k_spag_bwd(SpagK r, const float* __res
 }
 
 // -------------------------------------------------------------------------------------------------
-// Generic path: thread = (column of the chunk, head k = blockIdx.y), activations in LDS columns (device_common.h), LD = blockDim.x.
-struct SpagBufs { float *S, *XN, *LAM, *U, *UR, *X, *PH, *DH, *GA, *GB; };
-__host__ __device__ inline int spag_hidden_rows(const NetDesc& n) {
-    int rows = 0;
-    for (int l = 1; l < n.n_layers; ++l) rows += n.dims[l];
-    return rows;
-}
-__host__ __device__ inline int spag_mw(const ProblemDesc& pd) { return max(max(pd.dyn.max_width, pd.pol.max_width), pd.ns + pd.na); }
-__host__ __device__ inline size_t spag_gen_floats(const ProblemDesc& pd) {
-    return (size_t)(3 * pd.ns + 2 * pd.na + (pd.ns + pd.na) + spag_hidden_rows(pd.pol) + spag_hidden_rows(pd.dyn) + 2 * spag_mw(pd));
-}
-__device__ __forceinline__ SpagBufs spag_carve(float* lds, const ProblemDesc& pd, int LD) {
-    SpagBufs e;
-    e.S = lds; e.XN = e.S + pd.ns * LD; e.LAM = e.XN + pd.ns * LD; e.U = e.LAM + pd.ns * LD; e.UR = e.U + pd.na * LD; e.X = e.UR + pd.na * LD;
-    e.PH = e.X + (pd.ns + pd.na) * LD; e.DH = e.PH + spag_hidden_rows(pd.pol) * LD; e.GA = e.DH + spag_hidden_rows(pd.dyn) * LD; e.GB = e.GA + spag_mw(pd) * LD;
-    return e;
-}
-
+// Generic path (sact_sum.h: GradBufs with the policy's rows).
 // TV: with a terminal value -- a template parameter, so that the instantiation without one is the kernel it was (the runtime test costs it a stack slot)
 template <bool TV>
 __global__ void k_spag_gen_fwd(ProblemDesc pd, SpagK r, const float* __restrict__ dynp, const float* __restrict__ theta, const float* __restrict__ norm) {
@@ -359,7 +342,7 @@ __global__ void k_spag_gen_fwd(ProblemDesc pd, SpagK r, const float* __restrict_
     const int lc = blockIdx.x * blockDim.x + tid, k = blockIdx.y, b = r.c0 + lc;
     const bool active = lc < r.n;
     const int ns = pd.ns, na = pd.na;
-    SpagBufs e = spag_carve(lds, pd, LD);
+    GradBufs e = grad_carve(lds, pd, LD, true);
     const float* in_mean = norm; const float* in_std = norm + (ns + na);
     const float* diff_mean = norm + 2 * (ns + na); const float* diff_std = diff_mean + ns;
     const float* __restrict__ pk = dynp + (size_t)k * pd.dyn.n_params;
@@ -370,7 +353,7 @@ __global__ void k_spag_gen_fwd(ProblemDesc pd, SpagK r, const float* __restrict_
         e.S[i * LD + tid] = v;
         if (active) xs[(size_t)lc * ns + i] = v;
     }
-    SagrSum acc;
+    SactSum acc;
     for (int t = 0; t < r.T; ++t) {
         const float* m = mlp_col(pd.pol, theta, e.S, e.GA, e.GB, LD, tid);
         for (int d = 0; d < na; ++d) {                       // k_policy_actions' action (noise in std units: its eps) or k_spol_act's mean + noise
@@ -406,36 +389,6 @@ __global__ void k_spag_gen_fwd(ProblemDesc pd, SpagK r, const float* __restrict_
     }
 }
 
-// dout = W . (din * act'(h)) chains of one net, back from `da` (the adjoint of the net's output, n_out rows) to the adjoint of its input; `store` holds the
-// hidden layers' outputs in layer order (k_bptt_backward's loops, bptt.hip).  Returns the buffer (da or db) that holds the result.
-__device__ __forceinline__ float* spag_net_vjp(const NetDesc& n, const float* __restrict__ params, const float* store, float* da, float* db, int LD, int tid) {
-    int off = 0;
-    for (int l = 1; l < n.n_layers - 1; ++l) off += n.dims[l];                // rows of the LAST hidden layer in the store
-    for (int l = n.n_layers - 1; l >= 0; --l) {
-        dense_col_T(params + n.w_off[l], n.dims[l], n.dims[l + 1], da, db, LD, tid);
-        if (l > 0) {
-            const float* h = store + off * LD;                                 // output of layer l-1 (post-activation)
-            for (int j = 0; j < n.dims[l]; ++j) {
-                const float hv = h[j * LD + tid];
-                const float dact = (n.act[l - 1] == METRPO_ACT_RELU) ? (hv > 0.0f ? 1.0f : 0.0f)
-                                  : (n.act[l - 1] == METRPO_ACT_TANH) ? (1.0f - hv * hv) : 1.0f;
-                db[j * LD + tid] *= dact;
-            }
-            if (l > 1) off -= n.dims[l - 1];
-        }
-        float* tmp = da; da = db; db = tmp;
-    }
-    return da;
-}
-// the hidden layers of a net into `store` (all outputs kept; the output layer is not formed)
-__device__ __forceinline__ void spag_net_hidden(const NetDesc& n, const float* __restrict__ params, const float* in, float* store, int LD, int tid) {
-    const float* cur = in; float* dst = store;
-    for (int l = 0; l < n.n_layers - 1; ++l) {
-        dense_col(params + n.w_off[l], params + n.b_off[l], n.dims[l], n.dims[l + 1], n.act[l], cur, dst, LD, tid);
-        cur = dst; dst += n.dims[l + 1] * LD;
-    }
-}
-
 __global__ void k_spag_gen_bwd(ProblemDesc pd, SpagK r, const float* __restrict__ dynp, const float* __restrict__ theta, const float* __restrict__ norm) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int LD = blockDim.x, tid = threadIdx.x;
@@ -443,7 +396,7 @@ __global__ void k_spag_gen_bwd(ProblemDesc pd, SpagK r, const float* __restrict_
     const bool active = lc < r.n;
     const int ns = pd.ns, na = pd.na;
     const NetDesc& dn = pd.dyn; const NetDesc& pn = pd.pol;
-    SpagBufs e = spag_carve(lds, pd, LD);
+    GradBufs e = grad_carve(lds, pd, LD, true);
     const float* in_mean = norm; const float* in_std = norm + (ns + na);
     const float* diff_std = norm + 2 * (ns + na) + ns;
     const float* __restrict__ pk = dynp + (size_t)k * dn.n_params;
@@ -461,7 +414,7 @@ __global__ void k_spag_gen_bwd(ProblemDesc pd, SpagK r, const float* __restrict_
         }
         const float w = active ? r.WT[((size_t)k * r.T + t) * r.n + lc] : 0.0f;
         // ---- recompute the step: the policy's hidden layers, the stored action and its clip, normalise, the head's hidden layers (all outputs kept) ----
-        spag_net_hidden(pn, theta, e.S, e.PH, LD, tid);
+        net_hidden(pn, theta, e.S, e.PH, LD, tid);
         for (int d = 0; d < na; ++d) {
             const float a = active ? r.AW[(((size_t)k * r.T + t) * r.n + lc) * na + d] : 0.0f;
             e.UR[d * LD + tid] = a;
@@ -469,13 +422,13 @@ __global__ void k_spag_gen_bwd(ProblemDesc pd, SpagK r, const float* __restrict_
         }
         for (int i = 0; i < ns; ++i) e.X[i * LD + tid] = (e.S[i * LD + tid] - in_mean[i]) / in_std[i];
         for (int d = 0; d < na; ++d) e.X[(ns + d) * LD + tid] = (e.U[d * LD + tid] - in_mean[ns + d]) / in_std[ns + d];
-        spag_net_hidden(dn, pk, e.X + pd.n_drop * LD, e.DH, LD, tid);
+        net_hidden(dn, pk, e.X + pd.n_drop * LD, e.DH, LD, tid);
         // ---- adjoints of the return: G = lambda_t+1 - w dc/dx_next; gU_cost = -w dc/du (in X's place: the normalised input is dead) ----
         float* G = e.LAM;
         float* gUc = e.X;
         sagr_cost_adjoint(pd.env, ns, na, e.XN, e.U, -w, gUc, G, LD, tid);
         for (int i = 0; i < ns; ++i) e.GA[i * LD + tid] = diff_std[i] * G[i * LD + tid];
-        float* da = spag_net_vjp(dn, pk, e.DH, e.GA, e.GB, LD, tid);
+        float* da = net_vjp(dn, pk, e.DH, e.GA, e.GB, LD, tid);
         float* db = (da == e.GA) ? e.GB : e.GA;
         // da = adjoint of the (dropped) normalised input [nin].  State part: residual + normaliser -> gS (x_next is dead now); action part -> gm behind the gate
         for (int i = 0; i < ns; ++i) {
@@ -491,7 +444,7 @@ __global__ void k_spag_gen_bwd(ProblemDesc pd, SpagK r, const float* __restrict_
             if (active) r.grad[(((size_t)k * r.T + t) * r.B + b) * na + d] = r.in_std ? gm * __expf(fmaxf(log_std[d], LOG_MIN_STD)) : gm;
         }
         // ---- the policy path: J_pi(s_t)^T gm with the stored activations ----
-        const float* pa = spag_net_vjp(pn, theta, e.PH, db, da, LD, tid);
+        const float* pa = net_vjp(pn, theta, e.PH, db, da, LD, tid);
         for (int i = 0; i < ns; ++i) e.LAM[i * LD + tid] = e.XN[i * LD + tid] + pa[i * LD + tid];       // lambda_t
     }
     if (r.lam0 != nullptr && active)
@@ -512,7 +465,7 @@ int run_score_policy_actions_grad(metrpo_ctx* c, const metrpo_score_policy_actio
     // ---- a chunk's workspace (floats): XS [K][T + 1][Bc][ns] | WT [K][T][Bc] | AW [K][T][Bc][na] | (a terminal value is set) WE [K][Bc]; within 2^26 floats unless args.chunk says otherwise ----
     const TermVal tv = ctx_term_val(c);
     const size_t per_cand = K * ((T + 1) * ns + T + T * na + (tv.w1 ? 1 : 0));
-    const size_t Bc = a->chunk > 0 ? std::min<size_t>(B, (size_t)a->chunk) : std::min<size_t>(B, std::max<size_t>(1, ((size_t)1 << 26) / per_cand));
+    const size_t Bc = score_chunk(B, per_cand, (size_t)a->chunk);
     const size_t o_wt = (K * (T + 1) * Bc * ns + 3) & ~(size_t)3, o_aw = (o_wt + K * T * Bc + 3) & ~(size_t)3;
     const size_t o_we = o_aw + K * T * Bc * na;
     { const int rc = ws_grow(c, c->d_spag, sizeof(float) * (o_we + (tv.w1 ? K * Bc : 0))); if (rc) return rc; }
@@ -534,9 +487,8 @@ int run_score_policy_actions_grad(metrpo_ctx* c, const metrpo_score_policy_actio
         if (!rc) rc = allow_dynamic_lds(c, (const void*)en->bwd, sh_b);
         if (rc) return rc;
     } else {
-        const size_t fpt = spag_gen_floats(pd), LDS_MAX = 160 * 1024;             // bptt.hip's rule
-        while (bs > 1 && fpt * bs * sizeof(float) > LDS_MAX) bs >>= 1;
-        if (fpt * bs * sizeof(float) > LDS_MAX) return set_err(c, METRPO_EUNSUPPORTED, "score_policy_actions_grad: layer widths exceed the LDS budget of the generic kernel");
+        const size_t fpt = grad_gen_floats(pd, true);
+        if ((bs = lds_block_size(fpt)) == 0) return set_err(c, METRPO_EUNSUPPORTED, "score_policy_actions_grad: layer widths exceed the LDS budget of the generic kernel");
         sh_f = sh_b = fpt * bs * sizeof(float);
         gen_fwd = tv.w1 ? k_spag_gen_fwd<true> : k_spag_gen_fwd<false>;
         int rc = allow_dynamic_lds(c, (const void*)gen_fwd, sh_f);

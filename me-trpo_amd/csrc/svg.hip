@@ -281,10 +281,9 @@ static bool svg_gemm_ok(const metrpo_ctx* c) {
 
 // threads per block of k_svg_jac on `net`: the largest of 64, 32, ... whose LDS columns fit; 0: none does
 static int svg_jac_block(const NetDesc& net, size_t* lds_bytes) {
-    const size_t fpt = svg_jac_floats(net), LDS_MAX = 160 * 1024;
-    int bs = 64;
-    while (bs > 1 && fpt * bs * sizeof(float) > LDS_MAX) bs >>= 1;
-    if (fpt * bs * sizeof(float) > LDS_MAX) return 0;
+    const size_t fpt = svg_jac_floats(net);
+    const int bs = lds_block_size(fpt);
+    if (bs == 0) return 0;
     *lds_bytes = fpt * bs * sizeof(float);
     return bs;
 }

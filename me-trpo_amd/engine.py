@@ -418,6 +418,62 @@ class Engine(object):
         with want_all, then a reduction kernel); None before the first."""
         return {0: 'generic', 1: 'fused'}.get(int(lib.metrpo_last_disagreement_kernel(self._ctx)))
 
+    # ------------------------------------------------------------------ what the four scoring calls below share
+    def _score_starts(self, init_obs):
+        """init_obs [S, ns] or [ns] -> (the device tensor [S, ns], S)"""
+        init_obs = _f32(init_obs, self.device)
+        if init_obs.dim() == 1:
+            init_obs = init_obs.unsqueeze(0)
+        if init_obs.dim() != 2 or init_obs.shape[1] != self.ns or init_obs.shape[0] < 1:
+            raise ValueError("init_obs: expected [S, %d] or [%d], got %s" % (self.ns, self.ns, tuple(init_obs.shape)))
+        return init_obs, init_obs.shape[0]
+
+    def _score_sequences(self, seq, name, S, T=None):
+        """The candidates' [T, B, na] sequences (name: 'actions' or 'noise') -> (the device tensor, T, B); noise=None: (None, T=, S)."""
+        if seq is None and name == 'noise':
+            if T is None or int(T) < 0:
+                raise ValueError("noise=None needs T= (the number of steps), got %r" % (T,))
+            return None, int(T), S
+        seq = _f32(seq, self.device)
+        if seq.dim() != 3 or seq.shape[2] != self.na or seq.shape[1] % S != 0:
+            raise ValueError("%s: expected [T, B, %d] with B a multiple of %d, got %s" % (name, self.na, S, tuple(seq.shape)))
+        if T is not None and int(T) != int(seq.shape[0]):
+            raise ValueError("T = %r does not match %s %s" % (T, name, tuple(seq.shape)))
+        return seq, int(seq.shape[0]), int(seq.shape[1])
+
+    def _score_call(self, fn, a, names, want, out, init_obs, S, T, B, gamma, stop_at_done, force_generic, chunk=None):
+        """Checks want / gamma / chunk, allocates the outputs (names[0] is always computed), fills the args struct `a` -- the caller has set what only its
+        call has -- and enqueues fn.  -> dict name -> device tensor"""
+        dev = self.device
+        want = (want,) if isinstance(want, str) else tuple(want)
+        for w in want:
+            if w not in names:
+                raise ValueError("want: %r is none of %s" % (w, names))
+        if not np.isfinite(float(gamma)):
+            raise ValueError("gamma must be finite")
+        if chunk is not None:
+            if int(chunk) < 0:
+                raise ValueError("chunk must not be negative")
+            a.chunk = int(chunk)
+        K, ns, na = self.K, self.ns, self.na
+        shapes = {'ret': (K, B), 'len': (K, B), 'ret_mean': (B,), 'ret_std': (B,), 'act_out': (K, T, B, na), 'grad': (K, T, B, na), 'grad_mean': (T, B, na),
+                  'lam0': (K, B, ns)}
+        res = {}
+        for w in names[:1] + tuple(x for x in want if x != names[0]):
+            dt = torch.int32 if w == 'len' else torch.float32
+            if out is not None and w in out:
+                t = out[w]
+                assert t.dtype == dt and t.is_contiguous() and t.device == dev and t.numel() >= int(np.prod(shapes[w], dtype=np.int64))
+            else:
+                t = torch.empty(shapes[w], dtype=dt, device=dev)
+            res[w] = t
+        a.B, a.T, a.S, a.stop_at_done, a.force_generic, a.gamma = B, T, S, int(bool(stop_at_done)), int(bool(force_generic)), float(gamma)
+        a.d_init_obs = init_obs.data_ptr()
+        for w in names:
+            setattr(a, 'd_' + w, res[w].data_ptr() if w in res else None)
+        self._chk(fn(self._ctx, C.byref(a), self._stream()))
+        return res
+
     # ------------------------------------------------------------------ every head's return of candidate action sequences
     SCORE_ACTIONS_OUTPUTS = ('ret', 'len', 'ret_mean', 'ret_std')
 
@@ -428,39 +484,11 @@ class Engine(object):
         (the step that ends it still counts), False: every step counts.  want: any of ret [K, B], len [K, B] int32 (steps counted), ret_mean [B],
         ret_std [B] (population std over the heads); ret is always computed.  -> dict of device tensors, nothing synchronised.  out: dict name ->
         tensor to write into instead (contiguous, at least that large)."""
-        dev = self.device
-        init_obs = _f32(init_obs, dev)
-        if init_obs.dim() == 1:
-            init_obs = init_obs.unsqueeze(0)
-        if init_obs.dim() != 2 or init_obs.shape[1] != self.ns or init_obs.shape[0] < 1:
-            raise ValueError("init_obs: expected [S, %d] or [%d], got %s" % (self.ns, self.ns, tuple(init_obs.shape)))
-        S = init_obs.shape[0]
-        actions = _f32(actions, dev)
-        if actions.dim() != 3 or actions.shape[2] != self.na or actions.shape[1] % S != 0:
-            raise ValueError("actions: expected [T, B, %d] with B a multiple of %d, got %s" % (self.na, S, tuple(actions.shape)))
-        T, B = int(actions.shape[0]), int(actions.shape[1])
-        want = (want,) if isinstance(want, str) else tuple(want)
-        for w in want:
-            if w not in self.SCORE_ACTIONS_OUTPUTS:
-                raise ValueError("want: %r is none of %s" % (w, self.SCORE_ACTIONS_OUTPUTS))
-        if not np.isfinite(float(gamma)):
-            raise ValueError("gamma must be finite")
-        shapes = {'ret': (self.K, B), 'len': (self.K, B), 'ret_mean': (B,), 'ret_std': (B,)}
-        res = {}
-        for w in ('ret',) + tuple(x for x in want if x != 'ret'):
-            dt = torch.int32 if w == 'len' else torch.float32
-            if out is not None and w in out:
-                t = out[w]
-                assert t.dtype == dt and t.is_contiguous() and t.device == dev and t.numel() >= int(np.prod(shapes[w], dtype=np.int64))
-            else:
-                t = torch.empty(shapes[w], dtype=dt, device=dev)
-            res[w] = t
+        init_obs, S = self._score_starts(init_obs)
+        actions, T, B = self._score_sequences(actions, 'actions', S)
         a = _lib.ScoreActionsArgs()
-        a.B, a.T, a.S, a.stop_at_done, a.force_generic, a.gamma = B, T, S, int(bool(stop_at_done)), int(bool(force_generic)), float(gamma)
-        a.d_init_obs, a.d_actions = init_obs.data_ptr(), actions.data_ptr()
-        for w in self.SCORE_ACTIONS_OUTPUTS:
-            setattr(a, 'd_' + w, res[w].data_ptr() if w in res else None)
-        self._chk(lib.metrpo_score_actions(self._ctx, C.byref(a), self._stream()))
+        a.d_actions = actions.data_ptr()
+        res = self._score_call(lib.metrpo_score_actions, a, self.SCORE_ACTIONS_OUTPUTS, want, out, init_obs, S, T, B, gamma, stop_at_done, force_generic)
         self._sa_keep = (init_obs, actions)                                        # alive until the stream has consumed them
         return res
 
@@ -480,47 +508,12 @@ class Engine(object):
         init_obs[b // (B // S)]; never written), or None: the deterministic policy for T= steps, B = S.  want: any of ret [K, B], len [K, B] int32,
         ret_mean [B], ret_std [B], act_out [K, T, B, na] (the UNCLIPPED action head k's trajectory took); ret is always computed.  -> dict of device
         tensors, nothing synchronised.  out: dict name -> tensor to write into instead (contiguous, at least that large)."""
-        dev = self.device
-        init_obs = _f32(init_obs, dev)
-        if init_obs.dim() == 1:
-            init_obs = init_obs.unsqueeze(0)
-        if init_obs.dim() != 2 or init_obs.shape[1] != self.ns or init_obs.shape[0] < 1:
-            raise ValueError("init_obs: expected [S, %d] or [%d], got %s" % (self.ns, self.ns, tuple(init_obs.shape)))
-        S = init_obs.shape[0]
-        if noise is None:
-            if T is None or int(T) < 0:
-                raise ValueError("noise=None needs T= (the number of steps), got %r" % (T,))
-            T, B = int(T), S
-        else:
-            noise = _f32(noise, dev)
-            if noise.dim() != 3 or noise.shape[2] != self.na or noise.shape[1] % S != 0:
-                raise ValueError("noise: expected [T, B, %d] with B a multiple of %d, got %s" % (self.na, S, tuple(noise.shape)))
-            if T is not None and int(T) != int(noise.shape[0]):
-                raise ValueError("T = %r does not match noise %s" % (T, tuple(noise.shape)))
-            T, B = int(noise.shape[0]), int(noise.shape[1])
-        want = (want,) if isinstance(want, str) else tuple(want)
-        for w in want:
-            if w not in self.SCORE_POLICY_ACTIONS_OUTPUTS:
-                raise ValueError("want: %r is none of %s" % (w, self.SCORE_POLICY_ACTIONS_OUTPUTS))
-        if not np.isfinite(float(gamma)):
-            raise ValueError("gamma must be finite")
-        shapes = {'ret': (self.K, B), 'len': (self.K, B), 'ret_mean': (B,), 'ret_std': (B,), 'act_out': (self.K, T, B, self.na)}
-        res = {}
-        for w in ('ret',) + tuple(x for x in want if x != 'ret'):
-            dt = torch.int32 if w == 'len' else torch.float32
-            if out is not None and w in out:
-                t = out[w]
-                assert t.dtype == dt and t.is_contiguous() and t.device == dev and t.numel() >= int(np.prod(shapes[w], dtype=np.int64))
-            else:
-                t = torch.empty(shapes[w], dtype=dt, device=dev)
-            res[w] = t
+        init_obs, S = self._score_starts(init_obs)
+        noise, T, B = self._score_sequences(noise, 'noise', S, T)
         a = _lib.ScorePolicyActionsArgs()
-        a.B, a.T, a.S, a.stop_at_done, a.noise_in_std, a.force_generic = B, T, S, int(bool(stop_at_done)), int(bool(noise_in_std)), int(bool(force_generic))
-        a.gamma = float(gamma)
-        a.d_init_obs, a.d_noise = init_obs.data_ptr(), (noise.data_ptr() if noise is not None else None)
-        for w in self.SCORE_POLICY_ACTIONS_OUTPUTS:
-            setattr(a, 'd_' + w, res[w].data_ptr() if w in res else None)
-        self._chk(lib.metrpo_score_policy_actions(self._ctx, C.byref(a), self._stream()))
+        a.noise_in_std, a.d_noise = int(bool(noise_in_std)), (noise.data_ptr() if noise is not None else None)
+        res = self._score_call(lib.metrpo_score_policy_actions, a, self.SCORE_POLICY_ACTIONS_OUTPUTS, want, out, init_obs, S, T, B, gamma, stop_at_done,
+                               force_generic)
         self._spa_keep = (init_obs, noise)                                         # alive until the stream has consumed them
         return res
 
@@ -539,41 +532,12 @@ class Engine(object):
         heads' mean, summed in head order), lam0 [K, B, ns] (the gradient with respect to the start state).  chunk: candidates per pass of the
         workspace (0: the library's rule); it changes no bit of any output.  -> dict of device tensors, nothing synchronised.  out: dict name ->
         tensor to write into instead (contiguous, at least that large)."""
-        dev = self.device
-        init_obs = _f32(init_obs, dev)
-        if init_obs.dim() == 1:
-            init_obs = init_obs.unsqueeze(0)
-        if init_obs.dim() != 2 or init_obs.shape[1] != self.ns or init_obs.shape[0] < 1:
-            raise ValueError("init_obs: expected [S, %d] or [%d], got %s" % (self.ns, self.ns, tuple(init_obs.shape)))
-        S = init_obs.shape[0]
-        actions = _f32(actions, dev)
-        if actions.dim() != 3 or actions.shape[2] != self.na or actions.shape[1] % S != 0:
-            raise ValueError("actions: expected [T, B, %d] with B a multiple of %d, got %s" % (self.na, S, tuple(actions.shape)))
-        T, B = int(actions.shape[0]), int(actions.shape[1])
-        want = (want,) if isinstance(want, str) else tuple(want)
-        for w in want:
-            if w not in self.SCORE_ACTIONS_GRAD_OUTPUTS:
-                raise ValueError("want: %r is none of %s" % (w, self.SCORE_ACTIONS_GRAD_OUTPUTS))
-        if not np.isfinite(float(gamma)):
-            raise ValueError("gamma must be finite")
-        if int(chunk) < 0:
-            raise ValueError("chunk must not be negative")
-        shapes = {'grad': (self.K, T, B, self.na), 'ret': (self.K, B), 'len': (self.K, B), 'grad_mean': (T, B, self.na), 'lam0': (self.K, B, self.ns)}
-        res = {}
-        for w in ('grad',) + tuple(x for x in want if x != 'grad'):
-            dt = torch.int32 if w == 'len' else torch.float32
-            if out is not None and w in out:
-                t = out[w]
-                assert t.dtype == dt and t.is_contiguous() and t.device == dev and t.numel() >= int(np.prod(shapes[w], dtype=np.int64))
-            else:
-                t = torch.empty(shapes[w], dtype=dt, device=dev)
-            res[w] = t
+        init_obs, S = self._score_starts(init_obs)
+        actions, T, B = self._score_sequences(actions, 'actions', S)
         a = _lib.ScoreActionsGradArgs()
-        a.B, a.T, a.S, a.stop_at_done, a.force_generic, a.chunk, a.gamma = B, T, S, int(bool(stop_at_done)), int(bool(force_generic)), int(chunk), float(gamma)
-        a.d_init_obs, a.d_actions = init_obs.data_ptr(), actions.data_ptr()
-        for w in self.SCORE_ACTIONS_GRAD_OUTPUTS:
-            setattr(a, 'd_' + w, res[w].data_ptr() if w in res else None)
-        self._chk(lib.metrpo_score_actions_grad(self._ctx, C.byref(a), self._stream()))
+        a.d_actions = actions.data_ptr()
+        res = self._score_call(lib.metrpo_score_actions_grad, a, self.SCORE_ACTIONS_GRAD_OUTPUTS, want, out, init_obs, S, T, B, gamma, stop_at_done,
+                               force_generic, chunk)
         self._sag_keep = (init_obs, actions)                                       # alive until the stream has consumed them
         return res
 
@@ -595,50 +559,12 @@ class Engine(object):
         act_out [K, T, B, na].  ret, len and act_out carry score_policy_actions' bits on the same path.  chunk: candidates per pass of the workspace
         (0: the library's rule); it changes no bit of any output.  -> dict of device tensors, nothing synchronised.  out: dict name -> tensor to
         write into instead (contiguous, at least that large)."""
-        dev = self.device
-        init_obs = _f32(init_obs, dev)
-        if init_obs.dim() == 1:
-            init_obs = init_obs.unsqueeze(0)
-        if init_obs.dim() != 2 or init_obs.shape[1] != self.ns or init_obs.shape[0] < 1:
-            raise ValueError("init_obs: expected [S, %d] or [%d], got %s" % (self.ns, self.ns, tuple(init_obs.shape)))
-        S = init_obs.shape[0]
-        if noise is None:
-            if T is None or int(T) < 0:
-                raise ValueError("noise=None needs T= (the number of steps), got %r" % (T,))
-            T, B = int(T), S
-        else:
-            noise = _f32(noise, dev)
-            if noise.dim() != 3 or noise.shape[2] != self.na or noise.shape[1] % S != 0:
-                raise ValueError("noise: expected [T, B, %d] with B a multiple of %d, got %s" % (self.na, S, tuple(noise.shape)))
-            if T is not None and int(T) != int(noise.shape[0]):
-                raise ValueError("T = %r does not match noise %s" % (T, tuple(noise.shape)))
-            T, B = int(noise.shape[0]), int(noise.shape[1])
-        want = (want,) if isinstance(want, str) else tuple(want)
-        for w in want:
-            if w not in self.SCORE_POLICY_ACTIONS_GRAD_OUTPUTS:
-                raise ValueError("want: %r is none of %s" % (w, self.SCORE_POLICY_ACTIONS_GRAD_OUTPUTS))
-        if not np.isfinite(float(gamma)):
-            raise ValueError("gamma must be finite")
-        if int(chunk) < 0:
-            raise ValueError("chunk must not be negative")
-        shapes = {'grad': (self.K, T, B, self.na), 'ret': (self.K, B), 'len': (self.K, B), 'grad_mean': (T, B, self.na), 'lam0': (self.K, B, self.ns),
-                  'act_out': (self.K, T, B, self.na)}
-        res = {}
-        for w in ('grad',) + tuple(x for x in want if x != 'grad'):
-            dt = torch.int32 if w == 'len' else torch.float32
-            if out is not None and w in out:
-                t = out[w]
-                assert t.dtype == dt and t.is_contiguous() and t.device == dev and t.numel() >= int(np.prod(shapes[w], dtype=np.int64))
-            else:
-                t = torch.empty(shapes[w], dtype=dt, device=dev)
-            res[w] = t
+        init_obs, S = self._score_starts(init_obs)
+        noise, T, B = self._score_sequences(noise, 'noise', S, T)
         a = _lib.ScorePolicyActionsGradArgs()
-        a.B, a.T, a.S, a.stop_at_done, a.noise_in_std, a.force_generic = B, T, S, int(bool(stop_at_done)), int(bool(noise_in_std)), int(bool(force_generic))
-        a.chunk, a.gamma = int(chunk), float(gamma)
-        a.d_init_obs, a.d_noise = init_obs.data_ptr(), (noise.data_ptr() if noise is not None else None)
-        for w in self.SCORE_POLICY_ACTIONS_GRAD_OUTPUTS:
-            setattr(a, 'd_' + w, res[w].data_ptr() if w in res else None)
-        self._chk(lib.metrpo_score_policy_actions_grad(self._ctx, C.byref(a), self._stream()))
+        a.noise_in_std, a.d_noise = int(bool(noise_in_std)), (noise.data_ptr() if noise is not None else None)
+        res = self._score_call(lib.metrpo_score_policy_actions_grad, a, self.SCORE_POLICY_ACTIONS_GRAD_OUTPUTS, want, out, init_obs, S, T, B, gamma,
+                               stop_at_done, force_generic, chunk)
         self._spag_keep = (init_obs, noise)                                        # alive until the stream has consumed them
         return res
 
