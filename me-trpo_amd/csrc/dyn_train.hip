@@ -191,7 +191,8 @@ static void train_forward(metrpo_ctx* c, const TrainWs& ws, int rows, hipStream_
         // 64-column tile per 64 rows walks the whole K axis on a fifth of the CUs: 25.8 us of a 210 us step at 2 x 512, batch 1000)
         if (l == L - 1) gemm_skinny_bias(ws.H[l], (long long)rows * Kd, Kd, Wl, pd.dyn.n_params, N, ep.bias, ep.strideBias, out, (long long)rows * N, rows, N, Kd, K, ws.part, st);
         else if (pd.dyn.act[l] == METRPO_ACT_RELU) gemm_auto<EPI_BIAS_RELU, false, false>(ws.H[l], (long long)rows * Kd, Kd, Wl, pd.dyn.n_params, N, out, (long long)rows * N, N, rows, N, Kd, K, ep, st);
-        else gemm_auto<EPI_BIAS_TANH, false, false>(ws.H[l], (long long)rows * Kd, Kd, Wl, pd.dyn.n_params, N, out, (long long)rows * N, N, rows, N, Kd, K, ep, st);
+        else if (pd.dyn.act[l] == METRPO_ACT_TANH) gemm_auto<EPI_BIAS_TANH, false, false>(ws.H[l], (long long)rows * Kd, Kd, Wl, pd.dyn.n_params, N, out, (long long)rows * N, N, rows, N, Kd, K, ep, st);
+        else gemm_auto<EPI_BIAS_ID, false, false>(ws.H[l], (long long)rows * Kd, Kd, Wl, pd.dyn.n_params, N, out, (long long)rows * N, N, rows, N, Kd, K, ep, st);   // identity (build_net admits no fourth)
     }
 }
 

@@ -53,9 +53,19 @@ def _dyn_forward_cache(dm, k, s, a):
     for l in range(L):
         h = h @ dm.Ws[l][k] + dm.bs[l][k]
         if l < L - 1:
-            assert dm.acts[l] == 'relu'
-            h = np.maximum(h, 0); hs.append(h)
+            h = O._ACTS[dm.acts[l]](h); hs.append(h)
     return dm.diff_mean[:dm.ns] + dm.diff_std[:dm.ns] * h + s, hs
+
+
+def _dact(name, h):
+    """Derivative of a hidden activation (training.py:156-208: one per hidden layer) written in its OUTPUT h: relu' = [h > 0], tanh' = 1 - h^2, identity' = 1."""
+    if name == 'relu':
+        return h > 0
+    if name == 'tanh':
+        return 1.0 - np.square(h)
+    if name == 'identity':
+        return 1.0
+    raise KeyError(name)
 
 
 def _dyn_vjp(dm, k, hs, g_next):
@@ -66,7 +76,7 @@ def _dyn_vjp(dm, k, hs, g_next):
     for l in range(L - 1, -1, -1):
         d = d @ dm.Ws[l][k].T
         if l > 0:
-            d = d * (hs[l] > 0)
+            d = d * _dact(dm.acts[l - 1], hs[l])
     gxu = np.zeros((g_next.shape[0], ns + na), dtype=g_next.dtype)
     gxu[:, dm.n_drop:] = d
     gxu = gxu / dm.in_std

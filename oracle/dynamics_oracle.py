@@ -184,7 +184,7 @@ def model_forward_cache(dm, k, x):
     for l in range(L):
         h = h @ dm.Ws[l][k] + dm.bs[l][k]
         if l < L - 1:
-            h = np.maximum(h, 0)
+            h = O._ACTS[dm.acts[l]](h)
             hs.append(h)
     return dm.diff_mean + dm.diff_std * h + s, hs
 
@@ -200,7 +200,8 @@ def regularizer_loss(dm, k, constant):
 
 
 def model_gradients(dm, k, x, y):
-    """d(prediction_loss_k)/d(W_l, b_l) by back-propagation (relu hidden layers)."""
+    """d(prediction_loss_k)/d(W_l, b_l) by back-propagation (relu hidden layers: what the training step supports)."""
+    assert all(a == 'relu' for a in dm.acts), dm.acts
     n = x.shape[0]
     pred, hs = model_forward_cache(dm, k, x)
     dz = 2.0 * (pred - y) / n * dm.diff_std

@@ -191,8 +191,9 @@ def walk(dm, theta, dims, env, x0, T, gamma, eps=None, dtype=np.float64, mut=Non
             for l in range(L):
                 h = h @ d.Ws[l][k] + d.bs[l][k]
                 if l < L - 1:
-                    site('relu', h)
-                    h = np.maximum(h, 0); hs_d.append(h)
+                    if d.acts[l] == 'relu':                          # the only hidden activation with a kink
+                        site('relu', h)
+                    h = O._ACTS[d.acts[l]](h); hs_d.append(h)
             xn = d.diff_mean[:ns] + d.diff_std[:ns] * h + x
             if env == 'half_cheetah':
                 site('hc_inner', np.abs(xn[:, 9] - f(1e-1 * 0.5) * np.sum(np.square(u), axis=1)) - 10.0)

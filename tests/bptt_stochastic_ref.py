@@ -63,7 +63,7 @@ def stochastic_costs_and_grad(dm, theta, dims, env, x0, T, gamma, eps):
             for l in range(len(dm.Ws)):
                 z = z @ t64(dm.Ws[l][k]) + t64(dm.bs[l][k])
                 if l < len(dm.Ws) - 1:
-                    z = torch.relu(z)
+                    z = {'relu': torch.relu, 'tanh': torch.tanh, 'identity': lambda v: v}[dm.acts[l]](z)
             xn = dmean + dstd * z + x
             c = _cost(env, u, xn)
             if env == 'ant':

@@ -191,14 +191,15 @@ def exact_rollout(env, K, hidden, B, T, H, sam_mode, seed):
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
 # random real-valued nets
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
-def random_case(hidden, env='half_cheetah', K=3, B=4097, seed=5):
+def random_case(hidden, env='half_cheetah', K=3, B=4097, seed=5, acts='relu'):
     """Xavier nets as synthetic makes them (oracle make_problem), states from the pool, actions in [-1, 1]; everything f32-representable.
     B = 4097 rows (not a multiple of any tile; 33 row tiles), not 129: a hidden activation within f32 error of a bf16 tie rounds the other way under another
     summation order, about two in a million do, and ONE such flip moves a head's rel-L2 over 129 rows by 3e-5 at hidden (128, 128) -- 600 x the
     flip-free figure (5e-8) and 1/60 of the distance to the unrounded model (1.8e-3).  At 129 rows the measured figure is therefore 5e-8 or 3e-5 by the luck
     of the order, and 8 x 10 x 3e-5 exceeds 1.8e-3: margin and discrimination cannot both hold.  Over 4097 rows every head sees a few flips, the figure
-    is stable (1.8e-5 / 8.3e-6) and both hold (the unrounded model is 102 / 112 figures away).  The case was enlarged, not the bound."""
-    dm, theta, pdims, pool = O.make_problem(env, K=K, dyn_hidden=hidden, pol_hidden=(32, 32), seed=seed, n_pool=B)
+    is stable (1.8e-5 / 8.3e-6) and both hold (the unrounded model is 102 / 112 figures away).  The case was enlarged, not the bound.
+    acts: one activation name, or one per hidden layer (the weights do not depend on it)."""
+    dm, theta, pdims, pool = O.make_problem(env, K=K, dyn_hidden=hidden, pol_hidden=(32, 32), seed=seed, n_pool=B, dyn_act=acts)
     dm = dm.astype(np.float32).astype(np.float64)
     rng = np.random.RandomState(seed + 1)
     s = pool.astype(np.float32)
@@ -220,7 +221,7 @@ def emu_f32_step(dm, s, ac):
             for k0 in range(0, hr.shape[1], 4):
                 acc = acc + hr[:, k0:k0 + 4] @ Wr[k0:k0 + 4]
             z = dm.bs[l][k].astype(np.float32) + acc
-            h = np.maximum(z, np.float32(0)) if l < L - 1 else z
+            h = _ACT[dm.acts[l]](z).astype(np.float32) if l < L - 1 else z
         out.append(dm.diff_mean.astype(np.float32) + dm.diff_std.astype(np.float32) * h)
     return np.stack(out).astype(np.float64)
 
@@ -237,10 +238,10 @@ RANDOM_HIDDEN = [(128, 128), (512, 512)]
 BOUND_FACTOR = 8.0          # margin for a third summation order (the matrix instruction's)
 
 
-def random_bound(hidden):
+def random_bound(hidden, acts='relu'):
     """rel-L2 bound of the random-net GPU test at this width: 8 x the distance between the float32-accumulating emulation and the restatement
     (worst head).  -> (bound, emulation figure, case, restated delta)"""
-    dm, s, ac = random_case(hidden)
+    dm, s, ac = random_case(hidden, acts=acts)
     ref = ref_delta(dm, s, ac)
     fig = float(np.max(rel_l2_per_head(emu_f32_step(dm, s, ac), ref)))
     return BOUND_FACTOR * fig, fig, (dm, s, ac), ref

@@ -99,11 +99,15 @@ def f32(x):
 class Problem(object):
     """helpers.problem_data(env, K, hidden, pol) with a pool of 257 distinct rows, everything rounded to fp32 (the device's storage type)."""
 
-    def __init__(self, env, K, hidden=(64, 64), pol=(32, 32), row=TOL.STEP):
+    def __init__(self, env, K, hidden=(64, 64), pol=(32, 32), row=TOL.STEP, dyn_act='relu', shape=None):
+        """dyn_act: one activation name or one per hidden layer; shape(dm, theta, pdims, pool): changes the float64 net in place before it is rounded
+        (tests/dyn_act_cases.py scales the first layer with it).  The defaults give the table of this file."""
         self.env, self.K, self.hidden, self.pol = env, K, tuple(hidden), tuple(pol)
-        dm, theta, self.pdims, pool = Hh.problem_data(env, K, hidden, pol, seed=PROBLEM_SEED, n_pool=N_POOL)
+        dm, theta, self.pdims, pool = Hh.problem_data(env, K, hidden, pol, seed=PROBLEM_SEED, n_pool=N_POOL, dyn_act=dyn_act)
         if env == 'ant':                                           # some envs start near the lower z bound: state-dependent dones inside the call
             pool[::3, 2] = 0.21; dm.diff_mean[2] = -0.02
+        if shape is not None:
+            shape(dm, theta, self.pdims, pool)
         self.dm = dm.astype(np.float32).astype(np.float64)
         self.th, self.pool32 = f32(theta), f32(pool)
         assert len({r.tobytes() for r in self.pool32}) == N_POOL    # distinct rows: a pool row identifies its index

@@ -104,10 +104,10 @@ def kink_sites(env, s, a, dtype):
 def rollout_margin(dm, env, model, s, a):
     """min over the kink sites of |z64| / |z32 - z64| (inf where the two agree exactly); 0 if a branch differs"""
     sites = []
-    if all(x == 'relu' for x in dm.acts):
+    if 'relu' in dm.acts:                                         # the pre-activations of the relu layers (tanh and identity have no kink)
         _, z64 = R.dyn_jacobian(dm, model, s, a, np.float64)
         _, z32 = R.dyn_jacobian(dm, model, s, a, np.float32)
-        sites += [(p.ravel(), q.ravel().astype(np.float64)) for p, q in zip(z64, z32)]
+        sites += [(p.ravel(), q.ravel().astype(np.float64)) for x, p, q in zip(dm.acts, z64, z32) if x == 'relu']
     sites.append((kink_sites(env, s, a, np.float64).ravel(), kink_sites(env, s, a, np.float32).ravel().astype(np.float64)))
     m = np.inf
     for z64, z32 in sites:

@@ -55,6 +55,44 @@ def test_bench_configs_of_the_params_files_are_the_files_shapes():
         assert synthetic.config_from_params(os.path.join(GOLD, 'params_%s.json' % name)) == dict(c, gpus=1)
 
 
+def test_per_layer_nonlinearity_reaches_the_engine_arguments():
+    """dynamics_model.nonlinearity is a list with one activation per hidden layer (training.py:156-208): tanh (both spellings) and identity are mapped
+    onto Engine(dyn_act=[...]) in layer order; an unknown name is refused by name."""
+    m = load_params_module()
+    p = json.load(open(os.path.join(GOLD, 'params_swimmer.json')))
+    p['dynamics_model']['nonlinearity'] = ['tf.nn.tanh', 'tf.identity']
+    assert m.shapes_from_params(p)['dyn_act'] == ['tanh', 'identity']
+    p['dynamics_model']['nonlinearity'] = ['tf.identity', 'tf.tanh']
+    assert m.shapes_from_params(p)['dyn_act'] == ['identity', 'tanh']
+    p['dynamics_model']['nonlinearity'] = ['tf.nn.relu', 'tf.nn.tanh']
+    assert m.shapes_from_params(p)['dyn_act'] == ['relu', 'tanh']
+    p['dynamics_model']['nonlinearity'] = ['tf.nn.tanh', 'tf.nn.elu']
+    with pytest.raises(ValueError, match='nonlinearity'):
+        m.shapes_from_params(p)
+
+
+def test_from_params_hands_the_activations_to_the_engine(monkeypatch):
+    """from_params builds Engine(..., dyn_act=[one name per hidden layer]): the constructor's arguments, caught in front of the device."""
+    import importlib
+    import sys
+    m = load_params_module()
+    pkg = sys.modules[m.from_params.__module__].__package__
+    seen = {}
+
+    class Caught(Exception):
+        pass
+
+    def fake_engine(*args, **kw):
+        seen.update(args=args, kw=kw)
+        raise Caught()
+    monkeypatch.setattr(importlib.import_module(pkg + '.engine'), 'Engine', fake_engine)
+    p = json.load(open(os.path.join(GOLD, 'params_swimmer.json')))
+    p['dynamics_model']['nonlinearity'] = ['tf.nn.tanh', 'tf.identity']
+    with pytest.raises(Caught):
+        m.from_params(p)
+    assert seen['kw']['dyn_act'] == ['tanh', 'identity'] and tuple(seen['args'][2]) == (512, 512)
+
+
 def test_variants_without_a_kernel_are_named():
     m = load_params_module()
     for name in ('point_mass', 'point2D'):                      # envs without an analytic reward on this path

@@ -332,14 +332,15 @@ def mutation_applies(mut, f):
 
 
 def heads_forward(p, s, ac, mut=None):
-    """Every head's next state [K, B, ns]: normalise, drop the leading columns, relu layers, identity output layer, de-normalise + residual."""
+    """Every head's next state [K, B, ns]: normalise, drop the leading columns, the hidden layers with dm.acts (relu on every net of this table: Problem
+    asserts it), identity output layer, de-normalise + residual."""
     dm = p.dm
     x = ((np.concatenate([s, ac], axis=1) - dm.in_mean) / dm.in_std)[:, dm.n_drop:]
     h = np.broadcast_to(x, (dm.K,) + x.shape)
     L = len(dm.Ws)
     for l in range(L - 1):
         b = np.zeros_like(dm.bs[l]) if (l == 0 and mut == 'l0_bias_missing') else dm.bs[l]
-        h = np.maximum(np.matmul(h, dm.Ws[l]) + b[:, None, :], 0.0)
+        h = O._ACTS[dm.acts[l]](np.matmul(h, dm.Ws[l]) + b[:, None, :])
     W = h.shape[2]
     if mut == 'out_partial_dropped':                                   # one partial of the output layer never added: a 256-column block, a 64-column tile where narrower
         h = h.copy(); h[:, :, W - (256 if W > 256 else 64):] = 0.0
