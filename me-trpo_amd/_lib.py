@@ -133,6 +133,18 @@ class ScorePolicyActionsGradArgs(C.Structure):
                 ('d_ret', C.c_void_p), ('d_len', C.c_void_p), ('d_grad_mean', C.c_void_p), ('d_lam0', C.c_void_p), ('d_act_out', C.c_void_p)]
 
 
+class DebugGemmArgs(C.Structure):          # csrc/gemm_debug.h (a diagnostics hook, not part of include/metrpo.h)
+    _fields_ = ([(n, C.c_int32) for n in ('op', 'epi', 'ta', 'tb', 'tm', 'tn', 'M', 'N', 'Kd', 'heads', 'lda', 'ldw', 'ldc', 'ldm')] +
+                [(n, C.c_int64) for n in ('strideA', 'strideW', 'strideC', 'strideBias', 'strideMask', 'strideAdam', 'stridePart', 'strideW2')] +
+                [(n, C.c_void_p) for n in ('A', 'W', 'C', 'bias', 'mask', 'am', 'av', 'bvec', 'bam', 'bav', 'part', 'w2')] +
+                [(n, C.c_float) for n in ('lr_t', 'beta1', 'beta2', 'eps', 'decay')] +
+                [(n, C.c_int32) for n in ('splits', 'kchunk', 'no', 'act', 'defer')] +
+                [(n, C.c_int32) for n in ('o_tm', 'o_tn', 'o_al', 'o_pd', 'o_splits', 'o_kchunk', 'o_gx', 'o_gy', 'o_gz', 'o_reduced')] +
+                [('o_stride_part', C.c_int64)])
+
+
+GEMM_EPIS = {'BIAS_ID': 0, 'BIAS_RELU': 1, 'BIAS_TANH': 2, 'RELU_MASK': 3, 'ADAM': 4, 'PLAIN': 5, 'PARTIAL': 6, 'DTANH': 7}     # csrc/gemm_mfma.h
+GEMM_DEBUG_OPS = {'auto': 0, 'skinny': 1, 'fused_out': 2}
 SVG_PATHS = {'auto': 0, 'generic': 1, 'gemm': 2}          # metrpo_svg_args.path
 MODEL_ERROR_MAX_HORIZONS = 32          # include/metrpo.h
 
@@ -252,6 +264,7 @@ EXTRA_SYMBOLS = {
     'metrpo_debug_coop_waves': (_I, [_P]),
     'metrpo_set_coop_split': (_I, [_P, _I]),
     'metrpo_debug_score_policy_chunk': (_I, [_P, _I]),
+    'metrpo_debug_gemm': (_I, [_P, C.POINTER(DebugGemmArgs), _P]),
 }
 
 

@@ -338,18 +338,35 @@ __global__ void __launch_bounds__(256) k_gemm_mfma(const float* __restrict__ A, 
         }
 }
 
+// The launched form of gemm_mfma_launch as pure host arithmetic (the launch below and the diagnostics hook of gemm_debug.hip both call these).
+struct GemmForm { bool al; int pd; unsigned gx, gy, gz; };
+static inline bool gemm_mult4(long long v) { return (v & 3) == 0; }
+static inline bool gemm_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// AL: both base pointers on 16 bytes; head strides and leading dimensions multiples of 4 floats; the extent along each operand's contiguous axis
+// (A rows run along Kd, or along M when TA; W rows along N, or along Kd when TB) a multiple of 4; and for split-K every chunk start as well.
+// PD 4 (64x64 tiles only): few workgroups per CU and a long contraction (see k_gemm_mfma's PD).
+static inline GemmForm gemm_launch_form(int tm, int tn, int epi, bool ta, bool tb, const float* A, long long sA, int lda, const float* W, long long sW, int ldw,
+                                        int M, int N, int Kd, int heads, const GemmEpi& ep) {
+    GemmForm f;
+    f.gx = (unsigned)((N + 64 * tn - 1) / (64 * tn)); f.gy = (unsigned)((M + 64 * tm - 1) / (64 * tm)); f.gz = (unsigned)(heads * (epi == EPI_PARTIAL ? ep.splits : 1));
+    const bool bases = gemm_aligned16(A) && gemm_aligned16(W);
+    const bool strides = gemm_mult4(sA) && gemm_mult4(sW) && gemm_mult4(lda) && gemm_mult4(ldw);
+    const bool extents = gemm_mult4(ta ? M : Kd) && gemm_mult4(tb ? Kd : N);
+    const bool chunks = epi != EPI_PARTIAL || gemm_mult4(ep.kchunk);
+    f.al = bases && strides && extents && chunks;
+    const long long nblocks = (long long)f.gx * f.gy * f.gz;
+    f.pd = (tm * tn == 1 && nblocks <= 1280 && Kd >= 256) ? 4 : 1;
+    return f;
+}
+
 template <int TM, int TN, int EPI, bool TA, bool TB>
 static inline void gemm_mfma_launch(const float* A, long long sA, int lda, const float* W, long long sW, int ldw, float* C, long long sC,
                                     int ldc, int M, int N, int Kd, int heads, const GemmEpi& ep, hipStream_t st) {
-    dim3 grid((N + 64 * TN - 1) / (64 * TN), (M + 64 * TM - 1) / (64 * TM), heads * (EPI == EPI_PARTIAL ? ep.splits : 1));
-    auto m4 = [](long long v) { return (v & 3) == 0; };
-    // contiguous axes: A rows run along Kd (or along M when TA), W rows along N (or along Kd when TB)
-    const bool al = m4((long long)(uintptr_t)A >> 2) && (((uintptr_t)A & 15) == 0) && (((uintptr_t)W & 15) == 0) && m4(sA) && m4(sW) && m4(lda) && m4(ldw) &&
-                    m4(TA ? M : Kd) && m4(TB ? Kd : N) && (EPI != EPI_PARTIAL || m4(ep.kchunk));
-    // few workgroups per CU and a long contraction: deeper prefetch (see k_gemm_mfma's PD)
-    const long long nblocks = (long long)grid.x * grid.y * grid.z;
+    const GemmForm f = gemm_launch_form(TM, TN, EPI, TA, TB, A, sA, lda, W, sW, ldw, M, N, Kd, heads, ep);
+    const dim3 grid(f.gx, f.gy, f.gz);
+    const bool al = f.al;
     if constexpr (TM * TN == 1) {
-        if (nblocks <= 1280 && Kd >= 256) {
+        if (f.pd == 4) {
             if (al) hipLaunchKernelGGL((k_gemm_mfma<TM, TN, EPI, TA, TB, true, 4>), grid, dim3(256), 0, st, A, sA, lda, W, sW, ldw, C, sC, ldc, M, N, Kd, ep);
             else hipLaunchKernelGGL((k_gemm_mfma<TM, TN, EPI, TA, TB, false, 4>), grid, dim3(256), 0, st, A, sA, lda, W, sW, ldw, C, sC, ldc, M, N, Kd, ep);
             return;
@@ -362,14 +379,20 @@ static inline void gemm_mfma_launch(const float* A, long long sA, int lda, const
 // Tile choice shared by every caller: 128x128 block tiles when that already yields enough workgroups to fill the 256 CUs a few
 // times over, otherwise halve the tile in M and then in N (more, smaller workgroups beat idle CUs on the small-batch shapes:
 // M = 500 rows x N = 512 x 5 heads is 80 tiles of 128x128 but 320 of 64x64).
-template <int EPI, bool TA, bool TB>
-static inline void gemm_auto(const float* A, long long sA, int lda, const float* W, long long sW, int ldw, float* C, long long sC, int ldc, int M,
-                             int N, int Kd, int heads, const GemmEpi& ep, hipStream_t st) {
+struct GemmTile { int tm, tn; };
+static inline GemmTile gemm_auto_tile(int M, int N, int heads) {
     auto blocks = [&](int tm, int tn) { return (long long)((M + 64 * tm - 1) / (64 * tm)) * ((N + 64 * tn - 1) / (64 * tn)) * heads; };
     int tm = (M > 64) ? 2 : 1, tn = (N > 64) ? 2 : 1;
     const long long want = 2048;            // ~8 workgroups per CU (measured: 64x64 tiles beat 128x128 by 15 % at 800 tiles, 128x128 wins from ~8k tiles)
     if (tm == 2 && blocks(tm, tn) < want) tm = 1;
     if (tn == 2 && blocks(tm, tn) < want) tn = 1;
+    return GemmTile{tm, tn};
+}
+template <int EPI, bool TA, bool TB>
+static inline void gemm_auto(const float* A, long long sA, int lda, const float* W, long long sW, int ldw, float* C, long long sC, int ldc, int M,
+                             int N, int Kd, int heads, const GemmEpi& ep, hipStream_t st) {
+    const GemmTile t = gemm_auto_tile(M, N, heads);
+    const int tm = t.tm, tn = t.tn;
     if (tm == 2 && tn == 2) gemm_mfma_launch<2, 2, EPI, TA, TB>(A, sA, lda, W, sW, ldw, C, sC, ldc, M, N, Kd, heads, ep, st);
     else if (tm == 2) gemm_mfma_launch<2, 1, EPI, TA, TB>(A, sA, lda, W, sW, ldw, C, sC, ldc, M, N, Kd, heads, ep, st);
     else if (tn == 2) gemm_mfma_launch<1, 2, EPI, TA, TB>(A, sA, lda, W, sW, ldw, C, sC, ldc, M, N, Kd, heads, ep, st);
@@ -430,12 +453,23 @@ static inline size_t skinny_part_floats(int M, int N, int Kd, int heads) {
 // defer != NULL: when the layer runs as split-K partials, skip the reduce launch and report {splits, stridePart} instead -- the
 // caller's next kernel adds the partials and the bias itself (rollout_gemm.hip: k_big_post); {0, 0} when C was written directly.
 struct SkinnyDefer { int splits; long long stridePart; };
+// the split gemm_skinny_bias launches: splits <= 1 means one unsplit gemm_auto launch writes C (no workspace, or splitting does not pay)
+struct SkinnyPlan { int splits, kchunk; long long stridePart; };
+static inline SkinnyPlan skinny_plan(int M, int N, int Kd, int heads, bool have_part) {
+    const int S = skinny_splits(M, N, Kd, heads);
+    if (S <= 1 || !have_part) return SkinnyPlan{1, Kd, 0};
+    SkinnyPlan p;
+    p.kchunk = (((Kd + S - 1) / S) + 15) & ~15;
+    p.splits = (Kd + p.kchunk - 1) / p.kchunk;
+    p.stridePart = (((long long)M * N + N) + 3) & ~3LL;
+    return p;
+}
 static inline void gemm_skinny_bias(const float* A, long long sA, int lda, const float* W, long long sW, int ldw, const float* bias, long long sBias,
                                     float* C, long long sC, int M, int N, int Kd, int heads, float* part, hipStream_t st, int act = 0,
                                     SkinnyDefer* defer = nullptr) {
     if (defer) { defer->splits = 0; defer->stridePart = 0; }
-    const int S = skinny_splits(M, N, Kd, heads);
-    if (S <= 1 || part == nullptr) {
+    const SkinnyPlan sp = skinny_plan(M, N, Kd, heads, part != nullptr);
+    if (sp.splits <= 1) {
         GemmEpi ep = {}; ep.bias = bias; ep.strideBias = sBias;
         if (act == 1) gemm_auto<EPI_BIAS_RELU, false, false>(A, sA, lda, W, sW, ldw, C, sC, N, M, N, Kd, heads, ep, st);
         else if (act == 2) gemm_auto<EPI_BIAS_TANH, false, false>(A, sA, lda, W, sW, ldw, C, sC, N, M, N, Kd, heads, ep, st);
@@ -443,8 +477,7 @@ static inline void gemm_skinny_bias(const float* A, long long sA, int lda, const
         return;
     }
     GemmEpi ep = {};
-    ep.part = part; ep.stridePart = (((long long)M * N + N) + 3) & ~3LL; ep.splits = S; ep.kchunk = (((Kd + S - 1) / S) + 15) & ~15;
-    ep.splits = (Kd + ep.kchunk - 1) / ep.kchunk;
+    ep.part = part; ep.stridePart = sp.stridePart; ep.splits = sp.splits; ep.kchunk = sp.kchunk;
     gemm_mfma_launch<1, 1, EPI_PARTIAL, false, false>(A, sA, lda, W, sW, ldw, nullptr, 0, N, M, N, Kd, heads, ep, st);
     if (defer && act == 0) { defer->splits = ep.splits; defer->stridePart = ep.stridePart; return; }
     const long long tot = (long long)M * N;

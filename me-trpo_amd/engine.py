@@ -703,6 +703,27 @@ class Engine(object):
         (set_coop_split(False), two workgroups per CU, K = 1, K > 5, half-cheetah, Ant); 0 before the first."""
         return int(lib.metrpo_debug_coop_waves(self._ctx))
 
+    GEMM_FORM_FIELDS = ('tm', 'tn', 'al', 'pd', 'splits', 'kchunk', 'gx', 'gy', 'gz', 'reduced', 'stride_part')
+
+    def debug_gemm(self, op, epi=0, **fields):
+        """Diagnostics: ONE call of the shared MFMA GEMM's host entries (csrc/gemm_mfma.h) on caller-owned float32 device tensors, for
+        tests/test_gpu_gemm.py.  op 'auto' (gemm_auto<epi, ta, tb>, or the tile forced with tm, tn = 1 | 2), 'skinny' (gemm_skinny_bias) or
+        'fused_out' (gemm_relu_fused_out); epi a name of _lib.GEMM_EPIS.  The other fields are those of _lib.DebugGemmArgs; a pointer field
+        takes a tensor or (tensor, offset in floats).  The caller sizes every tensor for the extents and strides it passes; no context state
+        is read or written.  -> the launched form, a dict over GEMM_FORM_FIELDS."""
+        a = _lib.DebugGemmArgs()
+        a.op, a.epi = _lib.GEMM_DEBUG_OPS[op], _lib.GEMM_EPIS[epi] if isinstance(epi, str) else int(epi)
+        kinds = dict((n, t) for n, t in _lib.DebugGemmArgs._fields_)
+        for name, val in fields.items():
+            if kinds[name] is C.c_void_p:
+                t, off = val if isinstance(val, tuple) else (val, 0)
+                if t is not None:
+                    assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device and 0 <= off < t.numel()
+                val = None if t is None else t.data_ptr() + 4 * int(off)
+            setattr(a, name, val)
+        self._chk(lib.metrpo_debug_gemm(self._ctx, C.byref(a), self._stream()))
+        return dict((n, int(getattr(a, 'o_' + n))) for n in self.GEMM_FORM_FIELDS)
+
     def rollout_note(self):
         """Why the last rollout() ran outside the fast dispatch table (K != 5 at 2x64, hidden widths 65..127, ...); '' when it did not."""
         return lib.metrpo_rollout_note(self._ctx).decode()
