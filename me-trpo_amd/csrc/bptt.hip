@@ -11,7 +11,9 @@
 //                    of the policy MEAN for every (i, t, b).
 //   policy VJP       sum over all (i, t, b) samples of J_policy(x_t)^T adjoint_mean: the gradient kernels of the TRPO update with
 //                    the mean-adjoint supplied (PolK.gm) instead of derived from the surrogate loss -- MFMA path included.
-// Generic in the layer widths (activations in LDS columns, one thread per trajectory).
+// Generic in the layer widths (activations in LDS columns, one thread per trajectory).  The reverse sweep's pieces -- a net's hidden layers
+// (net_hidden), its vector-Jacobian product (net_vjp) and the cost adjoint (cost_adjoint) -- are device_common.h's, shared with the generic
+// gradient kernels of score_actions_grad.hip and score_policy_actions_grad.hip.
 #include <cmath>
 #include "device_common.h"
 
@@ -48,33 +50,6 @@ __device__ __forceinline__ float* mlp_col_store(const NetDesc& net, const float*
         dst += net.dims[l + 1] * LD;
     }
     return const_cast<float*>(cur);
-}
-
-// d(w * cost)/du -> gU (written), d(w * cost)/dx_next -> added into G
-__device__ __forceinline__ void cost_adjoint(int env, int ns, int na, const float* xn, const float* u, float w, float* gU, float* G, int LD, int tid) {
-    float su2 = 0.0f;
-    for (int d = 0; d < na; ++d) { const float a = u[d * LD + tid]; su2 = fmaf(a, a, su2); }
-    float cu = 0.0f;                                         // gU[d] = cu * u[d]
-    switch (env) {
-    case METRPO_ENV_SWIMMER: G[5 * LD + tid] -= w; cu = w * 1e-2f * 2.0f / (float)na; break;
-    case METRPO_ENV_HALF_CHEETAH: {
-        const float inner = xn[9 * LD + tid] - 1e-1f * 0.5f * su2;
-        const float p = (inner >= -10.0f && inner <= 10.0f) ? 1.0f : 0.0f;       // tf.clip_by_value passes the gradient inside [min, max]
-        G[9 * LD + tid] -= w * p; cu = w * p * 1e-1f; break;
-    }
-    case METRPO_ENV_ANT: G[15 * LD + tid] -= w; cu = w * 1e-2f; break;
-    case METRPO_ENV_HUMANOID: G[(ns - 1) * LD + tid] += w * 2.0f * (xn[(ns - 1) * LD + tid] - 1.5f); cu = w * 2e-5f; break;
-    case METRPO_ENV_HOPPER: {
-        G[5 * LD + tid] -= w; cu = w * 0.01f;
-        if (0.45f - xn[0 * LD + tid] > 0.0f) G[0 * LD + tid] -= w * 10.0f;
-        const float a1 = xn[1 * LD + tid];
-        if (fabsf(a1) - 0.2f > 0.0f) G[1 * LD + tid] += w * 10.0f * (a1 > 0.0f ? 1.0f : -1.0f);
-        for (int i = 2; i < ns; ++i) { const float v = xn[i * LD + tid]; if (fabsf(v) - 100.0f > 0.0f) G[i * LD + tid] += w * (v > 0.0f ? 1.0f : -1.0f); }
-        break;
-    }
-    case METRPO_ENV_SNAKE: G[7 * LD + tid] -= w; cu = w * 1e-2f; break;
-    }
-    for (int d = 0; d < na; ++d) gU[d * LD + tid] = cu * u[d * LD + tid];
 }
 
 // STOCH ('bptt-stochastic'): the policy mean gets the noise of nz before the clip, u = clip(mean + eps exp(log_std)) (training.py:115-116);
@@ -168,38 +143,15 @@ __global__ void k_bptt_backward(ProblemDesc pd, const float* __restrict__ dynp, 
         }
         for (int i = 0; i < ns; ++i) e.X[i * LD + tid] = (e.S[i * LD + tid] - in_mean[i]) / in_std[i];
         for (int d = 0; d < na; ++d) e.X[(ns + d) * LD + tid] = (e.U[d * LD + tid] - in_mean[ns + d]) / in_std[ns + d];
-        {
-            const float* cur = e.X + pd.n_drop * LD; float* dst = e.DH;
-            for (int l = 0; l < dn.n_layers - 1; ++l) {
-                dense_col(pk + dn.w_off[l], pk + dn.b_off[l], dn.dims[l], dn.dims[l + 1], dn.act[l], cur, dst, LD, tid);
-                cur = dst; dst += dn.dims[l + 1] * LD;
-            }
-        }
+        net_hidden(dn, pk, e.X + pd.n_drop * LD, e.DH, LD, tid);
         // ---- adjoints: G = lambda_{t+1} + w dc/dx_next ;  gU_cost = w dc/du (kept in XN's place after use) -------------------
         float* G = e.LAM;                                       // lambda_{t+1} is consumed here
         float* gUc = e.X;                                       // the normalised input is dead after the forward recompute
         cost_adjoint(pd.env, ns, na, e.XN, e.U, w, gUc, G, LD, tid);
         // dynamics VJP: delta_out = diff_std * G ; back through the layers (relu masks from DH)
-        float* da = e.GA; float* db = e.GB;
-        for (int i = 0; i < ns; ++i) da[i * LD + tid] = diff_std[i] * G[i * LD + tid];
-        {
-            int off = 0;
-            for (int l = 1; l < dn.n_layers - 1; ++l) off += dn.dims[l];          // rows of the LAST hidden layer in DH
-            for (int l = dn.n_layers - 1; l >= 0; --l) {
-                dense_col_T(pk + dn.w_off[l], dn.dims[l], dn.dims[l + 1], da, db, LD, tid);
-                if (l > 0) {
-                    const float* h = e.DH + off * LD;                              // output of layer l-1 (post-activation)
-                    for (int j = 0; j < dn.dims[l]; ++j) {
-                        const float hv = h[j * LD + tid];
-                        const float dact = (dn.act[l - 1] == METRPO_ACT_RELU) ? (hv > 0.0f ? 1.0f : 0.0f)
-                                          : (dn.act[l - 1] == METRPO_ACT_TANH) ? (1.0f - hv * hv) : 1.0f;
-                        db[j * LD + tid] *= dact;
-                    }
-                    if (l > 1) off -= dn.dims[l - 1];
-                }
-                float* tmp = da; da = db; db = tmp;
-            }
-        }
+        for (int i = 0; i < ns; ++i) e.GA[i * LD + tid] = diff_std[i] * G[i * LD + tid];
+        float* da = net_vjp(dn, pk, e.DH, e.GA, e.GB, LD, tid);
+        float* db = (da == e.GA) ? e.GB : e.GA;
         // da = adjoint of the (dropped) normalised input [nin].  State part: residual + normaliser; action part -> gU
         for (int i = 0; i < ns; ++i) {
             float v = G[i * LD + tid];
@@ -214,26 +166,8 @@ __global__ void k_bptt_backward(ProblemDesc pd, const float* __restrict__ dynp, 
             if (active) GM[(((size_t)model * (T + 1) + t) * B + b) * na + d] = gm;
         }
         // policy input VJP: back through the layers with the stored activations
-        {
-            float* pa = db; float* pb = da;
-            int off = 0;
-            for (int l = 1; l < pn.n_layers - 1; ++l) off += pn.dims[l];          // rows of the last hidden layer in PH
-            for (int l = pn.n_layers - 1; l >= 0; --l) {
-                dense_col_T(theta + pn.w_off[l], pn.dims[l], pn.dims[l + 1], pa, pb, LD, tid);
-                if (l > 0) {
-                    const float* h = e.PH + off * LD;
-                    for (int j = 0; j < pn.dims[l]; ++j) {
-                        const float hv = h[j * LD + tid];
-                        const float dact = (pn.act[l - 1] == METRPO_ACT_TANH) ? (1.0f - hv * hv)
-                                          : (pn.act[l - 1] == METRPO_ACT_RELU) ? (hv > 0.0f ? 1.0f : 0.0f) : 1.0f;
-                        pb[j * LD + tid] *= dact;
-                    }
-                    if (l > 1) off -= pn.dims[l - 1];
-                }
-                float* tmp = pa; pa = pb; pb = tmp;
-            }
-            for (int i = 0; i < ns; ++i) e.LAM[i * LD + tid] = e.XN[i * LD + tid] + pa[i * LD + tid];       // lambda_t
-        }
+        const float* pa = net_vjp(pn, theta, e.PH, db, da, LD, tid);
+        for (int i = 0; i < ns; ++i) e.LAM[i * LD + tid] = e.XN[i * LD + tid] + pa[i * LD + tid];       // lambda_t
     }
 }
 

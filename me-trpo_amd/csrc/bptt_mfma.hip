@@ -10,23 +10,31 @@
 // so activations and deltas never leave registers between layers.  Constant factors are folded into the fragments: diff_std
 // into the first adjoint layer, 1/in_std and the column drop into the last one, which is split into a state part (rows = state
 // dims: lands in the layout of the residual path) and an action part (rows = action dims).
-// The forward dynamics head is dyn_head_mfma.h's (register-resident fragments; the layout is described there); adjoint fragments
-// and the policy's live in an LDS image shared by the 4 waves of a workgroup (same model).
-#include "dyn_head_mfma.h"
+// The forward dynamics head is dyn_head_mfma.h's (register-resident fragments; the layout is described there); its adjoint is
+// dyn_head_adjoint.h's DynHeadAdjoint and the policy's two tanh layers and input adjoint are pol_head_mfma.h's PolHeadAdjoint, both on
+// fragment tables in an LDS image shared by the 4 waves of a workgroup (same model).  What this file states itself: the image's
+// composition (DetL), the mean's last layer, the clip and its gate, and the cost adjoint in D layout (profiles/r28_score_bodies.txt:
+// factoring that block out cost its sibling kernels registers).
+#include "dyn_head_adjoint.h"
+#include "pol_head_mfma.h"
 
 enum { DET_FWD = 0, DET_BWD = 1 };
 
 template <int ENV>
 struct DetL {
     using C = Cfg<ENV, 64, 32>;
-    static constexpr int NS = C::NS, NA = C::NA, OUT_CB = C::OUT_CB, NS_KS = C::NS_KS, NIN_KS = C::NIN_KS;
-    static constexpr int RK = (NA < 4) ? NA : 4;                       // k-steps of the first policy-adjoint layer that are not padding
-    // LDS image (floats): fragment tables [k-step][col-block][64 lanes], then biases
-    static constexpr int O_PF0 = 0, O_PF1 = O_PF0 + NS_KS * 2 * 64, O_PF2 = O_PF1 + 8 * 2 * 64, O_PB2 = O_PF2 + 8 * 64,
-                         O_PB1 = O_PB2 + RK * 2 * 64, O_PB0 = O_PB1 + 8 * 2 * 64, O_DB2 = O_PB0 + 8 * OUT_CB * 64,
-                         O_DB1 = O_DB2 + 4 * OUT_CB * 4 * 64, O_DAS = O_DB1 + 16 * 4 * 64, O_DAA = O_DAS + 16 * OUT_CB * 64,
-                         O_BD0 = O_DAA + 16 * 64, O_BD1 = O_BD0 + 64, O_BD2 = O_BD1 + 64, O_BP0 = O_BD2 + 16 * OUT_CB,
-                         O_BP1 = O_BP0 + 32, O_BP2 = O_BP1 + 32, IMG = O_BP2 + 16;
+    using Pol = PolHeadAdjoint<C>;
+    using Adj = DynHeadAdjoint<C>;
+    static constexpr int NS = C::NS, NA = C::NA, OUT_CB = C::OUT_CB;
+    // LDS image (floats): the policy's fragment tables and hidden bias rows (pol_head_mfma.h) | the mean's last forward layer [k-step][64 lanes] and its
+    // bias row, this file's own | the dynamics adjoint tables (dyn_head_adjoint.h) | the three dynamics bias rows
+    static constexpr int O_PF2 = Pol::FLOATS, O_BP2 = O_PF2 + 8 * 64, O_ADJ = O_BP2 + 16, O_BD0 = O_ADJ + Adj::FLOATS, O_BD1 = O_BD0 + 64,
+                         O_BD2 = O_BD1 + 64, IMG = O_BD2 + 16 * OUT_CB;
+    static constexpr int LOC_P = O_ADJ - O_PF2, LOCAL = LOC_P + (IMG - O_BD0);       // the rows that k_det_mfma fills itself
+    static_assert(IMG == 64 * (2 * C::NS_KS + 16 + 8 + 2 * Pol::RK + 16 + 8 * OUT_CB)       // policy tables: PF0 PF1 PF2 PB2 PB1 PB0
+                         + 64 * (16 * OUT_CB + 64 + 16 * OUT_CB + 16)                    // dynamics adjoint tables: DB2 DB1 DAS DAA
+                         + 64 + 64 + 16 * OUT_CB + 32 + 32 + 16,                         // the six bias rows
+                  "the image holds what it held when this file laid out every table itself");
     static constexpr int WV = ((16 * NS * 2 + 16 * NA + 3) / 4) * 4;     // per wave: ST | NX | ACT
     static constexpr int TOTAL = IMG + 4 * WV;
 };
@@ -57,7 +65,7 @@ __global__ void __launch_bounds__(256, 2) k_det_mfma(int K, int B, int T, double
                                                     float* __restrict__ GM, double* __restrict__ cost_part, BpttNoise nz) {
     using L = DetL<ENV>;
     using C = typename L::C;
-    constexpr int NS = C::NS, NA = C::NA, NDROP = C::NDROP, DH = 64, PH = 32, OUT_CB = C::OUT_CB, NS_KS = C::NS_KS, RK = L::RK;
+    constexpr int NS = C::NS, NA = C::NA, OUT_CB = C::OUT_CB;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, q = lane >> 4;
@@ -67,38 +75,23 @@ __global__ void __launch_bounds__(256, 2) k_det_mfma(int K, int B, int T, double
     const float* __restrict__ pk = dynp + (size_t)model * C::PD;
     float* IMG = lds;
     float* ST = lds + L::IMG + wave * L::WV; float* NX = ST + 16 * NS; float* ACT = NX + 16 * NS;
-    const float* in_std = norm + (NS + NA);
-    const float* dstd_p = norm + 2 * (NS + NA) + NS;
 
-    // ---------------- LDS image: fragment tables (see header) and biases; each element written by one thread ----------------
-    for (int i = tid; i < L::IMG; i += 256) {
+    // ---------------- LDS image: the shared heads' tables, then this file's own rows; each element written by one thread ----------------
+    L::Pol::fill(IMG, theta, tid, 256);
+    L::Adj::fill(IMG + L::O_ADJ, pk, norm, tid, 256);
+    for (int j = tid; j < L::LOCAL; j += 256) {
+        const int i = (j < L::LOC_P) ? L::O_PF2 + j : L::O_BD0 + (j - L::LOC_P);
         float w = 0.0f;
         const int ln = i & 63, cc = ln & 15, qq = ln >> 4;
-        if (i < L::O_PF1) { const int f = i >> 6, s = f >> 1, cb = f & 1, in = 4 * s + qq; if (in < NS) w = theta[C::pW0 + in * PH + 16 * cb + cc]; }
-        else if (i < L::O_PF2) { const int f = (i - L::O_PF1) >> 6, kk = f >> 1, cb = f & 1; w = theta[C::pW1 + chained_in(kk, qq) * PH + 16 * cb + cc]; }
-        else if (i < L::O_PB2) { const int kk = (i - L::O_PF2) >> 6; if (cc < NA) w = theta[C::pW2 + chained_in(kk, qq) * NA + cc]; }
-        else if (i < L::O_PB1) { const int f = (i - L::O_PB2) >> 6, r = f >> 1, cb = f & 1, d = 4 * qq + r; if (d < NA) w = theta[C::pW2 + (16 * cb + cc) * NA + d]; }
-        else if (i < L::O_PB0) { const int f = (i - L::O_PB1) >> 6, kk = f >> 1, cb = f & 1; w = theta[C::pW1 + (16 * cb + cc) * PH + chained_in(kk, qq)]; }
-        else if (i < L::O_DB2) { const int f = (i - L::O_PB0) >> 6, kk = f / OUT_CB, cb = f % OUT_CB, dim = 16 * cb + cc; if (dim < NS) w = theta[C::pW0 + dim * PH + chained_in(kk, qq)]; }
-        else if (i < L::O_DB1) {                 // first adjoint layer of the dynamics: k-steps (cbd, r) over state dims, diff_std folded in
-            const int f = (i - L::O_DB2) >> 6, ks = f >> 2, cb = f & 3, dim = chained_in(ks, qq);
-            if (dim < NS) w = pk[C::dW2 + (16 * cb + cc) * NS + dim] * dstd_p[dim];
-        }
-        else if (i < L::O_DAS) { const int f = (i - L::O_DB1) >> 6, kk = f >> 2, cb = f & 3; w = pk[C::dW1 + (16 * cb + cc) * DH + chained_in(kk, qq)]; }
-        else if (i < L::O_DAA) {                 // last adjoint layer, state rows: column drop and 1/in_std folded in
-            const int f = (i - L::O_DAS) >> 6, kk = f / OUT_CB, cb = f % OUT_CB, dim = 16 * cb + cc;
-            if (dim >= NDROP && dim < NS) w = pk[C::dW0 + (dim - NDROP) * DH + chained_in(kk, qq)] / in_std[dim];
-        }
-        else if (i < L::O_BD0) { const int kk = (i - L::O_DAA) >> 6; if (cc < NA) w = pk[C::dW0 + (NS - NDROP + cc) * DH + chained_in(kk, qq)] / in_std[NS + cc]; }
+        if (i < L::O_BP2) { const int kk = (i - L::O_PF2) >> 6; if (cc < NA) w = theta[C::pW2 + chained_in(kk, qq) * NA + cc]; }
+        else if (i < L::O_ADJ) { const int d = i - L::O_BP2; if (d < NA) w = theta[C::pb2 + d]; }
         else if (i < L::O_BD1) w = pk[C::db0 + (i - L::O_BD0)];
         else if (i < L::O_BD2) w = pk[C::db1 + (i - L::O_BD1)];
-        else if (i < L::O_BP0) { const int u = i - L::O_BD2; if (u < NS) w = pk[C::db2 + u]; }
-        else if (i < L::O_BP1) w = theta[C::pb0 + (i - L::O_BP0)];
-        else if (i < L::O_BP2) w = theta[C::pb1 + (i - L::O_BP1)];
-        else { const int d = i - L::O_BP2; if (d < NA) w = theta[C::pb2 + d]; }
+        else { const int u = i - L::O_BD2; if (u < NS) w = pk[C::db2 + u]; }
         IMG[i] = w;
     }
-#define TAB2(off, ks, cb, ncb) IMG[(off) + (((ks) * (ncb)) + (cb)) * 64 + lane]
+    const typename L::Pol pol = {IMG, lane};
+    const typename L::Adj adj = {IMG + L::O_ADJ, lane};
     // ---------------- register-resident forward dynamics fragments ----------------
     DynHeadFrags<C, MODE == DET_FWD> head;                                   // the reverse sweep recomputes layers 0 and 1 only
     DynInNorm<C> in;
@@ -116,28 +109,7 @@ __global__ void __launch_bounds__(256, 2) k_det_mfma(int K, int B, int T, double
     f32x4 p0[2], p1[2], mu, h0[4], h1[4];
     int nsat[4] = {0, 0, 0, 0};                                              // STOCH forward: |u| == 1 count of (env c, dim 4q + r) over t
     auto step_forward = [&](int t) {
-        p0[0] = *(const f32x4*)&IMG[L::O_BP0 + 4 * q]; p0[1] = *(const f32x4*)&IMG[L::O_BP0 + 16 + 4 * q];
-#pragma unroll
-        for (int s = 0; s < NS_KS; ++s) {
-            const int f = 4 * s + q;
-            const float x = (f < NS) ? ST[c * NS + f] : 0.0f;
-            p0[0] = MFMA16(TAB2(L::O_PF0, s, 0, 2), x, p0[0]);
-            p0[1] = MFMA16(TAB2(L::O_PF0, s, 1, 2), x, p0[1]);
-        }
-        p1[0] = *(const f32x4*)&IMG[L::O_BP1 + 4 * q]; p1[1] = *(const f32x4*)&IMG[L::O_BP1 + 16 + 4 * q];
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) p0[cb][r] = tanh_fast(p0[cb][r]);
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
-            p1[0] = MFMA16(TAB2(L::O_PF1, kk, 0, 2), p0[kk >> 2][kk & 3], p1[0]);
-            p1[1] = MFMA16(TAB2(L::O_PF1, kk, 1, 2), p0[kk >> 2][kk & 3], p1[1]);
-        }
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) p1[cb][r] = tanh_fast(p1[cb][r]);
+        pol.hidden(p0, p1, ST, c);
         f32x4 m0 = *(const f32x4*)&IMG[L::O_BP2 + 4 * q], m1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kk = 0; kk < 8; kk += 2) {
@@ -266,37 +238,9 @@ __global__ void __launch_bounds__(256, 2) k_det_mfma(int K, int B, int T, double
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) { const int d = 4 * q + r; if (d < NA) gU[r] = cu * ACT[c * NA + d]; }
-            // ---- dynamics adjoint chain: d2 = W2.(diff_std G) * relu'(h1); d1 = W1.d2 * relu'(h0); gS += W0s.d1 ; gU += W0a.d1 ----
-            f32x4 d2[4], d1[4];
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) d2[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < 4 * OUT_CB; ++ks)
-#pragma unroll
-                for (int cb = 0; cb < 4; ++cb) d2[cb] = MFMA16(TAB2(L::O_DB2, ks, cb, 4), G[ks >> 2][ks & 3], d2[cb]);
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) {
-                d1[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) d2[cb][r] = (h1[cb][r] > 0.0f) ? d2[cb][r] : 0.0f;
-            }
-#pragma unroll
-            for (int kk = 0; kk < 16; ++kk)
-#pragma unroll
-                for (int cb = 0; cb < 4; ++cb) d1[cb] = MFMA16(TAB2(L::O_DB1, kk, cb, 4), d2[kk >> 2][kk & 3], d1[cb]);
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) d1[cb][r] = (h0[cb][r] > 0.0f) ? d1[cb][r] : 0.0f;
+            // ---- dynamics adjoint: gS = G + state rows of F^T G (the residual identity), gU += action rows ----
             f32x4 gS[OUT_CB];
-#pragma unroll
-            for (int cb = 0; cb < OUT_CB; ++cb) gS[cb] = G[cb];                       // residual connection x' = x + ...
-#pragma unroll
-            for (int kk = 0; kk < 16; ++kk) {
-#pragma unroll
-                for (int cb = 0; cb < OUT_CB; ++cb) gS[cb] = MFMA16(TAB2(L::O_DAS, kk, cb, OUT_CB), d1[kk >> 2][kk & 3], gS[cb]);
-                gU = MFMA16(IMG[L::O_DAA + kk * 64 + lane], d1[kk >> 2][kk & 3], gU);
-            }
+            adj.run(gS, gU, G, h0, h1);
             // ---- clip gate (tf.clip_by_value passes the gradient inside [min, max]) and the mean-adjoint output ----
             f32x4 gm;
 #pragma unroll
@@ -305,39 +249,13 @@ __global__ void __launch_bounds__(256, 2) k_det_mfma(int K, int B, int T, double
                 gm[r] = (d < NA && mu[r] >= -1.0f && mu[r] <= 1.0f) ? gU[r] : 0.0f;
                 if (d < NA && active) GM[(((size_t)model * (T + 1) + t) * B + b) * NA + d] = gm[r];
             }
-            // ---- policy input adjoint chain ----
-            f32x4 e1[2], e0[2];
-            e1[0] = e1[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int r = 0; r < RK; ++r) {
-                e1[0] = MFMA16(TAB2(L::O_PB2, r, 0, 2), gm[r], e1[0]);
-                e1[1] = MFMA16(TAB2(L::O_PB2, r, 1, 2), gm[r], e1[1]);
-            }
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb) {
-                e0[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) e1[cb][r] *= fmaf(-p1[cb][r], p1[cb][r], 1.0f);
-            }
-#pragma unroll
-            for (int kk = 0; kk < 8; ++kk) {
-                e0[0] = MFMA16(TAB2(L::O_PB1, kk, 0, 2), e1[kk >> 2][kk & 3], e0[0]);
-                e0[1] = MFMA16(TAB2(L::O_PB1, kk, 1, 2), e1[kk >> 2][kk & 3], e0[1]);
-            }
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) e0[cb][r] *= fmaf(-p0[cb][r], p0[cb][r], 1.0f);
-#pragma unroll
-            for (int kk = 0; kk < 8; ++kk)
-#pragma unroll
-                for (int cb = 0; cb < OUT_CB; ++cb) gS[cb] = MFMA16(TAB2(L::O_PB0, kk, cb, OUT_CB), e0[kk >> 2][kk & 3], gS[cb]);
+            // ---- policy input adjoint: gS += J_pi(x_t)^T gm ----
+            pol.run(gS, gm, p0, p1);
 #pragma unroll
             for (int cb = 0; cb < OUT_CB; ++cb) lam[cb] = gS[cb];                     // lambda_t
             wave_lds_sync();
         }
     }
-#undef TAB2
 }
 
 // fixed-order sum of the per-tile cost partials of one model

@@ -212,7 +212,7 @@ __device__ __forceinline__ float* mlp_col(const NetDesc& net, const float* __res
     return const_cast<float*>(cur);
 }
 
-// dout[j] = sum_i W[j][i] * din[i]   (W row-major n_in x n_out: the VJP of  out = in . W); shared by the BPTT sweeps (bptt.hip) and the
+// dout[j] = sum_i W[j][i] * din[i]   (W row-major n_in x n_out: the VJP of  out = in . W); net_vjp's step (below) and the
 // Jacobian rows of svg.hip
 __device__ __forceinline__ void dense_col_T(const float* __restrict__ W, int n_in, int n_out, const float* din, float* dout, int LD, int tid) {
     for (int j = 0; j < n_in; ++j) {
@@ -223,6 +223,43 @@ __device__ __forceinline__ void dense_col_T(const float* __restrict__ W, int n_i
         if (i < n_out) s0 = fmaf(w[i], din[i * LD + tid], s0);
         dout[j * LD + tid] = s0 + s1;
     }
+}
+
+// A net's hidden layers and its vector-Jacobian product in column layout: the reverse sweeps of bptt.hip, score_actions_grad.hip and
+// score_policy_actions_grad.hip, and the recompute of svg.hip's k_svg_jac.
+__host__ __device__ inline int net_hidden_rows(const NetDesc& n) {
+    int rows = 0;
+    for (int l = 1; l < n.n_layers; ++l) rows += n.dims[l];
+    return rows;
+}
+// the hidden layers of a net into `store` (all outputs kept; the output layer is not formed)
+__device__ __forceinline__ void net_hidden(const NetDesc& n, const float* __restrict__ params, const float* in, float* store, int LD, int tid) {
+    const float* cur = in; float* dst = store;
+    for (int l = 0; l < n.n_layers - 1; ++l) {
+        dense_col(params + n.w_off[l], params + n.b_off[l], n.dims[l], n.dims[l + 1], n.act[l], cur, dst, LD, tid);
+        cur = dst; dst += n.dims[l + 1] * LD;
+    }
+}
+// dout = W . (din * act'(h)) chains of one net, back from `da` (the adjoint of the net's output, n_out rows) to the adjoint of its input; `store` holds the
+// hidden layers' outputs in layer order.  Returns the buffer (da or db) that holds the result.
+__device__ __forceinline__ float* net_vjp(const NetDesc& n, const float* __restrict__ params, const float* store, float* da, float* db, int LD, int tid) {
+    int off = 0;
+    for (int l = 1; l < n.n_layers - 1; ++l) off += n.dims[l];                // rows of the LAST hidden layer in the store
+    for (int l = n.n_layers - 1; l >= 0; --l) {
+        dense_col_T(params + n.w_off[l], n.dims[l], n.dims[l + 1], da, db, LD, tid);
+        if (l > 0) {
+            const float* h = store + off * LD;                                 // output of layer l-1 (post-activation)
+            for (int j = 0; j < n.dims[l]; ++j) {
+                const float hv = h[j * LD + tid];
+                const float dact = (n.act[l - 1] == METRPO_ACT_RELU) ? (hv > 0.0f ? 1.0f : 0.0f)
+                                  : (n.act[l - 1] == METRPO_ACT_TANH) ? (1.0f - hv * hv) : 1.0f;
+                db[j * LD + tid] *= dact;
+            }
+            if (l > 1) off -= n.dims[l - 1];
+        }
+        float* tmp = da; da = db; db = tmp;
+    }
+    return da;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -246,6 +283,34 @@ __device__ __forceinline__ float env_cost(int env, int ns, int na, const float* 
     case METRPO_ENV_SNAKE: return -(xn[7 * LD + tid] - 1e-2f * 0.5f * su2);
     }
     return 0.0f;
+}
+
+// env_cost's adjoint: d(w cost)/du -> gU (written), d(w cost)/dx_next -> added into G.  The BPTT reverse sweep passes the step's weight, the gradient
+// kernels of the scorers w = -w_t for the gradient of the return.
+__device__ __forceinline__ void cost_adjoint(int env, int ns, int na, const float* xn, const float* u, float w, float* gU, float* G, int LD, int tid) {
+    float su2 = 0.0f;
+    for (int d = 0; d < na; ++d) { const float a = u[d * LD + tid]; su2 = fmaf(a, a, su2); }
+    float cu = 0.0f;                                         // gU[d] = cu * u[d]
+    switch (env) {
+    case METRPO_ENV_SWIMMER: G[5 * LD + tid] -= w; cu = w * 1e-2f * 2.0f / (float)na; break;
+    case METRPO_ENV_HALF_CHEETAH: {
+        const float inner = xn[9 * LD + tid] - 1e-1f * 0.5f * su2;
+        const float p = (inner >= -10.0f && inner <= 10.0f) ? 1.0f : 0.0f;       // tf.clip_by_value passes the gradient inside [min, max]
+        G[9 * LD + tid] -= w * p; cu = w * p * 1e-1f; break;
+    }
+    case METRPO_ENV_ANT: G[15 * LD + tid] -= w; cu = w * 1e-2f; break;
+    case METRPO_ENV_HUMANOID: G[(ns - 1) * LD + tid] += w * 2.0f * (xn[(ns - 1) * LD + tid] - 1.5f); cu = w * 2e-5f; break;
+    case METRPO_ENV_HOPPER: {
+        G[5 * LD + tid] -= w; cu = w * 0.01f;
+        if (0.45f - xn[0 * LD + tid] > 0.0f) G[0 * LD + tid] -= w * 10.0f;
+        const float a1 = xn[1 * LD + tid];
+        if (fabsf(a1) - 0.2f > 0.0f) G[1 * LD + tid] += w * 10.0f * (a1 > 0.0f ? 1.0f : -1.0f);
+        for (int i = 2; i < ns; ++i) { const float v = xn[i * LD + tid]; if (fabsf(v) - 100.0f > 0.0f) G[i * LD + tid] += w * (v > 0.0f ? 1.0f : -1.0f); }
+        break;
+    }
+    case METRPO_ENV_SNAKE: G[7 * LD + tid] -= w; cu = w * 1e-2f; break;
+    }
+    for (int d = 0; d < na; ++d) gU[d * LD + tid] = cu * u[d * LD + tid];
 }
 
 __device__ __forceinline__ bool env_is_done(int env, int ns, const float* xn, int LD, int tid) {

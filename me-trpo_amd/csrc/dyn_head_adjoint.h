@@ -3,9 +3,8 @@
 // activations h0, h1 of the step, it returns
 //   gS = G + (state rows of F^T G)       the residual identity x' = x + ... is the initial value of the last chain
 //   gU += (action rows of F^T G)         lane (e, q), register r = action dim 4 q + r of env e
-// with F the head's Jacobian including both normalisers and the column drop.  This restates the dynamics part of k_det_mfma<DET_BWD> (bptt_mfma.hip:
-// its O_DB2 / O_DB1 / O_DAS / O_DAA fragment tables and the three chains behind the cost adjoint) for score_actions_grad.hip; bptt_mfma.hip keeps its
-// own copy until the two are unified with a code-object comparison.
+// with F the head's Jacobian including both normalisers and the column drop.  Users: the reverse sweeps k_det_mfma<DET_BWD> (bptt_mfma.hip), k_sagr<.., SAGR_BWD>
+// (score_actions_grad.hip) and k_spag_bwd (score_policy_actions_grad.hip); each places the table in its own LDS image and calls fill() in front of its barrier.
 //   adjoint   dX^T[in][env] = W . dH^T      A = W fragments (an LDS table shared by the waves of a workgroup), B = deltas in D layout of the next layer
 // Constant factors are folded into the fragments: diff_std into the first adjoint layer, 1/in_std and the column drop into the last one, which is split
 // into a state part (rows = state dims: lands in the layout of the residual path) and an action part (rows = action dims).  relu'(h) = [h > 0].

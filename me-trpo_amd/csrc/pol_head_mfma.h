@@ -1,7 +1,8 @@
 // The mean net of the 2 x 32 tanh policy ([rllab] GaussianMLPPolicy.get_actions, the mean half) for a tile of 16 envs, TRANSPOSED on
-// v_mfma_f32_16x16x4_f32 in the fragment layout of dyn_head_mfma.h: the statements of rollout_mfma.hip's policy chain (its one-time fragment and bias
-// load and its per-step chain, tanh_fast and the two accumulators of the last layer included) stated once as a type.  score_policy_actions.hip is
-// its first user; the kernels that carry their own copy of the chain keep it.
+// v_mfma_f32_16x16x4_f32 in the fragment layout of dyn_head_mfma.h: the one-time fragment and bias load and the per-step chain (tanh_fast and the two
+// accumulators of the last layer included) of a wave that evaluates the whole policy itself, stated once as a type.  Users: k_rollout_mfma (rollout_mfma.hip),
+// k_score_policy_actions (score_policy_actions.hip) and k_spag_fwd (score_policy_actions_grad.hip).  The kernels that pipeline the chain differently
+// (rollout_coop_body.h, rollout_resident.hip, big_prepost.h, policy_chain3.h, det_gemm.hip) state their own.
 //   PolWaveHead     a wave's policy: weight fragments in registers (swimmer 6 + 16 + 8, Ant 16 + 16 + 8), its three bias rows in LDS;
 //                   mean() = the mean's action dims 4 q .. 4 q + 3 of env e in D layout
 //   NoiseTile       the tile's noise block, double-buffered in LDS and committed unclipped (ActTile's prefetch)
@@ -105,9 +106,9 @@ struct NoiseTile : ActTile<C> {
 };
 
 // The policy's INPUT adjoint for a tile of 16 envs, on the same transposed chains: given the adjoint gm of the (pre-clip) mean (D layout: register r of lane
-// (e, q) is action dim 4 q + r of env e) it adds J_pi(s)^T gm into gS (D layout of the state, as DynHeadAdjoint returns it).  This restates the policy part
-// of k_det_mfma<DET_BWD> (bptt_mfma.hip: its O_PF0 / O_PF1 forward and O_PB2 / O_PB1 / O_PB0 adjoint fragment tables, the recomputed hidden layers and the
-// three chains behind the clip gate) for score_policy_actions_grad.hip; bptt_mfma.hip keeps its own copy (the note in dyn_head_adjoint.h).
+// (e, q) is action dim 4 q + r of env e) it adds J_pi(s)^T gm into gS (D layout of the state, as DynHeadAdjoint returns it).  Users: k_det_mfma (bptt_mfma.hip:
+// both sweeps take hidden() as the policy's two tanh layers, and form the mean's last layer from a table of their own behind this image; the reverse sweep
+// calls run() behind the clip gate) and k_spag_bwd (score_policy_actions_grad.hip).
 //   hidden()  p0, p1 = the two tanh layers of env e from its LDS state row: PolWaveHead::mean's statements on LDS fragments (the mean itself is not formed)
 //   run()     e1 = W2 . gm * (1 - p1^2);  e0 = W1 . e1 * (1 - p0^2);  gS += W0 . e0
 // The fragment tables and the two hidden bias rows are one LDS image shared by the waves of a workgroup.

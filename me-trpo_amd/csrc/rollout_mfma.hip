@@ -7,12 +7,12 @@
 //     (K <= 8 waves).  Every wave also evaluates the (tiny) policy redundantly, so the only
 //     cross-wave traffic is the K head outputs, exchanged through LDS with ONE barrier per step.
 //   * every layer, dynamics and policy, is computed TRANSPOSED on v_mfma_f32_16x16x4_f32 in the fragment layout of dyn_head_mfma.h (the dynamics head
-//     is that header's; the policy chain follows the same conventions): activations never leave registers between layers, numerics are plain fp32.
+//     is that header's, the policy's mean net is pol_head_mfma.h's PolWaveHead): activations never leave registers between layers, numerics are plain fp32.
 //   * all weights of the wave's head + the policy are register-resident for the whole rollout
 //     (~120 VGPRs); biases live in LDS and enter as the MFMA C operand.
 //   * state of the tile is kept per wave in LDS in [env][ns] order == the global layout of one
 //     time step of the trajectory, so the obs store is a fully coalesced linear copy.
-#include "dyn_head_mfma.h"
+#include "pol_head_mfma.h"
 #include <cstdlib>
 
 template <int ENV, int DH, int PH>
@@ -35,38 +35,19 @@ __global__ void __launch_bounds__(512) k_rollout_mfma(RolloutK r, int K, const f
     const float* __restrict__ pk = dynp + (size_t)wave * C::PD;
     DynHeadFrags<C> head;
     head.load(pk, e, q);
-    float wp0[C::NS_KS][C::PH_CB], wp1[C::PH_CB * 4][C::PH_CB], wp2[C::PH_CB * 4];
-#pragma unroll
-    for (int s = 0; s < C::NS_KS; ++s)
-#pragma unroll
-        for (int cb = 0; cb < C::PH_CB; ++cb) {
-            const int i = 4 * s + q, o = 16 * cb + e;
-            wp0[s][cb] = (i < NS && o < PH) ? theta[C::pW0 + i * PH + o] : 0.0f;
-        }
-#pragma unroll
-    for (int kk = 0; kk < C::PH_CB * 4; ++kk) {
-        const int i = chained_in(kk, q);
-#pragma unroll
-        for (int cb = 0; cb < C::PH_CB; ++cb) {
-            const int o = 16 * cb + e;
-            wp1[kk][cb] = (i < PH && o < PH) ? theta[C::pW1 + i * PH + o] : 0.0f;
-        }
-        wp2[kk] = (i < PH && e < NA) ? theta[C::pW2 + i * NA + e] : 0.0f;
-    }
     for (int i = lane; i < C::BD; i += 64) {
         W[C::W_BD0 + i] = (i < DH) ? pk[C::db0 + i] : 0.0f;
         W[C::W_BD1 + i] = (i < DH) ? pk[C::db1 + i] : 0.0f;
     }
     for (int i = lane; i < NSP; i += 64) W[C::W_BD2 + i] = (i < NS) ? pk[C::db2 + i] : 0.0f;
-    for (int i = lane; i < C::BP; i += 64) {
-        W[C::W_BP0 + i] = (i < PH) ? theta[C::pb0 + i] : 0.0f;
-        W[C::W_BP1 + i] = (i < PH) ? theta[C::pb1 + i] : 0.0f;
-    }
-    if (lane < 16) W[C::W_BP2 + lane] = (lane < NA) ? theta[C::pb2 + lane] : 0.0f;
-    // per-lane constants: policy sigma for its 4 action dims, the normalisers of its k-step features and output dims
+    // per-lane constants: policy sigma for its 4 action dims and the policy's fragments (its bias rows -> LDS), the normalisers of its k-step
+    // features and output dims.  pol.load stands here on purpose: the compiler's schedule of the step loop depends on its place among these
+    // statements (in front of the dynamics bias stores the kernel is 1.2 % slower: profiles/r31_shared_heads.txt)
     float sig[4];
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) sig[rr] = (4 * q + rr < NA) ? expf(fmaxf(theta[C::pLS + 4 * q + rr], LOG_MIN_STD)) : 0.0f;
+    PolWaveHead<C> pol;
+    pol.load(theta, W + C::W_BP0, W + C::W_BP1, W + C::W_BP2, lane);
     DynInNorm<C> in;
     DynOutNorm<C> out;
     in.load(norm, q);
@@ -102,37 +83,7 @@ __global__ void __launch_bounds__(512) k_rollout_mfma(RolloutK r, int K, const f
             for (int i = lane; i < lim; i += 64) r.obs[base + i] = ST[i];
         }
         // ---- policy.get_actions: mean = MLP(s), a = mean + exp(log_std) * eps ----------------------
-        f32x4 p0[C::PH_CB], p1[C::PH_CB];
-#pragma unroll
-        for (int cb = 0; cb < C::PH_CB; ++cb) p0[cb] = *(const f32x4*)&W[C::W_BP0 + 16 * cb + 4 * q];
-#pragma unroll
-        for (int s = 0; s < C::NS_KS; ++s) {
-            const int f = 4 * s + q;
-            const float x = (f < NS) ? ST[e * NS + f] : 0.0f;
-#pragma unroll
-            for (int cb = 0; cb < C::PH_CB; ++cb) p0[cb] = MFMA16(wp0[s][cb], x, p0[cb]);
-        }
-#pragma unroll
-        for (int cb = 0; cb < C::PH_CB; ++cb) {
-            p1[cb] = *(const f32x4*)&W[C::W_BP1 + 16 * cb + 4 * q];
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) p0[cb][rr] = tanh_fast(p0[cb][rr]);
-        }
-#pragma unroll
-        for (int kk = 0; kk < C::PH_CB * 4; ++kk)
-#pragma unroll
-            for (int cb = 0; cb < C::PH_CB; ++cb) p1[cb] = MFMA16(wp1[kk][cb], p0[kk >> 2][kk & 3], p1[cb]);
-#pragma unroll
-        for (int cb = 0; cb < C::PH_CB; ++cb)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) p1[cb][rr] = tanh_fast(p1[cb][rr]);
-        f32x4 m0 = *(const f32x4*)&W[C::W_BP2 + 4 * q], m1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < C::PH_CB * 4; kk += 2) {              // two accumulators: 40-cycle dependent latency
-            m0 = MFMA16(wp2[kk], p1[kk >> 2][kk & 3], m0);
-            m1 = MFMA16(wp2[kk + 1], p1[(kk + 1) >> 2][(kk + 1) & 3], m1);
-        }
-        const f32x4 mu = m0 + m1;
+        const f32x4 mu = pol.mean(ST, e);
         const uint4 dstep = rng_draw(r.seed, genv, r.t0 + t, RNG_STEP, 0);
         float z[4] = {0.f, 0.f, 0.f, 0.f};
         if (!r.determ && r.eps == nullptr) {            // lane q owns action dims 4q..4q+3 = chunks 2q, 2q+1 (chunk 0 = dstep)

@@ -22,7 +22,7 @@
 //   gathered per row (a tile may straddle two start states).
 //
 // Generic path (every other shape, and force_generic): k_sagr_gen_fwd / k_sagr_gen_bwd, one thread per (candidate, head) with activations in LDS
-// columns (sact_sum.h: GradBufs, net_hidden, net_vjp, sagr_cost_adjoint) -- k_bptt_forward / k_bptt_backward (bptt.hip) with the policy removed; block size by
+// columns (sact_sum.h: GradBufs; device_common.h: net_hidden, net_vjp, cost_adjoint) -- k_bptt_forward / k_bptt_backward (bptt.hip) with the policy removed; block size by
 // lds_block_size (metrpo_internal.h).  Same outputs, workspace, chunking.
 //
 // Terminal value (metrpo_set_terminal_value; sact_sum.h: TermVal): the forward sweeps add gamma^T alive_T V(s_T) to the sum behind the loop (score_actions.hip's
@@ -347,7 +347,7 @@ __global__ void k_sagr_gen_bwd(ProblemDesc pd, SagrK r, const float* __restrict_
         // ---- adjoints of the return: G = lambda_t+1 - w dc/dx_next; gU_cost = -w dc/du (in X's place: the normalised input is dead) ----
         float* G = e.LAM;
         float* gUc = e.X;
-        sagr_cost_adjoint(pd.env, ns, na, e.XN, e.U, -w, gUc, G, LD, tid);
+        cost_adjoint(pd.env, ns, na, e.XN, e.U, -w, gUc, G, LD, tid);
         for (int i = 0; i < ns; ++i) e.GA[i * LD + tid] = diff_std[i] * G[i * LD + tid];
         const float* da = net_vjp(dn, pk, e.DH, e.GA, e.GB, LD, tid);
         // da = adjoint of the (dropped) normalised input [nin].  Action part -> the gated gradient; state part: residual + normaliser -> lambda_t

@@ -22,7 +22,7 @@
 //   forward sweep computes rows of a later chunk that share its last tile and drops them, so chunking changes no bit.
 //
 // Generic path (every other shape, and force_generic): k_spag_gen_fwd / k_spag_gen_bwd, one thread per (candidate, head) with activations in LDS
-// columns -- k_sagr_gen_fwd / k_sagr_gen_bwd with the policy in the loop (both on sact_sum.h's GradBufs, net_hidden, net_vjp and sagr_cost_adjoint): the forward is k_policy_actions' and k_step's arithmetic (rollout_generic.hip;
+// columns -- k_sagr_gen_fwd / k_sagr_gen_bwd with the policy in the loop (both on sact_sum.h's GradBufs and device_common.h's net_hidden, net_vjp and cost_adjoint): the forward is k_policy_actions' and k_step's arithmetic (rollout_generic.hip;
 // sigma by __expf as there), so ret, len and act_out carry the bits of metrpo_score_policy_actions' generic path; the reverse is k_bptt_backward's policy
 // VJP (bptt.hip) behind the clip gate.  Block size by lds_block_size (metrpo_internal.h).  Same outputs, workspace, chunking.
 //
@@ -426,7 +426,7 @@ __global__ void k_spag_gen_bwd(ProblemDesc pd, SpagK r, const float* __restrict_
         // ---- adjoints of the return: G = lambda_t+1 - w dc/dx_next; gU_cost = -w dc/du (in X's place: the normalised input is dead) ----
         float* G = e.LAM;
         float* gUc = e.X;
-        sagr_cost_adjoint(pd.env, ns, na, e.XN, e.U, -w, gUc, G, LD, tid);
+        cost_adjoint(pd.env, ns, na, e.XN, e.U, -w, gUc, G, LD, tid);
         for (int i = 0; i < ns; ++i) e.GA[i * LD + tid] = diff_std[i] * G[i * LD + tid];
         float* da = net_vjp(dn, pk, e.DH, e.GA, e.GB, LD, tid);
         float* db = (da == e.GA) ? e.GB : e.GA;

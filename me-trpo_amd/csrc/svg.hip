@@ -77,13 +77,7 @@ __global__ void k_svg_jac(ProblemDesc pd, const float* __restrict__ params, cons
     } else {
         for (int i = 0; i < ns; ++i) IN[i * LD + tid] = OBSZ[(size_t)S * ns + i];
     }
-    {
-        const float* cur = IN; float* dst = H;
-        for (int l = 0; l < L - 1; ++l) {
-            dense_col(params + net.w_off[l], params + net.b_off[l], net.dims[l], net.dims[l + 1], net.act[l], cur, dst, LD, tid);
-            cur = dst; dst += net.dims[l + 1] * LD;
-        }
-    }
+    net_hidden(net, params, IN, H, LD, tid);
     int off = 0;                                                   // rows of the LAST hidden layer in H
     for (int l = 1; l < L - 1; ++l) off += net.dims[l];
     {
