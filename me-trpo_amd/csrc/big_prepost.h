@@ -1,11 +1,13 @@
 // Pre-step (policy.get_actions + clip + normalise / drop -> X) and closing of a step (k_big_post's work) of the step-wise rollout paths, as
 // WAVE-level device functions: one wave = one 16-env tile.  Shared by the launch-per-step kernels of rollout_gemm.hip (k_big_pre_mfma) and the
 // persistent stream-K rollout (mlp_persist.h), which runs them inside its own launch for the row block whose last tile it just finished -- same
-// arithmetic in the same order, so the trajectories of both paths are bit for bit the same (tests/test_gpu_persist.py).
+// arithmetic in the same order, so the trajectories of both paths are bit for bit the same (tests/test_gpu_persist.py).  The policy's fragment image and
+// its mean chain are not stated here: P2 (policy_chain2.h), shared with det_gemm.hip and the post roles of rollout_resident.hip.
 // Reference: samplers/vectorized_sampler.py:45-116 (policy.get_actions, vec_env.step), env_helpers.py:597-635 (step: clip, selection over the heads,
 // reward, done, reset), training.py:228,146-151 (input normalisation, dropped columns), training.py:257 (de-normalise + residual).
 #pragma once
 #include "mfma_common.h"
+#include "policy_chain2.h"
 
 struct BigState { float* S; int* ts; int* cur_model; float* X; float* U; float* HA; float* HB; float* OUT; float* PART;
                   int ldx;
@@ -168,26 +170,8 @@ __device__ __forceinline__ void big_close_step(const ProblemDesc& pd, const Roll
 }
 
 
-// ---- the pre-step of the 2 x 32 tanh policies (every shipped params file except Humanoid) as a transposed MFMA chain, one wave per 16-env tile ----
-// LDS image of the policy (floats): W0 fragments [NS_KS][2][64] | W1 fragments [8][2][64] | Wout fragments [8][64] | b0 [32] | b1 [32] | bout [16]
-template <int ENV> struct PreImg {
-    using C = Cfg<ENV, 64, 32>;
-    static constexpr int NS = C::NS, NA = C::NA, PH = 32, NS_KS = C::NS_KS;
-    static constexpr int O_PF1 = NS_KS * 2 * 64, O_PF2 = O_PF1 + 16 * 64, O_B0 = O_PF2 + 8 * 64, O_B1 = O_B0 + 32, O_B2 = O_B1 + 32, IMG = O_B2 + 16;
-    // value of image entry i (a gather from the flat policy vector, rllab order)
-    static __device__ __forceinline__ float entry(const float* __restrict__ theta, int i) {
-        float w = 0.0f;
-        const int ln = i & 63, cc = ln & 15, qq = ln >> 4;
-        if (i < O_PF1) { const int f = i >> 6, s_ = f >> 1, cb = f & 1, in = 4 * s_ + qq; if (in < NS) w = theta[C::pW0 + in * PH + 16 * cb + cc]; }
-        else if (i < O_PF2) { const int f = (i - O_PF1) >> 6, kk = f >> 1, cb = f & 1; w = theta[C::pW1 + (16 * (kk >> 2) + 4 * qq + (kk & 3)) * PH + 16 * cb + cc]; }
-        else if (i < O_B0) { const int kk = (i - O_PF2) >> 6; if (cc < NA) w = theta[C::pW2 + (16 * (kk >> 2) + 4 * qq + (kk & 3)) * NA + cc]; }
-        else if (i < O_B1) w = theta[C::pb0 + (i - O_B0)];
-        else if (i < O_B2) w = theta[C::pb1 + (i - O_B1)];
-        else if (i < IMG) { const int d = i - O_B2; if (d < NA) w = theta[C::pb2 + d]; }
-        return w;
-    }
-};
-
+// ---- the pre-step of the 2 x 32 tanh policies (every shipped params file except Humanoid) as a transposed MFMA chain, one wave per 16-env tile: the
+// fragment image and the chain are P2<Cfg<ENV, 64, 32>> (policy_chain2.h) ----
 // what the END of a pre-step needs that depends on nothing computed in it: loaded / drawn up front, while the loads of the closing part are under way
 template <int ENV> struct PreLane {
     static constexpr int NSQ = (Cfg<ENV, 64, 32>::NS + 3) / 4;
@@ -246,47 +230,16 @@ template <bool SC1> __device__ __forceinline__ void store_x(float* p, float v) {
     else *p = v;
 }
 
-// Second half: the policy chain on the state tile ST (30 matrix instructions; img = the PreImg<ENV> image in LDS), a = mean + sigma z, clip, act / mean / U and
+// Second half: the policy chain on the state tile ST (P2::mean_tile, 30 matrix instructions; img = the P2 image in LDS), a = mean + sigma z, clip, act / mean / U and
 // the normalised, dropped input row X of step t.
 template <int ENV, bool SC1X>
 __device__ __forceinline__ void big_pre_tail(const RolloutK& r, int t, const BigState& st, const float* img, const float* ST, int b0, int lane, const PreLane<ENV>& pl) {
     using C = Cfg<ENV, 64, 32>;
-    using IM = PreImg<ENV>;
-    constexpr int NS = C::NS, NA = C::NA, NDROP = C::NDROP, NS_KS = C::NS_KS, NSQ = PreLane<ENV>::NSQ;
-    constexpr int O_PF1 = IM::O_PF1, O_PF2 = IM::O_PF2, O_B0 = IM::O_B0, O_B1 = IM::O_B1, O_B2 = IM::O_B2;
+    constexpr int NS = C::NS, NA = C::NA, NDROP = C::NDROP, NSQ = PreLane<ENV>::NSQ;
     const int c = lane & 15, q = lane >> 4, b = b0 + c;
     const bool active = b < r.B;
     const int tt = t + RK_TOFF(r, b);
-    f32x4 p0[2], p1[2];
-    p0[0] = *(const f32x4*)&img[O_B0 + 4 * q]; p0[1] = *(const f32x4*)&img[O_B0 + 16 + 4 * q];
-#pragma unroll
-    for (int s_ = 0; s_ < NS_KS; ++s_) {
-        const int f = 4 * s_ + q;
-        const float x = (f < NS) ? ST[c * NS + f] : 0.0f;
-        p0[0] = MFMA16(img[(s_ * 2 + 0) * 64 + lane], x, p0[0]);
-        p0[1] = MFMA16(img[(s_ * 2 + 1) * 64 + lane], x, p0[1]);
-    }
-    p1[0] = *(const f32x4*)&img[O_B1 + 4 * q]; p1[1] = *(const f32x4*)&img[O_B1 + 16 + 4 * q];
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) p0[cb][rr] = tanh_fast(p0[cb][rr]);
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk) {
-        p1[0] = MFMA16(img[O_PF1 + (kk * 2 + 0) * 64 + lane], p0[kk >> 2][kk & 3], p1[0]);
-        p1[1] = MFMA16(img[O_PF1 + (kk * 2 + 1) * 64 + lane], p0[kk >> 2][kk & 3], p1[1]);
-    }
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) p1[cb][rr] = tanh_fast(p1[cb][rr]);
-    f32x4 m0 = *(const f32x4*)&img[O_B2 + 4 * q], m1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kk = 0; kk < 8; kk += 2) {
-        m0 = MFMA16(img[O_PF2 + kk * 64 + lane], p1[kk >> 2][kk & 3], m0);
-        m1 = MFMA16(img[O_PF2 + (kk + 1) * 64 + lane], p1[(kk + 1) >> 2][(kk + 1) & 3], m1);
-    }
-    const f32x4 mu = m0 + m1;
+    const f32x4 mu = P2<C>::mean_tile(img, ST, lane);
     if (!active) return;
     const size_t tb = (size_t)tt * RK_STRIDE(r) + RK_ENV(r, b);
     // state part of the normalised, dropped input: lane (c, q) writes its dims q, q + 4, ...

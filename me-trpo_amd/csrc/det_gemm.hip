@@ -9,6 +9,7 @@
 //                  mean-adjoint output, policy input VJP)
 #include "gemm_mfma.h"
 #include "mfma_common.h"
+#include "policy_chain2.h"
 #include "policy_chain3.h"
 
 struct DgState {
@@ -61,13 +62,13 @@ __global__ void k_dg_pre(ProblemDesc pd, int B, const float* __restrict__ theta,
 }
 
 // MFMA variant of k_dg_pre for the 2x32 tanh policies: a wave evaluates the policy of a 16-row tile of one model as the transposed MFMA
-// chain of the fused kernels (30 MFMAs) instead of 64 threads walking three dense layers each.  grid = (ceil(B/64), K) blocks of 4 waves.
+// chain of policy_chain2.h (P2: image, fill and the 30 MFMAs) instead of 64 threads walking three dense layers each.  grid = (ceil(B/64), K) blocks of 4 waves.
 template <int ENV, bool STOCH>
 __global__ void __launch_bounds__(256) k_dg_pre_mfma(ProblemDesc pd, int B, const float* __restrict__ theta, const float* __restrict__ norm,
                                                      const float* __restrict__ xs_t, long long xs_model_stride, DgState st, BpttNoise nz, int t) {
     using C = Cfg<ENV, 64, 32>;
-    constexpr int NS = C::NS, NA = C::NA, NDROP = C::NDROP, NIN = C::NIN, PH = 32, NS_KS = C::NS_KS;
-    constexpr int O_PF1 = NS_KS * 2 * 64, O_PF2 = O_PF1 + 16 * 64, O_B0 = O_PF2 + 8 * 64, O_B1 = O_B0 + 32, O_B2 = O_B1 + 32, IMG = O_B2 + 16;
+    using PC = P2<C>;
+    constexpr int NS = C::NS, NA = C::NA, NDROP = C::NDROP, NIN = C::NIN, IMG = PC::IMG;
     __shared__ __attribute__((aligned(16))) float lds[IMG + 4 * 16 * NS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, q = lane >> 4;
@@ -75,17 +76,7 @@ __global__ void __launch_bounds__(256) k_dg_pre_mfma(ProblemDesc pd, int B, cons
     const int b0 = (blockIdx.x * 4 + wave) * 16, b = b0 + c;
     const bool active = b < B;
     float* ST = lds + IMG + wave * 16 * NS;
-    for (int i = tid; i < IMG; i += 256) {
-        float w = 0.0f;
-        const int ln = i & 63, cc = ln & 15, qq = ln >> 4;
-        if (i < O_PF1) { const int f = i >> 6, s_ = f >> 1, cb = f & 1, in = 4 * s_ + qq; if (in < NS) w = theta[C::pW0 + in * PH + 16 * cb + cc]; }
-        else if (i < O_PF2) { const int f = (i - O_PF1) >> 6, kk = f >> 1, cb = f & 1; w = theta[C::pW1 + (16 * (kk >> 2) + 4 * qq + (kk & 3)) * PH + 16 * cb + cc]; }
-        else if (i < O_B0) { const int kk = (i - O_PF2) >> 6; if (cc < NA) w = theta[C::pW2 + (16 * (kk >> 2) + 4 * qq + (kk & 3)) * NA + cc]; }
-        else if (i < O_B1) w = theta[C::pb0 + (i - O_B0)];
-        else if (i < O_B2) w = theta[C::pb1 + (i - O_B1)];
-        else { const int d = i - O_B2; if (d < NA) w = theta[C::pb2 + d]; }
-        lds[i] = w;
-    }
+    PC::fill(lds, theta, tid, 256);
     const size_t row0 = (size_t)k * B + b0;
     const float* src = (xs_t != nullptr) ? xs_t + (size_t)k * xs_model_stride + (size_t)b0 * NS : st.S + row0 * NS;
     const int lim = min(16, max(0, B - b0)) * NS;
@@ -95,36 +86,7 @@ __global__ void __launch_bounds__(256) k_dg_pre_mfma(ProblemDesc pd, int B, cons
         if (xs_t != nullptr && i < lim) st.S[row0 * NS + i] = v;
     }
     __syncthreads();
-    f32x4 p0[2], p1[2];
-    p0[0] = *(const f32x4*)&lds[O_B0 + 4 * q]; p0[1] = *(const f32x4*)&lds[O_B0 + 16 + 4 * q];
-#pragma unroll
-    for (int s_ = 0; s_ < NS_KS; ++s_) {
-        const int f = 4 * s_ + q;
-        const float x = (f < NS) ? ST[c * NS + f] : 0.0f;
-        p0[0] = MFMA16(lds[(s_ * 2 + 0) * 64 + lane], x, p0[0]);
-        p0[1] = MFMA16(lds[(s_ * 2 + 1) * 64 + lane], x, p0[1]);
-    }
-    p1[0] = *(const f32x4*)&lds[O_B1 + 4 * q]; p1[1] = *(const f32x4*)&lds[O_B1 + 16 + 4 * q];
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) p0[cb][rr] = tanh_fast(p0[cb][rr]);
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk) {
-        p1[0] = MFMA16(lds[O_PF1 + (kk * 2 + 0) * 64 + lane], p0[kk >> 2][kk & 3], p1[0]);
-        p1[1] = MFMA16(lds[O_PF1 + (kk * 2 + 1) * 64 + lane], p0[kk >> 2][kk & 3], p1[1]);
-    }
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) p1[cb][rr] = tanh_fast(p1[cb][rr]);
-    f32x4 m0 = *(const f32x4*)&lds[O_B2 + 4 * q], m1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kk = 0; kk < 8; kk += 2) {
-        m0 = MFMA16(lds[O_PF2 + kk * 64 + lane], p1[kk >> 2][kk & 3], m0);
-        m1 = MFMA16(lds[O_PF2 + (kk + 1) * 64 + lane], p1[(kk + 1) >> 2][(kk + 1) & 3], m1);
-    }
-    f32x4 mu = m0 + m1;
+    f32x4 mu = PC::mean_tile(lds, ST, lane);
     if (!active) return;
     if (STOCH && 4 * q < NA) {
         float e[4];

@@ -69,7 +69,7 @@ enum { SKP_HALT = 0x40000000, SKP_NOHALT = 0x7fffffff };      // ready-flag valu
 enum { SKP_NCLOSE = 8 };                           // most closing workgroups of a launch (SkpArgs::nclose of them: blockIdx 0 .. nclose - 1, on different XCDs)
 
 // Step t closed and step t + 1 prepared for the 128 envs of row block rb, by all 8 waves of a closing workgroup: the wave functions of the launch-per-step
-// pre-kernel (big_prepost.h).  scratch: [8][16][NS] floats of LDS state tiles; img: the policy image (PreImg<ENV>).
+// pre-kernel (big_prepost.h).  scratch: [8][16][NS] floats of LDS state tiles; img: the policy image (P2, policy_chain2.h).
 template <int ENV>
 __device__ __forceinline__ void skp_close_and_prepare(const SkpPost* __restrict__ pp, int t, int rb, const float* img, float* scratch, int* xflag,
                                                       unsigned long long* cnt_t = nullptr) {
@@ -102,12 +102,12 @@ __device__ __forceinline__ void skp_close_and_prepare(const SkpPost* __restrict_
 // for nothing but arrival counters (whose tiles need only flags this closer raised a step earlier): no cycle, whatever the dispatch order of the compute workgroups.
 template <int ENV>
 __device__ __forceinline__ void skp_closer_role(const SkpArgs& p, float* lds) {
-    using IM = PreImg<ENV>;
+    using IM = P2<Cfg<ENV, 64, 32>>;
     float* const img = lds;
     float* const scratch = lds + IM::IMG;
     int* const sh = (int*)(scratch + 8 * 16 * Cfg<ENV, 64, 32>::NS);
     const int tid = threadIdx.x;
-    for (int k = tid; k < IM::IMG; k += 512) img[k] = IM::entry(p.post->theta, k);
+    IM::fill(img, p.post->theta, tid, 512);
     __syncthreads();
     const int RB = (p.a.M + 127) / 128;
     const bool stopping = p.stop_batch > 0;
@@ -175,7 +175,7 @@ __global__ void __launch_bounds__(512) k_sk_persist(const SkpArgs p) {
     constexpr int E = EP::E, UPC = EP::UPC, NI0 = GE::NI0, STAGE = GE::STAGE, NH = WIDE ? 2 : 1;
     static_assert(EP::FLOATS <= STAGE, "EPI image larger than a ring stage");
     static_assert(NI0 <= 8, "layer-0 slice: at most 8 one-KB pieces (one per wave)");
-    static_assert(PreImg<ENV>::IMG + 8 * 16 * Cfg<ENV, 64, 32>::NS + 4 <= 4 * STAGE, "the closing role's image and state tiles fit the ring's LDS");
+    static_assert(P2<Cfg<ENV, 64, 32>>::IMG + 8 * 16 * Cfg<ENV, 64, 32>::NS + 4 <= 4 * STAGE, "the closing role's image and state tiles fit the ring's LDS");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (p.stop != nullptr && *p.stop != 0) return;                             // the sampling loop already ended
     if ((int)blockIdx.x < p.nclose) { skp_closer_role<ENV>(p, lds); return; }

@@ -1,8 +1,9 @@
 // The mean net of the 2 x 32 tanh policy ([rllab] GaussianMLPPolicy.get_actions, the mean half) for a tile of 16 envs, TRANSPOSED on
 // v_mfma_f32_16x16x4_f32 in the fragment layout of dyn_head_mfma.h: the one-time fragment and bias load and the per-step chain (tanh_fast and the two
 // accumulators of the last layer included) of a wave that evaluates the whole policy itself, stated once as a type.  Users: k_rollout_mfma (rollout_mfma.hip),
-// k_score_policy_actions (score_policy_actions.hip) and k_spag_fwd (score_policy_actions_grad.hip).  The kernels that pipeline the chain differently
-// (rollout_coop_body.h, rollout_resident.hip, big_prepost.h, policy_chain3.h, det_gemm.hip) state their own.
+// k_score_policy_actions (score_policy_actions.hip) and k_spag_fwd (score_policy_actions_grad.hip).  The wide-net pre-steps (big_prepost.h, mlp_persist.h,
+// det_gemm.hip, the post roles of rollout_resident.hip) run the chain on an image in LDS: policy_chain2.h.  rollout_coop_body.h and policy_chain3.h pipeline
+// it differently and state their own.
 //   PolWaveHead     a wave's policy: weight fragments in registers (swimmer 6 + 16 + 8, Ant 16 + 16 + 8), its three bias rows in LDS;
 //                   mean() = the mean's action dims 4 q .. 4 q + 3 of env e in D layout
 //   NoiseTile       the tile's noise block, double-buffered in LDS and committed unclipped (ActTile's prefetch)

@@ -93,7 +93,7 @@ template <int ENV, bool POST>
 __global__ void __launch_bounds__(256) k_big_pre_mfma(ProblemDesc pd, RolloutK r, int t, const float* __restrict__ theta,
                                                       const float* __restrict__ norm, BigState st) {
     using C = Cfg<ENV, 64, 32>;
-    using IM = PreImg<ENV>;
+    using IM = P2<C>;
     constexpr int NS = C::NS, IMG = IM::IMG;
     __shared__ __attribute__((aligned(16))) float lds[IMG + 4 * 16 * NS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;

@@ -10,7 +10,7 @@
 //     tile they recompute their quarter of hidden layer 0 (cheaper than fetching 512 activations per env from another CU every step) and
 //     contract it with the slice -- one uninterrupted matrix-instruction stream per SIMD; its 4 FINISHER waves add the quarters, apply
 //     bias + ReLU and emit the slice's contribution to the output layer: [ns x 16 envs] partial sums (resident_compute);
-//   * a POST wave owns (round, env tile): policy forward (the MFMA chain of k_big_pre_mfma), action noise, normalised input -> X
+//   * a POST wave owns (round, env tile): policy forward (the MFMA chain of policy_chain2.h), action noise, normalised input -> X
 //     packets; then it adds the DH/WS partials of each env's selected model in slice order, applies the residual, reward, done,
 //     reset, and writes the trajectory rows.  R x ceil(B/16) post waves on the CUs the compute grid leaves free (resident_post);
 //   * hand-over in both directions by {32 data bits | 32-bit step stamp} packets in an uncached exchange region (agent-scope relaxed
@@ -24,6 +24,7 @@
 // every wait is bounded (2 s), a launch that gives up is reported by the next metrpo_trpo_update / metrpo_comm_check and retires the kernel
 // for its context (metrpo_internal.h: rollout_error_seen).
 #include "mfma_common.h"
+#include "policy_chain2.h"
 #include <string.h>
 // test hook RESIDENT_PLAN: comma-separated words -- "norotate" (fixed deal of tiles to columns), "nosentinel" (post wave polls without the sentinel read)
 static inline bool resident_plan_has(const metrpo_ctx* c, const char* word) { const char* v = ctx_opt(c, OPT_RESIDENT_PLAN); return v != nullptr && strstr(v, word) != nullptr; }
@@ -495,6 +496,29 @@ __device__ __forceinline__ void resident_compute_wide(const ProblemDesc& pd, con
 // ---- post role ------------------------------------------------------------------------------------------------------------------------
 // value held by lane q of an env's four lanes out of (a0, a1, a2, a3)
 __device__ __forceinline__ float sel4(int q, float a0, float a1, float a2, float a3) { return (q & 2) ? ((q & 1) ? a3 : a2) : ((q & 1) ? a1 : a0); }
+// B value of the policy's layer-0 k-step s_ in lane q (P2::mean, policy_chain2.h): dim 4 s_ + q of the env's register state s, zero beyond NS
+template <int NS> __device__ __forceinline__ float res_pol_x(int q, const float (&s)[NS], int s_) {
+    return sel4(q, s[4 * s_], (4 * s_ + 1 < NS) ? s[(4 * s_ + 1 < NS) ? 4 * s_ + 1 : 0] : 0.0f, (4 * s_ + 2 < NS) ? s[(4 * s_ + 2 < NS) ? 4 * s_ + 2 : 0] : 0.0f,
+                (4 * s_ + 3 < NS) ? s[(4 * s_ + 3 < NS) ? 4 * s_ + 3 : 0] : 0.0f);
+}
+
+// Cost of the state reached v (every dim, in registers) under the clipped action's sum of squares su2 (env_helpers.py:601), for both post roles.
+// device_common.h's env_cost is the same expression on memory rows: it sums u from memory itself, behind the wait for the partial sums, where the post roles
+// form su2 while the compute workgroups are busy, and it would send v[] through memory.  Ant: without the dones factor of the validation mode.
+template <int ENV, int NS> __device__ __forceinline__ float res_cost(const float (&v)[NS], float su2) {
+    constexpr int NA = Cfg<ENV, 64, 32>::NA;
+    float cost = 0.0f;
+    if constexpr (ENV == METRPO_ENV_SWIMMER) cost = -(v[5] - 1e-2f * (su2 / (float)NA));
+    else if constexpr (ENV == METRPO_ENV_HALF_CHEETAH) cost = -fminf(fmaxf(v[9] - 1e-1f * 0.5f * su2, -10.0f), 10.0f);
+    else if constexpr (ENV == METRPO_ENV_HOPPER) {
+        float pen = 0.0f;
+#pragma unroll
+        for (int j = 2; j < NS; ++j) pen += fmaxf(fabsf(v[j]) - 100.0f, 0.0f);
+        cost = -(v[5] - 0.01f * 0.5f * su2 - 10.0f * fmaxf(0.45f - v[0], 0.0f) - 10.0f * fmaxf(fabsf(v[1]) - 0.2f, 0.0f) - pen);
+    } else if constexpr (ENV == METRPO_ENV_SNAKE) cost = -(v[7] - 1e-2f * 0.5f * su2);
+    else if constexpr (ENV == METRPO_ENV_ANT) cost = -(v[15] - 1e-2f * 0.5f * su2 + 0.05f);
+    return cost;
+}
 
 // The four lanes (c, q = 0..3) of env c hold the env's whole state in registers (the same values): nothing on the path from "last partial
 // sum arrived" to "next input pushed" goes through memory except the 16 x NA clipped / normalised actions (LDS).  Everything that does not
@@ -505,22 +529,12 @@ __device__ __forceinline__ void resident_post(const ProblemDesc& pd, const Rollo
                                               const float* __restrict__ theta, const float* __restrict__ norm, float* lds) {
     static_assert(ENV != METRPO_ENV_HUMANOID, "2 x 32 policies only");
     using C = Cfg<ENV, 64, 32>;
-    constexpr int NS = C::NS, NA = C::NA, NDROP = C::NDROP, NIN = C::NIN, PH = 32, NS_KS = C::NS_KS, NIN_KS = cdiv(NIN + 1, 4), NSP = C::NSP;   // X element NIN = 1 (bias input of layer 0)
-    constexpr int O_PF1 = NS_KS * 2 * 64, O_PF2 = O_PF1 + 16 * 64, O_B0 = O_PF2 + 8 * 64, O_B1 = O_B0 + 32, O_B2 = O_B1 + 32, IMG = ((O_B2 + 16 + 3) / 4) * 4;
+    using PC = P2<C>;
+    constexpr int NS = C::NS, NA = C::NA, NDROP = C::NDROP, NIN = C::NIN, NIN_KS = cdiv(NIN + 1, 4), NSP = C::NSP, IMG = PC::IMG;   // X element NIN = 1 (bias input of layer 0)
     constexpr int PW_LDS = 2 * 16 * NA;
     constexpr int DCH = (NS <= 12) ? NS : (NS + 1) / 2;               // output dims per batch of partial-sum loads (4 slices x DCH packets in flight per lane)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, q = lane >> 4;
-    for (int i = tid; i < IMG; i += (int)blockDim.x) {                // policy fragment image (layout of k_big_pre_mfma, rollout_gemm.hip)
-        float w = 0.0f;
-        const int ln = i & 63, cc = ln & 15, qq = ln >> 4;
-        if (i < O_PF1) { const int f = i >> 6, s_ = f >> 1, cb = f & 1, in = 4 * s_ + qq; if (in < NS) w = theta[C::pW0 + in * PH + 16 * cb + cc]; }
-        else if (i < O_PF2) { const int f = (i - O_PF1) >> 6, kk = f >> 1, cb = f & 1; w = theta[C::pW1 + (16 * (kk >> 2) + 4 * qq + (kk & 3)) * PH + 16 * cb + cc]; }
-        else if (i < O_B0) { const int kk = (i - O_PF2) >> 6; if (cc < NA) w = theta[C::pW2 + (16 * (kk >> 2) + 4 * qq + (kk & 3)) * NA + cc]; }
-        else if (i < O_B1) w = theta[C::pb0 + (i - O_B0)];
-        else if (i < O_B2) w = theta[C::pb1 + (i - O_B1)];
-        else { const int d = i - O_B2; if (d < NA) w = theta[C::pb2 + d]; }
-        lds[i] = w;
-    }
+    PC::fill(lds, theta, tid, (int)blockDim.x);                       // policy fragment image
     __syncthreads();
     const int g = ((int)blockIdx.x - z.U) * z.PW + wave;
     if (wave >= z.PW || g >= z.R * z.NT) return;
@@ -594,37 +608,8 @@ __device__ __forceinline__ void resident_post(const ProblemDesc& pd, const Rollo
         const unsigned int seq = z.seq0 + (unsigned int)tau + 1u;
         const int t_loc = round * z.steps + tau;                      // row of the trajectory tensors; draws are keyed by r.t0 + t_loc
         const size_t tb = (size_t)t_loc * B + bc;
-        // ---- policy.get_actions (MFMA chain of k_big_pre_mfma; input k-slot q of step s_ = state dim 4 s_ + q)
-        f32x4 p0[2], p1[2];
-        p0[0] = *(const f32x4*)&lds[O_B0 + 4 * q]; p0[1] = *(const f32x4*)&lds[O_B0 + 16 + 4 * q];
-#pragma unroll
-        for (int s_ = 0; s_ < NS_KS; ++s_) {
-            const float xs = sel4(q, s[4 * s_], (4 * s_ + 1 < NS) ? s[(4 * s_ + 1 < NS) ? 4 * s_ + 1 : 0] : 0.0f, (4 * s_ + 2 < NS) ? s[(4 * s_ + 2 < NS) ? 4 * s_ + 2 : 0] : 0.0f,
-                                  (4 * s_ + 3 < NS) ? s[(4 * s_ + 3 < NS) ? 4 * s_ + 3 : 0] : 0.0f);
-            p0[0] = MFMA16(lds[(s_ * 2 + 0) * 64 + lane], xs, p0[0]);
-            p0[1] = MFMA16(lds[(s_ * 2 + 1) * 64 + lane], xs, p0[1]);
-        }
-        p1[0] = *(const f32x4*)&lds[O_B1 + 4 * q]; p1[1] = *(const f32x4*)&lds[O_B1 + 16 + 4 * q];
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) p0[cb][rr] = tanh_fast(p0[cb][rr]);
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
-            p1[0] = MFMA16(lds[O_PF1 + (kk * 2 + 0) * 64 + lane], p0[kk >> 2][kk & 3], p1[0]);
-            p1[1] = MFMA16(lds[O_PF1 + (kk * 2 + 1) * 64 + lane], p0[kk >> 2][kk & 3], p1[1]);
-        }
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) p1[cb][rr] = tanh_fast(p1[cb][rr]);
-        f32x4 m0 = *(const f32x4*)&lds[O_B2 + 4 * q], m1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < 8; kk += 2) {
-            m0 = MFMA16(lds[O_PF2 + kk * 64 + lane], p1[kk >> 2][kk & 3], m0);
-            m1 = MFMA16(lds[O_PF2 + (kk + 1) * 64 + lane], p1[(kk + 1) >> 2][(kk + 1) & 3], m1);
-        }
-        const f32x4 mu = m0 + m1;
+        // ---- policy.get_actions (P2::mean; input k-slot q of step s_ = state dim 4 s_ + q)
+        const f32x4 mu = PC::mean(lds, lane, [&](int s_) { return res_pol_x(q, s, s_); });
         // ---- actions of dims 4q .. 4q+3 (env_helpers.py:599 clip; training.py:228,146-151 normalisation)
         float av[4];
 #pragma unroll
@@ -746,16 +731,7 @@ __device__ __forceinline__ void resident_post(const ProblemDesc& pd, const Rollo
         float v[NS];
 #pragma unroll
         for (int i = 0; i < NS; ++i) v[i] = fmaf(dsd[i], xor_sum(out[i]) + bias[i], dmn[i]) + s[i];
-        float cost = 0.0f;
-        if constexpr (ENV == METRPO_ENV_SWIMMER) cost = -(v[5] - 1e-2f * (su2 / (float)NA));
-        else if constexpr (ENV == METRPO_ENV_HALF_CHEETAH) cost = -fminf(fmaxf(v[9] - 1e-1f * 0.5f * su2, -10.0f), 10.0f);
-        else if constexpr (ENV == METRPO_ENV_HOPPER) {
-            float pen = 0.0f;
-#pragma unroll
-            for (int j = 2; j < NS; ++j) pen += fmaxf(fabsf(v[j]) - 100.0f, 0.0f);
-            cost = -(v[5] - 0.01f * 0.5f * su2 - 10.0f * fmaxf(0.45f - v[0], 0.0f) - 10.0f * fmaxf(fabsf(v[1]) - 0.2f, 0.0f) - pen);
-        } else if constexpr (ENV == METRPO_ENV_SNAKE) cost = -(v[7] - 1e-2f * 0.5f * su2);
-        else if constexpr (ENV == METRPO_ENV_ANT) cost = -(v[15] - 1e-2f * 0.5f * su2 + 0.05f);
+        const float cost = res_cost<ENV>(v, su2);
         bool dn = dn_h;
         if constexpr (STATE_DONE) {                                   // not (0.2 <= z <= 1.0 and every state dim finite), as k_big_post
             bool fin = true;
@@ -789,22 +765,12 @@ template <int ENV, int NTW>
 __device__ __forceinline__ void resident_post_det(const ProblemDesc& pd, const ResidentK& z, int B, const float* __restrict__ dyn,
                                                   const float* __restrict__ theta, const float* __restrict__ norm, float* lds) {
     using C = Cfg<ENV, 64, 32>;
-    constexpr int NS = C::NS, NA = C::NA, NDROP = C::NDROP, NIN = C::NIN, PH = 32, NS_KS = C::NS_KS, NIN_KS = cdiv(NIN + 1, 4), NSP = C::NSP;
-    constexpr int O_PF1 = NS_KS * 2 * 64, O_PF2 = O_PF1 + 16 * 64, O_B0 = O_PF2 + 8 * 64, O_B1 = O_B0 + 32, O_B2 = O_B1 + 32, IMG = ((O_B2 + 16 + 3) / 4) * 4;
+    using PC = P2<C>;
+    constexpr int NS = C::NS, NA = C::NA, NDROP = C::NDROP, NIN = C::NIN, NIN_KS = cdiv(NIN + 1, 4), NSP = C::NSP, IMG = PC::IMG;
     constexpr int PW_LDS = 2 * 16 * NA;
     constexpr int DCH = (NS <= 12) ? NS : (NS + 1) / 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, q = lane >> 4;
-    for (int i = tid; i < IMG; i += (int)blockDim.x) {                // policy fragment image (layout of k_big_pre_mfma, rollout_gemm.hip)
-        float w = 0.0f;
-        const int ln = i & 63, cc = ln & 15, qq = ln >> 4;
-        if (i < O_PF1) { const int f = i >> 6, s_ = f >> 1, cb = f & 1, in = 4 * s_ + qq; if (in < NS) w = theta[C::pW0 + in * PH + 16 * cb + cc]; }
-        else if (i < O_PF2) { const int f = (i - O_PF1) >> 6, kk = f >> 1, cb = f & 1; w = theta[C::pW1 + (16 * (kk >> 2) + 4 * qq + (kk & 3)) * PH + 16 * cb + cc]; }
-        else if (i < O_B0) { const int kk = (i - O_PF2) >> 6; if (cc < NA) w = theta[C::pW2 + (16 * (kk >> 2) + 4 * qq + (kk & 3)) * NA + cc]; }
-        else if (i < O_B1) w = theta[C::pb0 + (i - O_B0)];
-        else if (i < O_B2) w = theta[C::pb1 + (i - O_B1)];
-        else { const int d = i - O_B2; if (d < NA) w = theta[C::pb2 + d]; }
-        lds[i] = w;
-    }
+    PC::fill(lds, theta, tid, (int)blockDim.x);                       // policy fragment image
     __syncthreads();
     // a wave serves NTW tiles (fewer post workgroups leave room for another column of compute workgroups): g_j = (wave index) * NTW + j
     const int wv = ((int)blockIdx.x - z.U) * z.PW + wave;
@@ -845,36 +811,7 @@ __device__ __forceinline__ void resident_post_det(const ProblemDesc& pd, const R
         if (!live[j]) continue;
         float* UA = UAw + j * PW_LDS; float* XA = UA + 16 * NA;
         unsigned long long* xp = z.X + ((size_t)gt[j] * (4 * NIN_KS)) * 16 + c;
-        f32x4 p0[2], p1[2];
-        p0[0] = *(const f32x4*)&lds[O_B0 + 4 * q]; p0[1] = *(const f32x4*)&lds[O_B0 + 16 + 4 * q];
-#pragma unroll
-        for (int s_ = 0; s_ < NS_KS; ++s_) {
-            const float xs = sel4(q, s[j][4 * s_], (4 * s_ + 1 < NS) ? s[j][(4 * s_ + 1 < NS) ? 4 * s_ + 1 : 0] : 0.0f, (4 * s_ + 2 < NS) ? s[j][(4 * s_ + 2 < NS) ? 4 * s_ + 2 : 0] : 0.0f,
-                                  (4 * s_ + 3 < NS) ? s[j][(4 * s_ + 3 < NS) ? 4 * s_ + 3 : 0] : 0.0f);
-            p0[0] = MFMA16(lds[(s_ * 2 + 0) * 64 + lane], xs, p0[0]);
-            p0[1] = MFMA16(lds[(s_ * 2 + 1) * 64 + lane], xs, p0[1]);
-        }
-        p1[0] = *(const f32x4*)&lds[O_B1 + 4 * q]; p1[1] = *(const f32x4*)&lds[O_B1 + 16 + 4 * q];
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) p0[cb][rr] = tanh_fast(p0[cb][rr]);
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
-            p1[0] = MFMA16(lds[O_PF1 + (kk * 2 + 0) * 64 + lane], p0[kk >> 2][kk & 3], p1[0]);
-            p1[1] = MFMA16(lds[O_PF1 + (kk * 2 + 1) * 64 + lane], p0[kk >> 2][kk & 3], p1[1]);
-        }
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) p1[cb][rr] = tanh_fast(p1[cb][rr]);
-        f32x4 m0 = *(const f32x4*)&lds[O_B2 + 4 * q], m1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < 8; kk += 2) {
-            m0 = MFMA16(lds[O_PF2 + kk * 64 + lane], p1[kk >> 2][kk & 3], m0);
-            m1 = MFMA16(lds[O_PF2 + (kk + 1) * 64 + lane], p1[(kk + 1) >> 2][(kk + 1) & 3], m1);
-        }
-        const f32x4 mu = m0 + m1;
+        const f32x4 mu = PC::mean(lds, lane, [&](int s_) { return res_pol_x(q, s[j], s_); });
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
             const int d = 4 * q + jj;
@@ -937,18 +874,9 @@ __device__ __forceinline__ void resident_post_det(const ProblemDesc& pd, const R
         float v[NS];
 #pragma unroll
         for (int i = 0; i < NS; ++i) v[i] = fmaf(dsd[i], xor_sum(out[i]) + b2[i], dmn[i]) + s[j][i];
-        const float su = su2[j];
-        float cost = 0.0f;
-        if constexpr (ENV == METRPO_ENV_SWIMMER) cost = -(v[5] - 1e-2f * (su / (float)NA));
-        else if constexpr (ENV == METRPO_ENV_HALF_CHEETAH) cost = -fminf(fmaxf(v[9] - 1e-1f * 0.5f * su, -10.0f), 10.0f);
-        else if constexpr (ENV == METRPO_ENV_HOPPER) {
-            float pen = 0.0f;
-#pragma unroll
-            for (int jj = 2; jj < NS; ++jj) pen += fmaxf(fabsf(v[jj]) - 100.0f, 0.0f);
-            cost = -(v[5] - 0.01f * 0.5f * su - 10.0f * fmaxf(0.45f - v[0], 0.0f) - 10.0f * fmaxf(fabsf(v[1]) - 0.2f, 0.0f) - pen);
-        } else if constexpr (ENV == METRPO_ENV_SNAKE) cost = -(v[7] - 1e-2f * 0.5f * su);
-        else if constexpr (ENV == METRPO_ENV_ANT) {                   // cost_tf(..., dones) then the dones update (model_based_rl.py:134-137)
-            cost = -(v[15] - 1e-2f * 0.5f * su + 0.05f) * (1.0f - dones[j]);
+        float cost = res_cost<ENV>(v, su2[j]);
+        if constexpr (ENV == METRPO_ENV_ANT) {                        // cost_tf(..., dones) then the dones update (model_based_rl.py:134-137)
+            cost *= 1.0f - dones[j];
             bool fin = true;
 #pragma unroll
             for (int i = 0; i < NS; ++i) fin = fin && isfinite(v[i]);
@@ -1006,14 +934,14 @@ template <int ENV, int DH, int WS> static size_t resident_lds_bytes() {
     using C = Cfg<ENV, 64, 32>;
     constexpr int MT = WS / 16;
     const size_t comp = (size_t)(32 + 8 * 4 * MT * 256) * sizeof(float);
-    const size_t post = (size_t)((C::NS_KS * 2 + 24) * 64 + 84 + 8 * (2 * 16 * C::NA)) * sizeof(float);
+    const size_t post = (size_t)(P2<C>::IMG + 4 + 8 * (2 * 16 * C::NA)) * sizeof(float);
     return std::max(comp, post);
 }
 template <int ENV, int DH, int WS> static size_t resident_lds_bytes_wide() {
     using C = Cfg<ENV, 64, 32>;
     constexpr int MT = WS / 16, OUT_CB = (C::NS + 15) / 16, NIN_KS = (C::NIN + 1 + 3) / 4, W0L = (NIN_KS > 6) ? NIN_KS - 6 : 0, NSLOT = W0L ? 4 : 8;
     const size_t comp = (size_t)(48 + OUT_CB * MT * 256 + MT * 256 + 4 * (DH / 64) * W0L * 64 + NSLOT * 4 * MT * 256) * sizeof(float);
-    const size_t post = (size_t)((C::NS_KS * 2 + 24) * 64 + 84 + 4 * (2 * 16 * C::NA)) * sizeof(float);
+    const size_t post = (size_t)(P2<C>::IMG + 4 + 4 * (2 * 16 * C::NA)) * sizeof(float);
     return std::max(comp, post);
 }
 typedef void (*resident_kernel_t)(ProblemDesc, RolloutK, ResidentK, const float*, const float*, const float*);
@@ -1141,7 +1069,7 @@ typedef void (*resident_val_kernel_t)(ProblemDesc, int, ResidentK, const float*,
 struct ResidentValEntry { int env, ns, na, n_drop, dh, ws; resident_val_kernel_t fn[3]; size_t lds; };      // fn[i]: a post wave serves 1 << i tiles
 template <int ENV, int DH, int WS> static size_t resident_val_lds_bytes() {                                 // compute role | post role with four tiles per wave
     using C = Cfg<ENV, 64, 32>;
-    return std::max(resident_lds_bytes_wide<ENV, DH, WS>(), (size_t)((C::NS_KS * 2 + 24) * 64 + 84 + 4 * 4 * (2 * 16 * C::NA)) * sizeof(float));
+    return std::max(resident_lds_bytes_wide<ENV, DH, WS>(), (size_t)(P2<C>::IMG + 4 + 4 * 4 * (2 * 16 * C::NA)) * sizeof(float));
 }
 #define RES_VAL_ENTRY(ENV, DH, WS) {ENV, EnvDim<ENV>::NS, EnvDim<ENV>::NA, EnvDim<ENV>::NDROP, DH, WS, \
     {k_validation_resident<ENV, DH, WS, 1>, k_validation_resident<ENV, DH, WS, 2>, k_validation_resident<ENV, DH, WS, 4>}, resident_val_lds_bytes<ENV, DH, WS>()}

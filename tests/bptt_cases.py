@@ -112,6 +112,12 @@ def _build():
             for T in (2, 3):
                 for gamma in (0.97, 1.0):
                     add(ant, B, T, gamma=gamma, variant='ant_all')
+    # k_dg_pre_mfma<ENV, STOCH> (det_gemm.hip) on the envs SHAPES leaves to swimmer; appended, so that no earlier case's index or seed moves
+    for env in FUSED_ENVS[1:]:
+        shape = ('gemm', env, (128, 128), (32, 32), 'mfma')
+        for B in SHORT_B:
+            add(shape, B, 2)
+        add(shape, 17, 2, stoch=True)
     return cases
 
 

@@ -21,8 +21,13 @@ def test_case_table_is_well_formed():
     assert {s[2] for s in shapes if s[0] == 'gemm'} == {(128, 128), (128, 160, 128), (24, 16)}
     assert {U.generic_bs(s[1], s[2], s[3]) for s in U.SHAPES if s[0] == 'generic'} == {64, 32}
     assert U.bptt_floats('humanoid', (48, 48, 32), (100, 50, 25)) == 786 and 786 * 64 * 4 > U.LDS_MAX >= 786 * 32 * 4
+    # k_dg_pre_mfma<ENV, STOCH> beyond swimmer: the four other envs on the GEMM path behind a 2 x 32 policy, appended behind everything else
+    extra = [c for c in U.CASES if c.sweep == 'gemm' and (c.dh, c.ph) == ((128, 128), (32, 32)) and c.env != 'swimmer']
+    assert U.CASES[-len(extra):] == extra and all(c.seed == 4000 + U.CASES.index(c) or c.id in U.SEEDS for c in U.CASES)
+    for env in U.FUSED_ENVS[1:]:
+        assert sorted((c.B, c.T, c.stoch) for c in extra if c.env == env) == [(1, 2, False), (17, 2, False), (17, 2, True), (65, 2, False)], env
     for fam in U.DET_PATH:
-        mine = [c for c in U.CASES if c.sweep == fam]
+        mine = [c for c in U.CASES if c.sweep == fam and c not in extra]
         assert any(c.K == 1 and (c.B, c.T) == (1, 1) for c in mine) and any(c.K == 1 and c.B == 65 for c in mine)
         assert any(c.gamma == 1.0 and c.variant == 'plain' for c in mine)
         assert _sizes(c for c in mine if c.stoch) == {(B, T) for B in U.STOCH_B for T in (1, 3)}
