@@ -962,6 +962,29 @@ int32_t metrpo_set_terminal_value(metrpo_ctx* ctx, const float* d_w1, const floa
 int32_t metrpo_clear_terminal_value(metrpo_ctx* ctx);
 int32_t metrpo_has_terminal_value(const metrpo_ctx* ctx);   /* 0 / n_bias */
 
+/* ---- the terminal value's SECOND form: a two-layer tanh value net.  The diagonal quadratic above cannot couple state dims ("forward velocity is worth
+ * more while the torso is upright"); a small MLP behind a short horizon can.  Further additions to ABI 4: no struct changes, no option key is added.
+ *   o_d  = clip(s_d, -10, 10)
+ *   p0   = tanh(W0^T o + b0)          h1 units
+ *   p1   = tanh(W1^T p0 + b1)         h2 units
+ *   V(s) = bias_row + (b2 + sum_j W2[j] p1[j])            bias_row = bias[n_bias > 1 ? b / (B / S) : 0], the rule above
+ *   dV/ds_d = (W0 (W1 (W2 * (1 - p1^2)) * (1 - p0^2)))_d  if -10 <= s_d <= 10,  else 0
+ * fp32, one device function for every kernel: each sum starts from its bias and adds by fmaf in input order, tanh is the library's tanh_fast; the head
+ * b2 + sum_j W2[j] p1[j] is accumulated from b2 in unit order and THEN added to bias_row (so W2 = 0, b2 = 0 gives bias_row exactly, as the quadratic
+ * form with w1 = w2 = 0 does).
+ * d_params is a DEVICE pointer, weights in-major like theta:  W0 [ns][h1] | b0 [h1] | W1 [h1][h2] | b1 [h2] | W2 [h2] | b2 [1];  1 <= h1, h2 <= 32, the
+ * policy's own shape class.  The context keeps a zero-padded 32 x 32 image (exact: tanh_fast(0) = 0 and a zero weight adds an exact zero).
+ * The clip acts on the RAW state, so an input normaliser (o - mean) / std folds into W0 and b0 exactly; fold it on the host.  tanh is the only
+ * activation built.
+ * Context state and stream discipline are metrpo_set_terminal_value's: stream-ordered into ctx-owned memory through the one growth path, neither frees
+ * nor synchronises.  Setting either form replaces the other; metrpo_clear_terminal_value clears whichever is set; metrpo_has_terminal_value returns
+ * n_bias for either; metrpo_terminal_value_kind says which.  Everything stated above about ret, grad, w_T, the bits shared between the calls, chunking,
+ * repeated calls, n_bias against S and the other entry points holds unchanged for this form.  The forward kernels evaluate the net once per lane behind
+ * their step loop; the gradient calls form the seed lambda_T = w_T dV/ds_T in one small launch between their two sweeps.
+ * METRPO_ENULL: ctx or a pointer; METRPO_EINVAL: h1 or h2 outside [1, 32], n_bias < 1. */
+int32_t metrpo_set_terminal_value_mlp(metrpo_ctx* ctx, const float* d_params, int32_t h1, int32_t h2, const float* d_bias, int32_t n_bias, void* stream);
+int32_t metrpo_terminal_value_kind(const metrpo_ctx* ctx);   /* 0 none, 1 quadratic, 2 mlp */
+
 #ifdef __cplusplus
 }
 #endif

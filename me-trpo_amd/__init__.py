@@ -31,10 +31,12 @@ from .planning import score_action_sequences, plan_random_shooting, plan_cem, Sh
 from .planning import engine_grad_scorer, aggregate_heads_grad, refine_actions, plan_cem_gd
 from .planning import engine_policy_scorer, score_noise_sequences, plan_cem_policy
 from .planning import engine_policy_grad_scorer, refine_noise, plan_cem_policy_gd
+from .planning import baseline_terminal_value, ValueMLP, value_targets
 
 __all__ = ['Engine', 'Trajectory', 'xavier_policy_theta', 'Comm', 'NeuralNetEnv', 'VecSimpleEnv', 'InitStatePool',
            'Box', 'EnvSpec', 'GaussianMLPPolicy', 'LinearFeatureBaseline', 'VectorizedSampler', 'BaseSampler',
            'DevicePaths', 'ConjugateGradientOptimizer', 'BatchPolopt', 'NPO', 'TRPO', 'VPG', 'PPO', 'FirstOrderOptimizer', 'AdamOptimizer', 'LBFGS', 'svg', 'SVG', 'rollout_triplets', 'pack_rollouts', 'early_stop', 'dynamics_training', 'from_params', 'shapes_from_params', 'model_error', 'evaluate_model_predictions', 'get_error_distribution', 'open_loop_predictions', 'ensemble_disagreement',
            'planning', 'score_action_sequences', 'plan_random_shooting', 'plan_cem', 'ShootingController',
            'engine_grad_scorer', 'aggregate_heads_grad', 'refine_actions', 'plan_cem_gd',
-           'engine_policy_scorer', 'score_noise_sequences', 'plan_cem_policy', 'engine_policy_grad_scorer', 'refine_noise', 'plan_cem_policy_gd']
+           'engine_policy_scorer', 'score_noise_sequences', 'plan_cem_policy', 'engine_policy_grad_scorer', 'refine_noise', 'plan_cem_policy_gd',
+           'baseline_terminal_value', 'ValueMLP', 'value_targets']

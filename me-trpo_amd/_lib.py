@@ -217,6 +217,8 @@ SYMBOLS = {
     'metrpo_set_terminal_value': (_I, [_P, _P, _P, _P, _I, _P]),
     'metrpo_clear_terminal_value': (_I, [_P]),
     'metrpo_has_terminal_value': (_I, [_P]),
+    'metrpo_set_terminal_value_mlp': (_I, [_P, _P, _I, _I, _P, _I, _P]),
+    'metrpo_terminal_value_kind': (_I, [_P]),
     'metrpo_dyn_train_reset': (_I, [_P, _P]),
     'metrpo_dyn_train_step': (_I, [_P, _P, _P, C.POINTER(TrainParams), _P, _P]),
     'metrpo_dyn_eval_losses': (_I, [_P, _P, _P, _L, _D, _P, _P]),

@@ -1118,9 +1118,19 @@ extern "C" int32_t metrpo_set_terminal_value(metrpo_ctx* c, const float* d_w1, c
     HIP_TRY(c, hipMemcpyAsync(c->d_tv.p, d_w1, sizeof(float) * ns, hipMemcpyDeviceToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(c->d_tv.p + ns, d_w2, sizeof(float) * ns, hipMemcpyDeviceToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(c->d_tv.p + 2 * ns, d_bias, sizeof(float) * (size_t)n_bias, hipMemcpyDeviceToDevice, st));
-    c->tv_n_bias = n_bias;
+    c->tv_n_bias = n_bias; c->tv_kind = 1;
     return METRPO_OK;
 }
+// ... its second form, a two-layer tanh net (sact_sum.h: TermVal's mlp_*): setting either form replaces the other, in the same buffer
+extern "C" int32_t metrpo_set_terminal_value_mlp(metrpo_ctx* c, const float* d_params, int32_t h1, int32_t h2, const float* d_bias, int32_t n_bias, void* stream) {
+    if (!c) return METRPO_ENULL;
+    if (!d_params || !d_bias) return set_err(c, METRPO_ENULL, "set_terminal_value_mlp: NULL pointer");
+    if (h1 < 1 || h1 > 32 || h2 < 1 || h2 > 32)
+        return set_err(c, METRPO_EINVAL, "set_terminal_value_mlp: hidden widths " + std::to_string(h1) + ", " + std::to_string(h2) + " must lie in 1 ... 32");
+    if (n_bias < 1) return set_err(c, METRPO_EINVAL, "set_terminal_value_mlp: n_bias = " + std::to_string(n_bias) + " must be at least 1");
+    return run_set_terminal_value_mlp(c, d_params, h1, h2, d_bias, n_bias, (hipStream_t)stream);
+}
+extern "C" int32_t metrpo_terminal_value_kind(const metrpo_ctx* c) { return c ? (c->tv_n_bias < 1 ? 0 : c->tv_kind) : METRPO_ENULL; }
 extern "C" int32_t metrpo_clear_terminal_value(metrpo_ctx* c) {
     if (!c) return METRPO_ENULL;
     c->tv_n_bias = 0;                                            // the buffer stays: enqueued calls may still read it

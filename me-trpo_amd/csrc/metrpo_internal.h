@@ -131,6 +131,7 @@ struct metrpo_ctx {
     int last_spol_kernel = -1; DevBuf<void> d_spol;       // metrpo_score_policy_actions (score_policy_actions.hip): -1 none yet, 0 generic, 1 fused | the generic path's chunk workspace (start | two state rows | act | mean | rew | done | head vectors)
     int last_spag_kernel = -1; DevBuf<void> d_spag;       // metrpo_score_policy_actions_grad (score_policy_actions_grad.hip): -1 none yet, 0 generic, 1 fused | a chunk's states, weights and per-head actions (XS | WT | AW)
     DevBuf<float> d_tv; int tv_n_bias = 0;                // metrpo_set_terminal_value: w1 [ns] | w2 [ns] | bias [n_bias], read by the four scoring calls above (sact_sum.h: TermVal) | 0: none set
+    int tv_kind = 0;                                      // ... which form d_tv holds while tv_n_bias > 0: 1 the quadratic above, 2 metrpo_set_terminal_value_mlp's zero-padded image | bias (sact_sum.h: tvm_*)
     int spol_chunk_cap = 0;                               // ... test hook (metrpo_debug_score_policy_chunk): at most this many candidates per chunk of its generic path; 0: the 2^26-float rule alone
     DevBuf<void> d_svg; int last_svg_path = -1;         // svg.hip: workspace of metrpo_svg_grad / _update (zeroed copy of the rollouts | mean-adjoint | F | Pi | chunk buffers | lambda_0 | gradient) | -1 none yet, 1 generic, 2 GEMM
     int coop_no_split = 0;                                // switch (metrpo_set_coop_split): 1 keeps the 4-wave form of the cooperative kernel where the head-split form would run
@@ -497,8 +498,10 @@ int run_score_actions(metrpo_ctx*, const metrpo_score_actions_args*, hipStream_t
 // ... its generic path's start-row gather (act_c NULL: the start rows only), its reduction over a stored rew / done [T][Bc], and the head statistics of d_ret
 void launch_sact_starts(const float* init_obs, const float* actions, int B, int T, int per, int c0, int Bc, int ns, int na, float* obs0, float* act_c, hipStream_t);
 struct TermVal;   // sact_sum.h: the context's terminal value; set: sT is the chunk's states behind step T [Bc][ns], c0 the chunk's first candidate, per = B / S
-void launch_sact_reduce(const float* rew, const uint8_t* done, int Bc, int T, int stop, double gamma, float* ret, int32_t* len, const TermVal& tv, const float* sT, int ns,
+void launch_sact_reduce(const float* rew, const uint8_t* done, int Bc, int T, int stop, double gamma, float* ret, int32_t* len, const TermVal& tv, bool mlp, const float* sT, int ns,
                         int c0, int per, hipStream_t);
+// ... the body of metrpo_set_terminal_value_mlp (arguments checked by the entry point): d_tv <- the zero-padded image of d_params | bias, stream-ordered
+int run_set_terminal_value_mlp(metrpo_ctx*, const float* d_params, int h1, int h2, const float* d_bias, int n_bias, hipStream_t);
 void launch_sact_aggregate(const float* ret, int B, int K, float* mean, float* sd, hipStream_t);
 // score_policy_actions.hip: the body of metrpo_score_policy_actions (arguments checked by the entry point; B, T > 0, B % S == 0, policy and dynamics set)
 int run_score_policy_actions(metrpo_ctx*, const metrpo_score_policy_actions_args*, hipStream_t);
@@ -506,6 +509,8 @@ int run_score_policy_actions(metrpo_ctx*, const metrpo_score_policy_actions_args
 int run_score_actions_grad(metrpo_ctx*, const metrpo_score_actions_grad_args*, hipStream_t);
 // ... its head-order mean of d_grad [K][n] (k_sagr_mean), for score_policy_actions_grad.hip as well; reports no error of its own
 void launch_sagr_mean(const float* grad, size_t n, int K, float* mean, hipStream_t);
+// ... the MLP terminal value's seed of a chunk (k_tv_mlp_seed), for score_policy_actions_grad.hip as well: seed [K][n][ns] = WE * dV/ds at slice T of XS [K][T + 1][n][ns]
+void launch_tv_mlp_seed(const TermVal& tv, const float* XS, const float* WE, float* seed, int K, int T, int n, int ns, hipStream_t);
 // score_policy_actions_grad.hip: the body of metrpo_score_policy_actions_grad (arguments checked by the entry point; B, T > 0, B % S == 0, chunk >= 0, policy and dynamics set)
 int run_score_policy_actions_grad(metrpo_ctx*, const metrpo_score_policy_actions_grad_args*, hipStream_t);
 // svg.hip: the body of metrpo_svg_grad / metrpo_svg_update (arguments checked by the entry points); update: the SGD step with `lr` on the ctx theta

@@ -44,7 +44,8 @@ struct SactK {
 // tile_rollout's sink that stores nothing inside the step loop: every lane carries its env's sum, quad 0 writes d_ret / d_len once behind the loop.
 // TV: with a terminal value -- a template parameter, so that the kernel without one is the kernel it was (the runtime test's operands cost it 8 .. 14
 // scalar registers held across the loop, and 0.3 .. 0.7 % of its time: profiles/r26_terminal_value.txt)
-template <bool TV>
+// TV_MLP: the two-layer tanh value, a further value of the same parameter (its two hidden rows take the registers the loop's fragments have released)
+template <int TV>
 struct SactSink {
     const SactK& r;
     SactSum acc;
@@ -55,7 +56,7 @@ struct SactSink {
     __device__ __forceinline__ void finish(int k, int b0, int lane, const float* ST) {
         const int b = b0 + (lane & 15);
         if ((lane >> 4) == 0 && b < r.B) {                       // rounded to fp32 once, here
-            if (TV) acc.terminal(r.tv.value(ST + (lane & 15) * NS, 1, NS, b, r.per));
+            if (TV) acc.terminal(r.tv.template value_of<TV>(ST + (lane & 15) * NS, 1, NS, b, r.per));
             const size_t kb = (size_t)k * r.B + b;
             r.ret[kb] = (float)acc.sum;
             if (r.len != nullptr) r.len[kb] = acc.n;
@@ -63,7 +64,7 @@ struct SactSink {
     }
 };
 
-template <int ENV, bool TV>
+template <int ENV, int TV>
 __global__ void __launch_bounds__(64) k_score_actions(SactK r, const float* __restrict__ dynp, const float* __restrict__ norm) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int b0 = blockIdx.x * 16, k = blockIdx.y;
@@ -91,13 +92,16 @@ __global__ void __launch_bounds__(256) k_sact_starts(const float* __restrict__ i
 }
 // k_sact_reduce: one thread per candidate of the chunk over the step loop's rew / done [T][Bc]; SactSum is the fused kernel's.  ret / len point at [k][c0].
 // tv set: sT holds the chunk's states behind step T, [Bc][ns]; c0 is the chunk's first candidate (the bias row is (c0 + i) / per).
+// MLP: the value is the two-layer net (a template parameter: the instantiation without it is the kernel it was).
+template <bool MLP>
 __global__ void __launch_bounds__(256) k_sact_reduce(const float* __restrict__ rew, const uint8_t* __restrict__ done, int Bc, int T, int stop, double gamma,
                                                      float* __restrict__ ret, int32_t* __restrict__ len, TermVal tv, const float* __restrict__ sT, int ns, int c0, int per) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Bc) return;
     SactSum acc;
     for (int t = 0; t < T; ++t) acc.step(rew[(size_t)t * Bc + i], done[(size_t)t * Bc + i] != 0, gamma, stop);
-    if (tv.set()) acc.terminal(tv.value(sT + (size_t)i * ns, 1, ns, c0 + i, per));
+    if constexpr (MLP) acc.terminal(tv.mlp_value(sT + (size_t)i * ns, 1, ns, c0 + i, per));
+    else if (tv.set()) acc.terminal(tv.value(sT + (size_t)i * ns, 1, ns, c0 + i, per));
     ret[i] = (float)acc.sum;
     if (len != nullptr) len[i] = acc.n;
 }
@@ -124,18 +128,46 @@ void launch_sact_starts(const float* init_obs, const float* actions, int B, int 
     const size_t work = (size_t)Bc * ns + (act_c ? (size_t)T * Bc * na : 0);
     hipLaunchKernelGGL(k_sact_starts, dim3((unsigned)std::min<size_t>((work + 255) / 256, 4096)), dim3(256), 0, st, init_obs, actions, B, T, per, c0, Bc, ns, na, obs0, act_c);
 }
-void launch_sact_reduce(const float* rew, const uint8_t* done, int Bc, int T, int stop, double gamma, float* ret, int32_t* len, const TermVal& tv, const float* sT, int ns,
+void launch_sact_reduce(const float* rew, const uint8_t* done, int Bc, int T, int stop, double gamma, float* ret, int32_t* len, const TermVal& tv, bool mlp, const float* sT, int ns,
                         int c0, int per, hipStream_t st) {
-    hipLaunchKernelGGL(k_sact_reduce, dim3((Bc + 255) / 256), dim3(256), 0, st, rew, done, Bc, T, stop, gamma, ret, len, tv, sT, ns, c0, per);
+    hipLaunchKernelGGL(mlp ? k_sact_reduce<true> : k_sact_reduce<false>, dim3((Bc + 255) / 256), dim3(256), 0, st, rew, done, Bc, T, stop, gamma, ret, len, tv, sT, ns, c0, per);
 }
 void launch_sact_aggregate(const float* ret, int B, int K, float* mean, float* sd, hipStream_t st) {
     hipLaunchKernelGGL(k_sact_aggregate, dim3((B + 255) / 256), dim3(256), 0, st, ret, B, K, mean, sd);
 }
 
+// metrpo_set_terminal_value_mlp: the context's image of the net (sact_sum.h: tvm_*) from the caller's packed parameters
+//   W0 [ns][h1] | b0 [h1] | W1 [h1][h2] | b1 [h2] | W2 [h2] | b2, the hidden widths padded with zeros to TVM, and the biases behind it.  One thread per float of the image.
+__global__ void __launch_bounds__(256) k_tv_mlp_image(const float* __restrict__ par, int ns, int h1, int h2, const float* __restrict__ bias, int n_bias, float* __restrict__ img) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int n_img = tvm_floats(ns);
+    if (i >= n_img + n_bias) return;
+    if (i >= n_img) { img[i] = bias[i - n_img]; return; }
+    const float* W0 = par; const float* b0 = W0 + ns * h1; const float* W1 = b0 + h1; const float* b1 = W1 + h1 * h2; const float* W2 = b1 + h2; const float* b2 = W2 + h2;
+    float v = 0.0f;
+    if (i < tvm_b0(ns)) { const int d = i / TVM, u = i % TVM; if (u < h1) v = W0[d * h1 + u]; }
+    else if (i < tvm_w1(ns)) { const int u = i - tvm_b0(ns); if (u < h1) v = b0[u]; }
+    else if (i < tvm_b1(ns)) { const int j = i - tvm_w1(ns), w = j / TVM, u = j % TVM; if (u < h1 && w < h2) v = W1[u * h2 + w]; }      // out-major: row w holds unit w's inputs
+    else if (i < tvm_w2(ns)) { const int w = i - tvm_b1(ns); if (w < h2) v = b1[w]; }
+    else { const int w = i - tvm_w2(ns); if (w < h2) v = W2[w]; else if (w == TVM) v = b2[0]; }
+    img[i] = v;
+}
+// ... context state like metrpo_set_terminal_value's: the one growth path (an outgrown buffer is retired, not freed), one stream-ordered launch, no synchronisation
+int run_set_terminal_value_mlp(metrpo_ctx* c, const float* d_params, int h1, int h2, const float* d_bias, int n_bias, hipStream_t st) {
+    const int ns = c->pd.ns;
+    const size_t total = (size_t)tvm_floats(ns) + (size_t)n_bias;
+    { const int rc = ws_grow(c, c->d_tv, sizeof(float) * total); if (rc) { c->tv_n_bias = 0; return rc; } }
+    c->tv_n_bias = 0;                                            // a failed launch leaves none set
+    hipLaunchKernelGGL(k_tv_mlp_image, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_params, ns, h1, h2, d_bias, n_bias, c->d_tv.p);
+    HIP_TRY(c, hipGetLastError());
+    c->tv_n_bias = n_bias; c->tv_kind = TV_MLP;
+    return METRPO_OK;
+}
+
 // -------------------------------------------------------------------------------------------------
 typedef void (*sact_kernel_t)(SactK, const float*, const float*);
-struct SactEntry { int env; sact_kernel_t kern[2]; int w_sz; };      // kern[terminal value set]
-#define SENTRY(ENVID) {ENVID, {k_score_actions<ENVID, false>, k_score_actions<ENVID, true>}, act_wave_floats<ENVID>()}
+struct SactEntry { int env; sact_kernel_t kern[3]; int w_sz; };      // kern[the terminal value's kind]
+#define SENTRY(ENVID) {ENVID, {k_score_actions<ENVID, TV_NONE>, k_score_actions<ENVID, TV_QUAD>, k_score_actions<ENVID, TV_MLP>}, act_wave_floats<ENVID>()}
 static const SactEntry kSact[] = {FUSED_HEAD_ENVS(SENTRY)};
 
 static int launch_sact_fused(metrpo_ctx* c, const SactEntry& en, bool padded, const metrpo_score_actions_args* a, hipStream_t st) {
@@ -145,7 +177,7 @@ static int launch_sact_fused(metrpo_ctx* c, const SactEntry& en, bool padded, co
     const float* dyn;
     { const int rc = fused_head_dyn(c, padded, st, &dyn); if (rc) return rc; }
     const size_t sh = sizeof(float) * (size_t)en.w_sz;
-    hipLaunchKernelGGL(en.kern[r.tv.w1 ? 1 : 0], dim3((a->B + 15) / 16, c->pd.K), dim3(64), sh, st, r, dyn, c->d_norm.p);
+    hipLaunchKernelGGL(en.kern[ctx_tv_kind(c)], dim3((a->B + 15) / 16, c->pd.K), dim3(64), sh, st, r, dyn, c->d_norm.p);
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
 }
@@ -176,7 +208,7 @@ static int launch_sact_generic(metrpo_ctx* c, const metrpo_score_actions_args* a
             rc = run_rollout_actions(c, &ra, st);
             if (rc) break;
             launch_sact_reduce(ra.d_rew, ra.d_done, n, a->T, a->stop_at_done ? 1 : 0, a->gamma, a->d_ret + (size_t)k * B + c0,
-                               a->d_len ? a->d_len + (size_t)k * B + c0 : nullptr, ctx_term_val(c), ra.d_obs + T * n * ns, (int)ns, (int)c0, per, st);      // row T of the chunk's trajectory
+                               a->d_len ? a->d_len + (size_t)k * B + c0 : nullptr, ctx_term_val(c), ctx_tv_kind(c) == TV_MLP, ra.d_obs + T * n * ns, (int)ns, (int)c0, per, st);      // row T of the chunk's trajectory
             if (hipGetLastError() != hipSuccess) rc = set_err(c, METRPO_EHIP, "score_actions: launch failed");
         }
     }

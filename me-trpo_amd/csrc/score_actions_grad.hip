@@ -30,6 +30,8 @@
 // set -- stored, not re-derived: the reverse sweep would have to redo the done test of s_T and the float64 discount to form it.  The reverse sweeps start from
 // lambda_T = w_T dV/ds_T, formed from the stored XS[T] tile in lambda's own layout (fused: the x_T buffer in LDS, behind its commit) instead of 0.  The forward
 // sweeps take the value as a template parameter (k_sagr<.., SAGR_FWD, TV>, k_sagr_gen_fwd<TV>), the reverse sweeps by the runtime-uniform pointer test.
+// The MLP form (metrpo_set_terminal_value_mlp) is TV_MLP of the same parameter in the forward sweeps; its seed is formed by a launch of its own between the two
+// sweeps (k_tv_mlp_seed: XS[T], WE -> seed [K][Bc][ns] behind WE), and the reverse sweeps' TV_MLP / SEEDED instantiations read it in front of their loop.
 //
 // Workspace: ctx->d_sagr = XS | WT (| WE) of one chunk, within 2^26 floats (score_chunk, metrpo_internal.h; args.chunk > 0 overrides).  d_grad_mean: k_sagr_mean, a small
 // launch over d_grad adding in head order (k_sact_aggregate's style).  No atomics anywhere: repeated calls are bit-identical.
@@ -55,7 +57,7 @@ struct SagrK {
 };
 
 // tile_rollout's sink of the forward sweep: b0 is the tile's first candidate in the batch, the chunk's column is b - c0
-template <int NS, bool TV>
+template <int NS, int TV>
 struct SagrSink {
     const SagrK& r;
     int k;
@@ -77,7 +79,7 @@ struct SagrSink {
     __device__ __forceinline__ void finish(int b0, int lane, const float* ST) {
         const int b = b0 + (lane & 15);
         if ((lane >> 4) == 0 && b < r.c0 + r.n) {
-            if (TV) r.WE[(size_t)k * r.n + (b - r.c0)] = acc.terminal(r.tv.value(ST + (lane & 15) * NS, 1, NS, b, r.per));
+            if (TV) r.WE[(size_t)k * r.n + (b - r.c0)] = acc.terminal(r.tv.template value_of<TV>(ST + (lane & 15) * NS, 1, NS, b, r.per));
             const size_t kb = (size_t)k * r.B + b;
             if (r.ret != nullptr) r.ret[kb] = (float)acc.sum;
             if (r.len != nullptr) r.len[kb] = acc.n;
@@ -97,7 +99,9 @@ struct SagrL {
 
 // TV: the forward sweep with a terminal value.  A template parameter there, not the runtime-uniform pointer test of the other kernels: the test's
 // operands live in scalar registers across the step loop, the Ant instantiation has none to spare, and what spills costs it a wave per SIMD.
-template <int ENV, int MODE, bool TV = false>
+// TV is the value's kind (sact_sum.h: TV_NONE, TV_QUAD, TV_MLP).  The reverse sweep knows two: TV_NONE, the kernel it was, with the runtime test for the quadratic
+// form; TV_MLP, which reads lambda_T from the workspace behind WE (k_tv_mlp_seed below wrote it: the net's 64 hidden values have no room beside this sweep's fragments).
+template <int ENV, int MODE, int TV = TV_NONE>
 __global__ void __launch_bounds__(MODE == SAGR_FWD ? 64 : 256, MODE == SAGR_FWD ? 1 : 2)
 k_sagr(SagrK r, const float* __restrict__ dynp, const float* __restrict__ norm) {
     using L = SagrL<ENV>;
@@ -172,7 +176,16 @@ k_sagr(SagrK r, const float* __restrict__ dynp, const float* __restrict__ norm) 
 #pragma unroll
         for (int cb = 0; cb < OUT_CB; ++cb) lam[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
         // the terminal value's seed, lambda_T = w_T dV/ds_T, from the x_T tile in lambda's own layout; w_T is the forward sweep's (WE)
-        if (r.tv.set()) {
+        if constexpr (TV == TV_MLP) {
+            const float* __restrict__ seed = tv_mlp_seed_of(r.WE, r.n, (int)gridDim.y) + ((size_t)k * r.n + min(lc, r.n - 1)) * NS;
+#pragma unroll
+            for (int cb = 0; cb < OUT_CB; ++cb)
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) {
+                    const int dim = 16 * cb + 4 * q + rr;
+                    if (dim < NS) lam[cb][rr] = active ? seed[dim] : 0.0f;
+                }
+        } else if (r.tv.set()) {
             const float* XT = W + (r.T & 1) * L::SB;
             const float wT = active ? r.WE[(size_t)k * r.n + min(lc, r.n - 1)] : 0.0f;
 #pragma unroll
@@ -272,7 +285,7 @@ k_sagr(SagrK r, const float* __restrict__ dynp, const float* __restrict__ norm) 
 // -------------------------------------------------------------------------------------------------
 // Generic path (sact_sum.h: GradBufs without the policy's rows).
 // TV: with a terminal value -- a template parameter, so that the instantiation without one is the kernel it was (the runtime test costs it a stack slot)
-template <bool TV>
+template <int TV>
 __global__ void k_sagr_gen_fwd(ProblemDesc pd, SagrK r, const float* __restrict__ dynp, const float* __restrict__ norm) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int LD = blockDim.x, tid = threadIdx.x;
@@ -306,12 +319,14 @@ __global__ void k_sagr_gen_fwd(ProblemDesc pd, SagrK r, const float* __restrict_
         for (int i = 0; i < ns; ++i) e.S[i * LD + tid] = e.XN[i * LD + tid];
     }
     if (active) {
-        if (TV) r.WE[(size_t)k * r.n + lc] = acc.terminal(r.tv.value(e.S + tid, LD, ns, b, r.per));      // S holds s_T behind the loop
+        if (TV) r.WE[(size_t)k * r.n + lc] = acc.terminal(r.tv.template value_of<TV>(e.S + tid, LD, ns, b, r.per));      // S holds s_T behind the loop
         if (r.ret != nullptr) r.ret[(size_t)k * r.B + b] = (float)acc.sum;
         if (r.len != nullptr) r.len[(size_t)k * r.B + b] = acc.n;
     }
 }
 
+// SEEDED: the MLP form -- lambda_T is read from the workspace behind WE (k_tv_mlp_seed); without it the kernel it was
+template <bool SEEDED>
 __global__ void k_sagr_gen_bwd(ProblemDesc pd, SagrK r, const float* __restrict__ dynp, const float* __restrict__ norm) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int LD = blockDim.x, tid = threadIdx.x;
@@ -325,7 +340,10 @@ __global__ void k_sagr_gen_bwd(ProblemDesc pd, SagrK r, const float* __restrict_
     const float* __restrict__ pk = dynp + (size_t)k * dn.n_params;
     const float* xs = r.XS + (size_t)k * (r.T + 1) * r.n * ns;
     for (int i = 0; i < ns; ++i) e.LAM[i * LD + tid] = 0.0f;
-    if (r.tv.set() && active) {                              // the terminal value's seed: lambda_T = w_T dV/ds_T
+    if constexpr (SEEDED) {
+        const float* seed = tv_mlp_seed_of(r.WE, r.n, (int)gridDim.y) + ((size_t)k * r.n + lc) * ns;
+        if (active) for (int i = 0; i < ns; ++i) e.LAM[i * LD + tid] = seed[i];
+    } else if (r.tv.set() && active) {                       // the terminal value's seed: lambda_T = w_T dV/ds_T
         const float wT = r.WE[(size_t)k * r.n + lc];
         for (int i = 0; i < ns; ++i) e.LAM[i * LD + tid] = wT * r.tv.grad(i, xs[((size_t)r.T * r.n + lc) * ns + i]);
     }
@@ -381,10 +399,27 @@ void launch_sagr_mean(const float* grad, size_t n, int K, float* mean, hipStream
     hipLaunchKernelGGL(k_sagr_mean, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st, grad, n, K, mean);
 }
 
+// The MLP terminal value's seed of one chunk, between the forward and the reverse sweep: one thread per (column of the chunk, head k = blockIdx.y),
+// seed [K][n][ns] = w_T dV/ds_T from the stored slice T of XS and the stored w_T (WE).  The reverse sweeps find it behind WE (sact_sum.h: tv_mlp_seed_of).
+__global__ void __launch_bounds__(64) k_tv_mlp_seed(TermVal tv, const float* __restrict__ XS, const float* __restrict__ WE, float* __restrict__ seed, int T, int n, int ns) {
+    const int lc = blockIdx.x * blockDim.x + threadIdx.x, k = blockIdx.y;
+    if (lc >= n) return;
+    const float* sT = XS + (((size_t)k * (T + 1) + T) * n + lc) * ns;
+    const float wT = WE[(size_t)k * n + lc];
+    float g0[TVM];
+    tv.mlp_adjoint(sT, 1, ns, g0);
+    float* out = seed + ((size_t)k * n + lc) * ns;
+    for (int d = 0; d < ns; ++d) out[d] = wT * tv.mlp_grad(d, sT[d], g0);
+}
+void launch_tv_mlp_seed(const TermVal& tv, const float* XS, const float* WE, float* seed, int K, int T, int n, int ns, hipStream_t st) {
+    hipLaunchKernelGGL(k_tv_mlp_seed, dim3((n + 63) / 64, (unsigned)K), dim3(64), 0, st, tv, XS, WE, seed, T, n, ns);
+}
+
 // -------------------------------------------------------------------------------------------------
 typedef void (*sagr_kernel_t)(SagrK, const float*, const float*);
-struct SagrEntry { int env; sagr_kernel_t fwd[2], bwd; int fwd_floats, bwd_floats; };      // fwd[terminal value set]
-#define GENTRY(ENVID) {ENVID, {k_sagr<ENVID, SAGR_FWD>, k_sagr<ENVID, SAGR_FWD, true>}, k_sagr<ENVID, SAGR_BWD>, act_wave_floats<ENVID>(), SagrL<ENVID>::TOTAL}
+struct SagrEntry { int env; sagr_kernel_t fwd[3], bwd[2]; int fwd_floats, bwd_floats; };      // fwd[the terminal value's kind], bwd[it is the MLP]
+#define GENTRY(ENVID) {ENVID, {k_sagr<ENVID, SAGR_FWD>, k_sagr<ENVID, SAGR_FWD, TV_QUAD>, k_sagr<ENVID, SAGR_FWD, TV_MLP>}, {k_sagr<ENVID, SAGR_BWD>, k_sagr<ENVID, SAGR_BWD, TV_MLP>},   \
+                       act_wave_floats<ENVID>(), SagrL<ENVID>::TOTAL}
 static const SagrEntry kSagr[] = {FUSED_HEAD_ENVS(GENTRY)};
 
 int run_score_actions_grad(metrpo_ctx* c, const metrpo_score_actions_grad_args* a, hipStream_t st) {
@@ -392,13 +427,16 @@ int run_score_actions_grad(metrpo_ctx* c, const metrpo_score_actions_grad_args* 
     const size_t ns = pd.ns, B = a->B, T = a->T, K = pd.K;
     bool padded = false;
     const SagrEntry* en = a->force_generic ? nullptr : fused_head_entry(kSagr, c, 65535, &padded);      // the heads are gridDim.y
-    // ---- a chunk's workspace (floats): XS [K][T + 1][Bc][ns] | WT [K][T][Bc] | (a terminal value is set) WE [K][Bc]; within 2^26 floats unless args.chunk says otherwise ----
+    // ---- a chunk's workspace (floats): XS [K][T + 1][Bc][ns] | WT [K][T][Bc] | (a terminal value is set) WE [K][Bc] | (it is the MLP) its seed [K][Bc][ns];
+    // within 2^26 floats unless args.chunk says otherwise ----
     const TermVal tv = ctx_term_val(c);
-    const size_t per_cand = K * ((T + 1) * ns + T + (tv.w1 ? 1 : 0));
+    const int kind = ctx_tv_kind(c);
+    const bool mlp = kind == TV_MLP;
+    const size_t per_cand = K * ((T + 1) * ns + T + (tv.w1 ? 1 : 0) + (mlp ? ns : 0));
     const size_t Bc = score_chunk(B, per_cand, (size_t)a->chunk);
     const size_t o_wt = (K * (T + 1) * Bc * ns + 3) & ~(size_t)3;
     const size_t o_we = o_wt + K * T * Bc;
-    { const int rc = ws_grow(c, c->d_sagr, sizeof(float) * (o_we + (tv.w1 ? K * Bc : 0))); if (rc) return rc; }
+    { const int rc = ws_grow(c, c->d_sagr, sizeof(float) * (o_we + (tv.w1 ? K * Bc : 0) + (mlp ? K * Bc * ns : 0))); if (rc) return rc; }
     float* ws = (float*)c->d_sagr.p;
     SagrK r = {};
     r.B = a->B; r.T = a->T; r.per = a->B / a->S; r.stop = a->stop_at_done ? 1 : 0; r.gamma = a->gamma;
@@ -408,28 +446,32 @@ int run_score_actions_grad(metrpo_ctx* c, const metrpo_score_actions_grad_args* 
     size_t sh_f = 0, sh_b = 0;
     int bs = 64;
     void (*gen_fwd)(ProblemDesc, SagrK, const float*, const float*) = nullptr;
+    void (*gen_bwd)(ProblemDesc, SagrK, const float*, const float*) = nullptr;
     if (en != nullptr) {
         { const int rc = fused_head_dyn(c, padded, st, &dyn); if (rc) return rc; }
         sh_f = sizeof(float) * (size_t)en->fwd_floats; sh_b = sizeof(float) * (size_t)en->bwd_floats;
-        { const int rc = allow_dynamic_lds(c, (const void*)en->bwd, sh_b); if (rc) return rc; }
+        { const int rc = allow_dynamic_lds(c, (const void*)en->bwd[mlp ? 1 : 0], sh_b); if (rc) return rc; }
     } else {
         const size_t fpt = grad_gen_floats(pd, false);
         if ((bs = lds_block_size(fpt)) == 0) return set_err(c, METRPO_EUNSUPPORTED, "score_actions_grad: layer widths exceed the LDS budget of the generic kernel");
         sh_f = sh_b = fpt * bs * sizeof(float);
-        gen_fwd = tv.w1 ? k_sagr_gen_fwd<true> : k_sagr_gen_fwd<false>;
+        gen_fwd = mlp ? k_sagr_gen_fwd<TV_MLP> : (tv.w1 ? k_sagr_gen_fwd<TV_QUAD> : k_sagr_gen_fwd<TV_NONE>);
+        gen_bwd = mlp ? k_sagr_gen_bwd<true> : k_sagr_gen_bwd<false>;
         int rc = allow_dynamic_lds(c, (const void*)gen_fwd, sh_f);
-        if (!rc) rc = allow_dynamic_lds(c, (const void*)k_sagr_gen_bwd, sh_b);
+        if (!rc) rc = allow_dynamic_lds(c, (const void*)gen_bwd, sh_b);
         if (rc) return rc;
     }
     for (size_t c0 = 0; c0 < B; c0 += Bc) {
         r.c0 = (int)c0; r.n = (int)std::min(Bc, B - c0);
         if (en != nullptr) {
-            hipLaunchKernelGGL(en->fwd[tv.w1 ? 1 : 0], dim3((r.n + 15) / 16, (unsigned)K), dim3(64), sh_f, st, r, dyn, c->d_norm.p);
-            hipLaunchKernelGGL(en->bwd, dim3((r.n + 63) / 64, (unsigned)K), dim3(256), sh_b, st, r, dyn, c->d_norm.p);
+            hipLaunchKernelGGL(en->fwd[kind], dim3((r.n + 15) / 16, (unsigned)K), dim3(64), sh_f, st, r, dyn, c->d_norm.p);
+            if (mlp) launch_tv_mlp_seed(tv, r.XS, r.WE, tv_mlp_seed_of(r.WE, r.n, (int)K), (int)K, r.T, r.n, (int)ns, st);
+            hipLaunchKernelGGL(en->bwd[mlp ? 1 : 0], dim3((r.n + 63) / 64, (unsigned)K), dim3(256), sh_b, st, r, dyn, c->d_norm.p);
         } else {
             const dim3 grid((r.n + bs - 1) / bs, (unsigned)K);
             hipLaunchKernelGGL(gen_fwd, grid, dim3(bs), sh_f, st, pd, r, dyn, c->d_norm.p);
-            hipLaunchKernelGGL(k_sagr_gen_bwd, grid, dim3(bs), sh_b, st, pd, r, dyn, c->d_norm.p);
+            if (mlp) launch_tv_mlp_seed(tv, r.XS, r.WE, tv_mlp_seed_of(r.WE, r.n, (int)K), (int)K, r.T, r.n, (int)ns, st);
+            hipLaunchKernelGGL(gen_bwd, grid, dim3(bs), sh_b, st, pd, r, dyn, c->d_norm.p);
         }
         HIP_TRY(c, hipGetLastError());
     }

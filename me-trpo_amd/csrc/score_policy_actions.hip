@@ -17,7 +17,7 @@
 //   * start rows, edge tiles (rows >= B: zero state, zero noise, never read from or written to memory) and padded ensembles as in score_actions.hip.
 //
 //   * terminal value (sact_sum.h: TermVal): behind the loop ST holds s_T; V is evaluated there once per lane in front of the single rounding (a template
-//     parameter, as in score_actions.hip; nothing inside the loop).  Generic path: k_sact_reduce reads the last step's s_out.
+//     parameter TV = the value's kind, as in score_actions.hip; nothing inside the loop).  Generic path: k_sact_reduce reads the last step's s_out.
 //
 // Generic path (every other shape, and force_generic): per chunk of candidates (workspace within 2^26 floats), per head k, per step t the library's
 // own policy forward (launch_policy_actions: noise_in_std = 1 hands the noise row in as its eps), k_spol_act where mean + noise has to be formed or
@@ -38,7 +38,7 @@ struct SpolK {
     TermVal tv;               // the context's terminal value; unset: all NULL
 };
 
-template <int ENV, bool NOISE, bool AOUT, bool TV>
+template <int ENV, bool NOISE, bool AOUT, int TV>
 __global__ void __launch_bounds__(64) k_score_policy_actions(SpolK r, const float* __restrict__ dynp, const float* __restrict__ theta, const float* __restrict__ norm) {
     using C = Cfg<ENV, 64, 32>;
     constexpr int NS = C::NS, NA = C::NA, NST = cdiv(16 * NS, 64);
@@ -112,7 +112,7 @@ __global__ void __launch_bounds__(64) k_score_policy_actions(SpolK r, const floa
         acc.step(-cost, dn, r.gamma, r.stop);
     }
     if (q == 0 && b < r.B) {                                   // rounded to fp32 once, here
-        if (TV) acc.terminal(r.tv.value(ST + e * NS, 1, NS, b, r.per));               // ST holds s_T behind the loop
+        if (TV) acc.terminal(r.tv.template value_of<TV>(ST + e * NS, 1, NS, b, r.per));               // ST holds s_T behind the loop
         const size_t kb = (size_t)k * r.B + b;
         r.ret[kb] = (float)acc.sum;
         if (r.len != nullptr) r.len[kb] = acc.n;
@@ -137,10 +137,10 @@ __global__ void __launch_bounds__(256) k_spol_heads(int32_t* __restrict__ model,
 
 // -------------------------------------------------------------------------------------------------
 typedef void (*spol_kernel_t)(SpolK, const float*, const float*, const float*);
-struct SpolEntry { int env; spol_kernel_t kern[2][2][2]; int w_sz; };      // kern[terminal value set][noise][act_out]
+struct SpolEntry { int env; spol_kernel_t kern[3][2][2]; int w_sz; };      // kern[the terminal value's kind][noise][act_out]
 #define PKERNS(ENVID, TV) {{k_score_policy_actions<ENVID, false, false, TV>, k_score_policy_actions<ENVID, false, true, TV>},   \
                            {k_score_policy_actions<ENVID, true, false, TV>, k_score_policy_actions<ENVID, true, true, TV>}}
-#define PENTRY(ENVID) {ENVID, {PKERNS(ENVID, false), PKERNS(ENVID, true)}, pol_wave_floats<ENVID>()}
+#define PENTRY(ENVID) {ENVID, {PKERNS(ENVID, TV_NONE), PKERNS(ENVID, TV_QUAD), PKERNS(ENVID, TV_MLP)}, pol_wave_floats<ENVID>()}
 static const SpolEntry kSpol[] = {FUSED_HEAD_ENVS(PENTRY)};
 
 static int launch_spol_fused(metrpo_ctx* c, const SpolEntry& en, bool padded, const metrpo_score_policy_actions_args* a, hipStream_t st) {
@@ -149,7 +149,7 @@ static int launch_spol_fused(metrpo_ctx* c, const SpolEntry& en, bool padded, co
     r.init_obs = a->d_init_obs; r.noise = a->d_noise; r.ret = a->d_ret; r.len = a->d_len; r.act_out = a->d_act_out; r.tv = ctx_term_val(c);
     const float* dyn;
     { const int rc = fused_head_dyn(c, padded, st, &dyn); if (rc) return rc; }
-    const spol_kernel_t kern = en.kern[r.tv.w1 ? 1 : 0][a->d_noise != nullptr ? 1 : 0][a->d_act_out != nullptr ? 1 : 0];
+    const spol_kernel_t kern = en.kern[ctx_tv_kind(c)][a->d_noise != nullptr ? 1 : 0][a->d_act_out != nullptr ? 1 : 0];
     const size_t sh = sizeof(float) * (size_t)en.w_sz;
     { const int rc = allow_dynamic_lds(c, (const void*)kern, sh); if (rc) return rc; }
     hipLaunchKernelGGL(kern, dim3((a->B + 15) / 16, c->pd.K), dim3(64), sh, st, r, dyn, c->d_theta.p, c->d_norm.p);
@@ -194,7 +194,7 @@ static int launch_spol_generic(metrpo_ctx* c, const metrpo_score_policy_actions_
                 if (rc) return rc;
             }
             launch_sact_reduce(ws + o_rew, (const uint8_t*)(ws + o_done), n, a->T, a->stop_at_done ? 1 : 0, a->gamma, a->d_ret + (size_t)k * B + c0,
-                               a->d_len ? a->d_len + (size_t)k * B + c0 : nullptr, ctx_term_val(c), ws + o_st + (T & 1) * Bc * ns, (int)ns, (int)c0, per, st);      // the last step's s_out
+                               a->d_len ? a->d_len + (size_t)k * B + c0 : nullptr, ctx_term_val(c), ctx_tv_kind(c) == TV_MLP, ws + o_st + (T & 1) * Bc * ns, (int)ns, (int)c0, per, st);      // the last step's s_out
             if (hipGetLastError() != hipSuccess) return set_err(c, METRPO_EHIP, "score_policy_actions: launch failed");
         }
     }

@@ -30,6 +30,8 @@
 // of WT, only while a value is set; stored, not re-derived); the reverse sweeps start from lambda_T = w_T dV/ds_T formed from the stored XS[T] tile.  The seed
 // enters step T-1 through G and so reaches J_pi(s_T-1) like any lambda.  k_spag_gen_fwd<TV> takes the value as a template parameter (the runtime test reserved
 // a stack slot there); k_spag_fwd, k_spag_bwd and k_spag_gen_bwd test the pointer, runtime-uniform: none of them loses a register or a wave to it.
+// The MLP form (metrpo_set_terminal_value_mlp): k_spag_gen_fwd<TV_MLP> and k_spag_fwd<.., MLP> evaluate it behind their loop; its seed comes from k_tv_mlp_seed
+// (score_actions_grad.hip), launched between the sweeps, and k_spag_bwd<.., SEEDED> / k_spag_gen_bwd<SEEDED> read it in front of their loop.
 //
 // Workspace: ctx->d_spag = XS | WT | AW (| WE) of one chunk, within 2^26 floats (args.chunk > 0 overrides).  d_grad_mean: k_sagr_mean.  No atomics anywhere.
 #include "dyn_tile_step.h"
@@ -54,7 +56,8 @@ struct SpagK {
 };
 
 // ------------------------------------------------ forward sweep: k_score_policy_actions' step, storing ------------------------------------------------
-template <int ENV, bool NOISE>
+// MLP: the terminal value is the two-layer net (sact_sum.h) -- a template parameter; without it the kernel it was, with the runtime test for the quadratic form
+template <int ENV, bool NOISE, bool MLP = false>
 __global__ void __launch_bounds__(64) k_spag_fwd(SpagK r, const float* __restrict__ dynp, const float* __restrict__ theta, const float* __restrict__ norm) {
     using C = Cfg<ENV, 64, 32>;
     constexpr int NS = C::NS, NA = C::NA, NST = cdiv(16 * NS, 64);
@@ -137,7 +140,8 @@ __global__ void __launch_bounds__(64) k_spag_fwd(SpagK r, const float* __restric
         for (int i = lane; i < lim; i += 64) dst[i] = ST[i];
     }
     if (q == 0 && mine) {                                      // rounded to fp32 once, here
-        if (r.tv.set()) r.WE[(size_t)k * r.n + lc] = acc.terminal(r.tv.value(ST + e * NS, 1, NS, b, r.per));      // ST holds s_T behind the loop
+        if constexpr (MLP) r.WE[(size_t)k * r.n + lc] = acc.terminal(r.tv.mlp_value(ST + e * NS, 1, NS, b, r.per));
+        else if (r.tv.set()) r.WE[(size_t)k * r.n + lc] = acc.terminal(r.tv.value(ST + e * NS, 1, NS, b, r.per));      // ST holds s_T behind the loop
         const size_t kb = (size_t)k * r.B + b;
         if (r.ret != nullptr) r.ret[kb] = (float)acc.sum;
         if (r.len != nullptr) r.len[kb] = acc.n;
@@ -158,7 +162,8 @@ struct SpagL {
 };
 
 // ------------------------------------------------ reverse sweep ------------------------------------------------
-template <int ENV>
+// SEEDED: the MLP form -- lambda_T is read from the workspace behind WE, where k_tv_mlp_seed (score_actions_grad.hip) wrote it; without it the kernel it was
+template <int ENV, bool SEEDED = false>
 __global__ void __launch_bounds__(256, 2) k_spag_bwd(SpagK r, const float* __restrict__ dynp, const float* __restrict__ theta, const float* __restrict__ norm) {
     using L = SpagL<ENV>;
     using C = typename L::C;
@@ -229,7 +234,16 @@ __global__ void __launch_bounds__(256, 2) k_spag_bwd(SpagK r, const float* __res
 #pragma unroll
     for (int cb = 0; cb < OUT_CB; ++cb) lam[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
     // the terminal value's seed, lambda_T = w_T dV/ds_T, from the x_T tile in lambda's own layout; w_T is the forward sweep's (WE)
-    if (r.tv.set()) {
+    if constexpr (SEEDED) {
+        const float* __restrict__ seed = tv_mlp_seed_of(r.WE, r.n, (int)gridDim.y) + ((size_t)k * r.n + min(lc, r.n - 1)) * NS;
+#pragma unroll
+        for (int cb = 0; cb < OUT_CB; ++cb)
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                const int dim = 16 * cb + 4 * q + rr;
+                if (dim < NS) lam[cb][rr] = active ? seed[dim] : 0.0f;
+            }
+    } else if (r.tv.set()) {
         const float* XT = W + (r.T & 1) * L::SB;
         const float wT = active ? r.WE[(size_t)k * r.n + min(lc, r.n - 1)] : 0.0f;
 #pragma unroll
@@ -335,7 +349,7 @@ __global__ void __launch_bounds__(256, 2) k_spag_bwd(SpagK r, const float* __res
 // -------------------------------------------------------------------------------------------------
 // Generic path (sact_sum.h: GradBufs with the policy's rows).
 // TV: with a terminal value -- a template parameter, so that the instantiation without one is the kernel it was (the runtime test costs it a stack slot)
-template <bool TV>
+template <int TV>
 __global__ void k_spag_gen_fwd(ProblemDesc pd, SpagK r, const float* __restrict__ dynp, const float* __restrict__ theta, const float* __restrict__ norm) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int LD = blockDim.x, tid = threadIdx.x;
@@ -383,12 +397,14 @@ __global__ void k_spag_gen_fwd(ProblemDesc pd, SpagK r, const float* __restrict_
         for (int i = 0; i < ns; ++i) e.S[i * LD + tid] = e.XN[i * LD + tid];
     }
     if (active) {
-        if (TV) r.WE[(size_t)k * r.n + lc] = acc.terminal(r.tv.value(e.S + tid, LD, ns, b, r.per));      // S holds s_T behind the loop
+        if (TV) r.WE[(size_t)k * r.n + lc] = acc.terminal(r.tv.template value_of<TV>(e.S + tid, LD, ns, b, r.per));      // S holds s_T behind the loop
         if (r.ret != nullptr) r.ret[(size_t)k * r.B + b] = (float)acc.sum;
         if (r.len != nullptr) r.len[(size_t)k * r.B + b] = acc.n;
     }
 }
 
+// SEEDED: as k_spag_bwd's
+template <bool SEEDED>
 __global__ void k_spag_gen_bwd(ProblemDesc pd, SpagK r, const float* __restrict__ dynp, const float* __restrict__ theta, const float* __restrict__ norm) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int LD = blockDim.x, tid = threadIdx.x;
@@ -403,7 +419,10 @@ __global__ void k_spag_gen_bwd(ProblemDesc pd, SpagK r, const float* __restrict_
     const float* __restrict__ log_std = theta + pn.n_params;
     const float* xs = r.XS + (size_t)k * (r.T + 1) * r.n * ns;
     for (int i = 0; i < ns; ++i) e.LAM[i * LD + tid] = 0.0f;
-    if (r.tv.set() && active) {                              // the terminal value's seed: lambda_T = w_T dV/ds_T; it reaches J_pi through G like any lambda
+    if constexpr (SEEDED) {
+        const float* seed = tv_mlp_seed_of(r.WE, r.n, (int)gridDim.y) + ((size_t)k * r.n + lc) * ns;
+        if (active) for (int i = 0; i < ns; ++i) e.LAM[i * LD + tid] = seed[i];
+    } else if (r.tv.set() && active) {                       // the terminal value's seed: lambda_T = w_T dV/ds_T; it reaches J_pi through G like any lambda
         const float wT = r.WE[(size_t)k * r.n + lc];
         for (int i = 0; i < ns; ++i) e.LAM[i * LD + tid] = wT * r.tv.grad(i, xs[((size_t)r.T * r.n + lc) * ns + i]);
     }
@@ -453,8 +472,9 @@ __global__ void k_spag_gen_bwd(ProblemDesc pd, SpagK r, const float* __restrict_
 
 // -------------------------------------------------------------------------------------------------
 typedef void (*spag_kernel_t)(SpagK, const float*, const float*, const float*);
-struct SpagEntry { int env; spag_kernel_t fwd[2], bwd; int fwd_floats, bwd_floats; };      // fwd[noise]
-#define GENTRY(ENVID) {ENVID, {k_spag_fwd<ENVID, false>, k_spag_fwd<ENVID, true>}, k_spag_bwd<ENVID>, pol_wave_floats<ENVID>(), SpagL<ENVID>::TOTAL}
+struct SpagEntry { int env; spag_kernel_t fwd[2][2], bwd[2]; int fwd_floats, bwd_floats; };      // fwd[the value is the MLP][noise], bwd[the value is the MLP]
+#define GENTRY(ENVID) {ENVID, {{k_spag_fwd<ENVID, false>, k_spag_fwd<ENVID, true>}, {k_spag_fwd<ENVID, false, true>, k_spag_fwd<ENVID, true, true>}},   \
+                       {k_spag_bwd<ENVID>, k_spag_bwd<ENVID, true>}, pol_wave_floats<ENVID>(), SpagL<ENVID>::TOTAL}
 static const SpagEntry kSpag[] = {FUSED_HEAD_ENVS(GENTRY)};
 
 int run_score_policy_actions_grad(metrpo_ctx* c, const metrpo_score_policy_actions_grad_args* a, hipStream_t st) {
@@ -462,13 +482,15 @@ int run_score_policy_actions_grad(metrpo_ctx* c, const metrpo_score_policy_actio
     const size_t ns = pd.ns, na = pd.na, B = a->B, T = a->T, K = pd.K;
     bool padded = false;
     const SpagEntry* en = a->force_generic ? nullptr : fused_head_entry(kSpag, c, 65535, &padded);      // the heads are gridDim.y; the class holds the 2 x 32 tanh policy
-    // ---- a chunk's workspace (floats): XS [K][T + 1][Bc][ns] | WT [K][T][Bc] | AW [K][T][Bc][na] | (a terminal value is set) WE [K][Bc]; within 2^26 floats unless args.chunk says otherwise ----
+    // ---- a chunk's workspace (floats): XS [K][T + 1][Bc][ns] | WT [K][T][Bc] | AW [K][T][Bc][na] | (a terminal value is set) WE [K][Bc] | (it is the MLP) its seed [K][Bc][ns];
+    // within 2^26 floats unless args.chunk says otherwise ----
     const TermVal tv = ctx_term_val(c);
-    const size_t per_cand = K * ((T + 1) * ns + T + T * na + (tv.w1 ? 1 : 0));
+    const bool mlp = ctx_tv_kind(c) == TV_MLP;
+    const size_t per_cand = K * ((T + 1) * ns + T + T * na + (tv.w1 ? 1 : 0) + (mlp ? ns : 0));
     const size_t Bc = score_chunk(B, per_cand, (size_t)a->chunk);
     const size_t o_wt = (K * (T + 1) * Bc * ns + 3) & ~(size_t)3, o_aw = (o_wt + K * T * Bc + 3) & ~(size_t)3;
     const size_t o_we = o_aw + K * T * Bc * na;
-    { const int rc = ws_grow(c, c->d_spag, sizeof(float) * (o_we + (tv.w1 ? K * Bc : 0))); if (rc) return rc; }
+    { const int rc = ws_grow(c, c->d_spag, sizeof(float) * (o_we + (tv.w1 ? K * Bc : 0) + (mlp ? K * Bc * ns : 0))); if (rc) return rc; }
     float* ws = (float*)c->d_spag.p;
     SpagK r = {};
     r.B = a->B; r.T = a->T; r.per = a->B / a->S; r.stop = a->stop_at_done ? 1 : 0; r.in_std = a->noise_in_std ? 1 : 0; r.gamma = a->gamma;
@@ -479,31 +501,35 @@ int run_score_policy_actions_grad(metrpo_ctx* c, const metrpo_score_policy_actio
     int bs = 64;
     spag_kernel_t fwd = nullptr;
     void (*gen_fwd)(ProblemDesc, SpagK, const float*, const float*, const float*) = nullptr;
+    void (*gen_bwd)(ProblemDesc, SpagK, const float*, const float*, const float*) = nullptr;
     if (en != nullptr) {
         { const int rc = fused_head_dyn(c, padded, st, &dyn); if (rc) return rc; }
-        fwd = en->fwd[a->d_noise != nullptr ? 1 : 0];
+        fwd = en->fwd[mlp ? 1 : 0][a->d_noise != nullptr ? 1 : 0];
         sh_f = sizeof(float) * (size_t)en->fwd_floats; sh_b = sizeof(float) * (size_t)en->bwd_floats;
         int rc = allow_dynamic_lds(c, (const void*)fwd, sh_f);
-        if (!rc) rc = allow_dynamic_lds(c, (const void*)en->bwd, sh_b);
+        if (!rc) rc = allow_dynamic_lds(c, (const void*)en->bwd[mlp ? 1 : 0], sh_b);
         if (rc) return rc;
     } else {
         const size_t fpt = grad_gen_floats(pd, true);
         if ((bs = lds_block_size(fpt)) == 0) return set_err(c, METRPO_EUNSUPPORTED, "score_policy_actions_grad: layer widths exceed the LDS budget of the generic kernel");
         sh_f = sh_b = fpt * bs * sizeof(float);
-        gen_fwd = tv.w1 ? k_spag_gen_fwd<true> : k_spag_gen_fwd<false>;
+        gen_fwd = mlp ? k_spag_gen_fwd<TV_MLP> : (tv.w1 ? k_spag_gen_fwd<TV_QUAD> : k_spag_gen_fwd<TV_NONE>);
+        gen_bwd = mlp ? k_spag_gen_bwd<true> : k_spag_gen_bwd<false>;
         int rc = allow_dynamic_lds(c, (const void*)gen_fwd, sh_f);
-        if (!rc) rc = allow_dynamic_lds(c, (const void*)k_spag_gen_bwd, sh_b);
+        if (!rc) rc = allow_dynamic_lds(c, (const void*)gen_bwd, sh_b);
         if (rc) return rc;
     }
     for (size_t c0 = 0; c0 < B; c0 += Bc) {
         r.c0 = (int)c0; r.n = (int)std::min(Bc, B - c0);
         if (en != nullptr) {
             hipLaunchKernelGGL(fwd, dim3((r.n + 15) / 16, (unsigned)K), dim3(64), sh_f, st, r, dyn, c->d_theta.p, c->d_norm.p);
-            hipLaunchKernelGGL(en->bwd, dim3((r.n + 63) / 64, (unsigned)K), dim3(256), sh_b, st, r, dyn, c->d_theta.p, c->d_norm.p);
+            if (mlp) launch_tv_mlp_seed(tv, r.XS, r.WE, tv_mlp_seed_of(r.WE, r.n, (int)K), (int)K, r.T, r.n, (int)ns, st);
+            hipLaunchKernelGGL(en->bwd[mlp ? 1 : 0], dim3((r.n + 63) / 64, (unsigned)K), dim3(256), sh_b, st, r, dyn, c->d_theta.p, c->d_norm.p);
         } else {
             const dim3 grid((r.n + bs - 1) / bs, (unsigned)K);
             hipLaunchKernelGGL(gen_fwd, grid, dim3(bs), sh_f, st, pd, r, dyn, c->d_theta.p, c->d_norm.p);
-            hipLaunchKernelGGL(k_spag_gen_bwd, grid, dim3(bs), sh_b, st, pd, r, dyn, c->d_theta.p, c->d_norm.p);
+            if (mlp) launch_tv_mlp_seed(tv, r.XS, r.WE, tv_mlp_seed_of(r.WE, r.n, (int)K), (int)K, r.T, r.n, (int)ns, st);
+            hipLaunchKernelGGL(gen_bwd, grid, dim3(bs), sh_b, st, pd, r, dyn, c->d_theta.p, c->d_norm.p);
         }
         HIP_TRY(c, hipGetLastError());
     }

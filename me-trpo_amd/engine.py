@@ -586,8 +586,26 @@ class Engine(object):
         self._chk(lib.metrpo_set_terminal_value(self._ctx, _ptr(a), _ptr(b), _ptr(c), int(c.numel()), self._stream()))
         self._tv_keep = (a, b, c)                                                  # alive until the stream has consumed them
 
+    def set_terminal_value_mlp(self, params, hidden, bias=0.0):
+        """The terminal value's second form (include/metrpo.h: metrpo_set_terminal_value_mlp), a two-layer tanh net on o = clip(s, -10, 10):
+        V(s) = bias + b2 + W2 . tanh(W1^T tanh(W0^T o + b0) + b1).  params: the packed vector W0 [ns][h1] | b0 | W1 [h1][h2] | b1 | W2 [h2] | b2
+        (planning.ValueMLP.packed() forms it, input normaliser folded in); hidden = (h1, h2), each in 1 .. 32; bias a scalar, or [S] as in
+        set_terminal_value.  Replaces a quadratic value that is set, and is replaced by one; clear_terminal_value() clears either."""
+        dev = self.device
+        h1, h2 = (int(h) for h in hidden)
+        n = self.ns * h1 + h1 + h1 * h2 + h2 + h2 + 1
+        p = _f32(params, dev, (n,))
+        c = _f32(bias, dev).reshape(-1)
+        self._chk(lib.metrpo_set_terminal_value_mlp(self._ctx, _ptr(p), h1, h2, _ptr(c), int(c.numel()), self._stream()))
+        self._tv_keep = (p, c)                                                     # alive until the stream has consumed them
+
     def clear_terminal_value(self):
         self._chk(lib.metrpo_clear_terminal_value(self._ctx))
+
+    @property
+    def terminal_value_kind(self):
+        """0 while no terminal value is set, 1: the quadratic form (set_terminal_value), 2: the MLP (set_terminal_value_mlp)."""
+        return int(lib.metrpo_terminal_value_kind(self._ctx))
 
     @property
     def terminal_value(self):

@@ -19,7 +19,9 @@ each refit, and ShootingController(policy_prior=True, noise_grad_steps=n) plans 
 
 A value behind the horizon: Engine.set_terminal_value / metrpo_set_terminal_value adds gamma^T alive_T V(s_T) to every return above and seeds the
 gradients to match.  The scorers are closures over the engine, so every planner here has it without a signature change: set it, plan, clear it.
-baseline_terminal_value forms V from a LinearFeatureBaseline fit; ShootingController(terminal_value=baseline) does the setting and clearing."""
+baseline_terminal_value forms V from a LinearFeatureBaseline fit; ShootingController(terminal_value=baseline) does the setting and clearing.
+The value's second form is a two-layer tanh net (Engine.set_terminal_value_mlp): ValueMLP holds and fits one, value_targets forms its fit targets, and
+ShootingController(terminal_value=ValueMLP) plans with it."""
 import numpy as np
 import torch
 
@@ -552,6 +554,102 @@ def baseline_terminal_value(baseline, t_index, ns):
     return c[:ns], c[ns:2 * ns], bias
 
 
+class ValueMLP(object):
+    """A two-layer tanh value net for Engine.set_terminal_value_mlp (include/metrpo.h: metrpo_set_terminal_value_mlp): a plain container of the six
+    arrays W0 [ns, h1], b0 [h1], W1 [h1, h2], b1 [h2], W2 [h2], b2 [1] (float64 tensors, weights in-major) and an input normaliser mean, std [ns]:
+        o = clip(s, -10, 10);  x = (o - mean) / std;  V = b2 + W2 . tanh(W1^T tanh(W0^T x + b0) + b1)
+    The clip acts on the raw state, so packed() folds the normaliser into W0 / b0 exactly and the library never sees it.  `bias` (a scalar, or [S]:
+    one per start state of the scoring call) is what ShootingController hands on with the net; predict() adds it only when it is a scalar.
+    Fitting is torch autograd (plumbing, not a hot path); value_targets below forms the targets."""
+
+    def __init__(self, ns, hidden=(32, 32), generator=None):
+        self.ns, self.hidden = int(ns), tuple(int(h) for h in hidden)
+        if len(self.hidden) != 2 or min(self.hidden) < 1 or max(self.hidden) > 32:
+            raise ValueError("ValueMLP: hidden = %r must be two widths in 1 .. 32" % (hidden,))
+        h1, h2 = self.hidden
+        draw = lambda *shape: torch.randn(*shape, dtype=torch.float64, generator=generator)
+        self.W0, self.b0 = draw(self.ns, h1) / np.sqrt(self.ns), torch.zeros(h1, dtype=torch.float64)
+        self.W1, self.b1 = draw(h1, h2) / np.sqrt(h1), torch.zeros(h2, dtype=torch.float64)
+        self.W2, self.b2 = draw(h2) / np.sqrt(h2), torch.zeros(1, dtype=torch.float64)
+        self.mean, self.std = torch.zeros(self.ns, dtype=torch.float64), torch.ones(self.ns, dtype=torch.float64)
+        self.bias = 0.0
+
+    def arrays(self):
+        return [self.W0, self.b0, self.W1, self.b1, self.W2, self.b2]
+
+    @staticmethod
+    def _forward(arrays, mean, std, states):
+        W0, b0, W1, b1, W2, b2 = arrays
+        x = (torch.clamp(states, -10.0, 10.0) - mean) / std
+        return torch.tanh(torch.tanh(x @ W0 + b0) @ W1 + b1) @ W2 + b2
+
+    def predict(self, states):
+        """V of states [N, ns] (tensor or array) -> [N] float64 tensor on the states' device"""
+        s = torch.as_tensor(states).to(torch.float64)
+        dev = s.device
+        v = self._forward([a.to(dev) for a in self.arrays()], self.mean.to(dev), self.std.to(dev), s.reshape(-1, self.ns))
+        return v + float(self.bias) if np.ndim(self.bias) == 0 else v
+
+    def fit(self, states, targets, n_steps, lr, normalise=True):
+        """Adam on the mean squared error of V(states) against targets [N], n_steps full-batch steps from the current arrays, on the states' device
+        (hand it tensors on the engine's device).  normalise: mean / std of the CLIPPED states first (std floored at 1e-6).  -> the losses [n_steps + 1],
+        before the first step and behind every step."""
+        s = torch.as_tensor(states).to(torch.float64).reshape(-1, self.ns)
+        dev = s.device
+        y = torch.as_tensor(targets).to(device=dev, dtype=torch.float64).reshape(-1)
+        if y.shape[0] != s.shape[0]:
+            raise ValueError("ValueMLP.fit: %d targets for %d states" % (y.shape[0], s.shape[0]))
+        if normalise:
+            o = torch.clamp(s, -10.0, 10.0)
+            self.mean, self.std = o.mean(dim=0), torch.clamp(o.std(dim=0, unbiased=False), min=1e-6)
+        mean, std = self.mean.to(dev), self.std.to(dev)
+        par = [a.detach().to(dev).clone().requires_grad_(True) for a in self.arrays()]
+        opt = torch.optim.Adam(par, lr=lr)
+        losses = []
+        for _ in range(int(n_steps)):
+            opt.zero_grad()
+            loss = torch.mean((self._forward(par, mean, std, s) - y) ** 2)
+            loss.backward()
+            opt.step()
+            losses.append(loss.detach())
+        with torch.no_grad():
+            losses.append(torch.mean((self._forward(par, mean, std, s) - y) ** 2))
+        self.W0, self.b0, self.W1, self.b1, self.W2, self.b2 = (p.detach() for p in par)
+        return torch.stack(losses).cpu().numpy()
+
+    def packed(self):
+        """The library's d_params, float32: W0' | b0' | W1 | b1 | W2 | b2 with the normaliser folded in, W0' = W0 / std[:, None], b0' = b0 - (mean / std) @ W0"""
+        dev = self.W0.device
+        mean, std = self.mean.to(dev), self.std.to(dev)
+        W0 = self.W0 / std[:, None]
+        b0 = self.b0 - (mean / std) @ self.W0
+        return torch.cat([W0.reshape(-1), b0, self.W1.reshape(-1), self.b1, self.W2, self.b2]).to(torch.float32)
+
+
+def value_targets(engine, baseline, paths, gamma):
+    """Fit targets for ValueMLP.fit from recorded or imagined paths (dicts with 'observations' [L, ns] and 'rewards' [L], the baseline's own form):
+    every row's discounted return-to-go  G_t = sum_{u >= t} gamma^(u - t) r_u.  A path that was cut off rather than ended (path['truncated'] set) and a
+    fitted baseline: the last row's own reward is replaced by the baseline's prediction there, so the tail behind the cut is the baseline's estimate,
+    G_t = sum_{t <= u < L - 1} gamma^(u - t) r_u + gamma^(L - 1 - t) V_b(row L - 1).  baseline None: nothing is bootstrapped.
+    -> (states [N, ns], targets [N]) float64 tensors on the engine's device, rows of all paths in order."""
+    states, targets = [], []
+    for path in paths:
+        obs = np.asarray(path['observations'], dtype=np.float64)
+        r = np.asarray(path['rewards'], dtype=np.float64).reshape(-1).copy()
+        if obs.ndim != 2 or obs.shape[0] != r.shape[0]:
+            raise ValueError("value_targets: observations %s do not go with %d rewards" % (obs.shape, r.shape[0]))
+        if baseline is not None and path.get('truncated', False) and r.shape[0] > 0:
+            r[-1] = float(np.asarray(baseline.predict(path))[-1])
+        g, acc = np.zeros_like(r), 0.0
+        for t in range(r.shape[0] - 1, -1, -1):
+            acc = r[t] + gamma * acc
+            g[t] = acc
+        states.append(obs); targets.append(g)
+    dev = engine.device if engine is not None else torch.device('cpu')
+    return (torch.as_tensor(np.concatenate(states, axis=0), dtype=torch.float64, device=dev),
+            torch.as_tensor(np.concatenate(targets, axis=0), dtype=torch.float64, device=dev))
+
+
 class ShootingController(object):
     """Model-predictive control by CEM with a warm start, with the policy's call shape: get_actions(obs [S, ns]) -> (actions [S, na], {}).
     Every call plans `horizon` steps ahead from obs, returns the first action of the plan's mean and keeps the rest: the next call starts from the
@@ -564,7 +662,9 @@ class ShootingController(object):
     NOISE, the policy path included.
     terminal_value=baseline (a fitted LinearFeatureBaseline, or its coefficient vector) plans with a value behind the horizon: the controller counts
     every env's path steps (one per get_actions call, zeroed by reset), and around each plan sets the engine's terminal value to the baseline at
-    path step counter + horizon -- one bias per env -- and clears it again.  None: nothing is set, cleared or counted."""
+    path step counter + horizon -- one bias per env -- and clears it again.  None: nothing is set, cleared or counted.
+    terminal_value=ValueMLP: the net is set around each plan in the same way (Engine.set_terminal_value_mlp) with the net's own `bias`: a scalar unless
+    the caller made it [S]."""
 
     def __init__(self, engine, horizon, n_candidates, n_elites, n_iters, init_mean=None, init_std=1.0, alpha=0.0, min_std=0.0, gamma=1.0,
                  aggregate='mean', generator=None, stop_at_done=True, scorer=None, na=None, grad_steps=0, grad_lr=0.05, refine='elites', grad_scorer=None,
@@ -634,7 +734,10 @@ class ShootingController(object):
         S = obs.shape[0] if obs.ndim == 2 else 1
         if self._steps is None or self._steps.shape[0] != S:
             self._steps = np.zeros(S, dtype=np.int64)
-        self.engine.set_terminal_value(*baseline_terminal_value(self.terminal_value, self._steps + self.horizon, self.engine.ns))
+        if isinstance(self.terminal_value, ValueMLP):
+            self.engine.set_terminal_value_mlp(self.terminal_value.packed(), self.terminal_value.hidden, self.terminal_value.bias)
+        else:
+            self.engine.set_terminal_value(*baseline_terminal_value(self.terminal_value, self._steps + self.horizon, self.engine.ns))
         try:
             out = self._plan(observations)
         finally:

@@ -11,8 +11,10 @@ Timed, as medians of interleaved rounds (CUDA events around `reps` back-to-back 
 Expected pgrad / grad from the matrix-instruction counts per step and tile (swimmer, counted off the source): forward 92 + 30 (policy), reverse
 76 + 112 + 22 (the policy's hidden layers) + 28 (its adjoint: 2 x 2 + 8 x 2 + 8) = 360 against 92 + 76 + 112 = 280: 1.29.
 Parity printed with the times: fused against generic, rel-L2 of the gradient per head at worst; ret against score_policy_actions in bits.
-Usage: score_policy_actions_grad_time.py [--out FILE] [--reps N] [--rounds R] [--T 30] [--sizes 4096,512] [--S 8] [--terminal-value]
---terminal-value: with a terminal value set (metrpo_set_terminal_value: w1 ~ 0.5 N(0, 1), w2 ~ 0.1 N(0, 1), one bias ~ N(0, 1) for every candidate: the sides of this tool differ in S)."""
+Usage: score_policy_actions_grad_time.py [--out FILE] [--reps N] [--rounds R] [--T 30] [--sizes 4096,512] [--S 8] [--terminal-value | --terminal-mlp]
+--terminal-value: with a terminal value set (metrpo_set_terminal_value: w1 ~ 0.5 N(0, 1), w2 ~ 0.1 N(0, 1), one bias ~ N(0, 1) for every candidate: the sides of this tool differ in S).
+--terminal-mlp: with the value's MLP form set instead (metrpo_set_terminal_value_mlp: a 32 x 32 tanh net, W0 ~ N(0, 1) / sqrt(ns), W1 ~ N(0, 1) / sqrt(32),
+W2 ~ 2 N(0, 1) / sqrt(32), biases 0.1 N(0, 1), one bias ~ N(0, 1) for every candidate)."""
 import sys, os, argparse
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
@@ -53,6 +55,7 @@ def main():
     ap.add_argument('--S', type=int, default=8)
     ap.add_argument('--sizes', default='4096,512')
     ap.add_argument('--terminal-value', action='store_true')
+    ap.add_argument('--terminal-mlp', action='store_true')
     a = ap.parse_args()
     env, K, T, S, gamma = 'swimmer', 5, a.T, a.S, 0.99
     dm, theta, pdims, pool = O.make_problem(env, K=K, dyn_hidden=(64, 64), pol_hidden=(32, 32), seed=0, n_pool=64)
@@ -64,11 +67,17 @@ def main():
     if a.terminal_value:                                       # draws of its own: the candidates below are the same with and without
         tvr = np.random.RandomState(1)
         eng.set_terminal_value(0.5 * tvr.randn(dm.ns), 0.1 * tvr.randn(dm.ns), tvr.randn(1))
+    if a.terminal_mlp:
+        if a.terminal_value:
+            ap.error('--terminal-value and --terminal-mlp: one form at a time')
+        tvr, h = np.random.RandomState(1), 32
+        net = [tvr.randn(dm.ns, h) / np.sqrt(dm.ns), 0.1 * tvr.randn(h), tvr.randn(h, h) / np.sqrt(h), 0.1 * tvr.randn(h), 2.0 * tvr.randn(h) / np.sqrt(h), 0.1 * tvr.randn(1)]
+        eng.set_terminal_value_mlp(np.concatenate([x.reshape(-1) for x in net]), (h, h), tvr.randn(1))
     m = MFMA_SWIMMER
     mine = m['dyn_fwd'] + m['pol_fwd'] + m['dyn_recompute'] + m['dyn_adjoint'] + m['pol_hidden'] + m['pol_adjoint']
     theirs = m['dyn_fwd'] + m['dyn_recompute'] + m['dyn_adjoint']
     lines = ["# metrpo_score_policy_actions_grad%s: %s, K = %d, 2x64 dynamics, 2x32 policy, T = %d, S = %d start states, gamma = %g.  %d interleaved rounds of %d"
-             % (" with a terminal value" if a.terminal_value else "", env, K, T, S, gamma, a.rounds, a.reps),
+             % (" with a terminal value" if a.terminal_value else (" with an MLP terminal value" if a.terminal_mlp else ""), env, K, T, S, gamma, a.rounds, a.reps),
              "# back-to-back calls (generic: %d), CUDA events, 2 warm-up calls each; medians and [min, max] over the rounds.  Device: %s"
              % (max(1, a.reps // 4), torch.cuda.get_device_name(0)),
              "# matrix instructions per step and tile, from the source: %d (forward %d + %d policy; reverse %d + %d + %d policy hidden + %d policy adjoint) against"
