@@ -17,6 +17,11 @@ The same in NOISE space around the policy: Engine.score_policy_actions_grad / me
 included; refine_noise is refine_actions there (projection clamp(+-noise_clip)), plan_cem_policy_gd refines plan_cem_policy's elites (or all) before
 each refit, and ShootingController(policy_prior=True, noise_grad_steps=n) plans with it.
 
+Structure: one loop, two spaces, optional refinement.  _cem is the CEM iteration, written once; plan_cem, plan_cem_gd, plan_cem_policy and
+plan_cem_policy_gd check their arguments (_check_cem), resolve their scorers (_resolve, _resolve_pair), call it once and name the result.  The two spaces
+differ in the clamp bound (1 / noise_clip), in the planted delta = 0 candidate and in the scorers; refinement is one _refine call before or behind the
+top-k.  A batch of supplied candidates goes through _candidates (score_*_sequences, refine_*).
+
 A value behind the horizon: Engine.set_terminal_value / metrpo_set_terminal_value adds gamma^T alive_T V(s_T) to every return above and seeds the
 gradients to match.  The scorers are closures over the engine, so every planner here has it without a signature change: set it, plan, clear it.
 baseline_terminal_value forms V from a LinearFeatureBaseline fit; ShootingController(terminal_value=baseline) does the setting and clearing.
@@ -75,11 +80,28 @@ def aggregate_heads_grad(ret, grad, aggregate='mean'):
     raise ValueError("aggregate: %r is none of 'mean', 'min', ('pessimistic', beta)" % (aggregate,))
 
 
-def _setup(engine, states, scorer, na, gamma, stop_at_done):
-    if scorer is None:
-        if engine is None:
-            raise ValueError("an engine or a scorer is needed")
-        scorer = engine_scorer(engine, gamma, stop_at_done)
+def _resolve(engine, given, factory, what, *args):
+    """The scorer (what = 'scorer') or gradient scorer ('grad_scorer') a call uses: the one given, else factory(engine, *args)"""
+    if given is not None:
+        return given
+    if engine is None:
+        raise ValueError("an engine or a %s is needed" % what)
+    return factory(engine, *args)
+
+
+def _resolve_pair(engine, scorer, grad_scorer, factory, grad_factory, grad_steps, *args):
+    """(scorer, grad_scorer) of a _gd planner.  No gradient scorer is built where none is used (grad_steps = 0 with an engine or a scorer); with neither
+    scorer nor engine the scorer is the gradient scorer's first output."""
+    derived = scorer is None and engine is None
+    if grad_steps > 0 or derived:
+        grad_scorer = _resolve(engine, grad_scorer, grad_factory, 'grad_scorer', *args)
+    if derived:
+        return (lambda a, init: grad_scorer(a, init)[0]), grad_scorer
+    return _resolve(engine, scorer, factory, 'scorer', *args), grad_scorer
+
+
+def _states(engine, states, na):
+    """-> (states [S, ns] float32 contiguous on the engine's device, na): the engine's na, else the one passed"""
     dev = engine.device if engine is not None else None
     states = torch.as_tensor(states, device=dev).to(torch.float32)
     if states.dim() == 1:
@@ -91,7 +113,7 @@ def _setup(engine, states, scorer, na, gamma, stop_at_done):
         na = engine.na
     if na is None or int(na) < 1:
         raise ValueError("na is needed when there is no engine")
-    return scorer, states.contiguous(), int(na)
+    return states.contiguous(), int(na)
 
 
 def _device_major(cand):
@@ -100,20 +122,39 @@ def _device_major(cand):
     return cand.permute(2, 0, 1, 3).reshape(T, S * N, na).contiguous()
 
 
+def _from_device_major(x, S, N):
+    """[T, S * N, na] -> [S, N, T, na]"""
+    T, _, na = x.shape
+    return x.reshape(T, S, N, na).permute(1, 2, 0, 3).contiguous()
+
+
+def _candidates(engine, states, x, name):
+    """Supplied candidates x (a tensor: [S, N, T, na], or [S, T, na] = one per state; `name` is the word for them in the message) with their states
+    -> (states [S, ns], the candidates device-major [T, S * N, na], S, N, single: whether x was the 3-D form)"""
+    states, na = _states(engine, states, x.shape[-1] if x.dim() >= 1 else None)
+    cand = x.to(device=states.device, dtype=torch.float32)
+    S = states.shape[0]
+    single = cand.dim() == 3
+    if single:
+        cand = cand.unsqueeze(1)
+    if cand.dim() != 4 or cand.shape[0] != S or cand.shape[3] != na or cand.shape[1] < 1 or cand.shape[2] < 1:
+        raise ValueError("%s: expected [%d, N, T, %d] or [%d, T, %d], got %s" % (name, S, na, S, na, tuple(x.shape)))
+    return states, _device_major(cand), S, cand.shape[1], single
+
+
+def _score_candidates(engine, states, x, name, scorer, aggregate):
+    """score_action_sequences / score_noise_sequences behind the scorer's resolution"""
+    states, cand, S, N, single = _candidates(engine, states, x, name)
+    scores = aggregate_heads(scorer(cand, states), aggregate).reshape(S, N)
+    return scores[:, 0] if single else scores
+
+
 def score_action_sequences(engine, states, actions, gamma=1.0, stop_at_done=True, aggregate='mean', scorer=None):
     """Score supplied action sequences: states [S, ns], actions [S, N, T, na] (N candidates per state) or [S, T, na] (one each), trajectory-major
     and unclipped (clipped on the device).  -> scores [S, N] (or [S]): the heads' discounted returns folded by `aggregate`.  A device tensor."""
     act = torch.as_tensor(actions)
-    scorer, states, na = _setup(engine, states, scorer, act.shape[-1] if act.dim() >= 1 else None, gamma, stop_at_done)
-    act = act.to(device=states.device, dtype=torch.float32)
-    S = states.shape[0]
-    single = act.dim() == 3
-    if single:
-        act = act.unsqueeze(1)
-    if act.dim() != 4 or act.shape[0] != S or act.shape[3] != na or act.shape[1] < 1 or act.shape[2] < 1:
-        raise ValueError("actions: expected [%d, N, T, %d] or [%d, T, %d], got %s" % (S, na, S, na, tuple(torch.as_tensor(actions).shape)))
-    scores = aggregate_heads(scorer(_device_major(act), states), aggregate).reshape(S, act.shape[1])
-    return scores[:, 0] if single else scores
+    scorer = _resolve(engine, scorer, engine_scorer, 'scorer', gamma, stop_at_done)
+    return _score_candidates(engine, states, act, 'actions', scorer, aggregate)
 
 
 def _check_counts(horizon, n_candidates):
@@ -126,7 +167,8 @@ def plan_random_shooting(engine, states, horizon, n_candidates, generator=None, 
     """Random shooting: per state, n_candidates sequences of `horizon` actions drawn uniformly from [-1, 1], scored in one call, the best taken.
     -> dict(actions [S, T, na] the best sequence, score [S] its score, scores [S, N] all of them), device tensors."""
     T, N = _check_counts(horizon, n_candidates)
-    scorer, states, na = _setup(engine, states, scorer, na, gamma, stop_at_done)
+    scorer = _resolve(engine, scorer, engine_scorer, 'scorer', gamma, stop_at_done)
+    states, na = _states(engine, states, na)
     S, dev = states.shape[0], states.device
     cand = torch.rand(T, S, N, na, generator=generator, device=dev, dtype=torch.float32) * 2.0 - 1.0
     scores = aggregate_heads(scorer(cand.reshape(T, S * N, na), states), aggregate).reshape(S, N)
@@ -147,6 +189,68 @@ def _time_major_param(x, T, S, na, dev, name):
     raise ValueError("%s: expected a scalar, [%d, %d] or [%d, %d, %d], got %s" % (name, T, na, S, T, na, tuple(x.shape)))
 
 
+def _check_cem(horizon, n_candidates, n_elites, n_iters, alpha, grad_steps=0, grad_lr=0.05, optimizer='adam', refine='elites'):
+    """The CEM family's argument check -> (T, N, E, n_iters, grad_steps) as ints.  The plain planners leave the refinement arguments at values that pass."""
+    T, N = _check_counts(horizon, n_candidates)
+    E, n_iters = int(n_elites), int(n_iters)
+    grad_steps = _check_refine(grad_steps, grad_lr, optimizer)
+    if refine not in ('elites', 'all'):
+        raise ValueError("refine: %r is neither 'elites' nor 'all'" % (refine,))
+    if not (1 <= E <= N):
+        raise ValueError("n_elites must be in 1 ... n_candidates = %d, got %r" % (N, n_elites))
+    if n_iters < 1:
+        raise ValueError("n_iters must be positive, got %r" % (n_iters,))
+    if not (0.0 <= float(alpha) < 1.0):
+        raise ValueError("alpha must be in [0, 1), got %r" % (alpha,))
+    return T, N, E, n_iters, grad_steps
+
+
+def _cem(scorer, states, na, T, N, E, n_iters, init_mean, init_std, alpha, min_std, aggregate, generator, bound, plant_zero,
+         grad_scorer=None, grad_steps=0, refine='elites', refine_args=()):
+    """The CEM loop of the four planners, over candidates clamped to +-bound (1 for actions, noise_clip for noise around the policy).
+    plant_zero: candidate 0 of every state is set to 0 in every iteration (plan_cem_policy's include_policy) and its DRAWN score in iteration 0 is kept.
+    grad_steps > 0: _refine with refine_args = (lr, optimizer, betas, eps), on all candidates before the top-k (refine = 'all') or on the elites behind it.
+    One randn(T, S, N, na) per iteration; nothing is read back.
+    -> (mean [S, T, na], std [S, T, na], best [S, T, na], best_score [S], history [n_iters, S], elites [S, E], policy_score [S] or None)"""
+    S, dev = states.shape[0], states.device
+    mean = _time_major_param(0.0 if init_mean is None else init_mean, T, S, na, dev, 'init_mean')
+    std = _time_major_param(init_std, T, S, na, dev, 'init_std')
+    alpha, min_std = float(alpha), float(min_std)
+    best_score = torch.full((S,), float('-inf'), device=dev, dtype=torch.float32)
+    best = torch.zeros(T, S, na, device=dev, dtype=torch.float32)
+    history = torch.empty(n_iters, S, device=dev, dtype=torch.float32)
+    policy_score = None
+    for it in range(n_iters):
+        eps = torch.randn(T, S, N, na, generator=generator, device=dev, dtype=torch.float32)
+        a = torch.clamp(mean + std * eps, -bound, bound)
+        if plant_zero:
+            a[:, :, 0] = 0.0                                                              # the policy itself rides along in every iteration
+        if grad_steps > 0 and refine == 'all':
+            ref_a, ref_s, _, _, first = _refine(grad_scorer, states, a.reshape(T, S * N, na), grad_steps, *refine_args, aggregate, bound)
+            a, scores, drawn = ref_a.reshape(T, S, N, na), ref_s.reshape(S, N), first.reshape(S, N)
+        else:
+            scores = drawn = aggregate_heads(scorer(a.reshape(T, S * N, na), states), aggregate).reshape(S, N)
+        if plant_zero and it == 0:
+            policy_score = drawn[:, 0].clone()
+        vals, idx = torch.topk(scores, E, dim=1)                                          # sorted: column 0 is the iteration's best
+        elites = a.gather(2, idx.view(1, S, E, 1).expand(T, S, E, na))
+        if grad_steps > 0 and refine == 'elites':
+            ref_a, ref_s = _refine(grad_scorer, states, elites.reshape(T, S * E, na), grad_steps, *refine_args, aggregate, bound)[:2]
+            vals, order = torch.topk(ref_s.reshape(S, E), E, dim=1)                       # sorted again: refinement may reorder the elites
+            elites = ref_a.reshape(T, S, E, na).gather(2, order.view(1, S, E, 1).expand(T, S, E, na))
+        elites = elites.double()
+        e_mean = elites.sum(dim=2, keepdim=True) / E
+        e_std = torch.sqrt(((elites - e_mean) ** 2).sum(dim=2, keepdim=True) / E)
+        mean = alpha * mean + (1.0 - alpha) * e_mean.float()
+        std = torch.clamp(alpha * std + (1.0 - alpha) * e_std.float(), min=min_std)
+        better = vals[:, 0] > best_score
+        best_score = torch.where(better, vals[:, 0], best_score)
+        best = torch.where(better.view(1, S, 1), elites[:, :, 0].float(), best)
+        history[it] = vals.mean(dim=1)
+    tm = lambda x: x.permute(1, 0, 2).contiguous()
+    return tm(mean[:, :, 0]), tm(std[:, :, 0]), tm(best), best_score, history, idx, policy_score
+
+
 def plan_cem(engine, states, horizon, n_candidates, n_elites, n_iters, init_mean=None, init_std=1.0, alpha=0.0, min_std=0.0, gamma=1.0,
              aggregate='mean', generator=None, stop_at_done=True, scorer=None, na=None):
     """Cross-entropy method over action sequences, per state.  Each iteration: eps = randn(T, S, N, na); a = clip(mean + std * eps, -1, 1); one scoring
@@ -156,44 +260,12 @@ def plan_cem(engine, states, horizon, n_candidates, n_elites, n_iters, init_mean
     -> dict(actions [S, T, na] the final mean, std [S, T, na], best_actions [S, T, na] / best_score [S] the best candidate seen in any iteration,
     history [n_iters, S] the elites' mean score per iteration, elites [S, n_elites] the candidate indices of the LAST iteration's elites, best first),
     device tensors; nothing is read back."""
-    T, N = _check_counts(horizon, n_candidates)
-    E, n_iters = int(n_elites), int(n_iters)
-    if not (1 <= E <= N):
-        raise ValueError("n_elites must be in 1 ... n_candidates = %d, got %r" % (N, n_elites))
-    if n_iters < 1:
-        raise ValueError("n_iters must be positive, got %r" % (n_iters,))
-    if not (0.0 <= float(alpha) < 1.0):
-        raise ValueError("alpha must be in [0, 1), got %r" % (alpha,))
-    scorer, states, na = _setup(engine, states, scorer, na, gamma, stop_at_done)
-    S, dev = states.shape[0], states.device
-    mean = _time_major_param(0.0 if init_mean is None else init_mean, T, S, na, dev, 'init_mean')
-    std = _time_major_param(init_std, T, S, na, dev, 'init_std')
-    alpha, min_std = float(alpha), float(min_std)
-    best_score = torch.full((S,), float('-inf'), device=dev, dtype=torch.float32)
-    best_actions = torch.zeros(T, S, na, device=dev, dtype=torch.float32)
-    history = torch.empty(n_iters, S, device=dev, dtype=torch.float32)
-    for it in range(n_iters):
-        eps = torch.randn(T, S, N, na, generator=generator, device=dev, dtype=torch.float32)
-        a = torch.clamp(mean + std * eps, -1.0, 1.0)
-        scores = aggregate_heads(scorer(a.reshape(T, S * N, na), states), aggregate).reshape(S, N)
-        vals, idx = torch.topk(scores, E, dim=1)                                          # sorted: column 0 is the iteration's best
-        elites = a.gather(2, idx.view(1, S, E, 1).expand(T, S, E, na)).double()
-        e_mean = elites.sum(dim=2, keepdim=True) / E
-        e_std = torch.sqrt(((elites - e_mean) ** 2).sum(dim=2, keepdim=True) / E)
-        mean = alpha * mean + (1.0 - alpha) * e_mean.float()
-        std = torch.clamp(alpha * std + (1.0 - alpha) * e_std.float(), min=min_std)
-        better = vals[:, 0] > best_score
-        best_score = torch.where(better, vals[:, 0], best_score)
-        best_actions = torch.where(better.view(1, S, 1), elites[:, :, 0].float(), best_actions)
-        history[it] = vals.mean(dim=1)
-    tm = lambda x: x.permute(1, 0, 2).contiguous()
-    return dict(actions=tm(mean[:, :, 0]), std=tm(std[:, :, 0]), best_actions=tm(best_actions), best_score=best_score, history=history, elites=idx)
-
-
-def _from_device_major(x, S, N):
-    """[T, S * N, na] -> [S, N, T, na]"""
-    T, _, na = x.shape
-    return x.reshape(T, S, N, na).permute(1, 2, 0, 3).contiguous()
+    T, N, E, n_iters, _ = _check_cem(horizon, n_candidates, n_elites, n_iters, alpha)
+    scorer = _resolve(engine, scorer, engine_scorer, 'scorer', gamma, stop_at_done)
+    states, na = _states(engine, states, na)
+    mean, std, best, best_score, history, elites, _ = _cem(scorer, states, na, T, N, E, n_iters, init_mean, init_std, alpha, min_std, aggregate, generator,
+                                                           bound=1.0, plant_zero=False)
+    return dict(actions=mean, std=std, best_actions=best, best_score=best_score, history=history, elites=elites)
 
 
 def _refine(grad_scorer, states, a, n_steps, lr, optimizer, betas, eps, aggregate, bound=1.0):
@@ -234,12 +306,20 @@ def _check_refine(n_steps, lr, optimizer):
     return int(n_steps)
 
 
-def _setup_grad(engine, grad_scorer, gamma, stop_at_done):
-    if grad_scorer is None:
-        if engine is None:
-            raise ValueError("an engine or a grad_scorer is needed")
-        grad_scorer = engine_grad_scorer(engine, gamma, stop_at_done)
-    return grad_scorer
+def _check_noise_clip(noise_clip):
+    noise_clip = float(noise_clip)
+    if not (noise_clip > 0.0 and np.isfinite(noise_clip)):
+        raise ValueError("noise_clip must be positive and finite, got %r" % (noise_clip,))
+    return noise_clip
+
+
+def _refine_candidates(engine, states, x, name, grad_scorer, n_steps, lr, optimizer, betas, eps, aggregate, bound):
+    """refine_actions / refine_noise behind their checks: _refine on supplied candidates (_candidates' x and name) -> the result dict, its first key `name`"""
+    states, cand, S, N, single = _candidates(engine, states, x, name)
+    best, best_score, last, last_score, first = _refine(grad_scorer, states, cand, n_steps, lr, optimizer, betas, eps, aggregate, bound)
+    res = {name: _from_device_major(best, S, N), 'score': best_score.reshape(S, N), 'last': _from_device_major(last, S, N),
+           'last_score': last_score.reshape(S, N), 'initial_score': first.reshape(S, N)}
+    return {k: v[:, 0] for k, v in res.items()} if single else res
 
 
 def refine_actions(engine, states, actions, n_steps, lr, optimizer='adam', betas=(0.9, 0.999), eps=1e-8, gamma=1.0, stop_at_done=True, aggregate='mean',
@@ -250,21 +330,8 @@ def refine_actions(engine, states, actions, n_steps, lr, optimizer='adam', betas
     best-scoring iterate seen per candidate, so the result is never worse than the input.
     -> dict(actions [S, N, T, na], score [S, N], last / last_score the final iterate, initial_score [S, N]), device tensors; nothing is read back."""
     n_steps = _check_refine(n_steps, lr, optimizer)
-    grad_scorer = _setup_grad(engine, grad_scorer, gamma, stop_at_done)
-    act = torch.as_tensor(actions)
-    _, states, na = _setup(engine, states, grad_scorer, act.shape[-1] if act.dim() >= 1 else None, gamma, stop_at_done)
-    act = act.to(device=states.device, dtype=torch.float32)
-    S = states.shape[0]
-    single = act.dim() == 3
-    if single:
-        act = act.unsqueeze(1)
-    if act.dim() != 4 or act.shape[0] != S or act.shape[3] != na or act.shape[1] < 1 or act.shape[2] < 1:
-        raise ValueError("actions: expected [%d, N, T, %d] or [%d, T, %d], got %s" % (S, na, S, na, tuple(torch.as_tensor(actions).shape)))
-    N = act.shape[1]
-    best, best_score, last, last_score, first = _refine(grad_scorer, states, _device_major(act), n_steps, lr, optimizer, betas, eps, aggregate)
-    res = dict(actions=_from_device_major(best, S, N), score=best_score.reshape(S, N), last=_from_device_major(last, S, N),
-               last_score=last_score.reshape(S, N), initial_score=first.reshape(S, N))
-    return {k: x[:, 0] for k, x in res.items()} if single else res
+    grad_scorer = _resolve(engine, grad_scorer, engine_grad_scorer, 'grad_scorer', gamma, stop_at_done)
+    return _refine_candidates(engine, states, torch.as_tensor(actions), 'actions', grad_scorer, n_steps, lr, optimizer, betas, eps, aggregate, 1.0)
 
 
 def plan_cem_gd(engine, states, horizon, n_candidates, n_elites, n_iters, grad_steps, grad_lr=0.05, refine='elites', optimizer='adam', betas=(0.9, 0.999),
@@ -275,54 +342,13 @@ def plan_cem_gd(engine, states, horizon, n_candidates, n_elites, n_iters, grad_s
     refine='all': refines every candidate (no separate scoring call) and takes the n_elites best of the refined ones.
     The refit uses the refined elites (keep-best: never worse than the ones drawn).  grad_steps = 0 returns plan_cem's tensors bit for bit for the
     same generator state.  -> plan_cem's dict; `elites` indexes the drawn candidates."""
-    T, N = _check_counts(horizon, n_candidates)
-    E, n_iters = int(n_elites), int(n_iters)
-    grad_steps = _check_refine(grad_steps, grad_lr, optimizer)
-    if refine not in ('elites', 'all'):
-        raise ValueError("refine: %r is neither 'elites' nor 'all'" % (refine,))
-    if not (1 <= E <= N):
-        raise ValueError("n_elites must be in 1 ... n_candidates = %d, got %r" % (N, n_elites))
-    if n_iters < 1:
-        raise ValueError("n_iters must be positive, got %r" % (n_iters,))
-    if not (0.0 <= float(alpha) < 1.0):
-        raise ValueError("alpha must be in [0, 1), got %r" % (alpha,))
-    if grad_steps > 0 or (scorer is None and engine is None):
-        grad_scorer = _setup_grad(engine, grad_scorer, gamma, stop_at_done)
-    if scorer is None and engine is None:
-        scorer = lambda a, init: grad_scorer(a, init)[0]
-    scorer, states, na = _setup(engine, states, scorer, na, gamma, stop_at_done)
-    S, dev = states.shape[0], states.device
-    mean = _time_major_param(0.0 if init_mean is None else init_mean, T, S, na, dev, 'init_mean')
-    std = _time_major_param(init_std, T, S, na, dev, 'init_std')
-    alpha, min_std = float(alpha), float(min_std)
-    best_score = torch.full((S,), float('-inf'), device=dev, dtype=torch.float32)
-    best_actions = torch.zeros(T, S, na, device=dev, dtype=torch.float32)
-    history = torch.empty(n_iters, S, device=dev, dtype=torch.float32)
-    for it in range(n_iters):
-        eps_ = torch.randn(T, S, N, na, generator=generator, device=dev, dtype=torch.float32)
-        a = torch.clamp(mean + std * eps_, -1.0, 1.0)
-        if grad_steps > 0 and refine == 'all':
-            ref_a, ref_s = _refine(grad_scorer, states, a.reshape(T, S * N, na), grad_steps, grad_lr, optimizer, betas, eps, aggregate)[:2]
-            a, scores = ref_a.reshape(T, S, N, na), ref_s.reshape(S, N)
-        else:
-            scores = aggregate_heads(scorer(a.reshape(T, S * N, na), states), aggregate).reshape(S, N)
-        vals, idx = torch.topk(scores, E, dim=1)                                          # sorted: column 0 is the iteration's best
-        elites = a.gather(2, idx.view(1, S, E, 1).expand(T, S, E, na))
-        if grad_steps > 0 and refine == 'elites':
-            ref_a, ref_s = _refine(grad_scorer, states, elites.reshape(T, S * E, na), grad_steps, grad_lr, optimizer, betas, eps, aggregate)[:2]
-            vals, order = torch.topk(ref_s.reshape(S, E), E, dim=1)                       # sorted again: refinement may reorder the elites
-            elites = ref_a.reshape(T, S, E, na).gather(2, order.view(1, S, E, 1).expand(T, S, E, na))
-        elites = elites.double()
-        e_mean = elites.sum(dim=2, keepdim=True) / E
-        e_std = torch.sqrt(((elites - e_mean) ** 2).sum(dim=2, keepdim=True) / E)
-        mean = alpha * mean + (1.0 - alpha) * e_mean.float()
-        std = torch.clamp(alpha * std + (1.0 - alpha) * e_std.float(), min=min_std)
-        better = vals[:, 0] > best_score
-        best_score = torch.where(better, vals[:, 0], best_score)
-        best_actions = torch.where(better.view(1, S, 1), elites[:, :, 0].float(), best_actions)
-        history[it] = vals.mean(dim=1)
-    tm = lambda x: x.permute(1, 0, 2).contiguous()
-    return dict(actions=tm(mean[:, :, 0]), std=tm(std[:, :, 0]), best_actions=tm(best_actions), best_score=best_score, history=history, elites=idx)
+    T, N, E, n_iters, grad_steps = _check_cem(horizon, n_candidates, n_elites, n_iters, alpha, grad_steps, grad_lr, optimizer, refine)
+    scorer, grad_scorer = _resolve_pair(engine, scorer, grad_scorer, engine_scorer, engine_grad_scorer, grad_steps, gamma, stop_at_done)
+    states, na = _states(engine, states, na)
+    mean, std, best, best_score, history, elites, _ = _cem(scorer, states, na, T, N, E, n_iters, init_mean, init_std, alpha, min_std, aggregate, generator,
+                                                           bound=1.0, plant_zero=False, grad_scorer=grad_scorer, grad_steps=grad_steps, refine=refine,
+                                                           refine_args=(grad_lr, optimizer, betas, eps))
+    return dict(actions=mean, std=std, best_actions=best, best_score=best_score, history=history, elites=elites)
 
 
 # ---------------------------------------------------------------------- planning in noise space around the policy (POPLIN-A)
@@ -334,29 +360,13 @@ def engine_policy_scorer(engine, gamma=1.0, stop_at_done=True, noise_in_std=Fals
     return scorer
 
 
-def _setup_policy(engine, states, scorer, na, gamma, stop_at_done, noise_in_std=False):
-    if scorer is None:
-        if engine is None:
-            raise ValueError("an engine or a scorer is needed")
-        scorer = engine_policy_scorer(engine, gamma, stop_at_done, noise_in_std)
-    return _setup(engine, states, scorer, na, gamma, stop_at_done)
-
-
 def score_noise_sequences(engine, states, noise, gamma=1.0, stop_at_done=True, aggregate='mean', noise_in_std=False, scorer=None):
     """score_action_sequences' counterpart in noise space: states [S, ns], noise [S, N, T, na] (N candidates per state) or [S, T, na] (one each),
     trajectory-major; every candidate is the closed loop a_t = clip(policy mean(s_t) + noise_t) on each head (noise_in_std: noise in units of the
     policy's std).  -> scores [S, N] (or [S]): the heads' discounted returns folded by `aggregate`.  A device tensor."""
     nz = torch.as_tensor(noise)
-    scorer, states, na = _setup_policy(engine, states, scorer, nz.shape[-1] if nz.dim() >= 1 else None, gamma, stop_at_done, noise_in_std)
-    nz = nz.to(device=states.device, dtype=torch.float32)
-    S = states.shape[0]
-    single = nz.dim() == 3
-    if single:
-        nz = nz.unsqueeze(1)
-    if nz.dim() != 4 or nz.shape[0] != S or nz.shape[3] != na or nz.shape[1] < 1 or nz.shape[2] < 1:
-        raise ValueError("noise: expected [%d, N, T, %d] or [%d, T, %d], got %s" % (S, na, S, na, tuple(torch.as_tensor(noise).shape)))
-    scores = aggregate_heads(scorer(_device_major(nz), states), aggregate).reshape(S, nz.shape[1])
-    return scores[:, 0] if single else scores
+    scorer = _resolve(engine, scorer, engine_policy_scorer, 'scorer', gamma, stop_at_done, noise_in_std)
+    return _score_candidates(engine, states, nz, 'noise', scorer, aggregate)
 
 
 def plan_cem_policy(engine, states, horizon, n_candidates, n_elites, n_iters, init_mean=None, init_std=0.5, noise_clip=2.0, alpha=0.0, min_std=0.0,
@@ -370,47 +380,13 @@ def plan_cem_policy(engine, states, horizon, n_candidates, n_elites, n_iters, in
     -> dict(noise [S, T, na] the final mean, std [S, T, na], best_noise [S, T, na] / best_score [S] the best candidate seen in any iteration, history
     [n_iters, S], elites [S, n_elites] of the last iteration, policy_score [S] the score of delta = 0 in the first iteration (None without
     include_policy)), device tensors; nothing is read back."""
-    T, N = _check_counts(horizon, n_candidates)
-    E, n_iters = int(n_elites), int(n_iters)
-    if not (1 <= E <= N):
-        raise ValueError("n_elites must be in 1 ... n_candidates = %d, got %r" % (N, n_elites))
-    if n_iters < 1:
-        raise ValueError("n_iters must be positive, got %r" % (n_iters,))
-    if not (0.0 <= float(alpha) < 1.0):
-        raise ValueError("alpha must be in [0, 1), got %r" % (alpha,))
-    noise_clip = float(noise_clip)
-    if not (noise_clip > 0.0 and np.isfinite(noise_clip)):
-        raise ValueError("noise_clip must be positive and finite, got %r" % (noise_clip,))
-    scorer, states, na = _setup_policy(engine, states, scorer, na, gamma, stop_at_done)
-    S, dev = states.shape[0], states.device
-    mean = _time_major_param(0.0 if init_mean is None else init_mean, T, S, na, dev, 'init_mean')
-    std = _time_major_param(init_std, T, S, na, dev, 'init_std')
-    alpha, min_std = float(alpha), float(min_std)
-    best_score = torch.full((S,), float('-inf'), device=dev, dtype=torch.float32)
-    best_noise = torch.zeros(T, S, na, device=dev, dtype=torch.float32)
-    history = torch.empty(n_iters, S, device=dev, dtype=torch.float32)
-    policy_score = None
-    for it in range(n_iters):
-        eps = torch.randn(T, S, N, na, generator=generator, device=dev, dtype=torch.float32)
-        d = torch.clamp(mean + std * eps, -noise_clip, noise_clip)
-        if include_policy:
-            d[:, :, 0] = 0.0                                                              # the policy itself rides along in every iteration
-        scores = aggregate_heads(scorer(d.reshape(T, S * N, na), states), aggregate).reshape(S, N)
-        if include_policy and it == 0:
-            policy_score = scores[:, 0].clone()
-        vals, idx = torch.topk(scores, E, dim=1)                                          # sorted: column 0 is the iteration's best
-        elites = d.gather(2, idx.view(1, S, E, 1).expand(T, S, E, na)).double()
-        e_mean = elites.sum(dim=2, keepdim=True) / E
-        e_std = torch.sqrt(((elites - e_mean) ** 2).sum(dim=2, keepdim=True) / E)
-        mean = alpha * mean + (1.0 - alpha) * e_mean.float()
-        std = torch.clamp(alpha * std + (1.0 - alpha) * e_std.float(), min=min_std)
-        better = vals[:, 0] > best_score
-        best_score = torch.where(better, vals[:, 0], best_score)
-        best_noise = torch.where(better.view(1, S, 1), elites[:, :, 0].float(), best_noise)
-        history[it] = vals.mean(dim=1)
-    tm = lambda x: x.permute(1, 0, 2).contiguous()
-    return dict(noise=tm(mean[:, :, 0]), std=tm(std[:, :, 0]), best_noise=tm(best_noise), best_score=best_score, history=history, elites=idx,
-                policy_score=policy_score)
+    T, N, E, n_iters, _ = _check_cem(horizon, n_candidates, n_elites, n_iters, alpha)
+    noise_clip = _check_noise_clip(noise_clip)
+    scorer = _resolve(engine, scorer, engine_policy_scorer, 'scorer', gamma, stop_at_done)
+    states, na = _states(engine, states, na)
+    mean, std, best, best_score, history, elites, policy_score = _cem(scorer, states, na, T, N, E, n_iters, init_mean, init_std, alpha, min_std, aggregate,
+                                                                      generator, bound=noise_clip, plant_zero=include_policy)
+    return dict(noise=mean, std=std, best_noise=best, best_score=best_score, history=history, elites=elites, policy_score=policy_score)
 
 
 def engine_policy_grad_scorer(engine, gamma=1.0, stop_at_done=True, noise_in_std=False, force_generic=False):
@@ -423,21 +399,6 @@ def engine_policy_grad_scorer(engine, gamma=1.0, stop_at_done=True, noise_in_std
     return grad_scorer
 
 
-def _setup_policy_grad(engine, grad_scorer, gamma, stop_at_done, noise_in_std=False):
-    if grad_scorer is None:
-        if engine is None:
-            raise ValueError("an engine or a grad_scorer is needed")
-        grad_scorer = engine_policy_grad_scorer(engine, gamma, stop_at_done, noise_in_std)
-    return grad_scorer
-
-
-def _check_noise_clip(noise_clip):
-    noise_clip = float(noise_clip)
-    if not (noise_clip > 0.0 and np.isfinite(noise_clip)):
-        raise ValueError("noise_clip must be positive and finite, got %r" % (noise_clip,))
-    return noise_clip
-
-
 def refine_noise(engine, states, noise, n_steps, lr, noise_clip=2.0, optimizer='adam', betas=(0.9, 0.999), eps=1e-8, gamma=1.0, stop_at_done=True,
                  aggregate='mean', noise_in_std=False, grad_scorer=None):
     """refine_actions in noise space: projected gradient ASCENT on candidate noise sequences around the policy, states [S, ns], noise [S, N, T, na] (or
@@ -447,21 +408,8 @@ def refine_noise(engine, states, noise, n_steps, lr, noise_clip=2.0, optimizer='
     -> dict(noise [S, N, T, na], score [S, N], last / last_score the final iterate, initial_score [S, N]), device tensors; nothing is read back."""
     n_steps = _check_refine(n_steps, lr, optimizer)
     noise_clip = _check_noise_clip(noise_clip)
-    grad_scorer = _setup_policy_grad(engine, grad_scorer, gamma, stop_at_done, noise_in_std)
-    nz = torch.as_tensor(noise)
-    _, states, na = _setup(engine, states, grad_scorer, nz.shape[-1] if nz.dim() >= 1 else None, gamma, stop_at_done)
-    nz = nz.to(device=states.device, dtype=torch.float32)
-    S = states.shape[0]
-    single = nz.dim() == 3
-    if single:
-        nz = nz.unsqueeze(1)
-    if nz.dim() != 4 or nz.shape[0] != S or nz.shape[3] != na or nz.shape[1] < 1 or nz.shape[2] < 1:
-        raise ValueError("noise: expected [%d, N, T, %d] or [%d, T, %d], got %s" % (S, na, S, na, tuple(torch.as_tensor(noise).shape)))
-    N = nz.shape[1]
-    best, best_score, last, last_score, first = _refine(grad_scorer, states, _device_major(nz), n_steps, lr, optimizer, betas, eps, aggregate, noise_clip)
-    res = dict(noise=_from_device_major(best, S, N), score=best_score.reshape(S, N), last=_from_device_major(last, S, N),
-               last_score=last_score.reshape(S, N), initial_score=first.reshape(S, N))
-    return {k: x[:, 0] for k, x in res.items()} if single else res
+    grad_scorer = _resolve(engine, grad_scorer, engine_policy_grad_scorer, 'grad_scorer', gamma, stop_at_done, noise_in_std)
+    return _refine_candidates(engine, states, torch.as_tensor(noise), 'noise', grad_scorer, n_steps, lr, optimizer, betas, eps, aggregate, noise_clip)
 
 
 def plan_cem_policy_gd(engine, states, horizon, n_candidates, n_elites, n_iters, grad_steps, grad_lr=0.05, refine='elites', optimizer='adam',
@@ -474,61 +422,14 @@ def plan_cem_policy_gd(engine, states, horizon, n_candidates, n_elites, n_iters,
     The refit uses the refined elites (keep-best: never worse than the ones drawn, so the best candidate seen is still never worse than the policy).
     grad_steps = 0 returns plan_cem_policy's tensors bit for bit for the same generator state.  -> plan_cem_policy's dict; `elites` indexes the drawn
     candidates; policy_score is the score of delta = 0 itself, before any refinement."""
-    T, N = _check_counts(horizon, n_candidates)
-    E, n_iters = int(n_elites), int(n_iters)
-    grad_steps = _check_refine(grad_steps, grad_lr, optimizer)
-    if refine not in ('elites', 'all'):
-        raise ValueError("refine: %r is neither 'elites' nor 'all'" % (refine,))
-    if not (1 <= E <= N):
-        raise ValueError("n_elites must be in 1 ... n_candidates = %d, got %r" % (N, n_elites))
-    if n_iters < 1:
-        raise ValueError("n_iters must be positive, got %r" % (n_iters,))
-    if not (0.0 <= float(alpha) < 1.0):
-        raise ValueError("alpha must be in [0, 1), got %r" % (alpha,))
+    T, N, E, n_iters, grad_steps = _check_cem(horizon, n_candidates, n_elites, n_iters, alpha, grad_steps, grad_lr, optimizer, refine)
     noise_clip = _check_noise_clip(noise_clip)
-    if grad_steps > 0 or (scorer is None and engine is None):
-        grad_scorer = _setup_policy_grad(engine, grad_scorer, gamma, stop_at_done)
-    if scorer is None and engine is None:
-        scorer = lambda d, init: grad_scorer(d, init)[0]
-    scorer, states, na = _setup_policy(engine, states, scorer, na, gamma, stop_at_done)
-    S, dev = states.shape[0], states.device
-    mean = _time_major_param(0.0 if init_mean is None else init_mean, T, S, na, dev, 'init_mean')
-    std = _time_major_param(init_std, T, S, na, dev, 'init_std')
-    alpha, min_std = float(alpha), float(min_std)
-    best_score = torch.full((S,), float('-inf'), device=dev, dtype=torch.float32)
-    best_noise = torch.zeros(T, S, na, device=dev, dtype=torch.float32)
-    history = torch.empty(n_iters, S, device=dev, dtype=torch.float32)
-    policy_score = None
-    for it in range(n_iters):
-        eps_ = torch.randn(T, S, N, na, generator=generator, device=dev, dtype=torch.float32)
-        d = torch.clamp(mean + std * eps_, -noise_clip, noise_clip)
-        if include_policy:
-            d[:, :, 0] = 0.0                                                              # the policy itself rides along in every iteration
-        if grad_steps > 0 and refine == 'all':
-            ref_d, ref_s, _, _, first = _refine(grad_scorer, states, d.reshape(T, S * N, na), grad_steps, grad_lr, optimizer, betas, eps, aggregate, noise_clip)
-            d, scores, drawn = ref_d.reshape(T, S, N, na), ref_s.reshape(S, N), first.reshape(S, N)
-        else:
-            scores = drawn = aggregate_heads(scorer(d.reshape(T, S * N, na), states), aggregate).reshape(S, N)
-        if include_policy and it == 0:
-            policy_score = drawn[:, 0].clone()
-        vals, idx = torch.topk(scores, E, dim=1)                                          # sorted: column 0 is the iteration's best
-        elites = d.gather(2, idx.view(1, S, E, 1).expand(T, S, E, na))
-        if grad_steps > 0 and refine == 'elites':
-            ref_d, ref_s = _refine(grad_scorer, states, elites.reshape(T, S * E, na), grad_steps, grad_lr, optimizer, betas, eps, aggregate, noise_clip)[:2]
-            vals, order = torch.topk(ref_s.reshape(S, E), E, dim=1)                       # sorted again: refinement may reorder the elites
-            elites = ref_d.reshape(T, S, E, na).gather(2, order.view(1, S, E, 1).expand(T, S, E, na))
-        elites = elites.double()
-        e_mean = elites.sum(dim=2, keepdim=True) / E
-        e_std = torch.sqrt(((elites - e_mean) ** 2).sum(dim=2, keepdim=True) / E)
-        mean = alpha * mean + (1.0 - alpha) * e_mean.float()
-        std = torch.clamp(alpha * std + (1.0 - alpha) * e_std.float(), min=min_std)
-        better = vals[:, 0] > best_score
-        best_score = torch.where(better, vals[:, 0], best_score)
-        best_noise = torch.where(better.view(1, S, 1), elites[:, :, 0].float(), best_noise)
-        history[it] = vals.mean(dim=1)
-    tm = lambda x: x.permute(1, 0, 2).contiguous()
-    return dict(noise=tm(mean[:, :, 0]), std=tm(std[:, :, 0]), best_noise=tm(best_noise), best_score=best_score, history=history, elites=idx,
-                policy_score=policy_score)
+    scorer, grad_scorer = _resolve_pair(engine, scorer, grad_scorer, engine_policy_scorer, engine_policy_grad_scorer, grad_steps, gamma, stop_at_done)
+    states, na = _states(engine, states, na)
+    mean, std, best, best_score, history, elites, policy_score = _cem(scorer, states, na, T, N, E, n_iters, init_mean, init_std, alpha, min_std, aggregate,
+                                                                      generator, bound=noise_clip, plant_zero=include_policy, grad_scorer=grad_scorer,
+                                                                      grad_steps=grad_steps, refine=refine, refine_args=(grad_lr, optimizer, betas, eps))
+    return dict(noise=mean, std=std, best_noise=best, best_score=best_score, history=history, elites=elites, policy_score=policy_score)
 
 
 def baseline_terminal_value(baseline, t_index, ns):
@@ -728,10 +629,10 @@ class ShootingController(object):
         return torch.cat([noise[:, 1:], torch.zeros_like(noise[:, -1:])], dim=1)
 
     def get_actions(self, observations):
+        obs = torch.as_tensor(np.asarray(observations) if not torch.is_tensor(observations) else observations)
+        S = obs.shape[0] if obs.dim() == 2 else 1
         if self.terminal_value is None:
-            return self._plan(observations)
-        obs = observations if torch.is_tensor(observations) else np.asarray(observations)
-        S = obs.shape[0] if obs.ndim == 2 else 1
+            return self._plan(obs, S)
         if self._steps is None or self._steps.shape[0] != S:
             self._steps = np.zeros(S, dtype=np.int64)
         if isinstance(self.terminal_value, ValueMLP):
@@ -739,36 +640,31 @@ class ShootingController(object):
         else:
             self.engine.set_terminal_value(*baseline_terminal_value(self.terminal_value, self._steps + self.horizon, self.engine.ns))
         try:
-            out = self._plan(observations)
+            out = self._plan(obs, S)
         finally:
             self.engine.clear_terminal_value()
         self._steps = self._steps + 1
         return out
 
-    def _plan(self, observations):
-        obs = torch.as_tensor(np.asarray(observations) if not torch.is_tensor(observations) else observations)
-        S = obs.shape[0] if obs.dim() == 2 else 1
+    def _plan(self, obs, S):
         start = self._mean if (self._mean is not None and self._mean.shape[0] == S) else self.init_mean
+        kw = dict(self.kw, init_mean=start, init_std=self.init_std, scorer=self.scorer, na=self.na)
         if self.policy_prior:
-            if self.noise_grad_steps > 0:
-                plan = plan_cem_policy_gd(self.engine, obs, self.horizon, grad_steps=self.noise_grad_steps, init_mean=start, init_std=self.init_std,
-                                          noise_clip=self.noise_clip, scorer=self.scorer, na=self.na, **dict(self.kw, **self.noise_grad_kw))
-            else:
-                plan = plan_cem_policy(self.engine, obs, self.horizon, init_mean=start, init_std=self.init_std, noise_clip=self.noise_clip,
-                                       scorer=self.scorer, na=self.na, **self.kw)
-            self.last_plan = plan
+            planners, steps, grad_kw = (plan_cem_policy, plan_cem_policy_gd), self.noise_grad_steps, self.noise_grad_kw
+            kw['noise_clip'] = self.noise_clip
+        else:
+            planners, steps, grad_kw = (plan_cem, plan_cem_gd), self.grad_steps, self.grad_kw
+        if steps > 0:
+            kw.update(grad_kw, grad_steps=steps)
+        plan = self.last_plan = planners[steps > 0](self.engine, obs, self.horizon, **kw)
+        if self.policy_prior:
             self._mean = self.shifted_noise(plan['noise'])
             obs2 = obs.reshape(S, -1).to(device=plan['noise'].device, dtype=torch.float32)
             pmean = self.engine.policy_actions(obs2)[1]                                   # one policy forward, not a second scoring call
             return torch.clamp(pmean + plan['noise'][:, 0], -1.0, 1.0).double().cpu().numpy(), {}
-        if self.grad_steps > 0:
-            plan = plan_cem_gd(self.engine, obs, self.horizon, grad_steps=self.grad_steps, init_mean=start, init_std=self.init_std, scorer=self.scorer,
-                               na=self.na, **dict(self.kw, **self.grad_kw))
-        else:
-            plan = plan_cem(self.engine, obs, self.horizon, init_mean=start, init_std=self.init_std, scorer=self.scorer, na=self.na, **self.kw)
-        self.last_plan = plan
         self._mean = self.shifted(plan['actions'])
         return plan['actions'][:, 0].double().cpu().numpy(), {}
+
 
     def get_action(self, observation):
         a, info = self.get_actions(np.asarray(observation)[None])
