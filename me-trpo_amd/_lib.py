@@ -143,6 +143,14 @@ class DebugGemmArgs(C.Structure):          # csrc/gemm_debug.h (a diagnostics ho
                 [('o_stride_part', C.c_int64)])
 
 
+class DebugGemmBf16Args(C.Structure):      # csrc/rollout_bf16.hip (a diagnostics hook, not part of include/metrpo.h)
+    _fields_ = ([(n, C.c_int32) for n in ('op', 'a_bf16', 'c_bf16', 'bn', 'M', 'N', 'Kd', 'Kp', 'heads', 'lda', 'ldc', 'act')] +
+                [(n, C.c_int64) for n in ('sA', 'sW', 'sB', 'sC')] +
+                [(n, C.c_void_p) for n in ('A', 'W', 'bias', 'C')] +
+                [(n, C.c_int32) for n in ('o_bn', 'o_gx', 'o_gy', 'o_gz', 'o_n_cu')])
+
+
+GEMM_BF16_DEBUG_OPS = {'image': 0, 'gemm': 1}
 GEMM_EPIS = {'BIAS_ID': 0, 'BIAS_RELU': 1, 'BIAS_TANH': 2, 'RELU_MASK': 3, 'ADAM': 4, 'PLAIN': 5, 'PARTIAL': 6, 'DTANH': 7}     # csrc/gemm_mfma.h
 GEMM_DEBUG_OPS = {'auto': 0, 'skinny': 1, 'fused_out': 2}
 SVG_PATHS = {'auto': 0, 'generic': 1, 'gemm': 2}          # metrpo_svg_args.path
@@ -267,6 +275,8 @@ EXTRA_SYMBOLS = {
     'metrpo_set_coop_split': (_I, [_P, _I]),
     'metrpo_debug_score_policy_chunk': (_I, [_P, _I]),
     'metrpo_debug_gemm': (_I, [_P, C.POINTER(DebugGemmArgs), _P]),
+    'metrpo_debug_gemm_bf16': (_I, [_P, C.POINTER(DebugGemmBf16Args), _P]),
+    'metrpo_debug_last_bf16_layers': (_I, [_P, _P]),
 }
 
 

@@ -139,6 +139,7 @@ struct metrpo_ctx {
     int last_rollout_kernel = -1;                         // which kernel family the last metrpo_rollout ran on: 0 generic, 1 head-per-wave MFMA, 2 cooperative MFMA, 3 step-wise GEMM, 4 resident
     int dyn_precision = METRPO_DYN_F32;                   // metrpo_set_dyn_precision: operand precision of the dynamics forward inside metrpo_rollout (rollout_bf16.hip)
     DevBuf<uint16_t> d_dyn_bf16;                          // ... its bf16 weight image [K][layer][N][Kp], rebuilt from d_dyn in front of every bf16 rollout call
+    int bf16_last_layers = 0, bf16_last_bn[MAXL] = {};    // ... the column tile (64 / 128) of every layer GEMM of its last step, written on the host by launch_bf16_layers (metrpo_debug_last_bf16_layers)
     // metrpo_trpo_update_begin / _end: an update whose line search is still undecided on the host
     // metrpo_trpo_update_begin's outcome lands in pinned host memory straight from its last kernel (k_ls_publish: scal | lk | ls, then a
     // stamp); _end polls the stamp (no copy engine, no event, no blocking wait to wake up from).  Publishing from a side stream behind a device-scope
@@ -334,6 +335,8 @@ int launch_rollout_gemm(metrpo_ctx*, const metrpo_rollout_args*, hipStream_t);
 // rollout_bf16.hip: the bf16-operand dynamics layers of metrpo_rollout (METRPO_DYN_BF16).  Image of one head: layer l at off[l], [dims[l + 1]][Kp[l]] bf16
 struct Bf16Img { int Kp[MAXL]; size_t off[MAXL]; size_t per_head; };
 Bf16Img bf16_img_layout(const ProblemDesc&);
+struct Bf16GemmForm { int bn, gx, gy, gz; };               // one layer GEMM's launch: column tile and grid (column tiles, 128-row tiles, heads)
+Bf16GemmForm gemm_bf16_form(int n_cu, int M, int N, int heads, int force_bn = 0);
 int launch_bf16_dyn_image(metrpo_ctx*, hipStream_t);      // d_dyn -> d_dyn_bf16
 size_t bf16_hidden_floats(const ProblemDesc&, int B);      // floats of one hidden-activation buffer ([K][B][width up to 64] bf16)
 int launch_bf16_layers(metrpo_ctx*, const float* X, int ldx, void* HA, void* HB, float* OUT, int B, hipStream_t);      // one step's layers: X f32 -> OUT [K][B][ns] f32

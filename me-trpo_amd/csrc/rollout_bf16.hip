@@ -10,6 +10,8 @@
 //                   Layer 0 reads the f32 input rows X and rounds on the way into LDS; hidden layers store their activations ROUNDED ONCE as bf16
 //                   ([K][B][ld], ld = width rounded up to 64, pad columns written as zeros); the output layer stores f32 [K][B][ns] for k_big_post.
 // Every edge is predicated: rows >= M and columns >= N load zeros and store nothing (pad columns of a bf16 output: zeros).
+// At the end of the file: two diagnostics hooks for the tests (not in include/metrpo.h), metrpo_debug_gemm_bf16 (one launch of either kernel on
+// caller-owned memory: tests/test_gpu_bf16_gemm.py) and metrpo_debug_last_bf16_layers (the column tile each layer of the last step was launched on).
 #include <algorithm>
 #include "metrpo_internal.h"
 #include "device_common.h"
@@ -58,14 +60,17 @@ __global__ void __launch_bounds__(256) k_bf16_wimage(const float* __restrict__ W
     }
 }
 
+static void bf16_wimage_launch(const float* W, long long sW, int Kd, int N, int Kp, uint16_t* img, long long sImg, int heads, hipStream_t st) {
+    hipLaunchKernelGGL(k_bf16_wimage, dim3(Kp / 32, (N + 31) / 32, heads), dim3(256), 0, st, W, sW, Kd, N, Kp, img, sImg);
+}
+
 int launch_bf16_dyn_image(metrpo_ctx* c, hipStream_t st) {
     const ProblemDesc& pd = c->pd;
     const Bf16Img im = bf16_img_layout(pd);
     { const int rc = ws_grow(c, c->d_dyn_bf16, sizeof(uint16_t) * im.per_head * pd.K); if (rc) return rc; }
     for (int l = 0; l < pd.dyn.n_layers; ++l) {
         const int Kd = (l == 0) ? pd.nin : pd.dyn.dims[l], N = pd.dyn.dims[l + 1];
-        hipLaunchKernelGGL(k_bf16_wimage, dim3(im.Kp[l] / 32, (N + 31) / 32, pd.K), dim3(256), 0, st, c->d_dyn.p + pd.dyn.w_off[l], (long long)pd.dyn.n_params, Kd, N,
-                           im.Kp[l], c->d_dyn_bf16.p + im.off[l], (long long)im.per_head);
+        bf16_wimage_launch(c->d_dyn.p + pd.dyn.w_off[l], (long long)pd.dyn.n_params, Kd, N, im.Kp[l], c->d_dyn_bf16.p + im.off[l], (long long)im.per_head, pd.K, st);
     }
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
@@ -177,15 +182,22 @@ __global__ void __launch_bounds__(256) k_gemm_bf16(const AT* __restrict__ A, lon
     }
 }
 
-template <typename AT, typename CT>
-static void gemm_bf16_pick(int n_cu, const AT* A, long long sA, int lda, const uint16_t* W, long long sW, int Kp, const float* bias, long long sB, CT* C, long long sC, int ldc,
-                           int M, int N, int Kd, int heads, int act, hipStream_t st) {
+// The launch gemm_bf16_pick makes, as a pure host function: 64-column tiles for narrow layers (the output layer: ns <= 64) and while 128-column tiles would
+// leave CUs without one.  force_bn = 64 / 128 (metrpo_debug_gemm_bf16 only) takes the tile as given.
+Bf16GemmForm gemm_bf16_form(int n_cu, int M, int N, int heads, int force_bn) {
     const int rt = (M + 127) / 128;
-    // 64-column tiles for narrow layers (the output layer: ns <= 64) and while 128-column tiles would leave CUs without one
-    if (N <= 64 || (long long)heads * rt * ((N + 127) / 128) < n_cu)
-        hipLaunchKernelGGL((k_gemm_bf16<AT, CT, 64>), dim3((N + 63) / 64, rt, heads), dim3(256), 0, st, A, sA, lda, W, sW, Kp, bias, sB, C, sC, ldc, M, N, Kd, act);
-    else
-        hipLaunchKernelGGL((k_gemm_bf16<AT, CT, 128>), dim3((N + 127) / 128, rt, heads), dim3(256), 0, st, A, sA, lda, W, sW, Kp, bias, sB, C, sC, ldc, M, N, Kd, act);
+    int bn = force_bn;
+    if (bn == 0) bn = (N <= 64 || (long long)heads * rt * ((N + 127) / 128) < n_cu) ? 64 : 128;
+    return Bf16GemmForm{bn, (N + bn - 1) / bn, rt, heads};
+}
+
+template <typename AT, typename CT>
+static Bf16GemmForm gemm_bf16_pick(int n_cu, const AT* A, long long sA, int lda, const uint16_t* W, long long sW, int Kp, const float* bias, long long sB, CT* C, long long sC,
+                                   int ldc, int M, int N, int Kd, int heads, int act, hipStream_t st, int force_bn = 0) {
+    const Bf16GemmForm f = gemm_bf16_form(n_cu, M, N, heads, force_bn);
+    if (f.bn == 64) hipLaunchKernelGGL((k_gemm_bf16<AT, CT, 64>), dim3(f.gx, f.gy, f.gz), dim3(256), 0, st, A, sA, lda, W, sW, Kp, bias, sB, C, sC, ldc, M, N, Kd, act);
+    else hipLaunchKernelGGL((k_gemm_bf16<AT, CT, 128>), dim3(f.gx, f.gy, f.gz), dim3(256), 0, st, A, sA, lda, W, sW, Kp, bias, sB, C, sC, ldc, M, N, Kd, act);
+    return f;
 }
 
 // floats of ONE hidden-activation buffer of the step loop's workspace: bf16 [K][B][widest hidden layer rounded up to 64]
@@ -210,10 +222,84 @@ int launch_bf16_layers(metrpo_ctx* c, const float* X, int ldx, void* HA, void* H
         const uint16_t* W = c->d_dyn_bf16.p + im.off[l];
         const float* bias = c->d_dyn.p + pd.dyn.b_off[l];
         const long long sW = (long long)im.per_head, sB = pd.dyn.n_params;
-        if (l == 0) gemm_bf16_pick(c->n_sm, X, 0LL, ldx, W, sW, im.Kp[l], bias, sB, hb[0], sC, ldc, B, N, ldx, K, pd.dyn.act[l], st);
-        else if (l == L - 1) gemm_bf16_pick(c->n_sm, hin, sA, lda, W, sW, im.Kp[l], bias, sB, OUT, sC, ldc, B, N, im.Kp[l], K, pd.dyn.act[l], st);
-        else gemm_bf16_pick(c->n_sm, hin, sA, lda, W, sW, im.Kp[l], bias, sB, hb[l & 1], sC, ldc, B, N, im.Kp[l], K, pd.dyn.act[l], st);
+        Bf16GemmForm f;
+        if (l == 0) f = gemm_bf16_pick(c->n_sm, X, 0LL, ldx, W, sW, im.Kp[l], bias, sB, hb[0], sC, ldc, B, N, ldx, K, pd.dyn.act[l], st);
+        else if (l == L - 1) f = gemm_bf16_pick(c->n_sm, hin, sA, lda, W, sW, im.Kp[l], bias, sB, OUT, sC, ldc, B, N, im.Kp[l], K, pd.dyn.act[l], st);
+        else f = gemm_bf16_pick(c->n_sm, hin, sA, lda, W, sW, im.Kp[l], bias, sB, hb[l & 1], sC, ldc, B, N, im.Kp[l], K, pd.dyn.act[l], st);
         hin = hb[l & 1]; sA = sC; lda = ldc;
+        c->bf16_last_bn[l] = f.bn;
+    }
+    c->bf16_last_layers = L;
+    HIP_TRY(c, hipGetLastError());
+    return METRPO_OK;
+}
+
+// Diagnostics hook (not part of include/metrpo.h; tests/test_gpu_dyn_bf16.py): the column tile of every layer GEMM of the last bf16 rollout step this context enqueued, as
+// launch_bf16_layers wrote it down on the host (no device work, no synchronisation).  out[1 + MAXL] = number of layers (0: no bf16 rollout yet), then bn per layer.
+extern "C" int32_t metrpo_debug_last_bf16_layers(const metrpo_ctx* c, int32_t* out) {
+    if (!c || !out) return METRPO_ENULL;
+    out[0] = c->bf16_last_layers;
+    for (int l = 0; l < MAXL; ++l) out[1 + l] = (l < c->bf16_last_layers) ? c->bf16_last_bn[l] : 0;
+    return METRPO_OK;
+}
+
+// Diagnostics hook (not part of include/metrpo.h; tests/test_gpu_bf16_gemm.py, Engine.debug_gemm_bf16): ONE launch of k_bf16_wimage or of gemm_bf16_pick on caller-owned
+// device memory, in exactly the argument shapes launch_bf16_dyn_image / launch_bf16_layers pass.  It allocates nothing, measures nothing and reads and writes no context
+// state besides the CU count the rule takes (a rejected call records its reason in the context's error string, like every entry point).  The caller sizes every buffer
+// for the extents and strides it passes.
+struct metrpo_debug_gemm_bf16_args {       // mirrored by _lib.DebugGemmBf16Args
+    int32_t op;                            // 0 image: W f32 [heads][Kd][N] (head stride sW floats) -> C = img bf16 [heads][N][Kp] (head stride sC elements); 1 gemm
+    int32_t a_bf16, c_bf16;                // gemm: element types of A and C: (0, 1) layer 0, (1, 1) a layer between, (1, 0) the output layer
+    int32_t bn;                            // gemm: 0 the rule, 64 or 128 the tile as given (128 only where the rule can choose it: N > 64)
+    int32_t M, N, Kd, Kp, heads, lda, ldc, act;
+    int64_t sA, sW, sB, sC;                // head strides in elements of the operand's type
+    const void* A; const void* W; const float* bias; void* C;
+    int32_t o_bn, o_gx, o_gy, o_gz, o_n_cu;      // on return: the launched form (image: o_bn = 0)
+};
+
+extern "C" int32_t metrpo_debug_gemm_bf16(metrpo_ctx* c, metrpo_debug_gemm_bf16_args* a, void* stream) {
+    if (!c || !a) return METRPO_ENULL;
+    hipStream_t st = (hipStream_t)stream;
+    auto bad = [&](const char* why) { return set_err(c, METRPO_EINVAL, std::string("debug_gemm_bf16: ") + why); };
+    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    if (!a->W || !a->C) return bad("W and C must be given");
+    if (a->N < 1 || a->Kd < 1 || a->heads < 1 || a->heads > 65535) return bad("N, Kd and heads must be positive (heads below 65536)");
+    if (a->Kp < 64 || a->Kp % 64 != 0) return bad("Kp must be a positive multiple of 64");
+    a->o_n_cu = c->n_sm;
+    if (a->op == 0) {
+        if (a->Kp != ((a->Kd + 63) & ~63)) return bad("image: Kp must be Kd rounded up to 64");
+        if (a->sW < 0 || a->sC < 0) return bad("image: head strides must not be negative");
+        bf16_wimage_launch((const float*)a->W, a->sW, a->Kd, a->N, a->Kp, (uint16_t*)a->C, a->sC, a->heads, st);
+        a->o_bn = 0; a->o_gx = a->Kp / 32; a->o_gy = (a->N + 31) / 32; a->o_gz = a->heads;
+    } else if (a->op == 1) {
+        if (!a->A || !a->bias) return bad("gemm: A and bias must be given");
+        if (a->M < 1 || (a->M + 127) / 128 > 65535) return bad("gemm: M must be positive, at most 65535 row tiles");
+        if (a->act < METRPO_ACT_IDENTITY || a->act > METRPO_ACT_TANH) return bad("gemm: act must be 0, 1 or 2");
+        if (a->bn != 0 && a->bn != 64 && a->bn != 128) return bad("gemm: bn must be 0, 64 or 128");
+        if (a->bn == 128 && a->N <= 64) return bad("gemm: the 128-column tile is launched at N > 64 only");
+        if (!((a->a_bf16 == 0 && a->c_bf16 == 1) || (a->a_bf16 == 1 && (a->c_bf16 == 0 || a->c_bf16 == 1)))) return bad("gemm: (A, C) must be (f32, bf16), (bf16, bf16) or (bf16, f32)");
+        if (!al16(a->A) || !al16(a->W)) return bad("gemm: A and W must be 16-byte aligned");
+        if (a->sW < 0 || a->sW % 8 != 0) return bad("gemm: sW must be a non-negative multiple of 8");
+        if (a->sA < 0 || a->sB < 0 || a->sC < 0) return bad("gemm: head strides must not be negative");
+        if (a->a_bf16) {
+            if (a->Kd != a->Kp) return bad("gemm: bf16 A is read up to Kp: Kd must equal Kp");
+            if (a->lda < a->Kp || a->lda % 8 != 0 || a->sA % 8 != 0) return bad("gemm: bf16 A needs lda >= Kp, lda and sA multiples of 8");
+        } else {
+            if (a->Kd != a->lda || a->lda % 4 != 0 || a->sA % 4 != 0) return bad("gemm: f32 A needs Kd = lda, lda and sA multiples of 4");
+            if (a->Kp != ((a->Kd + 63) & ~63)) return bad("gemm: f32 A needs Kp = Kd rounded up to 64");
+        }
+        if (a->ldc != (a->c_bf16 ? ((a->N + 63) & ~63) : a->N)) return bad("gemm: ldc must be N rounded up to 64 (bf16 C) or N (f32 C)");
+        Bf16GemmForm f;
+#define GB_ARGS_ a->sA, a->lda, (const uint16_t*)a->W, a->sW, a->Kp, a->bias, a->sB
+#define GB_TAIL_ a->sC, a->ldc, a->M, a->N, a->Kd, a->heads, a->act, st, a->bn
+        if (!a->a_bf16) f = gemm_bf16_pick(c->n_sm, (const float*)a->A, GB_ARGS_, (uint16_t*)a->C, GB_TAIL_);
+        else if (a->c_bf16) f = gemm_bf16_pick(c->n_sm, (const uint16_t*)a->A, GB_ARGS_, (uint16_t*)a->C, GB_TAIL_);
+        else f = gemm_bf16_pick(c->n_sm, (const uint16_t*)a->A, GB_ARGS_, (float*)a->C, GB_TAIL_);
+#undef GB_ARGS_
+#undef GB_TAIL_
+        a->o_bn = f.bn; a->o_gx = f.gx; a->o_gy = f.gy; a->o_gz = f.gz;
+    } else {
+        return bad("unknown op");
     }
     HIP_TRY(c, hipGetLastError());
     return METRPO_OK;

@@ -742,6 +742,32 @@ class Engine(object):
         self._chk(lib.metrpo_debug_gemm(self._ctx, C.byref(a), self._stream()))
         return dict((n, int(getattr(a, 'o_' + n))) for n in self.GEMM_FORM_FIELDS)
 
+    BF16_GEMM_FORM_FIELDS = ('bn', 'gx', 'gy', 'gz', 'n_cu')
+
+    def debug_gemm_bf16(self, op, **fields):
+        """Diagnostics: ONE launch of the bf16 dynamics forward's own kernels (csrc/rollout_bf16.hip) on caller-owned device tensors, for
+        tests/test_gpu_bf16_gemm.py.  op 'image' (k_bf16_wimage: W float32 [heads][Kd][N] -> C int16 [heads][N][Kp]) or 'gemm' (gemm_bf16_pick:
+        a_bf16 / c_bf16 choose the element types, float32 or int16 tensors holding bf16 bits; bn = 0 leaves the tile to the rule, 64 / 128 force
+        it).  The other fields are those of _lib.DebugGemmBf16Args; a pointer field takes a tensor.  The caller sizes every tensor for the
+        extents and strides it passes; no context state is read or written.  -> the launched form, a dict over BF16_GEMM_FORM_FIELDS."""
+        a = _lib.DebugGemmBf16Args()
+        a.op = _lib.GEMM_BF16_DEBUG_OPS[op] if isinstance(op, str) else int(op)
+        kinds = dict((n, t) for n, t in _lib.DebugGemmBf16Args._fields_)
+        for name, val in fields.items():
+            if kinds[name] is C.c_void_p and val is not None:
+                assert val.dtype in (torch.float32, torch.int16) and val.is_contiguous() and val.device == self.device
+                val = val.data_ptr()
+            setattr(a, name, val)
+        self._chk(lib.metrpo_debug_gemm_bf16(self._ctx, C.byref(a), self._stream()))
+        return dict((n, int(getattr(a, 'o_' + n))) for n in self.BF16_GEMM_FORM_FIELDS)
+
+    def last_bf16_layers(self):
+        """Diagnostics: the column tile (64 or 128) of every dynamics-layer GEMM of the last bf16 rollout's steps, as the host noted it when it
+        enqueued them; [] before the first bf16 rollout."""
+        out = (C.c_int32 * 8)()
+        self._chk(lib.metrpo_debug_last_bf16_layers(self._ctx, out))
+        return [int(out[1 + l]) for l in range(int(out[0]))]
+
     def rollout_note(self):
         """Why the last rollout() ran outside the fast dispatch table (K != 5 at 2x64, hidden widths 65..127, ...); '' when it did not."""
         return lib.metrpo_rollout_note(self._ctx).decode()

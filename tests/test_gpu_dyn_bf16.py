@@ -3,7 +3,9 @@
 env_helpers.py:597-635 (the step around it); the operand rounding itself is this library's extension.
 
   * exact arithmetic: sparse small-integer nets on a dyadic grid (dyn_bf16_ref.exact_rollout, self-checked on the CPU in tests/test_dyn_bf16_ref.py):
-    any summation order gives the same f32 bits, so d_obs and d_last_obs must equal the restatement's BITS over T = 3 free-running steps.
+    any summation order gives the same f32 bits, so d_obs and d_last_obs must equal the restatement's BITS over T = 3 free-running steps.  Every case
+    asserts the column tile of each layer from the host's note (Engine.last_bf16_layers) against the pick rule; four cases are sized from the CU count so
+    that their hidden layers run the 128-column tile with column and row edges inside it (the kernels on their own: tests/test_gpu_bf16_gemm.py).
   * rounding mode: inputs on and next to bf16 ties routed straight to the output; truncation and round-half-up each give other bits.
   * random Xavier nets: per-head rel-L2 of s' - s against the rounded float64 restatement.  The bound is MEASURED: 8 x the distance between a float32-
     accumulating NumPy emulation in another summation order and the restatement, on the same case (dyn_bf16_ref.random_bound).  Figures of the emulation
@@ -17,6 +19,7 @@ import pytest
 import torch
 from oracle import metrpo_oracle as O
 import dyn_bf16_ref as R
+import bf16_gemm_cases as BG
 import helpers as Hh
 import tolerances as TOL
 
@@ -44,16 +47,30 @@ EXACT = [('swimmer', 1, (128, 128), 1, 'step_rand'), ('swimmer', 5, (144, 136), 
          ('half_cheetah', 1, (128, 64, 128), 129, 'model_mean'), ('ant', 5, (128, 128), 129, 'step_rand'), ('ant', 5, (100, 72), 17, 'model_mean'),
          ('ant', 1, (144, 136), 64, 'model_med'), ('humanoid', 5, (144, 136), 64, 'model_med'), ('humanoid', 1, (128, 64, 128), 17, 'step_rand'),
          ('humanoid', 5, (128, 128), 129, 'model_mean'), ('swimmer', 5, (100, 72), 129, 'model_mean'), ('half_cheetah', 5, (128, 128), 1, 'model_med')]
+# The 128-column tile (gemm_bf16_pick: N > 64 and K * ceil(B / 128) * ceil(N / 128) >= CU count) with column edges inside the tile (136 = 128 + 8: the
+# col >= ldc skip; 200 = 128 + 72) and a row edge (B = 128 r + 1).  The B below serve 256 CUs; the test enlarges them where the device has more.  Each has
+# a twin at B = 129, which stays on the 64-column tile throughout.
+WIDE_B = 1024
+EXACT_WIDE = [('half_cheetah', 5, (136, 200), 3329, 'step_rand'), ('swimmer', 5, (200, 136), 3457, 'model_mean'), ('humanoid', 3, (256, 136), 5633, 'model_med'),
+              ('ant', 5, (136, 200), 3329, 'step_rand')]
+EXACT += EXACT_WIDE + [(env, K, hidden, 129, mode) for env, K, hidden, B, mode in EXACT_WIDE]
 
 
 @pytest.mark.parametrize('env,K,hidden,B,sam_mode', EXACT)
 def test_exact_arithmetic_bit_for_bit(env, K, hidden, B, sam_mode):
     T, H = 3, 2                                                    # every env is reset from the pool behind step 1 (supplied rows); ant also ends by itself
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    wide = B > WIDE_B
+    if wide:                                                       # enough row tiles for the narrowest hidden layer's grid to reach the CU count, plus one row
+        B = max(B, 128 * -(-n_cu // (K * min(-(-N // 128) for N in hidden))) + 1)
     dm, theta, pdims, pool, dr, ref = R.exact_rollout(env, K, hidden, B, T, H, sam_mode, seed=3)
     eng = engine_for(env, dm, theta)
     eng.set_dyn_precision('bf16')
     tr = eng.rollout(B, T, H, sam_mode, pool, determ=True, model_idx=dr['model_idx'], reset_idx=dr['reset_idx'], reset_model=dr['reset_model'])
     assert eng.last_rollout_kernel() == 'gemm-bf16' and eng.rollout_note() == ''
+    tiles = eng.last_bf16_layers()                                 # the column tile of every layer, as the host noted it
+    assert tiles == [BG.want_form(BG.gemm_case('bf16', 'f32', 0, B, N, K=64, Kp=64, heads=K), n_cu)['bn'] for N in hidden + (dm.ns, )]
+    assert tiles == ([128] * len(hidden) + [64] if wide else [64] * (len(hidden) + 1))
     assert np.array_equal(bits(tr.obs), bits(ref['obs']))
     assert np.array_equal(bits(tr.last_obs), bits(ref['last_obs']))
     assert np.array_equal(bits(tr.act), bits(ref['act'])) and np.array_equal(bits(tr.mean), bits(ref['act']))
