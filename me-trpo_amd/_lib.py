@@ -150,6 +150,11 @@ class DebugGemmBf16Args(C.Structure):      # csrc/rollout_bf16.hip (a diagnostic
                 [(n, C.c_int32) for n in ('o_bn', 'o_gx', 'o_gy', 'o_gz', 'o_n_cu')])
 
 
+class DebugEnvModelArgs(C.Structure):      # csrc/probe.hip (a diagnostics hook, not part of include/metrpo.h)
+    _fields_ = ([(n, C.c_int32) for n in ('env', 'ns', 'na', 'N', 'compile_time')] +
+                [(n, C.c_void_p) for n in ('x', 'u', 'w', 'cost', 'done', 'gx', 'gx_row', 'gu')])
+
+
 GEMM_BF16_DEBUG_OPS = {'image': 0, 'gemm': 1}
 GEMM_EPIS = {'BIAS_ID': 0, 'BIAS_RELU': 1, 'BIAS_TANH': 2, 'RELU_MASK': 3, 'ADAM': 4, 'PLAIN': 5, 'PARTIAL': 6, 'DTANH': 7}     # csrc/gemm_mfma.h
 GEMM_DEBUG_OPS = {'auto': 0, 'skinny': 1, 'fused_out': 2}
@@ -277,6 +282,7 @@ EXTRA_SYMBOLS = {
     'metrpo_debug_gemm': (_I, [_P, C.POINTER(DebugGemmArgs), _P]),
     'metrpo_debug_gemm_bf16': (_I, [_P, C.POINTER(DebugGemmBf16Args), _P]),
     'metrpo_debug_last_bf16_layers': (_I, [_P, _P]),
+    'metrpo_debug_env_model': (_I, [_P, C.POINTER(DebugEnvModelArgs), _P]),
 }
 
 

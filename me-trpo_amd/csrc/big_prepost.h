@@ -125,21 +125,10 @@ __device__ __forceinline__ void big_close_step(const ProblemDesc& pd, const Roll
     fin &= __shfl_xor(fin, 16, 64); fin &= __shfl_xor(fin, 32, 64);
     wave_lds_sync();
     const float* Sv = ST + c * NS;                           // the env's next state, every dim
-    constexpr int ki = (ENV == METRPO_ENV_SWIMMER || ENV == METRPO_ENV_HOPPER) ? 5 : (ENV == METRPO_ENV_HALF_CHEETAH) ? 9 : (ENV == METRPO_ENV_ANT) ? 15 : (ENV == METRPO_ENV_SNAKE) ? 7 : (ENV == METRPO_ENV_HUMANOID) ? NS - 1 : 0;
-    const float key = Sv[ki], h0v = Sv[0], h1v = Sv[1], zc = Sv[2];
-    float pen = 0.0f;
-    if (ENV == METRPO_ENV_HOPPER) for (int j = 2; j < NS; ++j) pen += fmaxf(fabsf(Sv[j]) - 100.0f, 0.0f);
-    float cost = 0.0f;
-    switch (ENV) {
-    case METRPO_ENV_SWIMMER: cost = -(key - 1e-2f * (su2 / (float)NA)); break;
-    case METRPO_ENV_HALF_CHEETAH: cost = -fminf(fmaxf(key - 1e-1f * 0.5f * su2, -10.0f), 10.0f); break;
-    case METRPO_ENV_ANT: cost = -(key - 1e-2f * 0.5f * su2 + 0.05f); break;
-    case METRPO_ENV_HOPPER: cost = -(key - 0.01f * 0.5f * su2 - 10.0f * fmaxf(0.45f - h0v, 0.0f) - 10.0f * fmaxf(fabsf(h1v) - 0.2f, 0.0f) - pen); break;
-    case METRPO_ENV_SNAKE: cost = -(key - 1e-2f * 0.5f * su2); break;
-    case METRPO_ENV_HUMANOID: cost = (key - 1.5f) * (key - 1.5f) + 1e-2f * 1e-3f * su2; break;      // key = the last state dim (k_big_post: last)
-    }
+    const float pen = (ENV == METRPO_ENV_HOPPER) ? env_hopper_pen(NS, EnvVec{Sv, 1}) : 0.0f;
+    const float cost = env_cost_terms(ENV, NA, Sv[env_key_dim(ENV, NS)], Sv[0], Sv[1], su2, pen);
     int ts = st.ts[bc] + 1;
-    bool dn = (ENV == METRPO_ENV_ANT) ? !((zc >= 0.2f) && (zc <= 1.0f) && (fin != 0)) : false;
+    bool dn = env_done(ENV, Sv[2], fin != 0);
     dn = dn || (ts >= r.H);
     int cur = st.cur_model[bc];
     if (active && q == 0) { r.rew[tbp] = -cost; r.done[tbp] = dn ? 1 : 0; r.tpath[tbp] = ts - 1; }

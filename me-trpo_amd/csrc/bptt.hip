@@ -12,7 +12,7 @@
 //   policy VJP       sum over all (i, t, b) samples of J_policy(x_t)^T adjoint_mean: the gradient kernels of the TRPO update with
 //                    the mean-adjoint supplied (PolK.gm) instead of derived from the surrogate loss -- MFMA path included.
 // Generic in the layer widths (activations in LDS columns, one thread per trajectory).  The reverse sweep's pieces -- a net's hidden layers
-// (net_hidden), its vector-Jacobian product (net_vjp) and the cost adjoint (cost_adjoint) -- are device_common.h's, shared with the generic
+// (net_hidden) and its vector-Jacobian product (net_vjp), device_common.h's, and the cost adjoint (env_cost_adjoint, env_model.h) -- are shared with the generic
 // gradient kernels of score_actions_grad.hip and score_policy_actions_grad.hip.
 #include <cmath>
 #include "device_common.h"
@@ -96,9 +96,9 @@ __global__ void k_bptt_forward(ProblemDesc pd, const float* __restrict__ dynp, c
         for (int d = 0; d < na; ++d) e.X[(ns + d) * LD + tid] = (e.U[d * LD + tid] - in_mean[ns + d]) / in_std[ns + d];
         float* out = mlp_col(pd.dyn, pk, e.X + pd.n_drop * LD, e.GA, e.GB, LD, tid);
         for (int i = 0; i < ns; ++i) e.XN[i * LD + tid] = fmaf(diff_std[i], out[i * LD + tid], diff_mean[i]) + e.S[i * LD + tid];
-        const float c = env_cost(pd.env, ns, na, e.XN, e.U, LD, tid);
+        const float c = env_cost(pd.env, ns, na, env_col(e.XN, LD, tid), env_col(e.U, LD, tid));
         const float live = 1.0f - dones;
-        if (pd.env == METRPO_ENV_ANT) dones = fmaxf(dones, env_is_done(pd.env, ns, e.XN, LD, tid) ? 1.0f : 0.0f);
+        if (pd.env == METRPO_ENV_ANT) dones = fmaxf(dones, env_done_scan(pd.env, ns, env_col(e.XN, LD, tid)) ? 1.0f : 0.0f);
         if (active) {
             acc += g * (double)(c * live);
             WT[((size_t)model * T + t) * B + b] = (float)(g * (double)live / ((double)B * (double)K));
@@ -147,7 +147,7 @@ __global__ void k_bptt_backward(ProblemDesc pd, const float* __restrict__ dynp, 
         // ---- adjoints: G = lambda_{t+1} + w dc/dx_next ;  gU_cost = w dc/du (kept in XN's place after use) -------------------
         float* G = e.LAM;                                       // lambda_{t+1} is consumed here
         float* gUc = e.X;                                       // the normalised input is dead after the forward recompute
-        cost_adjoint(pd.env, ns, na, e.XN, e.U, w, gUc, G, LD, tid);
+        env_cost_adjoint(pd.env, ns, na, e.XN, e.U, w, gUc, G, LD, tid);
         // dynamics VJP: delta_out = diff_std * G ; back through the layers (relu masks from DH)
         for (int i = 0; i < ns; ++i) e.GA[i * LD + tid] = diff_std[i] * G[i * LD + tid];
         float* da = net_vjp(dn, pk, e.DH, e.GA, e.GB, LD, tid);

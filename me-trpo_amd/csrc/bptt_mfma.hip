@@ -39,23 +39,6 @@ struct DetL {
     static constexpr int TOTAL = IMG + 4 * WV;
 };
 
-// cost of one env from its row-major tiles (env_helpers.py:601 / com_*_env.py cost_np_vec == cost_tf per sample)
-template <int ENV>
-__device__ __forceinline__ float cost_row(const float* xn, const float* u, int NS, int NA) {
-    float su2 = 0.0f;
-    for (int d = 0; d < NA; ++d) su2 = fmaf(u[d], u[d], su2);
-    if (ENV == METRPO_ENV_SWIMMER) return -(xn[5] - 1e-2f * (su2 / (float)NA));
-    if (ENV == METRPO_ENV_HALF_CHEETAH) return -fminf(fmaxf(xn[9] - 1e-1f * 0.5f * su2, -10.0f), 10.0f);
-    if (ENV == METRPO_ENV_SNAKE) return -(xn[7] - 1e-2f * 0.5f * su2);
-    if (ENV == METRPO_ENV_ANT) return -(xn[15] - 1e-2f * 0.5f * su2 + 0.05f);
-    if (ENV == METRPO_ENV_HOPPER) {
-        float pen = 0.0f;
-        for (int i = 2; i < NS; ++i) pen += fmaxf(fabsf(xn[i]) - 100.0f, 0.0f);
-        return -(xn[5] - 0.01f * 0.5f * su2 - 10.0f * fmaxf(0.45f - xn[0], 0.0f) - 10.0f * fmaxf(fabsf(xn[1]) - 0.2f, 0.0f) - pen);
-    }
-    return 0.0f;
-}
-
 // STOCH ('bptt-stochastic', bptt.hip): mu becomes mean + eps exp(log_std) before the clip in both sweeps (lane (c, q) draws chunk q of env c,
 // bptt_eps4), so the reverse sweep's clip gate sees the forward sweep's pre-clip action; the deterministic instantiations never read nz.
 template <int ENV, int MODE, bool STOCH>
@@ -161,14 +144,9 @@ __global__ void __launch_bounds__(256, 2) k_det_mfma(int K, int B, int T, double
                 }
             wave_lds_sync();
             if (q == 0) {                                        // one lane per env: cost, dones, weight
-                const float cst = cost_row<ENV>(NX + c * NS, ACT + c * NA, NS, NA);
+                const float cst = env_cost(ENV, NS, NA, EnvVec{NX + c * NS, 1}, EnvVec{ACT + c * NA, 1});
                 const float live = 1.0f - dones;
-                if (ENV == METRPO_ENV_ANT) {
-                    bool fin = true;
-                    for (int i = 0; i < NS; ++i) fin = fin && isfinite(NX[c * NS + i]);
-                    const float z = NX[c * NS + 2];
-                    dones = fmaxf(dones, ((z >= 0.2f) && (z <= 1.0f) && fin) ? 0.0f : 1.0f);
-                }
+                if (ENV == METRPO_ENV_ANT) dones = fmaxf(dones, env_done_scan(ENV, NS, EnvVec{NX + c * NS, 1}) ? 1.0f : 0.0f);
                 if (active) {
                     acc += g * (double)(cst * live);
                     if (WT != nullptr) WT[((size_t)model * T + t) * B + b] = (float)(g * (double)live / ((double)B * (double)K));
@@ -199,45 +177,8 @@ __global__ void __launch_bounds__(256, 2) k_det_mfma(int K, int B, int T, double
             wave_lds_sync();
             step_forward(t);
             // ---- cost adjoint in D layout: G = lambda_{t+1} + w dc/dx_next (state dims), gU = w dc/du (action dims) ----
-            f32x4 G[OUT_CB], gU = {0.f, 0.f, 0.f, 0.f};
-            float cu = 0.0f;
-#pragma unroll
-            for (int cb = 0; cb < OUT_CB; ++cb) G[cb] = lam[cb];
-            auto addG = [&](int dim, float v) {                  // add v to the lane/register that owns state dim `dim`
-#pragma unroll
-                for (int cb = 0; cb < OUT_CB; ++cb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) if (16 * cb + 4 * q + r == dim) G[cb][r] += v;
-            };
-            if (ENV == METRPO_ENV_SWIMMER) { addG(5, -w); cu = w * 1e-2f * 2.0f / (float)NA; }
-            else if (ENV == METRPO_ENV_SNAKE) { addG(7, -w); cu = w * 1e-2f; }
-            else if (ENV == METRPO_ENV_ANT) { addG(15, -w); cu = w * 1e-2f; }
-            else if (ENV == METRPO_ENV_HALF_CHEETAH) {
-                float su2 = 0.0f;
-                for (int d = 0; d < NA; ++d) su2 = fmaf(ACT[c * NA + d], ACT[c * NA + d], su2);
-                const float inner = NX[c * NS + 9] - 1e-1f * 0.5f * su2;
-                const float p = (inner >= -10.0f && inner <= 10.0f) ? 1.0f : 0.0f;
-                addG(9, -w * p); cu = w * p * 1e-1f;
-            } else if (ENV == METRPO_ENV_HOPPER) {
-                cu = w * 0.01f;
-#pragma unroll
-                for (int cb = 0; cb < OUT_CB; ++cb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int dim = 16 * cb + 4 * q + r;
-                        if (dim < NS) {
-                            const float v = NX[c * NS + dim];
-                            float gsum = 0.0f;
-                            if (dim == 5) gsum -= w;
-                            if (dim == 0 && 0.45f - v > 0.0f) gsum -= w * 10.0f;
-                            if (dim == 1 && fabsf(v) - 0.2f > 0.0f) gsum += w * 10.0f * (v > 0.0f ? 1.0f : -1.0f);
-                            if (dim >= 2 && fabsf(v) - 100.0f > 0.0f) gsum += w * (v > 0.0f ? 1.0f : -1.0f);
-                            G[cb][r] += gsum;
-                        }
-                    }
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { const int d = 4 * q + r; if (d < NA) gU[r] = cu * ACT[c * NA + d]; }
+            f32x4 G[OUT_CB], gU;
+            env_cost_adjoint_d<ENV, NS, NA>(G, gU, lam, w, NX + c * NS, ACT + c * NA, q);
             // ---- dynamics adjoint: gS = G + state rows of F^T G (the residual identity), gU += action rows ----
             f32x4 gS[OUT_CB];
             adj.run(gS, gU, G, h0, h1);

@@ -182,24 +182,6 @@ static dg_pre_mfma_t dg_pre_mfma_select(const metrpo_ctx* c, size_t* dyn_lds = n
     return nullptr;
 }
 
-__device__ __forceinline__ float dg_cost(int env, int ns, int na, const float* xn, const float* u) {
-    float su2 = 0.0f;
-    for (int d = 0; d < na; ++d) su2 = fmaf(u[d], u[d], su2);
-    switch (env) {
-    case METRPO_ENV_SWIMMER: return -(xn[5] - 1e-2f * (su2 / (float)na));
-    case METRPO_ENV_HALF_CHEETAH: return -fminf(fmaxf(xn[9] - 1e-1f * 0.5f * su2, -10.0f), 10.0f);
-    case METRPO_ENV_ANT: return -(xn[15] - 1e-2f * 0.5f * su2 + 0.05f);
-    case METRPO_ENV_HUMANOID: { const float h = xn[ns - 1] - 1.5f; return h * h + 1e-2f * 1e-3f * su2; }
-    case METRPO_ENV_HOPPER: {
-        float pen = 0.0f;
-        for (int i = 2; i < ns; ++i) pen += fmaxf(fabsf(xn[i]) - 100.0f, 0.0f);
-        return -(xn[5] - 0.01f * 0.5f * su2 - 10.0f * fmaxf(0.45f - xn[0], 0.0f) - 10.0f * fmaxf(fabsf(xn[1]) - 0.2f, 0.0f) - pen);
-    }
-    case METRPO_ENV_SNAKE: return -(xn[7] - 1e-2f * 0.5f * su2);
-    }
-    return 0.0f;
-}
-
 // forward: x' = diff_mean + diff_std * out + x, cost, dones, weights, trajectory
 constexpr int DG_POST_ROWS = 32, DG_POST_THREADS = 256;
 __global__ __launch_bounds__(DG_POST_THREADS) void k_dg_post(ProblemDesc pd, int B, int T, int t, double gpow, const float* __restrict__ norm, DgState st,
@@ -230,9 +212,9 @@ __global__ __launch_bounds__(DG_POST_THREADS) void k_dg_post(ProblemDesc pd, int
     float xn[64];                                                   // ns <= 64 enforced by the launcher
     bool fin = true;
     for (int i = 0; i < ns; ++i) { xn[i] = fmaf(diff_std[i], so[threadIdx.x * lds + i], diff_mean[i]) + st.S[row * ns + i]; fin = fin && isfinite(xn[i]); }
-    const float c = dg_cost(pd.env, ns, na, xn, st.U + row * na);
+    const float c = env_cost(pd.env, ns, na, EnvVec{xn, 1}, EnvVec{st.U + row * na, 1});
     const float dones = st.DONES[row], live = 1.0f - dones;
-    if (pd.env == METRPO_ENV_ANT) st.DONES[row] = fmaxf(dones, ((xn[2] >= 0.2f) && (xn[2] <= 1.0f) && fin) ? 0.0f : 1.0f);
+    if (pd.env == METRPO_ENV_ANT) st.DONES[row] = fmaxf(dones, env_done(pd.env, xn[2], fin) ? 1.0f : 0.0f);
     st.ACC[row] += gpow * (double)(c * live);
     if (WT != nullptr) WT[((size_t)k * T + t) * B + b] = (float)(gpow * (double)live / ((double)B * (double)K));
     for (int i = 0; i < ns; ++i) {
@@ -265,21 +247,8 @@ __global__ void k_dg_mid(ProblemDesc pd, int B, int T, int t, const float* __res
     const float w = WT[((size_t)k * T + t) * B + b];
     float g[64];
     for (int i = 0; i < ns; ++i) g[i] = st.LAM[row * ns + i];
-    float su2 = 0.0f;
-    for (int d = 0; d < na; ++d) su2 = fmaf(u[d], u[d], su2);
-    switch (pd.env) {
-    case METRPO_ENV_SWIMMER: g[5] -= w; break;
-    case METRPO_ENV_HALF_CHEETAH: { const float inner = xn[9] - 1e-1f * 0.5f * su2; if (inner >= -10.0f && inner <= 10.0f) g[9] -= w; break; }
-    case METRPO_ENV_ANT: g[15] -= w; break;
-    case METRPO_ENV_HUMANOID: g[ns - 1] += w * 2.0f * (xn[ns - 1] - 1.5f); break;
-    case METRPO_ENV_HOPPER:
-        g[5] -= w;
-        if (0.45f - xn[0] > 0.0f) g[0] -= w * 10.0f;
-        if (fabsf(xn[1]) - 0.2f > 0.0f) g[1] += w * 10.0f * (xn[1] > 0.0f ? 1.0f : -1.0f);
-        for (int i = 2; i < ns; ++i) if (fabsf(xn[i]) - 100.0f > 0.0f) g[i] += w * (xn[i] > 0.0f ? 1.0f : -1.0f);
-        break;
-    case METRPO_ENV_SNAKE: g[7] -= w; break;
-    }
+    const bool inside = env_clip_inside_at(pd.env, ns, EnvVec{xn, 1}, env_su2(na, EnvVec{u, 1}));
+    env_cost_dx_row(pd.env, ns, EnvVec{xn, 1}, inside, w, [&](int i) -> float& { return g[i]; });
     for (int i = 0; i < ns; ++i) { st.G[row * ns + i] = g[i]; st.DZa[row * ns + i] = diff_std[i] * g[i]; }
 }
 
@@ -311,15 +280,8 @@ __global__ void k_dg_back(ProblemDesc pd, int B, int T, int t, const float* __re
     const float w = active ? WT[((size_t)k * T + t) * B + b] : 0.0f;
     float su2 = 0.0f;
     if (active) for (int d = 0; d < na; ++d) { const float a = st.U[row * na + d]; su2 = fmaf(a, a, su2); }
-    float cu = 0.0f;                                                // d(w cost)/du_d = cu * u_d
-    switch (pd.env) {
-    case METRPO_ENV_SWIMMER: cu = w * 1e-2f * 2.0f / (float)na; break;
-    case METRPO_ENV_HALF_CHEETAH: { const float inner = active ? xn[9] - 1e-1f * 0.5f * su2 : 0.0f; cu = (inner >= -10.0f && inner <= 10.0f) ? w * 1e-1f : 0.0f; break; }
-    case METRPO_ENV_ANT: cu = w * 1e-2f; break;
-    case METRPO_ENV_HUMANOID: cu = w * 2e-5f; break;
-    case METRPO_ENV_HOPPER: cu = w * 0.01f; break;
-    case METRPO_ENV_SNAKE: cu = w * 1e-2f; break;
-    }
+    const bool inside = !active || env_clip_inside_at(pd.env, ns, EnvVec{xn, 1}, su2);
+    const float cu = env_cost_du(pd.env, na, inside, w);          // d(w cost)/du_d = cu * u_d
     const float* dx = DX + row * pd.nin;
     for (int d = 0; d < na; ++d) {
         float gm = 0.0f;

@@ -1,6 +1,7 @@
 // Device-side helpers shared by the generic (VALU) kernels.  gfx950 only.
 #pragma once
 #include "metrpo_internal.h"
+#include "env_model.h"    // the environments' cost, adjoint and termination
 
 #define LOG_MIN_STD (-13.815510557964274f)   // log(1e-6): [rllab] GaussianMLPPolicy(min_std=1e-6)
 #define KL_EPS 1e-8f                         // [rllab] DiagonalGaussian.kl_sym denominator constant
@@ -260,65 +261,6 @@ __device__ __forceinline__ float* net_vjp(const NetDesc& n, const float* __restr
         float* tmp = da; da = db; db = tmp;
     }
     return da;
-}
-
-// ---------------------------------------------------------------------------------------------
-// analytic cost (reward = -cost) and termination; s_next/u accessed through column pointers
-//   envs/com_*_env.py cost_np_vec / is_done -- see include/metrpo.h metrpo_env for file:line
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float env_cost(int env, int ns, int na, const float* xn, const float* u, int LD, int tid) {
-    float su2 = 0.0f;
-    for (int d = 0; d < na; ++d) { const float a = u[d * LD + tid]; su2 = fmaf(a, a, su2); }
-    switch (env) {
-    case METRPO_ENV_SWIMMER: return -(xn[5 * LD + tid] - 1e-2f * (su2 / (float)na));
-    case METRPO_ENV_HALF_CHEETAH: return -fminf(fmaxf(xn[9 * LD + tid] - 1e-1f * 0.5f * su2, -10.0f), 10.0f);
-    case METRPO_ENV_ANT: return -(xn[15 * LD + tid] - 1e-2f * 0.5f * su2 + 0.05f);
-    case METRPO_ENV_HUMANOID: { const float h = xn[(ns - 1) * LD + tid] - 1.5f; return h * h + 1e-2f * 1e-3f * su2; }
-    case METRPO_ENV_HOPPER: {
-        float pen = 0.0f;
-        for (int i = 2; i < ns; ++i) pen += fmaxf(fabsf(xn[i * LD + tid]) - 100.0f, 0.0f);
-        return -(xn[5 * LD + tid] - 0.01f * 0.5f * su2 - 10.0f * fmaxf(0.45f - xn[0 * LD + tid], 0.0f) -
-                 10.0f * fmaxf(fabsf(xn[1 * LD + tid]) - 0.2f, 0.0f) - pen);
-    }
-    case METRPO_ENV_SNAKE: return -(xn[7 * LD + tid] - 1e-2f * 0.5f * su2);
-    }
-    return 0.0f;
-}
-
-// env_cost's adjoint: d(w cost)/du -> gU (written), d(w cost)/dx_next -> added into G.  The BPTT reverse sweep passes the step's weight, the gradient
-// kernels of the scorers w = -w_t for the gradient of the return.
-__device__ __forceinline__ void cost_adjoint(int env, int ns, int na, const float* xn, const float* u, float w, float* gU, float* G, int LD, int tid) {
-    float su2 = 0.0f;
-    for (int d = 0; d < na; ++d) { const float a = u[d * LD + tid]; su2 = fmaf(a, a, su2); }
-    float cu = 0.0f;                                         // gU[d] = cu * u[d]
-    switch (env) {
-    case METRPO_ENV_SWIMMER: G[5 * LD + tid] -= w; cu = w * 1e-2f * 2.0f / (float)na; break;
-    case METRPO_ENV_HALF_CHEETAH: {
-        const float inner = xn[9 * LD + tid] - 1e-1f * 0.5f * su2;
-        const float p = (inner >= -10.0f && inner <= 10.0f) ? 1.0f : 0.0f;       // tf.clip_by_value passes the gradient inside [min, max]
-        G[9 * LD + tid] -= w * p; cu = w * p * 1e-1f; break;
-    }
-    case METRPO_ENV_ANT: G[15 * LD + tid] -= w; cu = w * 1e-2f; break;
-    case METRPO_ENV_HUMANOID: G[(ns - 1) * LD + tid] += w * 2.0f * (xn[(ns - 1) * LD + tid] - 1.5f); cu = w * 2e-5f; break;
-    case METRPO_ENV_HOPPER: {
-        G[5 * LD + tid] -= w; cu = w * 0.01f;
-        if (0.45f - xn[0 * LD + tid] > 0.0f) G[0 * LD + tid] -= w * 10.0f;
-        const float a1 = xn[1 * LD + tid];
-        if (fabsf(a1) - 0.2f > 0.0f) G[1 * LD + tid] += w * 10.0f * (a1 > 0.0f ? 1.0f : -1.0f);
-        for (int i = 2; i < ns; ++i) { const float v = xn[i * LD + tid]; if (fabsf(v) - 100.0f > 0.0f) G[i * LD + tid] += w * (v > 0.0f ? 1.0f : -1.0f); }
-        break;
-    }
-    case METRPO_ENV_SNAKE: G[7 * LD + tid] -= w; cu = w * 1e-2f; break;
-    }
-    for (int d = 0; d < na; ++d) gU[d * LD + tid] = cu * u[d * LD + tid];
-}
-
-__device__ __forceinline__ bool env_is_done(int env, int ns, const float* xn, int LD, int tid) {
-    if (env != METRPO_ENV_ANT) return false;
-    bool finite = true;
-    for (int i = 0; i < ns; ++i) finite = finite && isfinite(xn[i * LD + tid]);
-    const float z = xn[2 * LD + tid];
-    return !((z >= 0.2f) && (z <= 1.0f) && finite);
 }
 
 // block-wide sum of a double over a 1-D block (<= 1024 threads); result valid in thread 0

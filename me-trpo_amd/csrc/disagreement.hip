@@ -17,7 +17,7 @@
 //     also a wait for every older store; placed there it meets only the stores of the tile before).
 //   * edge tile (N % 16 != 0) and skipped rows (d_valid): zero state and zero action in LDS.  Rows >= N are never read from or written to memory (the
 //     index is clamped into the tile's block); a skipped row's loaded values are dropped by a select and zeros are stored for it.
-//   * d_rew_std: env_cost (device_common.h, the function k_rollout_actions calls) on every head's own LDS row, combined like the states.
+//   * d_rew_std: env_cost (env_model.h, the function k_rollout_actions calls) on every head's own LDS row, combined like the states.
 //
 // Generic path (every other shape): metrpo_step's kernel once (one_model, its d_next_all into the caller's buffer or a workspace; s_next, reward and done
 // go to the workspace and are dropped), then k_dis_reduce, one thread per row.
@@ -188,11 +188,11 @@ __global__ void __launch_bounds__(512) k_disagreement(DisK r, int K, const float
             float rstd = 0.0f;
             if (r.rew_std != nullptr) {                                          // r_k = -cost_np_vec(s, clip(a), s'_k) (:601), every head's own next state
                 float rs = 0.0f;
-                for (int k = 0; k < K; ++k) rs += -env_cost(ENV, NS, NA, nxt_all + ((size_t)k * 16 + e) * NSP, ACT + e * NA, 1, 0);
+                for (int k = 0; k < K; ++k) rs += -env_cost(ENV, NS, NA, EnvVec{nxt_all + ((size_t)k * 16 + e) * NSP, 1}, EnvVec{ACT + e * NA, 1});
                 const float rm = rs / fK;
                 float rv = 0.0f;
                 for (int k = 0; k < K; ++k) {
-                    const float d = -env_cost(ENV, NS, NA, nxt_all + ((size_t)k * 16 + e) * NSP, ACT + e * NA, 1, 0) - rm;
+                    const float d = -env_cost(ENV, NS, NA, EnvVec{nxt_all + ((size_t)k * 16 + e) * NSP, 1}, EnvVec{ACT + e * NA, 1}) - rm;
                     rv = fmaf(d, d, rv);
                 }
                 rstd = sqrtf(rv / fK);
@@ -259,10 +259,10 @@ __global__ void __launch_bounds__(256) k_dis_reduce(int env, int ns, int na, int
         float* U = lds + (size_t)threadIdx.x * na;
         for (int d = 0; d < na; ++d) U[d] = fminf(fmaxf(r.act[n * na + d], -1.0f), 1.0f);                        // env_helpers.py:599
         float rs = 0.0f;
-        for (int k = 0; k < K; ++k) rs += -env_cost(env, ns, na, xa + ((size_t)k * N + n) * ns, U, 1, 0);
+        for (int k = 0; k < K; ++k) rs += -env_cost(env, ns, na, EnvVec{xa + ((size_t)k * N + n) * ns, 1}, EnvVec{U, 1});
         const float rm = rs / fK;
         float rv = 0.0f;
-        for (int k = 0; k < K; ++k) { const float d = -env_cost(env, ns, na, xa + ((size_t)k * N + n) * ns, U, 1, 0) - rm; rv = fmaf(d, d, rv); }
+        for (int k = 0; k < K; ++k) { const float d = -env_cost(env, ns, na, EnvVec{xa + ((size_t)k * N + n) * ns, 1}, EnvVec{U, 1}) - rm; rv = fmaf(d, d, rv); }
         r.rew_std[n] = sqrtf(rv / fK);
     }
 }

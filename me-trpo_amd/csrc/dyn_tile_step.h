@@ -193,8 +193,8 @@ __device__ __forceinline__ void tile_rollout(float* lds, const TileRollK& r, int
             }
         act.commit(t + 1);                                                       // the loop's only vmcnt wait
         wave_lds_sync();
-        const float cost = env_cost(ENV, NS, NA, NX + e * NS, ACT + e * NA, 1, 0);
-        const bool dn = env_is_done(ENV, NS, NX + e * NS, 1, 0);
+        const float cost = env_cost(ENV, NS, NA, EnvVec{NX + e * NS, 1}, EnvVec{ACT + e * NA, 1});
+        const bool dn = env_done_scan(ENV, NS, EnvVec{NX + e * NS, 1});
 #pragma unroll
         for (int j = 0; j < NST; ++j) {
             const int i = lane + 64 * j;

@@ -3,6 +3,7 @@
 // beside the nominal ones of MI355X_MICROARCH.md -- `frac` keeps the nominal peak, the stricter denominator.
 #include <algorithm>
 #include "metrpo_internal.h"
+#include "env_model.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -143,5 +144,51 @@ extern "C" int32_t metrpo_set_exclusive(metrpo_ctx* c, int32_t exclusive) {
     if (!c) return METRPO_ENULL;
     c->exclusive = exclusive ? 1 : 0;
     if (c->exclusive) { c->n_cu_sched = 0; (void)sched_cus(c, nullptr); }      // the tenants may have changed: count again, here and not inside the next launch
+    return METRPO_OK;
+}
+
+// ---- metrpo_debug_env_model: the environments' reward model (env_model.h) on its own ----
+// Diagnostics hook (not part of include/metrpo.h; tests/test_gpu_env_model.py, Engine.debug_env_model): ONE launch, one thread per row of caller-owned
+// x_next [N][ns], u [N][na], w [N]: cost [N], done [N], gx [N][ns] = the per-dimension adjoint d(w cost)/dx_next, gx_row [N][ns] = the row form added into
+// zeros, gu [N][na] = d(w cost)/du.  ENV < 0 passes the runtime env as the generic kernels do; the others are the compile-time instantiations.
+struct metrpo_debug_env_model_args {       // mirrored by _lib.DebugEnvModelArgs
+    int32_t env, ns, na, N, compile_time;
+    const float* x; const float* u; const float* w;
+    float* cost; int32_t* done; float* gx; float* gx_row; float* gu;
+};
+template <int ENV>
+__global__ void __launch_bounds__(64) k_debug_env_model(metrpo_debug_env_model_args a) {
+    const int env = (ENV >= 0) ? ENV : a.env, ns = a.ns, na = a.na;
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= a.N) return;
+    const EnvVec x = {a.x + (size_t)n * ns, 1}, u = {a.u + (size_t)n * na, 1};
+    const float w = a.w[n];
+    a.cost[n] = env_cost(env, ns, na, x, u);
+    a.done[n] = env_done_scan(env, ns, x) ? 1 : 0;
+    const bool inside = env_clip_inside_at(env, ns, x, env_su2(na, u));
+    float* gr = a.gx_row + (size_t)n * ns;
+    for (int i = 0; i < ns; ++i) { a.gx[(size_t)n * ns + i] = env_cost_dx(env, ns, i, x(i), inside, w); gr[i] = 0.0f; }
+    env_cost_dx_row(env, ns, x, inside, w, [&](int i) -> float& { return gr[i]; });
+    const float cu = env_cost_du(env, na, inside, w);
+    for (int d = 0; d < na; ++d) a.gu[(size_t)n * na + d] = cu * u(d);
+}
+extern "C" int32_t metrpo_debug_env_model(metrpo_ctx* c, metrpo_debug_env_model_args* a, void* stream) {
+    if (!c || !a) return METRPO_ENULL;
+    auto bad = [&](const char* why) { return set_err(c, METRPO_EINVAL, std::string("debug_env_model: ") + why); };
+    if (!a->x || !a->u || !a->w || !a->cost || !a->done || !a->gx || !a->gx_row || !a->gu) return bad("every pointer must be given");
+    if (a->N < 1 || a->na < 1 || a->env < METRPO_ENV_SWIMMER || a->env > METRPO_ENV_SNAKE) return bad("N and na must be positive, env one of metrpo_env");
+    if (a->ns < 1 || a->ns <= env_key_dim(a->env, a->ns)) return bad("ns must hold the dimensions the environment's cost reads");
+    void (*k)(metrpo_debug_env_model_args) = k_debug_env_model<-1>;
+    if (a->compile_time)
+        switch (a->env) {
+        case METRPO_ENV_SWIMMER: k = k_debug_env_model<METRPO_ENV_SWIMMER>; break;
+        case METRPO_ENV_HALF_CHEETAH: k = k_debug_env_model<METRPO_ENV_HALF_CHEETAH>; break;
+        case METRPO_ENV_ANT: k = k_debug_env_model<METRPO_ENV_ANT>; break;
+        case METRPO_ENV_HOPPER: k = k_debug_env_model<METRPO_ENV_HOPPER>; break;
+        case METRPO_ENV_SNAKE: k = k_debug_env_model<METRPO_ENV_SNAKE>; break;
+        default: return bad("the compile-time instantiations are those of the five 2 x 64 environments");
+        }
+    hipLaunchKernelGGL(k, dim3((a->N + 63) / 64), dim3(64), 0, (hipStream_t)stream, *a);
+    HIP_TRY(c, hipGetLastError());
     return METRPO_OK;
 }

@@ -7,7 +7,7 @@
 //   * one workgroup = one tile of 16 envs, walked through all T steps, on the shared head of dyn_head_mfma.h (layout and arithmetic are described there).
 //   * the head's weight fragments are register-resident for the whole loop (swimmer 92, Ant 132 registers), biases, normalisers' source map and the
 //     tile's state live in LDS; the state is [env][ns], the layout of one row of d_obs, so a row is one linear coalesced store.
-//   * cost and is_done are device_common.h's env_cost / env_is_done on the LDS rows (the functions metrpo_step's kernel calls).
+//   * cost and is_done are env_model.h's env_cost / env_done_scan on the LDS rows (the functions metrpo_step's kernel calls).
 //   * the ONLY global load of the step loop is the tile's action block of the NEXT step (16 * na contiguous floats of d_actions, <= 2 per lane), issued
 //     at the top of a step and read behind that step's matrix instructions into the other of two LDS action buffers -- IN FRONT of the step's stores.
 //     The vector-memory counter is in order, so the wait for a load is also a wait for every older store (rollout_coop_kernel.h, DRAWS): placed

@@ -142,7 +142,7 @@
         }
     };
     constexpr bool LOCAL_REWARD = (ENV == METRPO_ENV_SWIMMER || ENV == METRPO_ENV_HALF_CHEETAH || ENV == METRPO_ENV_SNAKE);
-    constexpr int RDIM = (ENV == METRPO_ENV_SWIMMER) ? 5 : (ENV == METRPO_ENV_HALF_CHEETAH) ? 9 : 7;   // reward reads next_state[RDIM]
+    constexpr int RDIM = env_key_dim(ENV, NS);                             // reward reads next_state[RDIM]
     // One workgroup per CU and a small state (one col-block): the policy weight fragments and biases of this lane stay in registers for
     // the whole launch -- the policy chain is the step's critical path before B0 and otherwise starts with an LDS round trip.  (Only wave 0 uses them.)
     constexpr bool PWREG = SOLO && ONE && OUT_CB == 1;
@@ -512,10 +512,7 @@
         else if (LOCAL_REWARD) {
             // the reward reads ONE next-state dim: the lane that owns it (q == RDIM/4 of col-block 0) evaluates and stores it from
             // registers -- no LDS round trip; is_done is the horizon only (uniform)
-            const float xr = nx[RDIM / 16][RDIM & 3];
-            if (ENV == METRPO_ENV_SWIMMER) cost = -(xr - 1e-2f * (su2 / (float)NA));
-            else if (ENV == METRPO_ENV_HALF_CHEETAH) cost = -fminf(fmaxf(xr - 1e-1f * 0.5f * su2, -10.0f), 10.0f);
-            else cost = -(xr - 1e-2f * 0.5f * su2);
+            cost = env_cost_terms(ENV, NA, nx[RDIM / 16][RDIM & 3], 0.0f, 0.0f, su2, 0.0f);
             dn = (ts >= r.H);
             if (reww() && q == ((RDIM & 15) >> 2) && active) { (r.rew + trow)[ub] = -cost; (r.done + trow)[ub] = dn ? 1 : 0; (r.tpath + trow)[ub] = ts - 1; }
         } else {
@@ -526,21 +523,18 @@
                     const int dim = 16 * cb + 4 * q + rr;
                     if (dim < NS) {
                         NX[e * NS + dim] = nx[cb][rr];
-                        if (ENV == METRPO_ENV_HOPPER && dim >= 2) pen += fmaxf(fabsf(nx[cb][rr]) - 100.0f, 0.0f);
+                        if (ENV == METRPO_ENV_HOPPER && dim >= 2) pen += env_hopper_pen_term(nx[cb][rr]);
                         if (ENV == METRPO_ENV_ANT) fin &= isfinite(nx[cb][rr]) ? 1 : 0;
                     }
                 }
             wave_lds_sync();
             const float* xn = NX + e * NS;
-            if (ENV == METRPO_ENV_HOPPER) {
-                pen = xor_sum(pen);
-                cost = -(xn[5] - 0.01f * 0.5f * su2 - 10.0f * fmaxf(0.45f - xn[0], 0.0f) - 10.0f * fmaxf(fabsf(xn[1]) - 0.2f, 0.0f) - pen);
-            } else if (ENV == METRPO_ENV_ANT) {
-                cost = -(xn[15] - 1e-2f * 0.5f * su2 + 0.05f);
+            if (ENV == METRPO_ENV_HOPPER) pen = xor_sum(pen);
+            cost = env_cost_terms(ENV, NA, xn[env_key_dim(ENV, NS)], xn[0], xn[1], su2, pen);
+            if (ENV == METRPO_ENV_ANT) {
                 int f2 = fin & __shfl_xor(fin, 16, 64);
                 f2 &= __shfl_xor(f2, 32, 64);
-                const float zc = xn[2];
-                dn = !((zc >= 0.2f) && (zc <= 1.0f) && (f2 != 0));
+                dn = env_done(ENV, xn[2], f2 != 0);
             }
             dn = dn || (ts >= r.H);
             if (reww() && q == 0 && active) { (r.rew + trow)[ub] = -cost; (r.done + trow)[ub] = dn ? 1 : 0; (r.tpath + trow)[ub] = ts - 1; }

@@ -528,25 +528,15 @@ __global__ void __launch_bounds__(256) k_big_post(ProblemDesc pd, RolloutK r, in
     }
     if (i >= ns) v = 0.0f;
     // per-env quantities
-    const int ki = (pd.env == METRPO_ENV_SWIMMER || pd.env == METRPO_ENV_HOPPER) ? 5 : (pd.env == METRPO_ENV_HALF_CHEETAH) ? 9
-                   : (pd.env == METRPO_ENV_ANT) ? 15 : (pd.env == METRPO_ENV_SNAKE) ? 7 : 0;
-    const float key = grp(v, ki), h0v = grp(v, 0), h1v = grp(v, 1), zc = grp(v, 2), last = grp(v, ns - 1);
+    const float key = grp(v, env_key_dim(pd.env, ns)), h0v = grp(v, 0), h1v = grp(v, 1), zc = grp(v, 2);
     float pen = 0.0f;
-    if (pd.env == METRPO_ENV_HOPPER) for (int j = 2; j < ns; ++j) pen += fmaxf(fabsf(grp(v, j)) - 100.0f, 0.0f);
+    if (pd.env == METRPO_ENV_HOPPER) for (int j = 2; j < ns; ++j) pen += env_hopper_pen_term(grp(v, j));
     int fin = isfinite(v) ? 1 : 0;                               // all-finite over the env's dims (lanes beyond ns hold 0)
 #pragma unroll
     for (int o = 1; o < DL; o <<= 1) fin &= __shfl_xor(fin, o, DL);
-    float cost = 0.0f;
-    switch (pd.env) {
-    case METRPO_ENV_SWIMMER: cost = -(key - 1e-2f * (su2 / (float)na)); break;
-    case METRPO_ENV_HALF_CHEETAH: cost = -fminf(fmaxf(key - 1e-1f * 0.5f * su2, -10.0f), 10.0f); break;
-    case METRPO_ENV_ANT: cost = -(key - 1e-2f * 0.5f * su2 + 0.05f); break;
-    case METRPO_ENV_HUMANOID: cost = (last - 1.5f) * (last - 1.5f) + 1e-2f * 1e-3f * su2; break;
-    case METRPO_ENV_HOPPER: cost = -(key - 0.01f * 0.5f * su2 - 10.0f * fmaxf(0.45f - h0v, 0.0f) - 10.0f * fmaxf(fabsf(h1v) - 0.2f, 0.0f) - pen); break;
-    case METRPO_ENV_SNAKE: cost = -(key - 1e-2f * 0.5f * su2); break;
-    }
+    const float cost = env_cost_terms(pd.env, na, key, h0v, h1v, su2, pen);
     int ts = st.ts[bc] + 1;
-    bool dn = (pd.env == METRPO_ENV_ANT) ? !((zc >= 0.2f) && (zc <= 1.0f) && (fin != 0)) : false;
+    bool dn = env_done(pd.env, zc, fin != 0);
     dn = dn || (ts >= r.H);
     int cur = st.cur_model[bc];
     if (env_ok && i == 0) { r.rew[tb] = -cost; r.done[tb] = dn ? 1 : 0; r.tpath[tb] = ts - 1; }

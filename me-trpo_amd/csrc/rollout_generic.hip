@@ -154,8 +154,8 @@ __global__ void k_step(ProblemDesc pd, const float* __restrict__ dynp, const flo
     dyn_heads_select(pd, dynp, norm, e, sam_mode, sel, noise_col, true, next_all, B, b, active, LD, tid);
     if (!active) return;
     for (int i = 0; i < pd.ns; ++i) s_next[(size_t)b * pd.ns + i] = e.NEXT[i * LD + tid];
-    reward[b] = -env_cost(pd.env, pd.ns, pd.na, e.NEXT, e.U, LD, tid);           // env_helpers.py:601
-    done[b] = env_is_done(pd.env, pd.ns, e.NEXT, LD, tid) ? 1 : 0;               // :603
+    reward[b] = -env_cost(pd.env, pd.ns, pd.na, env_col(e.NEXT, LD, tid), env_col(e.U, LD, tid));           // env_helpers.py:601
+    done[b] = env_done_scan(pd.env, pd.ns, env_col(e.NEXT, LD, tid)) ? 1 : 0;               // :603
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -225,8 +225,8 @@ __global__ void k_rollout_generic(ProblemDesc pd, RolloutK r, const float* __res
         }
         if (active) for (int i = 0; i < ns; ++i) r.obs[tb * ns + i] = e.S[i * LD + tid];
         dyn_heads_select(pd, dynp, norm, e, r.sam_mode, sel, noise_col, r.eval_all != 0, nullptr, r.B, b, active, LD, tid);
-        const float rew = -env_cost(pd.env, ns, na, e.NEXT, e.U, LD, tid);
-        bool dn = env_is_done(pd.env, ns, e.NEXT, LD, tid);
+        const float rew = -env_cost(pd.env, ns, na, env_col(e.NEXT, LD, tid), env_col(e.U, LD, tid));
+        bool dn = env_done_scan(pd.env, ns, env_col(e.NEXT, LD, tid));
         dn = dn || (ts >= r.H);                                               // env_helpers.py:604
         if (active) { r.rew[tb] = rew; r.done[tb] = dn ? 1 : 0; r.tpath[tb] = ts - 1; }
         // ---- reset(dones) (env_helpers.py:585-595): new state from the pool, new cur_model_idx ----
@@ -270,10 +270,10 @@ __global__ void k_validation(ProblemDesc pd, const float* __restrict__ dynp, con
         float* m = mlp_col(pd.pol, theta, e.S, e.A, e.Bq, LD, tid);
         for (int d = 0; d < na; ++d) e.U[d * LD + tid] = fminf(fmaxf(m[d * LD + tid], -1.0f), 1.0f);   // :128
         dyn_heads_select(pd, dynp, norm, e, METRPO_SAM_EPS_RAND, model, nullptr, false, nullptr, Bv, b, true, LD, tid);
-        float c = env_cost(pd.env, ns, na, e.NEXT, e.U, LD, tid);
+        float c = env_cost(pd.env, ns, na, env_col(e.NEXT, LD, tid), env_col(e.U, LD, tid));
         if (pd.env == METRPO_ENV_ANT) {                       // cost_tf(..., dones) then dones update (:134-137)
             c *= (1.0f - dones);
-            dones = fmaxf(dones, env_is_done(pd.env, ns, e.NEXT, LD, tid) ? 1.0f : 0.0f);
+            dones = fmaxf(dones, env_done_scan(pd.env, ns, env_col(e.NEXT, LD, tid)) ? 1.0f : 0.0f);
         }
         if (active) acc += g * (double)c;
         g *= gamma;

@@ -187,26 +187,19 @@ __global__ void __launch_bounds__(512) k_rollout_mfma(RolloutK r, int K, const f
                 const int dim = 16 * cb + 4 * q + rr;
                 if (dim < NS) {
                     NX[e * NS + dim] = nx[cb][rr];
-                    if (ENV == METRPO_ENV_HOPPER && dim >= 2) pen += fmaxf(fabsf(nx[cb][rr]) - 100.0f, 0.0f);
+                    if (ENV == METRPO_ENV_HOPPER && dim >= 2) pen += env_hopper_pen_term(nx[cb][rr]);
                     if (ENV == METRPO_ENV_ANT) fin &= isfinite(nx[cb][rr]) ? 1 : 0;
                 }
             }
         wave_lds_sync();
         const float* xn = NX + e * NS;
-        float cost = 0.0f;
+        if (ENV == METRPO_ENV_HOPPER) pen = xor_sum(pen);
+        const float cost = env_cost_terms(ENV, NA, xn[env_key_dim(ENV, NS)], xn[0], xn[1], su2, pen);
         bool dn = false;
-        if (ENV == METRPO_ENV_SWIMMER) cost = -(xn[5] - 1e-2f * (su2 / (float)NA));
-        else if (ENV == METRPO_ENV_HALF_CHEETAH) cost = -fminf(fmaxf(xn[9] - 1e-1f * 0.5f * su2, -10.0f), 10.0f);
-        else if (ENV == METRPO_ENV_SNAKE) cost = -(xn[7] - 1e-2f * 0.5f * su2);
-        else if (ENV == METRPO_ENV_HOPPER) {
-            pen = xor_sum(pen);
-            cost = -(xn[5] - 0.01f * 0.5f * su2 - 10.0f * fmaxf(0.45f - xn[0], 0.0f) - 10.0f * fmaxf(fabsf(xn[1]) - 0.2f, 0.0f) - pen);
-        } else if (ENV == METRPO_ENV_ANT) {
-            cost = -(xn[15] - 1e-2f * 0.5f * su2 + 0.05f);
+        if (ENV == METRPO_ENV_ANT) {
             int f2 = fin & __shfl_xor(fin, 16, 64);
             f2 &= __shfl_xor(f2, 32, 64);
-            const float zc = xn[2];
-            dn = !((zc >= 0.2f) && (zc <= 1.0f) && (f2 != 0));
+            dn = env_done(ENV, xn[2], f2 != 0);
         }
         dn = dn || (ts >= r.H);                                               // :604
         if (wave == 0 && q == 0 && active) { r.rew[tb] = -cost; r.done[tb] = dn ? 1 : 0; r.tpath[tb] = ts - 1; }

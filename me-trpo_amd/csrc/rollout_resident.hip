@@ -502,22 +502,10 @@ template <int NS> __device__ __forceinline__ float res_pol_x(int q, const float 
                 (4 * s_ + 3 < NS) ? s[(4 * s_ + 3 < NS) ? 4 * s_ + 3 : 0] : 0.0f);
 }
 
-// Cost of the state reached v (every dim, in registers) under the clipped action's sum of squares su2 (env_helpers.py:601), for both post roles.
-// device_common.h's env_cost is the same expression on memory rows: it sums u from memory itself, behind the wait for the partial sums, where the post roles
-// form su2 while the compute workgroups are busy, and it would send v[] through memory.  Ant: without the dones factor of the validation mode.
+// Cost of the state reached v (every dim, in registers) under the clipped action's sum of squares su2 (env_helpers.py:601), for both post roles: the post
+// roles form su2 while the compute workgroups are busy, and v[] never goes through memory.  Ant: without the dones factor of the validation mode.
 template <int ENV, int NS> __device__ __forceinline__ float res_cost(const float (&v)[NS], float su2) {
-    constexpr int NA = Cfg<ENV, 64, 32>::NA;
-    float cost = 0.0f;
-    if constexpr (ENV == METRPO_ENV_SWIMMER) cost = -(v[5] - 1e-2f * (su2 / (float)NA));
-    else if constexpr (ENV == METRPO_ENV_HALF_CHEETAH) cost = -fminf(fmaxf(v[9] - 1e-1f * 0.5f * su2, -10.0f), 10.0f);
-    else if constexpr (ENV == METRPO_ENV_HOPPER) {
-        float pen = 0.0f;
-#pragma unroll
-        for (int j = 2; j < NS; ++j) pen += fmaxf(fabsf(v[j]) - 100.0f, 0.0f);
-        cost = -(v[5] - 0.01f * 0.5f * su2 - 10.0f * fmaxf(0.45f - v[0], 0.0f) - 10.0f * fmaxf(fabsf(v[1]) - 0.2f, 0.0f) - pen);
-    } else if constexpr (ENV == METRPO_ENV_SNAKE) cost = -(v[7] - 1e-2f * 0.5f * su2);
-    else if constexpr (ENV == METRPO_ENV_ANT) cost = -(v[15] - 1e-2f * 0.5f * su2 + 0.05f);
-    return cost;
+    return env_cost_su2(ENV, NS, Cfg<ENV, 64, 32>::NA, [&](int i) { return v[i]; }, su2);
 }
 
 // The four lanes (c, q = 0..3) of env c hold the env's whole state in registers (the same values): nothing on the path from "last partial
@@ -737,7 +725,7 @@ __device__ __forceinline__ void resident_post(const ProblemDesc& pd, const Rollo
             bool fin = true;
 #pragma unroll
             for (int i = 0; i < NS; ++i) fin = fin && isfinite(v[i]);
-            dn = dn_h || !((v[2] >= 0.2f) && (v[2] <= 1.0f) && fin);
+            dn = dn_h || env_done(ENV, v[2], fin);
         }
         const int next_model = dn ? reset_model : cur_model;
         if (active && q == 0) { r.rew[tb] = -cost; r.done[tb] = dn ? 1 : 0; r.tpath[tb] = ts_new - 1; }
@@ -880,7 +868,7 @@ __device__ __forceinline__ void resident_post_det(const ProblemDesc& pd, const R
             bool fin = true;
 #pragma unroll
             for (int i = 0; i < NS; ++i) fin = fin && isfinite(v[i]);
-            dones[j] = fmaxf(dones[j], ((v[2] >= 0.2f) && (v[2] <= 1.0f) && fin) ? 0.0f : 1.0f);
+            dones[j] = fmaxf(dones[j], env_done(ENV, v[2], fin) ? 1.0f : 0.0f);
         }
         if (active[j]) acc[j] += gpow * (double)cost;
 #pragma unroll

@@ -1,7 +1,7 @@
 // The per-candidate return of metrpo_score_actions and metrpo_score_policy_actions (include/metrpo.h): what score_actions.hip's and
 // score_policy_actions.hip's fused kernels carry per lane and what k_sact_reduce applies to a stored trajectory.
 // Below it: what the generic kernels of the two gradient files (score_actions_grad.hip, score_policy_actions_grad.hip) share: their LDS columns (a net's hidden layers, its
-// vector-Jacobian product and the cost adjoint are device_common.h's).
+// vector-Jacobian product are device_common.h's, the cost adjoint is env_model.h's).
 #pragma once
 #include "device_common.h"
 

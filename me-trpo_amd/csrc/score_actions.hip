@@ -6,7 +6,7 @@
 // with a sink that sums instead of storing.
 //   * one wave owns one (16-candidate tile, head) pair for all T steps, on the shared head of dyn_head_mfma.h: weight fragments register-resident
 //     (swimmer 92, Ant 132 registers), biases and the tile's state in the wave's LDS, every activation in registers, no barrier.  The statements of a
-//     step -- normalise, three layers, de-normalise, env_cost / env_is_done on the LDS rows -- are that kernel's own, so s' and r carry its bits.
+//     step -- normalise, three layers, de-normalise, env_cost / env_done_scan (env_model.h) on the LDS rows -- are that kernel's own, so s' and r carry its bits.
 //   * PACKING: one wave per workgroup on a (tiles, K) grid.  The (tile, head) pairs share nothing but read-only inputs, so a workgroup of several waves
 //     would buy no exchange and no reuse; it would only tie the waves' placement together (a workgroup starts when ALL its waves fit one CU, and its LDS
 //     and registers are held until the slowest tile of it ends).  One-wave workgroups let the dispatcher fill whatever SIMD has the registers free, which

@@ -2,7 +2,7 @@
 //   R = -sum_t w_t cost_tf(s_t, clip(a_t), s_t+1),   w_t = gamma^t alive_t        (metrpo_score_actions' ret: model_based_rl.py:122-141 under supplied actions)
 // with respect to the UNCLIPPED candidate actions a_t (d_grad [K][T][B][na]) and the start state (d_lam0 [K][B][ns]).  Reverse recursion from lambda_T = 0:
 //   G = lambda_t+1 - w_t dc/dx_next;  gU = -w_t dc/du + (action rows of F^T G);  lambda_t = G + (state rows of F^T G);  grad_t = gU gated by -1 <= a_t <= 1
-// The conventions are the BPTT sweep's (bptt.hip): relu'(h) = [h > 0], cost_adjoint's expressions, the alive mask a constant of the differentiation.
+// The conventions are the BPTT sweep's (bptt.hip): relu'(h) = [h > 0], env_model.h's adjoint terms, the alive mask a constant of the differentiation.
 //
 // Fused path: TWO stream-ordered launches of k_sagr<ENV, MODE> (the second launch sees the first one's stores without any in-kernel fence), per chunk of
 // candidates.  This is k_det_mfma's structure (bptt_mfma.hip) with the policy chain removed; the departures from it are marked (*).
@@ -22,7 +22,7 @@
 //   gathered per row (a tile may straddle two start states).
 //
 // Generic path (every other shape, and force_generic): k_sagr_gen_fwd / k_sagr_gen_bwd, one thread per (candidate, head) with activations in LDS
-// columns (sact_sum.h: GradBufs; device_common.h: net_hidden, net_vjp, cost_adjoint) -- k_bptt_forward / k_bptt_backward (bptt.hip) with the policy removed; block size by
+// columns (sact_sum.h: GradBufs; device_common.h: net_hidden, net_vjp; env_model.h: env_cost_adjoint) -- k_bptt_forward / k_bptt_backward (bptt.hip) with the policy removed; block size by
 // lds_block_size (metrpo_internal.h).  Same outputs, workspace, chunking.
 //
 // Terminal value (metrpo_set_terminal_value; sact_sum.h: TermVal): the forward sweeps add gamma^T alive_T V(s_T) to the sum behind the loop (score_actions.hip's
@@ -208,46 +208,8 @@ k_sagr(SagrK r, const float* __restrict__ dynp, const float* __restrict__ norm) 
             head.layer0(h0, lds + L::O_BD0, xin, ReluBits());
             head.layer1(h1, lds + L::O_BD1, h0, ReluBits());
             // ---- cost adjoint of the RETURN in D layout: G = lambda_t+1 - w dc/dx_next (state dims), gU = -w dc/du (action dims) ----
-            const float wn = -w;
-            f32x4 G[OUT_CB], gU = {0.f, 0.f, 0.f, 0.f};
-            float cu = 0.0f;
-#pragma unroll
-            for (int cb = 0; cb < OUT_CB; ++cb) G[cb] = lam[cb];
-            auto addG = [&](int dim, float v) {                  // add v to the lane/register that owns state dim `dim`
-#pragma unroll
-                for (int cb = 0; cb < OUT_CB; ++cb)
-#pragma unroll
-                    for (int rr = 0; rr < 4; ++rr) if (16 * cb + 4 * q + rr == dim) G[cb][rr] += v;
-            };
-            if (ENV == METRPO_ENV_SWIMMER) { addG(5, -wn); cu = wn * 1e-2f * 2.0f / (float)NA; }
-            else if (ENV == METRPO_ENV_SNAKE) { addG(7, -wn); cu = wn * 1e-2f; }
-            else if (ENV == METRPO_ENV_ANT) { addG(15, -wn); cu = wn * 1e-2f; }
-            else if (ENV == METRPO_ENV_HALF_CHEETAH) {
-                float su2 = 0.0f;
-                for (int d = 0; d < NA; ++d) su2 = fmaf(ACT[c * NA + d], ACT[c * NA + d], su2);
-                const float inner = NX[c * NS + 9] - 1e-1f * 0.5f * su2;
-                const float p = (inner >= -10.0f && inner <= 10.0f) ? 1.0f : 0.0f;
-                addG(9, -wn * p); cu = wn * p * 1e-1f;
-            } else if (ENV == METRPO_ENV_HOPPER) {
-                cu = wn * 0.01f;
-#pragma unroll
-                for (int cb = 0; cb < OUT_CB; ++cb)
-#pragma unroll
-                    for (int rr = 0; rr < 4; ++rr) {
-                        const int dim = 16 * cb + 4 * q + rr;
-                        if (dim < NS) {
-                            const float v = NX[c * NS + dim];
-                            float gsum = 0.0f;
-                            if (dim == 5) gsum -= wn;
-                            if (dim == 0 && 0.45f - v > 0.0f) gsum -= wn * 10.0f;
-                            if (dim == 1 && fabsf(v) - 0.2f > 0.0f) gsum += wn * 10.0f * (v > 0.0f ? 1.0f : -1.0f);
-                            if (dim >= 2 && fabsf(v) - 100.0f > 0.0f) gsum += wn * (v > 0.0f ? 1.0f : -1.0f);
-                            G[cb][rr] += gsum;
-                        }
-                    }
-            }
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) { const int d = 4 * q + rr; if (d < NA) gU[rr] = cu * ACT[c * NA + d]; }
+            f32x4 G[OUT_CB], gU;
+            env_cost_adjoint_d<ENV, NS, NA>(G, gU, lam, -w, NX + c * NS, ACT + c * NA, q);
             // ---- the head's adjoint chains, the clip gate (tf.clip_by_value passes the gradient inside [min, max]) and the store ----
             f32x4 gS[OUT_CB];
             adj.run(gS, gU, G, h0, h1);
@@ -309,8 +271,8 @@ __global__ void k_sagr_gen_fwd(ProblemDesc pd, SagrK r, const float* __restrict_
         for (int d = 0; d < na; ++d) e.X[(ns + d) * LD + tid] = (e.U[d * LD + tid] - in_mean[ns + d]) / in_std[ns + d];
         float* out = mlp_col(pd.dyn, pk, e.X + pd.n_drop * LD, e.GA, e.GB, LD, tid);
         for (int i = 0; i < ns; ++i) e.XN[i * LD + tid] = fmaf(diff_std[i], out[i * LD + tid], diff_mean[i]) + e.S[i * LD + tid];
-        const float cst = env_cost(pd.env, ns, na, e.XN, e.U, LD, tid);
-        const bool dn = env_is_done(pd.env, ns, e.XN, LD, tid);
+        const float cst = env_cost(pd.env, ns, na, env_col(e.XN, LD, tid), env_col(e.U, LD, tid));
+        const bool dn = env_done_scan(pd.env, ns, env_col(e.XN, LD, tid));
         const float w = acc.step(-cst, dn, r.gamma, r.stop);
         if (active) {
             r.WT[((size_t)k * r.T + t) * r.n + lc] = w;
@@ -365,7 +327,7 @@ __global__ void k_sagr_gen_bwd(ProblemDesc pd, SagrK r, const float* __restrict_
         // ---- adjoints of the return: G = lambda_t+1 - w dc/dx_next; gU_cost = -w dc/du (in X's place: the normalised input is dead) ----
         float* G = e.LAM;
         float* gUc = e.X;
-        cost_adjoint(pd.env, ns, na, e.XN, e.U, -w, gUc, G, LD, tid);
+        env_cost_adjoint(pd.env, ns, na, e.XN, e.U, -w, gUc, G, LD, tid);
         for (int i = 0; i < ns; ++i) e.GA[i * LD + tid] = diff_std[i] * G[i * LD + tid];
         const float* da = net_vjp(dn, pk, e.DH, e.GA, e.GB, LD, tid);
         // da = adjoint of the (dropped) normalised input [nin].  Action part -> the gated gradient; state part: residual + normaliser -> lambda_t

@@ -9,7 +9,7 @@
 //     wave's LDS (pol_wave_floats<>), every activation in registers, no barrier.
 //   * a step: policy mean from ST (two tanh layers on the dependent chain), a = mean (+ noise, fmaf with sigma: sigma = 1 gives mean + noise exactly),
 //     the clipped action into the tile's ACT rows IN PLACE of the noise it was formed from (every lane overwrites only what it read), then
-//     DynWaveHead::step, env_cost / env_is_done on the LDS rows and SactSum -- the statements of tile_rollout's one-head body (dyn_tile_step.h), so fed
+//     DynWaveHead::step, env_cost / env_done_scan (env_model.h) on the LDS rows and SactSum -- the statements of tile_rollout's one-head body (dyn_tile_step.h), so fed
 //     the same clipped action the step carries k_score_actions' bits (d_act_out replayed through metrpo_score_actions reproduces ret).
 //   * the ONLY global load of the step loop is the tile's noise block of the NEXT step, issued at the top of a step and committed UNCLIPPED behind
 //     that step's matrix instructions into the other of two LDS buffers (NoiseTile: ActTile's prefetch, its own commit).  d_noise NULL: a variant with
@@ -101,8 +101,8 @@ __global__ void __launch_bounds__(64) k_score_policy_actions(SpolK r, const floa
             }
         if (NOISE) nz.commit(t + 1);                           // the loop's only wait for a load
         wave_lds_sync();
-        const float cost = env_cost(ENV, NS, NA, NX + e * NS, ACT + e * NA, 1, 0);
-        const bool dn = env_is_done(ENV, NS, NX + e * NS, 1, 0);
+        const float cost = env_cost(ENV, NS, NA, EnvVec{NX + e * NS, 1}, EnvVec{ACT + e * NA, 1});
+        const bool dn = env_done_scan(ENV, NS, EnvVec{NX + e * NS, 1});
 #pragma unroll
         for (int j = 0; j < NST; ++j) {
             const int i = lane + 64 * j;

@@ -22,7 +22,7 @@
 //   forward sweep computes rows of a later chunk that share its last tile and drops them, so chunking changes no bit.
 //
 // Generic path (every other shape, and force_generic): k_spag_gen_fwd / k_spag_gen_bwd, one thread per (candidate, head) with activations in LDS
-// columns -- k_sagr_gen_fwd / k_sagr_gen_bwd with the policy in the loop (both on sact_sum.h's GradBufs and device_common.h's net_hidden, net_vjp and cost_adjoint): the forward is k_policy_actions' and k_step's arithmetic (rollout_generic.hip;
+// columns -- k_sagr_gen_fwd / k_sagr_gen_bwd with the policy in the loop (both on sact_sum.h's GradBufs and device_common.h's net_hidden and net_vjp and env_model.h's env_cost_adjoint): the forward is k_policy_actions' and k_step's arithmetic (rollout_generic.hip;
 // sigma by __expf as there), so ret, len and act_out carry the bits of metrpo_score_policy_actions' generic path; the reverse is k_bptt_backward's policy
 // VJP (bptt.hip) behind the clip gate.  Block size by lds_block_size (metrpo_internal.h).  Same outputs, workspace, chunking.
 //
@@ -126,8 +126,8 @@ __global__ void __launch_bounds__(64) k_spag_fwd(SpagK r, const float* __restric
             }
         if (NOISE) nz.commit(t + 1);
         wave_lds_sync();
-        const float cost = env_cost(ENV, NS, NA, NX + e * NS, ACT + e * NA, 1, 0);
-        const bool dn = env_is_done(ENV, NS, NX + e * NS, 1, 0);
+        const float cost = env_cost(ENV, NS, NA, EnvVec{NX + e * NS, 1}, EnvVec{ACT + e * NA, 1});
+        const bool dn = env_done_scan(ENV, NS, EnvVec{NX + e * NS, 1});
 #pragma unroll
         for (int j = 0; j < NST; ++j) {
             const int i = lane + 64 * j;
@@ -265,47 +265,9 @@ __global__ void __launch_bounds__(256, 2) k_spag_bwd(SpagK r, const float* __res
         for (int s = 0; s < C::NIN_KS; ++s) xin[s] = in.get(ST, NS, ACT, c, s);
         head.layer0(h0, lds + L::O_BD0, xin, ReluBits());
         head.layer1(h1, lds + L::O_BD1, h0, ReluBits());
-        // ---- cost adjoint of the RETURN in D layout (k_sagr's statements): G = lambda_t+1 - w dc/dx_next (state dims), gU = -w dc/du (action dims) ----
-        const float wn = -w;
-        f32x4 G[OUT_CB], gU = {0.f, 0.f, 0.f, 0.f};
-        float cu = 0.0f;
-#pragma unroll
-        for (int cb = 0; cb < OUT_CB; ++cb) G[cb] = lam[cb];
-        auto addG = [&](int dim, float v) {                  // add v to the lane/register that owns state dim `dim`
-#pragma unroll
-            for (int cb = 0; cb < OUT_CB; ++cb)
-#pragma unroll
-                for (int rr = 0; rr < 4; ++rr) if (16 * cb + 4 * q + rr == dim) G[cb][rr] += v;
-        };
-        if (ENV == METRPO_ENV_SWIMMER) { addG(5, -wn); cu = wn * 1e-2f * 2.0f / (float)NA; }
-        else if (ENV == METRPO_ENV_SNAKE) { addG(7, -wn); cu = wn * 1e-2f; }
-        else if (ENV == METRPO_ENV_ANT) { addG(15, -wn); cu = wn * 1e-2f; }
-        else if (ENV == METRPO_ENV_HALF_CHEETAH) {
-            float su2 = 0.0f;
-            for (int d = 0; d < NA; ++d) su2 = fmaf(ACT[c * NA + d], ACT[c * NA + d], su2);
-            const float inner = NX[c * NS + 9] - 1e-1f * 0.5f * su2;
-            const float p = (inner >= -10.0f && inner <= 10.0f) ? 1.0f : 0.0f;
-            addG(9, -wn * p); cu = wn * p * 1e-1f;
-        } else if (ENV == METRPO_ENV_HOPPER) {
-            cu = wn * 0.01f;
-#pragma unroll
-            for (int cb = 0; cb < OUT_CB; ++cb)
-#pragma unroll
-                for (int rr = 0; rr < 4; ++rr) {
-                    const int dim = 16 * cb + 4 * q + rr;
-                    if (dim < NS) {
-                        const float v = NX[c * NS + dim];
-                        float gsum = 0.0f;
-                        if (dim == 5) gsum -= wn;
-                        if (dim == 0 && 0.45f - v > 0.0f) gsum -= wn * 10.0f;
-                        if (dim == 1 && fabsf(v) - 0.2f > 0.0f) gsum += wn * 10.0f * (v > 0.0f ? 1.0f : -1.0f);
-                        if (dim >= 2 && fabsf(v) - 100.0f > 0.0f) gsum += wn * (v > 0.0f ? 1.0f : -1.0f);
-                        G[cb][rr] += gsum;
-                    }
-                }
-        }
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) { const int d = 4 * q + rr; if (d < NA) gU[rr] = cu * ACT[c * NA + d]; }
+        // ---- cost adjoint of the RETURN in D layout: G = lambda_t+1 - w dc/dx_next (state dims), gU = -w dc/du (action dims) ----
+        f32x4 G[OUT_CB], gU;
+        env_cost_adjoint_d<ENV, NS, NA>(G, gU, lam, -w, NX + c * NS, ACT + c * NA, q);
         // ---- the head's adjoint chains, the clip gate on the head's own a_t and the store ----
         f32x4 gS[OUT_CB];
         adj.run(gS, gU, G, h0, h1);
@@ -387,8 +349,8 @@ __global__ void k_spag_gen_fwd(ProblemDesc pd, SpagK r, const float* __restrict_
         for (int d = 0; d < na; ++d) e.X[(ns + d) * LD + tid] = (e.U[d * LD + tid] - in_mean[ns + d]) / in_std[ns + d];
         float* out = mlp_col(pd.dyn, pk, e.X + pd.n_drop * LD, e.GA, e.GB, LD, tid);
         for (int i = 0; i < ns; ++i) e.XN[i * LD + tid] = fmaf(diff_std[i], out[i * LD + tid], diff_mean[i]) + e.S[i * LD + tid];
-        const float cst = env_cost(pd.env, ns, na, e.XN, e.U, LD, tid);
-        const bool dn = env_is_done(pd.env, ns, e.XN, LD, tid);
+        const float cst = env_cost(pd.env, ns, na, env_col(e.XN, LD, tid), env_col(e.U, LD, tid));
+        const bool dn = env_done_scan(pd.env, ns, env_col(e.XN, LD, tid));
         const float w = acc.step(-cst, dn, r.gamma, r.stop);
         if (active) {
             r.WT[((size_t)k * r.T + t) * r.n + lc] = w;
@@ -445,7 +407,7 @@ __global__ void k_spag_gen_bwd(ProblemDesc pd, SpagK r, const float* __restrict_
         // ---- adjoints of the return: G = lambda_t+1 - w dc/dx_next; gU_cost = -w dc/du (in X's place: the normalised input is dead) ----
         float* G = e.LAM;
         float* gUc = e.X;
-        cost_adjoint(pd.env, ns, na, e.XN, e.U, -w, gUc, G, LD, tid);
+        env_cost_adjoint(pd.env, ns, na, e.XN, e.U, -w, gUc, G, LD, tid);
         for (int i = 0; i < ns; ++i) e.GA[i * LD + tid] = diff_std[i] * G[i * LD + tid];
         float* da = net_vjp(dn, pk, e.DH, e.GA, e.GB, LD, tid);
         float* db = (da == e.GA) ? e.GB : e.GA;

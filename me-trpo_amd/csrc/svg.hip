@@ -148,46 +148,12 @@ __global__ void k_svg_finish(ProblemDesc pd, const float* __restrict__ norm, con
 }
 
 // ---- stage B: the scan ----------------------------------------------------------------------------------------------------------------------------
-// d cost(x_next = s, u = a) / d column c of [s | a]: cost_adjoint's expressions (bptt.hip) with w = 1.  sa: the step's [s | a] in LDS
+// d cost(x_next = s, u = a) / d column c of [s | a]: the cost adjoint's per-dimension terms (env_model.h) at w = 1.  sa: the step's [s | a] in LDS.
+// (Ant's columns would now carry Ant's terms where they were 0: svg is undefined on Ant and svg_check (api.hip) refuses it, so no launch reaches them.)
 __device__ __forceinline__ float svg_cost_grad(int env, int ns, int na, const float* sa, int c) {
-    const float* u = sa + ns;
-    if (c >= ns) {
-        const float a = u[c - ns];
-        switch (env) {
-        case METRPO_ENV_SWIMMER: return (1e-2f * 2.0f / (float)na) * a;
-        case METRPO_ENV_HALF_CHEETAH: {
-            float su2 = 0.0f;
-            for (int d = 0; d < na; ++d) su2 = fmaf(u[d], u[d], su2);
-            const float inner = sa[9] - 1e-1f * 0.5f * su2;
-            return (inner >= -10.0f && inner <= 10.0f) ? 1e-1f * a : 0.0f;
-        }
-        case METRPO_ENV_HUMANOID: return 2e-5f * a;
-        case METRPO_ENV_HOPPER: return 0.01f * a;
-        case METRPO_ENV_SNAKE: return 1e-2f * a;
-        }
-        return 0.0f;
-    }
-    const float v = sa[c];
-    switch (env) {
-    case METRPO_ENV_SWIMMER: return (c == 5) ? -1.0f : 0.0f;
-    case METRPO_ENV_HALF_CHEETAH: {
-        if (c != 9) return 0.0f;
-        float su2 = 0.0f;
-        for (int d = 0; d < na; ++d) su2 = fmaf(u[d], u[d], su2);
-        const float inner = sa[9] - 1e-1f * 0.5f * su2;
-        return (inner >= -10.0f && inner <= 10.0f) ? -1.0f : 0.0f;
-    }
-    case METRPO_ENV_HUMANOID: return (c == ns - 1) ? 2.0f * (v - 1.5f) : 0.0f;
-    case METRPO_ENV_HOPPER: {
-        float g = (c == 5) ? -1.0f : 0.0f;
-        if (c == 0) { if (0.45f - v > 0.0f) g -= 10.0f; }
-        else if (c == 1) { if (fabsf(v) - 0.2f > 0.0f) g += 10.0f * (v > 0.0f ? 1.0f : -1.0f); }
-        else if (fabsf(v) - 100.0f > 0.0f) g += (v > 0.0f ? 1.0f : -1.0f);
-        return g;
-    }
-    case METRPO_ENV_SNAKE: return (c == 7) ? -1.0f : 0.0f;
-    }
-    return 0.0f;
+    const EnvVec x = {sa, 1}, u = {sa + ns, 1};
+    const bool inside = env_clip_inside_at(env, ns, x, (env == METRPO_ENV_HALF_CHEETAH) ? env_su2(na, u) : 0.0f);
+    return (c >= ns) ? env_cost_du(env, na, inside, 1.0f) * u(c - ns) : env_cost_dx(env, ns, c, x(c), inside, 1.0f);
 }
 
 // One wave per rollout.  A step's operands -- F_t [ns][nsa] | Pi_t [na][ns] | s_t | a_t, E floats -- are staged in LDS; lane l holds elements

@@ -761,6 +761,26 @@ class Engine(object):
         self._chk(lib.metrpo_debug_gemm_bf16(self._ctx, C.byref(a), self._stream()))
         return dict((n, int(getattr(a, 'o_' + n))) for n in self.BF16_GEMM_FORM_FIELDS)
 
+    def debug_env_model(self, env, x_next, u, w, compile_time=False):
+        """Diagnostics: ONE launch that evaluates the reward model (csrc/env_model.h) of environment `env` (a name of _lib.ENV_IDS, any engine) on
+        float32 device tensors x_next [N][ns], u [N][na], w [N], for tests/test_gpu_env_model.py.  compile_time picks the kernel instantiated on
+        the environment (the five 2 x 64 environments) instead of the one that takes it at run time.  -> dict(cost [N], done [N] int32,
+        gx [N][ns] = d(w cost)/dx_next dimension by dimension, gx_row = the same in the row form added into zeros, gu [N][na] = d(w cost)/du)."""
+        for t in (x_next, u, w):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device
+        N, ns = x_next.shape
+        na = u.shape[1]
+        assert u.shape[0] == N and tuple(w.shape) == (N,)
+        out = dict(cost=torch.empty(N, dtype=torch.float32, device=self.device), done=torch.empty(N, dtype=torch.int32, device=self.device),
+                   gx=torch.empty_like(x_next), gx_row=torch.empty_like(x_next), gu=torch.empty_like(u))
+        a = _lib.DebugEnvModelArgs()
+        a.env, a.ns, a.na, a.N, a.compile_time = _lib.ENV_IDS[env], ns, na, N, int(bool(compile_time))
+        a.x, a.u, a.w = x_next.data_ptr(), u.data_ptr(), w.data_ptr()
+        for name, t in out.items():
+            setattr(a, name, t.data_ptr())
+        self._chk(lib.metrpo_debug_env_model(self._ctx, C.byref(a), self._stream()))
+        return out
+
     def last_bf16_layers(self):
         """Diagnostics: the column tile (64 or 128) of every dynamics-layer GEMM of the last bf16 rollout's steps, as the host noted it when it
         enqueued them; [] before the first bf16 rollout."""
